@@ -29,6 +29,11 @@ come from a fixed SplitMix64 stream instead of a Groestl transcript (host-side p
 scope).
 
 value = (elements of all multilinears of the global instance) * K / wall seconds  [elems/s].
+
+A plain run sets up, warms up, times the K steps and prints the line (with the sumcheck verifier's equations checked on
+the last step's transcript).  Everything else it can report runs only with `--full`: the instrumented pass behind
+`roofline` and `kernels`, the copy ceiling, the other exchanges (`alt_exchange`), the claim-group leg and the CPU
+baseline.  `--dump-outputs DIR` writes what the last timed step handed its caller (dump_outputs below).
 """
 import argparse
 import json
@@ -77,18 +82,168 @@ def transcript_digest(coeffs, finals):
     return h.hexdigest()
 
 
+def dump_outputs(path, coeffs, finals):
+    """Writes the transcript of one step as path/round_coeffs.npy, shape (rounds, 3, 128): the coefficients of every round
+    polynomial, and path/final_evals.npy, shape (m, 128): the final evaluations of the multilinears.  A GF(2^128) element is
+    stored as its 128 bits, least significant first, each 0.0 or 1.0 in float32: exact, and two transcripts that differ in
+    any bit differ by 1 in some entry."""
+    import numpy as np
+
+    def bits(vals):
+        raw = np.frombuffer(b"".join(int(v).to_bytes(16, "little") for v in vals), dtype=np.uint8)
+        return np.unpackbits(raw, bitorder="little").reshape(-1, 128).astype(np.float32)
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "round_coeffs.npy"), bits([c for rc in coeffs for c in rc]).reshape(len(coeffs), -1, 128))
+    np.save(os.path.join(path, "final_evals.npy"), bits(finals))
+
+
+def roofline_figures(args, hal, prof, n_vars, m, d_in, scratch):
+    # ---- roofline of the dominant kernel, from hipEvent pairs recorded around every launch in the timed region
+    # Algorithmic bytes (SURVEY.md section 8d; DESIGN.md section 5), per launch at r remaining variables:
+    #   round evaluation alone  reads 16*m*2^r                                  (round 0 only)
+    #   fold + next evaluation  reads 16*m*2^r, writes 8*m*2^r = 24*m*2^r       (rounds 0..n-2, one fused kernel;
+    #                           the evaluation consumes the folded values on chip -- no bytes of its own)
+    #   fold alone              24*m*2^r                                        (the last fold, r = 1)
+    # The ABI decides per launch which kernel runs; the launch counts per class say what actually ran.
+    # Classes (include/binius_amd.h BN_PROF_*), as rocprof lists the kernel symbols:
+    #   round_eval_mfma  k_roundeval_fp4_ws / k_roundeval_fp4 (>= 2^20 points: FP4 matrix path) / k_roundeval_mfma (int8; BN_FP4=0)   round 0 on the matrix cores
+    #                                                                          fold_eval_mfma   k_foldeval_mfma_fp4 (whole tiles, >= 2 per CU) / k_foldeval_mfma (the rest down to 2 tiles per CU)
+    #   round_eval       k_roundeval9       round 0, 9-lane VALU kernel        fold_eval        k_foldeval9<2>   (the next size down)
+    #   fold             k_extrapolate_line / k_fold_publish (last fold)       fold_eval_small  k_foldeval9_small (one workgroup per batch: latency-shaped)
+    #                                                                          tail             k_foldeval_tail  (resident; opt-in)
+    #                                                                          fold_eval8       k_foldeval8      (two rounds per launch: the small rounds)
+    K = args.steps
+    counts = {c: prof[c][1] // K if K else 0 for c in prof}
+    # the fused launches of a step, largest round first: mfma, then k_foldeval9<2>, then small, then tail
+    order = ["fold_eval_mfma", "fold_eval", "fold_eval_small"]
+    r_hi = n_vars  # r of the next fused launch (pre-fold size 2^r)
+    fused_bytes = {}
+    for c in order:
+        f = counts.get(c, 0)
+        fused_bytes[c] = sum(24 * m * (1 << r) for r in range(r_hi - f + 1, r_hi + 1)) * K
+        r_hi -= f
+    # two-round launches (k_foldeval8, kernels_foldeval8.hip): the first folds once (pre-fold size 2^r_hi), every later one
+    # folds twice -- 2^(r_hi - 1), 2^(r_hi - 3), ... -- each reads its arrays once and writes half of them: 24*m*n_in
+    f8 = counts.get("fold_eval8", 0)
+    fused_bytes["fold_eval8"] = sum(24 * m * (1 << r) for r in ([r_hi] + [r_hi - 1 - 2 * i for i in range(f8 - 1)] if f8 else []) if r >= 2) * K
+    fused = sum(counts.get(c, 0) for c in order) + counts.get("tail", 0) + f8 > 0
+    tl_bytes = sum(24 * m * (1 << r) for r in range(2, r_hi + 1)) * K if counts.get("tail", 0) else 0
+    n_re = counts.get("round_eval", 0) + counts.get("round_eval_mfma", 0)
+    if fused:
+        re_bytes_each = 16 * m * (1 << n_vars)  # round 0 (and round 0 of the residual instance: negligible)
+        fold_bytes = 24 * m * 2 * K
+    else:
+        re_bytes_each = None
+        fold_bytes = sum(24 * (1 << r) for r in range(1, n_vars + 1)) * m * K
+    # round 0 has 2^(n_vars - 1) points: from 2^20 on it runs on the FP4 matrix path (csrc/kernels_roundeval_mfma.hip fp4_applies)
+    fp4_round0 = os.environ.get("BN_FP4", "1")[:1] != "0" and n_vars - 1 >= int(os.environ.get("BN_FP4_MIN_LOG2", "20"))
+    label = {
+        "round_eval_mfma": "k_roundeval_fp4(round_eval)" if fp4_round0 else "k_roundeval_mfma(round_eval)",
+        "round_eval": "k_roundeval9(round_eval)",
+        "fold": "k_extrapolate_line(fold)",
+        "fold_eval_mfma": "k_foldeval_mfma(fold+round_eval)",
+        "fold_eval": "k_foldeval9(fold+round_eval)",
+        "fold_eval_small": "k_foldeval9_small(fold+round_eval, <= 2 batches per CU)",
+        "fold_eval8": "k_foldeval8(two rounds per launch: 1-2 folds + the eight quarter sums; the small rounds)",
+        "tail": "k_foldeval_tail(resident, rounds <= 2^12)",
+    }
+    kernels = {}
+    for c in ("round_eval_mfma", "round_eval"):
+        ms_c, cnt_c = prof[c]
+        if cnt_c:
+            if fused:
+                # the large launch of the class is round 0 of the local instance; residual-instance launches are bytes-free here
+                bytes_c = re_bytes_each * K if (c == "round_eval_mfma" or counts.get("round_eval_mfma", 0) == 0) else 0
+            else:
+                bytes_c = sum(16 * m * (1 << r) for r in range(1, n_vars + 1)) * K
+            kernels[label[c]] = (bytes_c, ms_c, cnt_c)
+    kernels[label["fold"]] = (fold_bytes, prof["fold"][0], prof["fold"][1])
+    for c in order + ["fold_eval8"]:
+        if prof[c][1]:
+            kernels[label[c]] = (fused_bytes[c], prof[c][0], prof[c][1])
+    if prof["tail"][1]:
+        kernels[label["tail"]] = (tl_bytes, prof["tail"][0], prof["tail"][1])
+    dom = max(kernels, key=lambda k: kernels[k][1])
+    b, ms, cnt = kernels[dom]
+    achieved = b / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+    roofline = {
+        "bound": "hbm",
+        "kernel": dom,
+        "achieved": round(achieved, 2),
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBS, 4),
+        "traffic": None,
+        "traffic_source": None,
+        "launches": cnt,
+        "avg_launch_ms": round(ms / cnt, 5) if cnt else None,
+        "algorithmic_bytes_per_launch": b // cnt if cnt else None,
+    }
+    # HBM traffic of the dominant kernel: PMC counters cannot be collected inside this process, so the
+    # value comes from the committed counters-only rocprofv3 passes OF THIS COMMAND (tools/pmc_bench.sh ->
+    # profiles/r06/bench_pmc.json: FETCH_SIZE x 2 (gfx950 correction) + WRITE_SIZE, average bytes per launch
+    # of the kernel symbol, with the commit of the build it was taken on); null for a workload it does not hold
+    try:
+        pmc = json.load(open(os.path.join(ROOT, PMC_FILE)))
+        sym = dom.split("(")[0]
+        ent = pmc["workloads"].get("n_vars_local=%d,m=%d" % (n_vars, m), {}).get(sym)
+        if ent and pmc.get("csrc_sha16") != csrc_sha16():
+            roofline["traffic_source"] = "%s is stale: taken on kernel sources %s, this tree is %s" % (PMC_FILE, pmc.get("csrc_sha16"), csrc_sha16())
+        elif ent:
+            roofline["traffic"] = ent["traffic_bytes_per_launch"]
+            roofline["traffic_source"] = "%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command at build %s; average bytes per launch of %s)" % (
+                PMC_FILE, pmc.get("build", "?"), sym)
+    except (OSError, KeyError, ValueError):
+        pass
+    # the streaming ceiling this box reaches: a device-to-device copy of one multilinear (read + write), next to
+    # the 8 TB/s spec the fractions above are quoted against (SURVEY.md section 8d: report both)
+    try:
+        cp_src, cp_dst = d_in[0], scratch.slice(0, min(scratch.len, d_in[0].len))
+        cp_n = cp_dst.len
+        best = None
+        for _ in range(4):
+            hal.sync()
+            hal.timer_begin()
+            hal.copy_d2d(cp_src.slice(0, cp_n), cp_dst)
+            ms_cp = hal.timer_end_ms()
+            best = ms_cp if best is None else min(best, ms_cp)
+        copy_gbs = 2 * 16 * cp_n / (best * 1e-3) / 1e9
+        roofline["measured_copy_GBps"] = round(copy_gbs, 1)
+        roofline["frac_of_measured_copy"] = round(achieved / copy_gbs, 4) if copy_gbs > 0 else None
+    except Exception as ex:  # noqa: BLE001 -- the ceiling is a side measurement
+        roofline["measured_copy_GBps"] = None
+        print("[bench] copy ceiling not measured: %r" % (ex,), file=sys.stderr)
+    per_kernel = {
+        k: {
+            "GBps": round(v[0] / (v[1] * 1e-3) / 1e9, 2) if v[1] > 0 else None,
+            "frac": round(v[0] / (v[1] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if v[1] > 0 else None,
+            "total_ms": round(v[1], 3),
+            "launches": v[2],
+        }
+        for k, v in kernels.items()
+    }
+    return roofline, per_kernel
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--n-vars", type=int, default=28, help="variables of the GLOBAL instance (28: north star; 24: BASELINE configs[1])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-claim-groups", action="store_true", help="skip the k = 4, m = 8 claim-group leg reported beside the headline")
-    ap.add_argument("--no-prof", action="store_true", help="diagnostic: no per-launch hipEvents in the timed region (no roofline block)")
-    ap.add_argument("--no-alt-exchange", action="store_true", help="do not time the shared-memory exchange beside the RCCL one")
+    ap.add_argument("--full", action="store_true", help="also measure what is reported beside the headline: the instrumented pass "
+                    "(roofline, kernels), the copy ceiling, the other exchanges, the claim-group leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's round polynomials and final evaluations "
+                    "to DIR/*.npy (128 bits per field element as float32 0/1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-claim-groups", action="store_true", help="with --full: skip the claim-group leg reported beside the headline")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: no instrumented pass (no roofline block)")
+    ap.add_argument("--no-alt-exchange", action="store_true", help="with --full: do not time the other exchanges beside the default one")
     ap.add_argument("--cpu-n-vars", type=int, default=0, help="size of the CPU baseline sample (0 = auto)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     # `python bench.py --gpus N` run bare (no launcher, WORLD_SIZE unset) must still be an N-rank run: the process replaces itself
     # with the launcher the driver would have used (one rank per GPU, rendezvous on 127.0.0.1), so that a scaling run cannot
@@ -348,13 +503,15 @@ def main():
     # ---- timed region: exactly K steps, barrier + synchronize on both sides, MAX over ranks
     elapsed = timed(plan, args.steps)
     get_coeffs, get_finals = plan.round_coeffs, plan.final_evals
-    # ---- the same K steps once more with a hipEvent pair around every kernel launch (bn_prof_*), for
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, get_coeffs(), get_finals())
+    # ---- (--full) the same K steps once more with a hipEvent pair around every kernel launch (bn_prof_*), for
     # the roofline block.  The events cost about 5 us per launch on the stream, which is instrumentation,
     # not the workload -- so they stay out of `value`; the instrumented pass's own wall time is reported
     # next to it as ms_per_step_instrumented.
     prof = {k: (0.0, 0) for k in hal.PROF_CLASSES}
     elapsed_prof = None
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         barrier()
         hal.prof_begin()
         t2 = time.perf_counter()
@@ -366,7 +523,7 @@ def main():
     # ---- the other exchanges, same steps, and the local shard with no exchange at all (diagnostic): reported beside the
     # default, never as `value`.  exchange_us_per_round = (step with the exchange - step of the shard alone) / rounds.
     alt = None
-    if dist is not None and not args.no_alt_exchange:
+    if dist is not None and args.full and not args.no_alt_exchange:
         alt = []
         solo = make_plan("solo")
         solo.run()
@@ -417,130 +574,7 @@ def main():
     value = total_elems * args.steps / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
 
-    # ---- roofline of the dominant kernel, from hipEvent pairs recorded around every launch in the timed region
-    # Algorithmic bytes, per launch at r remaining variables:
-    #   round evaluation alone  reads 16*m*2^r                                  (round 0 only)
-    #   fold + next evaluation  reads 16*m*2^r, writes 8*m*2^r = 24*m*2^r       (rounds 0..n-2, one fused kernel;
-    #                           the evaluation consumes the folded values on chip -- no bytes of its own)
-    #   fold alone              24*m*2^r                                        (the last fold, r = 1)
-    # The ABI decides per launch which kernel runs; the launch counts per class say what actually ran.
-    # Classes (include/binius_amd.h BN_PROF_*), as rocprof lists the kernel symbols:
-    #   round_eval_mfma  k_roundeval_fp4_ws / k_roundeval_fp4 (>= 2^20 points: FP4 matrix path) / k_roundeval_mfma (int8; BN_FP4=0)   round 0 on the matrix cores
-    #                                                                          fold_eval_mfma   k_foldeval_mfma_fp4 (whole tiles, >= 2 per CU) / k_foldeval_mfma (the rest down to 2 tiles per CU)
-    #   round_eval       k_roundeval9       round 0, 9-lane VALU kernel        fold_eval        k_foldeval9<2>   (the next size down)
-    #   fold             k_extrapolate_line / k_fold_publish (last fold)       fold_eval_small  k_foldeval9_small (one workgroup per batch: latency-shaped)
-    #                                                                          tail             k_foldeval_tail  (resident; opt-in)
-    #                                                                          fold_eval8       k_foldeval8      (two rounds per launch: the small rounds)
-    K = args.steps
-    counts = {c: prof[c][1] // K if K else 0 for c in prof}
-    # the fused launches of a step, largest round first: mfma, then k_foldeval9<2>, then small, then tail
-    order = ["fold_eval_mfma", "fold_eval", "fold_eval_small"]
-    r_hi = n_vars  # r of the next fused launch (pre-fold size 2^r)
-    fused_bytes = {}
-    for c in order:
-        f = counts.get(c, 0)
-        fused_bytes[c] = sum(24 * m * (1 << r) for r in range(r_hi - f + 1, r_hi + 1)) * K
-        r_hi -= f
-    # two-round launches (k_foldeval8, kernels_foldeval8.hip): the first folds once (pre-fold size 2^r_hi), every later one
-    # folds twice -- 2^(r_hi - 1), 2^(r_hi - 3), ... -- each reads its arrays once and writes half of them: 24*m*n_in
-    f8 = counts.get("fold_eval8", 0)
-    fused_bytes["fold_eval8"] = sum(24 * m * (1 << r) for r in ([r_hi] + [r_hi - 1 - 2 * i for i in range(f8 - 1)] if f8 else []) if r >= 2) * K
-    fused = sum(counts.get(c, 0) for c in order) + counts.get("tail", 0) + f8 > 0
-    tl_bytes = sum(24 * m * (1 << r) for r in range(2, r_hi + 1)) * K if counts.get("tail", 0) else 0
-    n_re = counts.get("round_eval", 0) + counts.get("round_eval_mfma", 0)
-    if fused:
-        re_bytes_each = 16 * m * (1 << n_vars)  # round 0 (and round 0 of the residual instance: negligible)
-        fold_bytes = 24 * m * 2 * K
-    else:
-        re_bytes_each = None
-        fold_bytes = sum(24 * (1 << r) for r in range(1, n_vars + 1)) * m * K
-    # round 0 has 2^(n_vars - 1) points: from 2^20 on it runs on the FP4 matrix path (csrc/kernels_roundeval_mfma.hip fp4_applies)
-    fp4_round0 = os.environ.get("BN_FP4", "1")[:1] != "0" and n_vars - 1 >= int(os.environ.get("BN_FP4_MIN_LOG2", "20"))
-    label = {
-        "round_eval_mfma": "k_roundeval_fp4(round_eval)" if fp4_round0 else "k_roundeval_mfma(round_eval)",
-        "round_eval": "k_roundeval9(round_eval)",
-        "fold": "k_extrapolate_line(fold)",
-        "fold_eval_mfma": "k_foldeval_mfma(fold+round_eval)",
-        "fold_eval": "k_foldeval9(fold+round_eval)",
-        "fold_eval_small": "k_foldeval9_small(fold+round_eval, <= 2 batches per CU)",
-        "fold_eval8": "k_foldeval8(two rounds per launch: 1-2 folds + the eight quarter sums; the small rounds)",
-        "tail": "k_foldeval_tail(resident, rounds <= 2^12)",
-    }
-    kernels = {}
-    for c in ("round_eval_mfma", "round_eval"):
-        ms_c, cnt_c = prof[c]
-        if cnt_c:
-            if fused:
-                # the large launch of the class is round 0 of the local instance; residual-instance launches are bytes-free here
-                bytes_c = re_bytes_each * K if (c == "round_eval_mfma" or counts.get("round_eval_mfma", 0) == 0) else 0
-            else:
-                bytes_c = sum(16 * m * (1 << r) for r in range(1, n_vars + 1)) * K
-            kernels[label[c]] = (bytes_c, ms_c, cnt_c)
-    kernels[label["fold"]] = (fold_bytes, prof["fold"][0], prof["fold"][1])
-    for c in order + ["fold_eval8"]:
-        if prof[c][1]:
-            kernels[label[c]] = (fused_bytes[c], prof[c][0], prof[c][1])
-    if prof["tail"][1]:
-        kernels[label["tail"]] = (tl_bytes, prof["tail"][0], prof["tail"][1])
-    dom = max(kernels, key=lambda k: kernels[k][1])
-    b, ms, cnt = kernels[dom]
-    achieved = b / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-    roofline = {
-        "bound": "hbm",
-        "kernel": dom,
-        "achieved": round(achieved, 2),
-        "peak": HBM_PEAK_GBS,
-        "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBS, 4),
-        "traffic": None,
-        "traffic_source": None,
-        "launches": cnt,
-        "avg_launch_ms": round(ms / cnt, 5) if cnt else None,
-        "algorithmic_bytes_per_launch": b // cnt if cnt else None,
-    }
-    # HBM traffic of the dominant kernel: PMC counters cannot be collected inside this process, so the
-    # value comes from the committed counters-only rocprofv3 passes OF THIS COMMAND (tools/pmc_bench.sh ->
-    # profiles/r06/bench_pmc.json: FETCH_SIZE x 2 (gfx950 correction) + WRITE_SIZE, average bytes per launch
-    # of the kernel symbol, with the commit of the build it was taken on); null for a workload it does not hold
-    try:
-        pmc = json.load(open(os.path.join(ROOT, PMC_FILE)))
-        sym = dom.split("(")[0]
-        ent = pmc["workloads"].get("n_vars_local=%d,m=%d" % (n_vars, m), {}).get(sym)
-        if ent and pmc.get("csrc_sha16") != csrc_sha16():
-            roofline["traffic_source"] = "%s is stale: taken on kernel sources %s, this tree is %s" % (PMC_FILE, pmc.get("csrc_sha16"), csrc_sha16())
-        elif ent:
-            roofline["traffic"] = ent["traffic_bytes_per_launch"]
-            roofline["traffic_source"] = "%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command at build %s; average bytes per launch of %s)" % (
-                PMC_FILE, pmc.get("build", "?"), sym)
-    except (OSError, KeyError, ValueError):
-        pass
-    # the streaming ceiling this box reaches: a device-to-device copy of one multilinear (read + write), next to
-    # the 8 TB/s spec the fractions above are quoted against (report both)
-    try:
-        cp_src, cp_dst = d_in[0], scratch.slice(0, min(scratch.len, d_in[0].len))
-        cp_n = cp_dst.len
-        best = None
-        for _ in range(4):
-            hal.sync()
-            hal.timer_begin()
-            hal.copy_d2d(cp_src.slice(0, cp_n), cp_dst)
-            ms_cp = hal.timer_end_ms()
-            best = ms_cp if best is None else min(best, ms_cp)
-        copy_gbs = 2 * 16 * cp_n / (best * 1e-3) / 1e9
-        roofline["measured_copy_GBps"] = round(copy_gbs, 1)
-        roofline["frac_of_measured_copy"] = round(achieved / copy_gbs, 4) if copy_gbs > 0 else None
-    except Exception as ex:  # noqa: BLE001 -- the ceiling is a side measurement
-        roofline["measured_copy_GBps"] = None
-        print("[bench] copy ceiling not measured: %r" % (ex,), file=sys.stderr)
-    per_kernel = {
-        k: {
-            "GBps": round(v[0] / (v[1] * 1e-3) / 1e9, 2) if v[1] > 0 else None,
-            "frac": round(v[0] / (v[1] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if v[1] > 0 else None,
-            "total_ms": round(v[1], 3),
-            "launches": v[2],
-        }
-        for k, v in kernels.items()
-    }
+    roofline, per_kernel = roofline_figures(args, hal, prof, n_vars, m, d_in, scratch) if args.full else (None, None)
 
     out = {
         "metric": "GF(2^128) sumcheck-fold elems/sec + achieved HBM GB/s (% of roofline)",
@@ -642,7 +676,7 @@ def main():
                           "rounds_on_the_host": (cnt["hosted_evals"] - c_before["hosted_evals"]) // 3, "plain_fold_launches": (cnt["prefolds"] + cnt["flushed_folds"] - c_before["prefolds"] - c_before["flushed_folds"]) // 3},
         }
 
-    if rank == 0 and world == 1 and dist is None and not args.no_claim_groups:
+    if args.full and rank == 0 and world == 1 and dist is None and not args.no_claim_groups:
         out["claim_groups"] = {}
         for name, gk, gn_vars in (("k4_m8", 4, min(24, n_global)), ("k50_m100_keccak_width", 50, min(22, n_global))):
             try:
@@ -654,7 +688,7 @@ def main():
     # Reported value = the OPTIMIZED port (oracle/fastcpu_ref.c: arithmetic in the isomorphic POLYVAL field with
     # PCLMULQDQ, OpenMP over all cores -- BASELINE.md section 2's "best available host ISA"), on the full
     # workload when that takes seconds; the scalar CpuLayer-style port is timed beside it on a bounded sample.
-    if rank == 0 and world == 1 and dist is None and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and dist is None and not args.no_cpu_baseline:
         import oracle  # the CPU ports being timed (the only use of oracle/ in this file)
 
         # host cores this process may actually use: affinity mask, capped by the cgroup CPU quota (this pool's

@@ -40,7 +40,7 @@ def test_bench_two_and_four_ranks_on_one_gpu(n_ranks, exchange):
     transcript."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n_ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), "bench.py", "--gpus", str(n_ranks), "--steps", "2", "--warmup", "1", "--n-vars", "17",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = _run(cmd, {"BN_ALL_ON_GPU0": "1", "BN_PG_BACKEND": "gloo", "BN_EXCHANGE": exchange})
     assert r["n_gpus"] == n_ranks and r["verifier_check"] is True
     assert (" -- " not in r["config"]["sharding"]), "the requested exchange fell back: " + r["config"]["sharding"]

@@ -11,15 +11,15 @@ BUILD=$(cat $R/tools/.build_id 2>/dev/null || python -c "import bench; print(ben
 tools/pmc_bench.sh $BUILD 28 24 > $O/pmc_bench.log 2>&1
 cp $R/gpurun_out/bench_pmc.json $O/bench_pmc.json
 mkdir -p $R/profiles/r06; cp $R/gpurun_out/bench_pmc.json $R/profiles/r06/bench_pmc.json
-python bench.py > $O/bench_n28.json 2> $O/bench_n28.stderr
-python bench.py --n-vars 24 --steps 20 --warmup 3 > $O/bench_n24.json 2> $O/bench_n24.stderr
-python bench.py --n-vars 25 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n25_one_shard_of_eight.json 2>/dev/null
-python bench.py --n-vars 20 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n20.json 2>/dev/null
-BN_HOST_TAIL=0 python bench.py --n-vars 24 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n24_BN_HOST_TAIL_0.json 2>/dev/null
-BN_HOST_TAIL=0 python bench.py --n-vars 25 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n25_BN_HOST_TAIL_0.json 2>/dev/null
-BN_HOST_TAIL=0 python bench.py --n-vars 20 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n20_BN_HOST_TAIL_0.json 2>/dev/null
-BN_TWO_ROUND=0 python bench.py --n-vars 24 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n24_BN_TWO_ROUND_0.json 2>/dev/null
-BN_TWO_ROUND=0 python bench.py --n-vars 25 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n25_BN_TWO_ROUND_0.json 2>/dev/null
+python bench.py --full > $O/bench_n28.json 2> $O/bench_n28.stderr
+python bench.py --full --n-vars 24 --steps 20 --warmup 3 > $O/bench_n24.json 2> $O/bench_n24.stderr
+python bench.py --full --n-vars 25 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n25_one_shard_of_eight.json 2>/dev/null
+python bench.py --full --n-vars 20 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n20.json 2>/dev/null
+BN_HOST_TAIL=0 python bench.py --full --n-vars 24 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n24_BN_HOST_TAIL_0.json 2>/dev/null
+BN_HOST_TAIL=0 python bench.py --full --n-vars 25 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n25_BN_HOST_TAIL_0.json 2>/dev/null
+BN_HOST_TAIL=0 python bench.py --full --n-vars 20 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n20_BN_HOST_TAIL_0.json 2>/dev/null
+BN_TWO_ROUND=0 python bench.py --full --n-vars 24 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n24_BN_TWO_ROUND_0.json 2>/dev/null
+BN_TWO_ROUND=0 python bench.py --full --n-vars 25 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_n25_BN_TWO_ROUND_0.json 2>/dev/null
 # ---- round 6: the keccak width (claim groups at 50 / 64 / 175 claims), the replay of config 4's HAL traffic
 { python tools/bench_piop.py claims --n-vars 22 --k 50 --steps 5 --group 1
   python tools/bench_piop.py claims --n-vars 22 --k 64 --steps 5 --group 1
@@ -82,14 +82,14 @@ python tools/bench_hal.py > $O/hal.jsonl 2>&1
 { for n in 20 16; do python tools/bench_zerocheck_cubic.py --n-vars $n; BN_HAL_COEF=0 python tools/bench_zerocheck_cubic.py --n-vars $n; done; } > $O/zerocheck_cubic.jsonl 2>/dev/null
 tools/trace_cmd.sh final/trace_cubic python tools/bench_hal_cubic.py --n-vars 24 --reps 2 > /dev/null 2>&1
 cp $O/trace_cubic/per_launch.jsonl $O/hal_cubic_n24_per_launch.jsonl; rm -rf $O/trace_cubic
-tools/trace_bench.sh final/trace_n28 --n-vars 28 --steps 3 --warmup 1 --no-cpu-baseline --no-claim-groups > /dev/null 2>&1
-tools/trace_bench.sh final/trace_n24 --n-vars 24 --steps 5 --warmup 2 --no-cpu-baseline --no-claim-groups > /dev/null 2>&1
+tools/trace_bench.sh final/trace_n28 --full --n-vars 28 --steps 3 --warmup 1 --no-cpu-baseline --no-claim-groups > /dev/null 2>&1
+tools/trace_bench.sh final/trace_n24 --full --n-vars 24 --steps 5 --warmup 2 --no-cpu-baseline --no-claim-groups > /dev/null 2>&1
 for t in trace_n28 trace_n24; do cp $O/$t/kernel_stats.csv $O/bench_${t#trace_}_kernel_stats.csv; cp $O/$t/per_launch.jsonl $O/per_launch_${t#trace_}.jsonl; cp $O/$t/bench_line.json $O/bench_${t#trace_}_under_rocprof.json; done
 rm -rf $O/trace_n28 $O/trace_n24
 # config 5's workload and the exchanges, all ranks on this one device (diagnostic: eight processes share one GPU); the bare
 # `--gpus N` form (no launcher: bench.py spawns its own ranks)
 for W in 2 4 8; do
-  BN_ALL_ON_GPU0=1 BN_PG_BACKEND=gloo timeout 300 python bench.py --gpus $W --n-vars 13 --steps 50 --warmup 5 --no-cpu-baseline --no-prof 2>/dev/null | grep '^{' > $O/bench_${W}_ranks_on_one_gpu_n13.json
+  BN_ALL_ON_GPU0=1 BN_PG_BACKEND=gloo timeout 300 python bench.py --full --gpus $W --n-vars 13 --steps 50 --warmup 5 --no-cpu-baseline --no-prof 2>/dev/null | grep '^{' > $O/bench_${W}_ranks_on_one_gpu_n13.json
 done
-BN_ALL_ON_GPU0=1 BN_PG_BACKEND=gloo timeout 600 python bench.py --gpus 8 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/bench_8_ranks_on_one_gpu_n28.json
+BN_ALL_ON_GPU0=1 BN_PG_BACKEND=gloo timeout 600 python bench.py --full --gpus 8 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/bench_8_ranks_on_one_gpu_n28.json
 tail -c 700 $O/bench_n28.json

@@ -9,7 +9,7 @@ one() { # name, env..., -- bench args
   local name=$1; shift
   local envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" python bench.py "$@" --no-cpu-baseline 2>/dev/null | python -c "
+  env "${envs[@]}" python bench.py "$@" --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$name', 'ms_per_step', round(d['ms_per_step'],4), 'roofline', round(d['roofline']['frac'],4), d['verifier_check'], d['transcript_digest'][:12], json.dumps(d.get('kernels'))[:400])"

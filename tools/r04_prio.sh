@@ -11,7 +11,7 @@ one() { # name, kernel label prefix, env..., -- bench args
   local kern=$1; shift
   local envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" python bench.py "$@" --no-cpu-baseline 2>/dev/null | python -c "
+  env "${envs[@]}" python bench.py "$@" --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=[v for n,v in d['kernels'].items() if n.startswith('$kern')]
