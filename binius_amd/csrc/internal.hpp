@@ -637,6 +637,28 @@ hipError_t launch_fri_fold(hipStream_t s, const uint64_t *d_s_evals, uint32_t tw
                            uint32_t log_len, uint32_t log_batch, const f128 *h_challenges, uint32_t n_challenges,
                            const void *in, void *out, uint64_t out_len, void *scratch, int n_cu, const uint8_t *d_mul8);
 
+// ---- kernels_univariate.hip: the univariate round of the univariate-skip zerocheck (abi_univariate.cpp)
+constexpr uint32_t kUskipMaxSteps = 64; // steps of one composition (one LDS byte per step and lane)
+struct uskip_col {
+	const void *ptr;
+	uint32_t level, pad; // tower level 0 or 3
+};
+struct uskip_args {
+	const uskip_col *cols;
+	const bn_step *steps;     // every composition's steps, back to back
+	const uint32_t *step_off; // n_comps + 1 offsets into steps
+	const uint32_t *n_j;      // per composition: its (d_c - 1) 2^k points 2^k <= j < d_c 2^k (0: nothing to evaluate)
+	const uint4 *masks;       // [256][8]: bit u of mask[j][b] = bit b of L_u(omega_j)
+	const uint8_t *lag;       // [256][256]: L_u(omega_j) at j * 256 + u
+	const uint8_t *logexp;    // B8 log[256] | exp[512] (exp[i] = g^(i mod 255))
+	const uint4 *eq;          // 2^n_x_log
+	void *partial;            // [n_comps][n_tiles][th] f128
+	uint32_t k, n_x_log, n_tiles, pad;
+	uint64_t x_per_tile;
+};
+// out[c][t] (th values per composition) = scale[c] (nullptr: 1) * R_c(omega_{2^k + t}), 0 for t >= n_j[c]
+hipError_t launch_uskip_evals(hipStream_t s, const uskip_args &a, uint32_t th, uint32_t n_comps, const f128 *scale, f128 *d_out);
+
 // is eq[0 .. n) a tensor expansion up to a constant: eq[i] == eq[i - 2^k] * rho[k] (k = top bit of i)?  *d_flag |= 1 if not.
 // d_rho[n_log] and d_first_wg[42] (from check_tensor_layout, which returns the grid size) are read by the kernel from memory.
 uint32_t check_tensor_layout(uint32_t n_log, uint32_t *first_wg);

@@ -224,6 +224,22 @@ int bn_hal_round_evals(bn_ctx *ctx, uint32_t order, uint32_t n_vars, const void 
  * this round's challenge (n_vars_ml = n_vars - 1 + query_vars).  *out_len evaluations are written. */
 int bn_hal_fold_multilinear(bn_ctx *ctx, uint32_t order, uint32_t n_vars, const bn_hal_multilinear *ml, const bn_f128 *challenge,
                             const void *d_tensor_query, uint32_t query_vars, void *d_out, uint64_t out_cap, uint64_t *out_len);
+/* The univariate round of the univariate-skip zerocheck: zerocheck_univariate_evals (prove/univariate.rs:235-507) with
+ * extrapolate_round_evals (:571-640), for the domain field B8 (core/src/constraint_system/prove.rs:484, the 0..=3 arm).
+ * k = skip_rounds (1 <= k <= n_vars), index i = u + 2^k x (u < 2^k), omega_j = the B8 element whose tower bits are j, L_u the
+ * Lagrange basis over omega_0 .. omega_{2^k - 1}, Mhat_i(omega, x) = sum_u L_u(omega) M_i(u + 2^k x), eq = the tensor expansion
+ * of the n_vars - k zerocheck challenges (d_eq, eq_len = 2^(n_vars - k) elements, challenge t on bit t of x).
+ *   mls[n_mls]: the columns, TRANSPARENT, tower level 0 (B1) or 3 (B8), n_vars_ml = n_vars, packed as bn_hal_multilinear says
+ *   steps / step_offsets[n_comps + 1] / degrees[n_comps]: composition c = steps[step_offsets[c] .. step_offsets[c + 1]) over B8
+ *   (at most 64 steps, constants in B8), of degree d_c with d_c 2^k <= 256;  max_domain_size D: max_c d_c 2^k <= D <= 256.
+ * P_c = the polynomial of degree < d_c 2^k that is zero on omega_0 .. omega_{2^k - 1} and equals
+ * R_c(omega_j) = sum_x eq(x) C_c(Mhat_1(omega_j, x), ...) on omega_{2^k} .. omega_{d_c 2^k - 1} (P_c = 0 for d_c = 1).
+ * h_out: P_c(omega_j) for 2^k <= j < D, composition by composition (n_comps (D - 2^k) values), or with h_batch_coeff = alpha
+ * only sum_c alpha^c P_c (D - 2^k values; prove/zerocheck.rs:354-370).  A column at another level, a constant outside B8,
+ * d_c 2^k > 256, k > n_vars and k = 0 are BN_ERR_INPUT_VALIDATION with nothing launched.  Synchronises the stream. */
+int bn_zerocheck_univariate_evals(bn_ctx *ctx, uint32_t n_vars, uint32_t skip_rounds, const bn_hal_multilinear *mls, uint32_t n_mls,
+                                  const bn_step *steps, const uint32_t *step_offsets, const uint32_t *degrees, uint32_t n_comps,
+                                  const void *d_eq, uint64_t eq_len, uint32_t max_domain_size, const bn_f128 *h_batch_coeff, bn_f128 *h_out);
 
 int bn_ntt_forward(bn_ctx *ctx, void *d_data, uint32_t elem_level, uint32_t tw_level, const uint64_t *h_s_evals,
                    uint32_t log_domain, uint32_t log_x, uint32_t log_y, uint32_t log_z, uint64_t coset,
