@@ -160,6 +160,7 @@ def lib():
         "bn_prof_end": [vp, C.POINTER(C.c_double), C.POINTER(u64)],
         "bn_arm_counters": [vp, C.POINTER(u64)],
         "bn_group_counters": [vp, C.POINTER(u64)],
+        "bn_fp4_last_grids": [vp, C.POINTER(u64)],
         "bn_xor_reduce": [vp, vp, u32, u32, PF],
         "bn_host_scratch": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)],
         "bn_device_numa_node": [C.c_int, C.POINTER(C.c_int)],
@@ -193,7 +194,7 @@ ABI_SYMBOLS = [
     "bn_extrapolate_line", "bn_extrapolate_line_batch", "bn_tensor_expand", "bn_inner_product", "bn_fold_left", "bn_fold_right", "bn_fri_fold",
     "bn_compute_composite", "bn_pairwise_product_reduce", "bn_log_chunks_range", "bn_pick_log_chunks",
     "bn_kernel_launch", "bn_ntt_forward", "bn_ntt_inverse", "bn_ntt_s_evals", "bn_scalar_mul", "bn_scalar_invert",
-    "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
+    "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
     "bn_merkle_build", "bn_groestl256_leaves", "bn_groestl256_compress_layer", "bn_gather_d2h",
     "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
@@ -535,6 +536,15 @@ class Context:
         keys = ("launches", "jobs_fused", "jobs_eval", "prefolds", "spec_jobs", "spec_hits", "evals", "flushed_folds", "hosted_started", "hosted_evals",
                 "hosted_folds", "hosted_writebacks", "jobs_fold", "chains")
         return {k: int(c[i]) for i, k in enumerate(keys)}
+
+    def fp4_last_grids(self):
+        """How the last FP4 round evaluation and the last fused FP4 fold + evaluation of this process were launched
+        (bn_fp4_last_grids): workgroups, most tiles per workgroup, whether the round evaluation ran its stager / Gram wave form, and the largest
+        share of a workgroup in any such launch of the process so far."""
+        c = (C.c_uint64 * 7)()
+        _check(lib().bn_fp4_last_grids(self._h, c))
+        return {"re_grid": int(c[0]), "re_tiles": int(c[1]), "re_ws": int(c[2]), "fe_grid": int(c[3]), "fe_tiles": int(c[4]),
+                "re_max_tiles": int(c[5]), "fe_max_tiles": int(c[6])}
 
     # ---- ComputeLayer
     def copy_h2d(self, src, dst):

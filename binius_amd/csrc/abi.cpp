@@ -1449,6 +1449,21 @@ int bn_group_counters(bn_ctx *ctx, uint64_t *counters)
 	return BN_OK;
 }
 
+int bn_fp4_last_grids(bn_ctx *ctx, uint64_t *grids)
+{
+	BN_REQUIRE(ctx && grids, "null argument");
+	BN_ENTER(ctx);
+	const bn::fp4_grid_record &g = bn::fp4_last_grids();
+	grids[BN_FP4_RE_GRID] = g.re_grid.load(std::memory_order_relaxed);
+	grids[BN_FP4_RE_TILES] = g.re_tiles.load(std::memory_order_relaxed);
+	grids[BN_FP4_RE_WS] = g.re_ws.load(std::memory_order_relaxed);
+	grids[BN_FP4_FE_GRID] = g.fe_grid.load(std::memory_order_relaxed);
+	grids[BN_FP4_FE_TILES] = g.fe_tiles.load(std::memory_order_relaxed);
+	grids[BN_FP4_RE_MAX_TILES] = g.re_max_tiles.load(std::memory_order_relaxed);
+	grids[BN_FP4_FE_MAX_TILES] = g.fe_max_tiles.load(std::memory_order_relaxed);
+	return BN_OK;
+}
+
 int bn_host_scratch(bn_ctx *ctx, void **h_ptr, void **d_ptr, uint64_t *elems)
 {
 	BN_REQUIRE(ctx && h_ptr && d_ptr && elems, "null argument");

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <initializer_list>
 #include <memory>
 #include <string>
@@ -510,6 +511,21 @@ hipError_t launch_roundeval_mfma_pair_strided(hipStream_t s, int n_cu, const voi
 hipError_t launch_roundeval_fp4_pair(hipStream_t s, int n_cu, const void *a_hi, const void *a_lo, const void *b_hi, const void *b_lo,
                                      uint64_t n, f128 *d_out, const fin_fuse *fuse);
 hipError_t launch_roundeval_fp4_split(hipStream_t s, int n_cu, const void *a, const void *b, uint64_t n, uint64_t split_off, f128 *d_out);
+// how the last launch of each FP4 launcher went out (bn_fp4_last_grids: a read-only query, so that a test of the 2^14-tile bound can
+// tell that the grid it asked for was the grid that ran)
+struct fp4_grid_record {
+	std::atomic<uint64_t> re_grid{0}, re_tiles{0}, re_ws{0}, fe_grid{0}, fe_tiles{0}, re_max_tiles{0}, fe_max_tiles{0};
+	static void note(std::atomic<uint64_t> &grid, std::atomic<uint64_t> &tiles, std::atomic<uint64_t> &max_tiles, uint64_t g, uint64_t n_tiles)
+	{
+		const uint64_t share = (n_tiles + g - 1) / g;
+		grid.store(g, std::memory_order_relaxed);
+		tiles.store(share, std::memory_order_relaxed);
+		uint64_t seen = max_tiles.load(std::memory_order_relaxed);
+		while (seen < share && !max_tiles.compare_exchange_weak(seen, share, std::memory_order_relaxed)) {
+		}
+	}
+};
+fp4_grid_record &fp4_last_grids();
 hipError_t launch_roundeval_mfma_split(hipStream_t s, int n_cu, const void *a, const void *b, uint64_t n, uint64_t split_off, f128 *d_out);
 hipError_t launch_foldeval_mfma(hipStream_t s, int n_cu, const foldeval_args &fa, uint64_t n_in, f128 z, f128 *d_out, const fin_fuse *fuse,
                                 const arm_args *armed = nullptr);

@@ -246,6 +246,8 @@ hipError_t launch_foldeval_fp4(hipStream_t s, int n_cu, const foldeval_args &fa_
 		return hipSuccess;
 	}();
 	if (attr != hipSuccess) return attr;
+	fp4_grid_record &rec = fp4_last_grids();
+	fp4_grid_record::note(rec.fe_grid, rec.fe_tiles, rec.fe_max_tiles, grid, n_tiles);
 #define BN_FQ_LAUNCH(SC)                                                                                                       \
 	if (nt)                                                                                                                    \
 		hipLaunchKernelGGL((k_foldeval_mfma_fp4<SC, true>), dim3(grid), dim3(kThreads), lds, s, fa, n_in, z, d_out, fz, arm);  \

@@ -264,6 +264,12 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_roundeval_fp4_ws(const uint4 
 	tail_publish(z3, out, fz, fz.args.seq, nullptr);
 }
 
+fp4_grid_record &fp4_last_grids()
+{
+	static fp4_grid_record r;
+	return r;
+}
+
 template <bool MIX>
 static hipError_t launch_fp4(hipStream_t s, int n_cu, const void *a_hi, const void *a_lo, const void *b_hi, const void *b_lo, uint64_t n, f128 *d_out,
                              const fin_fuse *fuse)
@@ -309,6 +315,9 @@ static hipError_t launch_fp4(hipStream_t s, int n_cu, const void *a_hi, const vo
 			return func_lds_limit(reinterpret_cast<const void *>(&k_roundeval_fp4_ws<MIX, false>), lds);
 		}();
 		if (attr != hipSuccess) return attr;
+		fp4_grid_record &rec = fp4_last_grids();
+		fp4_grid_record::note(rec.re_grid, rec.re_tiles, rec.re_max_tiles, ws_grid, n_tiles);
+		rec.re_ws.store(1, std::memory_order_relaxed);
 		if (nt)
 			hipLaunchKernelGGL((k_roundeval_fp4_ws<MIX, true>), dim3(ws_grid), dim3(kWsThreads), lds, s, (const uint4 *)a_hi, (const uint4 *)a_lo,
 			                   (const uint4 *)b_hi, (const uint4 *)b_lo, n, d_out, fz, xcd_tiles & 1u);
@@ -317,6 +326,9 @@ static hipError_t launch_fp4(hipStream_t s, int n_cu, const void *a_hi, const vo
 			                   (const uint4 *)b_hi, (const uint4 *)b_lo, n, d_out, fz, xcd_tiles & 1u);
 		return hipGetLastError();
 	}
+	fp4_grid_record &rec = fp4_last_grids();
+	fp4_grid_record::note(rec.re_grid, rec.re_tiles, rec.re_max_tiles, grid, n_tiles);
+	rec.re_ws.store(0, std::memory_order_relaxed);
 	if (nt)
 		hipLaunchKernelGGL((k_roundeval_fp4<MIX, true>), dim3(grid), dim3(256), 0, s, (const uint4 *)a_hi, (const uint4 *)a_lo, (const uint4 *)b_hi,
 		                   (const uint4 *)b_lo, n, d_out, fz, xcd_tiles);

@@ -369,6 +369,14 @@ int bn_arm_counters(bn_ctx *ctx, uint64_t *counters /*[BN_ARM_N]*/);
  * (folds first, then the evaluations that read them back). */
 enum { BN_GROUP_LAUNCHES = 0, BN_GROUP_JOBS_FUSED = 1, BN_GROUP_JOBS_EVAL = 2, BN_GROUP_PREFOLDS = 3, BN_GROUP_SPEC_JOBS = 4, BN_GROUP_SPEC_HITS = 5, BN_GROUP_EVALS = 6, BN_GROUP_FLUSHED_FOLDS = 7, BN_GROUP_HOSTED_STARTED = 8, BN_GROUP_HOSTED_EVALS = 9, BN_GROUP_HOSTED_FOLDS = 10, BN_GROUP_HOSTED_WRITEBACKS = 11, BN_GROUP_JOBS_FOLD = 12, BN_GROUP_CHAINS = 13, BN_GROUP_N = 14 };
 int bn_group_counters(bn_ctx *ctx, uint64_t *counters /*[BN_GROUP_N]*/);
+/* The wave-specialised FP4 kernels keep sums of GF(2) products as counts in f32 accumulators, exact while a workgroup sees at
+ * most 2^14 tiles (2^22 points) per launch; their launchers refuse a grid beyond that bound (also one asked for through the test
+ * switches BN_FP4_WS_GRID / BN_FE_FP4_GRID).  Read-only, process-wide: how the LAST FP4 round evaluation and the LAST fused FP4
+ * fold + evaluation were launched -- workgroups, the largest number of tiles a workgroup took, and for the round evaluation which
+ * form ran (1: stager / Gram waves, 0: three workgroups per CU); *_MAX_TILES: the largest share of a workgroup in any such launch
+ * of the process so far; zeros before the first such launch. */
+enum { BN_FP4_RE_GRID = 0, BN_FP4_RE_TILES = 1, BN_FP4_RE_WS = 2, BN_FP4_FE_GRID = 3, BN_FP4_FE_TILES = 4, BN_FP4_RE_MAX_TILES = 5, BN_FP4_FE_MAX_TILES = 6, BN_FP4_N = 7 };
+int bn_fp4_last_grids(bn_ctx *ctx, uint64_t *grids /*[BN_FP4_N]*/);
 
 #ifdef __cplusplus
 }

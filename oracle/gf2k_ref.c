@@ -7,6 +7,10 @@
  */
 #include "gf2k_ref.h"
 
+#ifdef _OPENMP
+#include <omp.h>
+#endif
+
 #include <string.h>
 
 static inline uint64_t mask_bits(int nbits) { return nbits >= 64 ? ~0ull : ((1ull << nbits) - 1); }
@@ -183,8 +187,22 @@ void ref_b128_mul_subfield_p(const ref_b128 *a, const ref_b128 *s, int iota, ref
 {
 	*out = ref_b128_mul_subfield(*a, *s, iota);
 }
+/* Threads of the loops below that are parallel over independent elements (or over terms of an XOR sum, which is associative and
+ * commutative: the result does not depend on the split): OMP_NUM_THREADS, at most 16. */
+int ref_par_threads(void)
+{
+	(void)ref_gf_mul(1, 1, 3); /* the product table is built before any thread reads it */
+#ifdef _OPENMP
+	const int t = omp_get_max_threads();
+	return t < 1 ? 1 : (t > 16 ? 16 : t);
+#else
+	return 1; /* (built without OpenMP, the loops run as written) */
+#endif
+}
+
 void ref_b128_mul_vec(const ref_b128 *a, const ref_b128 *b, ref_b128 *out, size_t n)
 {
+#pragma omp parallel for schedule(static) num_threads(ref_par_threads()) if (n >= 4096)
 	for (size_t i = 0; i < n; i++)
 		out[i] = ref_b128_mul(a[i], b[i]);
 }

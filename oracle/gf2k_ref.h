@@ -68,6 +68,7 @@ void ref_b128_mul_p(const ref_b128 *a, const ref_b128 *b, ref_b128 *out);
 void ref_b128_square_p(const ref_b128 *a, ref_b128 *out);
 void ref_b128_invert_p(const ref_b128 *a, ref_b128 *out);
 void ref_b128_mul_subfield_p(const ref_b128 *a, const ref_b128 *s, int iota, ref_b128 *out);
+int ref_par_threads(void); /* threads of the element-parallel loops: OMP_NUM_THREADS, at most 16 */
 void ref_b128_mul_vec(const ref_b128 *a, const ref_b128 *b, ref_b128 *out, size_t n);
 
 /* SplitMix64 -- the documented PRNG for every synthetic input */

@@ -56,45 +56,55 @@ int ref_hal_round_evals(int order, uint32_t n_vars, const ref_b128 *tensor_query
 	size_t total = 0;
 	for (uint32_t e = 0; e < n_evs; e++) total += evs[e].eval_point_end - evs[e].eval_point_start;
 	memset(out, 0, total * sizeof(ref_b128));
-	/* (one value per multilinear: a constraint set's zerocheck passes every column of its table, prove.rs:431-505) */
-	ref_b128 *e0 = (ref_b128 *)calloc(3 * (size_t)(n_mls ? n_mls : 1), sizeof(ref_b128));
-	ref_b128 *e1 = e0 + (n_mls ? n_mls : 1), *row = e1 + (n_mls ? n_mls : 1);
-	for (uint64_t i = 0; i < half && !rc; i++) {
-		for (uint32_t k = 0; k < n_mls; k++) {
-			/* the substituted variable is the lowest one (LowToHigh: pairs 2i, 2i+1, round_calculation.rs:443-464)
-			 * or the highest one (HighToLow: pairs i, i + 2^(n_vars-1), :521-556) */
-			const uint64_t i0 = order == REF_ORDER_LOW_TO_HIGH ? 2 * i : i;
-			const uint64_t i1 = order == REF_ORDER_LOW_TO_HIGH ? 2 * i + 1 : i + half;
-			e0[k] = ml_at(&mls[k], virt[k], i0);
-			e1[k] = ml_at(&mls[k], virt[k], i1);
-		}
-		for (uint32_t p = pt_lo; p < pt_hi; p++) {
-			/* f(z, xs) = f(0, xs) + z (f(1, xs) - f(0, xs)); index 2 is the point at infinity: f(1) - f(0)
-			 * (round_calculation.rs:186-232) */
+	/* (one value per multilinear: a constraint set's zerocheck passes every column of its table, prove.rs:431-505)
+	 * The hypercube vertices are dealt out to threads, each with its own row and partial sums; the partial sums are XORed
+	 * together at the end -- the same terms, the same sums. */
+	const size_t nm = n_mls ? n_mls : 1;
+#pragma omp parallel num_threads(ref_par_threads()) if (!rc && half >= 4096)
+	{
+		ref_b128 *e0 = (ref_b128 *)calloc(3 * nm + (total ? total : 1), sizeof(ref_b128));
+		ref_b128 *e1 = e0 + nm, *row = e1 + nm, *part = row + nm;
+#pragma omp for schedule(static) nowait
+		for (uint64_t i = 0; i < (rc ? 0 : half); i++) {
 			for (uint32_t k = 0; k < n_mls; k++) {
-				if (p == 0) row[k] = e0[k];
-				else if (p == 1) row[k] = e1[k];
-				else if (p == 2) row[k] = ref_b128_add(e1[k], e0[k]);
-				else row[k] = ref_b128_add(e0[k], ref_b128_mul(nontrivial_points[p - 3], ref_b128_add(e1[k], e0[k])));
+				/* the substituted variable is the lowest one (LowToHigh: pairs 2i, 2i+1, round_calculation.rs:443-464)
+				 * or the highest one (HighToLow: pairs i, i + 2^(n_vars-1), :521-556) */
+				const uint64_t i0 = order == REF_ORDER_LOW_TO_HIGH ? 2 * i : i;
+				const uint64_t i1 = order == REF_ORDER_LOW_TO_HIGH ? 2 * i + 1 : i + half;
+				e0[k] = ml_at(&mls[k], virt[k], i0);
+				e1[k] = ml_at(&mls[k], virt[k], i1);
 			}
-			size_t off = 0;
-			for (uint32_t e = 0; e < n_evs; e++) {
-				const uint32_t s = evs[e].eval_point_start, t = evs[e].eval_point_end;
-				if (p >= s && p < t) {
-					/* RegularSumcheckEvaluator / eq_ind Evaluator::process_subcube_at_eval_point
-					 * (regular_sumcheck.rs:248-270, eq_ind.rs:676-704) */
-					ref_b128 v = p == 2 ? ref_circuit_eval(evs[e].composition_at_infinity, evs[e].n_steps_inf, row)
-					                    : ref_circuit_eval(evs[e].composition, evs[e].n_steps, row);
-					if (evs[e].eq_ind) v = ref_b128_mul(v, evs[e].eq_ind[i]);
-					out[off + (p - s)] = ref_b128_add(out[off + (p - s)], v);
+			for (uint32_t p = pt_lo; p < pt_hi; p++) {
+				/* f(z, xs) = f(0, xs) + z (f(1, xs) - f(0, xs)); index 2 is the point at infinity: f(1) - f(0)
+				 * (round_calculation.rs:186-232) */
+				for (uint32_t k = 0; k < n_mls; k++) {
+					if (p == 0) row[k] = e0[k];
+					else if (p == 1) row[k] = e1[k];
+					else if (p == 2) row[k] = ref_b128_add(e1[k], e0[k]);
+					else row[k] = ref_b128_add(e0[k], ref_b128_mul(nontrivial_points[p - 3], ref_b128_add(e1[k], e0[k])));
 				}
-				off += t - s;
+				size_t off = 0;
+				for (uint32_t e = 0; e < n_evs; e++) {
+					const uint32_t s = evs[e].eval_point_start, t = evs[e].eval_point_end;
+					if (p >= s && p < t) {
+						/* RegularSumcheckEvaluator / eq_ind Evaluator::process_subcube_at_eval_point
+						 * (regular_sumcheck.rs:248-270, eq_ind.rs:676-704) */
+						ref_b128 v = p == 2 ? ref_circuit_eval(evs[e].composition_at_infinity, evs[e].n_steps_inf, row)
+						                    : ref_circuit_eval(evs[e].composition, evs[e].n_steps, row);
+						if (evs[e].eq_ind) v = ref_b128_mul(v, evs[e].eq_ind[i]);
+						part[off + (p - s)] = ref_b128_add(part[off + (p - s)], v);
+					}
+					off += t - s;
+				}
 			}
 		}
+#pragma omp critical(ref_hal_round_evals_sum)
+		for (size_t t = 0; t < total; t++)
+			out[t] = ref_b128_add(out[t], part[t]);
+		free(e0);
 	}
 	for (uint32_t k = 0; k < n_mls; k++) free(virt[k]);
 	free(virt);
-	free(e0);
 	return rc;
 }
 

@@ -216,11 +216,22 @@ int ref_round_evals_eq(const ref_b128 *const *multilins, size_t m, unsigned n_va
 		if (i >= m || j >= m) return 1;
 		const ref_b128 *a = multilins[i], *b = multilins[j];
 		ref_b128 s1 = ref_b128_zero(), sinf = ref_b128_zero();
-		for (size_t k = 0; k < half; k++) {
-			ref_b128 p1 = ref_b128_mul(ref_b128_mul(a[half + k], b[half + k]), eq_ind[k]);
-			ref_b128 pinf = ref_b128_mul(ref_b128_mul(ref_b128_add(a[k], a[half + k]), ref_b128_add(b[k], b[half + k])), eq_ind[k]);
-			s1 = ref_b128_add(s1, p1);
-			sinf = ref_b128_add(sinf, pinf);
+		/* (the terms of the two XOR sums dealt out to threads: the same terms, the same sums) */
+#pragma omp parallel num_threads(ref_par_threads()) if (half >= 4096)
+		{
+			ref_b128 t1 = ref_b128_zero(), tinf = ref_b128_zero();
+#pragma omp for schedule(static) nowait
+			for (size_t k = 0; k < half; k++) {
+				ref_b128 p1 = ref_b128_mul(ref_b128_mul(a[half + k], b[half + k]), eq_ind[k]);
+				ref_b128 pinf = ref_b128_mul(ref_b128_mul(ref_b128_add(a[k], a[half + k]), ref_b128_add(b[k], b[half + k])), eq_ind[k]);
+				t1 = ref_b128_add(t1, p1);
+				tinf = ref_b128_add(tinf, pinf);
+			}
+#pragma omp critical(ref_round_evals_eq_sum)
+			{
+				s1 = ref_b128_add(s1, t1);
+				sinf = ref_b128_add(sinf, tinf);
+			}
 		}
 		acc1 = ref_b128_add(acc1, ref_b128_mul(s1, coeff));     /* *accumulator += ret * batch_coeff (cpu/layer.rs:512) */
 		accinf = ref_b128_add(accinf, ref_b128_mul(sinf, coeff));
@@ -266,10 +277,11 @@ int ref_bivariate_mlecheck_prove(ref_b128 *const *multilins, size_t m, unsigned 
 		batched_sum = ref_evaluate_univariate(prime, 3, z);
 		prefix = ref_b128_mul(prefix, ref_b128_add(ref_b128_add(alpha, z), one)); /* eq(alpha, z) = alpha + z + 1 */
 		for (size_t j = 0; j < m; j++)
-			ref_fold_high(multilins[j], rem, z, 1);
+			ref_fold_high(multilins[j], rem, z, rem > 13 ? ref_par_threads() : 1);
 		if (rem - 1 != 0) {
 			/* fold_eq_ind (:195-254): evals_0[i] += evals_1[i] over the halves of the 2^(rem-1) table */
 			const size_t h = (size_t)1 << (rem - 2);
+#pragma omp parallel for schedule(static) num_threads(ref_par_threads()) if (h >= 4096)
 			for (size_t i = 0; i < h; i++)
 				eq_ind[i] = ref_b128_add(eq_ind[i], eq_ind[h + i]);
 		}
