@@ -145,6 +145,8 @@ def lib():
         "bn_fri_fold": [vp, C.POINTER(u64), u32, u32, u32, u32, PF, u32, vp, u64, vp, u64],
         "bn_compute_composite": [vp, C.POINTER(vp), u32, u64, vp, u64, vp],
         "bn_pairwise_product_reduce": [vp, vp, u64, C.POINTER(vp), C.POINTER(u64), u32],
+        "bn_product_tree_layers": [vp, u32, C.POINTER(u32), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), PF],
+        "bn_pad_with_ones": [vp, u32, C.POINTER(u32), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp)],
         "bn_log_chunks_range": [C.POINTER(MemMap), u32, C.POINTER(u32), C.POINTER(u32)],
         "bn_pick_log_chunks": [C.POINTER(MemMap), u32, C.POINTER(u32)],
         "bn_kernel_launch": [vp, C.POINTER(MemMap), u32, C.POINTER(KOp), u32, C.POINTER(u32), u32, u32, PF, vp],
@@ -197,6 +199,7 @@ ABI_SYMBOLS = [
     "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
     "bn_merkle_build", "bn_groestl256_leaves", "bn_groestl256_compress_layer", "bn_gather_d2h",
     "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals",
+    "bn_product_tree_layers", "bn_pad_with_ones",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -733,6 +736,31 @@ class Context:
         outs = (C.c_void_p * max(1, len(round_outputs)))(*[r.ptr for r in round_outputs])
         lens = (C.c_uint64 * max(1, len(round_outputs)))(*[r.len for r in round_outputs])
         _check(lib().bn_pairwise_product_reduce(self._h, inp.ptr, inp.len, outs, lens, len(round_outputs)))
+
+    def product_tree_layers(self, n_vars, inputs, arenas):
+        """Every layer of a batch of halves-product trees (bn_product_tree_layers; gkr_gpa/gkr_gpa.rs:38-90).  n_vars: one per
+        tree; inputs: DevSlices of up to 2^n_vars elements (None = empty; the absent tail counts as ONE); arenas: DevSlices of
+        2^n_vars elements receiving layer j at [2^j, 2^(j+1)) (None allowed for n_vars = 0).  Returns the products."""
+        n = len(n_vars)
+        nv = (C.c_uint32 * max(1, n))(*n_vars)
+        ins = (C.c_void_p * max(1, n))(*[(x.ptr if x is not None else None) for x in inputs])
+        lens = (C.c_uint64 * max(1, n))(*[(x.len if x is not None else 0) for x in inputs])
+        for t, a in enumerate(arenas):
+            if a is not None and a.len != (1 << n_vars[t]) and n_vars[t] <= 28:
+                raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: product tree: an arena holds 2^n_vars elements")
+        outs = (C.c_void_p * max(1, n))(*[(a.ptr if a is not None else None) for a in arenas])
+        prod = (F128 * max(1, n))()
+        _check(lib().bn_product_tree_layers(self._h, n, nv, ins, lens, outs, prod))
+        return [from_f128(prod[t]) for t in range(n)]
+
+    def pad_with_ones(self, log_lens, srcs, dsts):
+        """dsts[t] = srcs[t] followed by ONEs up to 2^log_lens[t] elements, every array in one launch (bn_pad_with_ones)."""
+        n = len(log_lens)
+        ll = (C.c_uint32 * max(1, n))(*log_lens)
+        ins = (C.c_void_p * max(1, n))(*[(x.ptr if x is not None else None) for x in srcs])
+        lens = (C.c_uint64 * max(1, n))(*[(x.len if x is not None else 0) for x in srcs])
+        outs = (C.c_void_p * max(1, n))(*[d.ptr for d in dsts])
+        _check(lib().bn_pad_with_ones(self._h, n, ll, ins, lens, outs))
 
     # ---- accumulate_kernels / map_kernels
     def pick_log_chunks(self, mem_maps):

@@ -68,6 +68,12 @@ def host_lib():
             C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32),
             C.POINTER(C.c_uint32), C.POINTER(F128), C.POINTER(F128), C.c_void_p, C.c_uint64, C.POINTER(F128), C.POINTER(F128), C.POINTER(F128), C.POINTER(F128),
         ]
+        L.bnh_gkr_gpa_prove.restype = C.c_int
+        L.bnh_gkr_gpa_prove.argtypes = [
+            C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64,
+            C.POINTER(F128), C.POINTER(F128), C.POINTER(F128), C.POINTER(F128), C.POINTER(F128), C.POINTER(F128), C.POINTER(F128), C.POINTER(F128),
+            C.POINTER(C.c_double),
+        ]
         L.bnh_rccl_open.argtypes = [C.c_char_p]
         L.bnh_rccl_unique_id.argtypes = [C.c_void_p]
         L.bnh_rccl_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -393,6 +399,67 @@ class EqIndPlan:
 
     def final_evals(self):
         return [from_f128(self.final[j]) for j in range(self.m + 1)]
+
+
+class GkrGpaPlan:
+    """gkr_gpa::batch_prove (bnh_gkr_gpa_prove = binius_amd/host/gkr_gpa.hpp; crates/core/src/protocols/gkr_gpa/prove.rs:33-296): the GKR
+    grand-product argument over a batch of witnesses.  n_vars: one per claim; inputs: device slices of up to 2^n_vars elements
+    (None = empty; the absent tail counts as ONE; only read); arenas: device slices of 2^n_vars elements (None for n_vars = 0),
+    CONSUMED by run(); scratch: device slice of at least scratch_elems(n_vars) elements; batch_coeffs / gpa_challenges: one per step
+    j < max(n_vars); sumcheck_challenges: list per step j of its j challenges."""
+
+    @staticmethod
+    def scratch_elems(n_vars):
+        m = max(list(n_vars) + [0])
+        return sum(1 << n for n in n_vars if n >= 1) + ((1 << (m - 1)) if m >= 1 else 0)
+
+    def __init__(self, hal, n_vars, inputs, arenas, scratch, batch_coeffs, sumcheck_challenges, gpa_challenges):
+        self.hal, self.n_vars, self.k = hal, list(n_vars), len(n_vars)
+        self.max_n = m = max(self.n_vars + [0])
+        self._keep = (inputs, arenas, scratch)
+        k1 = max(1, self.k)
+        self.nv = (C.c_uint32 * k1)(*self.n_vars)
+        self.ins = (C.c_void_p * k1)(*[(x.ptr if x is not None else None) for x in inputs])
+        self.lens = (C.c_uint64 * k1)(*[(x.len if x is not None else 0) for x in inputs])
+        self.ars = (C.c_void_p * k1)(*[(a.ptr if a is not None else None) for a in arenas])
+        self.scratch = scratch
+        assert len(batch_coeffs) >= m and len(gpa_challenges) >= m and len(sumcheck_challenges) >= m
+        assert all(len(sumcheck_challenges[j]) == j for j in range(m))
+        flat = [z for j in range(m) for z in sumcheck_challenges[j]]
+        self.bc, self.sc, self.gc = _f128_array(list(batch_coeffs[:m]) or [0]), _f128_array(flat or [0]), _f128_array(list(gpa_challenges[:m]) or [0])
+        # claims in the sorted order (n_vars descending, stable): the active ones of step j are those with n_vars > j
+        self.active = [sum(1 for n in self.n_vars if n > j) for j in range(m)]
+        self.products = (F128 * k1)()
+        self.proofs = (F128 * max(1, 3 * m * (m - 1) // 2))()
+        self.evals = (F128 * max(1, sum(2 * a + 1 for a in self.active)))()
+        self.points = (F128 * max(1, sum(self.n_vars)))()
+        self.finals = (F128 * k1)()
+        self.step_ms = (C.c_double * max(1, m))()
+
+    def run(self):
+        rc = host_lib().bnh_gkr_gpa_prove(self.hal._h, self.k, self.nv, self.ins, self.lens, self.ars, self.scratch.ptr, self.scratch.len, self.bc, self.sc, self.gc,
+                                          self.products, self.proofs, self.evals, self.points, self.finals, self.step_ms)
+        if rc != 0:
+            raise BnError(rc, host_lib().bnh_last_error().decode())
+
+    def output(self):
+        """The proof in the shape of tests/gkr_gpa_ref.py gpa_prove."""
+        proofs, evals, at_p, at_e = [], [], 0, 0
+        for j in range(self.max_n):
+            proofs.append([[from_f128(self.proofs[at_p + 3 * r + i]) for i in range(3)] for r in range(j)])
+            at_p += 3 * j
+            cnt = 2 * self.active[j] + 1
+            evals.append([from_f128(self.evals[at_e + i]) for i in range(cnt)])
+            at_e += cnt
+        points, at = [], 0
+        for n in self.n_vars:
+            points.append([from_f128(self.points[at + i]) for i in range(n)])
+            at += n
+        return {"products": [from_f128(self.products[t]) for t in range(self.k)], "round_proofs": proofs, "layer_evals": evals, "final_points": points,
+                "final_evals": [from_f128(self.finals[t]) for t in range(self.k)]}
+
+    def step_times_ms(self):
+        return [self.step_ms[j] for j in range(self.max_n)]
 
 
 class ShmExchange:

@@ -715,6 +715,26 @@ hipError_t launch_pairtree(hipStream_t s, const pairtree_args &args, uint32_t lo
 hipError_t launch_mul9(hipStream_t s, int n_cu, const void *a, uint64_t a_stride, const void *b, uint64_t b_stride, uint64_t b_off,
                        void *out, uint64_t n);
 
+// ---- kernels_prodtree.hip: the layers of a batch of halves-product trees (the GKR grand-product circuit, gkr_gpa.rs:38-90).
+// A job produces layers m - 1 .. m - n_levels of one tree from its layer m; a launch runs every job of a table.
+struct prodtree_job {
+	const f128 *src;   // layer m: the caller's input, or arena + 2^m
+	f128 *arena;       // the tree's layers in heap order: layer j at arena + 2^j (k_prodtree_pad: the destination)
+	uint64_t src_len;  // valid elements of src; the rest of its 2^m count as ONE
+	uint32_t m, n_levels;
+	uint32_t start;    // first unit of this job in the launch (small form: workgroups; big form: runs; pad: blocks of 256)
+	uint32_t pad_;
+};
+constexpr uint32_t kProdtreeSmallMaxLog2 = 15; // layers of up to 2^15 elements: the small form
+constexpr uint32_t kProdtreeSmallLevels = 6;   // layers per job of the small form
+constexpr uint32_t kProdtreeBigLevels = 2;     // layers per job of the big form
+constexpr uint32_t kProdtreeBatch = 224;       // products of a wave-batch of the bit-sliced product
+hipError_t launch_prodtree_small(hipStream_t s, const prodtree_job *d_jobs, uint32_t n_jobs, uint32_t total_wgs);
+// dual: two wave-batches per step of a wave (runs twice as long: the job table's `start` column is planned for the form)
+hipError_t launch_prodtree_big(hipStream_t s, int n_cu, const prodtree_job *d_jobs, uint32_t n_jobs, uint32_t total_runs, bool dual);
+hipError_t launch_prodtree_roots(hipStream_t s, const f128 *const *d_srcs, uint32_t n, f128 *d_out);
+hipError_t launch_prodtree_pad(hipStream_t s, const prodtree_job *d_jobs, uint32_t n_jobs, uint32_t total_blocks);
+
 // ---- kernels_ntt_tiled.hip
 hipError_t launch_build_mul8(hipStream_t s, uint8_t *d_tab);
 hipError_t launch_ntt_tiled(hipStream_t s, int n_cu, bool inverse, void *data, uint32_t elem_level, uint32_t tw_level,

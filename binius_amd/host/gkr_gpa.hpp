@@ -1,0 +1,192 @@
+// binius_amd/host/gkr_gpa.hpp -- C++ mirror of the GKR grand-product argument's batch prover, gkr_gpa::batch_prove
+// (crates/core/src/protocols/gkr_gpa/prove.rs:33-296), which the constraint system runs over every flush and non-zero oracle
+// (core/src/constraint_system/prove.rs:285-412, EvaluationOrder::HighToLow at :394):
+//
+//   GrandProductWitness::new            gkr_gpa.rs:38-90    ONE call of bn_product_tree_layers for all witnesses (every layer of
+//                                                           every tree, heap order); grand_product_evaluation = its products
+//   stable sort by n_vars, descending   prove.rs:61-62
+//   process_finished_provers            prove.rs:143-161    the states with n_vars = j leave with the current point and evaluation
+//   stage_sumcheck_provers              prove.rs:208-280    one EqIndSumcheckProver (eq_ind.hpp) over j variables: multilinears
+//                                                           2i, 2i + 1 = the halves of state i's layer j + 1, claim var(2i) var(2i+1)
+//                                                           with sum = its layer_eval, eq_ind_challenges = the current point
+//   front_loaded::BatchProver of ONE    front_loaded.rs:122-198   round proof = the prover's coefficients times the batch coefficient,
+//                                                           last coefficient dropped (RoundCoeffs::truncate)
+//   challenges reversed, gpa_challenge  prove.rs:106-116    eval_point = reversed challenges || gpa_challenge
+//   update_layer_eval                   prove.rs:282-284    layer_eval = e0 + gpa_challenge (e1 - e0)
+//
+// Step 0 has zero variables: no rounds, the final evaluations are the two elements of layer 1 and the indicator's prefix is ONE;
+// it is handled here (one gather), EqIndSumcheckProver does not learn n_vars = 0.
+// The sumcheck folds in place, so the arenas are consumed.  A tree's last step runs over its INPUT layer, which the caller owns and
+// which may be truncated: every input is first copied into the scratch, padded with ONEs to 2^n_vars elements (bn_pad_with_ones, one
+// launch for all), and the copy is folded; the inputs are never written.  The sumcheck over a truncated input just sees the ONEs
+// (with_const_suffixes, prove.rs:262-264, is an optimisation of the reference's CPU path).
+// Scratch: sum over the claims with n_vars >= 1 of 2^n_vars elements, plus 2^(max n_vars - 1) for the indicator's table.
+//
+// Protocol bookkeeping only: every hypercube-sized operation is a call of the backend.
+#pragma once
+#include <algorithm>
+#include <chrono>
+
+#include "eq_ind.hpp"
+
+namespace binius_amd {
+
+struct GkrGpaOutput {
+	std::vector<B128> products;                      // per claim, the callers' order
+	std::vector<std::vector<B128>> round_proofs;     // per step j: 3 j coefficients (j rounds of 3)
+	std::vector<std::vector<B128>> layer_evals;      // per step: 2 * active evaluations (sorted order), then the indicator's prefix
+	std::vector<std::vector<B128>> final_points;     // per claim (LayerClaim::eval_point, n_vars coordinates), the callers' order (unsort, :140)
+	std::vector<B128> final_evals;                   // per claim (LayerClaim::eval)
+	std::vector<double> step_ms;                     // wall time per step
+};
+
+inline size_t gkr_gpa_scratch_elems(const std::vector<size_t> &n_vars)
+{
+	size_t total = 0, max_n = 0;
+	for (size_t n : n_vars) {
+		if (n >= 1) total += (size_t)1 << n;
+		max_n = std::max(max_n, n);
+	}
+	return total + (max_n >= 1 ? (size_t)1 << (max_n - 1) : 0);
+}
+
+// batch_coeffs[j], gpa_challenges[j]: one per step j < max n_vars (step 0's batch coefficient is sampled and unused);
+// sumcheck_challenges: step j's j challenges, steps concatenated
+inline GkrGpaOutput gkr_gpa_batch_prove(ComputeLayer &hal, Mi355xBackend &backend, const std::vector<size_t> &n_vars, const std::vector<FSlice> &inputs,
+                                        const std::vector<FSliceMut> &arenas, FSliceMut scratch, const std::vector<B128> &batch_coeffs,
+                                        const std::vector<B128> &sumcheck_challenges, const std::vector<B128> &gpa_challenges)
+{
+	const size_t k = n_vars.size();
+	if (inputs.size() != k || arenas.size() != k) throw Error(Error::InputValidation, "MismatchedWitnessClaimLength");
+	size_t max_n = 0;
+	for (size_t n : n_vars) max_n = std::max(max_n, n);
+	if (batch_coeffs.size() < max_n || gpa_challenges.size() < max_n || sumcheck_challenges.size() < max_n * (max_n ? max_n - 1 : 0) / 2)
+		throw Error(Error::InputValidation, "too few transcript samples for the largest claim");
+	if (scratch.len_ < gkr_gpa_scratch_elems(n_vars)) throw Error(Error::InputValidation, "scratch holds fewer than sum 2^n_vars + 2^(max n_vars - 1) elements");
+	GkrGpaOutput out;
+	out.products.resize(k);
+	out.final_points.resize(k);
+	out.final_evals.resize(k);
+	if (k == 0) return out;
+
+	// ---- the witnesses: every layer of every tree in one call
+	{
+		std::vector<uint32_t> nv(k);
+		std::vector<const void *> ins(k);
+		std::vector<uint64_t> lens(k);
+		std::vector<void *> ars(k);
+		for (size_t t = 0; t < k; t++) {
+			if (n_vars[t] >= 1 && arenas[t].len_ != (size_t)1 << n_vars[t]) throw Error(Error::InputValidation, "an arena holds 2^n_vars elements");
+			nv[t] = (uint32_t)n_vars[t];
+			ins[t] = inputs[t].len_ ? inputs[t].ptr : nullptr;
+			lens[t] = inputs[t].len_;
+			ars[t] = arenas[t].ptr;
+		}
+		check(bn_product_tree_layers(hal.raw_ctx(), (uint32_t)k, nv.data(), ins.data(), lens.data(), ars.data(), reinterpret_cast<bn_f128 *>(out.products.data())));
+	}
+	// ---- full-length copies of the inputs (the last layer each tree's sumchecks fold)
+	std::vector<FSliceMut> padded(k);
+	size_t used = 0;
+	{
+		std::vector<uint32_t> ll;
+		std::vector<const void *> srcs;
+		std::vector<uint64_t> lens;
+		std::vector<void *> dsts;
+		for (size_t t = 0; t < k; t++) {
+			if (n_vars[t] == 0) continue;
+			padded[t] = FSliceMut{(char *)scratch.ptr + used * sizeof(B128), (size_t)1 << n_vars[t]};
+			used += padded[t].len_;
+			ll.push_back((uint32_t)n_vars[t]);
+			srcs.push_back(inputs[t].len_ ? inputs[t].ptr : nullptr);
+			lens.push_back(inputs[t].len_);
+			dsts.push_back(padded[t].ptr);
+		}
+		check(bn_pad_with_ones(hal.raw_ctx(), (uint32_t)ll.size(), ll.data(), srcs.data(), lens.data(), dsts.data()));
+	}
+	const FSliceMut eq_scratch{(char *)scratch.ptr + used * sizeof(B128), scratch.len_ - used};
+
+	// ---- the states, sorted stably by n_vars descending (:61-62)
+	std::vector<size_t> order(k);
+	for (size_t t = 0; t < k; t++) order[t] = t;
+	std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return n_vars[a] > n_vars[b]; });
+	std::vector<B128> layer_eval = out.products; // (GrandProductProverState::new, :185-189)
+	std::vector<B128> eval_point;
+	// claim i of a step is var(2i) var(2i + 1); its leading form is itself
+	std::vector<EqIndComposition> all_comps;
+	size_t n_multi = 0;
+	for (size_t n : n_vars) n_multi += n >= 2;
+	for (size_t i = 0; i < n_multi; i++) {
+		EqIndComposition ec;
+		ec.composition = hal.compile_expr(ArithCircuit::var(2 * i) * ArithCircuit::var(2 * i + 1));
+		ec.composition_at_infinity = ec.composition;
+		ec.degree = 2;
+		all_comps.push_back(ec);
+	}
+	size_t ch_at = 0;
+	for (size_t j = 0;; j++) {
+		// process_finished_provers (:143-161)
+		for (size_t t : order)
+			if (n_vars[t] == j) {
+				out.final_points[t] = eval_point;
+				out.final_evals[t] = layer_eval[t];
+			}
+		std::vector<size_t> active;
+		for (size_t t : order)
+			if (n_vars[t] > j) active.push_back(t);
+		if (active.empty()) break;
+		const auto t_begin = std::chrono::steady_clock::now();
+		const B128 batch_coeff = batch_coeffs[j], gpa_challenge = gpa_challenges[j];
+		// layer j + 1 of every active state: its arena, or the padded copy of its input
+		std::vector<const char *> layer(active.size());
+		for (size_t i = 0; i < active.size(); i++) {
+			const size_t t = active[i];
+			layer[i] = j + 1 == n_vars[t] ? (const char *)padded[t].ptr : (const char *)arenas[t].ptr + (((size_t)1 << (j + 1)) * sizeof(B128));
+		}
+		std::vector<B128> finals, proofs, challenges;
+		if (j == 0) {
+			// zero variables: the "final evaluations" are the two elements of layer 1, the indicator's prefix is ONE
+			const char *base = *std::min_element(layer.begin(), layer.end());
+			std::vector<uint64_t> offs;
+			for (const char *p : layer) offs.push_back((uint64_t)(p - base) / sizeof(B128));
+			finals.resize(2 * active.size());
+			check(bn_gather_d2h(hal.raw_ctx(), base, offs.data(), offs.size(), 2, reinterpret_cast<bn_f128 *>(finals.data())));
+			finals.push_back(B128::ONE());
+		} else {
+			const size_t half = (size_t)1 << j;
+			std::vector<SumcheckMultilinear> mls;
+			std::vector<B128> sums;
+			for (size_t i = 0; i < active.size(); i++) {
+				mls.push_back(SumcheckMultilinear::folded(FSlice{layer[i], half}));
+				mls.push_back(SumcheckMultilinear::folded(FSlice{layer[i] + half * sizeof(B128), half}));
+				sums.push_back(layer_eval[active[i]]);
+			}
+			DeviceBumpAllocator eq_alloc(eq_scratch);
+			// eq_ind_expand, High-to-Low: the tensor expansion of all challenges but the last (eq_ind.rs:430-446)
+			const FSlice table = backend.tensor_product_full_query(std::vector<B128>(eval_point.begin(), eval_point.end() - 1), eq_alloc);
+			EqIndSumcheckProver prover(hal, backend, eq_alloc, j, std::move(mls), std::vector<EqIndComposition>(all_comps.begin(), all_comps.begin() + active.size()),
+			                           std::move(sums), eval_point, FSliceMut{const_cast<void *>(table.ptr), table.len_});
+			for (size_t r = 0; r < j; r++) {
+				const std::vector<B128> rc = prover.execute(batch_coeff);
+				for (size_t i = 0; i + 1 < rc.size(); i++) proofs.push_back(rc[i] * batch_coeff); // (front_loaded.rs:131-136)
+				const B128 z = sumcheck_challenges[ch_at + r];
+				challenges.push_back(z);
+				prover.fold(z);
+			}
+			ch_at += j;
+			finals = prover.finish();
+			std::reverse(challenges.begin(), challenges.end()); // (:106-108)
+		}
+		eval_point = challenges;
+		eval_point.push_back(gpa_challenge);
+		for (size_t i = 0; i < active.size(); i++) {
+			const B128 e0 = finals[2 * i], e1 = finals[2 * i + 1];
+			layer_eval[active[i]] = e0 + gpa_challenge * (e1 + e0); // extrapolate_line_scalar (:282-284)
+		}
+		out.round_proofs.push_back(std::move(proofs));
+		out.layer_evals.push_back(std::move(finals));
+		out.step_ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+	}
+	return out;
+}
+
+} // namespace binius_amd

@@ -26,6 +26,7 @@
 
 #include "eq_ind.hpp"
 #include "fri.hpp"
+#include "gkr_gpa.hpp"
 #include "piop.hpp"
 #include "sumcheck.hpp"
 
@@ -894,6 +895,61 @@ int bnh_eqind_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void 
 			fprintf(stderr, "[bnh prof] eq-ind sumcheck, %u rounds, %u multilinears, %u compositions: set-up %.1f us, execute %.1f us, fold %.1f us, finish %.1f us\n", n_vars,
 			        n_mls, n_comps, std::chrono::duration<double, std::micro>(t_setup - t_begin).count(), us_exec, us_fold,
 			        std::chrono::duration<double, std::micro>(now() - t_rounds).count());
+		return 0;
+	} catch (const Error &e) {
+		g_err = e.what();
+		return (int)e.kind();
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return BN_ERR_CORE_LIB;
+	}
+}
+
+// gkr_gpa::batch_prove (crates/core/src/protocols/gkr_gpa/prove.rs:33-296) through the C++ mirror binius_amd/host/gkr_gpa.hpp; the
+// arguments are described in include/binius_amd_host.h.
+int bnh_gkr_gpa_prove(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, const void *const *d_inputs, const uint64_t *input_lens, void *const *d_arenas,
+                      void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *sumcheck_challenges, const bn_f128 *gpa_challenges,
+                      bn_f128 *products_out, bn_f128 *round_proofs_out, bn_f128 *layer_evals_out, bn_f128 *final_points_out, bn_f128 *final_evals_out,
+                      double *step_ms_out)
+{
+	try {
+		if (!ctx) throw Error(Error::InputValidation, "null ctx");
+		if (n_claims == 0) return 0;
+		if (!n_vars || !d_inputs || !input_lens || !d_arenas || !products_out || !final_evals_out) throw Error(Error::InputValidation, "null argument");
+		size_t max_n = 0;
+		std::vector<size_t> nv(n_claims);
+		std::vector<FSlice> ins(n_claims);
+		std::vector<FSliceMut> ars(n_claims);
+		for (uint32_t t = 0; t < n_claims; t++) {
+			if (n_vars[t] > BN_PRODUCT_TREE_MAX_VARS) throw Error(Error::InputValidation, "n_vars out of range (0 .. 28)");
+			nv[t] = n_vars[t];
+			max_n = std::max(max_n, nv[t]);
+			ins[t] = FSlice{d_inputs[t], (size_t)input_lens[t]};
+			if (nv[t] >= 1 && !d_arenas[t]) throw Error(Error::InputValidation, "null layer arena");
+			ars[t] = FSliceMut{d_arenas[t], (size_t)1 << nv[t]};
+		}
+		if (max_n >= 1 && (!d_scratch || !batch_coeffs || !gpa_challenges || !layer_evals_out || !final_points_out)) throw Error(Error::InputValidation, "null argument");
+		if (max_n >= 2 && (!sumcheck_challenges || !round_proofs_out)) throw Error(Error::InputValidation, "null argument");
+		auto vec = [](const bn_f128 *p, size_t n) {
+			std::vector<B128> v;
+			for (size_t i = 0; i < n; i++) v.emplace_back(p[i].lo, p[i].hi);
+			return v;
+		};
+		ComputeLayer hal(ctx);
+		Mi355xBackend backend(hal);
+		const GkrGpaOutput out = gkr_gpa_batch_prove(hal, backend, nv, ins, ars, FSliceMut{d_scratch, (size_t)scratch_elems}, vec(batch_coeffs, max_n),
+		                                            vec(sumcheck_challenges, max_n * (max_n ? max_n - 1 : 0) / 2), vec(gpa_challenges, max_n));
+		size_t at_p = 0, at_e = 0, at_f = 0;
+		for (uint32_t t = 0; t < n_claims; t++) {
+			products_out[t] = out.products[t].raw();
+			final_evals_out[t] = out.final_evals[t].raw();
+			for (const B128 &v : out.final_points[t]) final_points_out[at_f++] = v.raw();
+		}
+		for (size_t j = 0; j < out.round_proofs.size(); j++) {
+			for (const B128 &v : out.round_proofs[j]) round_proofs_out[at_p++] = v.raw();
+			for (const B128 &v : out.layer_evals[j]) layer_evals_out[at_e++] = v.raw();
+			if (step_ms_out) step_ms_out[j] = out.step_ms[j];
+		}
 		return 0;
 	} catch (const Error &e) {
 		g_err = e.what();

@@ -219,6 +219,23 @@ unsafe extern "C" {
 		round_lens: *const u64,
 		n_rounds: u32,
 	) -> c_int;
+	pub fn bn_product_tree_layers(
+		ctx: *mut bn_ctx,
+		n_trees: u32,
+		n_vars: *const u32,
+		d_inputs: *const *const c_void,
+		input_lens: *const u64,
+		d_layers: *const *mut c_void,
+		products_out: *mut bn_f128,
+	) -> c_int;
+	pub fn bn_pad_with_ones(
+		ctx: *mut bn_ctx,
+		n: u32,
+		log_lens: *const u32,
+		d_srcs: *const *const c_void,
+		src_lens: *const u64,
+		d_dsts: *const *mut c_void,
+	) -> c_int;
 
 	pub fn bn_log_chunks_range(maps: *const bn_memmap, n_maps: u32, start: *mut u32, end: *mut u32) -> c_int;
 	pub fn bn_pick_log_chunks(maps: *const bn_memmap, n_maps: u32, log_chunks: *mut u32) -> c_int;

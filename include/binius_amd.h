@@ -141,6 +141,23 @@ int bn_compute_composite(bn_ctx *ctx, const void *const *d_rows, uint32_t n_rows
 /* pairwise_product_reduce (layer.rs:505) */
 int bn_pairwise_product_reduce(bn_ctx *ctx, const void *d_in, uint64_t n, void *const *d_round_outs,
                                const uint64_t *round_lens, uint32_t n_rounds);
+/* Every layer of a batch of halves-product trees: the witness of the GKR grand-product argument (GrandProductWitness::new,
+ * core/src/protocols/gkr_gpa/gkr_gpa.rs:38-90; the same layers as ProductCircuitLayers::compute, prodcheck/prove.rs:24-77),
+ *   layer_j[i] = layer_{j+1}[i] * layer_{j+1}[i + 2^j],  0 <= i < 2^j,  layer_{n_vars} = the input.
+ * Tree t has n_vars[t] in 0 .. 28 variables; d_inputs[t] holds input_lens[t] <= 2^n_vars[t] B128 elements, the absent tail counts
+ * as ONE (the truncated witness, gkr_gpa.rs:34-37, 70-73; input_lens[t] = 0 is legal, d_inputs[t] may then be NULL).  d_layers[t]
+ * is an arena of 2^n_vars[t] elements in heap order: on return arena[2^j + i] = element i of layer j for 0 <= j < n_vars (arena[1]
+ * is the product), arena[0] is not touched, every layer is written in full.  The two multilinears of layer j's sumcheck are the
+ * contiguous halves arena[2^(j+1) ..] and arena[2^(j+1) + 2^j ..].  Inputs are only read; an arena must not overlap its input.
+ * products_out[t] = layer 0 (n_vars = 0: the input element, or ONE; d_layers[t] is not used).  All trees share the launches
+ * of the largest one.  Returns when the products are on the host. */
+#define BN_PRODUCT_TREE_MAX_VARS 28
+int bn_product_tree_layers(bn_ctx *ctx, uint32_t n_trees, const uint32_t *n_vars, const void *const *d_inputs,
+                           const uint64_t *input_lens, void *const *d_layers, bn_f128 *products_out);
+/* d_dsts[t][i] = i < src_lens[t] ? d_srcs[t][i] : ONE for i < 2^log_lens[t], all n arrays in one launch: the full-length copies
+ * of truncated inputs that the grand-product prover folds (its sumcheck consumes what it works on).  Synchronises the stream. */
+int bn_pad_with_ones(bn_ctx *ctx, uint32_t n, const uint32_t *log_lens, const void *const *d_srcs, const uint64_t *src_lens,
+                     void *const *d_dsts);
 
 /* ---- accumulate_kernels / map_kernels (layer.rs:183, 236) + KernelExecutor (layer.rs:518-590).
  * The kernel-spec closure cannot cross an FFI: the host shim runs it ONCE against a recording

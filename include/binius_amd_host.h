@@ -136,6 +136,29 @@ int bnh_eqind_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void 
                              const bn_f128 *eq_ind_challenges, void *d_eq_ind, uint64_t eq_ind_elems, const bn_f128 *batch_coeff, const bn_f128 *challenges,
                              bn_f128 *round_coeffs_out, bn_f128 *final_evals_out);
 
+/* gkr_gpa::batch_prove (crates/core/src/protocols/gkr_gpa/prove.rs:33-296) through the C++ mirror binius_amd/host/gkr_gpa.hpp: the GKR
+ * grand-product argument over n_claims witnesses, which the constraint system runs for every flush and non-zero oracle
+ * (core/src/constraint_system/prove.rs:285-412), High-to-Low.  The witnesses' layers come from ONE bn_product_tree_layers; step
+ * j = 0, 1, ... first lets the claims with n_vars = j leave, then runs one EqIndSumcheckProver over j variables for the others as a
+ * front-loaded batch of one prover.
+ *   n_vars[t] in 0 .. 28; d_inputs[t]: input_lens[t] <= 2^n_vars[t] elements, only read (the absent tail counts as ONE)
+ *   d_arenas[t]: 2^n_vars[t] elements, the tree's layers in heap order -- CONSUMED by the sumchecks (NULL allowed for n_vars = 0)
+ *   d_scratch: at least sum_{n_vars[t] >= 1} 2^n_vars[t] + 2^(max n_vars - 1) elements: the ONE-padded copies of the inputs that each
+ *     tree's last step folds, and the indicator's table
+ *   batch_coeffs[max n_vars]: one per step (step 0 has no rounds: its coefficient is sampled and unused)
+ *   sumcheck_challenges: step j's j challenges, steps concatenated (max (max - 1) / 2);  gpa_challenges[max n_vars]
+ *   products_out[n_claims];  round_proofs_out: 3 coefficients per round, steps concatenated;
+ *   layer_evals_out: per step the 2 * active evaluations (claims in the sorted order: n_vars descending, stable) then the
+ *     indicator's prefix evaluation
+ *   final_points_out: claim t's evaluation point (n_vars[t] coordinates), claims concatenated in the callers' order -- a claim that
+ *     leaves at step j has the point of step j - 1 (its reversed challenges, then its layer challenge), which is NOT a prefix of a
+ *     longer claim's point, so every claim gets its own
+ *   final_evals_out[n_claims]: the callers' order (unsort, prove.rs:140);  step_ms_out[max n_vars]: wall time per step, or NULL */
+int bnh_gkr_gpa_prove(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, const void *const *d_inputs, const uint64_t *input_lens, void *const *d_arenas,
+                      void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *sumcheck_challenges, const bn_f128 *gpa_challenges,
+                      bn_f128 *products_out, bn_f128 *round_proofs_out, bn_f128 *layer_evals_out, bn_f128 *final_points_out, bn_f128 *final_evals_out,
+                      double *step_ms_out);
+
 /* shared-memory exchange: rank 0 creates the segment `name` ("/..."), the others open it afterwards */
 int bnh_shm_open(const char *name, int world, int rank, int create, void **handle_out);
 int bnh_shm_close(void *handle);
