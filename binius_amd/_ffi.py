@@ -163,6 +163,7 @@ def lib():
         "bn_arm_counters": [vp, C.POINTER(u64)],
         "bn_group_counters": [vp, C.POINTER(u64)],
         "bn_fp4_last_grids": [vp, C.POINTER(u64)],
+        "bn_ntt_counters": [vp, C.POINTER(u64)],
         "bn_xor_reduce": [vp, vp, u32, u32, PF],
         "bn_host_scratch": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)],
         "bn_device_numa_node": [C.c_int, C.POINTER(C.c_int)],
@@ -196,7 +197,7 @@ ABI_SYMBOLS = [
     "bn_extrapolate_line", "bn_extrapolate_line_batch", "bn_tensor_expand", "bn_inner_product", "bn_fold_left", "bn_fold_right", "bn_fri_fold",
     "bn_compute_composite", "bn_pairwise_product_reduce", "bn_log_chunks_range", "bn_pick_log_chunks",
     "bn_kernel_launch", "bn_ntt_forward", "bn_ntt_inverse", "bn_ntt_s_evals", "bn_scalar_mul", "bn_scalar_invert",
-    "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
+    "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_ntt_counters", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
     "bn_merkle_build", "bn_groestl256_leaves", "bn_groestl256_compress_layer", "bn_gather_d2h",
     "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals",
     "bn_product_tree_layers", "bn_pad_with_ones",
@@ -548,6 +549,13 @@ class Context:
         _check(lib().bn_fp4_last_grids(self._h, c))
         return {"re_grid": int(c[0]), "re_tiles": int(c[1]), "re_ws": int(c[2]), "fe_grid": int(c[3]), "fe_tiles": int(c[4]),
                 "re_max_tiles": int(c[5]), "fe_max_tiles": int(c[6])}
+
+    def ntt_counters(self):
+        """bn_ntt_forward / bn_ntt_inverse calls of this context served by each kernel family (bn_ntt_counters): the bit-sliced
+        kernels, the LDS-tiled kernel, the per-layer kernel.  Rejected calls and accepted no-ops count nowhere."""
+        c = (C.c_uint64 * 3)()
+        _check(lib().bn_ntt_counters(self._h, c))
+        return {"bs": int(c[0]), "tiled": int(c[1]), "layer": int(c[2])}
 
     # ---- ComputeLayer
     def copy_h2d(self, src, dst):

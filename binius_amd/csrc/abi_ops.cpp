@@ -355,7 +355,10 @@ static int ntt_common(bn_ctx *ctx, bool inverse, void *d_data, uint32_t elem_lev
 		prof_scope ps(ctx, BN_PROF_NTT);
 		hipError_t be = bn::launch_ntt_bs(ctx->stream, inverse, d_data, h_s_evals, log_domain, lx, log_y, log_z, coset, coset_bits,
 		                                  skip_rounds, scr, (bn::ntt_bs_cache *)ctx->ntt_cache);
-		if (be == hipSuccess) return BN_OK;
+		if (be == hipSuccess) {
+			ctx->ntt_calls_bs++;
+			return BN_OK;
+		}
 		if (be != hipErrorNotSupported) return bn::hip_fail(be, "launch_ntt_bs");
 	}
 	uint64_t *d_s = nullptr;
@@ -365,11 +368,15 @@ static int ntt_common(bn_ctx *ctx, bool inverse, void *d_data, uint32_t elem_lev
 	if (!bn::settled_knob("BN_NTT_PER_LAYER")) {
 		hipError_t te = bn::launch_ntt_tiled(ctx->stream, ctx->n_cu, inverse, d_data, elem_level, tw_level, ctx->d_mul8, d_s, log_domain,
 		                                     log_x, log_y, log_z, coset, coset_bits, skip_rounds);
-		if (te == hipSuccess) return BN_OK;
+		if (te == hipSuccess) {
+			ctx->ntt_calls_tiled++;
+			return BN_OK;
+		}
 		if (te != hipErrorNotSupported) return bn::hip_fail(te, "launch_ntt_tiled");
 	}
 	BN_HIP(bn::launch_ntt(ctx->stream, inverse, d_data, elem_level, tw_level, d_s, log_domain, log_x, log_y, log_z, coset,
 	                      coset_bits, skip_rounds));
+	ctx->ntt_calls_layer++;
 	return BN_OK;
 }
 
@@ -387,6 +394,16 @@ int bn_ntt_inverse(bn_ctx *ctx, void *d_data, uint32_t elem_level, uint32_t tw_l
 {
 	return ntt_common(ctx, true, d_data, elem_level, tw_level, h_s_evals, log_domain, log_x, log_y, log_z, coset, coset_bits,
 	                  skip_rounds);
+}
+
+int bn_ntt_counters(bn_ctx *ctx, uint64_t *counters)
+{
+	BN_REQUIRE(ctx && counters, "null argument");
+	BN_ENTER(ctx);
+	counters[BN_NTT_CALLS_BS] = ctx->ntt_calls_bs;
+	counters[BN_NTT_CALLS_TILED] = ctx->ntt_calls_tiled;
+	counters[BN_NTT_CALLS_LAYER] = ctx->ntt_calls_layer;
+	return BN_OK;
 }
 
 // OnTheFlyTwiddleAccess::generate over BinarySubspace::with_dim(log_domain)

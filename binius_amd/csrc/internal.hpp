@@ -76,6 +76,7 @@ struct bn_ctx {
 	uint8_t *d_mul8 = nullptr;         // 64 KiB GF(2^8) product table (tiled NTT)
 	uint64_t *d_s_evals = nullptr;     // the twiddle basis last handed to bn_ntt_* / bn_fri_fold (BN_NTT_MAX_DIM^2 words) ...
 	std::vector<uint64_t> h_s_evals;   // ... and its host copy: an NTT instance's basis is uploaded once, not per call
+	uint64_t ntt_calls_bs = 0, ntt_calls_tiled = 0, ntt_calls_layer = 0; // bn_ntt_* calls served per kernel family (bn_ntt_counters)
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	int n_cu = 256;

@@ -91,6 +91,7 @@ pub struct bn_kop {
 pub const BN_PROF_N: usize = 11;
 pub const BN_ARM_N: usize = 15;
 pub const BN_FP4_N: usize = 7;
+pub const BN_NTT_N: usize = 3;
 
 // ---- the old HAL (binius_hal::ComputationBackend) on device-resident multilinears
 pub const BN_ORDER_LOW_TO_HIGH: u32 = 0;
@@ -343,6 +344,7 @@ unsafe extern "C" {
 	pub fn bn_arm_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 	pub fn bn_group_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 	pub fn bn_fp4_last_grids(ctx: *mut bn_ctx, grids: *mut u64) -> c_int;
+	pub fn bn_ntt_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 	// cross-rank reduction of the round evaluations inside the kernels' finalize step (one process per GPU)
 	pub fn bn_peer_create(ctx: *mut bn_ctx, world: u32, rank: u32, handle_out: *mut u8) -> c_int;
 	pub fn bn_peer_connect(ctx: *mut bn_ctx, handles: *const u8) -> c_int;

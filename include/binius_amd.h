@@ -394,6 +394,12 @@ int bn_group_counters(bn_ctx *ctx, uint64_t *counters /*[BN_GROUP_N]*/);
  * of the process so far; zeros before the first such launch. */
 enum { BN_FP4_RE_GRID = 0, BN_FP4_RE_TILES = 1, BN_FP4_RE_WS = 2, BN_FP4_FE_GRID = 3, BN_FP4_FE_TILES = 4, BN_FP4_RE_MAX_TILES = 5, BN_FP4_FE_MAX_TILES = 6, BN_FP4_N = 7 };
 int bn_fp4_last_grids(bn_ctx *ctx, uint64_t *grids /*[BN_FP4_N]*/);
+/* Which kernel family served the bn_ntt_forward / bn_ntt_inverse calls of this context since it was created: the bit-sliced
+ * kernels (B32 twiddles, log_y >= 14), the LDS-tiled kernel (B8 .. B32 twiddles, B16 .. B128 elements, 2^12 elements and more) or the
+ * per-layer kernel (everything else).  Read-only; a call that is rejected, or an accepted no-op (log_y == 0, skip_rounds == log_y),
+ * counts nowhere. */
+enum { BN_NTT_CALLS_BS = 0, BN_NTT_CALLS_TILED = 1, BN_NTT_CALLS_LAYER = 2, BN_NTT_N = 3 };
+int bn_ntt_counters(bn_ctx *ctx, uint64_t *counters /*[BN_NTT_N]*/);
 
 #ifdef __cplusplus
 }
