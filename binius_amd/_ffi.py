@@ -147,6 +147,9 @@ def lib():
         "bn_pairwise_product_reduce": [vp, vp, u64, C.POINTER(vp), C.POINTER(u64), u32],
         "bn_product_tree_layers": [vp, u32, C.POINTER(u32), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), PF],
         "bn_pad_with_ones": [vp, u32, C.POINTER(u32), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp)],
+        "bn_exp_circuit_layers": [vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), PF, C.POINTER(vp), C.POINTER(vp)],
+        "bn_bits_to_b128": [vp, u32, C.POINTER(u32), C.POINTER(vp), C.POINTER(vp)],
+        "bn_exp_counters": [vp, C.POINTER(u64)],
         "bn_log_chunks_range": [C.POINTER(MemMap), u32, C.POINTER(u32), C.POINTER(u32)],
         "bn_pick_log_chunks": [C.POINTER(MemMap), u32, C.POINTER(u32)],
         "bn_kernel_launch": [vp, C.POINTER(MemMap), u32, C.POINTER(KOp), u32, C.POINTER(u32), u32, u32, PF, vp],
@@ -200,7 +203,7 @@ ABI_SYMBOLS = [
     "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_ntt_counters", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
     "bn_merkle_build", "bn_groestl256_leaves", "bn_groestl256_compress_layer", "bn_gather_d2h",
     "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals",
-    "bn_product_tree_layers", "bn_pad_with_ones",
+    "bn_product_tree_layers", "bn_pad_with_ones", "bn_exp_circuit_layers", "bn_bits_to_b128", "bn_exp_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -769,6 +772,43 @@ class Context:
         lens = (C.c_uint64 * max(1, n))(*[(x.len if x is not None else 0) for x in srcs])
         outs = (C.c_void_p * max(1, n))(*[d.ptr for d in dsts])
         _check(lib().bn_pad_with_ones(self._h, n, ll, ins, lens, outs))
+
+    def exp_circuit_layers(self, n_vars, bit_columns, bases, arenas, kinds=None):
+        """Every layer of a batch of exponentiation circuits in one launch (bn_exp_circuit_layers; gkr_exp/witness.rs:31-110, 139-156,
+        258-284).  Per witness: n_vars; bit_columns: its DevSlices e_0 (least significant) .. e_{w-1}, each a packed B1 multilinear
+        (bit i = bit i & 127 of element i >> 7; one element for n_vars < 7); bases: an int (the constant base g: static) or a
+        DevSlice of 2^n_vars elements (dynamic); arenas: a DevSlice of w * 2^n_vars elements receiving layer k at k * 2^n_vars.
+        kinds overrides the kind inferred from `bases` (0 static, 1 dynamic)."""
+        n = len(n_vars)
+        nv = (C.c_uint32 * max(1, n))(*n_vars)
+        wd = (C.c_uint32 * max(1, n))(*[len(b) for b in bit_columns])
+        if kinds is None:
+            kinds = [0 if isinstance(b, int) else 1 for b in bases]
+        kd = (C.c_uint32 * max(1, n))(*kinds)
+        flat = [(c.ptr if c is not None else None) for cols in bit_columns for c in cols]
+        cols = (C.c_void_p * max(1, len(flat)))(*flat)
+        sb = (F128 * max(1, n))(*[to_f128(b if isinstance(b, int) else 0) for b in bases])
+        db = (C.c_void_p * max(1, n))(*[(None if b is None or isinstance(b, int) else b.ptr) for b in bases])
+        for t, a in enumerate(arenas):
+            if a is not None and n_vars[t] <= 28 and a.len != len(bit_columns[t]) << n_vars[t]:
+                raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: exp circuit: an arena holds width * 2^n_vars elements")
+        outs = (C.c_void_p * max(1, n))(*[(a.ptr if a is not None else None) for a in arenas])
+        _check(lib().bn_exp_circuit_layers(self._h, n, nv, wd, kd, cols, sb, db, outs))
+
+    def bits_to_b128(self, log_lens, srcs, dsts):
+        """dsts[t][i] = bit i of srcs[t] ? ONE : ZERO for i < 2^log_lens[t], every array in one launch (bn_bits_to_b128)."""
+        n = len(log_lens)
+        ll = (C.c_uint32 * max(1, n))(*log_lens)
+        ins = (C.c_void_p * max(1, n))(*[(x.ptr if x is not None else None) for x in srcs])
+        outs = (C.c_void_p * max(1, n))(*[(d.ptr if d is not None else None) for d in dsts])
+        _check(lib().bn_bits_to_b128(self._h, n, ll, ins, outs))
+
+    def exp_counters(self):
+        """Accepted bn_exp_circuit_layers calls of this context, the kernel launches they made, and the launches of bn_bits_to_b128
+        (bn_exp_counters).  Rejected calls count nowhere."""
+        c = (C.c_uint64 * 3)()
+        _check(lib().bn_exp_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "bits_launches": int(c[2])}
 
     # ---- accumulate_kernels / map_kernels
     def pick_log_chunks(self, mem_maps):

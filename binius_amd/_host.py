@@ -74,6 +74,12 @@ def host_lib():
             C.POINTER(F128), C.POINTER(F128), C.POINTER(F128), C.POINTER(F128), C.POINTER(F128), C.POINTER(F128), C.POINTER(F128), C.POINTER(F128),
             C.POINTER(C.c_double),
         ]
+        U32P, VPP, FP = C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(F128)
+        L.bnh_gkr_exp_prove.restype = C.c_int
+        L.bnh_gkr_exp_prove.argtypes = [
+            C.c_void_p, C.c_uint32, U32P, U32P, VPP, FP, VPP, VPP, C.c_uint32, U32P, FP, FP, C.c_void_p, C.c_uint64, FP, FP,
+            U32P, U32P, U32P, FP, U32P, U32P, FP, U32P, U32P, FP, FP, C.POINTER(C.c_double),
+        ]
         L.bnh_rccl_open.argtypes = [C.c_char_p]
         L.bnh_rccl_unique_id.argtypes = [C.c_void_p]
         L.bnh_rccl_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -460,6 +466,90 @@ class GkrGpaPlan:
 
     def step_times_ms(self):
         return [self.step_ms[j] for j in range(self.max_n)]
+
+
+class GkrExpPlan:
+    """gkr_exp::batch_prove (bnh_gkr_exp_prove = binius_amd/host/gkr_exp.hpp; crates/core/src/protocols/gkr_exp/batch_prove.rs:46-315): the
+    GKR exponentiation argument over a batch of claims sorted by n_vars descending.  Per claim: n_vars; bit_columns: device slices e_0 ..
+    e_{w-1} (packed B1 multilinears, only read); bases: an int (static) or a device slice of 2^n_vars elements (dynamic, only read);
+    arenas: device slices of w * 2^n_vars elements, filled and then CONSUMED by run(); eval_points / evals: the claims; scratch: a device
+    slice of at least scratch_elems(n_vars, dynamic) elements; batch_coeffs[L][g], challenges[L][r]: the samples per layer (g-th sumcheck
+    prover, round r).  n_witnesses: how many witnesses the caller believes it passes (default: as many as claims)."""
+
+    @staticmethod
+    def scratch_elems(n_vars, dynamic):
+        return sum(((2 if d else 1) << n) + ((1 << (n - 1)) if n >= 1 else 0) for n, d in zip(n_vars, dynamic))
+
+    def __init__(self, hal, n_vars, bit_columns, bases, arenas, eval_points, evals, scratch, batch_coeffs, challenges, n_witnesses=None):
+        self.hal, self.n_vars, self.k = hal, list(n_vars), len(n_vars)
+        self.n_witnesses = self.k if n_witnesses is None else n_witnesses
+        self._keep = (bit_columns, bases, arenas, scratch)
+        k1 = max(1, self.k)
+        self.widths = [len(b) for b in bit_columns]
+        self.M, self.N = max(self.widths + [0]), max(1, max(self.n_vars + [0]))
+        max_n = max(self.n_vars + [0])
+        self.nv = (C.c_uint32 * k1)(*self.n_vars)
+        self.wd = (C.c_uint32 * k1)(*self.widths)
+        self.kd = (C.c_uint32 * k1)(*[0 if isinstance(b, int) else 1 for b in bases])
+        flat = [c.ptr for cols in bit_columns for c in cols]
+        self.cols = (C.c_void_p * max(1, len(flat)))(*flat)
+        self.sb = _f128_array([b if isinstance(b, int) else 0 for b in bases] or [0])
+        self.db = (C.c_void_p * k1)(*[(None if isinstance(b, int) else b.ptr) for b in bases])
+        self.ars = (C.c_void_p * k1)(*[(a.ptr if a is not None else None) for a in arenas])
+        self.pts = _f128_array([z for p in eval_points for z in p] or [0])
+        self.evs = _f128_array(list(evals) or [0])
+        self.scratch = scratch
+        M, N, K = max(1, self.M), self.N, k1
+        bc = [0] * (M * K)
+        for L, row in enumerate(batch_coeffs[: self.M]):
+            bc[L * K : L * K + min(K, len(row))] = list(row)[:K]
+        ch = [0] * (M * N)
+        for L, row in enumerate(challenges[: self.M]):
+            ch[L * max_n : L * max_n + min(max_n, len(row))] = list(row)[:max_n]
+        self.bc, self.ch = _f128_array(bc), _f128_array(ch)
+        self.n_layers = C.c_uint32(0)
+        self.rounds, self.coeff_cnt, self.proofs = (C.c_uint32 * M)(), (C.c_uint32 * (M * N))(), (F128 * (5 * M * N))()
+        self.n_provers, self.eval_cnt, self.ml_evals = (C.c_uint32 * M)(), (C.c_uint32 * (M * K))(), (F128 * (4 * M * K))()
+        self.n_lc, self.lc_nv = (C.c_uint32 * M)(), (C.c_uint32 * (2 * M * K))()
+        self.lc_pts, self.lc_evs = (F128 * (2 * M * K * N))(), (F128 * (2 * M * K))()
+        self.layer_ms = (C.c_double * M)()
+
+    def run(self):
+        rc = host_lib().bnh_gkr_exp_prove(self.hal._h, self.n_witnesses, self.wd, self.kd, self.cols, self.sb, self.db, self.ars, self.k, self.nv, self.pts,
+                                          self.evs, self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0,
+                                          self.bc, self.ch, C.byref(self.n_layers), self.rounds, self.coeff_cnt, self.proofs, self.n_provers, self.eval_cnt,
+                                          self.ml_evals, self.n_lc, self.lc_nv, self.lc_pts, self.lc_evs, self.layer_ms)
+        if rc != 0:
+            raise BnError(rc, host_lib().bnh_last_error().decode())
+
+    def output(self):
+        """The proof in the shape of tests/gkr_exp_ref.py exp_prove."""
+        K, N = max(1, self.k), self.N
+        proofs, evals, claims, at_c, at_e, at_p, at_v = [], [], [], 0, 0, 0, 0
+        for L in range(self.n_layers.value):
+            rounds = []
+            for r in range(self.rounds[L]):
+                cnt = self.coeff_cnt[L * N + r]
+                rounds.append([from_f128(self.proofs[at_c + i]) for i in range(cnt)])
+                at_c += cnt
+            proofs.append(rounds)
+            per = []
+            for g in range(self.n_provers[L]):
+                cnt = self.eval_cnt[L * K + g]
+                per.append([from_f128(self.ml_evals[at_e + i]) for i in range(cnt)])
+                at_e += cnt
+            evals.append(per)
+            lcs = []
+            for i in range(self.n_lc[L]):
+                n = self.lc_nv[L * 2 * K + i]
+                lcs.append(([from_f128(self.lc_pts[at_p + j]) for j in range(n)], from_f128(self.lc_evs[at_v])))
+                at_p += n
+                at_v += 1
+            claims.append(lcs)
+        return {"round_proofs": proofs, "multilinear_evals": evals, "layer_claims": claims}
+
+    def layer_times_ms(self):
+        return [self.layer_ms[L] for L in range(self.n_layers.value)]
 
 
 class ShmExchange:

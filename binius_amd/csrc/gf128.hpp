@@ -151,6 +151,32 @@ BN_HD inline f128 mul_subfield_slow(f128 a, uint64_t s, int iota)
 
 BN_HD inline f128 square_slow(f128 a) { return mul_slow(a, a); }
 
+// Squaring is GF(2)-linear.  For u = u0 + u1 X_{K-1} in T_K: u^2 = (u0^2 + u1^2) + (u1^2 X_{K-2}) X_{K-1}, since
+// X_{K-1}^2 = X_{K-1} X_{K-2} + 1 (X_0^2 = X_0 + 1).  Squares every 2^K-bit limb of a 64-bit word (K <= 6); T_0 is fixed.
+template <int K>
+BN_HD inline uint64_t square64(uint64_t a)
+{
+	if constexpr (K == 0) {
+		return a;
+	} else {
+		constexpr uint64_t M = lo_half_mask<K - 1>();
+		constexpr int H = 1 << (K - 1);
+		const uint64_t s = square64<K - 1>(a);
+		const uint64_t l0 = s & M, l1 = (s >> H) & M;
+		if constexpr (K == 1)
+			return (l0 ^ l1) | (l1 << H);
+		else
+			return (l0 ^ l1) | (mulx64<K - 2>(l1) << H);
+	}
+}
+
+// a^2 in BinaryField128b without a product: two 64-bit squarings and one multiplication by X_5
+BN_HD inline f128 square_tower(f128 a)
+{
+	const uint64_t l = square64<6>(a.lo), h = square64<6>(a.hi);
+	return f128{l ^ h, mulx64<5>(h)};
+}
+
 BN_HD inline f128 pow_slow(f128 a, uint64_t e)
 {
 	f128 r = f128_one();

@@ -77,6 +77,7 @@ struct bn_ctx {
 	uint64_t *d_s_evals = nullptr;     // the twiddle basis last handed to bn_ntt_* / bn_fri_fold (BN_NTT_MAX_DIM^2 words) ...
 	std::vector<uint64_t> h_s_evals;   // ... and its host copy: an NTT instance's basis is uploaded once, not per call
 	uint64_t ntt_calls_bs = 0, ntt_calls_tiled = 0, ntt_calls_layer = 0; // bn_ntt_* calls served per kernel family (bn_ntt_counters)
+	uint64_t exp_calls = 0, exp_launches = 0, exp_bits_launches = 0;     // bn_exp_circuit_layers / bn_bits_to_b128 (bn_exp_counters)
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	int n_cu = 256;
@@ -735,6 +736,29 @@ hipError_t launch_prodtree_small(hipStream_t s, const prodtree_job *d_jobs, uint
 hipError_t launch_prodtree_big(hipStream_t s, int n_cu, const prodtree_job *d_jobs, uint32_t n_jobs, uint32_t total_runs, bool dual);
 hipError_t launch_prodtree_roots(hipStream_t s, const f128 *const *d_srcs, uint32_t n, f128 *d_out);
 hipError_t launch_prodtree_pad(hipStream_t s, const prodtree_job *d_jobs, uint32_t n_jobs, uint32_t total_blocks);
+
+// ---- kernels_expcircuit.hip: the layers of a batch of exponentiation circuits (the GKR exponentiation witness,
+// gkr_exp/witness.rs:31-110, 139-156, 258-284).  A job is one witness; a unit is a run of kExpRun rows that one wave takes through
+// every layer of its witness.
+struct expc_job {
+	const uint32_t *const *bits; // `width` device pointers to the bit columns, e_0 first
+	const f128 *base;            // dynamic: the base column; static: the `width` constants g^(2^k)
+	f128 *arena;                 // layer k at arena + k * rows
+	uint64_t rows;               // 2^n_vars
+	uint32_t width, dynamic;
+	uint32_t start;              // first unit of this job in the launch
+	uint32_t pad_;
+};
+constexpr uint32_t kExpRun = 224; // rows of a unit: one wave-batch of the bit-sliced product
+hipError_t launch_expcircuit(hipStream_t s, int n_cu, const expc_job *d_jobs, uint32_t n_jobs, uint32_t total_units);
+// dst[i] = bit i of src ? ONE : ZERO for i < rows (start: the job's first block of 256 elements)
+struct bits_job {
+	const uint32_t *src;
+	f128 *dst;
+	uint64_t rows;
+	uint32_t start, pad_;
+};
+hipError_t launch_bits_to_b128(hipStream_t s, const bits_job *d_jobs, uint32_t n_jobs, uint32_t total_blocks);
 
 // ---- kernels_ntt_tiled.hip
 hipError_t launch_build_mul8(hipStream_t s, uint8_t *d_tab);

@@ -26,6 +26,7 @@
 
 #include "eq_ind.hpp"
 #include "fri.hpp"
+#include "gkr_exp.hpp"
 #include "gkr_gpa.hpp"
 #include "piop.hpp"
 #include "sumcheck.hpp"
@@ -949,6 +950,90 @@ int bnh_gkr_gpa_prove(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, co
 			for (const B128 &v : out.round_proofs[j]) round_proofs_out[at_p++] = v.raw();
 			for (const B128 &v : out.layer_evals[j]) layer_evals_out[at_e++] = v.raw();
 			if (step_ms_out) step_ms_out[j] = out.step_ms[j];
+		}
+		return 0;
+	} catch (const Error &e) {
+		g_err = e.what();
+		return (int)e.kind();
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return BN_ERR_CORE_LIB;
+	}
+}
+
+// gkr_exp::batch_prove (crates/core/src/protocols/gkr_exp/batch_prove.rs:46-315) through the C++ mirror binius_amd/host/gkr_exp.hpp; the
+// arguments and the layout of the outputs are described in include/binius_amd_host.h.
+int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths, const uint32_t *kinds, const void *const *d_exponent_bits,
+                      const bn_f128 *static_bases, const void *const *d_bases, void *const *d_arenas, uint32_t n_claims, const uint32_t *n_vars,
+                      const bn_f128 *eval_points, const bn_f128 *evals, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs,
+                      const bn_f128 *challenges, uint32_t *n_layers_out, uint32_t *rounds_per_layer_out, uint32_t *coeffs_per_round_out,
+                      bn_f128 *round_proofs_out, uint32_t *provers_per_layer_out, uint32_t *evals_per_prover_out, bn_f128 *multilinear_evals_out,
+                      uint32_t *claims_per_layer_out, uint32_t *claim_n_vars_out, bn_f128 *claim_points_out, bn_f128 *claim_evals_out, double *layer_ms_out)
+{
+	try {
+		if (!ctx) throw Error(Error::InputValidation, "null ctx");
+		if (n_witnesses != n_claims) throw Error(Error::InputValidation, "MismatchedWitnessClaimLength");
+		if (n_layers_out) *n_layers_out = 0;
+		if (n_claims == 0) return 0;
+		if (!widths || !kinds || !d_exponent_bits || !static_bases || !d_bases || !d_arenas || !n_vars || !evals || !batch_coeffs || !n_layers_out ||
+		    !rounds_per_layer_out || !coeffs_per_round_out || !round_proofs_out || !provers_per_layer_out || !evals_per_prover_out || !multilinear_evals_out ||
+		    !claims_per_layer_out || !claim_n_vars_out || !claim_points_out || !claim_evals_out)
+			throw Error(Error::InputValidation, "null argument");
+		const size_t k = n_claims;
+		size_t max_w = 0, max_n = 0, at_bits = 0, at_pt = 0;
+		std::vector<GkrExpClaim> claims(k);
+		for (size_t t = 0; t < k; t++) {
+			GkrExpClaim &c = claims[t];
+			if (n_vars[t] > BN_EXP_MAX_VARS) throw Error(Error::InputValidation, "n_vars out of range (0 .. 28)");
+			if (widths[t] < 1 || widths[t] > BN_EXP_MAX_WIDTH) throw Error(Error::InputValidation, "width out of range (1 .. 128)");
+			if (kinds[t] != BN_EXP_STATIC && kinds[t] != BN_EXP_DYNAMIC) throw Error(Error::InputValidation, "unknown kind");
+			c.n_vars = n_vars[t];
+			c.width = widths[t];
+			c.dynamic = kinds[t] == BN_EXP_DYNAMIC;
+			c.static_base = B128(static_bases[t].lo, static_bases[t].hi);
+			c.base = FSlice{d_bases[t], c.dynamic ? (size_t)1 << c.n_vars : 0};
+			c.bits.assign(d_exponent_bits + at_bits, d_exponent_bits + at_bits + c.width);
+			at_bits += c.width;
+			c.arena = FSliceMut{d_arenas[t], c.width << c.n_vars};
+			if (c.n_vars && !eval_points) throw Error(Error::InputValidation, "null argument");
+			for (size_t i = 0; i < c.n_vars; i++) c.eval_point.emplace_back(eval_points[at_pt + i].lo, eval_points[at_pt + i].hi);
+			at_pt += c.n_vars;
+			c.eval = B128(evals[t].lo, evals[t].hi);
+			max_w = std::max(max_w, c.width);
+			max_n = std::max(max_n, c.n_vars);
+		}
+		if (max_n && !challenges) throw Error(Error::InputValidation, "null argument");
+		if (!d_scratch && scratch_elems) throw Error(Error::InputValidation, "null argument");
+		auto vec = [](const bn_f128 *p, size_t n) {
+			std::vector<B128> v;
+			for (size_t i = 0; i < n; i++) v.emplace_back(p[i].lo, p[i].hi);
+			return v;
+		};
+		ComputeLayer hal(ctx);
+		Mi355xBackend backend(hal);
+		const GkrExpOutput out = gkr_exp_batch_prove(hal, backend, n_witnesses, claims, FSliceMut{d_scratch, (size_t)scratch_elems}, vec(batch_coeffs, max_w * k),
+		                                            vec(challenges, max_w * max_n));
+		*n_layers_out = (uint32_t)out.round_proofs.size();
+		size_t at_c = 0, at_e = 0, at_p = 0, at_v = 0;
+		for (size_t L = 0; L < out.round_proofs.size(); L++) {
+			rounds_per_layer_out[L] = (uint32_t)out.round_proofs[L].size();
+			for (size_t r = 0; r < out.round_proofs[L].size(); r++) {
+				coeffs_per_round_out[L * std::max<size_t>(max_n, 1) + r] = (uint32_t)out.round_proofs[L][r].size();
+				for (const B128 &v : out.round_proofs[L][r]) round_proofs_out[at_c++] = v.raw();
+			}
+			provers_per_layer_out[L] = (uint32_t)out.multilinear_evals[L].size();
+			for (size_t g = 0; g < out.multilinear_evals[L].size(); g++) {
+				evals_per_prover_out[L * k + g] = (uint32_t)out.multilinear_evals[L][g].size();
+				for (const B128 &v : out.multilinear_evals[L][g]) multilinear_evals_out[at_e++] = v.raw();
+			}
+			claims_per_layer_out[L] = (uint32_t)out.layer_claims[L].size();
+			for (size_t i = 0; i < out.layer_claims[L].size(); i++) {
+				const GkrExpLayerClaim &lc = out.layer_claims[L][i];
+				claim_n_vars_out[L * 2 * k + i] = (uint32_t)lc.eval_point.size();
+				for (const B128 &v : lc.eval_point) claim_points_out[at_p++] = v.raw();
+				claim_evals_out[at_v++] = lc.eval.raw();
+			}
+			if (layer_ms_out) layer_ms_out[L] = out.layer_ms[L];
 		}
 		return 0;
 	} catch (const Error &e) {

@@ -92,6 +92,11 @@ pub const BN_PROF_N: usize = 11;
 pub const BN_ARM_N: usize = 15;
 pub const BN_FP4_N: usize = 7;
 pub const BN_NTT_N: usize = 3;
+pub const BN_EXP_N: usize = 3;
+pub const BN_EXP_STATIC: u32 = 0;
+pub const BN_EXP_DYNAMIC: u32 = 1;
+pub const BN_EXP_MAX_VARS: u32 = 28;
+pub const BN_EXP_MAX_WIDTH: u32 = 128;
 
 // ---- the old HAL (binius_hal::ComputationBackend) on device-resident multilinears
 pub const BN_ORDER_LOW_TO_HIGH: u32 = 0;
@@ -237,6 +242,19 @@ unsafe extern "C" {
 		src_lens: *const u64,
 		d_dsts: *const *mut c_void,
 	) -> c_int;
+	pub fn bn_exp_circuit_layers(
+		ctx: *mut bn_ctx,
+		n_witnesses: u32,
+		n_vars: *const u32,
+		widths: *const u32,
+		kinds: *const u32,
+		d_exponent_bits: *const *const c_void,
+		static_bases: *const bn_f128,
+		d_bases: *const *const c_void,
+		d_layers: *const *mut c_void,
+	) -> c_int;
+	pub fn bn_bits_to_b128(ctx: *mut bn_ctx, n: u32, log_lens: *const u32, d_srcs: *const *const c_void, d_dsts: *const *mut c_void) -> c_int;
+	pub fn bn_exp_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 
 	pub fn bn_log_chunks_range(maps: *const bn_memmap, n_maps: u32, start: *mut u32, end: *mut u32) -> c_int;
 	pub fn bn_pick_log_chunks(maps: *const bn_memmap, n_maps: u32, log_chunks: *mut u32) -> c_int;

@@ -158,6 +158,33 @@ int bn_product_tree_layers(bn_ctx *ctx, uint32_t n_trees, const uint32_t *n_vars
  * of truncated inputs that the grand-product prover folds (its sumcheck consumes what it works on).  Synchronises the stream. */
 int bn_pad_with_ones(bn_ctx *ctx, uint32_t n, const uint32_t *log_lens, const void *const *d_srcs, const uint64_t *src_lens,
                      void *const *d_dsts);
+/* Every layer of a batch of exponentiation circuits: the witness of the GKR exponentiation argument (core/src/protocols/gkr_exp/
+ * witness.rs:31-110 the static base, :139-156, 258-284 the dynamic base; built at constraint_system/prove.rs:186-195).  Witness t
+ * has n_vars[t] in 0 .. 28 variables (2^n_vars rows), an exponent of widths[t] in 1 .. 128 bit columns e_0 (least significant)
+ * .. e_{w-1}, and kinds[t]: BN_EXP_STATIC with the constant base g = static_bases[t], or BN_EXP_DYNAMIC with the column
+ * d_bases[t] of 2^n_vars B128 elements (the entry of the other kind is ignored).  Its w layers of 2^n_vars B128 elements are
+ *   static :  V_0[i] = e_0[i] ? g : 1              V_k[i] = V_{k-1}[i]   * (e_k[i] ? g^(2^k) : 1)
+ *   dynamic:  V_0[i] = e_{w-1}[i] ? base[i] : 1    V_k[i] = V_{k-1}[i]^2 * (e_{w-1-k}[i] ? base[i] : 1)
+ * (note the opposite bit orders); V_{w-1} is the exponentiation result.  All in B128: a base of a subfield is passed embedded,
+ * which is the identity on the low bits.  d_exponent_bits is a HOST array of sum(widths) device pointers, witness after witness,
+ * e_0 first.  A bit column is a B1 multilinear packed into F as bn_hal_multilinear describes for tower level 0: bit i of the
+ * column is bit i & 127 of 16-byte element i >> 7, little-endian; for n_vars < 7 the low 2^n_vars bits of one element.
+ * d_layers[t] is an arena of widths[t] * 2^n_vars[t] elements, layer k at offset k * 2^n_vars.  Inputs are only read, every layer
+ * is written in full, an arena must not overlap its witness's inputs; pointers are 16-byte aligned.  The whole batch is ONE
+ * launch whatever the widths and the number of witnesses.  Returns when the layers are complete. */
+enum { BN_EXP_STATIC = 0, BN_EXP_DYNAMIC = 1 };
+#define BN_EXP_MAX_VARS 28
+#define BN_EXP_MAX_WIDTH 128
+int bn_exp_circuit_layers(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *n_vars, const uint32_t *widths, const uint32_t *kinds,
+                          const void *const *d_exponent_bits, const bn_f128 *static_bases, const void *const *d_bases,
+                          void *const *d_layers);
+/* d_dsts[t][i] = bit i of d_srcs[t] ? ONE : ZERO for i < 2^log_lens[t] (bits packed as above), all n arrays in one launch: the bit
+ * columns as the B128 multilinears that the exponentiation prover folds.  Synchronises the stream. */
+int bn_bits_to_b128(bn_ctx *ctx, uint32_t n, const uint32_t *log_lens, const void *const *d_srcs, void *const *d_dsts);
+/* Read-only, per context (not part of the reference interface): accepted bn_exp_circuit_layers calls, the kernel launches they
+ * made, and the launches of bn_bits_to_b128.  A rejected call counts nowhere. */
+enum { BN_EXP_CALLS = 0, BN_EXP_LAUNCHES = 1, BN_EXP_BITS_LAUNCHES = 2, BN_EXP_N = 3 };
+int bn_exp_counters(bn_ctx *ctx, uint64_t *counters /*[BN_EXP_N]*/);
 
 /* ---- accumulate_kernels / map_kernels (layer.rs:183, 236) + KernelExecutor (layer.rs:518-590).
  * The kernel-spec closure cannot cross an FFI: the host shim runs it ONCE against a recording

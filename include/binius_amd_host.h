@@ -159,6 +159,36 @@ int bnh_gkr_gpa_prove(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, co
                       bn_f128 *products_out, bn_f128 *round_proofs_out, bn_f128 *layer_evals_out, bn_f128 *final_points_out, bn_f128 *final_evals_out,
                       double *step_ms_out);
 
+/* gkr_exp::batch_prove (crates/core/src/protocols/gkr_exp/batch_prove.rs:46-315; provers.rs:20-385, compositions.rs:43-61, utils.rs:5-10)
+ * through the C++ mirror binius_amd/host/gkr_exp.hpp: the GKR exponentiation argument over n_claims claims, which the constraint system runs
+ * for every Exp of its tables (core/src/constraint_system/prove.rs:236-274), High-to-Low.  The witnesses' layers come from ONE
+ * bn_exp_circuit_layers, made here.  Layer L = 0 .. max width - 1 groups the consecutive active provers with equal evaluation points
+ * (batch_prove.rs:123-196), runs one EqIndSumcheckProver per group that has a claim, batched by sumcheck::batch_prove
+ * (prove/batch_sumcheck.rs:102-199), emits the LayerClaims (batch_prove.rs:254-291) and retires the provers whose last layer it was (:112).
+ *   n_witnesses must equal n_claims (MismatchedWitnessClaimLength, :63-65); the claims sorted by n_vars descending (ClaimsOutOfOrder, :73-76)
+ *   widths / kinds / d_exponent_bits / static_bases / d_bases: as bn_exp_circuit_layers takes them; all only read
+ *   d_arenas[t]: widths[t] * 2^n_vars[t] elements -- filled, then CONSUMED by the sumchecks
+ *   eval_points: claim t's n_vars[t] coordinates, claims concatenated;  evals[n_claims]: the claimed evaluations of the result layers
+ *   d_scratch: at least sum_t ((kind_t dynamic ? 2 : 1) * 2^n_vars[t] + (n_vars[t] >= 1 ? 2^(n_vars[t] - 1) : 0)) elements: per layer the
+ *     bit columns as B128 multilinears, the copies of the dynamic bases, the indicators' tables (reused layer by layer)
+ *   batch_coeffs[max_width * n_claims]: [L * n_claims + g] = the coefficient of the g-th sumcheck prover of layer L (the groups that yield
+ *     a prover, in order; other slots ignored);  challenges[max_width * max_n_vars]: [L * max_n_vars + r] = round r of layer L
+ * Outputs (counts explicit; M = max_width, N = max(1, max_n_vars), K = n_claims):
+ *   *n_layers_out = M;  rounds_per_layer_out[M];  coeffs_per_round_out[M * N]: [L * N + r] = coefficients of round r of layer L (3, or 5
+ *     once a dynamic prover below its last layer is active);  round_proofs_out[<= 5 * M * N]: the coefficients, rounds and layers concatenated
+ *   provers_per_layer_out[M] (0: the layer had no sumcheck);  evals_per_prover_out[M * K]: [L * K + g];  multilinear_evals_out[<= 4 * M * K]: as
+ *     written to the transcript, the indicator's evaluation last in every prover's list
+ *   claims_per_layer_out[M];  claim_n_vars_out[M * 2 * K]: [L * 2 * K + i] = coordinates of claim i of layer L;  claim_points_out
+ *     [<= 2 * M * K * N] and claim_evals_out[<= 2 * M * K]: concatenated, in the reference's order (per prover the bit claim, then for a
+ *     dynamic base the base claim)
+ *   layer_ms_out[M]: wall time per layer, or NULL */
+int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths, const uint32_t *kinds, const void *const *d_exponent_bits,
+                      const bn_f128 *static_bases, const void *const *d_bases, void *const *d_arenas, uint32_t n_claims, const uint32_t *n_vars,
+                      const bn_f128 *eval_points, const bn_f128 *evals, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs,
+                      const bn_f128 *challenges, uint32_t *n_layers_out, uint32_t *rounds_per_layer_out, uint32_t *coeffs_per_round_out,
+                      bn_f128 *round_proofs_out, uint32_t *provers_per_layer_out, uint32_t *evals_per_prover_out, bn_f128 *multilinear_evals_out,
+                      uint32_t *claims_per_layer_out, uint32_t *claim_n_vars_out, bn_f128 *claim_points_out, bn_f128 *claim_evals_out, double *layer_ms_out);
+
 /* shared-memory exchange: rank 0 creates the segment `name` ("/..."), the others open it afterwards */
 int bnh_shm_open(const char *name, int world, int rank, int create, void **handle_out);
 int bnh_shm_close(void *handle);
