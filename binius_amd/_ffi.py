@@ -58,6 +58,12 @@ class MemMap(C.Structure):
     ]
 
 
+class PeColumn(C.Structure):
+    """bn_pe_column: one column of bn_partial_eval_high_batch."""
+
+    _fields_ = [("d_evals", C.c_void_p), ("tower_level", C.c_uint32), ("n_vars", C.c_uint32)]
+
+
 class HalMultilinear(C.Structure):
     """bn_hal_multilinear: SumcheckMultilinear::{Folded, Transparent} (crates/hal/src/common.rs)."""
 
@@ -150,6 +156,8 @@ def lib():
         "bn_exp_circuit_layers": [vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), PF, C.POINTER(vp), C.POINTER(vp)],
         "bn_bits_to_b128": [vp, u32, C.POINTER(u32), C.POINTER(vp), C.POINTER(vp)],
         "bn_exp_counters": [vp, C.POINTER(u64)],
+        "bn_partial_eval_high_batch": [vp, vp, u32, vp, u32, C.POINTER(vp)],
+        "bn_partial_eval_counters": [vp, C.POINTER(u64)],
         "bn_log_chunks_range": [C.POINTER(MemMap), u32, C.POINTER(u32), C.POINTER(u32)],
         "bn_pick_log_chunks": [C.POINTER(MemMap), u32, C.POINTER(u32)],
         "bn_kernel_launch": [vp, C.POINTER(MemMap), u32, C.POINTER(KOp), u32, C.POINTER(u32), u32, u32, PF, vp],
@@ -204,6 +212,7 @@ ABI_SYMBOLS = [
     "bn_merkle_build", "bn_groestl256_leaves", "bn_groestl256_compress_layer", "bn_gather_d2h",
     "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals",
     "bn_product_tree_layers", "bn_pad_with_ones", "bn_exp_circuit_layers", "bn_bits_to_b128", "bn_exp_counters",
+    "bn_partial_eval_high_batch", "bn_partial_eval_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -809,6 +818,30 @@ class Context:
         c = (C.c_uint64 * 3)()
         _check(lib().bn_exp_counters(self._h, c))
         return {"calls": int(c[0]), "launches": int(c[1]), "bits_launches": int(c[2])}
+
+    def partial_eval_high_batch(self, columns, query, query_vars, outs):
+        """A batch of columns evaluated at the high coordinates of one point (bn_partial_eval_high_batch; evaluate_partial_high of
+        every inner column of an evalcheck round, evalcheck/subclaims.rs:356-439).  columns: (DevSlice, tower_level, n_vars) per
+        column; query: the DevSlice of the 2^query_vars-element tensor expansion; outs[c]: a DevSlice of 2^(n_vars - query_vars)
+        elements that receives what fold_left(column, level, query, out) would write."""
+        n = len(columns)
+        if len(outs) != n:
+            raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: one output per column")
+        cols = (PeColumn * max(1, n))(*[PeColumn(c[0].ptr if c[0] is not None else None, c[1], c[2]) for c in columns])
+        for c, o in zip(columns, outs):
+            if o is not None and query_vars <= c[2] <= 40 and o.len != 1 << (c[2] - query_vars):
+                raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: output has the wrong number of elements")
+        op = (C.c_void_p * max(1, n))(*[(o.ptr if o is not None else None) for o in outs])
+        _check(lib().bn_partial_eval_high_batch(self._h, C.cast(cols, C.c_void_p), n, query.ptr if query is not None else None, query_vars, op))
+
+    def partial_eval_counters(self):
+        """bn_partial_eval_counters: accepted bn_partial_eval_high_batch calls, launches of the partial-evaluation kernels (routed
+        bn_fold_left calls included), columns they served, columns that went to the fold_left kernels, the largest number of
+        workgroups that shared one column in the last call, bn_fold_left calls routed to the kernel.  Rejected calls count nowhere."""
+        c = (C.c_uint64 * 6)()
+        _check(lib().bn_partial_eval_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "cols_kernel": int(c[2]), "cols_fallback": int(c[3]), "max_share": int(c[4]),
+                "fold_left_routed": int(c[5])}
 
     # ---- accumulate_kernels / map_kernels
     def pick_log_chunks(self, mem_maps):

@@ -80,6 +80,8 @@ def host_lib():
             C.c_void_p, C.c_uint32, U32P, U32P, VPP, FP, VPP, VPP, C.c_uint32, U32P, FP, FP, C.c_void_p, C.c_uint64, FP, FP,
             U32P, U32P, U32P, FP, U32P, U32P, FP, U32P, U32P, FP, FP, C.POINTER(C.c_double),
         ]
+        L.bnh_evalcheck_bivariate_prove.restype = C.c_int
+        L.bnh_evalcheck_bivariate_prove.argtypes = [C.c_void_p, C.c_uint32, U32P, U32P, VPP, FP, C.c_uint32, U32P, FP, C.c_void_p, C.c_uint64, FP, FP, FP, FP]
         L.bnh_rccl_open.argtypes = [C.c_char_p]
         L.bnh_rccl_unique_id.argtypes = [C.c_void_p]
         L.bnh_rccl_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -550,6 +552,81 @@ class GkrExpPlan:
 
     def layer_times_ms(self):
         return [self.layer_ms[L] for L in range(self.n_layers.value)]
+
+
+class EvalcheckPlan:
+    """One round of evalcheck's bivariate sumchecks (bnh_evalcheck_bivariate_prove = binius_amd/host/evalcheck.hpp; one call of
+    prove_bivariate_sumchecks_with_switchover, evalcheck/subclaims.rs:549-586, with the witness construction in front of it).
+    provers: list of (b, multilins, comps, sums) ascending by b; a multilinear is one of
+      ("proj", column DevSlice, tower_level, n_vars, suffix_off, suffix_len)   the inner column at the suffix pool[suffix_off : + suffix_len]
+      ("shift", block_size, shift_offset, variant, r_off, r_len)               variant: 0 circular left, 1 logical left, 2 logical right
+      ("basis", k, iota)
+    pool: the shared list of point coordinates; scratch: a device slice of at least scratch_elems(provers) elements.
+    A projection's final evaluation v is the new claim (r' || suffix, v) on its inner column, r' the reversed challenges."""
+
+    KINDS = {"proj": 0, "shift": 1, "basis": 2}
+
+    @staticmethod
+    def scratch_elems(provers):
+        suffixes, projections, total = set(), set(), 0
+        for b, mls, _comps, _sums in provers:
+            for ml in mls:
+                if ml[0] == "proj":
+                    s = (ml[4], ml[5])
+                    if s not in suffixes:
+                        suffixes.add(s)
+                        total += 1 << ml[5]
+                    if (ml[1].ptr, ml[2], s) not in projections:
+                        projections.add((ml[1].ptr, ml[2], s))
+                        total += 1 << b
+                else:
+                    total += 1 << b
+            if b >= 1:
+                total += len(mls) << (b - 1)
+        return total
+
+    def __init__(self, hal, provers, pool, scratch, batch_coeffs, challenges):
+        self.hal, self.scratch, self._keep = hal, scratch, provers
+        self.n = len(provers)
+        desc, mld, cols, flat, sums = [], [], [], [], []
+        for b, mls, comps, sm in provers:
+            desc += [b, len(mls), len(comps)]
+            for ml in mls:
+                words = [self.KINDS[ml[0]]] + [int(x) for x in (ml[2:] if ml[0] == "proj" else ml[1:])]
+                mld += words + [0] * (6 - len(words))
+                cols.append(ml[1].ptr if ml[0] == "proj" and ml[1] is not None else None)
+            flat += [i for pair in comps for i in pair]
+            sums += list(sm)
+        self.desc = (C.c_uint32 * max(1, len(desc)))(*desc)
+        self.mld = (C.c_uint32 * max(1, len(mld)))(*mld)
+        self.cols = (C.c_void_p * max(1, len(cols)))(*cols)
+        self.pool, self.pool_len = _f128_array(list(pool) or [0]), len(pool)
+        self.comps = (C.c_uint32 * max(1, len(flat)))(*flat)
+        self.sums = _f128_array(sums if sums else [0])
+        self.bcs = _f128_array(list(batch_coeffs) or [0])
+        self.rounds = max([pv[0] for pv in provers]) if provers else 0
+        assert len(challenges) >= self.rounds
+        self.ch = _f128_array(list(challenges) if challenges else [0])
+        self.proofs = (F128 * max(1, 2 * self.rounds))()
+        self.m_by_prover = [len(pv[1]) for pv in provers]
+        self.final = (F128 * max(1, sum(self.m_by_prover)))()
+
+    def run(self):
+        rc = host_lib().bnh_evalcheck_bivariate_prove(self.hal._h, self.n, self.desc, self.mld, self.cols, self.pool, self.pool_len, self.comps, self.sums,
+                                                      self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0,
+                                                      self.bcs, self.ch, self.proofs, self.final)
+        if rc != 0:
+            raise BnError(rc, host_lib().bnh_last_error().decode())
+
+    def round_proofs(self):
+        return [[from_f128(self.proofs[2 * r]), from_f128(self.proofs[2 * r + 1])] for r in range(self.rounds)]
+
+    def final_evals(self):
+        out, at = [], 0
+        for m in self.m_by_prover:
+            out.append([from_f128(self.final[at + j]) for j in range(m)])
+            at += m
+        return out
 
 
 class ShmExchange:

@@ -149,6 +149,10 @@ struct ip_collector {
 int circuit_multipass_collect(bn_ctx *ctx, const bn_expr *e, const void *const *rows, uint64_t seg, uint32_t n_b, const void *eq, size_t scratch_off,
                               const uint32_t *out_index, ip_collector &col);
 int circuit_ip_run(bn_ctx *ctx, const ip_collector &col, uint64_t n, const void *ones, bn::f128 *values);
+// ---- evaluate_partial_high (abi_ops.cpp, abi_partial_eval.cpp)
+int fold_left_dispatch(bn_ctx *ctx, const void *d_mat, uint32_t tower_level, const void *d_vec, uint64_t vec_len, void *d_out, uint64_t out_len);
+// validated columns (query_vars <= n_vars each) at the 2^q-entry query d_vec; routed: a bn_fold_left call served as a one-column job
+int partial_eval_run(bn_ctx *ctx, const bn_pe_column *cols, uint32_t n_cols, const void *d_vec, uint32_t q, void *const *d_outs, bool routed);
 // ---- small helpers shared by the op entry points (abi.cpp)
 int publish_result(bn_ctx *ctx, uint32_t n_groups, bn_f128 *h_out);
 int publish_vals(bn_ctx *ctx, const bn::f128 *d_vals, uint32_t n_groups, uint32_t group_len, uint32_t g_stride, uint32_t i_stride, bn::f128 *h_out);

@@ -4,6 +4,23 @@
 // kernel launch.  No arithmetic fallback lives here.
 #include "abi_common.hpp"
 
+namespace bnabi {
+// fold_left on the kernels of kernels_misc.hip / kernels_linmap.hip (arguments validated by the caller)
+int fold_left_dispatch(bn_ctx *ctx, const void *d_mat, uint32_t tower_level, const void *d_vec, uint64_t vec_len, void *d_out, uint64_t out_len)
+{
+	if (tower_level == 5 && out_len >= 4096 && (vec_len == 16 || vec_len == 32 || vec_len == 64)) {
+		void *tab = bn::ctx_scratch(ctx, bn::linmap_table_bytes(vec_len * 32));
+		if (tab) {
+			const hipError_t e = bn::launch_fold_left_mfma(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len, tab);
+			if (e == hipSuccess) return BN_OK;
+			if (e != hipErrorNotSupported) BN_HIP(e);
+		}
+	}
+	BN_HIP(bn::launch_fold_left(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len));
+	return BN_OK;
+}
+} // namespace bnabi
+
 extern "C" {
 
 int bn_tensor_expand(bn_ctx *ctx, void *d_data, uint64_t data_len, uint32_t log_n, const bn_f128 *h_coords, uint32_t k)
@@ -60,16 +77,16 @@ static int fold_common(bn_ctx *ctx, bool left, const void *d_mat, uint64_t mat_l
 	BN_REQUIRE(log_q <= log_evals, "query larger than evals");
 	BN_REQUIRE(out_len == ((uint64_t)1 << (log_evals - log_q)), "output has the wrong number of elements");
 	if (left) {
-		if (tower_level == 5 && out_len >= 4096 && (vec_len == 16 || vec_len == 32 || vec_len == 64)) {
-			void *tab = bn::ctx_scratch(ctx, bn::linmap_table_bytes(vec_len * 32));
-			if (tab) {
-				const hipError_t e = bn::launch_fold_left_mfma(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len, tab);
-				if (e == hipSuccess) return BN_OK;
-				if (e != hipErrorNotSupported) BN_HIP(e);
-			}
+		// few outputs under a long reduction (evaluate_partial_high at evalcheck's shapes): the reduction is split across
+		// workgroups by the partial-evaluation kernel, as a one-column job (abi_partial_eval.cpp)
+		// (BN_FOLD_LEFT_NO_PE=1, read per call: the fold_left kernels at these shapes too -- the baseline leg of tools/bench_evalcheck.py)
+		const char *no_pe = std::getenv("BN_FOLD_LEFT_NO_PE");
+		if (out_len <= ((uint64_t)1 << bn::kPeMaxLogOut) && vec_len >= 4096 && !(no_pe && no_pe[0] == '1')) {
+			const bn_pe_column col{d_mat, tower_level, log_evals};
+			void *const out = d_out;
+			return partial_eval_run(ctx, &col, 1, d_vec, log_q, &out, /*routed=*/true);
 		}
-		BN_HIP(bn::launch_fold_left(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len));
-		return BN_OK;
+		return fold_left_dispatch(ctx, d_mat, tower_level, d_vec, vec_len, d_out, out_len);
 	}
 	// rows of 512 .. 2048 bits: the linear map on the matrix cores (kernels_linmap.hip); every other shape: nibble tables
 	const uint64_t row_bits = vec_len << tower_level;

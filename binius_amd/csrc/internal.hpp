@@ -78,6 +78,7 @@ struct bn_ctx {
 	std::vector<uint64_t> h_s_evals;   // ... and its host copy: an NTT instance's basis is uploaded once, not per call
 	uint64_t ntt_calls_bs = 0, ntt_calls_tiled = 0, ntt_calls_layer = 0; // bn_ntt_* calls served per kernel family (bn_ntt_counters)
 	uint64_t exp_calls = 0, exp_launches = 0, exp_bits_launches = 0;     // bn_exp_circuit_layers / bn_bits_to_b128 (bn_exp_counters)
+	uint64_t pe_calls = 0, pe_launches = 0, pe_cols_kernel = 0, pe_cols_fallback = 0, pe_max_share = 0, pe_routed = 0; // bn_partial_eval_counters
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	int n_cu = 256;
@@ -759,6 +760,29 @@ struct bits_job {
 	uint32_t start, pad_;
 };
 hipError_t launch_bits_to_b128(hipStream_t s, const bits_job *d_jobs, uint32_t n_jobs, uint32_t total_blocks);
+
+// ---- kernels_partial_eval.hip: a batch of columns evaluated at the high coordinates of one point (evaluate_partial_high,
+// evalcheck/subclaims.rs:356-439): out_c[i] = sum_j vec[j] * M_c[j * 2^b + i] for every column c with 2^b <= 1024 outputs.  A unit
+// (one workgroup) is a chunk of 2^log_ch indices j of a GROUP of columns of one class (tower level, b): the chunk of `vec` is
+// staged in LDS once and serves every column of the group.  Partial results are XOR-combined with 64-bit atomics into outputs
+// zeroed by a launch of their own.
+struct pe_col {
+	const uint64_t *evals;
+	uint64_t *out;     // 2^b elements
+	uint32_t out_len, pad_;
+};
+struct pe_group {
+	uint32_t first, count; // columns [first, first + count) of the column table
+	uint32_t level, b;
+	uint32_t log_ch;       // 2^log_ch indices j per unit (<= kPeLogVecChunk, <= log2 |vec|)
+	uint32_t start;        // first unit of this group in the launch
+};
+constexpr uint32_t kPeMaxLogOut = 10;   // columns with more outputs go to the fold_left kernels
+constexpr uint32_t kPeLogVecChunk = 10; // entries of `vec` a workgroup stages in LDS (16 KiB)
+// bits_only: every group is at level 0 (the instantiation without the subfield products).
+// n_groups == 1 && d_groups == nullptr: the group and its single column travel as kernel arguments (no table upload)
+hipError_t launch_partial_eval(hipStream_t s, const pe_group *d_groups, uint32_t n_groups, const pe_col *d_cols, uint32_t n_cols, pe_group one_group,
+                               pe_col one_col, const void *vec, uint32_t total_units, bool bits_only);
 
 // ---- kernels_ntt_tiled.hip
 hipError_t launch_build_mul8(hipStream_t s, uint8_t *d_tab);

@@ -1,0 +1,246 @@
+// binius_amd/host/evalcheck.hpp -- C++ mirror of one round of evalcheck's bivariate sumchecks: one call of
+// prove_bivariate_sumchecks_with_switchover (core/src/protocols/evalcheck/subclaims.rs:549-586) together with the witness
+// construction in front of it:
+//
+//   process_shifted_sumcheck / process_packed_sumcheck   subclaims.rs:52-145     the constraint sets: inner projection x shift indicator,
+//                                                                                 inner projection x tower basis, over b variables
+//   collect_projected_mles                               subclaims.rs:356-439    evaluate_partial_high of every inner column at the high
+//                                                                                 coordinates of its claim -> ONE bn_partial_eval_high_batch
+//                                                                                 per distinct suffix
+//   ShiftIndPartialEval::multilinear_extension           transparent/shift_ind.rs:117-161, 276-366   host table of 2^b elements
+//   TowerBasis::multilinear_extension                    transparent/tower_basis.rs:54-70            host table of 2^k elements
+//   RegularSumcheckProver per constraint set + batch_prove   -> BivariateSumcheckProver + SumcheckBatchProver (sumcheck.hpp, piop.hpp):
+//     both batch a prover's claims by powers of the batch coefficient (prover_state.rs:302) and the round polynomial is unique,
+//     so the transcript is the same.  At 2^b <= 2^12 elements the backend's host tail finishes these provers.
+//
+// The caller hands in explicit multilinear lists (the order its constraint set holds them = the order of the final evaluations
+// in the transcript); the oracle-set bookkeeping of EvalcheckProver stays with the caller.
+//
+// What comes out: the truncated round proofs and the final evaluations in finishing order.  A PROJECTION's final evaluation v at
+// the reversed challenges r' (r'[i] = the challenge of round b - 1 - i of its prover) is the new evalcheck claim (r' || suffix, v)
+// on its inner column; a shift indicator's or tower basis's final evaluation is what the verifier recomputes itself.
+//
+// Protocol bookkeeping only: every hypercube-sized operation is a call of the backend.
+#pragma once
+#include <algorithm>
+#include <map>
+#include <memory>
+
+#include "piop.hpp"
+
+namespace binius_amd {
+
+enum class ShiftVariant : uint32_t { CircularLeft = 0, LogicalLeft = 1, LogicalRight = 2 };
+
+struct EvalcheckMultilinear {
+	enum Kind : uint32_t { Projection = 0, ShiftInd = 1, TowerBasis = 2 } kind = Projection;
+	// Projection: the inner column (2^n_vars values of tower_level, packed into F, only read) at the suffix pool[suffix_off .. + suffix_len)
+	const void *d_column = nullptr;
+	uint32_t tower_level = 0, n_vars = 0;
+	uint32_t suffix_off = 0, suffix_len = 0;
+	// ShiftInd: (block_size, shift_offset, variant) at the prefix pool[r_off .. + block_size)
+	uint32_t block_size = 0, shift_offset = 0;
+	ShiftVariant variant = ShiftVariant::CircularLeft;
+	uint32_t r_off = 0, r_len = 0;
+	// TowerBasis: table[i] = basis(iota, i), i < 2^k
+	uint32_t k = 0, iota = 0;
+};
+
+struct EvalcheckProver {
+	size_t n_vars = 0; // b
+	std::vector<EvalcheckMultilinear> multilins;
+	std::vector<IndexCompositionBivariate> compositions;
+	std::vector<B128> sums;
+};
+
+// the identity of a suffix: its slice of the pool
+using EvalcheckSuffix = std::pair<uint32_t, uint32_t>;
+// the identity of a projection: the column as it is read (pointer, tower level; n_vars follows from b and the suffix) and the suffix
+using EvalcheckProjection = std::pair<std::pair<const void *, uint32_t>, EvalcheckSuffix>;
+inline EvalcheckProjection evalcheck_projection_key(const EvalcheckMultilinear &m)
+{
+	return {{m.d_column, m.tower_level}, {m.suffix_off, m.suffix_len}};
+}
+
+// Exact: the tensor expansion of every distinct suffix, one table per distinct (column, tower level, suffix) projection and per transparent
+// multilinear, and the provers' fold buffers (m * 2^(b-1) each).
+inline size_t evalcheck_scratch_elems(const std::vector<EvalcheckProver> &provers)
+{
+	std::map<EvalcheckSuffix, bool> suffixes;
+	std::map<EvalcheckProjection, bool> projections;
+	size_t total = 0;
+	for (const EvalcheckProver &p : provers) {
+		for (const EvalcheckMultilinear &m : p.multilins) {
+			if (m.kind == EvalcheckMultilinear::Projection) {
+				const EvalcheckSuffix s{m.suffix_off, m.suffix_len};
+				if (suffixes.emplace(s, true).second) total += (size_t)1 << m.suffix_len;
+				if (projections.emplace(evalcheck_projection_key(m), true).second) total += (size_t)1 << p.n_vars;
+			} else {
+				total += (size_t)1 << p.n_vars;
+			}
+		}
+		if (p.n_vars >= 1) total += p.multilins.size() << (p.n_vars - 1);
+	}
+	return total;
+}
+
+// eq(r)[y] = prod_k (y_k ? r_k : 1 + r_k), bit k of y with r[k]
+inline std::vector<B128> evalcheck_eq_expand(const B128 *r, size_t b)
+{
+	std::vector<B128> eq{B128::ONE()};
+	for (size_t k = 0; k < b; k++) {
+		const size_t n = eq.size();
+		eq.resize(2 * n);
+		for (size_t y = 0; y < n; y++) {
+			const B128 hi = eq[y] * r[k];
+			eq[n + y] = hi;
+			eq[y] = eq[y] + hi;
+		}
+	}
+	return eq;
+}
+
+// ShiftIndPartialEval::multilinear_extension (shift_ind.rs:117-161, 332-366): table[x] = sum_y f(x, y) eq(y, r) with f(x, y) = 1 where
+// y is the position x is shifted to -- table[x] = eq(r)[y(x)], zero where the shift leaves the block
+inline std::vector<B128> evalcheck_shift_ind_table(size_t b, size_t offset, ShiftVariant variant, const B128 *r)
+{
+	// assert_valid_shift_ind_args (shift_ind.rs:218-235)
+	if (b == 0 || b >= 32) throw Error(Error::InputValidation, "shift indicator: block_size out of range");
+	const size_t n = (size_t)1 << b;
+	if (offset == 0 || offset >= n) throw Error(Error::InputValidation, "shift indicator: shift_offset must be in 1 .. 2^block_size - 1");
+	const std::vector<B128> eq = evalcheck_eq_expand(r, b);
+	std::vector<B128> table(n, B128::ZERO());
+	for (size_t x = 0; x < n; x++) {
+		switch (variant) {
+		case ShiftVariant::CircularLeft: table[x] = eq[(x + offset) & (n - 1)]; break;
+		case ShiftVariant::LogicalLeft:
+			if (x + offset < n) table[x] = eq[x + offset];
+			break;
+		case ShiftVariant::LogicalRight:
+			if (x >= offset) table[x] = eq[x - offset];
+			break;
+		}
+	}
+	return table;
+}
+
+struct EvalcheckOutput {
+	std::vector<std::vector<B128>> round_proofs;      // per round the truncated coefficients
+	std::vector<std::vector<B128>> multilinear_evals; // per prover, finishing (= input) order
+};
+
+inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::vector<EvalcheckProver> &provers, const std::vector<B128> &pool, FSliceMut scratch,
+                                                 const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges)
+{
+	EvalcheckOutput out;
+	if (batch_coeffs.size() != provers.size()) throw Error(Error::InputValidation, "IncorrectNumberOfBatchCoeffs");
+	size_t total_m = 0;
+	for (size_t i = 0; i < provers.size(); i++) {
+		const EvalcheckProver &p = provers[i];
+		if (p.n_vars > 12) throw Error(Error::InputValidation, "a prover of an evalcheck round has at most 12 variables");
+		if (i && p.n_vars < provers[i - 1].n_vars) throw Error(Error::InputValidation, "ClaimsOutOfOrder: provers ascend by number of variables");
+		if (p.compositions.size() != p.sums.size()) throw Error(Error::InputValidation, "one sum per claim");
+		for (const EvalcheckMultilinear &m : p.multilins) {
+			switch (m.kind) {
+			case EvalcheckMultilinear::Projection:
+				if (!m.d_column) throw Error(Error::InputValidation, "null inner column");
+				if (m.n_vars != p.n_vars + m.suffix_len) throw Error(Error::InputValidation, "a projection's inner column has b + |suffix| variables");
+				if ((size_t)m.suffix_off + m.suffix_len > pool.size()) throw Error(Error::InputValidation, "a suffix leaves the point pool");
+				break;
+			case EvalcheckMultilinear::ShiftInd:
+				if (m.block_size != p.n_vars || m.r_len != m.block_size) throw Error(Error::InputValidation, "shift indicator: block_size and |r| must equal the prover's number of variables");
+				if ((size_t)m.r_off + m.r_len > pool.size()) throw Error(Error::InputValidation, "a shift indicator's prefix leaves the point pool");
+				if (m.shift_offset == 0 || m.shift_offset >= (1u << m.block_size)) throw Error(Error::InputValidation, "shift indicator: shift_offset must be in 1 .. 2^block_size - 1");
+				if ((uint32_t)m.variant > 2) throw Error(Error::InputValidation, "shift indicator: unknown variant");
+				break;
+			case EvalcheckMultilinear::TowerBasis:
+				if (m.k != p.n_vars || m.iota + m.k > 7) throw Error(Error::InputValidation, "tower basis: k must equal the prover's number of variables and iota + k <= 7");
+				break;
+			default: throw Error(Error::InputValidation, "unknown multilinear kind");
+			}
+		}
+		total_m += p.multilins.size();
+	}
+	if (provers.empty()) return out;
+	if (challenges.size() < provers.back().n_vars) throw Error(Error::InputValidation, "too few challenges");
+	if (scratch.len_ < evalcheck_scratch_elems(provers)) throw Error(Error::InputValidation, "scratch holds fewer than evalcheck_scratch_elems elements");
+	DeviceBumpAllocator alloc(scratch);
+
+	// ---- collect_projected_mles: distinct suffixes expanded once, all projections of a suffix in one call, duplicates once
+	struct SuffixJob {
+		FSlice query;
+		std::vector<bn_pe_column> cols;
+		std::vector<void *> outs;
+	};
+	std::map<EvalcheckSuffix, SuffixJob> jobs;
+	std::map<EvalcheckProjection, FSlice> projected;
+	for (const EvalcheckProver &p : provers) {
+		for (const EvalcheckMultilinear &m : p.multilins) {
+			if (m.kind != EvalcheckMultilinear::Projection) continue;
+			const EvalcheckSuffix s{m.suffix_off, m.suffix_len};
+			auto job = jobs.find(s);
+			if (job == jobs.end()) {
+				FSliceMut q = alloc.alloc((size_t)1 << m.suffix_len);
+				FSliceMut first{q.ptr, 1};
+				hal.fill(first, B128::ONE());
+				check(bn_tensor_expand(hal.raw_ctx(), q.ptr, q.len_, 0, reinterpret_cast<const bn_f128 *>(pool.data() + m.suffix_off), m.suffix_len));
+				job = jobs.emplace(s, SuffixJob{ComputeMemory::as_const(q), {}, {}}).first;
+			}
+			const auto key = evalcheck_projection_key(m);
+			if (projected.count(key)) continue;
+			FSliceMut o = alloc.alloc((size_t)1 << p.n_vars);
+			job->second.cols.push_back(bn_pe_column{m.d_column, m.tower_level, m.n_vars});
+			job->second.outs.push_back(o.ptr);
+			projected.emplace(key, ComputeMemory::as_const(o));
+		}
+	}
+	for (auto &kv : jobs)
+		check(bn_partial_eval_high_batch(hal.raw_ctx(), kv.second.cols.data(), (uint32_t)kv.second.cols.size(), kv.second.query.ptr, kv.first.second, kv.second.outs.data()));
+
+	// ---- the transparent tables and the provers
+	std::vector<B128> host_mem(total_m + 8);
+	HostBumpAllocator host_alloc(HostSliceMut{host_mem.data(), host_mem.size()});
+	std::vector<std::unique_ptr<BivariateSumcheckProver>> sc;
+	for (const EvalcheckProver &p : provers) {
+		std::vector<FSlice> mls;
+		for (const EvalcheckMultilinear &m : p.multilins) {
+			if (m.kind == EvalcheckMultilinear::Projection) {
+				mls.push_back(projected.at(evalcheck_projection_key(m)));
+				continue;
+			}
+			std::vector<B128> table;
+			if (m.kind == EvalcheckMultilinear::ShiftInd) {
+				table = evalcheck_shift_ind_table(m.block_size, m.shift_offset, m.variant, pool.data() + m.r_off);
+			} else {
+				// TowerField::basis(iota, i): ONE in limb i of 2^iota bits (tower_basis.rs:54-70)
+				for (size_t i = 0; i < ((size_t)1 << m.k); i++) {
+					const size_t bit = i << m.iota;
+					table.push_back(bit < 64 ? B128((uint64_t)1 << bit, 0) : B128(0, (uint64_t)1 << (bit - 64)));
+				}
+			}
+			FSliceMut d = alloc.alloc(table.size());
+			hal.copy_h2d(table, d);
+			mls.push_back(ComputeMemory::as_const(d));
+		}
+		for (const IndexCompositionBivariate &c : p.compositions)
+			if (c.indices[0] >= p.multilins.size() || c.indices[1] >= p.multilins.size()) throw Error(Error::InputValidation, "a claim's index leaves its prover's multilinears");
+		sc.push_back(std::make_unique<BivariateSumcheckProver>(hal, alloc, host_alloc, p.n_vars, p.compositions, p.sums, mls));
+	}
+	SumcheckBatchProver batch(std::move(sc), batch_coeffs);
+	const size_t rounds = batch.total_rounds();
+	PiopTranscript tr;
+	for (size_t r = 0; r < rounds; r++) {
+		batch.send_round_proof(tr);
+		batch.receive_challenge(challenges[r]);
+	}
+	batch.finish(tr);
+	for (const auto &it : tr.items) {
+		if (it.kind == PiopTranscript::Item::RoundProof)
+			out.round_proofs.push_back(it.scalars);
+		else if (it.kind == PiopTranscript::Item::MultilinearEvals)
+			out.multilinear_evals.push_back(it.scalars);
+	}
+	return out;
+}
+
+} // namespace binius_amd

@@ -25,6 +25,7 @@
 #include <cstring>
 
 #include "eq_ind.hpp"
+#include "evalcheck.hpp"
 #include "fri.hpp"
 #include "gkr_exp.hpp"
 #include "gkr_gpa.hpp"
@@ -1035,6 +1036,88 @@ int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths,
 			}
 			if (layer_ms_out) layer_ms_out[L] = out.layer_ms[L];
 		}
+		return 0;
+	} catch (const Error &e) {
+		g_err = e.what();
+		return (int)e.kind();
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return BN_ERR_CORE_LIB;
+	}
+}
+
+// One round of evalcheck's bivariate sumchecks (evalcheck/subclaims.rs:549-586 with the witness construction in front of it) through
+// the C++ mirror binius_amd/host/evalcheck.hpp; the arguments and the layout of the outputs are described in include/binius_amd_host.h.
+int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const uint32_t *ml_desc, const void *const *d_columns,
+                                  const bn_f128 *point_pool, uint32_t pool_len, const uint32_t *comp_indices, const bn_f128 *sums, void *d_scratch,
+                                  uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges, bn_f128 *round_proofs_out,
+                                  bn_f128 *final_evals_out)
+{
+	try {
+		if (!ctx || (n_provers && (!prover_desc || !batch_coeffs)) || !round_proofs_out || !final_evals_out || (!d_scratch && scratch_elems) || (pool_len && !point_pool))
+			throw Error(Error::InputValidation, "null argument");
+		size_t total_m = 0, total_c = 0, max_b = 0;
+		for (uint32_t i = 0; i < n_provers; i++) {
+			if (prover_desc[3 * i] > 12) throw Error(Error::InputValidation, "a prover of an evalcheck round has at most 12 variables");
+			max_b = std::max<size_t>(max_b, prover_desc[3 * i]);
+			total_m += prover_desc[3 * i + 1];
+			total_c += prover_desc[3 * i + 2];
+		}
+		if ((total_m && (!ml_desc || !d_columns)) || (total_c && (!comp_indices || !sums)) || (max_b && !challenges)) throw Error(Error::InputValidation, "null argument");
+		std::vector<B128> pool;
+		for (uint32_t i = 0; i < pool_len; i++) pool.emplace_back(point_pool[i].lo, point_pool[i].hi);
+		std::vector<EvalcheckProver> provers(n_provers);
+		std::vector<B128> bcs, ch;
+		size_t at_ml = 0, at_c = 0;
+		for (uint32_t i = 0; i < n_provers; i++) {
+			EvalcheckProver &p = provers[i];
+			p.n_vars = prover_desc[3 * i];
+			const uint32_t m = prover_desc[3 * i + 1], nc = prover_desc[3 * i + 2];
+			for (uint32_t j = 0; j < m; j++, at_ml++) {
+				const uint32_t *d = ml_desc + (size_t)BNH_EC_DESC_WORDS * at_ml;
+				EvalcheckMultilinear ml;
+				switch (d[0]) {
+				case BNH_EC_PROJECTION:
+					ml.kind = EvalcheckMultilinear::Projection;
+					ml.d_column = d_columns[at_ml];
+					ml.tower_level = d[1];
+					ml.n_vars = d[2];
+					ml.suffix_off = d[3];
+					ml.suffix_len = d[4];
+					if (ml.suffix_len > 48) throw Error(Error::InputValidation, "a suffix has at most 48 coordinates");
+					break;
+				case BNH_EC_SHIFT_IND:
+					ml.kind = EvalcheckMultilinear::ShiftInd;
+					ml.block_size = d[1];
+					ml.shift_offset = d[2];
+					if (d[3] > BNH_SHIFT_LOGICAL_RIGHT) throw Error(Error::InputValidation, "shift indicator: unknown variant");
+					ml.variant = (ShiftVariant)d[3];
+					ml.r_off = d[4];
+					ml.r_len = d[5];
+					break;
+				case BNH_EC_TOWER_BASIS:
+					ml.kind = EvalcheckMultilinear::TowerBasis;
+					ml.k = d[1];
+					ml.iota = d[2];
+					break;
+				default: throw Error(Error::InputValidation, "unknown multilinear kind");
+				}
+				p.multilins.push_back(ml);
+			}
+			for (uint32_t c = 0; c < nc; c++, at_c++) {
+				p.compositions.push_back(IndexCompositionBivariate{m, {comp_indices[2 * at_c], comp_indices[2 * at_c + 1]}});
+				p.sums.emplace_back(sums[at_c].lo, sums[at_c].hi);
+			}
+			bcs.emplace_back(batch_coeffs[i].lo, batch_coeffs[i].hi);
+		}
+		for (size_t r = 0; r < max_b; r++) ch.emplace_back(challenges[r].lo, challenges[r].hi);
+		ComputeLayer hal(ctx);
+		const EvalcheckOutput out = evalcheck_bivariate_prove(hal, provers, pool, FSliceMut{d_scratch, (size_t)scratch_elems}, bcs, ch);
+		for (size_t r = 0; r < out.round_proofs.size(); r++)
+			for (size_t i = 0; i < 2; i++) round_proofs_out[2 * r + i] = i < out.round_proofs[r].size() ? out.round_proofs[r][i].raw() : bn_f128{0, 0};
+		size_t fe = 0;
+		for (const auto &evals : out.multilinear_evals)
+			for (const B128 &v : evals) final_evals_out[fe++] = v.raw();
 		return 0;
 	} catch (const Error &e) {
 		g_err = e.what();

@@ -93,6 +93,14 @@ pub const BN_ARM_N: usize = 15;
 pub const BN_FP4_N: usize = 7;
 pub const BN_NTT_N: usize = 3;
 pub const BN_EXP_N: usize = 3;
+pub const BN_PE_N: usize = 6;
+pub const BN_PE_CALLS: usize = 0;
+pub const BN_PE_LAUNCHES: usize = 1;
+pub const BN_PE_COLS_KERNEL: usize = 2;
+pub const BN_PE_COLS_FALLBACK: usize = 3;
+pub const BN_PE_MAX_SHARE: usize = 4;
+pub const BN_PE_FOLD_LEFT_ROUTED: usize = 5;
+pub const BN_PE_MAX_VARS: u32 = 40;
 pub const BN_EXP_STATIC: u32 = 0;
 pub const BN_EXP_DYNAMIC: u32 = 1;
 pub const BN_EXP_MAX_VARS: u32 = 28;
@@ -103,6 +111,14 @@ pub const BN_ORDER_LOW_TO_HIGH: u32 = 0;
 pub const BN_ORDER_HIGH_TO_LOW: u32 = 1;
 pub const BN_HAL_ML_FOLDED: u32 = 0;
 pub const BN_HAL_ML_TRANSPARENT: u32 = 1;
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bn_pe_column {
+	pub d_evals: *const c_void,
+	pub tower_level: u32,
+	pub n_vars: u32,
+}
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -255,6 +271,15 @@ unsafe extern "C" {
 	) -> c_int;
 	pub fn bn_bits_to_b128(ctx: *mut bn_ctx, n: u32, log_lens: *const u32, d_srcs: *const *const c_void, d_dsts: *const *mut c_void) -> c_int;
 	pub fn bn_exp_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_partial_eval_high_batch(
+		ctx: *mut bn_ctx,
+		cols: *const c_void,
+		n_cols: u32,
+		d_tensor_query: *const c_void,
+		query_vars: u32,
+		d_outs: *const *mut c_void,
+	) -> c_int;
+	pub fn bn_partial_eval_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 
 	pub fn bn_log_chunks_range(maps: *const bn_memmap, n_maps: u32, start: *mut u32, end: *mut u32) -> c_int;
 	pub fn bn_pick_log_chunks(maps: *const bn_memmap, n_maps: u32, log_chunks: *mut u32) -> c_int;

@@ -185,6 +185,35 @@ int bn_bits_to_b128(bn_ctx *ctx, uint32_t n, const uint32_t *log_lens, const voi
  * made, and the launches of bn_bits_to_b128.  A rejected call counts nowhere. */
 enum { BN_EXP_CALLS = 0, BN_EXP_LAUNCHES = 1, BN_EXP_BITS_LAUNCHES = 2, BN_EXP_N = 3 };
 int bn_exp_counters(bn_ctx *ctx, uint64_t *counters /*[BN_EXP_N]*/);
+/* A batch of columns evaluated at the high coordinates of one point: evaluate_partial_high (math/src/multilinear_extension.rs:
+ * 253-300) of the inner column of every shifted or packed virtual column of an evalcheck round (collect_projected_mles,
+ * core/src/protocols/evalcheck/subclaims.rs:356-439), where every claim of a table shares the point.  Column c holds 2^n_vars
+ * values of tower level 0 or 3 .. 7 packed into F as bn_fold_left takes them (at least one 16-byte element: n_vars + tower_level
+ * >= 7); d_tensor_query is the tensor expansion of the query_vars <= n_vars high coordinates (2^query_vars B128 elements, shared
+ * by all columns).  d_outs[c] receives exactly what
+ *   bn_fold_left(d_evals, 2^(n_vars - 7 + tower_level), tower_level, d_tensor_query, 2^query_vars, d_outs[c], 2^(n_vars - query_vars))
+ * writes: out[i] = sum_j query[j] * column[j * out_len + i], bit-exact, overwritten not accumulated.  query_vars = 0 widens the
+ * column to B128; n_vars = query_vars is one inner product.  cols and d_outs are HOST arrays; pointers are 16-byte aligned; inputs
+ * are only read; an output must not overlap its column.  Columns with at most 1024 outputs share TWO launches whatever their
+ * number, levels and sizes (the reduction of a column is split across workgroups, the query chunk of a workgroup serves several
+ * columns); a column with more outputs runs on the bn_fold_left kernels inside the same call.  n_cols = 0 is a no-op.
+ * bn_fold_left itself takes this route as a one-column job for out_len <= 1024 and vec_len >= 4096. */
+typedef struct {
+	const void *d_evals;
+	uint32_t tower_level;
+	uint32_t n_vars;
+} bn_pe_column;
+#define BN_PE_MAX_VARS 40
+/* (cols points to n_cols bn_pe_column; the prototype spells it as untyped memory so that the checked FFI declarations, which know a
+ * closed set of type names, carry it unchanged.) */
+int bn_partial_eval_high_batch(bn_ctx *ctx, const void *cols, uint32_t n_cols, const void *d_tensor_query, uint32_t query_vars,
+                               void *const *d_outs);
+/* Read-only, per context (not part of the reference interface): accepted bn_partial_eval_high_batch calls; kernel launches of
+ * the partial-evaluation kernels (routed bn_fold_left calls included); columns they served; columns that went to the fold_left
+ * kernels; the largest number of workgroups that shared one column in the last call; bn_fold_left calls routed here.  A rejected
+ * call counts nowhere. */
+enum { BN_PE_CALLS = 0, BN_PE_LAUNCHES = 1, BN_PE_COLS_KERNEL = 2, BN_PE_COLS_FALLBACK = 3, BN_PE_MAX_SHARE = 4, BN_PE_FOLD_LEFT_ROUTED = 5, BN_PE_N = 6 };
+int bn_partial_eval_counters(bn_ctx *ctx, uint64_t *counters /*[BN_PE_N]*/);
 
 /* ---- accumulate_kernels / map_kernels (layer.rs:183, 236) + KernelExecutor (layer.rs:518-590).
  * The kernel-spec closure cannot cross an FFI: the host shim runs it ONCE against a recording

@@ -189,6 +189,39 @@ int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths,
                       bn_f128 *round_proofs_out, uint32_t *provers_per_layer_out, uint32_t *evals_per_prover_out, bn_f128 *multilinear_evals_out,
                       uint32_t *claims_per_layer_out, uint32_t *claim_n_vars_out, bn_f128 *claim_points_out, bn_f128 *claim_evals_out, double *layer_ms_out);
 
+/* One round of evalcheck's bivariate sumchecks: one call of prove_bivariate_sumchecks_with_switchover (core/src/protocols/evalcheck/
+ * subclaims.rs:549-586) with the witness construction in front of it (process_shifted_sumcheck, process_packed_sumcheck :52-145,
+ * collect_projected_mles :356-439) through the C++ mirror binius_amd/host/evalcheck.hpp.  The caller hands in explicit multilinear lists;
+ * the greedy loop and EvalcheckProver's oracle bookkeeping stay with it.
+ *   prover_desc[3 * i] = (b, m, n_claims) of prover i, ascending by its number of variables b <= 12; its m multilinears in the order its
+ *     constraint set holds them (= the order of its final evaluations in the transcript)
+ *   ml_desc[BNH_EC_DESC_WORDS * j], multilinears of prover 0, then of prover 1, ...:
+ *     BNH_EC_PROJECTION : (kind, tower_level, n_vars, suffix_off, suffix_len) -- the inner column d_columns[j] (2^n_vars values packed into F,
+ *       only read, n_vars = b + suffix_len) evaluated at the high coordinates point_pool[suffix_off .. + suffix_len): evaluate_partial_high.
+ *       Distinct suffixes (slices of the pool) are tensor-expanded once each, all projections of one suffix are ONE
+ *       bn_partial_eval_high_batch, identical (column, suffix) pairs are projected once; an empty suffix is the column widened to B128
+ *     BNH_EC_SHIFT_IND  : (kind, block_size, shift_offset, variant, r_off, r_len) -- ShiftIndPartialEval::multilinear_extension (transparent/
+ *       shift_ind.rs:117-161, 276-366) at the prefix point_pool[r_off .. + r_len): table[x] = eq(r)[y(x)], y = x + o mod 2^b (circular left),
+ *       x + o or zero outside the block (logical left), x - o or zero when negative (logical right); block_size = r_len = b,
+ *       0 < shift_offset < 2^b (assert_valid_shift_ind_args, :218-235)
+ *     BNH_EC_TOWER_BASIS: (kind, k, iota) -- table[i] = TowerField::basis(iota, i) (transparent/tower_basis.rs:54-70), k = b, iota + k <= 7
+ *     d_columns[j] is ignored for the transparent kinds
+ *   comp_indices / sums: per prover its claims as index pairs into its multilinears with their sums, concatenated
+ *   d_scratch: at least the sum of 2^|suffix| per distinct suffix, 2^b per distinct (column, suffix) and per transparent multilinear, and
+ *     m * 2^(b-1) per prover (EvalcheckPlan.scratch_elems / evalcheck_scratch_elems)
+ *   batch_coeffs[n_provers], challenges[max b]: the transcript's samples, as for bnh_batch_sumcheck_prove
+ * Outputs, as for bnh_batch_sumcheck_prove: round_proofs_out[2 * max b] the truncated round polynomials; final_evals_out: the provers'
+ * final evaluations concatenated in finishing (= input) order.  A PROJECTION's final evaluation v is the evaluation of its table at the
+ * reversed challenges r' (r'[i] = the challenge of round b - 1 - i): the new evalcheck claim (r' || suffix, v) on the inner column.
+ * The caller's columns are only read. */
+enum { BNH_EC_PROJECTION = 0, BNH_EC_SHIFT_IND = 1, BNH_EC_TOWER_BASIS = 2 };
+enum { BNH_SHIFT_CIRCULAR_LEFT = 0, BNH_SHIFT_LOGICAL_LEFT = 1, BNH_SHIFT_LOGICAL_RIGHT = 2 };
+#define BNH_EC_DESC_WORDS 6
+int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const uint32_t *ml_desc, const void *const *d_columns,
+                                  const bn_f128 *point_pool, uint32_t pool_len, const uint32_t *comp_indices, const bn_f128 *sums, void *d_scratch,
+                                  uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges, bn_f128 *round_proofs_out,
+                                  bn_f128 *final_evals_out);
+
 /* shared-memory exchange: rank 0 creates the segment `name` ("/..."), the others open it afterwards */
 int bnh_shm_open(const char *name, int world, int rank, int create, void **handle_out);
 int bnh_shm_close(void *handle);
