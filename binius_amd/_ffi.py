@@ -156,6 +156,9 @@ def lib():
         "bn_exp_circuit_layers": [vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), PF, C.POINTER(vp), C.POINTER(vp)],
         "bn_bits_to_b128": [vp, u32, C.POINTER(u32), C.POINTER(vp), C.POINTER(vp)],
         "bn_exp_counters": [vp, C.POINTER(u64)],
+        "bn_flush_witness_batch": [vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), C.POINTER(u32), C.POINTER(vp), C.POINTER(u32), PF, PF,
+                                   C.POINTER(vp), C.POINTER(u64)],
+        "bn_flush_counters": [vp, C.POINTER(u64)],
         "bn_partial_eval_high_batch": [vp, vp, u32, vp, u32, C.POINTER(vp)],
         "bn_partial_eval_counters": [vp, C.POINTER(u64)],
         "bn_log_chunks_range": [C.POINTER(MemMap), u32, C.POINTER(u32), C.POINTER(u32)],
@@ -212,7 +215,7 @@ ABI_SYMBOLS = [
     "bn_merkle_build", "bn_groestl256_leaves", "bn_groestl256_compress_layer", "bn_gather_d2h",
     "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals",
     "bn_product_tree_layers", "bn_pad_with_ones", "bn_exp_circuit_layers", "bn_bits_to_b128", "bn_exp_counters",
-    "bn_partial_eval_high_batch", "bn_partial_eval_counters",
+    "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -818,6 +821,37 @@ class Context:
         c = (C.c_uint64 * 3)()
         _check(lib().bn_exp_counters(self._h, c))
         return {"calls": int(c[0]), "launches": int(c[1]), "bits_launches": int(c[2])}
+
+    def flush_witness_batch(self, n_vars, selectors, columns, const_terms, outs):
+        """The masked witnesses of a batch of channel flushes in one launch (bn_flush_witness_batch; make_masked_flush_witnesses,
+        constraint_system/prove.rs:671-881).  Per flush: n_vars; selectors: its DevSlices (packed B1 columns); columns: its
+        (DevSlice, tower_level, coefficient) triples, the coefficient an int (the entry's mixing power); const_terms: an int;
+        outs: a DevSlice of 2^n_vars elements, written below the returned prefix length only.  Returns the prefix lengths."""
+        n = len(n_vars)
+        nv = (C.c_uint32 * max(1, n))(*n_vars)
+        ns = (C.c_uint32 * max(1, n))(*[len(s) for s in selectors])
+        nc = (C.c_uint32 * max(1, n))(*[len(c) for c in columns])
+        flat_s = [(s.ptr if s is not None else None) for sel in selectors for s in sel]
+        flat_c = [c for cols in columns for c in cols]
+        sp = (C.c_void_p * max(1, len(flat_s)))(*flat_s)
+        cp = (C.c_void_p * max(1, len(flat_c)))(*[(c[0].ptr if c[0] is not None else None) for c in flat_c])
+        lv = (C.c_uint32 * max(1, len(flat_c)))(*[c[1] for c in flat_c])
+        cf = (F128 * max(1, len(flat_c)))(*[to_f128(c[2]) for c in flat_c])
+        ct = (F128 * max(1, n))(*[to_f128(c) for c in const_terms])
+        for t, o in enumerate(outs):
+            if o is not None and n_vars[t] <= 28 and o.len != 1 << n_vars[t]:
+                raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: flush witness: an output holds 2^n_vars elements")
+        op = (C.c_void_p * max(1, n))(*[(o.ptr if o is not None else None) for o in outs])
+        lens = (C.c_uint64 * max(1, n))()
+        _check(lib().bn_flush_witness_batch(self._h, n, nv, ns, sp, nc, cp, lv, cf, ct, op, lens))
+        return [int(lens[t]) for t in range(n)]
+
+    def flush_counters(self):
+        """bn_flush_counters: accepted bn_flush_witness_batch calls, the kernel launches they made, the flushes they served and how
+        many of those ran in more than one pass of nibble tables.  Rejected calls count nowhere."""
+        c = (C.c_uint64 * 4)()
+        _check(lib().bn_flush_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "flushes": int(c[2]), "multipass": int(c[3])}
 
     def partial_eval_high_batch(self, columns, query, query_vars, outs):
         """A batch of columns evaluated at the high coordinates of one point (bn_partial_eval_high_batch; evaluate_partial_high of

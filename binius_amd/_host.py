@@ -80,6 +80,12 @@ def host_lib():
             C.c_void_p, C.c_uint32, U32P, U32P, VPP, FP, VPP, VPP, C.c_uint32, U32P, FP, FP, C.c_void_p, C.c_uint64, FP, FP,
             U32P, U32P, U32P, FP, U32P, U32P, FP, U32P, U32P, FP, FP, C.POINTER(C.c_double),
         ]
+        U64P, DP = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+        L.bnh_flush_prodcheck_prove.restype = C.c_int
+        L.bnh_flush_prodcheck_prove.argtypes = [
+            C.c_void_p, C.c_uint32, U32P, U32P, U32P, U32P, VPP, U32P, U32P, U32P, VPP, U32P, FP, C.c_uint32, U32P, VPP, U32P, U32P, FP, FP, C.c_uint32,
+            C.c_void_p, C.c_uint64, FP, FP, FP, FP, FP, U64P, FP, FP, FP, FP, FP, U32P, U32P, U32P, FP, FP, U32P, U32P, DP,
+        ]
         L.bnh_evalcheck_bivariate_prove.restype = C.c_int
         L.bnh_evalcheck_bivariate_prove.argtypes = [C.c_void_p, C.c_uint32, U32P, U32P, VPP, FP, C.c_uint32, U32P, FP, C.c_void_p, C.c_uint64, FP, FP, FP, FP]
         L.bnh_rccl_open.argtypes = [C.c_char_p]
@@ -468,6 +474,119 @@ class GkrGpaPlan:
 
     def step_times_ms(self):
         return [self.step_ms[j] for j in range(self.max_n)]
+
+
+class FlushProdcheckPlan:
+    """The product-check phase of the constraint-system prover (bnh_flush_prodcheck_prove = binius_amd/host/flush.hpp;
+    crates/core/src/constraint_system/prove.rs:276-428): flush witnesses on the device, the grand-product argument over every flush and
+    non-zero oracle, and the reduction of the composite flush claims to claims on their selectors and inner columns.
+    flushes: dicts {"channel", "n_vars", "selectors": [(oracle id, device slice)], "entries": [("oracle", id, device slice, tower level) |
+    ("const", base)]} in the caller's order (sorted by channel); nonzero: [(id, device slice, tower level, n_vars)]; all columns only read.
+    gpa_*: the samples GkrGpaPlan takes, sized by the largest n_vars of all witnesses; red_batch_coeffs[g] / red_challenges[g]: one
+    coefficient and n_vars challenges per MLE-check, in the order of groups(flushes)."""
+
+    @staticmethod
+    def groups(flushes):
+        """[(n_vars, [flush indices], sorted de-duplicated ids)]: the composite flushes grouped by n_vars (= by evaluation point) in order
+        of first appearance."""
+        out = []
+        for f, fl in enumerate(flushes):
+            if not fl["selectors"]:
+                continue
+            g = next((g for g in out if g[0] == fl["n_vars"]), None)
+            if g is None:
+                g = (fl["n_vars"], [], set())
+                out.append(g)
+            g[1].append(f)
+            g[2].update([s[0] for s in fl["selectors"]] + [e[1] for e in fl["entries"] if e[0] == "oracle"])
+        return [(n, fs, sorted(ids)) for n, fs, ids in out]
+
+    @staticmethod
+    def scratch_elems(flushes, nonzero):
+        nv = [fl["n_vars"] for fl in flushes] + [z[3] for z in nonzero]
+        red = max([(len(ids) << n) + ((1 << (n - 1)) if n >= 1 else 0) for n, _, ids in FlushProdcheckPlan.groups(flushes)] + [0])
+        return 1 + sum((1 << n) + ((1 << n) if n >= 1 else 0) for n in nv) + GkrGpaPlan.scratch_elems(nv) + red
+
+    def __init__(self, hal, flushes, nonzero, mixing_challenge, permutation_challenges, scratch, gpa_batch_coeffs, gpa_sumcheck_challenges, gpa_challenges,
+                 red_batch_coeffs, red_challenges):
+        self.hal, self.flushes, self.nonzero, self.scratch = hal, flushes, nonzero, scratch
+        self.nf, self.nz = len(flushes), len(nonzero)
+        self.n_vars = [fl["n_vars"] for fl in flushes] + [z[3] for z in nonzero]
+        self.max_n = m = max(self.n_vars + [0])
+        self.grp = self.groups(flushes)
+        u32 = lambda v: (C.c_uint32 * max(1, len(v)))(*v)
+        vps = lambda v: (C.c_void_p * max(1, len(v)))(*[(x.ptr if x is not None else None) for x in v])
+        sels = [s for fl in flushes for s in fl["selectors"]]
+        ents = [e for fl in flushes for e in fl["entries"]]
+        self.a_ch, self.a_nv, self.a_ns = u32([fl["channel"] for fl in flushes]), u32([fl["n_vars"] for fl in flushes]), u32([len(fl["selectors"]) for fl in flushes])
+        self.a_sid, self.a_sp = u32([s[0] for s in sels]), vps([s[1] for s in sels])
+        self.a_ne = u32([len(fl["entries"]) for fl in flushes])
+        self.a_ek = u32([0 if e[0] == "oracle" else 1 for e in ents])
+        self.a_eid = u32([e[1] if e[0] == "oracle" else 0 for e in ents])
+        self.a_ep = vps([e[2] if e[0] == "oracle" else None for e in ents])
+        self.a_el = u32([e[3] if e[0] == "oracle" else 0 for e in ents])
+        self.a_ec = _f128_array([e[1] if e[0] == "const" else 0 for e in ents] or [0])
+        self.z_id, self.z_p, self.z_l, self.z_n = u32([z[0] for z in nonzero]), vps([z[1] for z in nonzero]), u32([z[2] for z in nonzero]), u32([z[3] for z in nonzero])
+        self.mix, self.perm, self.n_channels = _f128_array([mixing_challenge]), _f128_array(list(permutation_challenges) or [0]), len(permutation_challenges)
+        assert len(gpa_batch_coeffs) >= m and len(gpa_challenges) >= m and len(gpa_sumcheck_challenges) >= m
+        flat = [z for j in range(m) for z in gpa_sumcheck_challenges[j]]
+        self.bc, self.sc, self.gc = _f128_array(list(gpa_batch_coeffs[:m]) or [0]), _f128_array(flat or [0]), _f128_array(list(gpa_challenges[:m]) or [0])
+        assert len(red_batch_coeffs) >= len(self.grp) and all(len(red_challenges[g]) == self.grp[g][0] for g in range(len(self.grp)))
+        self.rbc = _f128_array(list(red_batch_coeffs[: len(self.grp)]) or [0])
+        self.rch = _f128_array([z for g in range(len(self.grp)) for z in red_challenges[g]] or [0])
+        k1 = max(1, self.nf + self.nz)
+        self.active = [sum(1 for n in self.n_vars if n > j) for j in range(m)]
+        self.prefix = (C.c_uint64 * max(1, self.nf))()
+        self.products, self.finals = (F128 * k1)(), (F128 * k1)()
+        self.proofs = (F128 * max(1, 3 * m * (m - 1) // 2))()
+        self.evals = (F128 * max(1, sum(2 * a + 1 for a in self.active)))()
+        self.points = (F128 * max(1, sum(self.n_vars)))()
+        g1 = max(1, len(self.grp))
+        self.n_checks, self.n_linear = C.c_uint32(0), C.c_uint32(0)
+        self.desc, self.ids = (C.c_uint32 * (3 * g1))(), (C.c_uint32 * max(1, sum(len(g[2]) for g in self.grp)))()
+        self.c_proofs = (F128 * max(1, sum(9 * g[0] for g in self.grp)))()
+        self.c_evals = (F128 * max(1, sum(len(g[2]) + 1 for g in self.grp)))()
+        self.linear = (C.c_uint32 * max(1, self.nf))()
+        self.phase_ms = (C.c_double * 4)()
+
+    def run(self):
+        rc = host_lib().bnh_flush_prodcheck_prove(
+            self.hal._h, self.nf, self.a_ch, self.a_nv, self.a_ns, self.a_sid, self.a_sp, self.a_ne, self.a_ek, self.a_eid, self.a_ep, self.a_el, self.a_ec,
+            self.nz, self.z_id, self.z_p, self.z_l, self.z_n, self.mix, self.perm, self.n_channels, self.scratch.ptr, self.scratch.len, self.bc, self.sc, self.gc,
+            self.rbc, self.rch, self.prefix, self.products, self.proofs, self.evals, self.points, self.finals, C.byref(self.n_checks), self.desc, self.ids,
+            self.c_proofs, self.c_evals, C.byref(self.n_linear), self.linear, self.phase_ms)
+        if rc != 0:
+            raise BnError(rc, host_lib().bnh_last_error().decode())
+
+    def output(self):
+        """The proof in the shape of tests/flush_ref.py flush_prodcheck_prove."""
+        m, k = self.max_n, self.nf + self.nz
+        proofs, evals, at_p, at_e = [], [], 0, 0
+        for j in range(m):
+            proofs.append([[from_f128(self.proofs[at_p + 3 * r + i]) for i in range(3)] for r in range(j)])
+            at_p += 3 * j
+            cnt = 2 * self.active[j] + 1
+            evals.append([from_f128(self.evals[at_e + i]) for i in range(cnt)])
+            at_e += cnt
+        points, at = [], 0
+        for n in self.n_vars:
+            points.append([from_f128(self.points[at + i]) for i in range(n)])
+            at += n
+        gpa = {"products": [from_f128(self.products[t]) for t in range(k)], "round_proofs": proofs, "layer_evals": evals, "final_points": points,
+               "final_evals": [from_f128(self.finals[t]) for t in range(k)]}
+        checks, at_i, at_c, at_v = [], 0, 0, 0
+        for g in range(self.n_checks.value):
+            n, n_ml, per = self.desc[3 * g], self.desc[3 * g + 1], self.desc[3 * g + 2]
+            ids = [int(self.ids[at_i + i]) for i in range(n_ml)]
+            rounds = [[from_f128(self.c_proofs[at_c + per * r + i]) for i in range(per)] for r in range(n)]
+            fin = [from_f128(self.c_evals[at_v + i]) for i in range(n_ml + 1)]
+            at_i, at_c, at_v = at_i + n_ml, at_c + per * n, at_v + n_ml + 1
+            checks.append({"n_vars": int(n), "ids": ids, "round_proofs": rounds, "final_evals": fin})
+        return {"prefix_lens": [int(self.prefix[f]) for f in range(self.nf)], "gpa": gpa, "checks": checks,
+                "linear_flushes": [int(self.linear[i]) for i in range(self.n_linear.value)]}
+
+    def phase_times_ms(self):
+        return dict(zip(("witnesses", "gpa", "reductions", "total"), [self.phase_ms[i] for i in range(4)]))
 
 
 class GkrExpPlan:

@@ -78,6 +78,7 @@ struct bn_ctx {
 	std::vector<uint64_t> h_s_evals;   // ... and its host copy: an NTT instance's basis is uploaded once, not per call
 	uint64_t ntt_calls_bs = 0, ntt_calls_tiled = 0, ntt_calls_layer = 0; // bn_ntt_* calls served per kernel family (bn_ntt_counters)
 	uint64_t exp_calls = 0, exp_launches = 0, exp_bits_launches = 0;     // bn_exp_circuit_layers / bn_bits_to_b128 (bn_exp_counters)
+	uint64_t flush_calls = 0, flush_launches = 0, flush_served = 0, flush_multipass = 0; // bn_flush_witness_batch (bn_flush_counters)
 	uint64_t pe_calls = 0, pe_launches = 0, pe_cols_kernel = 0, pe_cols_fallback = 0, pe_max_share = 0, pe_routed = 0; // bn_partial_eval_counters
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -760,6 +761,43 @@ struct bits_job {
 	uint32_t start, pad_;
 };
 hipError_t launch_bits_to_b128(hipStream_t s, const bits_job *d_jobs, uint32_t n_jobs, uint32_t total_blocks);
+
+// ---- kernels_flush.hip: the masked flush witnesses of a batch of channel flushes (make_masked_flush_witnesses,
+// core/src/constraint_system/prove.rs:671-881).  A job is one flush; a unit (one workgroup) is a run of kFlushUnitRows rows that the
+// workgroup takes through every pass of its flush.
+struct flush_col {
+	const void *ptr;  // the packed subfield column
+	f128 coeff;       // its mixing power
+	uint32_t level;   // tower level 0, 3 .. 7
+	uint32_t table;   // first nibble table of the column inside its pass; kFlushNoTable: none (level 0, or coefficient ONE)
+};
+constexpr uint32_t kFlushNoTable = 0xFFFFFFFFu;
+constexpr uint32_t kFlushUnitRows = 2048;   // rows of a unit: eight per thread
+constexpr uint32_t kFlushPassTables = 256;  // nibble tables (256 B each) of one pass: 64 KiB of LDS
+constexpr uint32_t kFlushMaxPasses = 8;     // 64 columns x 32 tables / kFlushPassTables
+constexpr uint32_t kFlushSelChunk = 1u << 12; // 16-byte elements of a selector that one workgroup of the pre-pass scans
+struct flush_job {
+	const flush_col *cols;         // n_cols descriptors, in pass order
+	const uint32_t *const *sels;   // n_sels device pointers to the selector columns
+	const uint64_t *sel_prefix;    // n_sels non-zero prefixes (unclipped), written by the pre-pass
+	uint4 *out;
+	f128 const_term;
+	uint64_t rows;                 // 2^n_vars
+	uint32_t n_cols, n_sels;
+	uint32_t start;                // first unit of this job in the launch
+	uint32_t n_passes;
+	uint32_t pass_first[kFlushMaxPasses + 1]; // columns [pass_first[p], pass_first[p + 1]) belong to pass p
+	uint32_t pad_;
+};
+// a selector of the pre-pass: `start` = its first workgroup, each workgroup scans kFlushSelChunk elements
+struct flush_sel {
+	const uint4 *col;
+	uint64_t *prefix; // zero before the launch; receives 128 * (1 + index of the last non-zero element), 0 if there is none
+	uint64_t elems;   // 16-byte elements of the column
+	uint32_t start, pad_;
+};
+hipError_t launch_flush_prefix(hipStream_t s, const flush_sel *d_sels, uint32_t n_sels, uint32_t total_wgs);
+hipError_t launch_flush_witness(hipStream_t s, const flush_job *d_jobs, uint32_t n_jobs, uint32_t total_units);
 
 // ---- kernels_partial_eval.hip: a batch of columns evaluated at the high coordinates of one point (evaluate_partial_high,
 // evalcheck/subclaims.rs:356-439): out_c[i] = sum_j vec[j] * M_c[j * 2^b + i] for every column c with 2^b <= 1024 outputs.  A unit

@@ -26,6 +26,7 @@
 
 #include "eq_ind.hpp"
 #include "evalcheck.hpp"
+#include "flush.hpp"
 #include "fri.hpp"
 #include "gkr_exp.hpp"
 #include "gkr_gpa.hpp"
@@ -1036,6 +1037,111 @@ int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths,
 			}
 			if (layer_ms_out) layer_ms_out[L] = out.layer_ms[L];
 		}
+		return 0;
+	} catch (const Error &e) {
+		g_err = e.what();
+		return (int)e.kind();
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return BN_ERR_CORE_LIB;
+	}
+}
+
+// The product-check phase of the constraint-system prover (core/src/constraint_system/prove.rs:276-428) through the C++ mirror
+// binius_amd/host/flush.hpp; the arguments and the layout of the outputs are described in include/binius_amd_host.h.
+int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *channel_ids, const uint32_t *flush_n_vars, const uint32_t *n_selectors,
+                              const uint32_t *selector_ids, const void *const *d_selectors, const uint32_t *n_entries, const uint32_t *entry_kinds,
+                              const uint32_t *entry_ids, const void *const *d_entry_columns, const uint32_t *entry_levels, const bn_f128 *entry_consts,
+                              uint32_t n_nonzero, const uint32_t *nonzero_ids, const void *const *d_nonzero_columns, const uint32_t *nonzero_levels,
+                              const uint32_t *nonzero_n_vars, const bn_f128 *mixing_challenge, const bn_f128 *permutation_challenges, uint32_t n_channels,
+                              void *d_scratch, uint64_t scratch_elems, const bn_f128 *gpa_batch_coeffs, const bn_f128 *gpa_sumcheck_challenges,
+                              const bn_f128 *gpa_challenges, const bn_f128 *red_batch_coeffs, const bn_f128 *red_challenges, uint64_t *prefix_lens_out,
+                              bn_f128 *products_out, bn_f128 *gpa_round_proofs_out, bn_f128 *gpa_layer_evals_out, bn_f128 *gpa_final_points_out,
+                              bn_f128 *gpa_final_evals_out, uint32_t *n_checks_out, uint32_t *check_desc_out, uint32_t *check_ids_out,
+                              bn_f128 *check_round_proofs_out, bn_f128 *check_final_evals_out, uint32_t *n_linear_out, uint32_t *linear_flushes_out,
+                              double *phase_ms_out)
+{
+	try {
+		if (!ctx) throw Error(Error::InputValidation, "null ctx");
+		if (n_checks_out) *n_checks_out = 0;
+		if (n_linear_out) *n_linear_out = 0;
+		if (n_flushes + n_nonzero == 0) return 0;
+		if (!mixing_challenge || !d_scratch || !products_out || !gpa_final_evals_out || !n_checks_out || !n_linear_out) throw Error(Error::InputValidation, "null argument");
+		if (n_flushes && (!channel_ids || !flush_n_vars || !n_selectors || !n_entries || !entry_kinds || !entry_ids || !d_entry_columns || !entry_levels || !entry_consts ||
+		                  !permutation_challenges || !prefix_lens_out || !check_desc_out || !check_ids_out || !check_round_proofs_out || !check_final_evals_out ||
+		                  !linear_flushes_out || !red_batch_coeffs))
+			throw Error(Error::InputValidation, "null argument");
+		if (n_nonzero && (!nonzero_ids || !d_nonzero_columns || !nonzero_levels || !nonzero_n_vars)) throw Error(Error::InputValidation, "null argument");
+		auto vec = [](const bn_f128 *p, size_t n) {
+			std::vector<B128> v;
+			for (size_t i = 0; p && i < n; i++) v.emplace_back(p[i].lo, p[i].hi);
+			return v;
+		};
+		std::vector<FlushSpec> flushes(n_flushes);
+		std::vector<NonZeroSpec> nonzero(n_nonzero);
+		size_t at_s = 0, at_e = 0, max_n = 0;
+		for (uint32_t f = 0; f < n_flushes; f++) {
+			FlushSpec &fl = flushes[f];
+			fl.channel = channel_ids[f];
+			fl.n_vars = flush_n_vars[f];
+			max_n = std::max(max_n, fl.n_vars);
+			if (n_selectors[f] && (!selector_ids || !d_selectors)) throw Error(Error::InputValidation, "null argument");
+			for (uint32_t i = 0; i < n_selectors[f]; i++, at_s++) fl.selectors.push_back(FlushSelector{selector_ids[at_s], d_selectors[at_s]});
+			for (uint32_t i = 0; i < n_entries[f]; i++, at_e++) {
+				FlushEntry e;
+				if (entry_kinds[at_e] != BNH_FLUSH_ORACLE && entry_kinds[at_e] != BNH_FLUSH_CONST) throw Error(Error::InputValidation, "unknown flush entry kind");
+				e.is_const = entry_kinds[at_e] == BNH_FLUSH_CONST;
+				e.id = entry_ids[at_e];
+				e.column = d_entry_columns[at_e];
+				e.level = entry_levels[at_e];
+				e.base = B128(entry_consts[at_e].lo, entry_consts[at_e].hi);
+				fl.entries.push_back(e);
+			}
+		}
+		for (uint32_t i = 0; i < n_nonzero; i++) {
+			nonzero[i] = NonZeroSpec{nonzero_ids[i], nonzero_n_vars[i], d_nonzero_columns[i], nonzero_levels[i]};
+			max_n = std::max(max_n, nonzero[i].n_vars);
+		}
+		if (max_n > BN_PRODUCT_TREE_MAX_VARS) throw Error(Error::InputValidation, "n_vars out of range (0 .. 28)");
+		if (max_n >= 1 && (!gpa_batch_coeffs || !gpa_challenges || !gpa_layer_evals_out || !gpa_final_points_out)) throw Error(Error::InputValidation, "null argument");
+		if (max_n >= 2 && (!gpa_sumcheck_challenges || !gpa_round_proofs_out)) throw Error(Error::InputValidation, "null argument");
+		size_t red_n = 0;
+		const std::vector<FlushMleCheck> groups = flush_groups(flushes);
+		for (const FlushMleCheck &g : groups) red_n += g.n_vars;
+		if (red_n && !red_challenges) throw Error(Error::InputValidation, "null argument");
+		ComputeLayer hal(ctx);
+		Mi355xBackend backend(hal);
+		const FlushProdcheckOutput out =
+		    flush_prodcheck_prove(hal, backend, flushes, nonzero, B128(mixing_challenge->lo, mixing_challenge->hi), vec(permutation_challenges, n_channels),
+		                          FSliceMut{d_scratch, (size_t)scratch_elems}, vec(gpa_batch_coeffs, max_n), vec(gpa_sumcheck_challenges, max_n * (max_n ? max_n - 1 : 0) / 2),
+		                          vec(gpa_challenges, max_n), vec(red_batch_coeffs, groups.size()), vec(red_challenges, red_n));
+		for (uint32_t f = 0; f < n_flushes; f++) prefix_lens_out[f] = out.prefix_lens[f];
+		size_t at_p = 0, at_l = 0, at_f = 0;
+		for (size_t t = 0; t < out.gpa.products.size(); t++) {
+			products_out[t] = out.gpa.products[t].raw();
+			gpa_final_evals_out[t] = out.gpa.final_evals[t].raw();
+			for (const B128 &v : out.gpa.final_points[t]) gpa_final_points_out[at_f++] = v.raw();
+		}
+		for (size_t j = 0; j < out.gpa.round_proofs.size(); j++) {
+			for (const B128 &v : out.gpa.round_proofs[j]) gpa_round_proofs_out[at_p++] = v.raw();
+			for (const B128 &v : out.gpa.layer_evals[j]) gpa_layer_evals_out[at_l++] = v.raw();
+		}
+		*n_checks_out = (uint32_t)out.checks.size();
+		size_t at_i = 0, at_c = 0, at_v = 0;
+		for (size_t g = 0; g < out.checks.size(); g++) {
+			const FlushMleCheck &c = out.checks[g];
+			check_desc_out[3 * g] = (uint32_t)c.n_vars;
+			check_desc_out[3 * g + 1] = (uint32_t)c.ids.size();
+			check_desc_out[3 * g + 2] = c.round_proofs.empty() ? 0 : (uint32_t)c.round_proofs[0].size();
+			for (size_t id : c.ids) check_ids_out[at_i++] = (uint32_t)id;
+			for (const auto &r : c.round_proofs)
+				for (const B128 &v : r) check_round_proofs_out[at_c++] = v.raw();
+			for (const B128 &v : c.final_evals) check_final_evals_out[at_v++] = v.raw();
+		}
+		*n_linear_out = (uint32_t)out.linear_flushes.size();
+		for (size_t i = 0; i < out.linear_flushes.size(); i++) linear_flushes_out[i] = (uint32_t)out.linear_flushes[i];
+		if (phase_ms_out)
+			for (int i = 0; i < 4; i++) phase_ms_out[i] = out.phase_ms[i];
 		return 0;
 	} catch (const Error &e) {
 		g_err = e.what();

@@ -271,6 +271,21 @@ unsafe extern "C" {
 	) -> c_int;
 	pub fn bn_bits_to_b128(ctx: *mut bn_ctx, n: u32, log_lens: *const u32, d_srcs: *const *const c_void, d_dsts: *const *mut c_void) -> c_int;
 	pub fn bn_exp_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_flush_witness_batch(
+		ctx: *mut bn_ctx,
+		n_flushes: u32,
+		n_vars: *const u32,
+		n_selectors: *const u32,
+		d_selectors: *const *const c_void,
+		n_columns: *const u32,
+		d_columns: *const *const c_void,
+		tower_levels: *const u32,
+		coeffs: *const bn_f128,
+		const_terms: *const bn_f128,
+		d_outs: *const *mut c_void,
+		prefix_lens_out: *mut u64,
+	) -> c_int;
+	pub fn bn_flush_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 	pub fn bn_partial_eval_high_batch(
 		ctx: *mut bn_ctx,
 		cols: *const c_void,

@@ -185,6 +185,38 @@ int bn_bits_to_b128(bn_ctx *ctx, uint32_t n, const uint32_t *log_lens, const voi
  * made, and the launches of bn_bits_to_b128.  A rejected call counts nowhere. */
 enum { BN_EXP_CALLS = 0, BN_EXP_LAUNCHES = 1, BN_EXP_BITS_LAUNCHES = 2, BN_EXP_N = 3 };
 int bn_exp_counters(bn_ctx *ctx, uint64_t *counters /*[BN_EXP_N]*/);
+/* The masked witnesses of a batch of channel flushes: make_masked_flush_witnesses (core/src/constraint_system/prove.rs:671-881), the
+ * input of the grand-product argument over every flush oracle (prove.rs:386-400).  Flush f has n_vars[f] in 0 .. 28 variables
+ * (2^n_vars rows), n_selectors[f] in 0 .. 8 selectors and n_columns[f] in 1 .. 64 columns (none is the reference's
+ * EmptyFlushOracles: BN_ERR_INPUT_VALIDATION).  d_selectors, d_columns, tower_levels and coeffs are HOST arrays, concatenated flush
+ * after flush; the first two hold device pointers.  A selector is a B1 column, a column holds values of tower level 0 or 3 .. 7
+ * (levels may be mixed inside a flush), both packed into F as bn_hal_multilinear describes: bit i & 127 of 16-byte element i >> 7
+ * is the level-0 value of row i; a column with n_vars + level < 7 occupies the low 2^(n_vars + level) bits of one element.  A
+ * subfield value embeds into B128 as the identity on the low bits.
+ *   p_s           = 128 * (1 + index of the last non-zero 16-byte element of selector s), 0 if there is none, clipped to 2^n_vars
+ *                   (count_zero_suffixes, prove.rs:883-902, at a 128-bit underlier)
+ *   prefix_len[f] = min_s p_s, or 2^n_vars without selectors
+ *   d_outs[f][i]  = (every selector has bit i set) ? const_terms[f] + sum_j coeffs[f, j] * col_{f, j}[i] : ONE    for i < prefix_len[f]
+ * bit-exact; the caller passes const_terms[f] = r_channel + sum over the flush's constant entries of base * alpha^k and the mixing
+ * powers alpha^k of its column entries as coeffs (prove.rs:744-771).  Elements at and beyond prefix_len[f] are NOT written:
+ * bn_product_tree_layers takes prefix_lens_out[f] as input_lens and counts the tail as ONE.  The result does not depend on which
+ * coefficients equal ONE (prove.rs:836-844 special-cases the first mixing power; so does the kernel).  Inputs are only read; an
+ * output must not overlap an input or another output of the call; pointers are 16-byte aligned; n_flushes = 0 is a no-op; a
+ * rejected call launches nothing.  The whole batch is ONE launch, behind ONE launch that finds the selectors' prefixes when the
+ * call has a selector, whatever the number of flushes, their sizes and levels.  Returns when the witnesses are complete and
+ * prefix_lens_out is filled in. */
+#define BN_FLUSH_MAX_VARS 28
+#define BN_FLUSH_MAX_SELECTORS 8
+#define BN_FLUSH_MAX_COLUMNS 64
+int bn_flush_witness_batch(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *n_vars, const uint32_t *n_selectors,
+                           const void *const *d_selectors, const uint32_t *n_columns, const void *const *d_columns,
+                           const uint32_t *tower_levels, const bn_f128 *coeffs, const bn_f128 *const_terms, void *const *d_outs,
+                           uint64_t *prefix_lens_out);
+/* Read-only, per context (not part of the reference interface): accepted bn_flush_witness_batch calls, the kernel launches they
+ * made, the flushes they served, and how many of those needed more than one pass of nibble tables.  A rejected call counts
+ * nowhere. */
+enum { BN_FLUSH_CALLS = 0, BN_FLUSH_LAUNCHES = 1, BN_FLUSH_SERVED = 2, BN_FLUSH_MULTIPASS = 3, BN_FLUSH_N = 4 };
+int bn_flush_counters(bn_ctx *ctx, uint64_t *counters /*[BN_FLUSH_N]*/);
 /* A batch of columns evaluated at the high coordinates of one point: evaluate_partial_high (math/src/multilinear_extension.rs:
  * 253-300) of the inner column of every shifted or packed virtual column of an evalcheck round (collect_projected_mles,
  * core/src/protocols/evalcheck/subclaims.rs:356-439), where every claim of a table shares the point.  Column c holds 2^n_vars

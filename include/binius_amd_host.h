@@ -189,6 +189,49 @@ int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths,
                       bn_f128 *round_proofs_out, uint32_t *provers_per_layer_out, uint32_t *evals_per_prover_out, bn_f128 *multilinear_evals_out,
                       uint32_t *claims_per_layer_out, uint32_t *claim_n_vars_out, bn_f128 *claim_points_out, bn_f128 *claim_evals_out, double *layer_ms_out);
 
+/* The product-check phase of the constraint-system prover (core/src/constraint_system/prove.rs:276-428) through the C++ mirror
+ * binius_amd/host/flush.hpp: the flush witnesses made on the device by ONE bn_flush_witness_batch (make_masked_flush_witnesses, :671-881),
+ * the non-zero columns widened by ONE bn_partial_eval_high_batch at query_vars = 0, gkr_gpa::batch_prove over chain(flush witnesses with their
+ * prefix lengths, non-zero witnesses) (:386-400, as bnh_gkr_gpa_prove runs it), and reduce_flush_evalcheck_claims (:1017-1117): the claim on a
+ * flush without selectors (a linear combination) is passed through; the claims on the others (composite oracles 1 + S * L,
+ * constraint_system/verify.rs:519-571) are grouped by equal evaluation point in order of first appearance -- flushes of equal n_vars leave the
+ * grand-product argument with the same point --, and per group ONE EqIndSumcheckProver runs at that point over the sorted, de-duplicated
+ * union of the group's oracle ids (oracle/constraint.rs:114-129) as a front-loaded batch of one (evalcheck/subclaims.rs:589-633).
+ *   Flushes in the caller's order (sorted by channel, :333).  Per flush f: channel_ids[f] < n_channels, flush_n_vars[f] in 0 .. 28,
+ *     n_selectors[f] in 0 .. 7, n_entries[f].  selector_ids / d_selectors: the selectors (caller's oracle id, packed B1 column), flushes
+ *     concatenated.  entry_kinds / entry_ids / d_entry_columns / entry_levels / entry_consts: the entries in order, flushes concatenated:
+ *     BNH_FLUSH_ORACLE (id, column of tower level 0 or 3 .. 7 packed into F) or BNH_FLUSH_CONST (base = entry_consts[i]; the rest ignored).
+ *     Entry k of a flush carries the mixing power alpha^k whatever its kind (:744-771).  A flush needs an ORACLE entry (EmptyFlushOracles);
+ *     a composite flush reads at most 16 distinct oracles.  Equal ids must name equal columns.
+ *   Non-zero oracles: nonzero_ids / d_nonzero_columns / nonzero_levels / nonzero_n_vars.  A zero product among them is the reference's
+ *     Error::Zeros (:311-316): BN_ERR_INPUT_VALIDATION with a bnh_last_error text that starts with "Zeros", before any flush work runs.
+ *   mixing_challenge; permutation_challenges[n_channels].
+ *   d_scratch: at least flush_prodcheck_scratch_elems elements = 1 + sum over all witnesses of 2^n_vars (+ 2^n_vars more for n_vars >= 1: the
+ *     arena) + the grand-product prover's scratch (bnh_gkr_gpa_prove) + the largest m * 2^n + 2^(n - 1) over the groups (m multilinears).
+ *   gpa_batch_coeffs / gpa_sumcheck_challenges / gpa_challenges: as bnh_gkr_gpa_prove takes them, N = the largest n_vars of all witnesses.
+ *   red_batch_coeffs[g], red_challenges: per group one batch coefficient and its n_vars challenges, groups concatenated.
+ * Outputs: prefix_lens_out[n_flushes]; products_out / gpa_final_evals_out [n_flushes + n_nonzero] and gpa_round_proofs_out /
+ *   gpa_layer_evals_out / gpa_final_points_out as bnh_gkr_gpa_prove lays them out, claims in the order flushes, non-zero oracles.
+ *   *n_checks_out groups; check_desc_out[3 g ..] = (n_vars, multilinears m, coefficients per round: max(2, largest n_selectors + 1) + 1);
+ *   check_ids_out: each group's m ids; check_round_proofs_out: its n_vars rounds of truncated coefficients; check_final_evals_out: its m
+ *   evaluations then the indicator's -- all groups concatenated.  The new claim on id i of a group is (id, the group's challenges reversed,
+ *   its evaluation); the indicator's evaluation is written and dropped (subclaims.rs:619-630).
+ *   *n_linear_out, linear_flushes_out: the flushes whose claims (their gpa final point and evaluation) pass through unchanged.
+ *   phase_ms_out[4]: witnesses, grand-product argument, reductions, total (wall time), or NULL.
+ * The caller's columns are only read. */
+enum { BNH_FLUSH_ORACLE = 0, BNH_FLUSH_CONST = 1 };
+int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *channel_ids, const uint32_t *flush_n_vars, const uint32_t *n_selectors,
+                              const uint32_t *selector_ids, const void *const *d_selectors, const uint32_t *n_entries, const uint32_t *entry_kinds,
+                              const uint32_t *entry_ids, const void *const *d_entry_columns, const uint32_t *entry_levels, const bn_f128 *entry_consts,
+                              uint32_t n_nonzero, const uint32_t *nonzero_ids, const void *const *d_nonzero_columns, const uint32_t *nonzero_levels,
+                              const uint32_t *nonzero_n_vars, const bn_f128 *mixing_challenge, const bn_f128 *permutation_challenges, uint32_t n_channels,
+                              void *d_scratch, uint64_t scratch_elems, const bn_f128 *gpa_batch_coeffs, const bn_f128 *gpa_sumcheck_challenges,
+                              const bn_f128 *gpa_challenges, const bn_f128 *red_batch_coeffs, const bn_f128 *red_challenges, uint64_t *prefix_lens_out,
+                              bn_f128 *products_out, bn_f128 *gpa_round_proofs_out, bn_f128 *gpa_layer_evals_out, bn_f128 *gpa_final_points_out,
+                              bn_f128 *gpa_final_evals_out, uint32_t *n_checks_out, uint32_t *check_desc_out, uint32_t *check_ids_out,
+                              bn_f128 *check_round_proofs_out, bn_f128 *check_final_evals_out, uint32_t *n_linear_out, uint32_t *linear_flushes_out,
+                              double *phase_ms_out);
+
 /* One round of evalcheck's bivariate sumchecks: one call of prove_bivariate_sumchecks_with_switchover (core/src/protocols/evalcheck/
  * subclaims.rs:549-586) with the witness construction in front of it (process_shifted_sumcheck, process_packed_sumcheck :52-145,
  * collect_projected_mles :356-439) through the C++ mirror binius_amd/host/evalcheck.hpp.  The caller hands in explicit multilinear lists;
