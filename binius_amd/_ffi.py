@@ -161,6 +161,8 @@ def lib():
         "bn_flush_counters": [vp, C.POINTER(u64)],
         "bn_partial_eval_high_batch": [vp, vp, u32, vp, u32, C.POINTER(vp)],
         "bn_partial_eval_counters": [vp, C.POINTER(u64)],
+        "bn_univariate_fold_batch": [vp, vp, u32, u32, PF, C.POINTER(vp)],
+        "bn_univariate_fold_counters": [vp, C.POINTER(u64)],
         "bn_log_chunks_range": [C.POINTER(MemMap), u32, C.POINTER(u32), C.POINTER(u32)],
         "bn_pick_log_chunks": [C.POINTER(MemMap), u32, C.POINTER(u32)],
         "bn_kernel_launch": [vp, C.POINTER(MemMap), u32, C.POINTER(KOp), u32, C.POINTER(u32), u32, u32, PF, vp],
@@ -216,6 +218,7 @@ ABI_SYMBOLS = [
     "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals",
     "bn_product_tree_layers", "bn_pad_with_ones", "bn_exp_circuit_layers", "bn_bits_to_b128", "bn_exp_counters",
     "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
+    "bn_univariate_fold_batch", "bn_univariate_fold_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -876,6 +879,31 @@ class Context:
         _check(lib().bn_partial_eval_counters(self._h, c))
         return {"calls": int(c[0]), "launches": int(c[1]), "cols_kernel": int(c[2]), "cols_fallback": int(c[3]), "max_share": int(c[4]),
                 "fold_left_routed": int(c[5])}
+
+    def univariate_fold_batch(self, columns, k, coeffs, outs):
+        """The fold of the univariate round of the univariate-skip zerocheck for a batch of columns in one launch
+        (bn_univariate_fold_batch; fold_univariate_round, sumcheck/prove/zerocheck.rs:384-434).  columns: (DevSlice, tower_level,
+        n_vars) per column, level 0 or 3; k = skip_rounds; coeffs: the 2^k coefficients as ints (host); outs[c]: a DevSlice of
+        2^(n_vars - k) elements that receives what fold_right(column, level, coeffs, out) would write."""
+        n = len(columns)
+        if len(outs) != n:
+            raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: one output per column")
+        coeffs = list(coeffs)
+        if 0 <= k <= 8 and len(coeffs) != 1 << k:
+            raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: univariate fold: 2^skip_rounds coefficients")
+        cols = (PeColumn * max(1, n))(*[PeColumn(c[0].ptr if c[0] is not None else None, c[1], c[2]) for c in columns])
+        for c, o in zip(columns, outs):
+            if o is not None and 1 <= k <= c[2] <= 40 and o.len != 1 << (c[2] - k):
+                raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: output has the wrong number of elements")
+        op = (C.c_void_p * max(1, n))(*[(o.ptr if o is not None else None) for o in outs])
+        _check(lib().bn_univariate_fold_batch(self._h, C.cast(cols, C.c_void_p), n, k, _f128_array(coeffs), op))
+
+    def univariate_fold_counters(self):
+        """bn_univariate_fold_counters: accepted bn_univariate_fold_batch calls, the kernel launches they made, the columns they
+        served.  Rejected calls count nowhere."""
+        c = (C.c_uint64 * 3)()
+        _check(lib().bn_univariate_fold_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "columns": int(c[2])}
 
     # ---- accumulate_kernels / map_kernels
     def pick_log_chunks(self, mem_maps):

@@ -4,7 +4,7 @@ call, i.e. the prover loop driven at compiled-host speed over the same C ABI."""
 import ctypes as C
 import os
 
-from ._ffi import F128, BnError, _f128_array, from_f128, lib, to_f128
+from ._ffi import BN_ERR_INPUT_VALIDATION, F128, BnError, _f128_array, from_f128, lib, to_f128
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libbinius_amd_host.so")
@@ -88,6 +88,13 @@ def host_lib():
         ]
         L.bnh_evalcheck_bivariate_prove.restype = C.c_int
         L.bnh_evalcheck_bivariate_prove.argtypes = [C.c_void_p, C.c_uint32, U32P, U32P, VPP, FP, C.c_uint32, U32P, FP, C.c_void_p, C.c_uint64, FP, FP, FP, FP]
+        L.bnh_zerocheck_batch_scratch_elems.restype = C.c_uint64
+        L.bnh_zerocheck_batch_scratch_elems.argtypes = [C.c_uint32, C.c_uint32, U32P, U32P]
+        L.bnh_zerocheck_batch_prove.restype = C.c_int
+        L.bnh_zerocheck_batch_prove.argtypes = [
+            C.c_void_p, C.c_uint32, C.c_uint32, U32P, U32P, VPP, U32P, U32P, C.c_void_p, U32P, C.c_void_p, U32P, U32P, FP, FP, FP, FP, FP, FP, C.c_void_p, C.c_uint64,
+            FP, FP, FP, FP, FP, FP, FP, FP, DP, U64P,
+        ]
         L.bnh_rccl_open.argtypes = [C.c_char_p]
         L.bnh_rccl_unique_id.argtypes = [C.c_void_p]
         L.bnh_rccl_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -879,3 +886,91 @@ class RcclComm:
         if self.handle:
             host_lib().bnh_rccl_destroy(self.handle)
             self.handle = None
+
+
+class ZerocheckBatchPlan:
+    """batch_zerocheck::batch_prove (bnh_zerocheck_batch_prove = binius_amd/host/zerocheck.hpp; crates/core/src/protocols/sumcheck/prove/
+    batch_zerocheck.rs:166-293): the batched univariate-skip zerocheck for the domain field B8, the transcript's samples handed in.
+    tables: in ascending n_vars, each (n_vars, columns, compositions) with columns = [(DevSlice of the packed column, tower_level 0 or 3)]
+    (only read) and compositions = [(steps, steps_of_the_leading_form, degree)] in compile_expr's notation, constants in B8; k =
+    skip_rounds; zerocheck_challenges and sumcheck_challenges: max_n - k each; batch_coeffs: one per table; reduction_challenges: k;
+    scratch: a device slice of at least scratch_elems(tables, k) elements.  run() returns the proof as a dict: message, round_coeffs (all
+    coefficients, padded to max(2, largest degree) + 2), final_evals (per table, the indicator's last), reduction_round_coeffs,
+    reduction_final_evals, skipped_challenges, unskipped_challenges, concat_multilinear_evals; phase_ms / phase_calls afterwards."""
+
+    PHASES = ("univariate", "fold", "multilinear", "projection", "reduction")
+
+    @staticmethod
+    def scratch_elems(tables, k):
+        n = len(tables)
+        nv = (C.c_uint32 * max(1, n))(*[t[0] for t in tables])
+        nc = (C.c_uint32 * max(1, n))(*[len(t[1]) for t in tables])
+        return int(host_lib().bnh_zerocheck_batch_scratch_elems(n, k, nv, nc))
+
+    def __init__(self, hal, tables, k, zerocheck_challenges, batch_coeffs, univariate_challenge, sumcheck_challenges, reduction_batch_coeff,
+                 reduction_challenges, scratch):
+        from ._ffi import make_steps
+
+        self.hal, self.k, self.n = hal, k, len(tables)
+        self._keep = (tables, scratch)
+        self.n_cols = [len(t[1]) for t in tables]
+        self.nv = (C.c_uint32 * max(1, self.n))(*[t[0] for t in tables])
+        self.nc = (C.c_uint32 * max(1, self.n))(*self.n_cols)
+        cols = [c for t in tables for c in t[1]]
+        self.ptrs = (C.c_void_p * max(1, len(cols)))(*[(c[0].ptr if c[0] is not None else None) for c in cols])
+        self.levels = (C.c_uint32 * max(1, len(cols)))(*[c[1] for c in cols])
+        comps = [c for t in tables for c in t[2]]
+        self.ncomp = (C.c_uint32 * max(1, self.n))(*[len(t[2]) for t in tables])
+        flat, flat_inf = [st for c in comps for st in c[0]], [st for c in comps for st in c[1]]
+        self.steps, self.steps_inf = make_steps(flat) if flat else None, make_steps(flat_inf) if flat_inf else None
+        self.n_steps = (C.c_uint32 * max(1, len(comps)))(*[len(c[0]) for c in comps])
+        self.n_steps_inf = (C.c_uint32 * max(1, len(comps)))(*[len(c[1]) for c in comps])
+        self.degrees = (C.c_uint32 * max(1, len(comps)))(*[c[2] for c in comps])
+        max_n = max([t[0] for t in tables] + [0])
+        self.rounds = max(0, max_n - k)
+        d_top = max([c[2] for c in comps] + [0])
+        self.msg_len = max(0, (d_top << k) - (1 << k)) if 0 <= k <= 8 and d_top <= 256 else 0
+        self.per_round = max(2, min(d_top, 256)) + 2
+        self.zc, self.sc = _f128_array(list(zerocheck_challenges) or [0]), _f128_array(list(sumcheck_challenges) or [0])
+        self.bc, self.rc = _f128_array(list(batch_coeffs) or [0]), _f128_array(list(reduction_challenges) or [0])
+        self.lens = (len(zerocheck_challenges), len(sumcheck_challenges), len(batch_coeffs), len(reduction_challenges))
+        self.z, self.rb = to_f128(univariate_challenge), to_f128(reduction_batch_coeff)
+        self.scratch = scratch
+        total = sum(self.n_cols)
+        self.message = (F128 * max(1, self.msg_len))()
+        self.coeffs = (F128 * max(1, self.per_round * self.rounds))()
+        self.final = (F128 * (total + self.n + 1))()
+        self.red_coeffs = (F128 * max(1, 3 * max(0, min(k, 8))))()
+        self.red_final = (F128 * (total + 1))()
+        self.skipped, self.unskipped = (F128 * max(1, min(k, 8)))(), (F128 * max(1, self.rounds))()
+        self.concat = (F128 * max(1, total))()
+        self.phase_ms, self.phase_calls = (C.c_double * 5)(), (C.c_uint64 * 5)()
+
+    def run(self):
+        if self.lens != (self.rounds, self.rounds, self.n, self.k):
+            raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: zerocheck: max_n - k zerocheck and sumcheck challenges, one coefficient per table, k reduction challenges")
+        rc = host_lib().bnh_zerocheck_batch_prove(
+            self.hal._h, self.n, self.k, self.nv, self.nc, self.ptrs, self.levels, self.ncomp, C.cast(self.steps, C.c_void_p), self.n_steps,
+            C.cast(self.steps_inf, C.c_void_p), self.n_steps_inf, self.degrees, self.zc, self.bc, C.byref(self.z), self.sc, C.byref(self.rb), self.rc,
+            self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0, self.message, self.coeffs, self.final,
+            self.red_coeffs, self.red_final, self.skipped, self.unskipped, self.concat, self.phase_ms, self.phase_calls)
+        if rc != 0:
+            raise BnError(rc, host_lib().bnh_last_error().decode())
+        ints = lambda a, n: [from_f128(a[i]) for i in range(n)]  # noqa: E731
+        finals, at = [], 0
+        for m in self.n_cols:
+            finals.append(ints(self.final, at + m + 1)[at:])
+            at += m + 1
+        total = sum(self.n_cols)
+        return {
+            "message": ints(self.message, self.msg_len),
+            "round_coeffs": [ints(self.coeffs, self.per_round * (r + 1))[self.per_round * r:] for r in range(self.rounds)],
+            "final_evals": finals,
+            "reduction_round_coeffs": [ints(self.red_coeffs, 3 * (r + 1))[3 * r:] for r in range(self.k)],
+            "reduction_final_evals": ints(self.red_final, total + 1),
+            "skipped_challenges": ints(self.skipped, self.k), "unskipped_challenges": ints(self.unskipped, self.rounds),
+            "concat_multilinear_evals": ints(self.concat, total),
+        }
+
+    def phases(self):
+        return {name: (float(self.phase_ms[i]), int(self.phase_calls[i])) for i, name in enumerate(self.PHASES)}

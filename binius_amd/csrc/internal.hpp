@@ -80,6 +80,7 @@ struct bn_ctx {
 	uint64_t exp_calls = 0, exp_launches = 0, exp_bits_launches = 0;     // bn_exp_circuit_layers / bn_bits_to_b128 (bn_exp_counters)
 	uint64_t flush_calls = 0, flush_launches = 0, flush_served = 0, flush_multipass = 0; // bn_flush_witness_batch (bn_flush_counters)
 	uint64_t pe_calls = 0, pe_launches = 0, pe_cols_kernel = 0, pe_cols_fallback = 0, pe_max_share = 0, pe_routed = 0; // bn_partial_eval_counters
+	uint64_t uf_calls = 0, uf_launches = 0, uf_cols = 0; // bn_univariate_fold_batch (bn_univariate_fold_counters)
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	int n_cu = 256;
@@ -821,6 +822,30 @@ constexpr uint32_t kPeLogVecChunk = 10; // entries of `vec` a workgroup stages i
 // n_groups == 1 && d_groups == nullptr: the group and its single column travel as kernel arguments (no table upload)
 hipError_t launch_partial_eval(hipStream_t s, const pe_group *d_groups, uint32_t n_groups, const pe_col *d_cols, uint32_t n_cols, pe_group one_group,
                                pe_col one_col, const void *vec, uint32_t total_units, bool bits_only);
+
+// ---- kernels_univariate_fold.hip: the fold of the univariate round of the univariate-skip zerocheck for a batch of columns
+// (fold_univariate_round, core/src/protocols/sumcheck/prove/zerocheck.rs:384-434): out_c[x] = sum_{u < 2^k} coeffs[u] * M_c(u + 2^k x).
+// A job is one column; a row is the 2^k values of one output: 2^log_row_bits bits, log_row_bits = k + tower level.  A unit is a run
+// of 256 * uf_rows_per_thread(log_row_bits) outputs of one job.  The jobs are sorted by level, every workgroup takes a contiguous
+// range of the launch's units and keeps the nibble tables of the level it is working on in LDS.
+struct uf_job {
+	const void *col;  // the packed subfield column
+	uint4 *out;
+	uint64_t out_len; // 2^(n_vars - k)
+	uint32_t level;   // tower level 0 or 3
+	uint32_t start;   // first unit of this job in the launch
+};
+constexpr uint32_t kUfPassTables = 256; // nibble tables (256 B each) of one pass: 64 KiB of LDS
+constexpr uint32_t uf_rows_per_thread(uint32_t log_row_bits) { return log_row_bits >= 9 ? 2 : 8; }
+// nibble tables the level needs in LDS at skip_rounds = k (level 3 at k = 8: two passes of kUfPassTables)
+constexpr uint32_t uf_tables(uint32_t level, uint32_t k)
+{
+	const uint32_t t = level == 0 ? (k >= 2 ? 1u << (k - 2) : 1u) : 2u << k;
+	return t < kUfPassTables ? t : kUfPassTables;
+}
+// d_coeffs: the 2^k coefficients; lds_tables: the largest uf_tables() over the levels of the call
+hipError_t launch_univariate_fold(hipStream_t s, const uf_job *d_jobs, uint32_t n_jobs, const void *d_coeffs, uint32_t k, uint32_t total_units,
+                                  uint32_t n_wgs, uint32_t lds_tables);
 
 // ---- kernels_ntt_tiled.hip
 hipError_t launch_build_mul8(hipStream_t s, uint8_t *d_tab);

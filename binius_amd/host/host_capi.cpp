@@ -32,6 +32,7 @@
 #include "gkr_gpa.hpp"
 #include "piop.hpp"
 #include "sumcheck.hpp"
+#include "zerocheck.hpp"
 
 using namespace binius_amd;
 
@@ -1224,6 +1225,107 @@ int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_
 		size_t fe = 0;
 		for (const auto &evals : out.multilinear_evals)
 			for (const B128 &v : evals) final_evals_out[fe++] = v.raw();
+		return 0;
+	} catch (const Error &e) {
+		g_err = e.what();
+		return (int)e.kind();
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return BN_ERR_CORE_LIB;
+	}
+}
+
+// batch_zerocheck::batch_prove (crates/core/src/protocols/sumcheck/prove/batch_zerocheck.rs:166-293) through the C++ mirror
+// binius_amd/host/zerocheck.hpp; the arguments are described in include/binius_amd_host.h.
+uint64_t bnh_zerocheck_batch_scratch_elems(uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols)
+{
+	std::vector<size_t> nv, nc;
+	for (uint32_t p = 0; p < n_tables; p++) {
+		if (n_vars[p] > BN_PE_MAX_VARS + 8) return 0;
+		nv.push_back(n_vars[p]);
+		nc.push_back(n_cols[p]);
+	}
+	return zerocheck_batch_scratch_elems(nv, nc, skip_rounds);
+}
+
+int bnh_zerocheck_batch_prove(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols, const void *const *d_cols,
+                              const uint32_t *tower_levels, const uint32_t *n_comps, const bn_step *steps, const uint32_t *n_steps, const bn_step *steps_inf,
+                              const uint32_t *n_steps_inf, const uint32_t *degrees, const bn_f128 *zerocheck_challenges, const bn_f128 *batch_coeffs,
+                              const bn_f128 *univariate_challenge, const bn_f128 *sumcheck_challenges, const bn_f128 *reduction_batch_coeff,
+                              const bn_f128 *reduction_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *message_out, bn_f128 *round_coeffs_out,
+                              bn_f128 *final_evals_out, bn_f128 *reduction_round_coeffs_out, bn_f128 *reduction_final_evals_out, bn_f128 *skipped_challenges_out,
+                              bn_f128 *unskipped_challenges_out, bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out)
+{
+	try {
+		if (!ctx || !n_tables || !n_vars || !n_cols || !n_comps || !batch_coeffs || !univariate_challenge || !reduction_batch_coeff || !reduction_challenges || !final_evals_out ||
+		    !reduction_round_coeffs_out || !reduction_final_evals_out || !skipped_challenges_out || !concat_multilinear_evals_out || (!d_scratch && scratch_elems))
+			throw Error(Error::InputValidation, "null argument");
+		if (skip_rounds < 1 || skip_rounds > 8) throw Error(Error::InputValidation, "zerocheck: skip_rounds out of range (1 .. 8)");
+		// (what the conversion below relies on is checked here; the mirror checks the rest before its first launch)
+		size_t max_n = 0, total_cols = 0, total_comps = 0;
+		for (uint32_t p = 0; p < n_tables; p++) {
+			if (n_vars[p] > BN_PE_MAX_VARS) throw Error(Error::InputValidation, "zerocheck: n_vars out of range");
+			if (p && n_vars[p] < n_vars[p - 1]) throw Error(Error::InputValidation, "ClaimsOutOfOrder: tables ascend by number of variables");
+			max_n = n_vars[p];
+			total_cols += n_cols[p];
+			total_comps += n_comps[p];
+		}
+		if (skip_rounds > max_n) throw Error(Error::InputValidation, "IncorrectSkippedRoundsCount: skip_rounds exceeds the largest n_vars");
+		if ((total_cols && (!d_cols || !tower_levels)) || (total_comps && (!steps || !n_steps || !steps_inf || !n_steps_inf || !degrees)))
+			throw Error(Error::InputValidation, "null argument");
+		const size_t rounds = max_n - skip_rounds;
+		if (rounds && (!zerocheck_challenges || !sumcheck_challenges || !round_coeffs_out || !unskipped_challenges_out)) throw Error(Error::InputValidation, "null argument");
+		ComputeLayer hal(ctx);
+		std::vector<ZerocheckTable> tables(n_tables);
+		size_t at_col = 0, at_comp = 0, at_step = 0, at_inf = 0;
+		for (uint32_t p = 0; p < n_tables; p++) {
+			ZerocheckTable &t = tables[p];
+			t.n_vars = n_vars[p];
+			for (uint32_t c = 0; c < n_cols[p]; c++, at_col++) t.columns.push_back(ZerocheckColumn{d_cols[at_col], tower_levels[at_col]});
+			for (uint32_t c = 0; c < n_comps[p]; c++, at_comp++) {
+				if (degrees[at_comp] < 1 || ((uint64_t)degrees[at_comp] << skip_rounds) > 256)
+					throw Error(Error::InputValidation, "zerocheck: a composition's degree d needs 1 <= d and d 2^k <= 256");
+				t.base_compositions.emplace_back(steps + at_step, steps + at_step + n_steps[at_comp]);
+				EqIndComposition ec;
+				ec.composition = hal.compile_expr(ArithCircuit::from_steps(t.base_compositions.back()));
+				ec.composition_at_infinity = hal.compile_expr(ArithCircuit::from_steps(std::vector<bn_step>(steps_inf + at_inf, steps_inf + at_inf + n_steps_inf[at_comp])));
+				ec.degree = degrees[at_comp];
+				t.compositions.push_back(ec);
+				at_step += n_steps[at_comp];
+				at_inf += n_steps_inf[at_comp];
+			}
+		}
+		auto vec = [](const bn_f128 *p, size_t n) {
+			std::vector<B128> v;
+			for (size_t i = 0; i < n; i++) v.emplace_back(p[i].lo, p[i].hi);
+			return v;
+		};
+		const ZerocheckBatchOutput out = zerocheck_batch_prove(hal, tables, skip_rounds, vec(zerocheck_challenges, rounds), vec(batch_coeffs, n_tables),
+		                                                       B128(univariate_challenge->lo, univariate_challenge->hi), vec(sumcheck_challenges, rounds),
+		                                                       B128(reduction_batch_coeff->lo, reduction_batch_coeff->hi), vec(reduction_challenges, skip_rounds),
+		                                                       FSliceMut{d_scratch, (size_t)scratch_elems});
+		auto put = [](bn_f128 *dst, const std::vector<B128> &v) {
+			for (size_t i = 0; i < v.size(); i++) dst[i] = v[i].raw();
+			return dst + v.size();
+		};
+		if (!out.message.empty()) {
+			if (!message_out) throw Error(Error::InputValidation, "null argument");
+			put(message_out, out.message);
+		}
+		bn_f128 *at = round_coeffs_out;
+		for (const auto &rc : out.round_coeffs) at = put(at, rc);
+		at = final_evals_out;
+		for (const auto &fe : out.final_evals) at = put(at, fe);
+		at = reduction_round_coeffs_out;
+		for (const auto &rc : out.reduction_round_coeffs) at = put(at, rc);
+		put(reduction_final_evals_out, out.reduction_final_evals);
+		put(skipped_challenges_out, out.skipped_challenges);
+		if (rounds) put(unskipped_challenges_out, out.unskipped_challenges);
+		put(concat_multilinear_evals_out, out.concat_multilinear_evals);
+		for (int i = 0; i < ZerocheckBatchOutput::NPhases; i++) {
+			if (phase_ms_out) phase_ms_out[i] = out.phase_ms[i];
+			if (phase_calls_out) phase_calls_out[i] = out.phase_calls[i];
+		}
 		return 0;
 	} catch (const Error &e) {
 		g_err = e.what();

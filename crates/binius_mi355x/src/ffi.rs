@@ -101,6 +101,11 @@ pub const BN_PE_COLS_FALLBACK: usize = 3;
 pub const BN_PE_MAX_SHARE: usize = 4;
 pub const BN_PE_FOLD_LEFT_ROUTED: usize = 5;
 pub const BN_PE_MAX_VARS: u32 = 40;
+pub const BN_UF_N: usize = 3;
+pub const BN_UF_CALLS: usize = 0;
+pub const BN_UF_LAUNCHES: usize = 1;
+pub const BN_UF_COLS: usize = 2;
+pub const BN_UNIVARIATE_FOLD_MAX_SKIP: u32 = 8;
 pub const BN_EXP_STATIC: u32 = 0;
 pub const BN_EXP_DYNAMIC: u32 = 1;
 pub const BN_EXP_MAX_VARS: u32 = 28;
@@ -295,6 +300,15 @@ unsafe extern "C" {
 		d_outs: *const *mut c_void,
 	) -> c_int;
 	pub fn bn_partial_eval_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_univariate_fold_batch(
+		ctx: *mut bn_ctx,
+		cols: *const c_void,
+		n_cols: u32,
+		skip_rounds: u32,
+		h_coeffs: *const bn_f128,
+		d_outs: *const *mut c_void,
+	) -> c_int;
+	pub fn bn_univariate_fold_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 
 	pub fn bn_log_chunks_range(maps: *const bn_memmap, n_maps: u32, start: *mut u32, end: *mut u32) -> c_int;
 	pub fn bn_pick_log_chunks(maps: *const bn_memmap, n_maps: u32, log_chunks: *mut u32) -> c_int;

@@ -246,6 +246,28 @@ int bn_partial_eval_high_batch(bn_ctx *ctx, const void *cols, uint32_t n_cols, c
  * call counts nowhere. */
 enum { BN_PE_CALLS = 0, BN_PE_LAUNCHES = 1, BN_PE_COLS_KERNEL = 2, BN_PE_COLS_FALLBACK = 3, BN_PE_MAX_SHARE = 4, BN_PE_FOLD_LEFT_ROUTED = 5, BN_PE_N = 6 };
 int bn_partial_eval_counters(bn_ctx *ctx, uint64_t *counters /*[BN_PE_N]*/);
+/* The fold of the univariate round of the univariate-skip zerocheck, for every column of a call: ZerocheckProverImpl::
+ * fold_univariate_round (core/src/protocols/sumcheck/prove/zerocheck.rs:384-434), which is evaluate_partial_low (math/src/
+ * multilinear_extension.rs:302-341) at a query whose expansion is overwritten with the Lagrange coefficients of the univariate
+ * challenge (prove/univariate.rs:139-193).  k = skip_rounds, 1 <= k <= 8; h_coeffs: the 2^k coefficients in B128, on the HOST, shared by
+ * all columns.  Column c (cols[c], the layout of bn_pe_column) is TRANSPARENT with n_vars in k .. BN_PE_MAX_VARS variables at tower
+ * level 0 (B1) or 3 (B8) -- the levels bn_zerocheck_univariate_evals accepts --, packed into F as bn_hal_multilinear says (a column of
+ * n_vars + tower_level < 7 occupies the low bits of one 16-byte element); sizes and levels may differ inside a call.  d_outs[c]
+ * receives exactly what
+ *   bn_fold_right(d_evals, 2^(n_vars - 7 + tower_level), tower_level, coeffs, 2^k, d_outs[c], 2^(n_vars - k))
+ * writes with the coefficients on the device (a column of at least one element): out[x] = sum_{u < 2^k} coeffs[u] * column[u + 2^k x], bit-exact, overwritten not
+ * accumulated, nothing written beyond 2^(n_vars - k) elements.  cols and d_outs are HOST arrays; pointers are 16-byte aligned; inputs
+ * are only read; an output must not overlap its column.  Another level, k = 0, k > 8, k > n_vars, a misaligned or null pointer and an
+ * overlapping output are BN_ERR_INPUT_VALIDATION with nothing launched; n_cols = 0 is a no-op.  The whole call is ONE launch whatever
+ * the number of columns, their sizes and levels: the nibble tables of the coefficients are built once per workgroup and serve every
+ * column.  Returns when the outputs are complete. */
+#define BN_UNIVARIATE_FOLD_MAX_SKIP 8
+int bn_univariate_fold_batch(bn_ctx *ctx, const void *cols, uint32_t n_cols, uint32_t skip_rounds, const bn_f128 *h_coeffs,
+                             void *const *d_outs);
+/* Read-only, per context (not part of the reference interface): accepted bn_univariate_fold_batch calls, the kernel launches they
+ * made, the columns they served.  A rejected call counts nowhere. */
+enum { BN_UF_CALLS = 0, BN_UF_LAUNCHES = 1, BN_UF_COLS = 2, BN_UF_N = 3 };
+int bn_univariate_fold_counters(bn_ctx *ctx, uint64_t *counters /*[BN_UF_N]*/);
 
 /* ---- accumulate_kernels / map_kernels (layer.rs:183, 236) + KernelExecutor (layer.rs:518-590).
  * The kernel-spec closure cannot cross an FFI: the host shim runs it ONCE against a recording

@@ -136,6 +136,45 @@ int bnh_eqind_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void 
                              const bn_f128 *eq_ind_challenges, void *d_eq_ind, uint64_t eq_ind_elems, const bn_f128 *batch_coeff, const bn_f128 *challenges,
                              bn_f128 *round_coeffs_out, bn_f128 *final_evals_out);
 
+/* The batched univariate-skip zerocheck prover, sumcheck::prove::batch_zerocheck::batch_prove (crates/core/src/protocols/sumcheck/prove/
+ * batch_zerocheck.rs:166-293) over ZerocheckProverImpl (prove/zerocheck.rs:121-516), for the domain field B8 (the 0..=3 arm of core/src/
+ * constraint_system/prove.rs:484), through the C++ mirror binius_amd/host/zerocheck.hpp.  The transcript's samples are handed in.
+ *   n_tables provers (tables) in ascending n_vars[p]; k = skip_rounds, 1 <= k <= 8, k <= the largest n_vars (= max_n)
+ *   d_cols / tower_levels: the tables' columns, concatenated, n_cols[p] each: device, TRANSPARENT (packed as bn_hal_multilinear says), level 0
+ *     or 3; only read.  A table of n_vars < k is padded high by repetition to k variables on the host (prove/zerocheck.rs:79-119)
+ *   steps / steps_inf / n_steps / n_steps_inf / degrees: the tables' compositions, concatenated, n_comps[p] each, as bnh_eqind_sumcheck_prove
+ *     takes them.  The constants lie in B8: the same steps are the B8 form of the univariate round and the B128 form of the multilinear
+ *     rounds.  1 <= degree and degree 2^k <= 256
+ *   zerocheck_challenges[max_n - k] (table p takes the suffix of length max(n_p, k) - k, constraint_system/prove.rs:470), batch_coeffs[n_tables]
+ *     (pre-sampled, batch_zerocheck.rs:198-206; front_loaded::BatchProver::new_prebatched), univariate_challenge, sumcheck_challenges[max_n - k],
+ *     reduction_batch_coeff, reduction_challenges[k]
+ *   d_scratch: at least bnh_zerocheck_batch_scratch_elems(n_tables, k, n_vars, n_cols) elements of device memory
+ * Steps: per table one bn_zerocheck_univariate_evals; the Lagrange coefficients and the claimed sums on the host (prove/univariate.rs:139-193);
+ * ONE bn_univariate_fold_batch over the columns of all tables; one EqIndSumcheckProver per table over max(n, k) - k variables, all started in
+ * round 0 (a table without remaining rounds finishes at once); ONE bn_partial_eval_high_batch per table for project_to_skipped_variables
+ * (prove/zerocheck.rs:472-516); the univariatizing reduction (batch_zerocheck.rs:115-154) as host arithmetic.
+ * Outputs, in the transcript's writing order:
+ *   message_out[D - 2^k], D = (largest degree of the batch) 2^k: the univariate round's message (may be NULL when D = 2^k)
+ *   round_coeffs_out[(max_n - k) (Dmax + 2)], Dmax = max(2, largest degree of the batch): the round polynomials of the multilinear rounds with
+ *     ALL their coefficients (the transcript carries the truncated form), padded to the widest degree of the batch as
+ *     bnh_eqind_sumcheck_prove pads
+ *   final_evals_out[sum (n_cols[p] + 1)]: per table in finishing (= input) order its columns' evaluations, then the indicator's
+ *   reduction_round_coeffs_out[3 k], reduction_final_evals_out[sum n_cols + 1]: every column's evaluation, then the Lagrange multilinear's
+ *   skipped_challenges_out[k], unskipped_challenges_out[max_n - k], concat_multilinear_evals_out[sum n_cols]: BatchZerocheckOutput
+ *     (zerocheck.rs:140-150), what the evalcheck phase starts from
+ *   phase_ms_out[5] / phase_calls_out[5] (or NULL): wall time and device-op calls of the univariate round, the fold, the multilinear rounds
+ *     (time only), the projection, the reduction (host only)
+ * Claims out of order, k > max_n, a level other than 0 or 3, a degree out of range and a short scratch are BN_ERR_INPUT_VALIDATION before
+ * anything is launched. */
+uint64_t bnh_zerocheck_batch_scratch_elems(uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols);
+int bnh_zerocheck_batch_prove(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols, const void *const *d_cols,
+                              const uint32_t *tower_levels, const uint32_t *n_comps, const bn_step *steps, const uint32_t *n_steps, const bn_step *steps_inf,
+                              const uint32_t *n_steps_inf, const uint32_t *degrees, const bn_f128 *zerocheck_challenges, const bn_f128 *batch_coeffs,
+                              const bn_f128 *univariate_challenge, const bn_f128 *sumcheck_challenges, const bn_f128 *reduction_batch_coeff,
+                              const bn_f128 *reduction_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *message_out, bn_f128 *round_coeffs_out,
+                              bn_f128 *final_evals_out, bn_f128 *reduction_round_coeffs_out, bn_f128 *reduction_final_evals_out, bn_f128 *skipped_challenges_out,
+                              bn_f128 *unskipped_challenges_out, bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out);
+
 /* gkr_gpa::batch_prove (crates/core/src/protocols/gkr_gpa/prove.rs:33-296) through the C++ mirror binius_amd/host/gkr_gpa.hpp: the GKR
  * grand-product argument over n_claims witnesses, which the constraint system runs for every flush and non-zero oracle
  * (core/src/constraint_system/prove.rs:285-412), High-to-Low.  The witnesses' layers come from ONE bn_product_tree_layers; step
