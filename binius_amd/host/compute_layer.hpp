@@ -76,6 +76,20 @@ struct B128 {
 };
 static_assert(sizeof(B128) == 16, "B128 must be a plain u128");
 
+// B128 <-> bn_f128 at the C boundary: one value, and a span (a null span is empty; to_raw returns the end of what it wrote)
+inline B128 from_raw(const bn_f128 &x) { return B128(x.lo, x.hi); }
+inline std::vector<B128> from_raw(const bn_f128 *p, size_t n)
+{
+	std::vector<B128> v;
+	for (size_t i = 0; p && i < n; i++) v.push_back(from_raw(p[i]));
+	return v;
+}
+inline bn_f128 *to_raw(const std::vector<B128> &v, bn_f128 *dst)
+{
+	for (const B128 &x : v) *dst++ = x.raw();
+	return dst;
+}
+
 // ---------------------------------------------------------------------------------------- errors
 // binius_compute::Error (layer.rs:706-716) + alloc::Error::OutOfMemory (alloc.rs:110-113)
 class Error : public std::runtime_error {
@@ -109,6 +123,11 @@ struct AbiProf {
 		return p;
 	}
 };
+// wall-clock milliseconds from t0 to t1 (default: now)
+inline double elapsed_ms(std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1 = std::chrono::steady_clock::now())
+{
+	return std::chrono::duration<double, std::milli>(t1 - t0).count();
+}
 template <class F>
 inline int abi_timed(AbiProf::Kind k, F &&f)
 {
@@ -144,6 +163,9 @@ struct ComputeMemory {
 	static FSliceMut to_owned_mut(FSliceMut &d) { return d; }
 	static FSlice as_const(const FSliceMut &d) { return FSlice{d.ptr, d.len_}; }
 	static FSlice to_const(FSliceMut d) { return FSlice{d.ptr, d.len_}; }
+	// the writable handle of memory that was handed in read-only: for a prover that was given its multilinears as FSlice and
+	// folds them in place, or that marks them pre-fold and never writes them
+	static FSliceMut to_mut(FSlice d) { return FSliceMut{const_cast<void *>(d.ptr), d.len_}; }
 	static FSlice slice(FSlice d, size_t start, size_t end)
 	{
 		if (start > end || end > d.len_) throw std::out_of_range("slice range out of bounds");
@@ -371,7 +393,7 @@ struct KernelMemMap {
 	size_t log_size = 0; // Local
 	static KernelMemMap chunked(FSlice d, size_t log_min_chunk_size)
 	{
-		return KernelMemMap{Chunked, FSliceMut{const_cast<void *>(d.ptr), d.len_}, log_min_chunk_size, 0};
+		return KernelMemMap{Chunked, ComputeMemory::to_mut(d), log_min_chunk_size, 0};
 	}
 	static KernelMemMap chunked_mut(FSliceMut d, size_t log_min_chunk_size) { return KernelMemMap{ChunkedMut, d, log_min_chunk_size, 0}; }
 	static KernelMemMap local(size_t log_size) { return KernelMemMap{Local, FSliceMut{}, 0, log_size}; }

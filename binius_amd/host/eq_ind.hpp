@@ -16,8 +16,13 @@
 //                                              the indicator's partial evaluations (prove/common.rs:13-75: upper half onto lower)
 //   finish()               eq_ind.rs:639-643   the multilinears' evaluations, then the prefix
 //
+// EqIndPointProver is how the protocols start one: folded multilinears and a point, zero variables included.
+//
 // Protocol bookkeeping only: every hypercube-sized operation is a call of the backend.
 #pragma once
+#include <algorithm>
+#include <memory>
+
 #include "hal_backend.hpp"
 #include "sumcheck.hpp"
 
@@ -207,6 +212,55 @@ private:
 	FSliceMut eq_ind_;
 	B128 eq_ind_prefix_eval_ = B128::ONE();
 	bool have_coeffs_ = false;
+};
+
+// An EqIndSumcheckProver over folded multilinears at `point` (n_vars coordinates), as the GKR arguments, the flush reduction and
+// the zerocheck start it: the indicator's table is the expansion of all coordinates but the last (eq_ind_expand, High-to-Low,
+// eq_ind.rs:430-446), allocated from `alloc`; the multilinears are folded in place.
+// Zero variables are a case of their own, which EqIndSumcheckProver does not learn: there are no rounds, finish() returns the first
+// `per` elements of every slice (ONE gather, offsets from the lowest address) and ONE for the indicator's prefix.
+class EqIndPointProver {
+public:
+	EqIndPointProver(ComputeLayer &hal, Mi355xBackend &backend, DeviceBumpAllocator &alloc, size_t n_vars, std::vector<FSlice> slices,
+	                 std::vector<EqIndComposition> compositions, std::vector<B128> sums, const std::vector<B128> &point, size_t per = 1)
+	    : hal_(hal), n_vars_(n_vars), slices_(std::move(slices)), per_(per)
+	{
+		if (n_vars == 0) return;
+		const FSlice table = backend.tensor_product_full_query(std::vector<B128>(point.begin(), point.end() - 1), alloc);
+		std::vector<SumcheckMultilinear> mls;
+		for (const FSlice &s : slices_) mls.push_back(SumcheckMultilinear::folded(s));
+		prover_ = std::make_unique<EqIndSumcheckProver>(hal, backend, alloc, n_vars, std::move(mls), std::move(compositions), std::move(sums), point,
+		                                                ComputeMemory::to_mut(table));
+	}
+	size_t n_vars() const { return n_vars_; }
+	std::vector<B128> execute(B128 batch_coeff) { return rounds().execute(batch_coeff); }
+	void fold(B128 challenge) { rounds().fold(challenge); }
+	std::vector<B128> finish()
+	{
+		if (prover_) return prover_->finish();
+		std::vector<B128> evals(per_ * slices_.size());
+		if (!slices_.empty()) {
+			const char *base = (const char *)slices_[0].ptr;
+			for (const FSlice &s : slices_) base = std::min(base, (const char *)s.ptr);
+			std::vector<uint64_t> offs;
+			for (const FSlice &s : slices_) offs.push_back((uint64_t)((const char *)s.ptr - base) / sizeof(B128));
+			check(bn_gather_d2h(hal_.raw_ctx(), base, offs.data(), offs.size(), per_, reinterpret_cast<bn_f128 *>(evals.data())));
+		}
+		evals.push_back(B128::ONE());
+		return evals;
+	}
+
+private:
+	EqIndSumcheckProver &rounds()
+	{
+		if (!prover_) throw SumcheckError("ExpectedFinish");
+		return *prover_;
+	}
+	ComputeLayer &hal_;
+	size_t n_vars_;
+	std::vector<FSlice> slices_;
+	size_t per_;
+	std::unique_ptr<EqIndSumcheckProver> prover_;
 };
 
 } // namespace binius_amd

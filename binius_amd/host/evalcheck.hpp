@@ -9,7 +9,7 @@
 //                                                                                 per distinct suffix
 //   ShiftIndPartialEval::multilinear_extension           transparent/shift_ind.rs:117-161, 276-366   host table of 2^b elements
 //   TowerBasis::multilinear_extension                    transparent/tower_basis.rs:54-70            host table of 2^k elements
-//   RegularSumcheckProver per constraint set + batch_prove   -> BivariateSumcheckProver + SumcheckBatchProver (sumcheck.hpp, piop.hpp):
+//   RegularSumcheckProver per constraint set + batch_prove   -> BivariateSumcheckProver + SumcheckBatchProver (sumcheck.hpp, batch_prover.hpp):
 //     both batch a prover's claims by powers of the batch coefficient (prover_state.rs:302) and the round polynomial is unique,
 //     so the transcript is the same.  At 2^b <= 2^12 elements the backend's host tail finishes these provers.
 //
@@ -26,7 +26,7 @@
 #include <map>
 #include <memory>
 
-#include "piop.hpp"
+#include "batch_prover.hpp"
 
 namespace binius_amd {
 
@@ -84,22 +84,6 @@ inline size_t evalcheck_scratch_elems(const std::vector<EvalcheckProver> &prover
 	return total;
 }
 
-// eq(r)[y] = prod_k (y_k ? r_k : 1 + r_k), bit k of y with r[k]
-inline std::vector<B128> evalcheck_eq_expand(const B128 *r, size_t b)
-{
-	std::vector<B128> eq{B128::ONE()};
-	for (size_t k = 0; k < b; k++) {
-		const size_t n = eq.size();
-		eq.resize(2 * n);
-		for (size_t y = 0; y < n; y++) {
-			const B128 hi = eq[y] * r[k];
-			eq[n + y] = hi;
-			eq[y] = eq[y] + hi;
-		}
-	}
-	return eq;
-}
-
 // ShiftIndPartialEval::multilinear_extension (shift_ind.rs:117-161, 332-366): table[x] = sum_y f(x, y) eq(y, r) with f(x, y) = 1 where
 // y is the position x is shifted to -- table[x] = eq(r)[y(x)], zero where the shift leaves the block
 inline std::vector<B128> evalcheck_shift_ind_table(size_t b, size_t offset, ShiftVariant variant, const B128 *r)
@@ -108,7 +92,7 @@ inline std::vector<B128> evalcheck_shift_ind_table(size_t b, size_t offset, Shif
 	if (b == 0 || b >= 32) throw Error(Error::InputValidation, "shift indicator: block_size out of range");
 	const size_t n = (size_t)1 << b;
 	if (offset == 0 || offset >= n) throw Error(Error::InputValidation, "shift indicator: shift_offset must be in 1 .. 2^block_size - 1");
-	const std::vector<B128> eq = evalcheck_eq_expand(r, b);
+	const std::vector<B128> eq = eq_expand(r, b);
 	std::vector<B128> table(n, B128::ZERO());
 	for (size_t x = 0; x < n; x++) {
 		switch (variant) {
@@ -124,15 +108,12 @@ inline std::vector<B128> evalcheck_shift_ind_table(size_t b, size_t offset, Shif
 	return table;
 }
 
-struct EvalcheckOutput {
-	std::vector<std::vector<B128>> round_proofs;      // per round the truncated coefficients
-	std::vector<std::vector<B128>> multilinear_evals; // per prover, finishing (= input) order
-};
+// per round the truncated coefficients; per prover, in finishing (= input) order, its final evaluations
+using EvalcheckOutput = BatchSumcheckOutput;
 
 inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::vector<EvalcheckProver> &provers, const std::vector<B128> &pool, FSliceMut scratch,
                                                  const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges)
 {
-	EvalcheckOutput out;
 	if (batch_coeffs.size() != provers.size()) throw Error(Error::InputValidation, "IncorrectNumberOfBatchCoeffs");
 	size_t total_m = 0;
 	for (size_t i = 0; i < provers.size(); i++) {
@@ -161,7 +142,7 @@ inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::v
 		}
 		total_m += p.multilins.size();
 	}
-	if (provers.empty()) return out;
+	if (provers.empty()) return {};
 	if (challenges.size() < provers.back().n_vars) throw Error(Error::InputValidation, "too few challenges");
 	if (scratch.len_ < evalcheck_scratch_elems(provers)) throw Error(Error::InputValidation, "scratch holds fewer than evalcheck_scratch_elems elements");
 	DeviceBumpAllocator alloc(scratch);
@@ -180,10 +161,7 @@ inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::v
 			const EvalcheckSuffix s{m.suffix_off, m.suffix_len};
 			auto job = jobs.find(s);
 			if (job == jobs.end()) {
-				FSliceMut q = alloc.alloc((size_t)1 << m.suffix_len);
-				FSliceMut first{q.ptr, 1};
-				hal.fill(first, B128::ONE());
-				check(bn_tensor_expand(hal.raw_ctx(), q.ptr, q.len_, 0, reinterpret_cast<const bn_f128 *>(pool.data() + m.suffix_off), m.suffix_len));
+				const FSliceMut q = ops::eq_ind_partial_eval(hal, alloc, std::vector<B128>(pool.begin() + m.suffix_off, pool.begin() + m.suffix_off + m.suffix_len));
 				job = jobs.emplace(s, SuffixJob{ComputeMemory::as_const(q), {}, {}}).first;
 			}
 			const auto key = evalcheck_projection_key(m);
@@ -226,21 +204,7 @@ inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::v
 			if (c.indices[0] >= p.multilins.size() || c.indices[1] >= p.multilins.size()) throw Error(Error::InputValidation, "a claim's index leaves its prover's multilinears");
 		sc.push_back(std::make_unique<BivariateSumcheckProver>(hal, alloc, host_alloc, p.n_vars, p.compositions, p.sums, mls));
 	}
-	SumcheckBatchProver batch(std::move(sc), batch_coeffs);
-	const size_t rounds = batch.total_rounds();
-	PiopTranscript tr;
-	for (size_t r = 0; r < rounds; r++) {
-		batch.send_round_proof(tr);
-		batch.receive_challenge(challenges[r]);
-	}
-	batch.finish(tr);
-	for (const auto &it : tr.items) {
-		if (it.kind == PiopTranscript::Item::RoundProof)
-			out.round_proofs.push_back(it.scalars);
-		else if (it.kind == PiopTranscript::Item::MultilinearEvals)
-			out.multilinear_evals.push_back(it.scalars);
-	}
-	return out;
+	return SumcheckBatchProver<BivariateSumcheckProver>(std::move(sc), batch_coeffs).run(challenges.data());
 }
 
 } // namespace binius_amd

@@ -16,9 +16,9 @@
 //                                                             point in order of first appearance (:1045-1073)
 //   ConstraintSetBuilder::build_one     constraint.rs:114-129 (oracle) per group the multilinears are the sorted, de-duplicated union
 //                                                             of the oracle ids, the compositions' variables remapped to it
-//   prove_mlecheck_with_switchover      evalcheck/subclaims.rs:589-633   one EqIndSumcheckProver (eq_ind.hpp) at the claims' point as a
-//                                                             front-loaded batch of one (truncated round polynomials, as in
-//                                                             gkr_gpa.hpp); challenges reversed; the indicator's evaluation is
+//   prove_mlecheck_with_switchover      evalcheck/subclaims.rs:589-633   one EqIndPointProver (eq_ind.hpp) at the claims' point as a
+//                                                             front-loaded batch of one (batch_prover.hpp: truncated round
+//                                                             polynomials, as in gkr_gpa.hpp); challenges reversed; the indicator's evaluation is
 //                                                             written with the others and dropped from the claims (:619-630)
 //
 // The order the reference fixes -- the non-zero products and their zero check come before the flushes -- is kept: the non-zero
@@ -175,11 +175,6 @@ inline void widen(ComputeLayer &hal, const std::vector<Widen> &cols, const std::
 	}
 }
 
-inline double ms_since(std::chrono::steady_clock::time_point t0)
-{
-	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 } // namespace flush_detail
 
 // gpa_*: the samples gkr_gpa_batch_prove takes, sized by the largest n_vars over flushes and non-zero oracles.
@@ -281,7 +276,7 @@ inline FlushProdcheckOutput flush_prodcheck_prove(ComputeLayer &hal, Mi355xBacke
 		check(bn_flush_witness_batch(hal.raw_ctx(), (uint32_t)nf, n32.data(), ns.data(), sels.data(), nc.data(), cols.data(), levels.data(), cf.data(), ct.data(),
 		                             outs.data(), out.prefix_lens.data()));
 	}
-	out.phase_ms[0] = ms_since(t_begin);
+	out.phase_ms[0] = elapsed_ms(t_begin);
 
 	// ---- the grand-product argument over chain(flush witnesses with their prefix lengths, non-zero witnesses)
 	const auto t_gpa = std::chrono::steady_clock::now();
@@ -291,7 +286,7 @@ inline FlushProdcheckOutput flush_prodcheck_prove(ComputeLayer &hal, Mi355xBacke
 		const size_t gpa_need = gkr_gpa_scratch_elems(nv);
 		out.gpa = gkr_gpa_batch_prove(hal, backend, nv, ins, arenas, alloc.alloc(gpa_need), gpa_batch_coeffs, gpa_sumcheck_challenges, gpa_challenges);
 	}
-	out.phase_ms[1] = ms_since(t_gpa);
+	out.phase_ms[1] = elapsed_ms(t_gpa);
 
 	// ---- reduce_flush_evalcheck_claims
 	const auto t_red = std::chrono::steady_clock::now();
@@ -352,38 +347,17 @@ inline FlushProdcheckOutput flush_prodcheck_prove(ComputeLayer &hal, Mi355xBacke
 			comps.push_back(ec);
 			sums.push_back(out.gpa.final_evals[f]);
 		}
-		const B128 batch_coeff = red_batch_coeffs[g];
-		if (n == 0) {
-			// zero variables: no rounds; the single elements of the multilinears, the indicator's prefix is ONE
-			const char *base = (const char *)mls[0].ptr;
-			for (const FSlice &x : mls) base = std::min(base, (const char *)x.ptr);
-			std::vector<uint64_t> offs;
-			for (const FSlice &x : mls) offs.push_back((uint64_t)((const char *)x.ptr - base) / sizeof(B128));
-			chk.final_evals.resize(m);
-			check(bn_gather_d2h(hal.raw_ctx(), base, offs.data(), offs.size(), 1, reinterpret_cast<bn_f128 *>(chk.final_evals.data())));
-			chk.final_evals.push_back(B128::ONE());
-		} else {
-			const FSlice table = backend.tensor_product_full_query(std::vector<B128>(point.begin(), point.end() - 1), ra);
-			std::vector<SumcheckMultilinear> sm;
-			for (const FSlice &x : mls) sm.push_back(SumcheckMultilinear::folded(x));
-			EqIndSumcheckProver prover(hal, backend, ra, n, std::move(sm), std::move(comps), std::move(sums), point, FSliceMut{const_cast<void *>(table.ptr), table.len_});
-			for (size_t r = 0; r < n; r++) {
-				const std::vector<B128> rc = prover.execute(batch_coeff);
-				std::vector<B128> proof;
-				for (size_t i = 0; i + 1 < rc.size(); i++) proof.push_back(rc[i] * batch_coeff); // (front_loaded.rs:131-136, RoundCoeffs::truncate)
-				chk.round_proofs.push_back(std::move(proof));
-				const B128 z = red_challenges[ch_at + r];
-				chk.point.push_back(z);
-				prover.fold(z);
-			}
-			chk.final_evals = prover.finish();
-			std::reverse(chk.point.begin(), chk.point.end()); // (subclaims.rs:623-624)
-		}
+		// a front-loaded batch of one; at n = 0 there are no rounds (EqIndPointProver's zero-variable case)
+		BatchSumcheckOutput res =
+		    prove_batch_of_one(std::make_unique<EqIndPointProver>(hal, backend, ra, n, mls, std::move(comps), std::move(sums), point), red_batch_coeffs[g], red_challenges.data() + ch_at);
+		chk.round_proofs = std::move(res.round_proofs);
+		chk.final_evals = std::move(res.multilinear_evals[0]);
+		chk.point.assign(red_challenges.rend() - (ch_at + n), red_challenges.rend() - ch_at); // reversed (subclaims.rs:623-624)
 		ch_at += n;
 		out.checks.push_back(std::move(chk));
 	}
-	out.phase_ms[2] = ms_since(t_red);
-	out.phase_ms[3] = ms_since(t_begin);
+	out.phase_ms[2] = elapsed_ms(t_red);
+	out.phase_ms[3] = elapsed_ms(t_begin);
 	return out;
 }
 

@@ -5,14 +5,15 @@
 //   BaseExpWitness::new_with_*_base        witness.rs:31-110, 139-156, 258-284   ONE call of bn_exp_circuit_layers for all witnesses
 //   claims sorted by n_vars, descending    batch_prove.rs:73-76                  else ClaimsOutOfOrder; :63-65 MismatchedWitnessClaimLength
 //   build_layer_gkr_sumcheck_provers       batch_prove.rs:123-196                consecutive provers with equal evaluation points form a
-//                                                                                group: ONE EqIndSumcheckProver (eq_ind.hpp; the
+//                                                                                group: ONE EqIndPointProver (eq_ind.hpp; the
 //                                                                                reference builds it from the same, common.rs:110-113) over
 //                                                                                the concatenated multilinears, one composition per prover
 //   layer_composite_sum_claim              provers.rs:117-165, 256-312           static, not last:  [V_{w-2-L}, e_{w-1-L}]      x0 ((1 - x1) + x1 c), c = g^(2^(w-1-L))
 //     compositions.rs:43-61                                                      static, last:      nothing (no claim, no multilinears)
 //                                                                                dynamic, not last: [V_{w-2-L}, e_L, base]      x0^2 ((1 - x1) + x1 x2), degree 4
 //                                                                                dynamic, last:     [base, e_{w-1}]             (1 - x1) + x1 x0
-//   sumcheck::batch_prove                  prove/batch_sumcheck.rs:102-199       provers by n_vars descending; a prover's batch coefficient is
+//   sumcheck::batch_prove                  prove/batch_sumcheck.rs:102-199       SumcheckBatchProver, JoinBySize (batch_prover.hpp):
+//                                                                                provers by n_vars descending; a prover's batch coefficient is
 //                                                                                taken when the round with its n_vars begins; round proof =
 //                                                                                sum of coefficient x its round coefficients, padded to the
 //                                                                                longest, last coefficient dropped; finish() of every prover
@@ -24,7 +25,7 @@
 //   provers.retain                         batch_prove.rs:112
 //
 // A group of zero variables has no rounds: its "final evaluations" are the single elements of its multilinears and the indicator's
-// prefix is ONE; it is handled here (one gather), EqIndSumcheckProver does not learn n_vars = 0 (as in gkr_gpa.hpp).
+// prefix is ONE (EqIndPointProver's zero-variable case).
 // Memory: the sumcheck folds in place and a layer V_k is a multilinear of exactly one sumcheck, so the arenas are CONSUMED.  Before a
 // layer's sumcheck its bit columns are expanded into the scratch as B128 multilinears (bn_bits_to_b128, one launch for all), and the
 // base column of every active dynamic prover is copied there: the caller owns it and every layer needs it again.  The scratch is
@@ -41,6 +42,7 @@
 #include <chrono>
 #include <memory>
 
+#include "batch_prover.hpp"
 #include "eq_ind.hpp"
 
 namespace binius_amd {
@@ -161,37 +163,31 @@ inline GkrExpOutput gkr_exp_batch_prove(ComputeLayer &hal, Mi355xBackend &backen
 			check(bn_bits_to_b128(hal.raw_ctx(), (uint32_t)ll.size(), ll.data(), srcs.data(), dsts.data()));
 		}
 		// ---- groups of consecutive provers with equal points; one sumcheck prover per group that has a claim
-		struct Group {
-			size_t n_vars = 0;
-			std::vector<FSlice> mls;
-			std::unique_ptr<EqIndSumcheckProver> prover; // n_vars >= 1
-		};
-		std::vector<Group> groups;
+		std::vector<std::unique_ptr<EqIndPointProver>> groups;
 		for (size_t i0 = 0; i0 < provers.size();) {
 			size_t i1 = i0 + 1;
 			while (i1 < provers.size() && provers[i1].point == provers[i0].point) i1++;
-			Group g;
-			g.n_vars = provers[i0].point.size();
+			std::vector<FSlice> mls;
 			std::vector<EqIndComposition> comps;
 			std::vector<B128> sums;
 			for (size_t i = i0; i < i1; i++) {
 				const Prover &p = provers[i];
 				const GkrExpClaim &c = claims[p.t];
-				const size_t rows = (size_t)1 << c.n_vars, at = g.mls.size();
+				const size_t rows = (size_t)1 << c.n_vars, at = mls.size();
 				if (n_mls(p, L) == 0) continue;
 				const ArithCircuit x0 = ArithCircuit::var(at), x1 = ArithCircuit::var(at + 1), x2 = ArithCircuit::var(at + 2);
 				EqIndComposition ec;
 				if (is_last(p, L)) { // (dynamic)
-					g.mls.push_back(base_ml[i]);
-					g.mls.push_back(bit_ml[i]);
+					mls.push_back(base_ml[i]);
+					mls.push_back(bit_ml[i]);
 					ec.composition = hal.compile_expr((one + x1) + x1 * x0);
 					ec.composition_at_infinity = hal.compile_expr(x1 * x0);
 					ec.degree = 2;
 				} else {
-					g.mls.push_back(FSlice{(const char *)c.arena.ptr + (c.width - 2 - L) * rows * sizeof(B128), rows});
-					g.mls.push_back(bit_ml[i]);
+					mls.push_back(FSlice{(const char *)c.arena.ptr + (c.width - 2 - L) * rows * sizeof(B128), rows});
+					mls.push_back(bit_ml[i]);
 					if (c.dynamic) {
-						g.mls.push_back(base_ml[i]);
+						mls.push_back(base_ml[i]);
 						ec.composition = hal.compile_expr(x0.pow(2) * ((one + x1) + x1 * x2));
 						ec.composition_at_infinity = hal.compile_expr(x0.pow(2) * (x1 * x2));
 						ec.degree = 4;
@@ -206,56 +202,17 @@ inline GkrExpOutput gkr_exp_batch_prove(ComputeLayer &hal, Mi355xBackend &backen
 				comps.push_back(ec);
 				sums.push_back(p.eval);
 			}
-			if (!comps.empty()) {
-				if (g.n_vars >= 1) {
-					const std::vector<B128> &pt = provers[i0].point;
-					const FSlice table = backend.tensor_product_full_query(std::vector<B128>(pt.begin(), pt.end() - 1), alloc);
-					std::vector<SumcheckMultilinear> mls;
-					for (const FSlice &m : g.mls) mls.push_back(SumcheckMultilinear::folded(m));
-					g.prover = std::make_unique<EqIndSumcheckProver>(hal, backend, alloc, g.n_vars, std::move(mls), std::move(comps), std::move(sums), pt,
-					                                                 FSliceMut{const_cast<void *>(table.ptr), table.len_});
-				}
-				groups.push_back(std::move(g));
-			}
+			if (!comps.empty())
+				groups.push_back(std::make_unique<EqIndPointProver>(hal, backend, alloc, provers[i0].point.size(), std::move(mls), std::move(comps), std::move(sums), provers[i0].point));
 			i0 = i1;
 		}
-		// ---- sumcheck::batch_prove
-		const size_t n_rounds = groups.empty() ? 0 : groups[0].n_vars;
-		std::vector<std::vector<B128>> proofs;
-		std::vector<B128> r;
-		size_t active = 0;
-		for (size_t round = 0; round < n_rounds; round++) {
-			while (active < groups.size() && groups[active].n_vars == n_rounds - round) active++;
-			std::vector<B128> acc;
-			for (size_t g = 0; g < active; g++) {
-				const B128 coeff = batch_coeffs[L * k + g];
-				const std::vector<B128> rc = groups[g].prover->execute(coeff);
-				if (rc.size() > acc.size()) acc.resize(rc.size(), B128::ZERO());
-				for (size_t i = 0; i < rc.size(); i++) acc[i] = acc[i] + rc[i] * coeff;
-			}
-			acc.pop_back(); // (RoundCoeffs::truncate)
-			proofs.push_back(std::move(acc));
-			const B128 z = challenges[L * max_n + round];
-			r.push_back(z);
-			for (size_t g = 0; g < active; g++) groups[g].prover->fold(z);
-		}
-		std::reverse(r.begin(), r.end());
-		std::vector<std::vector<B128>> evals;
-		for (Group &g : groups) {
-			if (g.prover) {
-				evals.push_back(g.prover->finish());
-			} else {
-				// zero variables: the single elements of the multilinears, the indicator's prefix is ONE
-				const char *base = (const char *)g.mls[0].ptr;
-				for (const FSlice &m : g.mls) base = std::min(base, (const char *)m.ptr);
-				std::vector<uint64_t> offs;
-				for (const FSlice &m : g.mls) offs.push_back((uint64_t)((const char *)m.ptr - base) / sizeof(B128));
-				std::vector<B128> v(offs.size());
-				check(bn_gather_d2h(hal.raw_ctx(), base, offs.data(), offs.size(), 1, reinterpret_cast<bn_f128 *>(v.data())));
-				v.push_back(B128::ONE());
-				evals.push_back(std::move(v));
-			}
-		}
+		// ---- sumcheck::batch_prove: the groups descend by n_vars and join as the rounds reach their size
+		const size_t n_rounds = groups.empty() ? 0 : groups[0]->n_vars(), n_groups = groups.size();
+		BatchSumcheckOutput res = SumcheckBatchProver<EqIndPointProver>(std::move(groups), std::vector<B128>(batch_coeffs.begin() + L * k, batch_coeffs.begin() + L * k + n_groups),
+		                                                                BatchSchedule::JoinBySize)
+		                              .run(challenges.data() + L * max_n);
+		const std::vector<B128> r(challenges.rend() - (L * max_n + n_rounds), challenges.rend() - L * max_n); // reversed
+		const std::vector<std::vector<B128>> &evals = res.multilinear_evals;
 		// ---- build_layer_exponent_bit_claims
 		std::vector<B128> flat;
 		for (const auto &e : evals) flat.insert(flat.end(), e.begin(), e.end() - 1);
@@ -277,11 +234,11 @@ inline GkrExpOutput gkr_exp_batch_prove(ComputeLayer &hal, Mi355xBackend &backen
 			}
 			at += m;
 		}
-		out.round_proofs.push_back(std::move(proofs));
-		out.multilinear_evals.push_back(std::move(evals));
+		out.round_proofs.push_back(std::move(res.round_proofs));
+		out.multilinear_evals.push_back(std::move(res.multilinear_evals));
 		out.layer_claims.push_back(std::move(layer_claims));
 		provers.erase(std::remove_if(provers.begin(), provers.end(), [&](const Prover &p) { return is_last(p, L); }), provers.end());
-		out.layer_ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+		out.layer_ms.push_back(elapsed_ms(t_begin));
 	}
 	return out;
 }

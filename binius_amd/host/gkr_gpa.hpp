@@ -9,13 +9,13 @@
 //   stage_sumcheck_provers              prove.rs:208-280    one EqIndSumcheckProver (eq_ind.hpp) over j variables: multilinears
 //                                                           2i, 2i + 1 = the halves of state i's layer j + 1, claim var(2i) var(2i+1)
 //                                                           with sum = its layer_eval, eq_ind_challenges = the current point
-//   front_loaded::BatchProver of ONE    front_loaded.rs:122-198   round proof = the prover's coefficients times the batch coefficient,
-//                                                           last coefficient dropped (RoundCoeffs::truncate)
+//   front_loaded::BatchProver of ONE    front_loaded.rs:122-198   SumcheckBatchProver (batch_prover.hpp): round proof = the prover's
+//                                                           coefficients times the batch coefficient, last coefficient dropped
 //   challenges reversed, gpa_challenge  prove.rs:106-116    eval_point = reversed challenges || gpa_challenge
 //   update_layer_eval                   prove.rs:282-284    layer_eval = e0 + gpa_challenge (e1 - e0)
 //
-// Step 0 has zero variables: no rounds, the final evaluations are the two elements of layer 1 and the indicator's prefix is ONE;
-// it is handled here (one gather), EqIndSumcheckProver does not learn n_vars = 0.
+// Step 0 has zero variables: no rounds, the final evaluations are the two elements of layer 1 and the indicator's prefix is ONE
+// (EqIndPointProver's zero-variable case, two elements per layer).
 // The sumcheck folds in place, so the arenas are consumed.  A tree's last step runs over its INPUT layer, which the caller owns and
 // which may be truncated: every input is first copied into the scratch, padded with ONEs to 2^n_vars elements (bn_pad_with_ones, one
 // launch for all), and the copy is folded; the inputs are never written.  The sumcheck over a truncated input just sees the ONEs
@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <chrono>
 
+#include "batch_prover.hpp"
 #include "eq_ind.hpp"
 
 namespace binius_amd {
@@ -142,49 +143,34 @@ inline GkrGpaOutput gkr_gpa_batch_prove(ComputeLayer &hal, Mi355xBackend &backen
 			const size_t t = active[i];
 			layer[i] = j + 1 == n_vars[t] ? (const char *)padded[t].ptr : (const char *)arenas[t].ptr + (((size_t)1 << (j + 1)) * sizeof(B128));
 		}
-		std::vector<B128> finals, proofs, challenges;
-		if (j == 0) {
-			// zero variables: the "final evaluations" are the two elements of layer 1, the indicator's prefix is ONE
-			const char *base = *std::min_element(layer.begin(), layer.end());
-			std::vector<uint64_t> offs;
-			for (const char *p : layer) offs.push_back((uint64_t)(p - base) / sizeof(B128));
-			finals.resize(2 * active.size());
-			check(bn_gather_d2h(hal.raw_ctx(), base, offs.data(), offs.size(), 2, reinterpret_cast<bn_f128 *>(finals.data())));
-			finals.push_back(B128::ONE());
-		} else {
-			const size_t half = (size_t)1 << j;
-			std::vector<SumcheckMultilinear> mls;
-			std::vector<B128> sums;
-			for (size_t i = 0; i < active.size(); i++) {
-				mls.push_back(SumcheckMultilinear::folded(FSlice{layer[i], half}));
-				mls.push_back(SumcheckMultilinear::folded(FSlice{layer[i] + half * sizeof(B128), half}));
-				sums.push_back(layer_eval[active[i]]);
-			}
-			DeviceBumpAllocator eq_alloc(eq_scratch);
-			// eq_ind_expand, High-to-Low: the tensor expansion of all challenges but the last (eq_ind.rs:430-446)
-			const FSlice table = backend.tensor_product_full_query(std::vector<B128>(eval_point.begin(), eval_point.end() - 1), eq_alloc);
-			EqIndSumcheckProver prover(hal, backend, eq_alloc, j, std::move(mls), std::vector<EqIndComposition>(all_comps.begin(), all_comps.begin() + active.size()),
-			                           std::move(sums), eval_point, FSliceMut{const_cast<void *>(table.ptr), table.len_});
-			for (size_t r = 0; r < j; r++) {
-				const std::vector<B128> rc = prover.execute(batch_coeff);
-				for (size_t i = 0; i + 1 < rc.size(); i++) proofs.push_back(rc[i] * batch_coeff); // (front_loaded.rs:131-136)
-				const B128 z = sumcheck_challenges[ch_at + r];
-				challenges.push_back(z);
-				prover.fold(z);
-			}
-			ch_at += j;
-			finals = prover.finish();
-			std::reverse(challenges.begin(), challenges.end()); // (:106-108)
+		// j >= 1: the halves of the layer are multilinears 2i, 2i + 1; j = 0: both elements of layer 1 are read in one piece
+		const size_t half = (size_t)1 << j;
+		std::vector<FSlice> slices;
+		std::vector<B128> sums;
+		for (size_t i = 0; i < active.size(); i++) {
+			slices.push_back(FSlice{layer[i], j ? half : 2});
+			if (j) slices.push_back(FSlice{layer[i] + half * sizeof(B128), half});
+			sums.push_back(layer_eval[active[i]]);
 		}
-		eval_point = challenges;
+		DeviceBumpAllocator eq_alloc(eq_scratch);
+		// (step 0 has no rounds and takes no composition)
+		auto prover = std::make_unique<EqIndPointProver>(hal, backend, eq_alloc, j, std::move(slices), std::vector<EqIndComposition>(all_comps.begin(), all_comps.begin() + (j ? active.size() : 0)),
+		                                                 std::move(sums), eval_point, j ? 1 : 2);
+		BatchSumcheckOutput res = prove_batch_of_one(std::move(prover), batch_coeff, sumcheck_challenges.data() + ch_at);
+		std::vector<B128> proofs;
+		for (const auto &rp : res.round_proofs) proofs.insert(proofs.end(), rp.begin(), rp.end());
+		const std::vector<B128> finals = std::move(res.multilinear_evals[0]);
+		eval_point.assign(sumcheck_challenges.begin() + ch_at, sumcheck_challenges.begin() + ch_at + j);
+		std::reverse(eval_point.begin(), eval_point.end()); // (:106-108)
+		ch_at += j;
 		eval_point.push_back(gpa_challenge);
 		for (size_t i = 0; i < active.size(); i++) {
 			const B128 e0 = finals[2 * i], e1 = finals[2 * i + 1];
 			layer_eval[active[i]] = e0 + gpa_challenge * (e1 + e0); // extrapolate_line_scalar (:282-284)
 		}
 		out.round_proofs.push_back(std::move(proofs));
-		out.layer_evals.push_back(std::move(finals));
-		out.step_ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+		out.layer_evals.push_back(finals);
+		out.step_ms.push_back(elapsed_ms(t_begin));
 	}
 	return out;
 }

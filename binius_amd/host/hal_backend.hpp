@@ -150,7 +150,7 @@ public:
 				};
 				std::vector<Args> prepared;
 				for (auto &m : multilinears) {
-					auto halves = ComputeMemory::split_half_mut(FSliceMut{const_cast<void *>(m.large_field_folded_evals.ptr), m.large_field_folded_evals.len_});
+					auto halves = ComputeMemory::split_half_mut(ComputeMemory::to_mut(m.large_field_folded_evals));
 					prepared.push_back(Args{halves.first, ComputeMemory::to_const(halves.second)});
 				}
 				hal_.execute([&](ComputeLayerExecutor &exec) {
@@ -175,7 +175,7 @@ public:
 			uint64_t n_out = 0;
 			FSliceMut out{};
 			if (m.kind == SumcheckMultilinear::Folded && evaluation_order == EvaluationOrder::HighToLow) {
-				out = FSliceMut{const_cast<void *>(m.large_field_folded_evals.ptr), m.large_field_folded_evals.len_};
+				out = ComputeMemory::to_mut(m.large_field_folded_evals);
 			} else {
 				const size_t cap = m.kind == SumcheckMultilinear::Folded ? (m.large_field_folded_evals.len_ + 1) / 2 : (size_t)1 << (n_vars - 1);
 				out = alloc.alloc(cap ? cap : 1);

@@ -1,29 +1,27 @@
 // binius_amd/host/host_capi.cpp -> libbinius_amd_host.so
 //
-// The compiled form of the C++ host mirror (compute_layer.hpp / sumcheck.hpp): a complete
-// BivariateSumcheckProver run behind one C call, so the benchmark times the prover loop the way a
-// compiled (Rust) host would drive the HAL -- per round: one accumulate_kernels, two scalar
-// multiplications, one extrapolate_line per multilinear -- without interpreter overhead between
-// HAL calls.  Links only against the C ABI of include/binius_amd.h.
+// The compiled form of the C++ host mirror: a complete prover run behind one C call, so a benchmark or a test times the prover
+// loop the way a compiled (Rust) host would drive the HAL -- for the BivariateSumcheckProver per round one accumulate_kernels, two
+// scalar multiplications, one extrapolate_line per multilinear -- without interpreter overhead between HAL calls.  One entry point
+// per mirror (sumcheck.hpp, batch_prover.hpp, eq_ind.hpp, fri.hpp, piop.hpp, gkr_gpa.hpp, gkr_exp.hpp, flush.hpp, evalcheck.hpp,
+// zerocheck.hpp): it converts the C arrays (from_raw / to_raw), runs inside guarded(), which turns what is thrown into the return
+// code and bnh_last_error().  Links only against the C ABI of include/binius_amd.h.
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <unistd.h>
 
 #include <atomic>
-#include <cstdio>
 #include <cerrno>
-#include <cstring>
-#include <thread>
-
+#include <chrono>
+#include <cstdio>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/binius_amd_host.h"
-#include <chrono>
-#include <cstring>
-
+#include "batch_prover.hpp"
 #include "eq_ind.hpp"
 #include "evalcheck.hpp"
 #include "flush.hpp"
@@ -57,6 +55,49 @@ struct rccl_api {
 	fn_get_error_string err = nullptr;
 } g_rccl;
 constexpr int kNcclUint8 = 1; // ncclDataType_t
+
+// n product claims over m multilinears, as the C callers pass them: two indices per claim
+std::vector<IndexCompositionBivariate> index_compositions(uint32_t m, uint32_t n, const uint32_t *comp_indices)
+{
+	std::vector<IndexCompositionBivariate> comps;
+	for (uint32_t c = 0; c < n; c++) comps.push_back(IndexCompositionBivariate{m, {comp_indices[2 * c], comp_indices[2 * c + 1]}});
+	return comps;
+}
+
+// the truncated quadratic round proofs (two coefficients a round, missing ones zero) and the provers' final evaluations, concatenated
+void put_batch_output(const BatchSumcheckOutput &out, bn_f128 *round_proofs_out, bn_f128 *final_evals_out)
+{
+	for (size_t r = 0; r < out.round_proofs.size(); r++)
+		for (size_t i = 0; i < 2; i++) round_proofs_out[2 * r + i] = i < out.round_proofs[r].size() ? out.round_proofs[r][i].raw() : bn_f128{0, 0};
+	for (const auto &evals : out.multilinear_evals) final_evals_out = to_raw(evals, final_evals_out);
+}
+
+// GkrGpaOutput but its timings: per claim the product, the final evaluation and the final point, per step the round proofs and the
+// layer evaluations, each concatenated
+void put_gkr_gpa_output(const GkrGpaOutput &out, bn_f128 *products_out, bn_f128 *round_proofs_out, bn_f128 *layer_evals_out, bn_f128 *final_points_out,
+                        bn_f128 *final_evals_out)
+{
+	to_raw(out.products, products_out);
+	to_raw(out.final_evals, final_evals_out);
+	for (const auto &pt : out.final_points) final_points_out = to_raw(pt, final_points_out);
+	for (const auto &rp : out.round_proofs) round_proofs_out = to_raw(rp, round_proofs_out);
+	for (const auto &le : out.layer_evals) layer_evals_out = to_raw(le, layer_evals_out);
+}
+
+// the body of an entry point: what it throws becomes the return code, the message goes to bnh_last_error()
+template <class F>
+int guarded(F &&body)
+{
+	try {
+		return body();
+	} catch (const Error &e) {
+		g_err = e.what();
+		return (int)e.kind();
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return BN_ERR_CORE_LIB;
+	}
+}
 } // namespace
 
 extern "C" {
@@ -227,20 +268,16 @@ int bnh_bivariate_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t m, const
 			(void)bn_host_tail_allow_peer(c, 0);
 		}
 	} peer_guard{ctx};
-	try {
+	return guarded([&]() -> int {
 		ComputeLayer hal(ctx);
 		DeviceBumpAllocator dev_alloc(FSliceMut{d_scratch, (size_t)scratch_elems});
 		std::vector<B128> host_mem(m + 4);
 		HostBumpAllocator host_alloc(HostSliceMut{host_mem.data(), host_mem.size()});
 		std::vector<FSlice> mls;
 		for (uint32_t j = 0; j < m; j++) mls.push_back(FSlice{d_multilins[j], (size_t)1 << n_vars});
-		std::vector<IndexCompositionBivariate> comps;
-		std::vector<B128> sv;
-		for (uint32_t c = 0; c < n_comps; c++) {
-			comps.push_back(IndexCompositionBivariate{m, {comp_indices[2 * c], comp_indices[2 * c + 1]}});
-			sv.emplace_back(sums[c].lo, sums[c].hi);
-		}
-		const B128 bc(batch_coeff->lo, batch_coeff->hi);
+		const std::vector<IndexCompositionBivariate> comps = index_compositions(m, n_comps, comp_indices);
+		const std::vector<B128> sv = from_raw(sums, n_comps);
+		const B128 bc = from_raw(*batch_coeff);
 		if (!reduce && !rccl_comm && !shm && !peer) {
 			const auto t_prof = std::chrono::steady_clock::now();
 			if (AbiProf::on()) AbiProf::get() = AbiProf{};
@@ -248,13 +285,12 @@ int bnh_bivariate_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t m, const
 			for (uint32_t r = 0; r < n_vars; r++) {
 				std::vector<B128> rc = prover.execute(bc);
 				for (size_t i = 0; i < 3 && i < rc.size(); i++) round_coeffs_out[3 * r + i] = rc[i].raw();
-				prover.fold(B128(challenges[r].lo, challenges[r].hi));
+				prover.fold(from_raw(challenges[r]));
 			}
-			std::vector<B128> fin = prover.finish();
-			for (uint32_t j = 0; j < m; j++) final_evals_out[j] = fin[j].raw();
+			to_raw(prover.finish(), final_evals_out);
 			if (AbiProf::on()) { // BNH_PROF=1: where the wall time of this prove went (us): inside the C ABI by kind of call, and the rest
 				const AbiProf &p = AbiProf::get();
-				const double tot = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_prof).count();
+				const double tot = 1e3 * elapsed_ms(t_prof);
 				fprintf(stderr, "[bnh prof] n_vars %u: total %.2f us; kernel_launch %.2f (%llu calls), extrapolate_line %.2f (%llu), copies %.2f (%llu); outside the ABI %.2f\n",
 				        n_vars, tot, p.ns[0] / 1e3, (unsigned long long)p.calls[0], p.ns[1] / 1e3, (unsigned long long)p.calls[1], p.ns[2] / 1e3,
 				        (unsigned long long)p.calls[2], tot - (p.ns[0] + p.ns[1] + p.ns[2]) / 1e3);
@@ -265,7 +301,7 @@ int bnh_bivariate_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t m, const
 		std::vector<ExprEval> evaluators;
 		for (const auto &c : comps) evaluators.push_back(hal.compile_expr(c.expression()));
 		std::vector<FSliceMut> cur;
-		for (const auto &ml : mls) cur.push_back(FSliceMut{const_cast<void *>(ml.ptr), ml.len_});
+		for (const auto &ml : mls) cur.push_back(ComputeMemory::to_mut(ml));
 		bool pre_fold = true;
 		B128 running = evaluate_univariate(sv, bc);
 		const std::vector<B128> coeffs = powers(bc, n_comps);
@@ -350,9 +386,9 @@ int bnh_bivariate_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t m, const
 					throw Error(Error::CoreLibError, "round reduce callback failed");
 				}
 			}
-			std::vector<B128> rc = calculate_round_coeffs_from_evals(running, {B128(ev[0].lo, ev[0].hi), B128(ev[1].lo, ev[1].hi)});
-			for (size_t i = 0; i < 3; i++) coeffs_out[3 * r + i] = rc[i].raw();
-			const B128 z(ch[r].lo, ch[r].hi);
+			std::vector<B128> rc = calculate_round_coeffs_from_evals(running, from_raw(ev, 2));
+			to_raw(rc, coeffs_out + 3 * r);
+			const B128 z = from_raw(ch[r]);
 			running = evaluate_univariate(rc, z);
 			struct FoldArgs {
 				FSliceMut evals_0;
@@ -439,13 +475,7 @@ int bnh_bivariate_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t m, const
 			final_evals_out[j] = v.raw();
 		}
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 static thread_local int g_mlecheck_mode = -1;
@@ -473,18 +503,13 @@ int bnh_mlecheck_new(bn_ctx *ctx, uint32_t n_vars, uint32_t m, const void *const
                      const bn_f128 *eq_ind_challenges, void *d_scratch, uint64_t scratch_elems, uint32_t n_comps,
                      const uint32_t *comp_indices, const bn_f128 *sums, bnh_mlecheck **out)
 {
-	try {
+	return guarded([&]() -> int {
 		if (!out) throw Error(Error::InputValidation, "null argument");
 		std::unique_ptr<bnh_mlecheck> h(new bnh_mlecheck(ctx, d_scratch, scratch_elems, m));
 		std::vector<FSlice> mls;
 		for (uint32_t j = 0; j < m; j++) mls.push_back(FSlice{d_multilins[j], (size_t)1 << n_vars});
-		std::vector<IndexCompositionBivariate> comps;
-		std::vector<B128> sv, eqc;
-		for (uint32_t c = 0; c < n_comps; c++) {
-			comps.push_back(IndexCompositionBivariate{m, {comp_indices[2 * c], comp_indices[2 * c + 1]}});
-			sv.emplace_back(sums[c].lo, sums[c].hi);
-		}
-		for (uint32_t i = 0; i < n_vars; i++) eqc.emplace_back(eq_ind_challenges[i].lo, eq_ind_challenges[i].hi);
+		const std::vector<IndexCompositionBivariate> comps = index_compositions(m, n_comps, comp_indices);
+		const std::vector<B128> sv = from_raw(sums, n_comps), eqc = from_raw(eq_ind_challenges, n_vars);
 		const FSlice eq_table{d_eq_ind, (size_t)1 << (n_vars ? n_vars - 1 : 0)};
 		// The weighted prover (sumcheck.hpp) when it applies: a proper 2-colouring of the compositions, invertible
 		// indicator coordinates, enough scratch, and a table that IS the tensor expansion of the coordinates (the
@@ -524,67 +549,42 @@ int bnh_mlecheck_new(bn_ctx *ctx, uint32_t n_vars, uint32_t m, const void *const
 			h->literal.reset(new BivariateMLEcheckProver(h->hal, h->dev_alloc, h->host_alloc, n_vars, comps, sv, mls, eq_table, eqc));
 		*out = h.release();
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 // coeffs_out[4]: the round polynomial (degree 3)
 int bnh_mlecheck_execute(bnh_mlecheck *h, const bn_f128 *batch_coeff, bn_f128 *coeffs_out)
 {
-	try {
+	return guarded([&]() -> int {
 		if (!h || !batch_coeff || !coeffs_out) throw Error(Error::InputValidation, "null argument");
-		const B128 bc(batch_coeff->lo, batch_coeff->hi);
+		const B128 bc = from_raw(*batch_coeff);
 		const std::vector<B128> rc = h->weighted ? h->weighted->execute(bc) : h->literal->execute(bc);
 		for (size_t i = 0; i < 4; i++) coeffs_out[i] = i < rc.size() ? rc[i].raw() : bn_f128{0, 0};
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 int bnh_mlecheck_fold(bnh_mlecheck *h, const bn_f128 *challenge)
 {
-	try {
+	return guarded([&]() -> int {
 		if (!h || !challenge) throw Error(Error::InputValidation, "null argument");
-		const B128 z(challenge->lo, challenge->hi);
+		const B128 z = from_raw(*challenge);
 		if (h->weighted)
 			h->weighted->fold(z);
 		else
 			h->literal->fold(z);
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 // final_evals_out[m + 1]: the multilinears' evaluations, then eq_ind_prefix_eval.  The handle stays valid (free it).
 int bnh_mlecheck_finish(bnh_mlecheck *h, bn_f128 *final_evals_out)
 {
-	try {
+	return guarded([&]() -> int {
 		if (!h || !final_evals_out) throw Error(Error::InputValidation, "null argument");
-		const std::vector<B128> fin = h->weighted ? h->weighted->finish() : h->literal->finish();
-		for (uint32_t j = 0; j <= h->m; j++) final_evals_out[j] = fin[j].raw();
+		to_raw(h->weighted ? h->weighted->finish() : h->literal->finish(), final_evals_out);
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 void bnh_mlecheck_free(bnh_mlecheck *h) { delete h; }
@@ -620,7 +620,7 @@ int bnh_fri_commit_fold(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, ui
                         uint32_t n_arities, uint32_t n_test_queries, const void *d_message, void *d_scratch, uint64_t scratch_elems,
                         const bn_f128 *challenges, uint8_t *roots_out, bn_f128 *terminate_out, double *phase_ms_out)
 {
-	try {
+	return guarded([&]() -> int {
 		ComputeLayer hal(ctx);
 		DeviceBumpAllocator dev_alloc(FSliceMut{d_scratch, (size_t)scratch_elems});
 		FRIParams p(log_dim, log_inv_rate, log_batch_size, std::vector<size_t>(fold_arities, fold_arities + n_arities), n_test_queries);
@@ -635,26 +635,19 @@ int bnh_fri_commit_fold(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, ui
 		FRIFolder folder(hal, p, ntt, merkle, ComputeMemory::as_const(out.codeword), out.committed);
 		size_t n_roots = 1;
 		for (size_t r = 0; r < folder.n_rounds(); r++) {
-			auto [has_root, root] = folder.execute_fold_round(dev_alloc, B128(challenges[r].lo, challenges[r].hi));
+			auto [has_root, root] = folder.execute_fold_round(dev_alloc, from_raw(challenges[r]));
 			if (has_root) std::memcpy(roots_out + 32 * n_roots++, root.data(), 32);
 		}
 		auto fin = folder.finalize();
 		hal.sync();
 		const auto t2 = std::chrono::steady_clock::now();
-		if (terminate_out)
-			for (size_t i = 0; i < fin.first.size(); i++) terminate_out[i] = fin.first[i].raw();
+		if (terminate_out) to_raw(fin.first, terminate_out);
 		if (phase_ms_out) {
-			phase_ms_out[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-			phase_ms_out[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+			phase_ms_out[0] = elapsed_ms(t0, t1);
+			phase_ms_out[1] = elapsed_ms(t1, t2);
 		}
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 // piop::prove (crates/core/src/piop/prove.rs:148-395) through the C++ mirror piop.hpp: commit_interleaved of the merged message,
@@ -670,7 +663,7 @@ int bnh_piop_prove(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_
                    bn_f128 *scalars_out, uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out, uint32_t max_digests, uint32_t *n_digests_out,
                    double *phase_ms_out)
 {
-	try {
+	return guarded([&]() -> int {
 		if (!ctx || !commitment_out || !items_out || !n_items_out || !scalars_out || !n_scalars_out || !digests_out || !n_digests_out)
 			throw Error(Error::InputValidation, "null argument");
 		if ((n_committed && (!committed_n_vars || !d_committed)) || (n_transparent && (!transparent_n_vars || !d_transparent)) || (n_claims && (!claims || !claim_sums)) ||
@@ -702,10 +695,8 @@ int bnh_piop_prove(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_
 		if (commit_meta.total_vars() != (size_t)log_dim + log_batch_size) throw PiopError("FRI message length does not match the commit metadata's total_vars");
 		std::vector<PIOPSumcheckClaim> cl;
 		for (uint32_t i = 0; i < n_claims; i++)
-			cl.push_back(PIOPSumcheckClaim{claims[3 * i], claims[3 * i + 1], claims[3 * i + 2], B128(claim_sums[i].lo, claim_sums[i].hi)});
-		std::vector<B128> bcs, chs;
-		for (uint32_t i = 0; i < n_batch_coeffs; i++) bcs.emplace_back(batch_coeffs[i].lo, batch_coeffs[i].hi);
-		for (uint32_t i = 0; i < n_challenges; i++) chs.emplace_back(challenges[i].lo, challenges[i].hi);
+			cl.push_back(PIOPSumcheckClaim{claims[3 * i], claims[3 * i + 1], claims[3 * i + 2], from_raw(claim_sums[i])});
+		const std::vector<B128> bcs = from_raw(batch_coeffs, n_batch_coeffs), chs = from_raw(challenges, n_challenges);
 		FRIParams p(log_dim, log_inv_rate, log_batch_size, std::vector<size_t>(fold_arities, fold_arities + n_arities), n_test_queries);
 		AdditiveNTT ntt(hal, 5, p.rs_log_len());
 		BinaryMerkleTreeProver merkle(hal);
@@ -723,7 +714,7 @@ int bnh_piop_prove(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_
 		if (AbiProf::on()) {
 			const AbiProf &pr = AbiProf::get();
 			fprintf(stderr, "[bnh prof] piop prove %.1f us: send_round_proof %.1f, receive_challenge %.1f, fri round %.1f | inside the ABI: kernel_launch %.1f (%llu calls), extrapolate_line %.1f (%llu), copies %.1f (%llu)\n",
-			        std::chrono::duration<double, std::micro>(t2 - t1).count(), out.phase_ns[0] / 1e3, out.phase_ns[1] / 1e3, out.phase_ns[2] / 1e3, pr.ns[0] / 1e3,
+			        1e3 * elapsed_ms(t1, t2), out.phase_ns[0] / 1e3, out.phase_ns[1] / 1e3, out.phase_ns[2] / 1e3, pr.ns[0] / 1e3,
 			        (unsigned long long)pr.calls[0], pr.ns[1] / 1e3, (unsigned long long)pr.calls[1], pr.ns[2] / 1e3, (unsigned long long)pr.calls[2]);
 		}
 		uint32_t ni = 0, nd = 0;
@@ -737,7 +728,7 @@ int bnh_piop_prove(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_
 				items_out[2 * ni + 1] = 1;
 			} else {
 				if (ns + it.scalars.size() > max_scalars) throw Error(Error::InputValidation, "transcript has more scalars than scalars_out holds");
-				for (const B128 &v : it.scalars) scalars_out[ns++] = v.raw();
+				ns = to_raw(it.scalars, scalars_out + ns) - scalars_out;
 				items_out[2 * ni + 1] = (uint32_t)it.scalars.size();
 			}
 			ni++;
@@ -746,17 +737,11 @@ int bnh_piop_prove(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_
 		*n_scalars_out = ns;
 		*n_digests_out = nd;
 		if (phase_ms_out) {
-			phase_ms_out[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-			phase_ms_out[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+			phase_ms_out[0] = elapsed_ms(t0, t1);
+			phase_ms_out[1] = elapsed_ms(t1, t2);
 		}
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 // The front-loaded batch prover alone (protocols/sumcheck/prove/front_loaded.rs:33-203: BatchProver::run with the transcript's
@@ -769,7 +754,7 @@ int bnh_batch_sumcheck_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_t *pr
                              const bn_f128 *sums, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges,
                              bn_f128 *round_proofs_out, bn_f128 *final_evals_out)
 {
-	try {
+	return guarded([&]() -> int {
 		// (public entry point: every pointer it dereferences and every shift amount it derives is checked first -- ADVICE r5)
 		if (!ctx || (n_provers && (!prover_desc || !batch_coeffs)) || !challenges || !round_proofs_out || !final_evals_out || (!d_scratch && scratch_elems))
 			throw Error(Error::InputValidation, "null argument");
@@ -788,48 +773,20 @@ int bnh_batch_sumcheck_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_t *pr
 		std::vector<B128> host_mem(total_m + 8);
 		HostBumpAllocator host_alloc(HostSliceMut{host_mem.data(), host_mem.size()});
 		std::vector<std::unique_ptr<BivariateSumcheckProver>> provers;
-		std::vector<B128> bcs;
 		size_t at_ml = 0, at_c = 0;
 		for (uint32_t i = 0; i < n_provers; i++) {
 			const uint32_t n_vars = prover_desc[3 * i], m = prover_desc[3 * i + 1], nc = prover_desc[3 * i + 2];
 			std::vector<FSlice> mls;
 			for (uint32_t j = 0; j < m; j++) mls.push_back(FSlice{d_multilins[at_ml + j], (size_t)1 << n_vars});
-			std::vector<IndexCompositionBivariate> comps;
-			std::vector<B128> sv;
-			for (uint32_t c = 0; c < nc; c++) {
-				comps.push_back(IndexCompositionBivariate{m, {comp_indices[2 * (at_c + c)], comp_indices[2 * (at_c + c) + 1]}});
-				sv.emplace_back(sums[at_c + c].lo, sums[at_c + c].hi);
-			}
+			provers.push_back(std::make_unique<BivariateSumcheckProver>(hal, dev_alloc, host_alloc, n_vars, index_compositions(m, nc, comp_indices + 2 * at_c),
+			                                                            from_raw(sums + at_c, nc), mls));
 			at_ml += m;
 			at_c += nc;
-			provers.push_back(std::make_unique<BivariateSumcheckProver>(hal, dev_alloc, host_alloc, n_vars, comps, sv, mls));
-			bcs.emplace_back(batch_coeffs[i].lo, batch_coeffs[i].hi);
 		}
-		SumcheckBatchProver batch(std::move(provers), bcs);
-		const size_t rounds = batch.total_rounds();
-		PiopTranscript tr;
-		for (size_t r = 0; r < rounds; r++) {
-			batch.send_round_proof(tr);
-			batch.receive_challenge(B128(challenges[r].lo, challenges[r].hi));
-		}
-		batch.finish(tr);
-		size_t r = 0, fe = 0;
-		for (const auto &it : tr.items) {
-			if (it.kind == PiopTranscript::Item::RoundProof) {
-				for (size_t i = 0; i < 2; i++) round_proofs_out[2 * r + i] = i < it.scalars.size() ? it.scalars[i].raw() : bn_f128{0, 0};
-				r++;
-			} else if (it.kind == PiopTranscript::Item::MultilinearEvals) {
-				for (const B128 &v : it.scalars) final_evals_out[fe++] = v.raw();
-			}
-		}
+		SumcheckBatchProver<BivariateSumcheckProver> batch(std::move(provers), from_raw(batch_coeffs, n_provers));
+		put_batch_output(batch.run(from_raw(challenges, batch.total_rounds()).data()), round_proofs_out, final_evals_out);
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 // EqIndSumcheckProver (crates/core/src/protocols/sumcheck/prove/eq_ind.rs:378-644; binius_amd/host/eq_ind.hpp) over the old HAL
@@ -846,7 +803,7 @@ int bnh_eqind_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void 
                              const bn_f128 *eq_ind_challenges, void *d_eq_ind, uint64_t eq_ind_elems, const bn_f128 *batch_coeff, const bn_f128 *challenges,
                              bn_f128 *round_coeffs_out, bn_f128 *final_evals_out)
 {
-	try {
+	return guarded([&]() -> int {
 		if (!ctx || (!d_multilins && n_mls) || (n_comps && (!steps || !n_steps || !steps_inf || !n_steps_inf || !sums)) || !eq_ind_challenges || !d_eq_ind || !batch_coeff ||
 		    !challenges || !round_coeffs_out || !final_evals_out)
 			throw Error(Error::InputValidation, "null argument");
@@ -858,10 +815,9 @@ int bnh_eqind_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void 
 		ComputeLayer hal(ctx);
 		Mi355xBackend backend(hal);
 		DeviceBumpAllocator dev_alloc(FSliceMut{d_eq_ind, (size_t)eq_ind_elems});
-		std::vector<SumcheckMultilinear> mls;
-		for (uint32_t j = 0; j < n_mls; j++) mls.push_back(SumcheckMultilinear::folded(FSlice{d_multilins[j], (size_t)1 << n_vars}));
+		std::vector<FSlice> mls;
+		for (uint32_t j = 0; j < n_mls; j++) mls.push_back(FSlice{d_multilins[j], (size_t)1 << n_vars});
 		std::vector<EqIndComposition> comps;
-		std::vector<B128> sv;
 		size_t at = 0, at_inf = 0;
 		for (uint32_t c = 0; c < n_comps; c++) {
 			EqIndComposition ec;
@@ -871,42 +827,30 @@ int bnh_eqind_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void 
 			at_inf += n_steps_inf[c];
 			ec.degree = degrees ? degrees[c] : 2;
 			comps.push_back(ec);
-			sv.emplace_back(sums[c].lo, sums[c].hi);
 		}
-		std::vector<B128> eqc;
-		for (uint32_t i = 0; i < n_vars; i++) eqc.emplace_back(eq_ind_challenges[i].lo, eq_ind_challenges[i].hi);
-		// eq_ind_expand, High-to-Low: the tensor expansion of all challenges but the last (eq_ind.rs:430-446)
-		const FSlice table = backend.tensor_product_full_query(std::vector<B128>(eqc.begin(), eqc.end() - 1), dev_alloc);
-		EqIndSumcheckProver prover(hal, backend, dev_alloc, n_vars, std::move(mls), std::move(comps), std::move(sv), eqc, FSliceMut{const_cast<void *>(table.ptr), table.len_});
-		const B128 bc(batch_coeff->lo, batch_coeff->hi);
+		EqIndPointProver prover(hal, backend, dev_alloc, n_vars, std::move(mls), std::move(comps), from_raw(sums, n_comps), from_raw(eq_ind_challenges, n_vars));
+		const B128 bc = from_raw(*batch_coeff);
 		double us_exec = 0, us_fold = 0;
 		const auto t_setup = now();
 		for (uint32_t r = 0; r < n_vars; r++) {
 			const auto t0 = prof ? now() : std::chrono::steady_clock::time_point{};
 			const std::vector<B128> rc = prover.execute(bc);
 			const auto t1 = prof ? now() : t0;
-			for (size_t i = 0; i < rc.size(); i++) round_coeffs_out[rc.size() * r + i] = rc[i].raw();
-			prover.fold(B128(challenges[r].lo, challenges[r].hi));
+			to_raw(rc, round_coeffs_out + rc.size() * r);
+			prover.fold(from_raw(challenges[r]));
 			if (prof) {
-				us_exec += std::chrono::duration<double, std::micro>(t1 - t0).count();
-				us_fold += std::chrono::duration<double, std::micro>(now() - t1).count();
+				us_exec += 1e3 * elapsed_ms(t0, t1);
+				us_fold += 1e3 * elapsed_ms(t1);
 			}
 		}
 		const auto t_rounds = now();
-		const std::vector<B128> fin = prover.finish();
-		for (size_t j = 0; j < fin.size(); j++) final_evals_out[j] = fin[j].raw();
+		to_raw(prover.finish(), final_evals_out);
 		if (prof)
 			fprintf(stderr, "[bnh prof] eq-ind sumcheck, %u rounds, %u multilinears, %u compositions: set-up %.1f us, execute %.1f us, fold %.1f us, finish %.1f us\n", n_vars,
-			        n_mls, n_comps, std::chrono::duration<double, std::micro>(t_setup - t_begin).count(), us_exec, us_fold,
-			        std::chrono::duration<double, std::micro>(now() - t_rounds).count());
+			        n_mls, n_comps, 1e3 * elapsed_ms(t_begin, t_setup), us_exec, us_fold,
+			        1e3 * elapsed_ms(t_rounds));
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 // gkr_gpa::batch_prove (crates/core/src/protocols/gkr_gpa/prove.rs:33-296) through the C++ mirror binius_amd/host/gkr_gpa.hpp; the
@@ -916,7 +860,7 @@ int bnh_gkr_gpa_prove(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, co
                       bn_f128 *products_out, bn_f128 *round_proofs_out, bn_f128 *layer_evals_out, bn_f128 *final_points_out, bn_f128 *final_evals_out,
                       double *step_ms_out)
 {
-	try {
+	return guarded([&]() -> int {
 		if (!ctx) throw Error(Error::InputValidation, "null ctx");
 		if (n_claims == 0) return 0;
 		if (!n_vars || !d_inputs || !input_lens || !d_arenas || !products_out || !final_evals_out) throw Error(Error::InputValidation, "null argument");
@@ -934,34 +878,14 @@ int bnh_gkr_gpa_prove(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, co
 		}
 		if (max_n >= 1 && (!d_scratch || !batch_coeffs || !gpa_challenges || !layer_evals_out || !final_points_out)) throw Error(Error::InputValidation, "null argument");
 		if (max_n >= 2 && (!sumcheck_challenges || !round_proofs_out)) throw Error(Error::InputValidation, "null argument");
-		auto vec = [](const bn_f128 *p, size_t n) {
-			std::vector<B128> v;
-			for (size_t i = 0; i < n; i++) v.emplace_back(p[i].lo, p[i].hi);
-			return v;
-		};
 		ComputeLayer hal(ctx);
 		Mi355xBackend backend(hal);
-		const GkrGpaOutput out = gkr_gpa_batch_prove(hal, backend, nv, ins, ars, FSliceMut{d_scratch, (size_t)scratch_elems}, vec(batch_coeffs, max_n),
-		                                            vec(sumcheck_challenges, max_n * (max_n ? max_n - 1 : 0) / 2), vec(gpa_challenges, max_n));
-		size_t at_p = 0, at_e = 0, at_f = 0;
-		for (uint32_t t = 0; t < n_claims; t++) {
-			products_out[t] = out.products[t].raw();
-			final_evals_out[t] = out.final_evals[t].raw();
-			for (const B128 &v : out.final_points[t]) final_points_out[at_f++] = v.raw();
-		}
-		for (size_t j = 0; j < out.round_proofs.size(); j++) {
-			for (const B128 &v : out.round_proofs[j]) round_proofs_out[at_p++] = v.raw();
-			for (const B128 &v : out.layer_evals[j]) layer_evals_out[at_e++] = v.raw();
-			if (step_ms_out) step_ms_out[j] = out.step_ms[j];
-		}
+		const GkrGpaOutput out = gkr_gpa_batch_prove(hal, backend, nv, ins, ars, FSliceMut{d_scratch, (size_t)scratch_elems}, from_raw(batch_coeffs, max_n),
+		                                            from_raw(sumcheck_challenges, max_n * (max_n ? max_n - 1 : 0) / 2), from_raw(gpa_challenges, max_n));
+		put_gkr_gpa_output(out, products_out, round_proofs_out, layer_evals_out, final_points_out, final_evals_out);
+		for (size_t j = 0; step_ms_out && j < out.step_ms.size(); j++) step_ms_out[j] = out.step_ms[j];
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 // gkr_exp::batch_prove (crates/core/src/protocols/gkr_exp/batch_prove.rs:46-315) through the C++ mirror binius_amd/host/gkr_exp.hpp; the
@@ -973,7 +897,7 @@ int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths,
                       bn_f128 *round_proofs_out, uint32_t *provers_per_layer_out, uint32_t *evals_per_prover_out, bn_f128 *multilinear_evals_out,
                       uint32_t *claims_per_layer_out, uint32_t *claim_n_vars_out, bn_f128 *claim_points_out, bn_f128 *claim_evals_out, double *layer_ms_out)
 {
-	try {
+	return guarded([&]() -> int {
 		if (!ctx) throw Error(Error::InputValidation, "null ctx");
 		if (n_witnesses != n_claims) throw Error(Error::InputValidation, "MismatchedWitnessClaimLength");
 		if (n_layers_out) *n_layers_out = 0;
@@ -993,59 +917,47 @@ int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths,
 			c.n_vars = n_vars[t];
 			c.width = widths[t];
 			c.dynamic = kinds[t] == BN_EXP_DYNAMIC;
-			c.static_base = B128(static_bases[t].lo, static_bases[t].hi);
+			c.static_base = from_raw(static_bases[t]);
 			c.base = FSlice{d_bases[t], c.dynamic ? (size_t)1 << c.n_vars : 0};
 			c.bits.assign(d_exponent_bits + at_bits, d_exponent_bits + at_bits + c.width);
 			at_bits += c.width;
 			c.arena = FSliceMut{d_arenas[t], c.width << c.n_vars};
 			if (c.n_vars && !eval_points) throw Error(Error::InputValidation, "null argument");
-			for (size_t i = 0; i < c.n_vars; i++) c.eval_point.emplace_back(eval_points[at_pt + i].lo, eval_points[at_pt + i].hi);
+			c.eval_point = from_raw(eval_points + at_pt, c.n_vars);
 			at_pt += c.n_vars;
-			c.eval = B128(evals[t].lo, evals[t].hi);
+			c.eval = from_raw(evals[t]);
 			max_w = std::max(max_w, c.width);
 			max_n = std::max(max_n, c.n_vars);
 		}
 		if (max_n && !challenges) throw Error(Error::InputValidation, "null argument");
 		if (!d_scratch && scratch_elems) throw Error(Error::InputValidation, "null argument");
-		auto vec = [](const bn_f128 *p, size_t n) {
-			std::vector<B128> v;
-			for (size_t i = 0; i < n; i++) v.emplace_back(p[i].lo, p[i].hi);
-			return v;
-		};
 		ComputeLayer hal(ctx);
 		Mi355xBackend backend(hal);
-		const GkrExpOutput out = gkr_exp_batch_prove(hal, backend, n_witnesses, claims, FSliceMut{d_scratch, (size_t)scratch_elems}, vec(batch_coeffs, max_w * k),
-		                                            vec(challenges, max_w * max_n));
+		const GkrExpOutput out = gkr_exp_batch_prove(hal, backend, n_witnesses, claims, FSliceMut{d_scratch, (size_t)scratch_elems}, from_raw(batch_coeffs, max_w * k),
+		                                            from_raw(challenges, max_w * max_n));
 		*n_layers_out = (uint32_t)out.round_proofs.size();
-		size_t at_c = 0, at_e = 0, at_p = 0, at_v = 0;
 		for (size_t L = 0; L < out.round_proofs.size(); L++) {
 			rounds_per_layer_out[L] = (uint32_t)out.round_proofs[L].size();
 			for (size_t r = 0; r < out.round_proofs[L].size(); r++) {
 				coeffs_per_round_out[L * std::max<size_t>(max_n, 1) + r] = (uint32_t)out.round_proofs[L][r].size();
-				for (const B128 &v : out.round_proofs[L][r]) round_proofs_out[at_c++] = v.raw();
+				round_proofs_out = to_raw(out.round_proofs[L][r], round_proofs_out);
 			}
 			provers_per_layer_out[L] = (uint32_t)out.multilinear_evals[L].size();
 			for (size_t g = 0; g < out.multilinear_evals[L].size(); g++) {
 				evals_per_prover_out[L * k + g] = (uint32_t)out.multilinear_evals[L][g].size();
-				for (const B128 &v : out.multilinear_evals[L][g]) multilinear_evals_out[at_e++] = v.raw();
+				multilinear_evals_out = to_raw(out.multilinear_evals[L][g], multilinear_evals_out);
 			}
 			claims_per_layer_out[L] = (uint32_t)out.layer_claims[L].size();
 			for (size_t i = 0; i < out.layer_claims[L].size(); i++) {
 				const GkrExpLayerClaim &lc = out.layer_claims[L][i];
 				claim_n_vars_out[L * 2 * k + i] = (uint32_t)lc.eval_point.size();
-				for (const B128 &v : lc.eval_point) claim_points_out[at_p++] = v.raw();
-				claim_evals_out[at_v++] = lc.eval.raw();
+				claim_points_out = to_raw(lc.eval_point, claim_points_out);
+				*claim_evals_out++ = lc.eval.raw();
 			}
 			if (layer_ms_out) layer_ms_out[L] = out.layer_ms[L];
 		}
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 // The product-check phase of the constraint-system prover (core/src/constraint_system/prove.rs:276-428) through the C++ mirror
@@ -1062,7 +974,7 @@ int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *c
                               bn_f128 *check_round_proofs_out, bn_f128 *check_final_evals_out, uint32_t *n_linear_out, uint32_t *linear_flushes_out,
                               double *phase_ms_out)
 {
-	try {
+	return guarded([&]() -> int {
 		if (!ctx) throw Error(Error::InputValidation, "null ctx");
 		if (n_checks_out) *n_checks_out = 0;
 		if (n_linear_out) *n_linear_out = 0;
@@ -1073,11 +985,6 @@ int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *c
 		                  !linear_flushes_out || !red_batch_coeffs))
 			throw Error(Error::InputValidation, "null argument");
 		if (n_nonzero && (!nonzero_ids || !d_nonzero_columns || !nonzero_levels || !nonzero_n_vars)) throw Error(Error::InputValidation, "null argument");
-		auto vec = [](const bn_f128 *p, size_t n) {
-			std::vector<B128> v;
-			for (size_t i = 0; p && i < n; i++) v.emplace_back(p[i].lo, p[i].hi);
-			return v;
-		};
 		std::vector<FlushSpec> flushes(n_flushes);
 		std::vector<NonZeroSpec> nonzero(n_nonzero);
 		size_t at_s = 0, at_e = 0, max_n = 0;
@@ -1095,7 +1002,7 @@ int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *c
 				e.id = entry_ids[at_e];
 				e.column = d_entry_columns[at_e];
 				e.level = entry_levels[at_e];
-				e.base = B128(entry_consts[at_e].lo, entry_consts[at_e].hi);
+				e.base = from_raw(entry_consts[at_e]);
 				fl.entries.push_back(e);
 			}
 		}
@@ -1113,44 +1020,28 @@ int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *c
 		ComputeLayer hal(ctx);
 		Mi355xBackend backend(hal);
 		const FlushProdcheckOutput out =
-		    flush_prodcheck_prove(hal, backend, flushes, nonzero, B128(mixing_challenge->lo, mixing_challenge->hi), vec(permutation_challenges, n_channels),
-		                          FSliceMut{d_scratch, (size_t)scratch_elems}, vec(gpa_batch_coeffs, max_n), vec(gpa_sumcheck_challenges, max_n * (max_n ? max_n - 1 : 0) / 2),
-		                          vec(gpa_challenges, max_n), vec(red_batch_coeffs, groups.size()), vec(red_challenges, red_n));
+		    flush_prodcheck_prove(hal, backend, flushes, nonzero, from_raw(*mixing_challenge), from_raw(permutation_challenges, n_channels),
+		                          FSliceMut{d_scratch, (size_t)scratch_elems}, from_raw(gpa_batch_coeffs, max_n), from_raw(gpa_sumcheck_challenges, max_n * (max_n ? max_n - 1 : 0) / 2),
+		                          from_raw(gpa_challenges, max_n), from_raw(red_batch_coeffs, groups.size()), from_raw(red_challenges, red_n));
 		for (uint32_t f = 0; f < n_flushes; f++) prefix_lens_out[f] = out.prefix_lens[f];
-		size_t at_p = 0, at_l = 0, at_f = 0;
-		for (size_t t = 0; t < out.gpa.products.size(); t++) {
-			products_out[t] = out.gpa.products[t].raw();
-			gpa_final_evals_out[t] = out.gpa.final_evals[t].raw();
-			for (const B128 &v : out.gpa.final_points[t]) gpa_final_points_out[at_f++] = v.raw();
-		}
-		for (size_t j = 0; j < out.gpa.round_proofs.size(); j++) {
-			for (const B128 &v : out.gpa.round_proofs[j]) gpa_round_proofs_out[at_p++] = v.raw();
-			for (const B128 &v : out.gpa.layer_evals[j]) gpa_layer_evals_out[at_l++] = v.raw();
-		}
+		put_gkr_gpa_output(out.gpa, products_out, gpa_round_proofs_out, gpa_layer_evals_out, gpa_final_points_out, gpa_final_evals_out);
 		*n_checks_out = (uint32_t)out.checks.size();
-		size_t at_i = 0, at_c = 0, at_v = 0;
+		size_t at_i = 0;
 		for (size_t g = 0; g < out.checks.size(); g++) {
 			const FlushMleCheck &c = out.checks[g];
 			check_desc_out[3 * g] = (uint32_t)c.n_vars;
 			check_desc_out[3 * g + 1] = (uint32_t)c.ids.size();
 			check_desc_out[3 * g + 2] = c.round_proofs.empty() ? 0 : (uint32_t)c.round_proofs[0].size();
 			for (size_t id : c.ids) check_ids_out[at_i++] = (uint32_t)id;
-			for (const auto &r : c.round_proofs)
-				for (const B128 &v : r) check_round_proofs_out[at_c++] = v.raw();
-			for (const B128 &v : c.final_evals) check_final_evals_out[at_v++] = v.raw();
+			for (const auto &r : c.round_proofs) check_round_proofs_out = to_raw(r, check_round_proofs_out);
+			check_final_evals_out = to_raw(c.final_evals, check_final_evals_out);
 		}
 		*n_linear_out = (uint32_t)out.linear_flushes.size();
 		for (size_t i = 0; i < out.linear_flushes.size(); i++) linear_flushes_out[i] = (uint32_t)out.linear_flushes[i];
 		if (phase_ms_out)
 			for (int i = 0; i < 4; i++) phase_ms_out[i] = out.phase_ms[i];
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 // One round of evalcheck's bivariate sumchecks (evalcheck/subclaims.rs:549-586 with the witness construction in front of it) through
@@ -1160,7 +1051,7 @@ int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_
                                   uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges, bn_f128 *round_proofs_out,
                                   bn_f128 *final_evals_out)
 {
-	try {
+	return guarded([&]() -> int {
 		if (!ctx || (n_provers && (!prover_desc || !batch_coeffs)) || !round_proofs_out || !final_evals_out || (!d_scratch && scratch_elems) || (pool_len && !point_pool))
 			throw Error(Error::InputValidation, "null argument");
 		size_t total_m = 0, total_c = 0, max_b = 0;
@@ -1171,10 +1062,8 @@ int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_
 			total_c += prover_desc[3 * i + 2];
 		}
 		if ((total_m && (!ml_desc || !d_columns)) || (total_c && (!comp_indices || !sums)) || (max_b && !challenges)) throw Error(Error::InputValidation, "null argument");
-		std::vector<B128> pool;
-		for (uint32_t i = 0; i < pool_len; i++) pool.emplace_back(point_pool[i].lo, point_pool[i].hi);
+		const std::vector<B128> pool = from_raw(point_pool, pool_len);
 		std::vector<EvalcheckProver> provers(n_provers);
-		std::vector<B128> bcs, ch;
 		size_t at_ml = 0, at_c = 0;
 		for (uint32_t i = 0; i < n_provers; i++) {
 			EvalcheckProver &p = provers[i];
@@ -1211,28 +1100,15 @@ int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_
 				}
 				p.multilins.push_back(ml);
 			}
-			for (uint32_t c = 0; c < nc; c++, at_c++) {
-				p.compositions.push_back(IndexCompositionBivariate{m, {comp_indices[2 * at_c], comp_indices[2 * at_c + 1]}});
-				p.sums.emplace_back(sums[at_c].lo, sums[at_c].hi);
-			}
-			bcs.emplace_back(batch_coeffs[i].lo, batch_coeffs[i].hi);
+			p.compositions = index_compositions(m, nc, comp_indices + 2 * at_c);
+			p.sums = from_raw(sums + at_c, nc);
+			at_c += nc;
 		}
-		for (size_t r = 0; r < max_b; r++) ch.emplace_back(challenges[r].lo, challenges[r].hi);
 		ComputeLayer hal(ctx);
-		const EvalcheckOutput out = evalcheck_bivariate_prove(hal, provers, pool, FSliceMut{d_scratch, (size_t)scratch_elems}, bcs, ch);
-		for (size_t r = 0; r < out.round_proofs.size(); r++)
-			for (size_t i = 0; i < 2; i++) round_proofs_out[2 * r + i] = i < out.round_proofs[r].size() ? out.round_proofs[r][i].raw() : bn_f128{0, 0};
-		size_t fe = 0;
-		for (const auto &evals : out.multilinear_evals)
-			for (const B128 &v : evals) final_evals_out[fe++] = v.raw();
+		const EvalcheckOutput out = evalcheck_bivariate_prove(hal, provers, pool, FSliceMut{d_scratch, (size_t)scratch_elems}, from_raw(batch_coeffs, n_provers), from_raw(challenges, max_b));
+		put_batch_output(out, round_proofs_out, final_evals_out);
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 // batch_zerocheck::batch_prove (crates/core/src/protocols/sumcheck/prove/batch_zerocheck.rs:166-293) through the C++ mirror
@@ -1256,7 +1132,7 @@ int bnh_zerocheck_batch_prove(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_roun
                               bn_f128 *final_evals_out, bn_f128 *reduction_round_coeffs_out, bn_f128 *reduction_final_evals_out, bn_f128 *skipped_challenges_out,
                               bn_f128 *unskipped_challenges_out, bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out)
 {
-	try {
+	return guarded([&]() -> int {
 		if (!ctx || !n_tables || !n_vars || !n_cols || !n_comps || !batch_coeffs || !univariate_challenge || !reduction_batch_coeff || !reduction_challenges || !final_evals_out ||
 		    !reduction_round_coeffs_out || !reduction_final_evals_out || !skipped_challenges_out || !concat_multilinear_evals_out || (!d_scratch && scratch_elems))
 			throw Error(Error::InputValidation, "null argument");
@@ -1295,19 +1171,11 @@ int bnh_zerocheck_batch_prove(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_roun
 				at_inf += n_steps_inf[at_comp];
 			}
 		}
-		auto vec = [](const bn_f128 *p, size_t n) {
-			std::vector<B128> v;
-			for (size_t i = 0; i < n; i++) v.emplace_back(p[i].lo, p[i].hi);
-			return v;
-		};
-		const ZerocheckBatchOutput out = zerocheck_batch_prove(hal, tables, skip_rounds, vec(zerocheck_challenges, rounds), vec(batch_coeffs, n_tables),
-		                                                       B128(univariate_challenge->lo, univariate_challenge->hi), vec(sumcheck_challenges, rounds),
-		                                                       B128(reduction_batch_coeff->lo, reduction_batch_coeff->hi), vec(reduction_challenges, skip_rounds),
+		const ZerocheckBatchOutput out = zerocheck_batch_prove(hal, tables, skip_rounds, from_raw(zerocheck_challenges, rounds), from_raw(batch_coeffs, n_tables),
+		                                                       from_raw(*univariate_challenge), from_raw(sumcheck_challenges, rounds),
+		                                                       from_raw(*reduction_batch_coeff), from_raw(reduction_challenges, skip_rounds),
 		                                                       FSliceMut{d_scratch, (size_t)scratch_elems});
-		auto put = [](bn_f128 *dst, const std::vector<B128> &v) {
-			for (size_t i = 0; i < v.size(); i++) dst[i] = v[i].raw();
-			return dst + v.size();
-		};
+		auto put = [](bn_f128 *dst, const std::vector<B128> &v) { return to_raw(v, dst); };
 		if (!out.message.empty()) {
 			if (!message_out) throw Error(Error::InputValidation, "null argument");
 			put(message_out, out.message);
@@ -1327,13 +1195,7 @@ int bnh_zerocheck_batch_prove(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_roun
 			if (phase_calls_out) phase_calls_out[i] = out.phase_calls[i];
 		}
 		return 0;
-	} catch (const Error &e) {
-		g_err = e.what();
-		return (int)e.kind();
-	} catch (const std::exception &e) {
-		g_err = e.what();
-		return BN_ERR_CORE_LIB;
-	}
+	});
 }
 
 } // extern "C"

@@ -1,7 +1,6 @@
 // binius_amd/host/piop.hpp -- C++ mirror of the reference's PCS prover loop, the caller that decides the call shape the backend
 // sees:
 //
-//   SumcheckBatchProver (front-loaded)     crates/core/src/protocols/sumcheck/prove/front_loaded.rs:33-203
 //   CommitMeta                             crates/core/src/piop/verify.rs:30-98
 //   PIOPSumcheckClaim                      crates/core/src/piop/verify.rs (n_vars, committed, transparent, sum)
 //   make_sumcheck_claim_descs              crates/core/src/piop/verify.rs:192-270
@@ -9,18 +8,18 @@
 //   prove                                  crates/core/src/piop/prove.rs:148-303
 //   prove_interleaved_fri_sumcheck         crates/core/src/piop/prove.rs:306-395
 //
-// over the mirrors of BivariateSumcheckProver (sumcheck.hpp) and FRIFolder / commit_interleaved (fri.hpp).  Protocol bookkeeping
+// over the mirrors of BivariateSumcheckProver (sumcheck.hpp), the front-loaded SumcheckBatchProver (batch_prover.hpp) and FRIFolder /
+// commit_interleaved (fri.hpp).  Protocol bookkeeping
 // only; every hypercube-sized operation is a HAL call.  The Fiat-Shamir transcript is replaced by what it would have produced
 // (batch coefficients, one challenge per round) and by a record of what the prover writes to it, in order -- the same
 // convention as the other mirrors (compute_test_utils' tests sample from a transcript; ours take a seeded stream).
 // F = P = BinaryField128b (the device field; packed committed multilinears are already its elements).
 #pragma once
 #include <chrono>
-#include <deque>
 #include <memory>
 
+#include "batch_prover.hpp"
 #include "fri.hpp"
-#include "sumcheck.hpp"
 
 namespace binius_amd {
 
@@ -28,13 +27,6 @@ class PiopError : public Error {
 public:
 	explicit PiopError(const std::string &what) : Error(InputValidation, what) {}
 };
-
-// RoundCoeffs arithmetic of the batch prover (protocols/sumcheck/common.rs:108-150)
-inline void round_coeffs_add_scaled(std::vector<B128> &acc, const std::vector<B128> &rhs, B128 scale)
-{
-	if (acc.size() < rhs.size()) acc.resize(rhs.size(), B128::ZERO());
-	for (size_t i = 0; i < rhs.size(); i++) acc[i] = acc[i] + rhs[i] * scale;
-}
 
 // What the prover writes to the transcript, in order (ProverTranscript::message()): scalars and digests
 struct PiopTranscript {
@@ -46,61 +38,6 @@ struct PiopTranscript {
 	std::vector<Item> items;
 	void write_scalar_slice(Item::Kind k, const std::vector<B128> &v) { items.push_back(Item{k, v, Digest{}}); }
 	void write_digest(const Digest &d) { items.push_back(Item{Item::FriCommitment, {}, d}); }
-};
-
-// front_loaded.rs:33-203 with the batch coefficients handed in (new_prebatched, :79-107)
-class SumcheckBatchProver {
-public:
-	SumcheckBatchProver(std::vector<std::unique_ptr<BivariateSumcheckProver>> provers, const std::vector<B128> &batch_coeffs)
-	{
-		for (size_t i = 1; i < provers.size(); i++)
-			if (provers[i]->n_vars() < provers[i - 1]->n_vars()) throw SumcheckError("ClaimsOutOfOrder");
-		if (batch_coeffs.size() != provers.size()) throw SumcheckError("IncorrectNumberOfBatchCoeffs");
-		for (size_t i = 0; i < provers.size(); i++) provers_.emplace_back(std::move(provers[i]), batch_coeffs[i]);
-	}
-	size_t total_rounds() const { return provers_.empty() ? 0 : provers_.back().first->n_vars(); }
-	size_t n_live() const { return provers_.size(); }
-
-	// :123-140
-	void send_round_proof(PiopTranscript &transcript)
-	{
-		finish_claim_provers(transcript);
-		std::vector<B128> round_coeffs;
-		for (auto &pc : provers_) {
-			const std::vector<B128> prover_coeffs = pc.first->execute(pc.second);
-			round_coeffs_add_scaled(round_coeffs, prover_coeffs, pc.second);
-		}
-		if (!round_coeffs.empty()) round_coeffs.pop_back(); // RoundCoeffs::truncate (common.rs:101-105)
-		transcript.write_scalar_slice(PiopTranscript::Item::RoundProof, round_coeffs);
-	}
-	// :143-158
-	void receive_challenge(B128 challenge)
-	{
-		for (auto &pc : provers_) pc.first->fold(challenge);
-		round_++;
-	}
-	// :161-172
-	std::vector<std::vector<B128>> finish(PiopTranscript &transcript)
-	{
-		finish_claim_provers(transcript);
-		if (!provers_.empty()) throw SumcheckError("ExpectedFold");
-		return multilinear_evals_;
-	}
-
-private:
-	// :109-120
-	void finish_claim_provers(PiopTranscript &transcript)
-	{
-		while (!provers_.empty() && provers_.front().first->n_vars() == round_) {
-			std::vector<B128> evals = provers_.front().first->finish();
-			provers_.pop_front();
-			transcript.write_scalar_slice(PiopTranscript::Item::MultilinearEvals, evals);
-			multilinear_evals_.push_back(std::move(evals));
-		}
-	}
-	std::deque<std::pair<std::unique_ptr<BivariateSumcheckProver>, B128>> provers_;
-	std::vector<std::vector<B128>> multilinear_evals_;
-	size_t round_ = 0;
 };
 
 // piop/verify.rs:30-98
@@ -224,7 +161,13 @@ inline PiopProveOutput prove_interleaved_fri_sumcheck(ComputeLayer &hal, DeviceB
 	PiopProveOutput out;
 	out.n_provers = sumcheck_provers.size();
 	FRIFolder fri_prover(hal, fri_params, ntt, merkle_prover, codeword, committed);
-	SumcheckBatchProver sumcheck_batch_prover(std::move(sumcheck_provers), batch_coeffs);
+	SumcheckBatchProver<BivariateSumcheckProver> sumcheck_batch_prover(std::move(sumcheck_provers), batch_coeffs);
+	// the evaluations of the provers that finished since the last call, in finishing order (front_loaded.rs:109-120)
+	size_t n_written = 0;
+	auto write_finished = [&] {
+		for (const auto &evals = sumcheck_batch_prover.multilinear_evals(); n_written < evals.size(); n_written++)
+			out.transcript.write_scalar_slice(PiopTranscript::Item::MultilinearEvals, evals[n_written]);
+	};
 	const bool prof = AbiProf::on(); // BNH_PROF=1: wall time of the three steps of a round, summed (diagnostic)
 	auto now = [] { return std::chrono::steady_clock::now(); };
 	auto ns = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -232,7 +175,9 @@ inline PiopProveOutput prove_interleaved_fri_sumcheck(ComputeLayer &hal, DeviceB
 	};
 	for (size_t round = 0; round < n_rounds; round++) {
 		const auto t0 = prof ? now() : std::chrono::steady_clock::time_point{};
-		sumcheck_batch_prover.send_round_proof(out.transcript);
+		const std::vector<B128> round_proof = sumcheck_batch_prover.round_proof();
+		write_finished();
+		out.transcript.write_scalar_slice(PiopTranscript::Item::RoundProof, round_proof);
 		const auto t1 = prof ? now() : t0;
 		const B128 challenge = challenges[round];
 		sumcheck_batch_prover.receive_challenge(challenge);
@@ -245,7 +190,8 @@ inline PiopProveOutput prove_interleaved_fri_sumcheck(ComputeLayer &hal, DeviceB
 			out.phase_ns[2] += ns(t2, now());
 		}
 	}
-	out.multilinear_evals = sumcheck_batch_prover.finish(out.transcript);
+	out.multilinear_evals = sumcheck_batch_prover.finish();
+	write_finished();
 	// fri_prover.finish_proof (fri/prove.rs:484-520): the terminate codeword goes to the transcript; the query phase (index sampling,
 	// openings) is the query prover's and is covered by tests/test_gpu_fri.py
 	auto fin = fri_prover.finalize();

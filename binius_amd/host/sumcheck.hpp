@@ -5,8 +5,11 @@
 //   calculate_round_evals          crates/core/src/protocols/sumcheck/v3/bivariate_product.rs:303-408
 //   (with eq_ind)                  crates/core/src/protocols/sumcheck/v3/bivariate_mlecheck.rs:391-520
 //   round coeffs from evals        v3/bivariate_product.rs:410-424
+//   BivariateRoundCore             what the three provers below share: the sum / coefficient state, the fold of the
+//                                  multilinears, the copy-out of the final evaluations
 //   BivariateSumcheckProver        v3/bivariate_product.rs:27-254  (execute / fold / finish)
 //   BivariateMLEcheckProver        v3/bivariate_mlecheck.rs:27-389  (execute / fold / finish, fold_eq_ind)
+//   WeightedMLEcheckProver         the same transcript with the indicator carried inside one factor of every product
 //   evaluate_univariate            crates/math/src/univariate.rs:264-270
 //
 // Protocol bookkeeping only; every hypercube-sized operation is a HAL call.
@@ -47,7 +50,9 @@ struct IndexCompositionBivariate {
 
 namespace ops {
 // eq_ind_partial_eval (ops.rs:26-50)
-inline FSliceMut eq_ind_partial_eval(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, const std::vector<B128> &point)
+// expand_empty = false: with no coordinates the expansion is the single ONE the fill wrote, and the expansion is not called
+// (a caller that counts its device calls)
+inline FSliceMut eq_ind_partial_eval(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, const std::vector<B128> &point, bool expand_empty = true)
 {
 	const size_t n_vars = point.size();
 	FSliceMut out = dev_alloc.alloc((size_t)1 << n_vars);
@@ -55,10 +60,11 @@ inline FSliceMut eq_ind_partial_eval(ComputeLayer &hal, DeviceBumpAllocator &dev
 		FSliceMut dev_val = ComputeMemory::slice_power_of_two_mut(out, 1);
 		hal.fill(dev_val, B128::ONE());
 	}
-	hal.execute([&](ComputeLayerExecutor &exec) {
-		exec.tensor_expand(0, point, out);
-		return std::vector<B128>{};
-	});
+	if (n_vars || expand_empty)
+		hal.execute([&](ComputeLayerExecutor &exec) {
+			exec.tensor_expand(0, point, out);
+			return std::vector<B128>{};
+		});
 	return out;
 }
 } // namespace ops
@@ -127,44 +133,90 @@ public:
 	using std::logic_error::logic_error;
 };
 
-// BivariateSumcheckProver (v3/bivariate_product.rs:27-254); evaluation order High-to-Low.
-class BivariateSumcheckProver {
+// eq(x, y): the 2-variate multilinear indicating x == y (field/src/util.rs:72-81); characteristic 2
+inline B128 eq(B128 x, B128 y) { return x + y + B128::ONE(); }
+
+// The host-side expansion of the equality indicator: eq(r)[y] = prod_k (y_k ? r_k : 1 + r_k), bit k of y with r[k]
+inline std::vector<B128> eq_expand(const B128 *r, size_t b)
+{
+	std::vector<B128> eq{B128::ONE()};
+	for (size_t k = 0; k < b; k++) {
+		const size_t n = eq.size();
+		eq.resize(2 * n);
+		for (size_t y = 0; y < n; y++) {
+			const B128 hi = eq[y] * r[k];
+			eq[n + y] = hi;
+			eq[y] = eq[y] + hi;
+		}
+	}
+	return eq;
+}
+
+// The MLE-check round (v3/bivariate_mlecheck.rs:273-318, 375-389) from (sum, y_1, y_inf), the round's indicator coordinate
+// alpha and the indicator's prefix evaluation: `prime` = the coefficients of v', returned = those of v = eq(X, alpha) v' prefix
+inline std::vector<B128> mlecheck_round_coeffs(B128 sum, const std::vector<B128> &round_evals, B128 alpha, B128 prefix, std::vector<B128> &prime)
+{
+	const B128 y_1 = round_evals[0], y_inf = round_evals[1];
+	const B128 y_0 = (sum - y_1 * alpha) * (B128::ONE() - alpha).invert_or_zero();
+	const B128 c_0 = y_0, c_2 = y_inf, c_1 = y_1 - c_0 - c_2;
+	prime = {c_0, c_1, c_2};
+	// v' -> v: eq(X, alpha) = (1 - alpha) + (2 alpha - 1) X   (:303-313)
+	const B128 k0 = B128::ONE() - alpha, k1 = alpha.dbl() - B128::ONE();
+	std::vector<B128> coeffs(4, B128::ZERO());
+	for (size_t d = 0; d < 3; d++) {
+		coeffs[d] = coeffs[d] + prime[d] * k0;
+		coeffs[d + 1] = coeffs[d + 1] + prime[d] * k1;
+	}
+	for (auto &c : coeffs) c = c * prefix;
+	return coeffs;
+}
+
+// What the bivariate provers share: the multilinears (read-only until their first fold), the compiled compositions, and the
+// state machine InitialSums -> Coeffs -> BatchedSum -> Coeffs ... of v3/bivariate_product.rs:27-254.
+class BivariateRoundCore {
 public:
-	BivariateSumcheckProver(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, size_t n_vars,
-	                        const std::vector<IndexCompositionBivariate> &compositions, const std::vector<B128> &sums,
-	                        const std::vector<FSlice> &multilins)
-	    : hal_(hal), dev_alloc_(dev_alloc), host_alloc_(host_alloc), n_vars_initial_(n_vars), n_vars_remaining_(n_vars)
+	struct Multilin {
+		bool pre_fold;
+		FSliceMut evals;
+	};
+	size_t n_vars() const { return n_vars_initial_; }
+	const std::vector<Multilin> &multilins() const { return multilins_; }
+
+protected:
+	BivariateRoundCore(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, size_t n_vars, const std::vector<B128> &sums,
+	                   const std::vector<FSlice> &multilins)
+	    : hal_(hal), dev_alloc_(dev_alloc), host_alloc_(host_alloc), n_vars_initial_(n_vars), n_vars_remaining_(n_vars), sums_or_coeffs_(sums)
 	{
 		for (const auto &ml : multilins)
 			if (ml.len() != (size_t)1 << n_vars) throw SumcheckError("NumberOfVariablesMismatch");
-		for (const auto &ml : multilins) multilins_.push_back(Multilin{true, FSliceMut{const_cast<void *>(ml.ptr), ml.len_}});
-		for (const auto &c : compositions) evaluators_.push_back(hal.compile_expr(c.expression()));
-		state_ = InitialSums;
-		sums_or_coeffs_ = sums;
+		for (const auto &ml : multilins) multilins_.push_back(Multilin{true, ComputeMemory::to_mut(ml)});
 	}
-	static size_t required_host_memory(size_t n_multilinears) { return n_multilinears; }
-	static size_t required_device_memory(size_t n_multilinears, size_t n_vars) { return n_multilinears * ((size_t)1 << (n_vars - 1)); }
-	size_t n_vars() const { return n_vars_initial_; }
 
-	std::vector<B128> execute(B128 batch_coeff)
+	// the sum this round's polynomial has to meet
+	B128 batched_sum(B128 batch_coeff) const
 	{
-		std::vector<FSlice> mls;
-		for (const auto &m : multilins_) mls.push_back(FSlice{m.evals.ptr, m.evals.len_});
-		const std::vector<B128> round_evals = calculate_round_evals(hal_, n_vars_remaining_, batch_coeff, mls, evaluators_);
-		B128 batched_sum;
 		switch (state_) {
 		case Coeffs: throw SumcheckError("ExpectedFold");
-		case InitialSums: batched_sum = evaluate_univariate(sums_or_coeffs_, batch_coeff); break;
-		default: batched_sum = batched_sum_; break;
+		case InitialSums: return evaluate_univariate(sums_or_coeffs_, batch_coeff);
+		default: return batched_sum_;
 		}
-		std::vector<B128> round_coeffs = calculate_round_coeffs_from_evals(batched_sum, round_evals);
+	}
+	// {y_1, y_inf} of the round over the current multilinears
+	std::vector<B128> round_evals(B128 batch_coeff, const FSlice *eq_ind = nullptr) const
+	{
+		std::vector<FSlice> mls;
+		for (const auto &m : multilins_) mls.push_back(ComputeMemory::as_const(m.evals));
+		return calculate_round_evals(hal_, n_vars_remaining_, batch_coeff, mls, evaluators_, eq_ind);
+	}
+	void set_coeffs(std::vector<B128> coeffs)
+	{
 		state_ = Coeffs;
-		sums_or_coeffs_ = round_coeffs;
-		if (evaluators_.empty()) return {};
-		return round_coeffs;
+		sums_or_coeffs_ = std::move(coeffs);
 	}
 
-	void fold(B128 challenge)
+	// One round's fold: the next sum, then every multilinear -- its first fold goes to a fresh buffer that starts as a copy of
+	// the lower half -- in ONE map of extrapolate_line; scaled[i]: extrapolate_line_scaled with hi_scale for multilinear i
+	void fold_multilinears(B128 challenge, const std::vector<bool> *scaled = nullptr, B128 hi_scale = B128::ONE())
 	{
 		if (n_vars_remaining_ == 0) throw SumcheckError("ExpectedFinish");
 		if (state_ != Coeffs) throw SumcheckError("ExpectedExecution");
@@ -173,199 +225,143 @@ public:
 		struct Args {
 			FSliceMut evals_0;
 			FSlice evals_1;
+			bool scaled;
 		};
 		std::vector<Args> prepared;
-		for (auto &m : multilins_) {
-			if (m.pre_fold) {
-				auto halves = ComputeMemory::split_half(FSlice{m.evals.ptr, m.evals.len_});
+		for (size_t i = 0; i < multilins_.size(); i++) {
+			auto halves = ComputeMemory::split_half_mut(multilins_[i].evals);
+			if (multilins_[i].pre_fold) {
 				// allocate a new buffer for the folded evaluations and copy in evals_0
-				FSliceMut folded = dev_alloc_.alloc((size_t)1 << (n_vars_remaining_ - 1));
-				hal_.copy_d2d(halves.first, folded);
-				prepared.push_back(Args{folded, halves.second});
-			} else {
-				auto halves = ComputeMemory::split_half_mut(m.evals);
-				prepared.push_back(Args{halves.first, ComputeMemory::to_const(halves.second)});
+				FSliceMut folded = dev_alloc_.alloc(halves.first.len());
+				hal_.copy_d2d(ComputeMemory::to_const(halves.first), folded);
+				halves.first = folded;
 			}
+			prepared.push_back(Args{halves.first, ComputeMemory::to_const(halves.second), scaled && (*scaled)[i]});
 		}
 		hal_.execute([&](ComputeLayerExecutor &exec) {
-			auto folded = exec.map(prepared.begin(), prepared.end(), [&](ComputeLayerExecutor &e, Args &a) {
-				e.extrapolate_line(a.evals_0, a.evals_1, challenge);
+			multilins_ = exec.map(prepared.begin(), prepared.end(), [&](ComputeLayerExecutor &e, Args &a) {
+				if (a.scaled)
+					e.extrapolate_line_scaled(a.evals_0, a.evals_1, challenge, hi_scale);
+				else
+					e.extrapolate_line(a.evals_0, a.evals_1, challenge);
 				return Multilin{false, a.evals_0};
 			});
-			multilins_ = folded;
 			return std::vector<B128>{};
 		});
 		n_vars_remaining_ -= 1;
 	}
 
-	std::vector<B128> finish()
+	// the single element every multilinear has come down to
+	std::vector<B128> final_evals()
 	{
 		if (state_ == Coeffs) throw SumcheckError("ExpectedFold");
 		if (n_vars_remaining_ != 0) throw SumcheckError("ExpectedExecution");
 		HostSliceMut buffer = host_alloc_.alloc(multilins_.size());
-		for (size_t i = 0; i < multilins_.size(); i++)
-			hal_.copy_d2h(FSlice{multilins_[i].evals.ptr, multilins_[i].evals.len_}, &buffer[i], 1);
+		for (size_t i = 0; i < multilins_.size(); i++) hal_.copy_d2h(ComputeMemory::as_const(multilins_[i].evals), &buffer[i], 1);
 		return std::vector<B128>(buffer.ptr, buffer.ptr + multilins_.size());
 	}
 
-	struct Multilin {
-		bool pre_fold;
-		FSliceMut evals;
-	};
-	const std::vector<Multilin> &multilins() const { return multilins_; }
-
-private:
-	enum State { Coeffs, InitialSums, BatchedSum };
 	ComputeLayer &hal_;
 	DeviceBumpAllocator &dev_alloc_;
 	HostBumpAllocator &host_alloc_;
 	size_t n_vars_initial_, n_vars_remaining_;
 	std::vector<Multilin> multilins_;
 	std::vector<ExprEval> evaluators_;
-	State state_;
+
+private:
+	enum State { Coeffs, InitialSums, BatchedSum } state_ = InitialSums;
 	std::vector<B128> sums_or_coeffs_;
 	B128 batched_sum_;
 };
 
-// eq(x, y): the 2-variate multilinear indicating x == y (field/src/util.rs:72-81); characteristic 2
-inline B128 eq(B128 x, B128 y) { return x + y + B128::ONE(); }
+// BivariateSumcheckProver (v3/bivariate_product.rs:27-254); evaluation order High-to-Low.
+class BivariateSumcheckProver : public BivariateRoundCore {
+public:
+	BivariateSumcheckProver(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, size_t n_vars,
+	                        const std::vector<IndexCompositionBivariate> &compositions, const std::vector<B128> &sums,
+	                        const std::vector<FSlice> &multilins)
+	    : BivariateRoundCore(hal, dev_alloc, host_alloc, n_vars, sums, multilins)
+	{
+		for (const auto &c : compositions) evaluators_.push_back(hal.compile_expr(c.expression()));
+	}
+	static size_t required_host_memory(size_t n_multilinears) { return n_multilinears; }
+	static size_t required_device_memory(size_t n_multilinears, size_t n_vars) { return n_multilinears * ((size_t)1 << (n_vars - 1)); }
+
+	std::vector<B128> execute(B128 batch_coeff)
+	{
+		const B128 sum = batched_sum(batch_coeff);
+		const std::vector<B128> round_coeffs = calculate_round_coeffs_from_evals(sum, round_evals(batch_coeff));
+		set_coeffs(round_coeffs);
+		if (evaluators_.empty()) return {};
+		return round_coeffs;
+	}
+	void fold(B128 challenge) { fold_multilinears(challenge); }
+	std::vector<B128> finish() { return final_evals(); }
+};
 
 // BivariateMLEcheckProver (v3/bivariate_mlecheck.rs:27-372): the eq-indicator sumcheck for bivariate
 // products.  eq_ind_partial_evals = tensor expansion of eq_ind_challenges[0 .. n_vars-1).
-class BivariateMLEcheckProver {
+class BivariateMLEcheckProver : public BivariateRoundCore {
 public:
 	BivariateMLEcheckProver(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, size_t n_vars,
 	                        const std::vector<IndexCompositionBivariate> &compositions, const std::vector<B128> &sums,
 	                        const std::vector<FSlice> &multilins, FSlice eq_ind_partial_evals, std::vector<B128> eq_ind_challenges)
-	    : hal_(hal), dev_alloc_(dev_alloc), host_alloc_(host_alloc), n_vars_initial_(n_vars), n_vars_remaining_(n_vars),
-	      eq_ind_challenges_(std::move(eq_ind_challenges))
+	    : BivariateRoundCore(hal, dev_alloc, host_alloc, n_vars, sums, multilins), eq_ind_challenges_(std::move(eq_ind_challenges))
 	{
-		for (const auto &ml : multilins)
-			if (ml.len() != (size_t)1 << n_vars) throw SumcheckError("NumberOfVariablesMismatch");
 		// only one value of the expanded indicator is used per 1-variable subcube (:97-101)
 		if (eq_ind_partial_evals.len() != (size_t)1 << (n_vars ? n_vars - 1 : 0)) throw SumcheckError("IncorrectEqIndPartialEvalsSize");
-		for (const auto &ml : multilins) multilins_.push_back(Multilin{true, FSliceMut{const_cast<void *>(ml.ptr), ml.len_}});
 		const size_t m = multilins.size();
 		for (const auto &c : compositions) {
 			ArithCircuit prod_expr = c.expression();
 			prod_expr *= ArithCircuit::var(m); // add eq_ind (:399-407)
 			evaluators_.push_back(hal.compile_expr(prod_expr));
 		}
-		state_ = InitialSums;
-		sums_or_coeffs_ = sums;
-		eq_ind_ = Multilin{true, FSliceMut{const_cast<void *>(eq_ind_partial_evals.ptr), eq_ind_partial_evals.len_}};
+		eq_ind_ = Multilin{true, ComputeMemory::to_mut(eq_ind_partial_evals)};
 	}
 	static size_t required_host_memory(size_t n_multilinears) { return n_multilinears + 1; }
 	static size_t required_device_memory(size_t n_multilinears, size_t n_vars, bool with_eq_ind_partial_evals)
 	{
 		return (n_multilinears + (with_eq_ind_partial_evals ? 0 : 1)) * ((size_t)1 << (n_vars - 1));
 	}
-	size_t n_vars() const { return n_vars_initial_; }
 
 	// round polynomial of degree 3 (:273-318)
 	std::vector<B128> execute(B128 batch_coeff)
 	{
-		std::vector<FSlice> mls;
-		for (const auto &m : multilins_) mls.push_back(FSlice{m.evals.ptr, m.evals.len_});
-		const FSlice eq{eq_ind_.evals.ptr, eq_ind_.evals.len_};
-		const std::vector<B128> round_evals = calculate_round_evals(hal_, n_vars_remaining_, batch_coeff, mls, evaluators_, &eq);
-		B128 batched_sum;
-		switch (state_) {
-		case Coeffs: throw SumcheckError("ExpectedFold");
-		case InitialSums: batched_sum = evaluate_univariate(sums_or_coeffs_, batch_coeff); break;
-		default: batched_sum = batched_sum_; break;
-		}
-		const B128 alpha = eq_ind_challenges_[n_vars_remaining_ - 1];
-		// calculate_round_coeffs_from_evals (:375-389)
-		const B128 y_1 = round_evals[0], y_inf = round_evals[1];
-		const B128 y_0 = (batched_sum - y_1 * alpha) * (B128::ONE() - alpha).invert_or_zero();
-		const B128 c_0 = y_0, c_2 = y_inf, c_1 = y_1 - c_0 - c_2;
-		const std::vector<B128> prime{c_0, c_1, c_2};
-		state_ = Coeffs;
-		sums_or_coeffs_ = prime;
-		// v' -> v: eq(X, alpha) = (1 - alpha) + (2 alpha - 1) X   (:303-313)
-		const B128 k0 = B128::ONE() - alpha, k1 = alpha.dbl() - B128::ONE();
-		std::vector<B128> coeffs(4, B128::ZERO());
-		for (size_t d = 0; d < 3; d++) {
-			coeffs[d] = coeffs[d] + prime[d] * k0;
-			coeffs[d + 1] = coeffs[d + 1] + prime[d] * k1;
-		}
-		for (auto &c : coeffs) c = c * eq_ind_prefix_eval_;
+		const B128 sum = batched_sum(batch_coeff);
+		const FSlice eq = ComputeMemory::as_const(eq_ind_.evals);
+		std::vector<B128> prime;
+		const std::vector<B128> coeffs =
+		    mlecheck_round_coeffs(sum, round_evals(batch_coeff, &eq), eq_ind_challenges_[n_vars_remaining_ - 1], eq_ind_prefix_eval_, prime);
+		set_coeffs(prime);
 		return coeffs;
 	}
 
 	void fold(B128 challenge)
 	{
-		if (n_vars_remaining_ == 0) throw SumcheckError("ExpectedFinish");
-		if (state_ != Coeffs) throw SumcheckError("ExpectedExecution");
-		batched_sum_ = evaluate_univariate(sums_or_coeffs_, challenge);
-		state_ = BatchedSum;
-		eq_ind_prefix_eval_ = eq_ind_prefix_eval_ * eq(eq_ind_challenges_[n_vars_remaining_ - 1], challenge); // (:120-123)
-		fold_multilinears(challenge);
-		if (n_vars_remaining_ - 1 != 0) fold_eq_ind();
-		n_vars_remaining_ -= 1;
+		const size_t n = n_vars_remaining_;
+		fold_multilinears(challenge); // (:145-193)
+		eq_ind_prefix_eval_ = eq_ind_prefix_eval_ * eq(eq_ind_challenges_[n - 1], challenge); // (:120-123)
+		if (n_vars_remaining_ != 0) fold_eq_ind();
 	}
 
 	// final evaluations followed by eq_ind_prefix_eval (:348-372)
 	std::vector<B128> finish()
 	{
-		if (state_ == Coeffs) throw SumcheckError("ExpectedFold");
-		if (n_vars_remaining_ != 0) throw SumcheckError("ExpectedExecution");
-		HostSliceMut buffer = host_alloc_.alloc(multilins_.size());
-		for (size_t i = 0; i < multilins_.size(); i++)
-			hal_.copy_d2h(FSlice{multilins_[i].evals.ptr, multilins_[i].evals.len_}, &buffer[i], 1);
-		std::vector<B128> res(buffer.ptr, buffer.ptr + multilins_.size());
+		std::vector<B128> res = final_evals();
 		res.push_back(eq_ind_prefix_eval_);
 		return res;
 	}
 
 private:
-	struct Multilin {
-		bool pre_fold;
-		FSliceMut evals;
-	};
-	struct FoldArgs {
-		FSliceMut evals_0;
-		FSlice evals_1;
-	};
-
-	void fold_multilinears(B128 challenge) // (:145-193)
-	{
-		std::vector<FoldArgs> prepared;
-		for (auto &m : multilins_) {
-			if (m.pre_fold) {
-				auto halves = ComputeMemory::split_half(FSlice{m.evals.ptr, m.evals.len_});
-				FSliceMut folded = dev_alloc_.alloc((size_t)1 << (n_vars_remaining_ - 1));
-				hal_.copy_d2d(halves.first, folded);
-				prepared.push_back(FoldArgs{folded, halves.second});
-			} else {
-				auto halves = ComputeMemory::split_half_mut(m.evals);
-				prepared.push_back(FoldArgs{halves.first, ComputeMemory::to_const(halves.second)});
-			}
-		}
-		hal_.execute([&](ComputeLayerExecutor &exec) {
-			multilins_ = exec.map(prepared.begin(), prepared.end(), [&](ComputeLayerExecutor &e, FoldArgs &a) {
-				e.extrapolate_line(a.evals_0, a.evals_1, challenge);
-				return Multilin{false, a.evals_0};
-			});
-			return std::vector<B128>{};
-		});
-	}
-
 	void fold_eq_ind() // (:195-254): map_kernels { add_assign(evals_1 -> evals_0) }
 	{
-		const size_t split_n_vars = n_vars_remaining_ - 2;
-		FSliceMut evals_0;
-		FSlice evals_1;
+		const size_t split_n_vars = n_vars_remaining_ - 1;
+		auto halves = ComputeMemory::split_half_mut(eq_ind_.evals);
+		FSliceMut evals_0 = halves.first;
+		const FSlice evals_1 = ComputeMemory::to_const(halves.second);
 		if (eq_ind_.pre_fold) {
-			auto halves = ComputeMemory::split_half(FSlice{eq_ind_.evals.ptr, eq_ind_.evals.len_});
 			evals_0 = dev_alloc_.alloc(halves.first.len());
-			hal_.copy_d2d(halves.first, evals_0);
-			evals_1 = halves.second;
-		} else {
-			auto halves = ComputeMemory::split_half_mut(eq_ind_.evals);
-			evals_0 = halves.first;
-			evals_1 = ComputeMemory::to_const(halves.second);
+			hal_.copy_d2d(ComputeMemory::to_const(halves.first), evals_0);
 		}
 		std::vector<KernelMemMap> kernel_mappings{KernelMemMap::chunked_mut(evals_0, 0), KernelMemMap::chunked(evals_1, 0)};
 		hal_.execute([&](ComputeLayerExecutor &exec) {
@@ -380,16 +376,6 @@ private:
 		eq_ind_ = Multilin{false, evals_0};
 	}
 
-	enum State { Coeffs, InitialSums, BatchedSum };
-	ComputeLayer &hal_;
-	DeviceBumpAllocator &dev_alloc_;
-	HostBumpAllocator &host_alloc_;
-	size_t n_vars_initial_, n_vars_remaining_;
-	std::vector<Multilin> multilins_;
-	std::vector<ExprEval> evaluators_;
-	State state_;
-	std::vector<B128> sums_or_coeffs_;
-	B128 batched_sum_;
 	B128 eq_ind_prefix_eval_ = B128::ONE();
 	Multilin eq_ind_{};
 	std::vector<B128> eq_ind_challenges_;
@@ -414,7 +400,7 @@ private:
 // Applicable when the compositions' graph has a proper 2-colouring (every product has exactly one weighted factor)
 // and no indicator coordinate is 0 or 1 (zeta and 1 - zeta are inverted); the caller falls back to
 // BivariateMLEcheckProver otherwise.  Device memory: 2^n per weighted multilinear, 2^(n-1) per other one.
-class WeightedMLEcheckProver {
+class WeightedMLEcheckProver : public BivariateRoundCore {
 public:
 	// colouring[i] = true: multilinear i carries the indicator.  Empty result = no proper colouring.
 	static std::vector<bool> colouring(size_t n_multilinears, const std::vector<IndexCompositionBivariate> &compositions)
@@ -470,31 +456,21 @@ public:
 	                       const std::vector<IndexCompositionBivariate> &compositions, const std::vector<B128> &sums,
 	                       const std::vector<FSlice> &multilins, FSlice eq_ind_partial_evals, std::vector<B128> eq_ind_challenges,
 	                       std::vector<bool> weighted)
-	    : hal_(hal), dev_alloc_(dev_alloc), host_alloc_(host_alloc), n_vars_initial_(n_vars), n_vars_remaining_(n_vars),
-	      eq_ind_challenges_(std::move(eq_ind_challenges)), weighted_(std::move(weighted))
+	    : BivariateRoundCore(hal, dev_alloc, host_alloc, n_vars, sums, multilins), eq_ind_challenges_(std::move(eq_ind_challenges)),
+	      weighted_(std::move(weighted))
 	{
-		for (const auto &ml : multilins)
-			if (ml.len() != (size_t)1 << n_vars) throw SumcheckError("NumberOfVariablesMismatch");
 		if (eq_ind_partial_evals.len() != (size_t)1 << (n_vars ? n_vars - 1 : 0)) throw SumcheckError("IncorrectEqIndPartialEvalsSize");
 		if (weighted_.size() != multilins.size()) throw SumcheckError("colouring does not match the multilinears");
 		for (const auto &c : compositions) {
 			if (weighted_[c.indices[0]] == weighted_[c.indices[1]]) throw SumcheckError("composition without exactly one weighted factor");
 			evaluators_.push_back(hal.compile_expr(c.expression()));
 		}
-		state_ = InitialSums;
-		sums_or_coeffs_ = sums;
-		// S_0 = a * eq_0 on both halves of every weighted multilinear
+		// S_0 = a * eq_0 on both halves of every weighted multilinear (n_vars = 0: a single value, no indicator variables,
+		// nothing to weight)
 		const ExprEval prod = hal.compile_expr(ArithCircuit::var(0) * ArithCircuit::var(1));
 		const size_t half = eq_ind_partial_evals.len();
-		for (size_t i = 0; i < multilins.size(); i++) {
-			if (!weighted_[i]) {
-				multilins_.push_back(Multilin{true, FSliceMut{const_cast<void *>(multilins[i].ptr), multilins[i].len_}});
-				continue;
-			}
-			if (n_vars == 0) { // a single value, no indicator variables: nothing to weight
-				multilins_.push_back(Multilin{true, FSliceMut{const_cast<void *>(multilins[i].ptr), multilins[i].len_}});
-				continue;
-			}
+		for (size_t i = 0; i < multilins.size() && n_vars != 0; i++) {
+			if (!weighted_[i]) continue;
 			FSliceMut s = dev_alloc_.alloc(multilins[i].len());
 			auto in = ComputeMemory::split_half(multilins[i]);
 			auto out = ComputeMemory::split_half_mut(s);
@@ -503,91 +479,38 @@ public:
 				exec.compute_composite(SlicesBatch<FSlice>({in.second, eq_ind_partial_evals}, half), out.second, prod);
 				return std::vector<B128>{};
 			});
-			multilins_.push_back(Multilin{false, s}); // our own buffer: folded in place from the first round on
+			multilins_[i] = Multilin{false, s}; // our own buffer: folded in place from the first round on
 		}
 	}
-	size_t n_vars() const { return n_vars_initial_; }
 
 	std::vector<B128> execute(B128 batch_coeff)
 	{
-		std::vector<FSlice> mls;
-		for (const auto &m : multilins_) mls.push_back(FSlice{m.evals.ptr, m.evals.len_});
-		std::vector<B128> round_evals = calculate_round_evals(hal_, n_vars_remaining_, batch_coeff, mls, evaluators_);
+		const B128 sum = batched_sum(batch_coeff);
+		std::vector<B128> evals = round_evals(batch_coeff);
 		const B128 lambda_inv = lambda_.invert_or_zero();
-		for (auto &e : round_evals) e = e * lambda_inv;
-		B128 batched_sum;
-		switch (state_) {
-		case Coeffs: throw SumcheckError("ExpectedFold");
-		case InitialSums: batched_sum = evaluate_univariate(sums_or_coeffs_, batch_coeff); break;
-		default: batched_sum = batched_sum_; break;
-		}
-		// from here on: BivariateMLEcheckProver::execute (:273-318) unchanged
-		const B128 alpha = eq_ind_challenges_[n_vars_remaining_ - 1];
-		const B128 y_1 = round_evals[0], y_inf = round_evals[1];
-		const B128 y_0 = (batched_sum - y_1 * alpha) * (B128::ONE() - alpha).invert_or_zero();
-		const B128 c_0 = y_0, c_2 = y_inf, c_1 = y_1 - c_0 - c_2;
-		const std::vector<B128> prime{c_0, c_1, c_2};
-		state_ = Coeffs;
-		sums_or_coeffs_ = prime;
-		const B128 k0 = B128::ONE() - alpha, k1 = alpha.dbl() - B128::ONE();
-		std::vector<B128> coeffs(4, B128::ZERO());
-		for (size_t d = 0; d < 3; d++) {
-			coeffs[d] = coeffs[d] + prime[d] * k0;
-			coeffs[d + 1] = coeffs[d + 1] + prime[d] * k1;
-		}
-		for (auto &c : coeffs) c = c * eq_ind_prefix_eval_;
+		for (auto &e : evals) e = e * lambda_inv;
+		std::vector<B128> prime;
+		const std::vector<B128> coeffs = mlecheck_round_coeffs(sum, evals, eq_ind_challenges_[n_vars_remaining_ - 1], eq_ind_prefix_eval_, prime);
+		set_coeffs(prime);
 		return coeffs;
 	}
 
 	void fold(B128 challenge)
 	{
-		if (n_vars_remaining_ == 0) throw SumcheckError("ExpectedFinish");
-		if (state_ != Coeffs) throw SumcheckError("ExpectedExecution");
-		batched_sum_ = evaluate_univariate(sums_or_coeffs_, challenge);
-		state_ = BatchedSum;
-		eq_ind_prefix_eval_ = eq_ind_prefix_eval_ * eq(eq_ind_challenges_[n_vars_remaining_ - 1], challenge);
+		const size_t n = n_vars_remaining_;
 		// the variable that splits the folded arrays becomes the next round variable: level its two halves
-		const bool scale = n_vars_remaining_ >= 2;
-		B128 hi_scale = B128::ONE();
-		if (scale) {
-			const B128 zeta = eq_ind_challenges_[n_vars_remaining_ - 2];
-			hi_scale = (B128::ONE() - zeta) * zeta.invert_or_zero();
-			lambda_ = lambda_ * (B128::ONE() - zeta);
-		}
-		std::vector<FoldArgs> prepared;
-		for (size_t i = 0; i < multilins_.size(); i++) {
-			auto &m = multilins_[i];
-			if (m.pre_fold) {
-				auto halves = ComputeMemory::split_half(FSlice{m.evals.ptr, m.evals.len_});
-				FSliceMut folded = dev_alloc_.alloc((size_t)1 << (n_vars_remaining_ - 1));
-				hal_.copy_d2d(halves.first, folded);
-				prepared.push_back(FoldArgs{folded, halves.second, scale && weighted_[i]});
-			} else {
-				auto halves = ComputeMemory::split_half_mut(m.evals);
-				prepared.push_back(FoldArgs{halves.first, ComputeMemory::to_const(halves.second), scale && weighted_[i]});
-			}
-		}
-		hal_.execute([&](ComputeLayerExecutor &exec) {
-			multilins_ = exec.map(prepared.begin(), prepared.end(), [&](ComputeLayerExecutor &e, FoldArgs &a) {
-				if (a.scaled)
-					e.extrapolate_line_scaled(a.evals_0, a.evals_1, challenge, hi_scale);
-				else
-					e.extrapolate_line(a.evals_0, a.evals_1, challenge);
-				return Multilin{false, a.evals_0};
-			});
-			return std::vector<B128>{};
-		});
-		n_vars_remaining_ -= 1;
+		const B128 zeta = n >= 2 ? eq_ind_challenges_[n - 2] : B128::ZERO();
+		if (n >= 2)
+			fold_multilinears(challenge, &weighted_, (B128::ONE() - zeta) * zeta.invert_or_zero());
+		else
+			fold_multilinears(challenge);
+		eq_ind_prefix_eval_ = eq_ind_prefix_eval_ * eq(eq_ind_challenges_[n - 1], challenge);
+		if (n >= 2) lambda_ = lambda_ * (B128::ONE() - zeta);
 	}
 
 	std::vector<B128> finish()
 	{
-		if (state_ == Coeffs) throw SumcheckError("ExpectedFold");
-		if (n_vars_remaining_ != 0) throw SumcheckError("ExpectedExecution");
-		HostSliceMut buffer = host_alloc_.alloc(multilins_.size());
-		for (size_t i = 0; i < multilins_.size(); i++)
-			hal_.copy_d2h(FSlice{multilins_[i].evals.ptr, multilins_[i].evals.len_}, &buffer[i], 1);
-		std::vector<B128> res(buffer.ptr, buffer.ptr + multilins_.size());
+		std::vector<B128> res = final_evals();
 		const B128 lambda_inv = lambda_.invert_or_zero();
 		for (size_t i = 0; i < res.size(); i++)
 			if (weighted_[i]) res[i] = res[i] * lambda_inv;
@@ -596,25 +519,6 @@ public:
 	}
 
 private:
-	struct Multilin {
-		bool pre_fold;
-		FSliceMut evals;
-	};
-	struct FoldArgs {
-		FSliceMut evals_0;
-		FSlice evals_1;
-		bool scaled;
-	};
-	enum State { Coeffs, InitialSums, BatchedSum };
-	ComputeLayer &hal_;
-	DeviceBumpAllocator &dev_alloc_;
-	HostBumpAllocator &host_alloc_;
-	size_t n_vars_initial_, n_vars_remaining_;
-	std::vector<Multilin> multilins_;
-	std::vector<ExprEval> evaluators_;
-	State state_;
-	std::vector<B128> sums_or_coeffs_;
-	B128 batched_sum_;
 	B128 eq_ind_prefix_eval_ = B128::ONE();
 	B128 lambda_ = B128::ONE();
 	std::vector<B128> eq_ind_challenges_;

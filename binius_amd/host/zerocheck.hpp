@@ -9,10 +9,10 @@
 //   ZerocheckUnivariateEvalsOutput::fold   univariate.rs:139-193   host: the Lagrange coefficients of the subcube and of the whole
 //                                                             domain at the univariate challenge, the claimed sums
 //   fold_univariate_round      prove/zerocheck.rs:384-470    ONE bn_univariate_fold_batch over the columns of ALL tables, then one
-//                                                             EqIndSumcheckProver (eq_ind.hpp) per table over max(n, k) - k variables;
+//                                                             EqIndPointProver (eq_ind.hpp) per table over max(n, k) - k variables;
 //                                                             its indicator table is the expansion of all its challenges but the
 //                                                             last (fold_partial_eq_ind, High-to-Low, of the univariate round's table)
-//   front_loaded::BatchProver::new_prebatched   prove/front_loaded.rs:78-198   every prover starts in round 0, its round polynomial
+//   front_loaded::BatchProver::new_prebatched   prove/front_loaded.rs:78-198   SumcheckBatchProver (batch_prover.hpp): every prover starts in round 0, its round polynomial
 //                                                             times its PRE-sampled coefficient; a prover finishes in the round that
 //                                                             equals its number of variables (with none: at once)
 //   project_to_skipped_variables   prove/zerocheck.rs:472-516   ONE bn_partial_eval_high_batch per table: the original columns at the
@@ -30,6 +30,7 @@
 #pragma once
 #include <chrono>
 
+#include "batch_prover.hpp"
 #include "eq_ind.hpp"
 
 namespace binius_amd {
@@ -112,21 +113,6 @@ inline std::vector<B128> lagrange_evals(size_t n, B128 z)
 	return out;
 }
 
-inline std::vector<B128> eq_expand(const B128 *r, size_t b)
-{
-	std::vector<B128> eq{B128::ONE()};
-	for (size_t i = 0; i < b; i++) {
-		const size_t n = eq.size();
-		eq.resize(2 * n);
-		for (size_t y = 0; y < n; y++) {
-			const B128 hi = eq[y] * r[i];
-			eq[n + y] = hi;
-			eq[y] = eq[y] + hi;
-		}
-	}
-	return eq;
-}
-
 // value i of a packed column of at most 2^11 bits held on the host
 inline uint8_t packed_value(const std::vector<B128> &col, uint32_t level, size_t i)
 {
@@ -135,11 +121,6 @@ inline uint8_t packed_value(const std::vector<B128> &col, uint32_t level, size_t
 }
 
 inline size_t column_elems(size_t n_vars, uint32_t level) { return n_vars + level <= 7 ? 1 : (size_t)1 << (n_vars + level - 7); }
-
-inline double ms_since(std::chrono::steady_clock::time_point t0)
-{
-	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 } // namespace zerocheck_detail
 
@@ -188,8 +169,7 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 		std::vector<std::vector<B128>> host_cols;      // n < k: the padded columns, packed
 		std::vector<B128> challenges;                  // the suffix of the zerocheck challenges (constraint_system/prove.rs:470)
 		std::vector<std::vector<B128>> round_evals;    // per composition, D - 2^k values
-		std::vector<FSliceMut> folded;
-		std::unique_ptr<EqIndSumcheckProver> prover;
+		std::vector<FSlice> folded;
 	};
 	std::vector<Prover> ps(tables.size());
 
@@ -223,10 +203,7 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 			pr.cols.push_back(d.ptr);
 			pr.host_cols.push_back(std::move(padded));
 		}
-		FSliceMut eq = alloc.alloc((size_t)1 << pr.nr);
-		FSliceMut first{eq.ptr, 1};
-		hal.fill(first, B128::ONE());
-		if (pr.nr) check(bn_tensor_expand(hal.raw_ctx(), eq.ptr, eq.len_, 0, reinterpret_cast<const bn_f128 *>(pr.challenges.data()), (uint32_t)pr.nr));
+		const FSliceMut eq = ops::eq_ind_partial_eval(hal, alloc, pr.challenges, false);
 		std::vector<bn_hal_multilinear> mls;
 		for (size_t c = 0; c < t.columns.size(); c++) {
 			bn_hal_multilinear m{};
@@ -258,7 +235,7 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 			scale = scale * batch_coeffs[p];
 		}
 	}
-	out.phase_ms[Out::Univariate] = ms_since(t0);
+	out.phase_ms[Out::Univariate] = elapsed_ms(t0);
 
 	// ---- ZerocheckUnivariateEvalsOutput::fold and fold_univariate_round
 	t0 = std::chrono::steady_clock::now();
@@ -268,63 +245,33 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 	for (size_t p = 0; p < tables.size(); p++)
 		for (size_t c = 0; c < tables[p].columns.size(); c++) {
 			FSliceMut o = alloc.alloc((size_t)1 << ps[p].nr);
-			ps[p].folded.push_back(o);
+			ps[p].folded.push_back(ComputeMemory::as_const(o));
 			fold_cols.push_back(bn_pe_column{ps[p].cols[c], tables[p].columns[c].tower_level, (uint32_t)ps[p].n_eff});
 			fold_outs.push_back(o.ptr);
 		}
 	check(bn_univariate_fold_batch(hal.raw_ctx(), fold_cols.data(), (uint32_t)fold_cols.size(), (uint32_t)k, reinterpret_cast<const bn_f128 *>(l_sub.data()), fold_outs.data()));
 	out.phase_calls[Out::Fold] += fold_cols.empty() ? 0 : 1;
-	out.phase_ms[Out::Fold] = ms_since(t0);
+	out.phase_ms[Out::Fold] = elapsed_ms(t0);
 
 	// ---- the multilinear rounds: front-loaded, pre-batched
 	t0 = std::chrono::steady_clock::now();
-	out.final_evals.resize(tables.size());
+	std::vector<std::unique_ptr<EqIndPointProver>> provers;
 	for (size_t p = 0; p < tables.size(); p++) {
 		Prover &pr = ps[p];
-		if (pr.nr == 0) continue;
 		std::vector<B128> sums;
 		for (const auto &evals : pr.round_evals) {
 			B128 s = B128::ZERO();
 			for (size_t j = 0; j < D - K; j++) s += evals[j] * l_full[K + j];
 			sums.push_back(s);
 		}
-		std::vector<SumcheckMultilinear> mls;
-		for (const FSliceMut &f : pr.folded) mls.push_back(SumcheckMultilinear::folded(FSlice{f.ptr, f.len_}));
-		const FSlice table = backend.tensor_product_full_query(std::vector<B128>(pr.challenges.begin(), pr.challenges.end() - 1), alloc);
-		pr.prover = std::make_unique<EqIndSumcheckProver>(hal, backend, alloc, pr.nr, std::move(mls), tables[p].compositions, std::move(sums), pr.challenges,
-		                                                 FSliceMut{const_cast<void *>(table.ptr), table.len_});
+		// (no remaining round: the folded columns are single values, the indicator's evaluation is ONE)
+		provers.push_back(std::make_unique<EqIndPointProver>(hal, backend, alloc, pr.nr, pr.folded, tables[p].compositions, std::move(sums), pr.challenges));
 	}
-	auto finish = [&](size_t round) {
-		for (size_t p = 0; p < tables.size(); p++) {
-			Prover &pr = ps[p];
-			if (pr.nr != round) continue;
-			if (pr.nr == 0) {
-				// zero remaining rounds: the folded columns are single values, the indicator's evaluation is ONE
-				for (const FSliceMut &f : pr.folded) {
-					std::vector<B128> v(1);
-					hal.copy_d2h(FSlice{f.ptr, 1}, v);
-					out.final_evals[p].push_back(v[0]);
-				}
-				out.final_evals[p].push_back(B128::ONE());
-			} else {
-				out.final_evals[p] = pr.prover->finish();
-			}
-		}
-	};
-	for (size_t r = 0; r < rounds; r++) {
-		finish(r);
-		std::vector<B128> coeffs(d_max + 2, B128::ZERO());
-		for (size_t p = 0; p < tables.size(); p++) {
-			if (ps[p].nr <= r) continue;
-			const std::vector<B128> pc = ps[p].prover->execute(batch_coeffs[p]);
-			for (size_t i = 0; i < pc.size(); i++) coeffs[i] += pc[i] * batch_coeffs[p];
-		}
-		out.round_coeffs.push_back(coeffs);
-		for (size_t p = 0; p < tables.size(); p++)
-			if (ps[p].nr > r) ps[p].prover->fold(sumcheck_challenges[r]);
-	}
-	finish(rounds);
-	out.phase_ms[Out::Multilinear] = ms_since(t0);
+	// all coefficients of a round polynomial, padded to Dmax + 2
+	BatchSumcheckOutput res = SumcheckBatchProver<EqIndPointProver>(std::move(provers), batch_coeffs, BatchSchedule::FrontLoaded, d_max + 2).run(sumcheck_challenges.data());
+	out.round_coeffs = std::move(res.round_proofs);
+	out.final_evals = std::move(res.multilinear_evals);
+	out.phase_ms[Out::Multilinear] = elapsed_ms(t0);
 
 	// ---- project_to_skipped_variables
 	t0 = std::chrono::steady_clock::now();
@@ -342,10 +289,7 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 			continue;
 		}
 		const B128 *point = out.unskipped_challenges.data() + (rounds - pr.nr); // the last n - k
-		FSliceMut q = alloc.alloc((size_t)1 << pr.nr);
-		FSliceMut q0{q.ptr, 1};
-		hal.fill(q0, B128::ONE());
-		if (pr.nr) check(bn_tensor_expand(hal.raw_ctx(), q.ptr, q.len_, 0, reinterpret_cast<const bn_f128 *>(point), (uint32_t)pr.nr));
+		const FSliceMut q = ops::eq_ind_partial_eval(hal, alloc, std::vector<B128>(point, point + pr.nr), false);
 		FSliceMut outs = alloc.alloc(t.columns.size() << k);
 		std::vector<bn_pe_column> cols;
 		std::vector<void *> d_outs;
@@ -375,7 +319,7 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 			for (size_t i = 0; i < on_device.size(); i++) projected[first + on_device[i]].assign(all.begin() + (i << k), all.begin() + ((i + 1) << k));
 		}
 	}
-	out.phase_ms[Out::Projection] = ms_since(t0);
+	out.phase_ms[Out::Projection] = elapsed_ms(t0);
 
 	// ---- the univariatizing reduction: RegularSumcheckProver, High-to-Low, claims (column i) * (Lagrange multilinear), on the host
 	t0 = std::chrono::steady_clock::now();
@@ -410,7 +354,7 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 	for (const auto &a : projected) out.reduction_final_evals.push_back(a[0]);
 	out.concat_multilinear_evals = out.reduction_final_evals;
 	out.reduction_final_evals.push_back(lag[0]);
-	out.phase_ms[Out::Reduction] = ms_since(t0);
+	out.phase_ms[Out::Reduction] = elapsed_ms(t0);
 	return out;
 }
 

@@ -401,6 +401,20 @@ def test_prover_flush_only_and_nonzero_only(oracle, hal):
         assert_same_transcript(run_prover(hal, fl, nz, smp), restated(fl, nz, smp))
 
 
+def test_prover_reduces_flushes_of_zero_variables(oracle, hal):
+    """Two composite flushes of a single row share the MLE-check over zero variables -- no rounds, the final evaluations are the
+    columns' single elements -- next to one of three variables; the second one's selector is zero, so its witness is empty."""
+    flushes = [{"channel": 0, "n_vars": 0, "selectors": [(5, np.array([1], dtype=np.uint8))], "entries": [("oracle", 1, column(0xB5001, 0, 5), 5), ("const", 0x1234)]},
+               {"channel": 1, "n_vars": 0, "selectors": [(2, np.array([0], dtype=np.uint8))], "entries": [("oracle", 6, column(0xB5002, 0, 3), 3)]},
+               {"channel": 0, "n_vars": 3, "selectors": [(9, selector_with_last_bit(3, 7, 0xB5010))], "entries": [("oracle", 4, column(0xB5003, 3, 7), 7)]}]
+    smp = samples(oracle, flushes, [], 0xB5100)
+    want = restated(flushes, [], smp)
+    assert want["prefix_lens"] == [1, 0, 8] and want["linear_flushes"] == []
+    assert [(c["n_vars"], len(c["round_proofs"])) for c in want["checks"]] == [(0, 0), (3, 3)]
+    assert want["checks"][0]["ids"] == [1, 2, 5, 6] and len(want["checks"][0]["final_evals"]) == 5
+    assert_same_transcript(run_prover(hal, flushes, [], smp), want)
+
+
 def test_prover_reports_a_zero_nonzero_product_and_the_context_stays_usable(oracle, hal):
     from binius_amd._ffi import BnError
 
