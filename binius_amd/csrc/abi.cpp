@@ -556,6 +556,15 @@ int ensure_d_steps(const bn_expr *e)
 }
 } // namespace bnabi
 
+// call_upload (abi_common.hpp): the scratch for every reserved section, the zeroed host mirror for the uploaded ones
+int call_upload::alloc()
+{
+	scr = (char *)bn::ctx_scratch(ctx, bytes);
+	if (!scr) return bn::fail(BN_ERR_ALLOC, "allocation error: allocator is out of memory (scratch)");
+	mirror.assign(std::min(bytes, upload_bytes), 0);
+	return BN_OK;
+}
+
 extern "C" {
 
 const char *bn_last_error(void) { return g_last_error.c_str(); }

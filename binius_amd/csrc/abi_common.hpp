@@ -1,6 +1,8 @@
 // binius_amd/csrc/abi_common.hpp -- pieces shared by the translation units of the extern "C" boundary
 // (abi.cpp: context, copies, deferral; abi_kernels.cpp: the recorded-kernel dispatcher; abi_ops.cpp: the
-// executor ops, Merkle and NTT entry points).  Not part of the public interface.
+// executor ops, Merkle and NTT entry points; the batched ops -- abi_prodtree.cpp, abi_expcircuit.cpp, abi_partial_eval.cpp,
+// abi_flush.cpp, abi_univariate_fold.cpp, abi_univariate.cpp -- use the helpers and call_upload at the end).  Not part of the
+// public interface.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -210,3 +212,40 @@ static inline uint32_t ilog2(uint64_t n)
 }
 static inline f128 to_f(const bn_f128 *p) { return f128{p->lo, p->hi}; }
 static inline bool valid_tower_level(uint32_t l) { return l == 0 || (l >= 3 && l <= 7); } // tower_macro.rs:9-15
+// ---- shared by the batched ops (one launch serves a table of jobs: batch.hpp on the device side)
+static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+// 128-bit elements of a packed column of 2^n_vars values at tower level `level` (a bit column: level 0)
+static inline uint64_t column_elems(uint32_t n_vars, uint32_t level) { return n_vars + level <= 7 ? 1 : (uint64_t)1 << (n_vars + level - 7); }
+static inline bool aligned16(const void *p, const void *q = nullptr) { return (((uintptr_t)p | (uintptr_t)q) & 15) == 0; }
+
+// The tables of one call in the context's scratch.  reserve() the sections first, in upload order, each 256-byte aligned: the layout
+// is fixed before anything is filled, because job entries point into other sections.  alloc() once; fill the zero-filled host mirror
+// through host(), with dev() the matching device pointer; send() is one copy on the context's stream.  Sections reserved after
+// device_only() get scratch but are not uploaded: the device writes them.
+template <typename T>
+struct upload_section {
+	size_t off;
+};
+struct call_upload {
+	bn_ctx *ctx;
+	size_t bytes = 0, upload_bytes = ~(size_t)0;
+	char *scr = nullptr;
+	std::vector<char> mirror;
+	explicit call_upload(bn_ctx *c) : ctx(c) {}
+	call_upload(const call_upload &) = delete; // (one owner of the mirror and of the scratch layout)
+	call_upload &operator=(const call_upload &) = delete;
+	template <typename T>
+	upload_section<T> reserve(size_t count)
+	{
+		const size_t at = bytes;
+		bytes = align_up(bytes + count * sizeof(T));
+		return upload_section<T>{at};
+	}
+	void device_only() { upload_bytes = bytes; }
+	int alloc(); // BN_OK or BN_ERR_ALLOC (abi.cpp)
+	template <typename T>
+	T *host(upload_section<T> s) { return reinterpret_cast<T *>(mirror.data() + s.off); }
+	template <typename T>
+	T *dev(upload_section<T> s) const { return reinterpret_cast<T *>(scr + s.off); }
+	hipError_t send() const { return hipMemcpyAsync(scr, mirror.data(), mirror.size(), hipMemcpyHostToDevice, ctx->stream); }
+};

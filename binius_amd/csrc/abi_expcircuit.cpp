@@ -11,14 +11,6 @@
 #include "abi_common.hpp"
 #include "hostmul.hpp"
 
-namespace {
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-uint64_t bit_column_elems(uint32_t n_vars) { return n_vars <= 7 ? 1 : (uint64_t)1 << (n_vars - 7); }
-
-} // namespace
-
 extern "C" {
 
 int bn_exp_circuit_layers(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *n_vars, const uint32_t *widths, const uint32_t *kinds,
@@ -38,16 +30,16 @@ int bn_exp_circuit_layers(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *n_v
 		BN_REQUIRE(kinds[t] == BN_EXP_STATIC || kinds[t] == BN_EXP_DYNAMIC, "exp circuit: unknown kind");
 		const uint64_t rows = (uint64_t)1 << n_vars[t], arena_elems = rows * widths[t];
 		BN_REQUIRE(d_layers[t], "exp circuit: null layer arena");
-		BN_REQUIRE(((uintptr_t)d_layers[t] & 15) == 0, "exp circuit: pointers must be 16-byte aligned");
+		BN_REQUIRE(aligned16(d_layers[t]), "exp circuit: pointers must be 16-byte aligned");
 		for (uint32_t j = 0; j < widths[t]; j++) {
 			const void *col = d_exponent_bits[n_ptrs + j];
 			BN_REQUIRE(col, "exp circuit: null bit column");
-			BN_REQUIRE(((uintptr_t)col & 15) == 0, "exp circuit: pointers must be 16-byte aligned");
-			BN_REQUIRE(!ranges_overlap(col, bit_column_elems(n_vars[t]), d_layers[t], arena_elems), "exp circuit: the layer arena overlaps a bit column");
+			BN_REQUIRE(aligned16(col), "exp circuit: pointers must be 16-byte aligned");
+			BN_REQUIRE(!ranges_overlap(col, column_elems(n_vars[t], 0), d_layers[t], arena_elems), "exp circuit: the layer arena overlaps a bit column");
 		}
 		if (kinds[t] == BN_EXP_DYNAMIC) {
 			BN_REQUIRE(d_bases[t], "exp circuit: null base column");
-			BN_REQUIRE(((uintptr_t)d_bases[t] & 15) == 0, "exp circuit: pointers must be 16-byte aligned");
+			BN_REQUIRE(aligned16(d_bases[t]), "exp circuit: pointers must be 16-byte aligned");
 			BN_REQUIRE(!ranges_overlap(d_bases[t], rows, d_layers[t], arena_elems), "exp circuit: the layer arena overlaps the base column");
 		} else {
 			n_pows += widths[t];
@@ -58,20 +50,19 @@ int bn_exp_circuit_layers(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *n_v
 	}
 
 	// ---- one upload: [jobs][bit-column pointers][g^(2^k)]
-	const size_t o_ptrs = align_up((size_t)n_witnesses * sizeof(bn::expc_job));
-	const size_t o_pows = align_up(o_ptrs + n_ptrs * sizeof(void *));
-	const size_t bytes = align_up(o_pows + n_pows * sizeof(f128));
-	char *scr = (char *)bn::ctx_scratch(ctx, bytes);
-	if (!scr) return bn::fail(BN_ERR_ALLOC, "allocation error: allocator is out of memory (scratch)");
-	std::vector<char> host(bytes, 0);
-	bn::expc_job *jobs = (bn::expc_job *)host.data();
-	f128 *pows = (f128 *)&host[o_pows];
-	memcpy(&host[o_ptrs], d_exponent_bits, n_ptrs * sizeof(void *));
+	call_upload up(ctx);
+	const auto s_jobs = up.reserve<bn::expc_job>(n_witnesses);
+	const auto s_ptrs = up.reserve<const uint32_t *>(n_ptrs);
+	const auto s_pows = up.reserve<f128>(n_pows);
+	if (const int rc = up.alloc()) return rc;
+	bn::expc_job *jobs = up.host(s_jobs);
+	f128 *pows = up.host(s_pows);
+	memcpy(up.host(s_ptrs), d_exponent_bits, n_ptrs * sizeof(void *));
 	size_t at_ptr = 0, at_pow = 0;
 	uint32_t at_unit = 0;
 	for (uint32_t t = 0; t < n_witnesses; t++) {
 		bn::expc_job &jb = jobs[t];
-		jb.bits = (const uint32_t *const *)(scr + o_ptrs) + at_ptr;
+		jb.bits = up.dev(s_ptrs) + at_ptr;
 		jb.arena = (f128 *)d_layers[t];
 		jb.rows = (uint64_t)1 << n_vars[t];
 		jb.width = widths[t];
@@ -80,7 +71,7 @@ int bn_exp_circuit_layers(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *n_v
 		if (jb.dynamic) {
 			jb.base = (const f128 *)d_bases[t];
 		} else {
-			jb.base = (const f128 *)(scr + o_pows) + at_pow;
+			jb.base = up.dev(s_pows) + at_pow;
 			f128 p = to_f(&static_bases[t]);
 			for (uint32_t k = 0; k < widths[t]; k++) {
 				pows[at_pow + k] = p;
@@ -91,8 +82,8 @@ int bn_exp_circuit_layers(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *n_v
 		at_ptr += widths[t];
 		at_unit += (uint32_t)((jb.rows + bn::kExpRun - 1) / bn::kExpRun);
 	}
-	BN_HIP(hipMemcpyAsync(scr, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-	BN_HIP(bn::launch_expcircuit(ctx->stream, ctx->n_cu, (const bn::expc_job *)scr, n_witnesses, at_unit));
+	BN_HIP(up.send());
+	BN_HIP(bn::launch_expcircuit(ctx->stream, ctx->n_cu, up.dev(s_jobs), n_witnesses, at_unit));
 	ctx->exp_calls++;
 	ctx->exp_launches++;
 	BN_HIP(hipStreamSynchronize(ctx->stream)); // (the layers are complete on return; the table is pageable host memory that goes out of scope)
@@ -113,8 +104,8 @@ int bn_bits_to_b128(bn_ctx *ctx, uint32_t n, const uint32_t *log_lens, const voi
 		BN_REQUIRE(log_lens[t] <= BN_EXP_MAX_VARS, "bits: log_len out of range (0 .. 28)");
 		const uint64_t full = (uint64_t)1 << log_lens[t];
 		BN_REQUIRE(d_srcs[t] && d_dsts[t], "bits: null pointer");
-		BN_REQUIRE(((uintptr_t)d_srcs[t] & 15) == 0 && ((uintptr_t)d_dsts[t] & 15) == 0, "bits: pointers must be 16-byte aligned");
-		BN_REQUIRE(!ranges_overlap(d_srcs[t], bit_column_elems(log_lens[t]), d_dsts[t], full), "bits: destination overlaps its source");
+		BN_REQUIRE(aligned16(d_srcs[t], d_dsts[t]), "bits: pointers must be 16-byte aligned");
+		BN_REQUIRE(!ranges_overlap(d_srcs[t], column_elems(log_lens[t], 0), d_dsts[t], full), "bits: destination overlaps its source");
 		jobs[t] = bn::bits_job{(const uint32_t *)d_srcs[t], (f128 *)d_dsts[t], full, (uint32_t)blocks, 0};
 		blocks += (full + 255) / 256;
 		BN_REQUIRE(blocks < (1ull << 31), "bits: batch too large for one call");

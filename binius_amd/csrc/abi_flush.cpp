@@ -13,10 +13,6 @@
 
 namespace {
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-uint64_t column_elems(uint32_t n_vars, uint32_t level) { return n_vars + level <= 7 ? 1 : (uint64_t)1 << (n_vars + level - 7); }
-
 struct span {
 	uintptr_t b, e;
 	bool operator<(const span &o) const { return b < o.b; }
@@ -64,11 +60,11 @@ int bn_flush_witness_batch(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *n_va
 		BN_REQUIRE(n_selectors[f] == 0 || d_selectors, "null argument");
 		const uint64_t rows = (uint64_t)1 << n_vars[f];
 		BN_REQUIRE(d_outs[f], "flush witness: null output");
-		BN_REQUIRE(((uintptr_t)d_outs[f] & 15) == 0, "flush witness: pointers must be 16-byte aligned");
+		BN_REQUIRE(aligned16(d_outs[f]), "flush witness: pointers must be 16-byte aligned");
 		for (uint32_t s = 0; s < n_selectors[f]; s++) {
 			const void *sel = d_selectors[n_sels + s];
 			BN_REQUIRE(sel, "flush witness: null selector");
-			BN_REQUIRE(((uintptr_t)sel & 15) == 0, "flush witness: pointers must be 16-byte aligned");
+			BN_REQUIRE(aligned16(sel), "flush witness: pointers must be 16-byte aligned");
 			ins.push_back(span{(uintptr_t)sel, (uintptr_t)sel + 16 * column_elems(n_vars[f], 0)});
 			sel_wgs += (column_elems(n_vars[f], 0) + bn::kFlushSelChunk - 1) / bn::kFlushSelChunk;
 		}
@@ -77,7 +73,7 @@ int bn_flush_witness_batch(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *n_va
 			const uint32_t level = tower_levels[n_cols + j];
 			BN_REQUIRE(valid_tower_level(level), "flush witness: tower level must be 0 or 3 .. 7");
 			BN_REQUIRE(col, "flush witness: null column");
-			BN_REQUIRE(((uintptr_t)col & 15) == 0, "flush witness: pointers must be 16-byte aligned");
+			BN_REQUIRE(aligned16(col), "flush witness: pointers must be 16-byte aligned");
 			ins.push_back(span{(uintptr_t)col, (uintptr_t)col + 16 * column_elems(n_vars[f], level)});
 		}
 		outs.push_back(span{(uintptr_t)d_outs[f], (uintptr_t)d_outs[f] + 16 * rows});
@@ -89,25 +85,24 @@ int bn_flush_witness_batch(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *n_va
 	BN_REQUIRE(!outputs_clash(ins, outs), "flush witness: an output overlaps an input or another output of the call");
 
 	// ---- one upload: [jobs][column descriptors][selector pointers][pre-pass table][prefix words]
-	const size_t o_cols = align_up((size_t)n_flushes * sizeof(bn::flush_job));
-	const size_t o_ptrs = align_up(o_cols + n_cols * sizeof(bn::flush_col));
-	const size_t o_sels = align_up(o_ptrs + n_sels * sizeof(void *));
-	const size_t o_pref = align_up(o_sels + n_sels * sizeof(bn::flush_sel));
-	const size_t bytes = align_up(o_pref + n_sels * sizeof(uint64_t));
-	char *scr = (char *)bn::ctx_scratch(ctx, bytes);
-	if (!scr) return bn::fail(BN_ERR_ALLOC, "allocation error: allocator is out of memory (scratch)");
-	std::vector<char> host(bytes, 0);
-	bn::flush_job *jobs = (bn::flush_job *)host.data();
-	bn::flush_col *cols = (bn::flush_col *)&host[o_cols];
-	bn::flush_sel *sels = (bn::flush_sel *)&host[o_sels];
-	if (n_sels) memcpy(&host[o_ptrs], d_selectors, n_sels * sizeof(void *));
+	call_upload up(ctx);
+	const auto s_jobs = up.reserve<bn::flush_job>(n_flushes);
+	const auto s_cols = up.reserve<bn::flush_col>(n_cols);
+	const auto s_ptrs = up.reserve<const uint32_t *>(n_sels);
+	const auto s_sels = up.reserve<bn::flush_sel>(n_sels);
+	const auto s_pref = up.reserve<uint64_t>(n_sels); // (uploaded as zeros; the pre-pass raises them)
+	if (const int rc = up.alloc()) return rc;
+	bn::flush_job *jobs = up.host(s_jobs);
+	bn::flush_col *cols = up.host(s_cols);
+	bn::flush_sel *sels = up.host(s_sels);
+	if (n_sels) memcpy(up.host(s_ptrs), d_selectors, n_sels * sizeof(void *));
 	size_t at_col = 0, at_sel = 0;
 	uint32_t at_unit = 0, at_wg = 0, multipass = 0;
 	for (uint32_t f = 0; f < n_flushes; f++) {
 		bn::flush_job &jb = jobs[f];
-		jb.cols = (const bn::flush_col *)(scr + o_cols) + at_col;
-		jb.sels = (const uint32_t *const *)(scr + o_ptrs) + at_sel;
-		jb.sel_prefix = (const uint64_t *)(scr + o_pref) + at_sel;
+		jb.cols = up.dev(s_cols) + at_col;
+		jb.sels = up.dev(s_ptrs) + at_sel;
+		jb.sel_prefix = up.dev(s_pref) + at_sel;
 		jb.out = (uint4 *)d_outs[f];
 		jb.const_term = to_f(&const_terms[f]);
 		jb.rows = (uint64_t)1 << n_vars[f];
@@ -136,7 +131,7 @@ int bn_flush_witness_batch(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *n_va
 		for (uint32_t s = 0; s < n_selectors[f]; s++) {
 			bn::flush_sel &sl = sels[at_sel + s];
 			sl.col = (const uint4 *)d_selectors[at_sel + s];
-			sl.prefix = (uint64_t *)(scr + o_pref) + at_sel + s;
+			sl.prefix = up.dev(s_pref) + at_sel + s;
 			sl.elems = column_elems(n_vars[f], 0);
 			sl.start = at_wg;
 			at_wg += (uint32_t)((sl.elems + bn::kFlushSelChunk - 1) / bn::kFlushSelChunk);
@@ -145,11 +140,11 @@ int bn_flush_witness_batch(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *n_va
 		at_sel += n_selectors[f];
 		at_unit += (uint32_t)((jb.rows + bn::kFlushUnitRows - 1) / bn::kFlushUnitRows);
 	}
-	BN_HIP(hipMemcpyAsync(scr, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-	BN_HIP(bn::launch_flush_prefix(ctx->stream, (const bn::flush_sel *)(scr + o_sels), (uint32_t)n_sels, at_wg));
-	BN_HIP(bn::launch_flush_witness(ctx->stream, (const bn::flush_job *)scr, n_flushes, at_unit));
+	BN_HIP(up.send());
+	BN_HIP(bn::launch_flush_prefix(ctx->stream, up.dev(s_sels), (uint32_t)n_sels, at_wg));
+	BN_HIP(bn::launch_flush_witness(ctx->stream, up.dev(s_jobs), n_flushes, at_unit));
 	std::vector<uint64_t> pref(n_sels);
-	if (n_sels) BN_HIP(hipMemcpyAsync(pref.data(), scr + o_pref, n_sels * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	if (n_sels) BN_HIP(hipMemcpyAsync(pref.data(), up.dev(s_pref), n_sels * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
 	ctx->flush_calls++;
 	ctx->flush_launches += n_sels ? 2 : 1;
 	ctx->flush_served += n_flushes;

@@ -70,15 +70,15 @@ int partial_eval_run(bn_ctx *ctx, const bn_pe_column *cols, uint32_t n_cols, con
 		if (order.size() == 1) {
 			BN_HIP(bn::launch_partial_eval(ctx->stream, nullptr, 1, nullptr, 1, groups[0], table[0], d_vec, (uint32_t)units, bits_only));
 		} else {
-			const size_t g_bytes = (groups.size() * sizeof(bn::pe_group) + 255) & ~(size_t)255, bytes = g_bytes + table.size() * sizeof(bn::pe_col);
-			char *scr = (char *)bn::ctx_scratch(ctx, bytes);
-			if (!scr) return bn::fail(BN_ERR_ALLOC, "allocation error: allocator is out of memory (scratch)");
-			std::vector<char> host(bytes, 0);
-			memcpy(host.data(), groups.data(), groups.size() * sizeof(bn::pe_group));
-			memcpy(host.data() + g_bytes, table.data(), table.size() * sizeof(bn::pe_col));
-			BN_HIP(hipMemcpyAsync(scr, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-			BN_HIP(bn::launch_partial_eval(ctx->stream, (const bn::pe_group *)scr, (uint32_t)groups.size(), (const bn::pe_col *)(scr + g_bytes),
-			                               (uint32_t)table.size(), bn::pe_group{}, bn::pe_col{}, d_vec, (uint32_t)units, bits_only));
+			call_upload up(ctx);
+			const auto s_groups = up.reserve<bn::pe_group>(groups.size());
+			const auto s_cols = up.reserve<bn::pe_col>(table.size());
+			if (const int rc = up.alloc()) return rc;
+			std::copy(groups.begin(), groups.end(), up.host(s_groups));
+			std::copy(table.begin(), table.end(), up.host(s_cols));
+			BN_HIP(up.send());
+			BN_HIP(bn::launch_partial_eval(ctx->stream, up.dev(s_groups), (uint32_t)groups.size(), up.dev(s_cols), (uint32_t)table.size(), bn::pe_group{},
+			                               bn::pe_col{}, d_vec, (uint32_t)units, bits_only));
 			BN_HIP(hipStreamSynchronize(ctx->stream)); // (the tables are pageable host memory that goes out of scope; the fold_left launches may regrow the scratch)
 		}
 	}
@@ -112,15 +112,15 @@ int bn_partial_eval_high_batch(bn_ctx *ctx, const void *cols_, uint32_t n_cols, 
 	BN_REQUIRE(cols && d_tensor_query && d_outs, "null argument");
 	BN_REQUIRE(n_cols <= (1u << 20), "too many columns for one call");
 	BN_REQUIRE(query_vars <= BN_PE_MAX_VARS, "partial eval: query_vars out of range");
-	BN_REQUIRE(((uintptr_t)d_tensor_query & 15) == 0, "partial eval: pointers must be 16-byte aligned");
+	BN_REQUIRE(aligned16(d_tensor_query), "partial eval: pointers must be 16-byte aligned");
 	for (uint32_t c = 0; c < n_cols; c++) {
 		BN_REQUIRE(cols[c].d_evals && d_outs[c], "partial eval: null pointer");
 		BN_REQUIRE(cols[c].tower_level <= 7, "invalid evals: tower_level > 7");
 		BN_REQUIRE(valid_tower_level(cols[c].tower_level), "unsupported value of tower_level");
 		BN_REQUIRE(cols[c].n_vars <= BN_PE_MAX_VARS && cols[c].n_vars + cols[c].tower_level >= 7, "partial eval: a column is at least one 128-bit element, at most 2^40 values");
 		BN_REQUIRE(query_vars <= cols[c].n_vars, "query larger than evals");
-		BN_REQUIRE((((uintptr_t)cols[c].d_evals | (uintptr_t)d_outs[c]) & 15) == 0, "partial eval: pointers must be 16-byte aligned");
-		BN_REQUIRE(!ranges_overlap(cols[c].d_evals, (uint64_t)1 << (cols[c].n_vars + cols[c].tower_level - 7), d_outs[c], (uint64_t)1 << (cols[c].n_vars - query_vars)),
+		BN_REQUIRE(aligned16(cols[c].d_evals, d_outs[c]), "partial eval: pointers must be 16-byte aligned");
+		BN_REQUIRE(!ranges_overlap(cols[c].d_evals, column_elems(cols[c].n_vars, cols[c].tower_level), d_outs[c], (uint64_t)1 << (cols[c].n_vars - query_vars)),
 		           "partial eval: an output overlaps its column");
 	}
 	return partial_eval_run(ctx, cols, n_cols, d_tensor_query, query_vars, d_outs, false);

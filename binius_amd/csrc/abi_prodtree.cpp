@@ -20,8 +20,6 @@ struct stage_list {
 	bool dual = false;
 };
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 } // namespace
 
 extern "C" {
@@ -40,7 +38,7 @@ int bn_product_tree_layers(bn_ctx *ctx, uint32_t n_trees, const uint32_t *n_vars
 		const uint64_t full = (uint64_t)1 << n_vars[t];
 		BN_REQUIRE(input_lens[t] <= full, "product tree: input_len exceeds 2^n_vars");
 		BN_REQUIRE(input_lens[t] == 0 || d_inputs[t], "product tree: null input");
-		BN_REQUIRE(((uintptr_t)d_inputs[t] & 15) == 0 && ((uintptr_t)d_layers[t] & 15) == 0, "product tree: pointers must be 16-byte aligned");
+		BN_REQUIRE(aligned16(d_inputs[t], d_layers[t]), "product tree: pointers must be 16-byte aligned");
 		if (n_vars[t] == 0) continue; // (an arena of one element, which is not touched)
 		BN_REQUIRE(d_layers[t], "product tree: null layer arena");
 		BN_REQUIRE(input_lens[t] == 0 || !ranges_overlap(d_inputs[t], input_lens[t], d_layers[t], full), "product tree: the layer arena overlaps its input");
@@ -93,36 +91,30 @@ int bn_product_tree_layers(bn_ctx *ctx, uint32_t n_trees, const uint32_t *n_vars
 	}
 
 	// ---- one upload: [job tables, stage by stage][root pointers]; the roots are gathered behind them
-	size_t off = 0;
-	std::vector<std::pair<size_t, size_t>> offs(stages.size());
-	for (size_t i = 0; i < stages.size(); i++) {
-		offs[i].first = off;
-		off = align_up(off + stages[i].big.size() * sizeof(bn::prodtree_job));
-		offs[i].second = off;
-		off = align_up(off + stages[i].small.size() * sizeof(bn::prodtree_job));
+	call_upload up(ctx);
+	std::vector<upload_section<bn::prodtree_job>> s_big, s_small;
+	for (const stage_list &sl : stages) {
+		s_big.push_back(up.reserve<bn::prodtree_job>(sl.big.size()));
+		s_small.push_back(up.reserve<bn::prodtree_job>(sl.small.size()));
 	}
-	const size_t o_roots = off;
-	off = align_up(off + (size_t)n_trees * sizeof(void *));
-	const size_t upload_bytes = off;
-	const size_t o_prod = off;
-	off = align_up(off + (size_t)n_trees * sizeof(f128));
-	char *scr = (char *)bn::ctx_scratch(ctx, off);
-	if (!scr) return bn::fail(BN_ERR_ALLOC, "allocation error: allocator is out of memory (scratch)");
-	std::vector<char> host(upload_bytes, 0);
+	const auto s_roots = up.reserve<const f128 *>(n_trees);
+	up.device_only();
+	const auto s_prod = up.reserve<f128>(n_trees);
+	if (const int rc = up.alloc()) return rc;
 	for (size_t i = 0; i < stages.size(); i++) {
-		if (!stages[i].big.empty()) memcpy(&host[offs[i].first], stages[i].big.data(), stages[i].big.size() * sizeof(bn::prodtree_job));
-		if (!stages[i].small.empty()) memcpy(&host[offs[i].second], stages[i].small.data(), stages[i].small.size() * sizeof(bn::prodtree_job));
+		std::copy(stages[i].big.begin(), stages[i].big.end(), up.host(s_big[i]));
+		std::copy(stages[i].small.begin(), stages[i].small.end(), up.host(s_small[i]));
 	}
-	memcpy(&host[o_roots], roots.data(), (size_t)n_trees * sizeof(void *));
-	BN_HIP(hipMemcpyAsync(scr, host.data(), upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+	std::copy(roots.begin(), roots.end(), up.host(s_roots));
+	BN_HIP(up.send());
 	for (size_t i = 0; i < stages.size(); i++) {
 		const stage_list &sl = stages[i];
-		BN_HIP(bn::launch_prodtree_big(ctx->stream, ctx->n_cu, (const bn::prodtree_job *)(scr + offs[i].first), (uint32_t)sl.big.size(), sl.big_units, sl.dual));
-		BN_HIP(bn::launch_prodtree_small(ctx->stream, (const bn::prodtree_job *)(scr + offs[i].second), (uint32_t)sl.small.size(), sl.small_units));
+		BN_HIP(bn::launch_prodtree_big(ctx->stream, ctx->n_cu, up.dev(s_big[i]), (uint32_t)sl.big.size(), sl.big_units, sl.dual));
+		BN_HIP(bn::launch_prodtree_small(ctx->stream, up.dev(s_small[i]), (uint32_t)sl.small.size(), sl.small_units));
 	}
-	f128 *d_prod = (f128 *)(scr + o_prod);
-	BN_HIP(bn::launch_prodtree_roots(ctx->stream, (const f128 *const *)(scr + o_roots), n_trees, d_prod));
-	// the products through the zero-copy mailbox, 64 at a time (the spin also covers the upload above: `host` may go)
+	f128 *d_prod = up.dev(s_prod);
+	BN_HIP(bn::launch_prodtree_roots(ctx->stream, up.dev(s_roots), n_trees, d_prod));
+	// the products through the zero-copy mailbox, 64 at a time (the spin also covers the upload above: its host mirror may go)
 	for (uint32_t t0 = 0; t0 < n_trees; t0 += 64) {
 		f128 vals[64];
 		const uint32_t cnt = std::min<uint32_t>(64, n_trees - t0);
@@ -148,7 +140,7 @@ int bn_pad_with_ones(bn_ctx *ctx, uint32_t n, const uint32_t *log_lens, const vo
 		const uint64_t full = (uint64_t)1 << log_lens[t];
 		BN_REQUIRE(src_lens[t] <= full, "pad: src_len exceeds 2^log_len");
 		BN_REQUIRE(d_dsts[t] && (src_lens[t] == 0 || d_srcs[t]), "pad: null pointer");
-		BN_REQUIRE(((uintptr_t)d_srcs[t] & 15) == 0 && ((uintptr_t)d_dsts[t] & 15) == 0, "pad: pointers must be 16-byte aligned");
+		BN_REQUIRE(aligned16(d_srcs[t], d_dsts[t]), "pad: pointers must be 16-byte aligned");
 		BN_REQUIRE(src_lens[t] == 0 || !ranges_overlap(d_srcs[t], src_lens[t], d_dsts[t], full), "pad: destination overlaps its source");
 		jobs[t] = bn::prodtree_job{(const f128 *)d_srcs[t], (f128 *)d_dsts[t], src_lens[t], log_lens[t], 0, (uint32_t)blocks, 0};
 		blocks += (full + 255) / 256;

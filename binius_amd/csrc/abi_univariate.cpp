@@ -104,8 +104,6 @@ void extrapolate(uint32_t k, uint32_t d, uint32_t D, const f128 *r, f128 *dst)
 	}
 }
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 } // namespace
 
 extern "C" {
@@ -201,61 +199,48 @@ int bn_zerocheck_univariate_evals(bn_ctx *ctx, uint32_t n_vars, uint32_t skip_ro
 			p = bn::mul_host(p, to_f(h_batch_coeff));
 		}
 	}
-	size_t off = 0;
-	const size_t o_cols = off;
-	off = align_up(off + cols.size() * sizeof(bn::uskip_col));
-	const size_t o_steps = off;
-	off = align_up(off + (size_t)n_steps * sizeof(bn_step));
-	const size_t o_soff = off;
-	off = align_up(off + (size_t)(n_comps + 1) * 4);
-	const size_t o_nj = off;
-	off = align_up(off + (size_t)n_comps * 4);
-	const size_t o_masks = off;
-	off = align_up(off + masks.size() * sizeof(bn::f128));
-	const size_t o_lag = off;
-	off = align_up(off + lag.size());
-	const size_t o_logexp = off;
-	off = align_up(off + sizeof(T.logexp));
-	const size_t o_scale = off;
-	off = align_up(off + scale.size() * sizeof(bn::f128));
-	const size_t args_bytes = off;
-	const size_t o_partial = off;
-	off = align_up(off + (size_t)n_comps * n_tiles * th * sizeof(bn::f128));
-	const size_t o_out = off;
-	off = align_up(off + (size_t)n_comps * th * sizeof(bn::f128));
-	char *scr = (char *)bn::ctx_scratch(ctx, off);
-	if (!scr) return bn::fail(BN_ERR_ALLOC, "allocation error: allocator is out of memory (scratch)");
-	std::vector<char> host(args_bytes, 0);
-	memcpy(&host[o_cols], cols.data(), cols.size() * sizeof(bn::uskip_col));
-	memcpy(&host[o_steps], steps, (size_t)n_steps * sizeof(bn_step));
-	memcpy(&host[o_soff], step_offsets, (size_t)(n_comps + 1) * 4);
-	memcpy(&host[o_nj], n_j.data(), (size_t)n_comps * 4);
-	memcpy(&host[o_masks], masks.data(), masks.size() * sizeof(bn::f128));
-	memcpy(&host[o_lag], lag.data(), lag.size());
-	memcpy(&host[o_logexp], T.logexp, sizeof(T.logexp));
-	if (!scale.empty()) memcpy(&host[o_scale], scale.data(), scale.size() * sizeof(bn::f128));
-	BN_HIP(hipMemcpyAsync(scr, host.data(), args_bytes, hipMemcpyHostToDevice, ctx->stream));
+	call_upload up(ctx);
+	const auto s_cols = up.reserve<bn::uskip_col>(cols.size());
+	const auto s_steps = up.reserve<bn_step>(n_steps);
+	const auto s_soff = up.reserve<uint32_t>(n_comps + 1);
+	const auto s_nj = up.reserve<uint32_t>(n_comps);
+	const auto s_masks = up.reserve<bn::f128>(masks.size());
+	const auto s_lag = up.reserve<uint8_t>(lag.size());
+	const auto s_logexp = up.reserve<uint8_t>(sizeof(T.logexp));
+	const auto s_scale = up.reserve<bn::f128>(scale.size());
+	up.device_only();
+	const auto s_partial = up.reserve<bn::f128>((size_t)n_comps * n_tiles * th);
+	const auto s_out = up.reserve<bn::f128>((size_t)n_comps * th);
+	if (const int rc = up.alloc()) return rc;
+	std::copy(cols.begin(), cols.end(), up.host(s_cols));
+	std::copy(steps, steps + n_steps, up.host(s_steps));
+	std::copy(step_offsets, step_offsets + n_comps + 1, up.host(s_soff));
+	std::copy(n_j.begin(), n_j.end(), up.host(s_nj));
+	std::copy(masks.begin(), masks.end(), up.host(s_masks));
+	std::copy(lag.begin(), lag.end(), up.host(s_lag));
+	std::copy(T.logexp, T.logexp + sizeof(T.logexp), up.host(s_logexp));
+	std::copy(scale.begin(), scale.end(), up.host(s_scale));
+	BN_HIP(up.send());
 	bn::uskip_args a{};
-	a.cols = (const bn::uskip_col *)(scr + o_cols);
-	a.steps = (const bn_step *)(scr + o_steps);
-	a.step_off = (const uint32_t *)(scr + o_soff);
-	a.n_j = (const uint32_t *)(scr + o_nj);
-	a.masks = (const uint4 *)(scr + o_masks);
-	a.lag = (const uint8_t *)(scr + o_lag);
-	a.logexp = (const uint8_t *)(scr + o_logexp);
+	a.cols = up.dev(s_cols);
+	a.steps = up.dev(s_steps);
+	a.step_off = up.dev(s_soff);
+	a.n_j = up.dev(s_nj);
+	a.masks = (const uint4 *)up.dev(s_masks);
+	a.lag = up.dev(s_lag);
+	a.logexp = up.dev(s_logexp);
 	a.eq = (const uint4 *)d_eq;
-	a.partial = scr + o_partial;
+	a.partial = up.dev(s_partial);
 	a.k = k;
 	a.n_x_log = n_x_log;
 	a.n_tiles = (uint32_t)n_tiles;
 	a.x_per_tile = x_per_tile;
 	{
 		prof_scope ps(ctx, BN_PROF_ROUND_EVAL);
-		BN_HIP(bn::launch_uskip_evals(ctx->stream, a, th, n_comps, scale.empty() ? nullptr : (const bn::f128 *)(scr + o_scale),
-		                              (bn::f128 *)(scr + o_out)));
+		BN_HIP(bn::launch_uskip_evals(ctx->stream, a, th, n_comps, scale.empty() ? nullptr : up.dev(s_scale), up.dev(s_out)));
 	}
 	std::vector<bn::f128> r((size_t)n_comps * th);
-	BN_HIP(hipMemcpyAsync(r.data(), scr + o_out, r.size() * sizeof(bn::f128), hipMemcpyDeviceToHost, ctx->stream));
+	BN_HIP(hipMemcpyAsync(r.data(), up.dev(s_out), r.size() * sizeof(bn::f128), hipMemcpyDeviceToHost, ctx->stream));
 	BN_HIP(hipStreamSynchronize(ctx->stream));
 
 	// ---- extrapolation to the max domain: per composition, or per degree class of the batched sum (extrapolation is linear)

@@ -9,14 +9,6 @@
 
 #include "abi_common.hpp"
 
-namespace {
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-uint64_t column_elems(uint32_t n_vars, uint32_t level) { return n_vars + level <= 7 ? 1 : (uint64_t)1 << (n_vars + level - 7); }
-
-} // namespace
-
 extern "C" {
 
 int bn_univariate_fold_batch(bn_ctx *ctx, const void *cols_, uint32_t n_cols, uint32_t skip_rounds, const bn_f128 *h_coeffs, void *const *d_outs)
@@ -38,7 +30,7 @@ int bn_univariate_fold_batch(bn_ctx *ctx, const void *cols_, uint32_t n_cols, ui
 		BN_REQUIRE(col.tower_level == 0 || col.tower_level == 3, "univariate fold: tower level must be 0 or 3");
 		BN_REQUIRE(col.n_vars <= BN_PE_MAX_VARS, "univariate fold: n_vars out of range");
 		BN_REQUIRE(k <= col.n_vars, "univariate fold: skip_rounds larger than n_vars");
-		BN_REQUIRE((((uintptr_t)col.d_evals | (uintptr_t)d_outs[c]) & 15) == 0, "univariate fold: pointers must be 16-byte aligned");
+		BN_REQUIRE(aligned16(col.d_evals, d_outs[c]), "univariate fold: pointers must be 16-byte aligned");
 		const uint64_t out_len = (uint64_t)1 << (col.n_vars - k);
 		BN_REQUIRE(!ranges_overlap(col.d_evals, column_elems(col.n_vars, col.tower_level), d_outs[c], out_len), "univariate fold: an output overlaps its column");
 		const uint64_t unit_rows = 256u * bn::uf_rows_per_thread(k + col.tower_level);
@@ -51,13 +43,12 @@ int bn_univariate_fold_batch(bn_ctx *ctx, const void *cols_, uint32_t n_cols, ui
 	std::vector<uint32_t> order(n_cols);
 	for (uint32_t c = 0; c < n_cols; c++) order[c] = c;
 	std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cols[x].tower_level < cols[y].tower_level; });
-	const size_t o_jobs = align_up(((size_t)1 << k) * sizeof(bn_f128));
-	const size_t bytes = align_up(o_jobs + (size_t)n_cols * sizeof(bn::uf_job));
-	char *scr = (char *)bn::ctx_scratch(ctx, bytes);
-	if (!scr) return bn::fail(BN_ERR_ALLOC, "allocation error: allocator is out of memory (scratch)");
-	std::vector<char> host(bytes, 0);
-	memcpy(host.data(), h_coeffs, ((size_t)1 << k) * sizeof(bn_f128));
-	bn::uf_job *jobs = (bn::uf_job *)&host[o_jobs];
+	call_upload up(ctx);
+	const auto s_coeffs = up.reserve<bn_f128>((size_t)1 << k);
+	const auto s_jobs = up.reserve<bn::uf_job>(n_cols);
+	if (const int rc = up.alloc()) return rc;
+	std::copy(h_coeffs, h_coeffs + ((size_t)1 << k), up.host(s_coeffs));
+	bn::uf_job *jobs = up.host(s_jobs);
 	uint32_t at_unit = 0;
 	for (uint32_t i = 0; i < n_cols; i++) {
 		const bn_pe_column &col = cols[order[i]];
@@ -72,8 +63,8 @@ int bn_univariate_fold_batch(bn_ctx *ctx, const void *cols_, uint32_t n_cols, ui
 	}
 	const uint32_t per_cu = lds_tables * 256 <= 32768 ? 3 : 2; // (about 160 registers per thread: three workgroups of a CU at most)
 	const uint32_t n_wgs = (uint32_t)std::min<uint64_t>(at_unit, (uint64_t)ctx->n_cu * per_cu);
-	BN_HIP(hipMemcpyAsync(scr, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-	BN_HIP(bn::launch_univariate_fold(ctx->stream, (const bn::uf_job *)(scr + o_jobs), n_cols, scr, k, at_unit, n_wgs, lds_tables));
+	BN_HIP(up.send());
+	BN_HIP(bn::launch_univariate_fold(ctx->stream, up.dev(s_jobs), n_cols, up.dev(s_coeffs), k, at_unit, n_wgs, lds_tables));
 	BN_HIP(hipStreamSynchronize(ctx->stream)); // (the tables are pageable host memory that goes out of scope; the outputs are complete on return)
 	ctx->uf_calls++;
 	ctx->uf_launches++;

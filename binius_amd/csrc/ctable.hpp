@@ -32,6 +32,21 @@ __device__ __forceinline__ f128 to_f128(uint4 v)
 }
 __device__ __forceinline__ uint4 xor4(uint4 a, uint4 b) { return uint4{a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w}; }
 
+// Entry e of a 16-entry nibble table: the XOR of the table's basis products k whose bit is set in e.  Product k is b[k], or, IN_PLACE,
+// b[1 << k]: b is then the table itself, whose entries 1, 2, 4, 8 are the products.
+// (ctable_build and ctable_build_group below spell the same four lines out: every fold kernel builds its table through them, and with
+// this call in their loops the compiler schedules those kernels differently.)
+template <bool IN_PLACE = false>
+__device__ __forceinline__ uint4 ctable_entry(const uint4 *b, unsigned e)
+{
+	uint4 v{0, 0, 0, 0};
+	if (e & 1) v = xor4(v, b[IN_PLACE ? 1 : 0]);
+	if (e & 2) v = xor4(v, b[IN_PLACE ? 2 : 1]);
+	if (e & 4) v = xor4(v, b[IN_PLACE ? 4 : 2]);
+	if (e & 8) v = xor4(v, b[IN_PLACE ? 8 : 3]);
+	return v;
+}
+
 // Group form: `nthreads` (>= 128) consecutive threads, numbered ltid, build table s for z; every
 // thread of the workgroup must call it (it contains workgroup barriers), threads outside any group
 // pass ltid >= nthreads.  Several groups can build different tables at the same time.
@@ -90,10 +105,55 @@ __device__ __forceinline__ uint32_t byte_and(uint32_t w, uint32_t m)
 
 __device__ __forceinline__ uint32_t ct_xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
 
+// off[p] = the table offset (nibble * 16) of nibble p of w, p < N: one rotate by 4 (the low nibbles become the high nibbles of the
+// rotated word's bytes) and one SDWA byte-select per nibble.
+template <int N = 8>
+__device__ __forceinline__ void ctable_offsets(uint32_t *off, uint32_t w)
+{
+	static_assert(N == 2 || N == 4 || N == 8, "a byte, a half word or a word");
+	const uint32_t m = 0xF0u;
+	const uint32_t rot = __builtin_amdgcn_alignbit(w, w, 28); // rotl(w, 4)
+	off[0] = byte_and<0>(rot, m);
+	off[1] = byte_and<0>(w, m);
+	if constexpr (N >= 4) {
+		off[2] = byte_and<1>(rot, m);
+		off[3] = byte_and<1>(w, m);
+	}
+	if constexpr (N == 8) {
+		off[4] = byte_and<2>(rot, m);
+		off[5] = byte_and<2>(w, m);
+		off[6] = byte_and<3>(rot, m);
+		off[7] = byte_and<3>(w, m);
+	}
+}
+
+// acc ^= XOR over the low NIB nibbles of w of their entries in the tables that start at `base` (table p = nibble p): the partial
+// lookup of the ops whose operand is narrower than 128 bits or whose tables belong to several constants.
+template <int NIB>
+__device__ __forceinline__ void ctable_lookup(uint4 &acc, const char *base, uint32_t w)
+{
+	static_assert(NIB == 1 || NIB == 2 || NIB == 4 || NIB == 8, "a nibble, a byte, a half word or a word");
+	if constexpr (NIB == 1) {
+		acc = xor4(acc, *reinterpret_cast<const uint4 *>(base + ((w & 15u) << 4)));
+	} else {
+		uint32_t off[NIB];
+		ctable_offsets<NIB>(off, w);
+		uint4 t[NIB];
+#pragma unroll
+		for (int j = 0; j < NIB; j++) t[j] = *reinterpret_cast<const uint4 *>(base + j * 256 + off[j]);
+#pragma unroll
+		for (int j = 0; j < NIB; j += 2) {
+			acc.x = ct_xor3(acc.x, t[j].x, t[j + 1].x);
+			acc.y = ct_xor3(acc.y, t[j].y, t[j + 1].y);
+			acc.z = ct_xor3(acc.z, t[j].z, t[j + 1].z);
+			acc.w = ct_xor3(acc.w, t[j].w, t[j + 1].w);
+		}
+	}
+}
+
 // x * z via 32 conflict-free ds_read_b128.  ~105 VALU per element: per 32-bit word one rotate by 4
-// (its low nibbles become the high nibbles of the rotated word's bytes), eight SDWA byte-selects
-// that produce nibble*16 directly, and the 32 looked-up entries folded two at a time with the
-// three-input XOR (v_bitop3_b32).
+// and eight SDWA byte-selects that produce nibble*16 directly (ctable_offsets), and the 32 looked-up
+// entries folded two at a time with the three-input XOR (v_bitop3_b32).
 // The lookups are issued in groups of G (default 16 = two words) before anything consumes them: a
 // dependent read-xor chain would keep only 2-4 reads in flight and turn the multiplication into
 // 8-16 serialized LDS round trips (measured: the fused fold+eval kernel 222 -> see profiles/r01).
@@ -104,24 +164,12 @@ __device__ __forceinline__ uint4 ctable_mul(const ctable_smem &s, uint4 x)
 	const char *base = reinterpret_cast<const char *>(s.T);
 	uint4 acc{0, 0, 0, 0};
 	const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-	const uint32_t m = 0xF0u;
 	constexpr int WPG = G / 8; // words per group
 #pragma unroll
 	for (int w0 = 0; w0 < 4; w0 += WPG) {
 		uint32_t off[G];
 #pragma unroll
-		for (int wq = 0; wq < WPG; wq++) {
-			const uint32_t hi = w[w0 + wq];
-			const uint32_t lo = __builtin_amdgcn_alignbit(hi, hi, 28); // rotl(w, 4)
-			off[8 * wq + 0] = byte_and<0>(lo, m);
-			off[8 * wq + 1] = byte_and<0>(hi, m);
-			off[8 * wq + 2] = byte_and<1>(lo, m);
-			off[8 * wq + 3] = byte_and<1>(hi, m);
-			off[8 * wq + 4] = byte_and<2>(lo, m);
-			off[8 * wq + 5] = byte_and<2>(hi, m);
-			off[8 * wq + 6] = byte_and<3>(lo, m);
-			off[8 * wq + 7] = byte_and<3>(hi, m);
-		}
+		for (int wq = 0; wq < WPG; wq++) ctable_offsets(off + 8 * wq, w[w0 + wq]);
 		uint4 t[G];
 #pragma unroll
 		for (int j = 0; j < G; j++) // byte offset of entry: table (8*word + nibble_index) * 256 + nibble * 16
@@ -149,21 +197,9 @@ __device__ __forceinline__ uint4 ctable_mul_pinned(const ctable_smem &s, uint4 x
 	static_assert(G == 4 || G == 8, "half a word or one word of lookups per group");
 	const char *base = reinterpret_cast<const char *>(s.T);
 	const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-	const uint32_t m = 0xF0u;
 	uint32_t off[32];
 #pragma unroll
-	for (int wq = 0; wq < 4; wq++) {
-		const uint32_t hi = w[wq];
-		const uint32_t lo = __builtin_amdgcn_alignbit(hi, hi, 28); // rotl(w, 4)
-		off[8 * wq + 0] = byte_and<0>(lo, m);
-		off[8 * wq + 1] = byte_and<0>(hi, m);
-		off[8 * wq + 2] = byte_and<1>(lo, m);
-		off[8 * wq + 3] = byte_and<1>(hi, m);
-		off[8 * wq + 4] = byte_and<2>(lo, m);
-		off[8 * wq + 5] = byte_and<2>(hi, m);
-		off[8 * wq + 6] = byte_and<3>(lo, m);
-		off[8 * wq + 7] = byte_and<3>(hi, m);
-	}
+	for (int wq = 0; wq < 4; wq++) ctable_offsets(off + 8 * wq, w[wq]);
 	uint4 acc{0, 0, 0, 0};
 	uint4 cur[G], nxt[G];
 #pragma unroll
@@ -192,9 +228,11 @@ __device__ __forceinline__ uint4 ctable_mul_pinned(const ctable_smem &s, uint4 x
 	return acc;
 }
 
-// Variant of ctable_mul_pinned for measurements (tools/gram_bench.hip, FE_VARIANT): returns init ^ x * z -- the fold's
-// "x0 +" rides in the first three-input XOR instead of costing four more --, and with LAZY the table offsets of a group are
-// formed right before its reads are issued (4 live offset registers instead of 32).
+// The form of ctable_mul_pinned that the group and FP4 fold+evaluate kernels use (kernels_group.hip, kernels_foldeval_fp4.hip; also
+// tools/gram_bench.hip and the FE_VARIANT builds): returns init ^ x * z -- the fold's "x0 +" rides in the first three-input XOR
+// instead of costing four more --, and with LAZY the table offsets of a group are formed right before its reads are issued (4 live
+// offset registers instead of 32).  Its offsets are picked one at a time, so it does not go through ctable_offsets: with that call
+// the kernels that use it are scheduled differently.
 template <int G, bool LAZY>
 __device__ __forceinline__ uint4 ctable_mul_acc(const ctable_smem &s, uint4 x, uint4 init)
 {

@@ -15,6 +15,7 @@
 // k_bits_to_b128: dst[i] = bit i ? ONE : ZERO, the bit columns as B128 multilinears for the prover's sumchecks.
 #include <hip/hip_runtime.h>
 
+#include "batch.hpp"
 #include "gf128.hpp"
 #include "internal.hpp"
 #include "mul9_wave.hpp"
@@ -26,25 +27,6 @@ namespace {
 static_assert(kWB == (int)kExpRun, "units are planned on the host");
 constexpr unsigned kStageQ4 = 2 * kWB;                 // the two staged operands of a wave, 224 elements each
 constexpr unsigned kExpWaveQ4 = kWaveQ4 + kStageQ4;    // 576 + 448 uint4 = 16 KiB per wave
-
-template <typename JOB>
-__device__ __forceinline__ uint32_t find_job(const JOB *__restrict__ jobs, uint32_t n_jobs, uint32_t u)
-{
-	uint32_t lo = 0, hi = n_jobs;
-	while (hi - lo > 1) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (jobs[mid].start <= u)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-__device__ __forceinline__ uint64_t uni64(uint64_t v)
-{
-	return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32);
-}
 
 __device__ __forceinline__ uint4 sel_one(bool bit, uint4 c)
 {
@@ -65,9 +47,9 @@ __global__ __launch_bounds__(256, 2) void k_expcircuit(const expc_job *__restric
 	for (uint32_t u = blockIdx.x * 4 + wave; u < total_units; u += gridDim.x * 4) {
 		const expc_job &jb = jobs[find_job(jobs, n_jobs, u)];
 		// (uniform per wave: into scalar registers)
-		const uint32_t width = (uint32_t)__builtin_amdgcn_readfirstlane((int)jb.width);
-		const bool dynamic = __builtin_amdgcn_readfirstlane((int)jb.dynamic) != 0;
-		const uint32_t start = (uint32_t)__builtin_amdgcn_readfirstlane((int)jb.start);
+		const uint32_t width = uni32(jb.width);
+		const bool dynamic = uni32(jb.dynamic) != 0;
+		const uint32_t start = uni32(jb.start);
 		const uint64_t rows = uni64(jb.rows);
 		const uint32_t *const *bits = (const uint32_t *const *)uni64((uint64_t)jb.bits);
 		const uint4 *base = (const uint4 *)uni64((uint64_t)jb.base);

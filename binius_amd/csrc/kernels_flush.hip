@@ -18,6 +18,7 @@
 // sums stay where they are, so the output is still written once, with plain 16-byte stores.
 #include <hip/hip_runtime.h>
 
+#include "batch.hpp"
 #include "ctable.hpp"
 #include "gf128.hpp"
 #include "internal.hpp"
@@ -33,55 +34,6 @@ struct flush_smem {
 	uint4 T[kFlushPassTables * 16]; // [table][entry]
 	uint4 basis[128];               // coeff * 2^i of the column being built
 };
-
-template <typename JOB>
-__device__ __forceinline__ uint32_t fl_find(const JOB *__restrict__ jobs, uint32_t n_jobs, uint32_t u)
-{
-	uint32_t lo = 0, hi = n_jobs;
-	while (hi - lo > 1) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (jobs[mid].start <= u)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return (uint64_t)uni32((uint32_t)v) | ((uint64_t)uni32((uint32_t)(v >> 32)) << 32); }
-
-// acc ^= XOR over the low NIB nibbles of w of their entries in the tables that start at `base` (table p = nibble p)
-template <int NIB>
-__device__ __forceinline__ void fl_lookup(uint4 &acc, const char *base, uint32_t w)
-{
-	static_assert(NIB == 2 || NIB == 4 || NIB == 8, "a byte, a half word or a word");
-	const uint32_t m = 0xF0u;
-	const uint32_t rot = __builtin_amdgcn_alignbit(w, w, 28); // rotl(w, 4): the low nibbles become the high nibbles of its bytes
-	uint32_t off[NIB];
-	off[0] = byte_and<0>(rot, m);
-	off[1] = byte_and<0>(w, m);
-	if constexpr (NIB >= 4) {
-		off[2] = byte_and<1>(rot, m);
-		off[3] = byte_and<1>(w, m);
-	}
-	if constexpr (NIB == 8) {
-		off[4] = byte_and<2>(rot, m);
-		off[5] = byte_and<2>(w, m);
-		off[6] = byte_and<3>(rot, m);
-		off[7] = byte_and<3>(w, m);
-	}
-	uint4 t[NIB];
-#pragma unroll
-	for (int j = 0; j < NIB; j++) t[j] = *reinterpret_cast<const uint4 *>(base + j * 256 + off[j]);
-#pragma unroll
-	for (int j = 0; j < NIB; j += 2) {
-		acc.x = ct_xor3(acc.x, t[j].x, t[j + 1].x);
-		acc.y = ct_xor3(acc.y, t[j].y, t[j + 1].y);
-		acc.z = ct_xor3(acc.z, t[j].z, t[j + 1].z);
-		acc.w = ct_xor3(acc.w, t[j].w, t[j + 1].w);
-	}
-}
 
 // The rows of a thread are r0 + tid + 256 k; a row at or beyond `limit` reads row r0 instead (valid: r0 < limit) and is never stored,
 // so neither the loads nor the lookups are under a branch: the eight loads of a column are in flight together.
@@ -127,23 +79,23 @@ __device__ __forceinline__ void fl_apply(uint4 (&acc)[kRowsPerThread], const uin
 			acc[k] = xor4(acc[k], uint4{coeff.x & m, coeff.y & m, coeff.z & m, coeff.w & m});
 		} else if constexpr (LEVEL <= 5) {
 			if (tab)
-				fl_lookup<(LEVEL == 3 ? 2 : LEVEL == 4 ? 4 : 8)>(acc[k], tab, x[k].x);
+				ctable_lookup<(LEVEL == 3 ? 2 : LEVEL == 4 ? 4 : 8)>(acc[k], tab, x[k].x);
 			else
 				acc[k].x ^= x[k].x;
 		} else if constexpr (LEVEL == 6) {
 			if (tab) {
-				fl_lookup<8>(acc[k], tab, x[k].x);
-				fl_lookup<8>(acc[k], tab + 8 * 256, x[k].y);
+				ctable_lookup<8>(acc[k], tab, x[k].x);
+				ctable_lookup<8>(acc[k], tab + 8 * 256, x[k].y);
 			} else {
 				acc[k].x ^= x[k].x;
 				acc[k].y ^= x[k].y;
 			}
 		} else {
 			if (tab) {
-				fl_lookup<8>(acc[k], tab, x[k].x);
-				fl_lookup<8>(acc[k], tab + 8 * 256, x[k].y);
-				fl_lookup<8>(acc[k], tab + 16 * 256, x[k].z);
-				fl_lookup<8>(acc[k], tab + 24 * 256, x[k].w);
+				ctable_lookup<8>(acc[k], tab, x[k].x);
+				ctable_lookup<8>(acc[k], tab + 8 * 256, x[k].y);
+				ctable_lookup<8>(acc[k], tab + 16 * 256, x[k].z);
+				ctable_lookup<8>(acc[k], tab + 24 * 256, x[k].w);
 			} else {
 				acc[k] = xor4(acc[k], x[k]);
 			}
@@ -170,7 +122,7 @@ __device__ __forceinline__ void fl_load_any(uint4 (&x)[kRowsPerThread], const fl
 __global__ __launch_bounds__(256) void k_flush_prefix(const flush_sel *__restrict__ sels, uint32_t n_sels)
 {
 	__shared__ unsigned long long best[4];
-	const flush_sel &sl = sels[fl_find(sels, n_sels, blockIdx.x)];
+	const flush_sel &sl = sels[find_job(sels, n_sels, blockIdx.x)];
 	const uint4 *col = (const uint4 *)uni64((uint64_t)sl.col);
 	const uint64_t elems = uni64(sl.elems);
 	const uint64_t c0 = (uint64_t)(blockIdx.x - uni32(sl.start)) * kFlushSelChunk;
@@ -197,7 +149,7 @@ __global__ __launch_bounds__(256, 2) void k_flush_witness(const flush_job *__res
 {
 	extern __shared__ uint4 fl_lds[];
 	flush_smem &sm = *reinterpret_cast<flush_smem *>(fl_lds);
-	const flush_job &jb = jobs[fl_find(jobs, n_jobs, blockIdx.x)];
+	const flush_job &jb = jobs[find_job(jobs, n_jobs, blockIdx.x)];
 	const uint64_t rows = uni64(jb.rows);
 	const uint32_t n_sels = uni32(jb.n_sels), n_passes = uni32(jb.n_passes);
 	const flush_col *cols = (const flush_col *)uni64((uint64_t)jb.cols);
@@ -230,15 +182,7 @@ __global__ __launch_bounds__(256, 2) void k_flush_witness(const flush_job *__res
 			const uint32_t bits = 1u << uni32(cols[c].level), entries = bits << 2; // 2^l / 4 tables of 16 entries
 			if (threadIdx.x < bits) sm.basis[threadIdx.x] = to_u4(mul_basis(cols[c].coeff, threadIdx.x));
 			__syncthreads();
-			for (uint32_t e = threadIdx.x; e < entries; e += 256) {
-				const unsigned p4 = (e >> 4) << 2;
-				uint4 v{0, 0, 0, 0};
-				if (e & 1) v = xor4(v, sm.basis[p4]);
-				if (e & 2) v = xor4(v, sm.basis[p4 + 1]);
-				if (e & 4) v = xor4(v, sm.basis[p4 + 2]);
-				if (e & 8) v = xor4(v, sm.basis[p4 + 3]);
-				sm.T[table * 16 + e] = v;
-			}
+			for (uint32_t e = threadIdx.x; e < entries; e += 256) sm.T[table * 16 + e] = ctable_entry(sm.basis + ((e >> 4) << 2), e);
 			__syncthreads(); // (the basis is rewritten by the next column; the tables are read below)
 		}
 		// ---- the columns of this pass into the sums: column c + 1 is loaded before column c is looked up

@@ -124,13 +124,7 @@ __global__ __launch_bounds__(TH) void k_fold_tab(const uint64_t *mat, const uint
 		__syncthreads();
 		for (unsigned q = tid; q < jn * P * 16; q += TH) {
 			const unsigned e = q & 15, p = (q >> 4) % P, jj = q / (16 * P);
-			const uint4 *bp = basis + jj * NB + 4 * p;
-			uint4 v{0, 0, 0, 0};
-			if (e & 1) v = xor4(v, bp[0]);
-			if (e & 2) v = xor4(v, bp[1]);
-			if (e & 4) v = xor4(v, bp[2]);
-			if (e & 8) v = xor4(v, bp[3]);
-			T[q] = v;
+			T[q] = ctable_entry(basis + jj * NB + 4 * p, e);
 		}
 		__syncthreads();
 #pragma unroll
@@ -184,18 +178,8 @@ __global__ __launch_bounds__(TH) void k_fold_tab(const uint64_t *mat, const uint
 					for (int kk = 0; kk < KG; kk++) {
 						const bool on = g0 + k + kk < jn; // (beyond the chunk: mm = 0 -> entry 0 of table 0 = vec * 0 = 0)
 						const char *tb = reinterpret_cast<const char *>(T + (on ? (g0 + k + kk) : 0) * P * 16);
-						// nibble * 16 of every nibble in one instruction each (ctable.hpp: a rotate by four puts the even nibbles
-						// where the odd ones are, an SDWA byte-select masks the high nibble of a byte in place)
-						const uint32_t hi = mm[k + kk], lo = __builtin_amdgcn_alignbit(hi, hi, 28);
-						uint32_t off[8];
-						off[0] = byte_and<0>(lo, 0xF0u);
-						off[1] = byte_and<0>(hi, 0xF0u);
-						off[2] = byte_and<1>(lo, 0xF0u);
-						off[3] = byte_and<1>(hi, 0xF0u);
-						off[4] = byte_and<2>(lo, 0xF0u);
-						off[5] = byte_and<2>(hi, 0xF0u);
-						off[6] = byte_and<3>(lo, 0xF0u);
-						off[7] = byte_and<3>(hi, 0xF0u);
+						uint32_t off[8]; // (nibble * 16 of every nibble in one instruction each)
+						ctable_offsets(off, mm[k + kk]);
 #pragma unroll
 						for (int p = 0; p < P; p++) t[kk * P + p] = *reinterpret_cast<const uint4 *>(tb + p * 256 + off[p]);
 					}

@@ -18,6 +18,7 @@
 
 #include <cstdlib>
 
+#include "batch.hpp"
 #include "bitslice.hpp"
 #include "internal.hpp"
 #include "mul9_wave.hpp"
@@ -108,17 +109,13 @@ __global__ __launch_bounds__(256, 2) void k_mul9_jobs(const mul9_job *__restrict
 	for (uint64_t bt = (uint64_t)blockIdx.x * 4 + wave; bt < total; bt += n_waves) {
 		const uint32_t j = (uint32_t)(bt / per_job);
 		const uint64_t e0 = (bt - (uint64_t)j * per_job) * kWB;
-		auto uni = [](const void *p) { // (uniform per wave: into scalar registers)
-			const uint64_t v = (uint64_t)p;
-			return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32);
-		};
 		if (j != cur) {
-			cur = j;
-			a = (const uint32_t *)uni(jobs[j].a);
-			b = (const uint32_t *)uni(jobs[j].b);
-			out = (uint32_t *)uni(jobs[j].out);
-			a2 = (const uint32_t *)uni(jobs[j].a2);
-			b2 = (const uint32_t *)uni(jobs[j].b2);
+			cur = j; // (uniform per wave: the pointers into scalar registers)
+			a = (const uint32_t *)uni64((uint64_t)jobs[j].a);
+			b = (const uint32_t *)uni64((uint64_t)jobs[j].b);
+			out = (uint32_t *)uni64((uint64_t)jobs[j].out);
+			a2 = (const uint32_t *)uni64((uint64_t)jobs[j].a2);
+			b2 = (const uint32_t *)uni64((uint64_t)jobs[j].b2);
 		}
 		mw.batch(a, b, out, e0, n, a2, b2);
 	}
@@ -142,17 +139,13 @@ __global__ __launch_bounds__(256, 2) void k_mul9_jobs_dual(const mul9_job *__res
 	for (uint64_t st = (uint64_t)blockIdx.x * 4 + wave; st < total; st += n_waves) {
 		const uint32_t j = (uint32_t)(st / per_job);
 		const uint64_t e0 = (st - (uint64_t)j * per_job) * 2 * kWB;
-		auto uni = [](const void *p) {
-			const uint64_t v = (uint64_t)p;
-			return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32);
-		};
 		if (j != cur) {
 			cur = j;
-			a = (const uint32_t *)uni(jobs[j].a);
-			b = (const uint32_t *)uni(jobs[j].b);
-			out = (uint32_t *)uni(jobs[j].out);
-			a2 = (const uint32_t *)uni(jobs[j].a2);
-			b2 = (const uint32_t *)uni(jobs[j].b2);
+			a = (const uint32_t *)uni64((uint64_t)jobs[j].a);
+			b = (const uint32_t *)uni64((uint64_t)jobs[j].b);
+			out = (uint32_t *)uni64((uint64_t)jobs[j].out);
+			a2 = (const uint32_t *)uni64((uint64_t)jobs[j].a2);
+			b2 = (const uint32_t *)uni64((uint64_t)jobs[j].b2);
 		}
 		mw.batch2(a, b, out, e0, n, a2, b2);
 	}

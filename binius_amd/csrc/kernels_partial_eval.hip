@@ -18,6 +18,7 @@
 // slices combined at the end.
 #include <hip/hip_runtime.h>
 
+#include "batch.hpp"
 #include "ctable.hpp"
 #include "gf128.hpp"
 #include "internal.hpp"
@@ -25,22 +26,6 @@
 namespace bn {
 
 namespace {
-
-__device__ __forceinline__ uint32_t pe_find_group(const pe_group *__restrict__ groups, uint32_t n_groups, uint32_t u)
-{
-	uint32_t lo = 0, hi = n_groups;
-	while (hi - lo > 1) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (groups[mid].start <= u)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return (uint64_t)uni32((uint32_t)v) | ((uint64_t)uni32((uint32_t)(v >> 32)) << 32); }
 
 constexpr uint32_t kStageMask = (1u << kPeLogVecChunk) - 1;
 // the 64-bit word lane k loaded, in a scalar register pair
@@ -159,7 +144,7 @@ __global__ __launch_bounds__(256, BITS_ONLY ? 4 : 2) void k_partial_eval(const p
 	__shared__ uint4 lvec[1u << kPeLogVecChunk];
 	__shared__ uint4 red[256];
 	pe_group g = one_group;
-	if (groups) g = groups[pe_find_group(groups, n_groups, blockIdx.x)];
+	if (groups) g = groups[find_job(groups, n_groups, blockIdx.x)];
 	const uint32_t first = uni32(g.first), count = uni32(g.count), level = uni32(g.level), b = uni32(g.b), log_ch = uni32(g.log_ch);
 	const uint32_t ch = 1u << log_ch;
 	const uint64_t j0 = (uint64_t)(blockIdx.x - uni32(g.start)) << log_ch;

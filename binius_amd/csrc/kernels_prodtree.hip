@@ -6,7 +6,8 @@
 //
 // The independence used: for a fixed residue r mod 2^s, the elements {r + t 2^s} of layer s + T are a complete subtree
 // down to element r of layer s.  Whoever owns a set of residues produces T layers from one read of layer s + T with no
-// grid-wide dependency in between.  Two forms, both driven by a job table so that one launch serves every tree of a batch:
+// grid-wide dependency in between.  Two forms, both driven by a job table so that one launch serves every tree of a batch (a unit
+// of batch.hpp is a workgroup of the small form, a run of the big one):
 //
 // * k_prodtree_big (layers above 2^15 elements): a workgroup owns a run of 448 contiguous residues (896 in the two-batch form of
 //   the product); its four waves take the four wave-batches of the 2 x 448 products of the first layer (two chunks of 448
@@ -22,6 +23,7 @@
 // product with ONE is a copy of the other operand (or ONE), done by the wave next to its bit-sliced batch.  Inputs are only read.
 #include <hip/hip_runtime.h>
 
+#include "batch.hpp"
 #include "gf128.hpp"
 #include "groupmul.hpp"
 #include "internal.hpp"
@@ -34,25 +36,6 @@ namespace {
 constexpr uint32_t kSmallLogS = kProdtreeSmallLevels; // 2^6 elements per workgroup
 constexpr uint32_t kSmallThreads = 256;
 static_assert(kWB == (int)kProdtreeBatch, "run sizes are planned on the host");
-
-// the job of unit `u` (a workgroup of the small form, a run of the big one): jobs[j].start <= u < jobs[j + 1].start
-__device__ __forceinline__ uint32_t find_job(const prodtree_job *__restrict__ jobs, uint32_t n_jobs, uint32_t u)
-{
-	uint32_t lo = 0, hi = n_jobs;
-	while (hi - lo > 1) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (jobs[mid].start <= u)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-__device__ __forceinline__ uint64_t uni64(uint64_t v)
-{
-	return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32);
-}
 
 // One layer inside a workgroup: product q = src[q] * src[q + n_prod], kept in LDS for the next layer and stored to the
 // arena (element q of this residue's subtree lies q << s elements into the layer).
@@ -125,8 +108,8 @@ __global__ __launch_bounds__(256, 2) void k_prodtree_big(const prodtree_job *__r
 	for (uint32_t k = blockIdx.x; k < total_runs; k += gridDim.x) {
 		const prodtree_job &jb = jobs[find_job(jobs, n_jobs, k)];
 		// (uniform per workgroup: into scalar registers)
-		const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)jb.m), T = (uint32_t)__builtin_amdgcn_readfirstlane((int)jb.n_levels);
-		const uint32_t start = (uint32_t)__builtin_amdgcn_readfirstlane((int)jb.start);
+		const uint32_t m = uni32(jb.m), T = uni32(jb.n_levels);
+		const uint32_t start = uni32(jb.start);
 		const uint64_t src_len = uni64(jb.src_len);
 		const f128 *src0 = (const f128 *)uni64((uint64_t)jb.src);
 		f128 *arena = (f128 *)uni64((uint64_t)jb.arena);

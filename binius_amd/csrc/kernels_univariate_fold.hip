@@ -24,6 +24,7 @@
 // kept the address arithmetic of every case live and spilled.
 #include <hip/hip_runtime.h>
 
+#include "batch.hpp"
 #include "ctable.hpp"
 #include "gf128.hpp"
 #include "internal.hpp"
@@ -32,59 +33,8 @@ namespace bn {
 
 namespace {
 
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return (uint64_t)uni32((uint32_t)v) | ((uint64_t)uni32((uint32_t)(v >> 32)) << 32); }
-
-__device__ __forceinline__ uint32_t uf_find(const uf_job *__restrict__ jobs, uint32_t n_jobs, uint32_t u)
-{
-	uint32_t lo = 0, hi = n_jobs;
-	while (hi - lo > 1) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (jobs[mid].start <= u)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-// acc ^= XOR over the low NIB nibbles of w of their entries in the tables that start at `base` (table p = nibble p)
-template <int NIB>
-__device__ __forceinline__ void uf_lookup(uint4 &acc, const char *base, uint32_t w)
-{
-	static_assert(NIB == 1 || NIB == 2 || NIB == 4 || NIB == 8, "a nibble, a byte, a half word or a word");
-	if constexpr (NIB == 1) {
-		acc = xor4(acc, *reinterpret_cast<const uint4 *>(base + ((w & 15u) << 4)));
-	} else {
-		const uint32_t m = 0xF0u;
-		const uint32_t rot = __builtin_amdgcn_alignbit(w, w, 28); // rotl(w, 4): the low nibbles become the high nibbles of its bytes
-		uint32_t off[NIB];
-		off[0] = byte_and<0>(rot, m);
-		off[1] = byte_and<0>(w, m);
-		if constexpr (NIB >= 4) {
-			off[2] = byte_and<1>(rot, m);
-			off[3] = byte_and<1>(w, m);
-		}
-		if constexpr (NIB == 8) {
-			off[4] = byte_and<2>(rot, m);
-			off[5] = byte_and<2>(w, m);
-			off[6] = byte_and<3>(rot, m);
-			off[7] = byte_and<3>(w, m);
-		}
-		uint4 t[NIB];
-#pragma unroll
-		for (int j = 0; j < NIB; j++) t[j] = *reinterpret_cast<const uint4 *>(base + j * 256 + off[j]);
-#pragma unroll
-		for (int j = 0; j < NIB; j += 2) {
-			acc.x = ct_xor3(acc.x, t[j].x, t[j + 1].x);
-			acc.y = ct_xor3(acc.y, t[j].y, t[j + 1].y);
-			acc.z = ct_xor3(acc.z, t[j].z, t[j + 1].z);
-			acc.w = ct_xor3(acc.w, t[j].w, t[j + 1].w);
-		}
-	}
-	// (pins the schedule: left alone, the scheduler hoists the lookups of all the rows of a batch to the front and spills)
-	asm volatile("" : "+v"(acc.x), "+v"(acc.y), "+v"(acc.z), "+v"(acc.w)::"memory");
-}
+// After every ctable_lookup: pins the schedule.  Left alone, the scheduler hoists the lookups of all the rows of a batch to the front and spills.
+__device__ __forceinline__ void uf_pin(uint4 &acc) { asm volatile("" : "+v"(acc.x), "+v"(acc.y), "+v"(acc.z), "+v"(acc.w)::"memory"); }
 
 // The part of row x that one pass covers: B bits (B < 32: in the low bits of w[0]).  ROW_U4: 16-byte vectors of a whole row (B >= 128),
 // first_u4: where the pass begins inside the row.
@@ -133,10 +83,14 @@ __device__ __forceinline__ void uf_rows(uint4 (&acc)[8], const char *__restrict_
 #pragma unroll
 		for (int r = 0; r < R; r++) {
 			if constexpr (B < 32) {
-				uf_lookup<(B <= 4 ? 1 : B / 4)>(acc[j0 + r], T, w[r][0]);
+				ctable_lookup<(B <= 4 ? 1 : B / 4)>(acc[j0 + r], T, w[r][0]);
+				uf_pin(acc[j0 + r]);
 			} else {
 #pragma unroll
-				for (int q = 0; q < NW; q++) uf_lookup<8>(acc[j0 + r], T + q * 8 * 256, w[r][q]);
+				for (int q = 0; q < NW; q++) {
+					ctable_lookup<8>(acc[j0 + r], T + q * 8 * 256, w[r][q]);
+					uf_pin(acc[j0 + r]);
+				}
 			}
 		}
 	}
@@ -164,13 +118,7 @@ __device__ __forceinline__ void uf_build(uint4 *__restrict__ T, const uint4 *__r
 	for (uint32_t i = threadIdx.x; i < n_tables * 16; i += 256) {
 		const uint32_t e = i & 15;
 		if (e && !(e & (e - 1))) continue; // (a basis entry)
-		const uint4 *bp = T + (i & ~15u);
-		uint4 v{0, 0, 0, 0};
-		if (e & 1) v = xor4(v, bp[1]);
-		if (e & 2) v = xor4(v, bp[2]);
-		if (e & 4) v = xor4(v, bp[4]);
-		if (e & 8) v = xor4(v, bp[8]);
-		T[i] = v;
+		T[i] = ctable_entry<true>(T + (i & ~15u), e);
 	}
 	__syncthreads();
 }
@@ -195,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void k_univariate_fold(const uf_job *__rest
 	const uint32_t u_begin = (uint32_t)((uint64_t)blockIdx.x * total_units / gridDim.x);
 	const uint32_t u_end = (uint32_t)((uint64_t)(blockIdx.x + 1) * total_units / gridDim.x);
 	if (u_begin >= u_end) return;
-	uint32_t j = uf_find(jobs, n_jobs, u_begin);
+	uint32_t j = find_job(jobs, n_jobs, u_begin);
 	uint32_t built = ~0u; // 2 * level + pass of the tables in LDS
 #pragma unroll 1
 	for (uint32_t u = u_begin; u < u_end; u++) {
