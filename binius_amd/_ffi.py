@@ -180,6 +180,7 @@ def lib():
         "bn_group_counters": [vp, C.POINTER(u64)],
         "bn_fp4_last_grids": [vp, C.POINTER(u64)],
         "bn_ntt_counters": [vp, C.POINTER(u64)],
+        "bn_fri_counters": [vp, C.POINTER(u64)],
         "bn_xor_reduce": [vp, vp, u32, u32, PF],
         "bn_host_scratch": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)],
         "bn_device_numa_node": [C.c_int, C.POINTER(C.c_int)],
@@ -213,7 +214,7 @@ ABI_SYMBOLS = [
     "bn_extrapolate_line", "bn_extrapolate_line_batch", "bn_tensor_expand", "bn_inner_product", "bn_fold_left", "bn_fold_right", "bn_fri_fold",
     "bn_compute_composite", "bn_pairwise_product_reduce", "bn_log_chunks_range", "bn_pick_log_chunks",
     "bn_kernel_launch", "bn_ntt_forward", "bn_ntt_inverse", "bn_ntt_s_evals", "bn_scalar_mul", "bn_scalar_invert",
-    "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_ntt_counters", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
+    "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_ntt_counters", "bn_fri_counters", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
     "bn_merkle_build", "bn_groestl256_leaves", "bn_groestl256_compress_layer", "bn_gather_d2h",
     "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals",
     "bn_product_tree_layers", "bn_pad_with_ones", "bn_exp_circuit_layers", "bn_bits_to_b128", "bn_exp_counters",
@@ -574,6 +575,14 @@ class Context:
         c = (C.c_uint64 * 3)()
         _check(lib().bn_ntt_counters(self._h, c))
         return {"bs": int(c[0]), "tiled": int(c[1]), "layer": int(c[2])}
+
+    def fri_counters(self):
+        """Passes launched by the bn_fri_fold calls of this context, by form (bn_fri_counters): one challenge per pass, two / three
+        interleave challenges in one pass, two / three challenges with a butterfly level among them in one pass (ntt3: a measurement
+        form, 0 in the normal build), and the calls without a challenge (one copy each).  Rejected calls count nowhere."""
+        c = (C.c_uint64 * 6)()
+        _check(lib().bn_fri_counters(self._h, c))
+        return {k: int(c[i]) for i, k in enumerate(("one", "inter2", "inter3", "ntt2", "ntt3", "copies"))}
 
     # ---- ComputeLayer
     def copy_h2d(self, src, dst):

@@ -153,6 +153,7 @@ int bn_fri_fold(bn_ctx *ctx, const uint64_t *h_s_evals, uint32_t tw_level, uint3
 	BN_REQUIRE(log_len <= log_domain && log_domain <= BN_NTT_MAX_DIM, "NTT domain too small");
 	if (n_challenges == 0) {
 		BN_HIP(hipMemcpyAsync(d_out, d_in, in_len * sizeof(f128), hipMemcpyDeviceToDevice, ctx->stream));
+		ctx->fri_passes[BN_FRI_COPIES] += 1;
 		return BN_OK;
 	}
 	uint64_t *d_s = nullptr;
@@ -162,7 +163,15 @@ int bn_fri_fold(bn_ctx *ctx, const uint64_t *h_s_evals, uint32_t tw_level, uint3
 	std::vector<f128> ch(n_challenges);
 	for (uint32_t i = 0; i < n_challenges; i++) ch[i] = to_f(&h_challenges[i]);
 	BN_HIP(bn::launch_fri_fold(ctx->stream, d_s, tw_level, log_domain, log_len, log_batch_size, ch.data(), n_challenges, d_in,
-	                           d_out, out_len, pp, ctx->n_cu, ctx->d_mul8));
+	                           d_out, out_len, pp, ctx->n_cu, ctx->d_mul8, ctx->fri_passes));
+	return BN_OK;
+}
+
+int bn_fri_counters(bn_ctx *ctx, uint64_t *counters)
+{
+	BN_REQUIRE(ctx && counters, "null argument");
+	BN_ENTER(ctx);
+	for (int i = 0; i < BN_FRI_N; i++) counters[i] = ctx->fri_passes[i];
 	return BN_OK;
 }
 

@@ -77,6 +77,7 @@ struct bn_ctx {
 	uint64_t *d_s_evals = nullptr;     // the twiddle basis last handed to bn_ntt_* / bn_fri_fold (BN_NTT_MAX_DIM^2 words) ...
 	std::vector<uint64_t> h_s_evals;   // ... and its host copy: an NTT instance's basis is uploaded once, not per call
 	uint64_t ntt_calls_bs = 0, ntt_calls_tiled = 0, ntt_calls_layer = 0; // bn_ntt_* calls served per kernel family (bn_ntt_counters)
+	uint64_t fri_passes[BN_FRI_N] = {}; // bn_fri_fold passes launched per form, and its copies (bn_fri_counters)
 	uint64_t exp_calls = 0, exp_launches = 0, exp_bits_launches = 0;     // bn_exp_circuit_layers / bn_bits_to_b128 (bn_exp_counters)
 	uint64_t flush_calls = 0, flush_launches = 0, flush_served = 0, flush_multipass = 0; // bn_flush_witness_batch (bn_flush_counters)
 	uint64_t pe_calls = 0, pe_launches = 0, pe_cols_kernel = 0, pe_cols_fallback = 0, pe_max_share = 0, pe_routed = 0; // bn_partial_eval_counters
@@ -656,7 +657,8 @@ hipError_t launch_compute_composite_generic(hipStream_t s, const void *const *d_
                                             uint64_t row_len, void *out, const bn_step *d_steps, uint32_t n_steps);
 hipError_t launch_fri_fold(hipStream_t s, const uint64_t *d_s_evals, uint32_t tw_level, uint32_t log_domain,
                            uint32_t log_len, uint32_t log_batch, const f128 *h_challenges, uint32_t n_challenges,
-                           const void *in, void *out, uint64_t out_len, void *scratch, int n_cu, const uint8_t *d_mul8);
+                           const void *in, void *out, uint64_t out_len, void *scratch, int n_cu, const uint8_t *d_mul8,
+                           uint64_t *launched /*[BN_FRI_N]: += the passes launched, by form*/);
 
 // ---- kernels_univariate.hip: the univariate round of the univariate-skip zerocheck (abi_univariate.cpp)
 constexpr uint32_t kUskipMaxSteps = 64; // steps of one composition (one LDS byte per step and lane)

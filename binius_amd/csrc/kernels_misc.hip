@@ -501,8 +501,9 @@ __global__ __launch_bounds__(NW * 64, NTT ? 1 : 2) void k_fri_pass_multi(const u
 	}
 }
 
-// (twiddles of at most 32 bits: B8 / B16 / B32 NTT fields)
-hipError_t run_fri_multi(hipStream_t s, int n_cu, int C, const uint4 *src, uint4 *dst, uint64_t n_out, const fri_level *lv, const uint8_t *d_mul8)
+// (twiddles of at most 32 bits: B8 / B16 / B32 NTT fields)  *form: the BN_FRI_PASS_* of the kernel that was launched
+hipError_t run_fri_multi(hipStream_t s, int n_cu, int C, const uint4 *src, uint4 *dst, uint64_t n_out, const fri_level *lv, const uint8_t *d_mul8,
+                         int *form)
 {
 	bool ntt = false;
 	for (int c = 0; c < C; c++) ntt = ntt || lv[c].s_row != nullptr;
@@ -520,11 +521,13 @@ hipError_t run_fri_multi(hipStream_t s, int n_cu, int C, const uint4 *src, uint4
 			const unsigned g = (unsigned)(want < (uint64_t)n_cu ? want : (uint64_t)n_cu);
 			fri_levels<3> a{{lv[0], lv[1], lv[2]}};
 			hipLaunchKernelGGL((k_fri_pass_multi<3, true, 4>), dim3(g), dim3(256), 65536, s, src, dst, n_out, a, (const uint4 *)d_mul8);
+			*form = BN_FRI_PASS_NTT3;
 		} else {
 			const uint64_t want = (n_wblocks + 7) / 8;
 			const unsigned g = (unsigned)(want < (uint64_t)n_cu ? want : (uint64_t)n_cu);
 			fri_levels<2> a{{lv[0], lv[1]}};
 			hipLaunchKernelGGL((k_fri_pass_multi<2, true, 8>), dim3(g), dim3(512), 65536, s, src, dst, n_out, a, (const uint4 *)d_mul8);
+			*form = BN_FRI_PASS_NTT2;
 		}
 	} else {
 		const uint64_t want = (n_wblocks + 3) / 4;
@@ -532,9 +535,11 @@ hipError_t run_fri_multi(hipStream_t s, int n_cu, int C, const uint4 *src, uint4
 		if (C == 3) {
 			fri_levels<3> a{{lv[0], lv[1], lv[2]}};
 			hipLaunchKernelGGL((k_fri_pass_multi<3, false, 4>), dim3(g), dim3(256), 0, s, src, dst, n_out, a, nullptr);
+			*form = BN_FRI_PASS_INTER3;
 		} else {
 			fri_levels<2> a{{lv[0], lv[1]}};
 			hipLaunchKernelGGL((k_fri_pass_multi<2, false, 4>), dim3(g), dim3(256), 0, s, src, dst, n_out, a, nullptr);
+			*form = BN_FRI_PASS_INTER2;
 		}
 	}
 	return hipGetLastError();
@@ -542,7 +547,7 @@ hipError_t run_fri_multi(hipStream_t s, int n_cu, int C, const uint4 *src, uint4
 
 hipError_t launch_fri_fold(hipStream_t s, const uint64_t *d_s_evals, uint32_t tw_level, uint32_t log_domain,
                            uint32_t log_len, uint32_t log_batch, const f128 *h_challenges, uint32_t n_challenges,
-                           const void *in, void *out, uint64_t out_len, void *scratch, int n_cu, const uint8_t *d_mul8)
+                           const void *in, void *out, uint64_t out_len, void *scratch, int n_cu, const uint8_t *d_mul8, uint64_t *launched)
 {
 	// scratch holds two ping-pong buffers of in_len/2 elements each
 	const uint64_t in_len = out_len << n_challenges;
@@ -584,6 +589,7 @@ hipError_t launch_fri_fold(hipStream_t s, const uint64_t *d_s_evals, uint32_t tw
 			if (ntt_pass) ll -= 1;
 		}
 		hipError_t e;
+		int form = BN_FRI_PASS_ONE;
 		if (C == 1) {
 			uint64_t want = (n_out + 255) / 256;
 			unsigned g = (unsigned)(want < 2048 ? want : 2048);
@@ -600,9 +606,10 @@ hipError_t launch_fri_fold(hipStream_t s, const uint64_t *d_s_evals, uint32_t tw
 			e = hipGetLastError();
 		} else {
 			if (tw_level < 3 || tw_level > 6) return hipErrorInvalidValue;
-			e = run_fri_multi(s, n_cu, (int)C, src, dst, n_out, lv, d_mul8);
+			e = run_fri_multi(s, n_cu, (int)C, src, dst, n_out, lv, d_mul8, &form);
 		}
 		if (e != hipSuccess) return e;
+		launched[form] += 1;
 		src = dst;
 		cur = n_out;
 		c += C;

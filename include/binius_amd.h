@@ -510,6 +510,13 @@ int bn_fp4_last_grids(bn_ctx *ctx, uint64_t *grids /*[BN_FP4_N]*/);
  * counts nowhere. */
 enum { BN_NTT_CALLS_BS = 0, BN_NTT_CALLS_TILED = 1, BN_NTT_CALLS_LAYER = 2, BN_NTT_N = 3 };
 int bn_ntt_counters(bn_ctx *ctx, uint64_t *counters /*[BN_NTT_N]*/);
+/* The passes that the bn_fri_fold calls of this context have launched since it was created, by form: one challenge per pass
+ * (PASS_ONE), two or three interleave challenges in one pass (PASS_INTER2 / PASS_INTER3), two challenges in one pass of which at least
+ * one is a fold round with its butterfly (PASS_NTT2: B8 .. B32 twiddles, 2^14 elements and more), three such (PASS_NTT3: a measurement
+ * form that the normal build never launches), and the calls with no challenge at all, which are one copy (COPIES).  Read-only; a
+ * rejected call counts nowhere. */
+enum { BN_FRI_PASS_ONE = 0, BN_FRI_PASS_INTER2 = 1, BN_FRI_PASS_INTER3 = 2, BN_FRI_PASS_NTT2 = 3, BN_FRI_PASS_NTT3 = 4, BN_FRI_COPIES = 5, BN_FRI_N = 6 };
+int bn_fri_counters(bn_ctx *ctx, uint64_t *counters /*[BN_FRI_N]*/);
 
 #ifdef __cplusplus
 }
