@@ -64,6 +64,12 @@ class PeColumn(C.Structure):
     _fields_ = [("d_evals", C.c_void_p), ("tower_level", C.c_uint32), ("n_vars", C.c_uint32)]
 
 
+class RsJob(C.Structure):
+    """bn_rs_job: one equality indicator of bn_ring_switch_eq_ind_batch."""
+
+    _fields_ = [("d_query", C.c_void_p), ("n_vars", C.c_uint32), ("kappa", C.c_uint32), ("mixing_coeff", F128)]
+
+
 class HalMultilinear(C.Structure):
     """bn_hal_multilinear: SumcheckMultilinear::{Folded, Transparent} (crates/hal/src/common.rs)."""
 
@@ -163,6 +169,8 @@ def lib():
         "bn_partial_eval_counters": [vp, C.POINTER(u64)],
         "bn_univariate_fold_batch": [vp, vp, u32, u32, PF, C.POINTER(vp)],
         "bn_univariate_fold_counters": [vp, C.POINTER(u64)],
+        "bn_ring_switch_eq_ind_batch": [vp, vp, u32, PF, u32, C.POINTER(vp)],
+        "bn_ring_switch_counters": [vp, C.POINTER(u64)],
         "bn_log_chunks_range": [C.POINTER(MemMap), u32, C.POINTER(u32), C.POINTER(u32)],
         "bn_pick_log_chunks": [C.POINTER(MemMap), u32, C.POINTER(u32)],
         "bn_kernel_launch": [vp, C.POINTER(MemMap), u32, C.POINTER(KOp), u32, C.POINTER(u32), u32, u32, PF, vp],
@@ -219,7 +227,7 @@ ABI_SYMBOLS = [
     "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals",
     "bn_product_tree_layers", "bn_pad_with_ones", "bn_exp_circuit_layers", "bn_bits_to_b128", "bn_exp_counters",
     "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
-    "bn_univariate_fold_batch", "bn_univariate_fold_counters",
+    "bn_univariate_fold_batch", "bn_univariate_fold_counters", "bn_ring_switch_eq_ind_batch", "bn_ring_switch_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -913,6 +921,29 @@ class Context:
         c = (C.c_uint64 * 3)()
         _check(lib().bn_univariate_fold_counters(self._h, c))
         return {"calls": int(c[0]), "launches": int(c[1]), "columns": int(c[2])}
+
+    def ring_switch_eq_ind_batch(self, jobs, coeffs, outs):
+        """Every ring-switch equality indicator of a call in one launch (bn_ring_switch_eq_ind_batch; RingSwitchEqInd, ring_switch/
+        eq_ind.rs:81-147).  jobs: (query DevSlice, n_vars, kappa, mixing_coeff) per job, the query the 2^n_vars-element tensor
+        expansion of the job's suffix, the coefficient an int; coeffs: the row-batch coefficients as ints (host), a power of two of
+        them and at least 2^kappa; outs[j]: a DevSlice of 2^n_vars elements that receives sum_i coeffs[i] * limb_i(mixing * query[x])."""
+        n = len(jobs)
+        if len(outs) != n:
+            raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: one output per job")
+        coeffs = list(coeffs)
+        for jb, o in zip(jobs, outs):
+            if 0 <= jb[1] <= 40 and ((jb[0] is not None and jb[0].len != 1 << jb[1]) or (o is not None and o.len != 1 << jb[1])):
+                raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: ring switch: a query and an output hold 2^n_vars elements")
+        table = (RsJob * max(1, n))(*[RsJob(jb[0].ptr if jb[0] is not None else None, jb[1], jb[2], to_f128(jb[3])) for jb in jobs])
+        op = (C.c_void_p * max(1, n))(*[(o.ptr if o is not None else None) for o in outs])
+        _check(lib().bn_ring_switch_eq_ind_batch(self._h, C.cast(table, C.c_void_p), n, _f128_array(coeffs), len(coeffs), op))
+
+    def ring_switch_counters(self):
+        """bn_ring_switch_counters: accepted bn_ring_switch_eq_ind_batch calls, the kernel launches they made, the jobs they served,
+        the distinct query pointers among them.  Rejected calls count nowhere."""
+        c = (C.c_uint64 * 4)()
+        _check(lib().bn_ring_switch_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2]), "queries": int(c[3])}
 
     # ---- accumulate_kernels / map_kernels
     def pick_log_chunks(self, mem_maps):

@@ -88,6 +88,11 @@ def host_lib():
         ]
         L.bnh_evalcheck_bivariate_prove.restype = C.c_int
         L.bnh_evalcheck_bivariate_prove.argtypes = [C.c_void_p, C.c_uint32, U32P, U32P, VPP, FP, C.c_uint32, U32P, FP, C.c_void_p, C.c_uint64, FP, FP, FP, FP]
+        L.bnh_ring_switch_scratch_elems.restype = C.c_uint64
+        L.bnh_ring_switch_scratch_elems.argtypes = [C.c_uint32, U32P, C.c_uint32, U32P]
+        L.bnh_ring_switch_prove.restype = C.c_int
+        L.bnh_ring_switch_prove.argtypes = [C.c_void_p, C.c_uint32, VPP, U32P, FP, C.c_uint32, C.c_uint32, U32P, C.c_uint32, U32P, C.c_uint32, U32P, FP, C.c_uint32, FP,
+                                            C.c_uint32, C.c_void_p, C.c_uint64, FP, FP, VPP, DP]
         L.bnh_zerocheck_batch_scratch_elems.restype = C.c_uint64
         L.bnh_zerocheck_batch_scratch_elems.argtypes = [C.c_uint32, C.c_uint32, U32P, U32P]
         L.bnh_zerocheck_batch_prove.restype = C.c_int
@@ -753,6 +758,78 @@ class EvalcheckPlan:
             out.append([from_f128(self.final[at + j]) for j in range(m)])
             at += m
         return out
+
+
+class RingSwitchPlan:
+    """The ring-switching reduction (bnh_ring_switch_prove = binius_amd/host/ring_switch.hpp; ring_switch::prove, ring_switch/prove.rs:42-144).
+    columns: (DevSlice, tower_level, n_vars) per committed column; pool: the shared list of point coordinates; suffixes: (off, len, kappa)
+    per suffix descriptor; prefix_kappas: kappa per prefix descriptor; claims: (committed_idx, suffix_desc_idx, prefix_desc_idx) in the
+    reference's claim order; mixing_challenges: ceil(log2 n_claims) of them, row_batch_challenges: max kappa of them; scratch: a device
+    slice of at least scratch_elems(suffixes, claims) elements.  The PIOP sumcheck claim of claim i is (suffix length, committed_idx,
+    transparent i, row_batched_evals()[i])."""
+
+    PHASES = ("partial_evals", "tensor_algebra", "eq_inds")
+
+    @staticmethod
+    def scratch_elems(suffixes, claims):
+        """2^len per distinct suffix (slice of the pool), 2^kappa per distinct (column, suffix), 2^len per claim."""
+        tables, pairs, total = set(), set(), 0
+        for col, si, _pi in claims:
+            off, ln, kappa = suffixes[si]
+            if (off, ln) not in tables:
+                tables.add((off, ln))
+                total += 1 << ln
+            if (col, off, ln) not in pairs:
+                pairs.add((col, off, ln))
+                total += 1 << kappa
+            total += 1 << ln
+        return total
+
+    def __init__(self, hal, columns, pool, suffixes, prefix_kappas, claims, scratch, mixing_challenges, row_batch_challenges):
+        self.hal, self.scratch, self._keep = hal, scratch, columns
+        self.n_columns, self.n_suffixes, self.n_prefixes, self.n_claims = len(columns), len(suffixes), len(prefix_kappas), len(claims)
+        self.cols = (C.c_void_p * max(1, self.n_columns))(*[(c[0].ptr if c[0] is not None else None) for c in columns])
+        self.col_desc = (C.c_uint32 * max(1, 2 * self.n_columns))(*[int(w) for c in columns for w in c[1:3]])
+        self.pool, self.pool_len = _f128_array(list(pool) or [0]), len(pool)
+        self.suffix_desc = (C.c_uint32 * max(1, 3 * self.n_suffixes))(*[int(w) for s in suffixes for w in s])
+        self.prefix_kappas = (C.c_uint32 * max(1, self.n_prefixes))(*[int(k) for k in prefix_kappas])
+        self.claim_desc = (C.c_uint32 * max(1, 3 * self.n_claims))(*[int(w) for c in claims for w in c])
+        self.mixing, self.n_mixing = _f128_array(list(mixing_challenges) or [0]), len(mixing_challenges)
+        self.row, self.n_row = _f128_array(list(row_batch_challenges) or [0]), len(row_batch_challenges)
+        self.mixed_counts = [1 << int(k) for k in prefix_kappas]
+        self.mixed = (F128 * max(1, sum(self.mixed_counts)))()
+        self.evals = (F128 * max(1, self.n_claims))()
+        self.transparent_ptrs = (C.c_void_p * max(1, self.n_claims))()
+        self.transparent_lens = [1 << int(suffixes[c[1]][1]) for c in claims] if all(c[1] < len(suffixes) for c in claims) else [0] * len(claims)
+        self.phase_ms = (C.c_double * 3)()
+
+    def run(self):
+        rc = host_lib().bnh_ring_switch_prove(self.hal._h, self.n_columns, self.cols, self.col_desc, self.pool, self.pool_len, self.n_suffixes, self.suffix_desc,
+                                              self.n_prefixes, self.prefix_kappas, self.n_claims, self.claim_desc, self.mixing, self.n_mixing, self.row, self.n_row,
+                                              self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0,
+                                              self.mixed, self.evals, self.transparent_ptrs, self.phase_ms)
+        if rc != 0:
+            raise BnError(rc, host_lib().bnh_last_error().decode())
+
+    def mixed_tensor_elems(self):
+        """Per prefix descriptor its 2^kappa vertical elements."""
+        out, at = [], 0
+        for n in self.mixed_counts:
+            out.append([from_f128(self.mixed[at + j]) for j in range(n)])
+            at += n
+        return out
+
+    def row_batched_evals(self):
+        return [from_f128(self.evals[i]) for i in range(self.n_claims)]
+
+    def transparents(self):
+        """The transparent of every claim as a DevSlice inside the scratch, in claim order."""
+        from ._ffi import DevSlice
+
+        return [DevSlice(self.transparent_ptrs[i], self.transparent_lens[i]) for i in range(self.n_claims)]
+
+    def phase_times_ms(self):
+        return {name: self.phase_ms[i] for i, name in enumerate(self.PHASES)}
 
 
 class ShmExchange:

@@ -82,6 +82,7 @@ struct bn_ctx {
 	uint64_t flush_calls = 0, flush_launches = 0, flush_served = 0, flush_multipass = 0; // bn_flush_witness_batch (bn_flush_counters)
 	uint64_t pe_calls = 0, pe_launches = 0, pe_cols_kernel = 0, pe_cols_fallback = 0, pe_max_share = 0, pe_routed = 0; // bn_partial_eval_counters
 	uint64_t uf_calls = 0, uf_launches = 0, uf_cols = 0; // bn_univariate_fold_batch (bn_univariate_fold_counters)
+	uint64_t rs_calls = 0, rs_launches = 0, rs_jobs = 0, rs_queries = 0; // bn_ring_switch_eq_ind_batch (bn_ring_switch_counters)
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	int n_cu = 256;
@@ -848,6 +849,27 @@ constexpr uint32_t uf_tables(uint32_t level, uint32_t k)
 // d_coeffs: the 2^k coefficients; lds_tables: the largest uf_tables() over the levels of the call
 hipError_t launch_univariate_fold(hipStream_t s, const uf_job *d_jobs, uint32_t n_jobs, const void *d_coeffs, uint32_t k, uint32_t total_units,
                                   uint32_t n_wgs, uint32_t lds_tables);
+
+// ---- kernels_ring_switch.hip: every ring-switch equality indicator of a call (RingSwitchEqInd, core/src/ring_switch/eq_ind.rs:81-147):
+// out_j[x] = sum_{i < 2^kappa} coeffs[i] * limb_i(mixing_j * query_j[x]).  The jobs are sorted by query; a RUN is up to kRsRunJobs jobs
+// of one query, a unit (one workgroup) a run and `span` consecutive tiles of kRsTile elements of its query.
+struct rs_job {
+	uint4 *out;
+	f128 mixing;
+	uint32_t kappa, pad_[3];
+};
+struct rs_run {
+	const void *query;
+	uint64_t len;      // 2^n_vars
+	uint32_t first_job, n_jobs;
+	uint32_t start;    // first unit of this run in the launch
+	uint32_t pad_;
+};
+constexpr uint32_t kRsTile = 2048;  // elements of a tile: eight per thread
+constexpr uint32_t kRsRunJobs = 8;  // nibble tables (8 KiB each) a workgroup keeps in LDS
+// d_coeffs: the first n_staged (<= 128) row-batch coefficients
+hipError_t launch_ring_switch_eq_ind(hipStream_t s, const rs_run *d_runs, uint32_t n_runs, const rs_job *d_jobs, const void *d_coeffs, uint32_t n_staged,
+                                     uint32_t span, uint32_t total_units);
 
 // ---- kernels_ntt_tiled.hip
 hipError_t launch_build_mul8(hipStream_t s, uint8_t *d_tab);

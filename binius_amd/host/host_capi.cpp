@@ -4,7 +4,7 @@
 // loop the way a compiled (Rust) host would drive the HAL -- for the BivariateSumcheckProver per round one accumulate_kernels, two
 // scalar multiplications, one extrapolate_line per multilinear -- without interpreter overhead between HAL calls.  One entry point
 // per mirror (sumcheck.hpp, batch_prover.hpp, eq_ind.hpp, fri.hpp, piop.hpp, gkr_gpa.hpp, gkr_exp.hpp, flush.hpp, evalcheck.hpp,
-// zerocheck.hpp): it converts the C arrays (from_raw / to_raw), runs inside guarded(), which turns what is thrown into the return
+// zerocheck.hpp, ring_switch.hpp): it converts the C arrays (from_raw / to_raw), runs inside guarded(), which turns what is thrown into the return
 // code and bnh_last_error().  Links only against the C ABI of include/binius_amd.h.
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -29,6 +29,7 @@
 #include "gkr_exp.hpp"
 #include "gkr_gpa.hpp"
 #include "piop.hpp"
+#include "ring_switch.hpp"
 #include "sumcheck.hpp"
 #include "zerocheck.hpp"
 
@@ -1194,6 +1195,59 @@ int bnh_zerocheck_batch_prove(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_roun
 			if (phase_ms_out) phase_ms_out[i] = out.phase_ms[i];
 			if (phase_calls_out) phase_calls_out[i] = out.phase_calls[i];
 		}
+		return 0;
+	});
+}
+
+// ring_switch::prove (crates/core/src/ring_switch/prove.rs:42-144) through the C++ mirror binius_amd/host/ring_switch.hpp; the arguments
+// are described in include/binius_amd_host.h.
+namespace {
+void ring_switch_descs(uint32_t n_suffixes, const uint32_t *suffix_desc, uint32_t n_claims, const uint32_t *claim_desc, std::vector<RingSwitchSuffix> &suffixes,
+                       std::vector<RingSwitchClaim> &claims)
+{
+	for (uint32_t i = 0; i < n_suffixes; i++) suffixes.push_back(RingSwitchSuffix{suffix_desc[3 * i], suffix_desc[3 * i + 1], suffix_desc[3 * i + 2]});
+	for (uint32_t i = 0; i < n_claims; i++) claims.push_back(RingSwitchClaim{claim_desc[3 * i], claim_desc[3 * i + 1], claim_desc[3 * i + 2]});
+}
+} // namespace
+
+uint64_t bnh_ring_switch_scratch_elems(uint32_t n_suffixes, const uint32_t *suffix_desc, uint32_t n_claims, const uint32_t *claim_desc)
+{
+	if ((n_suffixes && !suffix_desc) || (n_claims && !claim_desc)) return 0;
+	std::vector<RingSwitchSuffix> suffixes;
+	std::vector<RingSwitchClaim> claims;
+	ring_switch_descs(n_suffixes, suffix_desc, n_claims, claim_desc, suffixes, claims);
+	try {
+		return ring_switch_scratch_elems(suffixes, claims);
+	} catch (const Error &) {
+		return 0;
+	}
+}
+
+int bnh_ring_switch_prove(bn_ctx *ctx, uint32_t n_columns, const void *const *d_columns, const uint32_t *column_desc, const bn_f128 *point_pool, uint32_t pool_len,
+                          uint32_t n_suffixes, const uint32_t *suffix_desc, uint32_t n_prefixes, const uint32_t *prefix_kappas, uint32_t n_claims,
+                          const uint32_t *claim_desc, const bn_f128 *mixing_challenges, uint32_t n_mixing_challenges, const bn_f128 *row_batch_challenges,
+                          uint32_t n_row_batch_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *mixed_tensor_elems_out, bn_f128 *row_batched_evals_out,
+                          void **d_transparents_out, double *phase_ms_out)
+{
+	return guarded([&]() -> int {
+		if (!ctx || (n_columns && (!d_columns || !column_desc)) || (pool_len && !point_pool) || (n_suffixes && !suffix_desc) || (n_prefixes && (!prefix_kappas || !mixed_tensor_elems_out)) ||
+		    (n_claims && (!claim_desc || !row_batched_evals_out || !d_transparents_out)) || (n_mixing_challenges && !mixing_challenges) ||
+		    (n_row_batch_challenges && !row_batch_challenges) || (!d_scratch && scratch_elems))
+			throw Error(Error::InputValidation, "null argument");
+		std::vector<bn_pe_column> columns;
+		for (uint32_t c = 0; c < n_columns; c++) columns.push_back(bn_pe_column{d_columns[c], column_desc[2 * c], column_desc[2 * c + 1]});
+		std::vector<RingSwitchSuffix> suffixes;
+		std::vector<RingSwitchClaim> claims;
+		ring_switch_descs(n_suffixes, suffix_desc, n_claims, claim_desc, suffixes, claims);
+		ComputeLayer hal(ctx);
+		const RingSwitchOutput out = ring_switch_prove(hal, columns, from_raw(point_pool, pool_len), suffixes, std::vector<uint32_t>(prefix_kappas, prefix_kappas + n_prefixes), claims,
+		                                               from_raw(mixing_challenges, n_mixing_challenges), from_raw(row_batch_challenges, n_row_batch_challenges),
+		                                               FSliceMut{d_scratch, (size_t)scratch_elems});
+		if (!out.mixed_tensor_elems.empty()) to_raw(out.mixed_tensor_elems, mixed_tensor_elems_out);
+		if (!out.row_batched_evals.empty()) to_raw(out.row_batched_evals, row_batched_evals_out);
+		for (size_t i = 0; i < out.transparents.size(); i++) d_transparents_out[i] = const_cast<void *>(out.transparents[i].ptr);
+		if (phase_ms_out)
+			for (int i = 0; i < RingSwitchOutput::NPhases; i++) phase_ms_out[i] = out.phase_ms[i];
 		return 0;
 	});
 }

@@ -106,6 +106,11 @@ pub const BN_UF_N: usize = 3;
 pub const BN_UF_CALLS: usize = 0;
 pub const BN_UF_LAUNCHES: usize = 1;
 pub const BN_UF_COLS: usize = 2;
+pub const BN_RS_N: usize = 4;
+pub const BN_RS_CALLS: usize = 0;
+pub const BN_RS_LAUNCHES: usize = 1;
+pub const BN_RS_JOBS: usize = 2;
+pub const BN_RS_QUERIES: usize = 3;
 pub const BN_UNIVARIATE_FOLD_MAX_SKIP: u32 = 8;
 pub const BN_EXP_STATIC: u32 = 0;
 pub const BN_EXP_DYNAMIC: u32 = 1;
@@ -124,6 +129,15 @@ pub struct bn_pe_column {
 	pub d_evals: *const c_void,
 	pub tower_level: u32,
 	pub n_vars: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bn_rs_job {
+	pub d_query: *const c_void,
+	pub n_vars: u32,
+	pub kappa: u32,
+	pub mixing_coeff: bn_f128,
 }
 
 #[repr(C)]
@@ -310,6 +324,15 @@ unsafe extern "C" {
 		d_outs: *const *mut c_void,
 	) -> c_int;
 	pub fn bn_univariate_fold_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_ring_switch_eq_ind_batch(
+		ctx: *mut bn_ctx,
+		jobs: *const c_void,
+		n_jobs: u32,
+		h_row_batch_coeffs: *const bn_f128,
+		n_coeffs: u32,
+		d_outs: *const *mut c_void,
+	) -> c_int;
+	pub fn bn_ring_switch_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 
 	pub fn bn_log_chunks_range(maps: *const bn_memmap, n_maps: u32, start: *mut u32, end: *mut u32) -> c_int;
 	pub fn bn_pick_log_chunks(maps: *const bn_memmap, n_maps: u32, log_chunks: *mut u32) -> c_int;

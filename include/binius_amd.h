@@ -268,6 +268,35 @@ int bn_univariate_fold_batch(bn_ctx *ctx, const void *cols, uint32_t n_cols, uin
  * made, the columns they served.  A rejected call counts nowhere. */
 enum { BN_UF_CALLS = 0, BN_UF_LAUNCHES = 1, BN_UF_COLS = 2, BN_UF_N = 3 };
 int bn_univariate_fold_counters(bn_ctx *ctx, uint64_t *counters /*[BN_UF_N]*/);
+/* Every ring-switch equality indicator of a call: RingSwitchEqInd::multilinear_extension (core/src/ring_switch/eq_ind.rs:81-147),
+ * one per claim of ring_switch::prove (core/src/ring_switch/prove.rs:116-124).  Job j (jobs[j], a HOST array of bn_rs_job) has d_query,
+ * the tensor expansion of its suffix -- 2^n_vars B128 elements on the device, the table bn_partial_eval_high_batch takes as
+ * d_tensor_query, shared by every job of that suffix and only read --, n_vars in 0 .. BN_PE_MAX_VARS, kappa in {0, 1, 2, 3, 4, 7} (the
+ * packed tower level is 7 - kappa) and its mixing coefficient.  h_row_batch_coeffs: n_coeffs coefficients on the HOST that serve all
+ * jobs, n_coeffs a power of two and at least 2^kappa for every job; a job uses the first 2^kappa.  d_outs[j] (2^n_vars elements)
+ * receives exactly what
+ *   bn_fill(evals, 0); evals[0] = mixing_coeff; bn_tensor_expand(evals, 0, suffix);
+ *   bn_fold_right(evals, 2^n_vars, 7 - kappa, coeffs, 2^kappa, out, 2^n_vars)
+ * writes: out[x] = sum_{i < 2^kappa} coeffs[i] * limb_i(mixing_coeff * query[x]), bit-exact, overwritten not accumulated, nothing
+ * written beyond 2^n_vars elements.  A null or misaligned pointer, an output that overlaps a query or another output, kappa of 5 or 6
+ * or above 7, n_vars out of range and too few coefficients are BN_ERR_INPUT_VALIDATION with nothing launched; n_jobs = 0 is a no-op.
+ * The whole call is ONE launch whatever the number of jobs, queries and sizes: the jobs are sorted by query, a workgroup loads a
+ * tile of a query once and takes it through the nibble tables of up to eight of the query's jobs.  Returns when the outputs are
+ * complete. */
+typedef struct {
+	const void *d_query;
+	uint32_t n_vars;
+	uint32_t kappa;
+	bn_f128 mixing_coeff;
+} bn_rs_job;
+/* (jobs points to n_jobs bn_rs_job; untyped in the prototype for the same reason as bn_partial_eval_high_batch's cols.) */
+int bn_ring_switch_eq_ind_batch(bn_ctx *ctx, const void *jobs, uint32_t n_jobs, const bn_f128 *h_row_batch_coeffs, uint32_t n_coeffs,
+                                void *const *d_outs);
+/* Read-only, per context (not part of the reference interface): accepted bn_ring_switch_eq_ind_batch calls, the kernel launches
+ * they made, the jobs they served, the distinct query pointers among those jobs (summed over calls).  A rejected call counts
+ * nowhere. */
+enum { BN_RS_CALLS = 0, BN_RS_LAUNCHES = 1, BN_RS_JOBS = 2, BN_RS_QUERIES = 3, BN_RS_N = 4 };
+int bn_ring_switch_counters(bn_ctx *ctx, uint64_t *counters /*[BN_RS_N]*/);
 
 /* ---- accumulate_kernels / map_kernels (layer.rs:183, 236) + KernelExecutor (layer.rs:518-590).
  * The kernel-spec closure cannot cross an FFI: the host shim runs it ONCE against a recording

@@ -304,6 +304,31 @@ int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_
                                   uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges, bn_f128 *round_proofs_out,
                                   bn_f128 *final_evals_out);
 
+/* The ring-switching reduction: ring_switch::prove (core/src/ring_switch/prove.rs:42-144) through the C++ mirror binius_amd/host/
+ * ring_switch.hpp.  The caller has done the oracle-set bookkeeping of EvalClaimSystem::new (ring_switch/common.rs:72-205).
+ *   d_columns[c], column_desc[2 * c] = (tower_level, n_vars): the committed columns, 2^n_vars values packed into F as bn_partial_eval_high_batch
+ *     takes them (n_vars + tower_level >= 7), only read
+ *   point_pool / suffix_desc[3 * s] = (off, len, kappa): the suffix descriptors, suffix s = point_pool[off .. off + len)
+ *   prefix_kappas[p]: kappa of prefix descriptor p
+ *   claim_desc[3 * i] = (committed_idx, suffix_desc_idx, prefix_desc_idx), in the order the reference sorts the claims; kappa of the
+ *     suffix = 7 - tower_level of the column = kappa of the prefix (else the reference's TowerLevelMismatch), len = n_vars - kappa
+ *   mixing_challenges[ceil(log2 n_claims)], row_batch_challenges[max kappa]: the transcript's two sample_vec calls (prove.rs:68-69, 97)
+ *   d_scratch: at least bnh_ring_switch_scratch_elems elements (the formula is exact): 2^len per distinct suffix (slice of the pool), 2^kappa per distinct
+ *     (column, suffix), 2^len per claim
+ * Distinct suffixes are tensor-expanded once each; the partial evaluations of the distinct columns of one suffix are ONE
+ * bn_partial_eval_high_batch and one copy to the host; scaling, mixing per prefix and the row-batched evaluations run on the host; the
+ * transparents of ALL claims are ONE bn_ring_switch_eq_ind_batch over the same suffix tables.
+ * Outputs, in transcript order: mixed_tensor_elems_out -- per prefix its 2^kappa vertical elements, concatenated (prove.rs:90-94);
+ * row_batched_evals_out[n_claims] (prove.rs:104).  d_transparents_out[i]: the transparent of claim i (2^len elements inside d_scratch);
+ * the PIOP sumcheck claim of claim i is (n_vars = len, committed_idx, transparent = i, sum = row_batched_evals_out[i]) (prove.rs:127-138).
+ * phase_ms_out[3] (may be null): wall milliseconds of partial_evals, tensor_algebra, eq_inds. */
+uint64_t bnh_ring_switch_scratch_elems(uint32_t n_suffixes, const uint32_t *suffix_desc, uint32_t n_claims, const uint32_t *claim_desc);
+int bnh_ring_switch_prove(bn_ctx *ctx, uint32_t n_columns, const void *const *d_columns, const uint32_t *column_desc, const bn_f128 *point_pool, uint32_t pool_len,
+                          uint32_t n_suffixes, const uint32_t *suffix_desc, uint32_t n_prefixes, const uint32_t *prefix_kappas, uint32_t n_claims,
+                          const uint32_t *claim_desc, const bn_f128 *mixing_challenges, uint32_t n_mixing_challenges, const bn_f128 *row_batch_challenges,
+                          uint32_t n_row_batch_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *mixed_tensor_elems_out, bn_f128 *row_batched_evals_out,
+                          void **d_transparents_out, double *phase_ms_out);
+
 /* shared-memory exchange: rank 0 creates the segment `name` ("/..."), the others open it afterwards */
 int bnh_shm_open(const char *name, int world, int rank, int create, void **handle_out);
 int bnh_shm_close(void *handle);

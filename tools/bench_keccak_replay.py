@@ -17,7 +17,12 @@ Phases, in the order of core/src/constraint_system/prove.rs:74-588 (keccak has n
   commit        piop::commit -> commit_interleaved: additive NTT of the merged message + Groestl Merkle tree     (:217-233)
   zerocheck     EqIndSumcheckProver over the old HAL: per round one sumcheck_compute_round_evals with 100 evaluators over 204
                 multilinears, the fold of all of them, the fold of the indicator                                  (:431-505)
-  ring_switch   per transparent: fill + tensor_expand + fold_right over the 128 one-bit limbs                     (:541-566)
+  ring_switch   per transparent: fill + tensor_expand + fold_right over the 128 one-bit limbs, for THREE transparents (:541-566).
+                The reference builds one transparent per claim (ring_switch/prove.rs:127-138: 175 for this claim graph) and, in
+                front of them, the partial evaluations of every committed column at its claim's suffix, the tensor algebra per
+                prefix and the row-batched evaluations (ring_switch/prove.rs:147-264): this phase leaves all of that out.  The
+                faithful phase is bnh_ring_switch_prove (binius_amd/host/ring_switch.hpp); its figure at this shape, beside the
+                per-claim sequence, is tools/bench_ring_switch.py -> profiles/r14/ring_switch.json
   piop_prove    prove_interleaved_fri_sumcheck: execute / fold of the 175-claim prover, fri_fold + Merkle on commit rounds (:569-588)
 
 What the replay is NOT: the witness is random (on-device tensor expansions), so the constraints do not hold and the claimed sums
