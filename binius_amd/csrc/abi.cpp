@@ -490,6 +490,24 @@ int flush_legacy(bn_ctx *ctx, bool keep_tail, bool publish_tiny, bool keep_shado
 			BN_HIP(bn::launch_scale(ctx->stream, ctx->n_cu, (char *)ctx->pend.x0[i] + (ctx->pend.n / 2) * sizeof(f128), ctx->pend.n / 2, ctx->pend.hi_scale));
 	return BN_OK;
 }
+// Waits for the sequence word the publishing kernel writes after its values (fine-grained host memory): a bounded spin, then a
+// stream synchronisation so that device errors surface instead of hanging.  cancel_armed: an armed kernel queued behind the
+// launch would sit out its whole timeout inside that synchronisation -- it is told to leave first.
+int mail_wait(bn_ctx *ctx, uint64_t seq, bool cancel_armed)
+{
+	volatile uint64_t *seqw = &ctx->h_mail[64].lo;
+	uint64_t spins = 0;
+	while (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) {
+		if (++spins > (1ull << 22)) {
+			if (cancel_armed) arm_cancel(ctx);
+			BN_HIP(hipStreamSynchronize(ctx->stream));
+			if (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) return bn::fail(BN_ERR_DEVICE, "device error: result mailbox was not published");
+			break;
+		}
+	}
+	return BN_OK;
+}
+
 // one call at a time per context (the trait allows the host to call from several threads: rayon join/map)
 // XOR of n_groups partial results in d_result[0 .. n_groups) -> host, through the zero-copy mailbox
 // (one tiny kernel instead of a device-to-host copy plus a stream synchronisation)
@@ -497,18 +515,9 @@ int publish_result(bn_ctx *ctx, uint32_t n_groups, bn_f128 *h_out)
 {
 	const uint64_t seq = ++ctx->mail_seq;
 	BN_HIP(bn::launch_xor_publish(ctx->stream, ctx->d_result, n_groups, 1, ctx->d_result + 96, ctx->d_mail, seq));
-	volatile uint64_t *seqw = &ctx->h_mail[64].lo;
-	uint64_t spins = 0;
-	while (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) {
-		if (++spins > (1ull << 22)) {
-			BN_HIP(hipStreamSynchronize(ctx->stream));
-			if (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq)
-				return bn::fail(BN_ERR_DEVICE, "device error: result mailbox was not published");
-			break;
-		}
-	}
-	h_out->lo = __atomic_load_n(&ctx->h_mail[0].lo, __ATOMIC_RELAXED);
-	h_out->hi = __atomic_load_n(&ctx->h_mail[0].hi, __ATOMIC_RELAXED);
+	const int rc = mail_wait(ctx, seq);
+	if (rc) return rc;
+	mail_read(ctx, 0, 1, h_out);
 	return BN_OK;
 }
 
@@ -518,19 +527,9 @@ int publish_vals(bn_ctx *ctx, const f128 *d_vals, uint32_t n_groups, uint32_t gr
 {
 	const uint64_t seq = ++ctx->mail_seq;
 	BN_HIP(bn::launch_xor_publish(ctx->stream, d_vals, n_groups, group_len, ctx->d_result + 64, ctx->d_mail, seq, g_stride, i_stride));
-	volatile uint64_t *seqw = &ctx->h_mail[64].lo;
-	uint64_t spins = 0;
-	while (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) {
-		if (++spins > (1ull << 22)) {
-			BN_HIP(hipStreamSynchronize(ctx->stream));
-			if (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) return bn::fail(BN_ERR_DEVICE, "device error: result mailbox was not published");
-			break;
-		}
-	}
-	for (uint32_t r = 0; r < group_len; r++) {
-		h_out[r].lo = __atomic_load_n(&ctx->h_mail[r].lo, __ATOMIC_RELAXED);
-		h_out[r].hi = __atomic_load_n(&ctx->h_mail[r].hi, __ATOMIC_RELAXED);
-	}
+	const int rc = mail_wait(ctx, seq);
+	if (rc) return rc;
+	mail_read(ctx, 0, group_len, h_out);
 	return BN_OK;
 }
 
@@ -1009,21 +1008,10 @@ int bn_copy_d2h(bn_ctx *ctx, const void *d_src, uint64_t src_len, bn_f128 *h_dst
 					h_dst[0].hi = ctx->mirror.host_vals[i].hi;
 					return BN_OK;
 				}
-				volatile uint64_t *seqw = &ctx->h_mail[64].lo;
-				uint64_t spins = 0;
-				while (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != ctx->mirror.seq) {
-					if (++spins > (1ull << 22)) {
-						BN_HIP(hipStreamSynchronize(ctx->stream));
-						if (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != ctx->mirror.seq)
-							return bn::fail(BN_ERR_DEVICE, "device error: result mailbox was not published");
-						break;
-					}
-				}
+				const int rc = mail_wait(ctx, ctx->mirror.seq);
+				if (rc) return rc;
 				const size_t off = (size_t)i * ctx->mirror.n + (size_t)(p - base) / sizeof(f128);
-				for (uint64_t e = 0; e < src_len; e++) {
-					h_dst[e].lo = __atomic_load_n(&ctx->h_mail[off + e].lo, __ATOMIC_RELAXED);
-					h_dst[e].hi = __atomic_load_n(&ctx->h_mail[off + e].hi, __ATOMIC_RELAXED);
-				}
+				mail_read(ctx, (uint32_t)off, (uint32_t)src_len, h_dst);
 				return BN_OK;
 			}
 		}

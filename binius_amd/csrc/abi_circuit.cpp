@@ -573,19 +573,11 @@ int circuit_ip_run(bn_ctx *ctx, const ip_collector &col, uint64_t n, const void 
 			const hipError_t e = bn::launch_group(ctx->stream, ctx->n_cu, gj, nj, 2 * nj, ctx->d_result, ctx->d_mail, ctx->d_mail, ctx->d_ticket, seq, h_tb->jobs, d_tb->jobs);
 			if (e != hipSuccess) return bn::hip_fail(e, "launch_group (inner products of compiled circuits)");
 		}
-		volatile uint64_t *seqw = &ctx->h_mail[64].lo;
-		uint64_t spins = 0;
-		while (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) {
-			if (++spins > (1ull << 22)) {
-				BN_HIP(hipStreamSynchronize(ctx->stream));
-				if (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) return bn::fail(BN_ERR_DEVICE, "device error: result mailbox was not published");
-				break;
-			}
-		}
+		const int rc_w = mail_wait(ctx, seq);
+		if (rc_w) return rc_w;
 		for (uint32_t i = 0; i < n_ip; i++) {
 			f128 v;
-			v.lo = __atomic_load_n(&ctx->h_mail[i].lo, __ATOMIC_RELAXED);
-			v.hi = __atomic_load_n(&ctx->h_mail[i].hi, __ATOMIC_RELAXED);
+			mail_read(ctx, i, 1, &v);
 			const ip_job &q = jobs[first + i];
 			values[q.out] ^= (q.coeff == bn::f128_one()) ? v : bn::mul_host(q.coeff, v);
 		}

@@ -156,6 +156,18 @@ int fold_left_dispatch(bn_ctx *ctx, const void *d_mat, uint32_t tower_level, con
 // validated columns (query_vars <= n_vars each) at the 2^q-entry query d_vec; routed: a bn_fold_left call served as a one-column job
 int partial_eval_run(bn_ctx *ctx, const bn_pe_column *cols, uint32_t n_cols, const void *d_vec, uint32_t q, void *const *d_outs, bool routed);
 // ---- small helpers shared by the op entry points (abi.cpp)
+// the pinned result mailbox: wait until the sequence word shows `seq` (bounded spin, then a stream synchronisation -- before which
+// an armed kernel queued behind the launch is cancelled if cancel_armed -- and "result mailbox was not published")
+int mail_wait(bn_ctx *ctx, uint64_t seq, bool cancel_armed = false);
+// result slots [first, first + n) of the mailbox (relaxed loads: mail_wait's acquire ordered them); T is bn_f128 or f128
+template <typename T>
+inline void mail_read(bn_ctx *ctx, uint32_t first, uint32_t n, T *out)
+{
+	for (uint32_t r = 0; r < n; r++) {
+		out[r].lo = __atomic_load_n(&ctx->h_mail[first + r].lo, __ATOMIC_RELAXED);
+		out[r].hi = __atomic_load_n(&ctx->h_mail[first + r].hi, __ATOMIC_RELAXED);
+	}
+}
 int publish_result(bn_ctx *ctx, uint32_t n_groups, bn_f128 *h_out);
 int publish_vals(bn_ctx *ctx, const bn::f128 *d_vals, uint32_t n_groups, uint32_t group_len, uint32_t g_stride, uint32_t i_stride, bn::f128 *h_out);
 int upload_ptrs(bn_ctx *ctx, const void *const *ptrs, uint32_t n, const void ***d_ptrs);

@@ -745,19 +745,6 @@ void host_answer(bn_ctx *ctx, const bn_ctx::group_session &s, const request &rq,
 	ctx->grp.evals++;
 }
 
-int wait_mail(bn_ctx *ctx, uint64_t seq)
-{
-	volatile uint64_t *seqw = &ctx->h_mail[64].lo;
-	uint64_t spins = 0;
-	while (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) {
-		if (++spins > (1ull << 22)) {
-			BN_HIP(hipStreamSynchronize(ctx->stream));
-			if (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) return bn::fail(BN_ERR_DEVICE, "device error: result mailbox was not published");
-			break;
-		}
-	}
-	return BN_OK;
-}
 } // namespace
 
 int group_res_alloc(bn_ctx *ctx) { return res_alloc(ctx); }
@@ -1168,7 +1155,7 @@ int group_eval(bn_ctx *ctx, const bn_memmap *maps, uint32_t n_maps, const bn_kop
 				}
 			}
 			g.on = true;
-			rc = wait_mail(ctx, ma.seq);
+			rc = mail_wait(ctx, ma.seq);
 			if (rc) return rc;
 			pc.lap(bn_ctx::group_state::P_HOST_WAIT);
 			// the staging validates itself (kernels_group.hip k_group_mirror): accepted only when the tag computed from what is read is
@@ -1425,7 +1412,7 @@ int group_eval(bn_ctx *ctx, const bn_memmap *maps, uint32_t n_maps, const bn_kop
 	}
 	g.on = true;
 	pc.lap(bn_ctx::group_state::P_LAUNCH);
-	rc = wait_mail(ctx, seq);
+	rc = mail_wait(ctx, seq);
 	if (rc) return rc;
 	pc.lap(bn_ctx::group_state::P_WAIT);
 	std::vector<f128> raw(n_slots);

@@ -384,15 +384,8 @@ int round_evals_eq_set(bn_ctx *ctx, uint32_t n_vars, const bn_hal_multilinear *m
 			}
 		}
 		lap(3);
-		volatile uint64_t *seqw = &ctx->h_mail[64].lo;
-		uint64_t spins = 0;
-		while (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) {
-			if (++spins > (1ull << 22)) {
-				BN_HIP(hipStreamSynchronize(ctx->stream));
-				if (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) return bn::fail(BN_ERR_DEVICE, "device error: result mailbox was not published");
-				break;
-			}
-		}
+		const int rc_w = mail_wait(ctx, seq);
+		if (rc_w) return rc_w;
 		lap(4);
 		for (uint32_t i = 0; i < pl->n_slots; i++) {
 			sums[i].lo = __atomic_load_n(&ctx->grp.h_gmail[i].lo, __ATOMIC_RELAXED);
@@ -688,15 +681,8 @@ int round_evals_coef(bn_ctx *ctx, uint32_t n_vars, const bn_hal_multilinear *mls
 			ctx->grp.launches++;
 			ctx->grp.jobs_eval += jobs.size();
 		}
-		volatile uint64_t *seqw = &ctx->h_mail[64].lo;
-		uint64_t spins = 0;
-		while (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) {
-			if (++spins > (1ull << 22)) {
-				BN_HIP(hipStreamSynchronize(ctx->stream));
-				if (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != seq) return bn::fail(BN_ERR_DEVICE, "device error: result mailbox was not published");
-				break;
-			}
-		}
+		const int rc_w = mail_wait(ctx, seq);
+		if (rc_w) return rc_w;
 		for (uint32_t i = 0; i < n_slots; i++) {
 			S[i].lo = __atomic_load_n(&ctx->grp.h_gmail[i].lo, __ATOMIC_RELAXED);
 			S[i].hi = __atomic_load_n(&ctx->grp.h_gmail[i].hi, __ATOMIC_RELAXED);
