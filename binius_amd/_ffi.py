@@ -524,6 +524,12 @@ class Context:
     def set_stream(self, hip_stream):
         _check(lib().bn_ctx_set_stream(self._h, hip_stream))
 
+    def get_stream(self):
+        """The stream the context runs on, as an integer handle; everything deferred is launched first (bn_ctx_get_stream)."""
+        s = C.c_void_p()
+        _check(lib().bn_ctx_get_stream(self._h, C.byref(s)))
+        return s.value or 0
+
     def sync(self):
         _check(lib().bn_sync(self._h))
 

@@ -662,9 +662,9 @@ int bn_ctx_create(int device, uint64_t arena_elems, bn_ctx **out)
 	}
 	if (const char *t = getenv("BN_TAIL_MAX_LOG2")) {
 		const int l = atoi(t);
-		ctx->tail_max_n_in = (l >= 3 && l <= 12) ? (1ull << l) : 0; // one workgroup: at most 2^12 elements per array
+		ctx->tail_max_cfg = (l >= 3 && l <= 12) ? (1ull << l) : 0; // one workgroup: at most 2^12 elements per array
 	}
-	if (!ctx->lazy_fold) ctx->tail_max_n_in = 0;
+	ctx->tail_max_n_in = ctx->lazy_fold ? ctx->tail_max_cfg : 0;
 	*out = ctx;
 	return BN_OK;
 }
@@ -876,6 +876,7 @@ int bn_ctx_set_stream(bn_ctx *ctx, void *hip_stream)
 			BN_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
 			ctx->own_stream = true;
 			ctx->lazy_fold = getenv("BN_NO_LAZY_FOLD") == nullptr;
+			ctx->tail_max_n_in = ctx->lazy_fold ? ctx->tail_max_cfg : 0; // (the resident tail comes back with the deferral)
 		}
 		return BN_OK;
 	}
@@ -888,7 +889,7 @@ int bn_ctx_set_stream(bn_ctx *ctx, void *hip_stream)
 	// therefore off on caller-supplied streams unless the caller opts in (BN_LAZY_ON_SHARED_STREAM=1)
 	// and promises to call bn_ctx_get_stream / bn_sync (both flush) before touching the stream itself.
 	ctx->lazy_fold = getenv("BN_NO_LAZY_FOLD") == nullptr && getenv("BN_LAZY_ON_SHARED_STREAM") != nullptr;
-	if (!ctx->lazy_fold) ctx->tail_max_n_in = 0;
+	ctx->tail_max_n_in = ctx->lazy_fold ? ctx->tail_max_cfg : 0;
 	return BN_OK;
 }
 

@@ -236,6 +236,7 @@ struct bn_ctx {
 	} tail;
 	uint64_t tail_counter = 0;
 	uint64_t tail_max_n_in = 0; // BN_TAIL_MAX_LOG2=3..12 enables the resident tail (off by default: see DESIGN.md)
+	uint64_t tail_max_cfg = 0;  // the size BN_TAIL_MAX_LOG2 asked for: tail_max_n_in is this or, while nothing is deferred, 0
 	// armed round (arm.hpp): the kernel of the NEXT small round, enqueued behind the current one and waiting for its
 	// challenge on the command block h_mail[84..87]
 	struct arm_state {

@@ -65,9 +65,11 @@ int bn_arena_base(bn_ctx *ctx, void **d_base, uint64_t *elems);
  * every bn_* call, host read-back included.  Anything the caller enqueues on that stream itself must
  * come after bn_ctx_get_stream or bn_sync: both flush deferred work first.
  * bn_ctx_set_stream(s != NULL) runs the context on a caller-owned hipStream_t (e.g.
- * torch.cuda.current_stream().cuda_stream) and turns the deferral OFF (strict call order, no fold +
+ * torch.cuda.Stream().cuda_stream) and turns the deferral OFF (strict call order, no fold +
  * evaluation fusion) unless BN_LAZY_ON_SHARED_STREAM=1 accepts the rule above; NULL = back to an own
- * stream.  Every entry point makes the context's device current on the calling thread. */
+ * stream with the behaviour the context was created with.  Handle 0 IS NULL: the default (null) stream,
+ * torch's default stream included, selects the own stream and is never adopted.  Every entry point makes
+ * the context's device current on the calling thread. */
 int bn_ctx_set_stream(bn_ctx *ctx, void *hip_stream);
 int bn_sync(bn_ctx *ctx);
 /* the hipStream_t the context enqueues on, after flushing deferred work (so a caller can put an RCCL
