@@ -25,6 +25,7 @@ MASK64 = (1 << 64) - 1
 ORDER_LOW_TO_HIGH, ORDER_HIGH_TO_LOW = 0, 1  # EvaluationOrder (crates/math/src/fold.rs)
 HAL_ML_FOLDED, HAL_ML_TRANSPARENT = 0, 1
 NTT_MAX_DIM = 64
+BN_ME_MAX_LO_VARS, BN_ME_MAX_JOBS = 10, 4096  # bn_mle_evaluate_batch
 
 
 def lib_path():
@@ -68,6 +69,18 @@ class RsJob(C.Structure):
     """bn_rs_job: one equality indicator of bn_ring_switch_eq_ind_batch."""
 
     _fields_ = [("d_query", C.c_void_p), ("n_vars", C.c_uint32), ("kappa", C.c_uint32), ("mixing_coeff", F128)]
+
+
+class MePoint(C.Structure):
+    """bn_me_point: one point of bn_mle_evaluate_batch, as the tensor expansions of its first lo_vars and its other hi_vars coordinates."""
+
+    _fields_ = [("d_lo", C.c_void_p), ("d_hi", C.c_void_p), ("lo_vars", C.c_uint32), ("hi_vars", C.c_uint32)]
+
+
+class MeJob(C.Structure):
+    """bn_me_job: one column of bn_mle_evaluate_batch and the index of its point."""
+
+    _fields_ = [("d_evals", C.c_void_p), ("tower_level", C.c_uint32), ("n_vars", C.c_uint32), ("point", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class HalMultilinear(C.Structure):
@@ -171,6 +184,8 @@ def lib():
         "bn_univariate_fold_counters": [vp, C.POINTER(u64)],
         "bn_ring_switch_eq_ind_batch": [vp, vp, u32, PF, u32, C.POINTER(vp)],
         "bn_ring_switch_counters": [vp, C.POINTER(u64)],
+        "bn_mle_evaluate_batch": [vp, vp, u32, vp, u32, PF],
+        "bn_mle_evaluate_counters": [vp, C.POINTER(u64)],
         "bn_log_chunks_range": [C.POINTER(MemMap), u32, C.POINTER(u32), C.POINTER(u32)],
         "bn_pick_log_chunks": [C.POINTER(MemMap), u32, C.POINTER(u32)],
         "bn_kernel_launch": [vp, C.POINTER(MemMap), u32, C.POINTER(KOp), u32, C.POINTER(u32), u32, u32, PF, vp],
@@ -228,6 +243,7 @@ ABI_SYMBOLS = [
     "bn_product_tree_layers", "bn_pad_with_ones", "bn_exp_circuit_layers", "bn_bits_to_b128", "bn_exp_counters",
     "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
     "bn_univariate_fold_batch", "bn_univariate_fold_counters", "bn_ring_switch_eq_ind_batch", "bn_ring_switch_counters",
+    "bn_mle_evaluate_batch", "bn_mle_evaluate_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -950,6 +966,28 @@ class Context:
         c = (C.c_uint64 * 4)()
         _check(lib().bn_ring_switch_counters(self._h, c))
         return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2]), "queries": int(c[3])}
+
+    def mle_evaluate_batch(self, jobs, points):
+        """A batch of columns evaluated at their whole claim points in one call (bn_mle_evaluate_batch; the first step of
+        EvalcheckProver::prove, evalcheck/prove.rs:191-275, 812-879).  points: (lo DevSlice, lo_vars, hi DevSlice, hi_vars) per point,
+        the tensor expansions of its first lo_vars and its other hi_vars coordinates; jobs: (column DevSlice, tower_level, n_vars,
+        point_index) per job.  Returns the evaluations as ints, in job order."""
+        n, m = len(jobs), len(points)
+        for pt in points:
+            if (pt[0] is not None and 0 <= pt[1] <= 40 and pt[0].len != 1 << pt[1]) or (pt[2] is not None and 0 <= pt[3] <= 40 and pt[2].len != 1 << pt[3]):
+                raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: mle evaluate: a table holds 2^vars elements")
+        pts = (MePoint * max(1, m))(*[MePoint(pt[0].ptr if pt[0] is not None else None, pt[2].ptr if pt[2] is not None else None, pt[1], pt[3]) for pt in points])
+        table = (MeJob * max(1, n))(*[MeJob(jb[0].ptr if jb[0] is not None else None, jb[1], jb[2], jb[3], 0) for jb in jobs])
+        out = (F128 * max(1, n))()
+        _check(lib().bn_mle_evaluate_batch(self._h, C.cast(table, C.c_void_p), n, C.cast(pts, C.c_void_p), m, out))
+        return [from_f128(out[j]) for j in range(n)]
+
+    def mle_evaluate_counters(self):
+        """bn_mle_evaluate_counters: accepted bn_mle_evaluate_batch calls, the kernel launches they made, the jobs they served, the
+        largest number of workgroups that shared one job in the last call.  Rejected calls count nowhere."""
+        c = (C.c_uint64 * 4)()
+        _check(lib().bn_mle_evaluate_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2]), "max_share": int(c[3])}
 
     # ---- accumulate_kernels / map_kernels
     def pick_log_chunks(self, mem_maps):

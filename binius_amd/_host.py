@@ -88,6 +88,10 @@ def host_lib():
         ]
         L.bnh_evalcheck_bivariate_prove.restype = C.c_int
         L.bnh_evalcheck_bivariate_prove.argtypes = [C.c_void_p, C.c_uint32, U32P, U32P, VPP, FP, C.c_uint32, U32P, FP, C.c_void_p, C.c_uint64, FP, FP, FP, FP]
+        L.bnh_evalcheck_evaluate_scratch_elems.restype = C.c_uint64
+        L.bnh_evalcheck_evaluate_scratch_elems.argtypes = [C.c_uint32, U32P, C.c_uint32]
+        L.bnh_evalcheck_evaluate.restype = C.c_int
+        L.bnh_evalcheck_evaluate.argtypes = [C.c_void_p, C.c_uint32, U32P, VPP, FP, C.c_uint32, C.c_void_p, C.c_uint64, FP, DP]
         L.bnh_ring_switch_scratch_elems.restype = C.c_uint64
         L.bnh_ring_switch_scratch_elems.argtypes = [C.c_uint32, U32P, C.c_uint32, U32P]
         L.bnh_ring_switch_prove.restype = C.c_int
@@ -758,6 +762,54 @@ class EvalcheckPlan:
             out.append([from_f128(self.final[at + j]) for j in range(m)])
             at += m
         return out
+
+
+class EvalcheckEvaluatePlan:
+    """The evaluations in front of an evalcheck round (bnh_evalcheck_evaluate = evalcheck_evaluate_claims of binius_amd/host/evalcheck.hpp;
+    the first step of EvalcheckProver::prove, evalcheck/prove.rs:191-275).  claims: (column DevSlice, tower_level, n_vars, point_off,
+    point_len) per claim, the point pool[point_off : + point_len] with point_len == n_vars; pool: the shared list of point coordinates;
+    scratch: a device slice of at least scratch_elems(claims) elements.  Every point is split at min(point_len // 2, LO_SPLIT), distinct
+    prefix and suffix slices are expanded once, a repeated claim is evaluated once, one bn_mle_evaluate_batch serves all."""
+
+    LO_SPLIT = 8  # BNH_EVALCHECK_LO_SPLIT
+    PHASES = ("expand", "evaluate")
+
+    @classmethod
+    def scratch_elems(cls, claims, lo_split=None):
+        """2^len per distinct prefix slice and per distinct suffix slice of the pool."""
+        split = cls.LO_SPLIT if lo_split is None else lo_split
+        prefixes, suffixes, total = set(), set(), 0
+        for _col, _level, _n_vars, off, ln in claims:
+            lo = min(ln // 2, split)
+            if (off, lo) not in prefixes:
+                prefixes.add((off, lo))
+                total += 1 << lo
+            if (off + lo, ln - lo) not in suffixes:
+                suffixes.add((off + lo, ln - lo))
+                total += 1 << (ln - lo)
+        return total
+
+    def __init__(self, hal, claims, pool, scratch):
+        self.hal, self.scratch, self._keep = hal, scratch, claims
+        self.n = len(claims)
+        self.desc = (C.c_uint32 * max(1, 4 * self.n))(*[int(w) for c in claims for w in c[1:5]])
+        self.cols = (C.c_void_p * max(1, self.n))(*[(c[0].ptr if c[0] is not None else None) for c in claims])
+        self.pool, self.pool_len = _f128_array(list(pool) or [0]), len(pool)
+        self.out = (F128 * max(1, self.n))()
+        self.phase_ms = (C.c_double * 2)()
+
+    def run(self):
+        rc = host_lib().bnh_evalcheck_evaluate(self.hal._h, self.n, self.desc, self.cols, self.pool, self.pool_len,
+                                               self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0,
+                                               self.out, self.phase_ms)
+        if rc != 0:
+            raise BnError(rc, host_lib().bnh_last_error().decode())
+
+    def evals(self):
+        return [from_f128(self.out[i]) for i in range(self.n)]
+
+    def phase_times_ms(self):
+        return {name: self.phase_ms[i] for i, name in enumerate(self.PHASES)}
 
 
 class RingSwitchPlan:

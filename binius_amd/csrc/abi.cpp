@@ -841,6 +841,7 @@ int bn_ctx_destroy(bn_ctx *ctx)
 	if (ctx->d_ticket) hipFree(ctx->d_ticket);
 	if (ctx->h_result) hipHostFree(ctx->h_result);
 	if (ctx->h_mail) hipHostFree(ctx->h_mail);
+	if (ctx->h_me_rets) hipHostFree(ctx->h_me_rets);
 	if (ctx->h_gather) hipHostFree(ctx->h_gather);
 	if (ctx->ev0) hipEventDestroy(ctx->ev0);
 	if (ctx->ev1) hipEventDestroy(ctx->ev1);

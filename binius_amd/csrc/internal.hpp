@@ -83,6 +83,8 @@ struct bn_ctx {
 	uint64_t pe_calls = 0, pe_launches = 0, pe_cols_kernel = 0, pe_cols_fallback = 0, pe_max_share = 0, pe_routed = 0; // bn_partial_eval_counters
 	uint64_t uf_calls = 0, uf_launches = 0, uf_cols = 0; // bn_univariate_fold_batch (bn_univariate_fold_counters)
 	uint64_t rs_calls = 0, rs_launches = 0, rs_jobs = 0, rs_queries = 0; // bn_ring_switch_eq_ind_batch (bn_ring_switch_counters)
+	uint64_t me_calls = 0, me_launches = 0, me_jobs = 0, me_max_share = 0; // bn_mle_evaluate_batch (bn_mle_evaluate_counters)
+	bn::f128 *h_me_rets = nullptr, *d_me_rets = nullptr; // pinned: the results of a bn_mle_evaluate_batch call, BN_ME_MAX_JOBS values (the sequence word stays in h_mail[64])
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	int n_cu = 256;
@@ -826,6 +828,28 @@ constexpr uint32_t kPeLogVecChunk = 10; // entries of `vec` a workgroup stages i
 // n_groups == 1 && d_groups == nullptr: the group and its single column travel as kernel arguments (no table upload)
 hipError_t launch_partial_eval(hipStream_t s, const pe_group *d_groups, uint32_t n_groups, const pe_col *d_cols, uint32_t n_cols, pe_group one_group,
                                pe_col one_col, const void *vec, uint32_t total_units, bool bits_only);
+
+// ---- kernels_mle_eval.hip: a batch of columns evaluated at their whole points (EvalcheckProver::prove's first step, evalcheck/prove.rs:191-275,
+// 812-879): slot_j = sum_l lo[l] * sum_h hi[h] * M_j[h * 2^b + l].  A unit (one workgroup) is a chunk of 2^log_ch rows h of a GROUP of jobs of
+// one class (point, tower level), walked in stages of 2^kPeLogVecChunk rows of `hi`; the 2^b partial sums of every job of the group live in
+// LDS, the epilogue multiplies them by `lo` and XOR-combines one element per job into its slot (zeroed by the call's upload).
+struct me_job {
+	const uint64_t *evals;
+	uint64_t *slot; // the job's 16-byte result
+};
+struct me_group {
+	const void *lo, *hi;   // the point's tables: 2^b and 2^q elements
+	uint32_t first, count; // jobs [first, first + count) of the job table
+	uint32_t level, b;
+	uint32_t log_ch;       // 2^log_ch rows per unit (<= q)
+	uint32_t start;        // first unit of this group in the launch
+};
+constexpr uint32_t kMeGroupJobs = 8;   // jobs of a group ...
+constexpr uint32_t kMeAccs = 1u << 10; // ... as far as their 2^b accumulators each fit these LDS entries (16 KiB)
+// bits_only: every group is at level 0
+hipError_t launch_mle_eval(hipStream_t s, const me_group *d_groups, uint32_t n_groups, const me_job *d_jobs, uint32_t total_units, bool bits_only);
+// d_rets[j] = d_slots[j], j < n_jobs, into pinned host memory, then the mailbox's sequence word
+hipError_t launch_me_publish(hipStream_t s, const f128 *d_slots, uint32_t n_jobs, f128 *d_rets, f128 *d_mail, uint64_t seq);
 
 // ---- kernels_univariate_fold.hip: the fold of the univariate round of the univariate-skip zerocheck for a batch of columns
 // (fold_univariate_round, core/src/protocols/sumcheck/prove/zerocheck.rs:384-434): out_c[x] = sum_{u < 2^k} coeffs[u] * M_c(u + 2^k x).

@@ -20,6 +20,14 @@
 // the reversed challenges r' (r'[i] = the challenge of round b - 1 - i of its prover) is the new evalcheck claim (r' || suffix, v)
 // on its inner column; a shift indicator's or tower basis's final evaluation is what the verifier recomputes itself.
 //
+// evalcheck_evaluate_claims is the step in FRONT of every round: EvalcheckProver::prove evaluates the materialised witness of every leaf
+// oracle whose value is not yet known at its whole claim point ("MLE Fold Full", evalcheck/prove.rs:191-275, make_new_eval_claim :812-879).
+// The reference splits the point in the middle, reuses an already memoised suffix when it has one (:211-221), takes evaluate_partial_high
+// at the suffix and evaluates the result at the prefix.  The arithmetic is exact, so the value does not depend on where the point is
+// split: the mirror splits at min(|point| / 2, kEvalcheckLoSplit), the split the device op is fastest at, and does not reproduce the
+// reference's middle split or its suffix reuse.  Handing the per-(column, suffix) partial evaluations on to collect_projected_mles
+// stays out of scope.
+//
 // Protocol bookkeeping only: every hypercube-sized operation is a call of the backend.
 #pragma once
 #include <algorithm>
@@ -205,6 +213,96 @@ inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::v
 		sc.push_back(std::make_unique<BivariateSumcheckProver>(hal, alloc, host_alloc, p.n_vars, p.compositions, p.sums, mls));
 	}
 	return SumcheckBatchProver<BivariateSumcheckProver>(std::move(sc), batch_coeffs).run(challenges.data());
+}
+
+// ---- the evaluations in front of a round (prove.rs:191-275)
+struct EvalcheckEvalClaim {
+	const void *d_column = nullptr; // 2^n_vars values of tower_level, packed into F, only read
+	uint32_t tower_level = 0, n_vars = 0;
+	uint32_t point_off = 0, point_len = 0; // the point pool[point_off .. + point_len), point_len == n_vars
+};
+
+// The low part of every point has min(|point| / 2, kEvalcheckLoSplit) coordinates (<= BN_ME_MAX_LO_VARS).  Measured at 256 B1 columns
+// of 2^22 bits (profiles/r15/README.md): the sweep over 6, 8, 10.
+constexpr uint32_t kEvalcheckLoSplit = 8;
+inline uint32_t evalcheck_lo_vars(uint32_t point_len, uint32_t lo_split = kEvalcheckLoSplit) { return std::min(point_len / 2, lo_split); }
+
+// Exact: 2^len per distinct prefix slice and per distinct suffix slice of the pool.
+inline size_t evalcheck_evaluate_scratch_elems(const std::vector<EvalcheckEvalClaim> &claims, uint32_t lo_split = kEvalcheckLoSplit)
+{
+	if (lo_split > BN_ME_MAX_LO_VARS) throw Error(Error::InputValidation, "the split of a point is at most BN_ME_MAX_LO_VARS");
+	std::map<EvalcheckSuffix, bool> prefixes, suffixes;
+	size_t total = 0;
+	for (const EvalcheckEvalClaim &c : claims) {
+		if (c.point_len > BN_PE_MAX_VARS) throw Error(Error::InputValidation, "a point has at most BN_PE_MAX_VARS coordinates");
+		const uint32_t lo = evalcheck_lo_vars(c.point_len, lo_split);
+		if (prefixes.emplace(EvalcheckSuffix{c.point_off, lo}, true).second) total += (size_t)1 << lo;
+		if (suffixes.emplace(EvalcheckSuffix{c.point_off + lo, c.point_len - lo}, true).second) total += (size_t)1 << (c.point_len - lo);
+	}
+	return total;
+}
+
+struct EvalcheckEvaluateOutput {
+	std::vector<B128> evals; // in claim order
+	enum { Expand = 0, Evaluate = 1, NPhases = 2 };
+	double phase_ms[NPhases] = {};
+};
+
+// Every distinct prefix and suffix slice is expanded once (memoize_query_par, subclaims.rs:489-508), a repeated (column, level, point)
+// is evaluated once (visited_claims), and ONE bn_mle_evaluate_batch serves everything.
+inline EvalcheckEvaluateOutput evalcheck_evaluate_claims(ComputeLayer &hal, const std::vector<EvalcheckEvalClaim> &claims, const std::vector<B128> &pool, FSliceMut scratch)
+{
+	for (const EvalcheckEvalClaim &c : claims) {
+		if (!c.d_column) throw Error(Error::InputValidation, "null column");
+		if (c.tower_level > 7 || c.tower_level == 1 || c.tower_level == 2) throw Error(Error::InputValidation, "unsupported value of tower_level");
+		if (c.point_len != c.n_vars) throw Error(Error::InputValidation, "a claim's point has n_vars coordinates");
+		if ((size_t)c.point_off + c.point_len > pool.size()) throw Error(Error::InputValidation, "a point leaves the point pool");
+	}
+	if (scratch.len_ < evalcheck_evaluate_scratch_elems(claims)) throw Error(Error::InputValidation, "scratch holds fewer than evalcheck_evaluate_scratch_elems elements");
+	EvalcheckEvaluateOutput out;
+	out.evals.assign(claims.size(), B128::ZERO());
+	if (claims.empty()) return out;
+	const auto t_begin = std::chrono::steady_clock::now();
+	DeviceBumpAllocator alloc(scratch);
+	std::map<EvalcheckSuffix, const void *> prefixes, suffixes;
+	auto table = [&](std::map<EvalcheckSuffix, const void *> &memo, uint32_t off, uint32_t len) {
+		auto it = memo.find({off, len});
+		if (it == memo.end()) {
+			const FSliceMut t = ops::eq_ind_partial_eval(hal, alloc, std::vector<B128>(pool.begin() + off, pool.begin() + off + len), /*expand_empty=*/false);
+			it = memo.emplace(EvalcheckSuffix{off, len}, t.ptr).first;
+		}
+		return it->second;
+	};
+	std::map<EvalcheckSuffix, uint32_t> point_index;
+	std::vector<bn_me_point> points;
+	using ClaimKey = std::pair<std::pair<const void *, uint32_t>, EvalcheckSuffix>; // (column, level), point
+	std::map<ClaimKey, uint32_t> visited;
+	std::vector<bn_me_job> jobs;
+	std::vector<uint32_t> job_of(claims.size());
+	for (size_t i = 0; i < claims.size(); i++) {
+		const EvalcheckEvalClaim &c = claims[i];
+		const ClaimKey key{{c.d_column, c.tower_level}, {c.point_off, c.point_len}};
+		auto seen = visited.find(key);
+		if (seen == visited.end()) {
+			auto pt = point_index.find({c.point_off, c.point_len});
+			if (pt == point_index.end()) {
+				const uint32_t lo = evalcheck_lo_vars(c.point_len);
+				const void *d_lo = table(prefixes, c.point_off, lo), *d_hi = table(suffixes, c.point_off + lo, c.point_len - lo);
+				pt = point_index.emplace(EvalcheckSuffix{c.point_off, c.point_len}, (uint32_t)points.size()).first;
+				points.push_back(bn_me_point{d_lo, d_hi, lo, c.point_len - lo});
+			}
+			seen = visited.emplace(key, (uint32_t)jobs.size()).first;
+			jobs.push_back(bn_me_job{c.d_column, c.tower_level, c.n_vars, pt->second, 0});
+		}
+		job_of[i] = seen->second;
+	}
+	const auto t_expand = std::chrono::steady_clock::now();
+	out.phase_ms[EvalcheckEvaluateOutput::Expand] = elapsed_ms(t_begin, t_expand);
+	std::vector<bn_f128> vals(jobs.size());
+	check(bn_mle_evaluate_batch(hal.raw_ctx(), jobs.data(), (uint32_t)jobs.size(), points.data(), (uint32_t)points.size(), vals.data()));
+	for (size_t i = 0; i < claims.size(); i++) out.evals[i] = B128(vals[job_of[i]].lo, vals[job_of[i]].hi);
+	out.phase_ms[EvalcheckEvaluateOutput::Evaluate] = elapsed_ms(t_expand);
+	return out;
 }
 
 } // namespace binius_amd

@@ -1112,6 +1112,45 @@ int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_
 	});
 }
 
+// The evaluations in front of an evalcheck round (evalcheck/prove.rs:191-275) through evalcheck_evaluate_claims of the same mirror; the
+// arguments are described in include/binius_amd_host.h.
+static_assert(BNH_EVALCHECK_LO_SPLIT == kEvalcheckLoSplit, "include/binius_amd_host.h states the split the mirror uses");
+namespace {
+std::vector<EvalcheckEvalClaim> evalcheck_eval_claims(uint32_t n_claims, const uint32_t *claim_desc, const void *const *d_columns)
+{
+	std::vector<EvalcheckEvalClaim> claims;
+	for (uint32_t i = 0; i < n_claims; i++)
+		claims.push_back(EvalcheckEvalClaim{d_columns ? d_columns[i] : nullptr, claim_desc[4 * i], claim_desc[4 * i + 1], claim_desc[4 * i + 2], claim_desc[4 * i + 3]});
+	return claims;
+}
+} // namespace
+
+uint64_t bnh_evalcheck_evaluate_scratch_elems(uint32_t n_claims, const uint32_t *claim_desc, uint32_t lo_split)
+{
+	if (n_claims && !claim_desc) return 0;
+	try {
+		return evalcheck_evaluate_scratch_elems(evalcheck_eval_claims(n_claims, claim_desc, nullptr), lo_split ? lo_split : kEvalcheckLoSplit);
+	} catch (const Error &) {
+		return 0;
+	}
+}
+
+int bnh_evalcheck_evaluate(bn_ctx *ctx, uint32_t n_claims, const uint32_t *claim_desc, const void *const *d_columns, const bn_f128 *point_pool, uint32_t pool_len,
+                           void *d_scratch, uint64_t scratch_elems, bn_f128 *evals_out, double *phase_ms_out)
+{
+	return guarded([&]() -> int {
+		if (!ctx || (n_claims && (!claim_desc || !d_columns || !evals_out)) || (pool_len && !point_pool) || (!d_scratch && scratch_elems))
+			throw Error(Error::InputValidation, "null argument");
+		ComputeLayer hal(ctx);
+		const EvalcheckEvaluateOutput out = evalcheck_evaluate_claims(hal, evalcheck_eval_claims(n_claims, claim_desc, d_columns), from_raw(point_pool, pool_len),
+		                                                              FSliceMut{d_scratch, (size_t)scratch_elems});
+		if (!out.evals.empty()) to_raw(out.evals, evals_out);
+		if (phase_ms_out)
+			for (int i = 0; i < EvalcheckEvaluateOutput::NPhases; i++) phase_ms_out[i] = out.phase_ms[i];
+		return 0;
+	});
+}
+
 // batch_zerocheck::batch_prove (crates/core/src/protocols/sumcheck/prove/batch_zerocheck.rs:166-293) through the C++ mirror
 // binius_amd/host/zerocheck.hpp; the arguments are described in include/binius_amd_host.h.
 uint64_t bnh_zerocheck_batch_scratch_elems(uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols)

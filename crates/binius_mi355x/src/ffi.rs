@@ -111,6 +111,13 @@ pub const BN_RS_CALLS: usize = 0;
 pub const BN_RS_LAUNCHES: usize = 1;
 pub const BN_RS_JOBS: usize = 2;
 pub const BN_RS_QUERIES: usize = 3;
+pub const BN_ME_N: usize = 4;
+pub const BN_ME_CALLS: usize = 0;
+pub const BN_ME_LAUNCHES: usize = 1;
+pub const BN_ME_JOBS: usize = 2;
+pub const BN_ME_MAX_SHARE: usize = 3;
+pub const BN_ME_MAX_LO_VARS: u32 = 10;
+pub const BN_ME_MAX_JOBS: u32 = 4096;
 pub const BN_UNIVARIATE_FOLD_MAX_SKIP: u32 = 8;
 pub const BN_EXP_STATIC: u32 = 0;
 pub const BN_EXP_DYNAMIC: u32 = 1;
@@ -138,6 +145,25 @@ pub struct bn_rs_job {
 	pub n_vars: u32,
 	pub kappa: u32,
 	pub mixing_coeff: bn_f128,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bn_me_point {
+	pub d_lo: *const c_void,
+	pub d_hi: *const c_void,
+	pub lo_vars: u32,
+	pub hi_vars: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bn_me_job {
+	pub d_evals: *const c_void,
+	pub tower_level: u32,
+	pub n_vars: u32,
+	pub point: u32,
+	pub reserved: u32,
 }
 
 #[repr(C)]
@@ -333,6 +359,15 @@ unsafe extern "C" {
 		d_outs: *const *mut c_void,
 	) -> c_int;
 	pub fn bn_ring_switch_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_mle_evaluate_batch(
+		ctx: *mut bn_ctx,
+		jobs: *const c_void,
+		n_jobs: u32,
+		points: *const c_void,
+		n_points: u32,
+		h_out: *mut bn_f128,
+	) -> c_int;
+	pub fn bn_mle_evaluate_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 
 	pub fn bn_log_chunks_range(maps: *const bn_memmap, n_maps: u32, start: *mut u32, end: *mut u32) -> c_int;
 	pub fn bn_pick_log_chunks(maps: *const bn_memmap, n_maps: u32, log_chunks: *mut u32) -> c_int;

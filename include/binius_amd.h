@@ -299,6 +299,47 @@ int bn_ring_switch_eq_ind_batch(bn_ctx *ctx, const void *jobs, uint32_t n_jobs, 
  * nowhere. */
 enum { BN_RS_CALLS = 0, BN_RS_LAUNCHES = 1, BN_RS_JOBS = 2, BN_RS_QUERIES = 3, BN_RS_N = 4 };
 int bn_ring_switch_counters(bn_ctx *ctx, uint64_t *counters /*[BN_RS_N]*/);
+/* A batch of columns evaluated at their whole claim points: the first step of every EvalcheckProver::prove call ("MLE Fold Full",
+ * core/src/protocols/evalcheck/prove.rs:191-275, make_new_eval_claim evalcheck/prove.rs:812-879), which splits the point into a prefix
+ * and a suffix, takes evaluate_partial_high of the column at the suffix and evaluate of the result at the prefix
+ * (math/src/multilinear_extension.rs evaluate / evaluate_partial_high).  Point p (points[p], a HOST array of bn_me_point) has d_lo,
+ * the 2^lo_vars B128 elements of the tensor expansion of its first lo_vars coordinates, lo_vars <= BN_ME_MAX_LO_VARS, and d_hi, the
+ * 2^hi_vars elements of the expansion of the rest (the reference's memoised prefix and suffix query), both on the device.  Job j
+ * (jobs[j], a HOST array of bn_me_job) names a column of 2^n_vars values of tower level 0 or 3..7 packed into F as
+ * bn_partial_eval_high_batch takes them (n_vars + tower_level >= 7) and a point with lo_vars + hi_vars == n_vars; reserved is 0.
+ *   h_out[j] = sum_h hi[h] * sum_l lo[l] * col[h * 2^lo_vars + l],
+ * bit-exact, valid when the call returns (published through pinned memory and the sequence word, as bn_inner_product and
+ * bn_xor_reduce publish theirs).  lo_vars = 0 and hi_vars = 0 are legal: a plain inner product with one table.  Columns and tables
+ * are only read; pointers are 16-byte aligned; the work is issued on the context's stream.  n_jobs = 0 is a no-op.  A null or
+ * misaligned pointer, lo_vars above BN_ME_MAX_LO_VARS, lo_vars + hi_vars != n_vars, tower level 1 or 2 or above 7, a column of less
+ * than one 128-bit element, a point index outside the table, reserved != 0 and more than BN_ME_MAX_JOBS jobs are
+ * BN_ERR_INPUT_VALIDATION: nothing is launched and nothing is counted.
+ * TWO launches per call whatever the number of jobs, their levels, sizes and points: the evaluation kernel (a workgroup takes a
+ * chunk of the high rows of up to eight jobs of one point and level, keeps their 2^lo_vars partial sums in LDS, multiplies them by
+ * lo once and XOR-combines one element per job) and the kernel that publishes the results. */
+typedef struct {
+	const void *d_lo;
+	const void *d_hi;
+	uint32_t lo_vars;
+	uint32_t hi_vars;
+} bn_me_point;
+typedef struct {
+	const void *d_evals;
+	uint32_t tower_level;
+	uint32_t n_vars;
+	uint32_t point;
+	uint32_t reserved;
+} bn_me_job;
+#define BN_ME_MAX_LO_VARS 10
+#define BN_ME_MAX_JOBS 4096 /* the pinned result area of a context holds this many evaluations */
+/* (jobs points to n_jobs bn_me_job, points to n_points bn_me_point; untyped in the prototype for the same reason as
+ * bn_partial_eval_high_batch's cols.) */
+int bn_mle_evaluate_batch(bn_ctx *ctx, const void *jobs, uint32_t n_jobs, const void *points, uint32_t n_points, bn_f128 *h_out /*[n_jobs]*/);
+/* Read-only, per context (not part of the reference interface): accepted bn_mle_evaluate_batch calls, the kernel launches they made,
+ * the jobs they served, the largest number of workgroups that shared one job in the last call.  A rejected call counts nowhere; the
+ * BN_PE_* counters do not move. */
+enum { BN_ME_CALLS = 0, BN_ME_LAUNCHES = 1, BN_ME_JOBS = 2, BN_ME_MAX_SHARE = 3, BN_ME_N = 4 };
+int bn_mle_evaluate_counters(bn_ctx *ctx, uint64_t *counters /*[BN_ME_N]*/);
 
 /* ---- accumulate_kernels / map_kernels (layer.rs:183, 236) + KernelExecutor (layer.rs:518-590).
  * The kernel-spec closure cannot cross an FFI: the host shim runs it ONCE against a recording

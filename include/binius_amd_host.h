@@ -304,6 +304,28 @@ int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_
                                   uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges, bn_f128 *round_proofs_out,
                                   bn_f128 *final_evals_out);
 
+/* The evaluations in front of every evalcheck round: EvalcheckProver::prove evaluates the materialised witness of every leaf oracle whose
+ * value is not yet known at its whole claim point ("MLE Fold Full", core/src/protocols/evalcheck/prove.rs:191-275, make_new_eval_claim
+ * :812-879: evaluate_partial_high at the suffix of the point, then evaluate at its prefix) through the C++ mirror binius_amd/host/
+ * evalcheck.hpp (evalcheck_evaluate_claims).  Which oracles are leaves and which values are known (collect_subclaims_for_memoization,
+ * :350-467) stays with the caller.
+ *   claim_desc[4 * i] = (tower_level, n_vars, point_off, point_len): claim i is the column d_columns[i] (2^n_vars values of tower level 0 or
+ *     3..7 packed into F as bn_mle_evaluate_batch takes them, only read) at the point point_pool[point_off .. + point_len), point_len == n_vars
+ * Every point is split at lo = min(point_len / 2, BNH_EVALCHECK_LO_SPLIT); every distinct prefix slice [off, off + lo) and every distinct
+ * suffix slice [off + lo, off + len) of the pool is tensor-expanded once (memoize_query_par, evalcheck/subclaims.rs:489-508); a repeated
+ * (column, level, point) is evaluated once (visited_claims); ONE bn_mle_evaluate_batch serves everything; evals_out[i] is the value of
+ * claim i.  The arithmetic is exact, so the values do not depend on the split: the mirror reproduces neither the reference's middle
+ * split nor its reuse of an already memoised suffix (prove.rs:211-221).
+ *   d_scratch: at least bnh_evalcheck_evaluate_scratch_elems elements (the formula is exact): 2^len per distinct prefix slice and per
+ *     distinct suffix slice.  lo_split: the bound of the split to plan for, at most BN_ME_MAX_LO_VARS; 0 = BNH_EVALCHECK_LO_SPLIT, the one
+ *     bnh_evalcheck_evaluate uses.  Returns 0 for a null list or a lo_split out of range.
+ * A short scratch, point_len != n_vars, a slice outside the pool and a tower level of 1 or 2 are BN_ERR_INPUT_VALIDATION before anything is
+ * launched.  phase_ms_out[2] (may be null): wall milliseconds of the expansions and of the evaluation call. */
+#define BNH_EVALCHECK_LO_SPLIT 8
+uint64_t bnh_evalcheck_evaluate_scratch_elems(uint32_t n_claims, const uint32_t *claim_desc, uint32_t lo_split);
+int bnh_evalcheck_evaluate(bn_ctx *ctx, uint32_t n_claims, const uint32_t *claim_desc, const void *const *d_columns, const bn_f128 *point_pool,
+                           uint32_t pool_len, void *d_scratch, uint64_t scratch_elems, bn_f128 *evals_out, double *phase_ms_out);
+
 /* The ring-switching reduction: ring_switch::prove (core/src/ring_switch/prove.rs:42-144) through the C++ mirror binius_amd/host/
  * ring_switch.hpp.  The caller has done the oracle-set bookkeeping of EvalClaimSystem::new (ring_switch/common.rs:72-205).
  *   d_columns[c], column_desc[2 * c] = (tower_level, n_vars): the committed columns, 2^n_vars values packed into F as bn_partial_eval_high_batch

@@ -28,8 +28,11 @@ Phases, in the order of core/src/constraint_system/prove.rs:74-588 (keccak has n
 What the replay is NOT: the witness is random (on-device tensor expansions), so the constraints do not hold and the claimed sums
 are whatever the columns give -- the provers and kernels do the same arithmetic on the same shapes; the univariate-skip rounds
 and the small-field switchover of the reference's zerocheck (which run on its CPU `Backend`, not on the ComputeLayer) are replaced
-by the large-field rounds over the packed columns; evalcheck's bookkeeping between zerocheck and ring-switch is host-only in the
-reference and absent here.
+by the large-field rounds over the packed columns; the evalcheck phase between zerocheck and ring-switch is not replayed.  Its two
+device pieces exist behind the C ABI -- bnh_evalcheck_evaluate (the evaluations in front of every round: all leaf columns at their
+points in one bn_mle_evaluate_batch, tools/bench_mle_evaluate.py) and bnh_evalcheck_bivariate_prove (one round of the shifted / packed
+sumchecks, tools/bench_evalcheck.py) --; the greedy loop with EvalcheckProver's oracle bookkeeping, prove_mlecheck_with_switchover for
+composite claims and a phase here that strings them together do not.
 
 Checks: at any size the VERIFIER's equations on what the device produced (zerocheck: every round polynomial sums to the running
 claim, the last claim is the batched compositions of the final evaluations times the indicator; piop: RoundProof::recover chain and
