@@ -192,6 +192,7 @@ def lib():
         "bn_hal_round_evals": [vp, u32, u32, vp, u32, C.POINTER(HalMultilinear), u32, C.POINTER(HalEvaluator), u32, PF, u32, PF],
         "bn_hal_fold_multilinear": [vp, u32, u32, C.POINTER(HalMultilinear), PF, vp, u32, vp, u64, C.POINTER(u64)],
         "bn_zerocheck_univariate_evals": [vp, u32, u32, C.POINTER(HalMultilinear), u32, C.POINTER(Step), C.POINTER(u32), C.POINTER(u32), u32, vp, u64, u32, PF, PF],
+        "bn_zerocheck_univariate_evals_base": [vp, u32, u32, u32, C.POINTER(HalMultilinear), u32, C.POINTER(Step), C.POINTER(u32), C.POINTER(u32), u32, vp, u64, u32, PF, PF],
         "bn_ntt_forward": [vp, vp, u32, u32, C.POINTER(u64), u32, u32, u32, u32, u64, u32, u32],
         "bn_ntt_inverse": [vp, vp, u32, u32, C.POINTER(u64), u32, u32, u32, u32, u64, u32, u32],
         "bn_ntt_s_evals": [u32, u32, C.POINTER(u64)],
@@ -239,7 +240,7 @@ ABI_SYMBOLS = [
     "bn_kernel_launch", "bn_ntt_forward", "bn_ntt_inverse", "bn_ntt_s_evals", "bn_scalar_mul", "bn_scalar_invert",
     "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_ntt_counters", "bn_fri_counters", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
     "bn_merkle_build", "bn_groestl256_leaves", "bn_groestl256_compress_layer", "bn_gather_d2h",
-    "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals",
+    "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals", "bn_zerocheck_univariate_evals_base",
     "bn_product_tree_layers", "bn_pad_with_ones", "bn_exp_circuit_layers", "bn_bits_to_b128", "bn_exp_counters",
     "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
     "bn_univariate_fold_batch", "bn_univariate_fold_counters", "bn_ring_switch_eq_ind_batch", "bn_ring_switch_counters",
@@ -729,12 +730,18 @@ class Context:
         _check(lib().bn_hal_fold_multilinear(self._h, order, n_vars, C.byref(m), C.byref(z), q_ptr, q_vars, out.ptr, out.len, C.byref(n)))
         return n.value
 
-    def zerocheck_univariate_evals(self, n_vars, skip_rounds, columns, compositions, degrees, eq, max_domain_size, batch_coeff=None):
+    def zerocheck_univariate_evals_base(self, base_level, n_vars, skip_rounds, columns, compositions, degrees, eq, max_domain_size, batch_coeff=None):
+        """zerocheck_univariate_evals for every arm of constraint_system/prove.rs:483-490 (bn_zerocheck_univariate_evals_base):
+        base_level 3 .. 7 = compositions over B8 .. B128, columns at tower level 0 or 3 .. base_level (little-endian values of
+        2^(level - 3) bytes), constants in the base field.  base_level 3 is the call below."""
+        return self.zerocheck_univariate_evals(n_vars, skip_rounds, columns, compositions, degrees, eq, max_domain_size, batch_coeff, base_level=base_level)
+
+    def zerocheck_univariate_evals(self, n_vars, skip_rounds, columns, compositions, degrees, eq, max_domain_size, batch_coeff=None, base_level=None):
         """The univariate round of the univariate-skip zerocheck (bn_zerocheck_univariate_evals; prove/univariate.rs:235-507).
         columns: [(DevSlice of packed values, tower_level 0 or 3)] of 2^n_vars values each; compositions: step lists over B8;
         degrees: one per composition; eq: DevSlice of the 2^(n_vars - skip_rounds) expanded zerocheck challenges.  Returns per
         composition the list of P_c(omega_j), 2^skip_rounds <= j < max_domain_size -- or, with batch_coeff, the one list of
-        sum_c batch_coeff^c P_c."""
+        sum_c batch_coeff^c P_c.  base_level (None: this entry point) selects bn_zerocheck_univariate_evals_base."""
         mls = (HalMultilinear * max(1, len(columns)))()
         for i, (sl, level) in enumerate(columns):
             mls[i].kind, mls[i].tower_level, mls[i].d_evals, mls[i].len, mls[i].n_vars_ml = HAL_ML_TRANSPARENT, level, sl.ptr, sl.len, n_vars
@@ -748,9 +755,12 @@ class Context:
         n_out = max(0, max_domain_size - (1 << skip_rounds))
         out = (F128 * max(1, n_out if batch_coeff is not None else n_out * len(compositions)))()
         bc = to_f128(batch_coeff) if batch_coeff is not None else None
-        _check(lib().bn_zerocheck_univariate_evals(self._h, n_vars, skip_rounds, mls, len(columns), st, off_arr, deg_arr, len(compositions),
-                                                   eq.ptr if eq is not None else None, eq.len if eq is not None else 0, max_domain_size,
-                                                   C.byref(bc) if bc is not None else None, out))
+        tail = (mls, len(columns), st, off_arr, deg_arr, len(compositions), eq.ptr if eq is not None else None, eq.len if eq is not None else 0,
+                max_domain_size, C.byref(bc) if bc is not None else None, out)
+        if base_level is None:
+            _check(lib().bn_zerocheck_univariate_evals(self._h, n_vars, skip_rounds, *tail))
+        else:
+            _check(lib().bn_zerocheck_univariate_evals_base(self._h, base_level, n_vars, skip_rounds, *tail))
         if batch_coeff is not None:
             return [from_f128(out[i]) for i in range(n_out)]
         return [[from_f128(out[c * n_out + i]) for i in range(n_out)] for c in range(len(compositions))]

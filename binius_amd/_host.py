@@ -104,6 +104,10 @@ def host_lib():
             C.c_void_p, C.c_uint32, C.c_uint32, U32P, U32P, VPP, U32P, U32P, C.c_void_p, U32P, C.c_void_p, U32P, U32P, FP, FP, FP, FP, FP, FP, C.c_void_p, C.c_uint64,
             FP, FP, FP, FP, FP, FP, FP, FP, DP, U64P,
         ]
+        L.bnh_zerocheck_batch_scratch_elems_tower.restype = C.c_uint64
+        L.bnh_zerocheck_batch_scratch_elems_tower.argtypes = [C.c_uint32, C.c_uint32, U32P, U32P, U32P]
+        L.bnh_zerocheck_batch_prove_tower.restype = C.c_int
+        L.bnh_zerocheck_batch_prove_tower.argtypes = L.bnh_zerocheck_batch_prove.argtypes
         L.bnh_rccl_open.argtypes = [C.c_char_p]
         L.bnh_rccl_unique_id.argtypes = [C.c_void_p]
         L.bnh_rccl_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -1025,22 +1029,28 @@ class ZerocheckBatchPlan:
     skip_rounds; zerocheck_challenges and sumcheck_challenges: max_n - k each; batch_coeffs: one per table; reduction_challenges: k;
     scratch: a device slice of at least scratch_elems(tables, k) elements.  run() returns the proof as a dict: message, round_coeffs (all
     coefficients, padded to max(2, largest degree) + 2), final_evals (per table, the indicator's last), reduction_round_coeffs,
-    reduction_final_evals, skipped_challenges, unskipped_challenges, concat_multilinear_evals; phase_ms / phase_calls afterwards."""
+    reduction_final_evals, skipped_challenges, unskipped_challenges, concat_multilinear_evals; phase_ms / phase_calls afterwards.
+    tower=True is bnh_zerocheck_batch_prove_tower: every arm of constraint_system/prove.rs:483-490 -- columns at tower_level 0 or 3 .. 7
+    (little-endian values of 2^(level - 3) bytes), constants anywhere in B128, a table's arm chosen from its levels; the fold phase's call
+    count then includes one bn_fold_right per column above level 3.  With the default the old entry point is called."""
 
     PHASES = ("univariate", "fold", "multilinear", "projection", "reduction")
 
     @staticmethod
-    def scratch_elems(tables, k):
+    def scratch_elems(tables, k, tower=False):
         n = len(tables)
         nv = (C.c_uint32 * max(1, n))(*[t[0] for t in tables])
         nc = (C.c_uint32 * max(1, n))(*[len(t[1]) for t in tables])
+        if tower:  # (the formula depends on the levels: a padded column takes what its level needs)
+            levels = [c[1] for t in tables for c in t[1]]
+            return int(host_lib().bnh_zerocheck_batch_scratch_elems_tower(n, k, nv, nc, (C.c_uint32 * max(1, len(levels)))(*levels)))
         return int(host_lib().bnh_zerocheck_batch_scratch_elems(n, k, nv, nc))
 
     def __init__(self, hal, tables, k, zerocheck_challenges, batch_coeffs, univariate_challenge, sumcheck_challenges, reduction_batch_coeff,
-                 reduction_challenges, scratch):
+                 reduction_challenges, scratch, tower=False):
         from ._ffi import make_steps
 
-        self.hal, self.k, self.n = hal, k, len(tables)
+        self.hal, self.k, self.n, self.tower = hal, k, len(tables), bool(tower)
         self._keep = (tables, scratch)
         self.n_cols = [len(t[1]) for t in tables]
         self.nv = (C.c_uint32 * max(1, self.n))(*[t[0] for t in tables])
@@ -1078,7 +1088,8 @@ class ZerocheckBatchPlan:
     def run(self):
         if self.lens != (self.rounds, self.rounds, self.n, self.k):
             raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: zerocheck: max_n - k zerocheck and sumcheck challenges, one coefficient per table, k reduction challenges")
-        rc = host_lib().bnh_zerocheck_batch_prove(
+        prove = host_lib().bnh_zerocheck_batch_prove_tower if self.tower else host_lib().bnh_zerocheck_batch_prove
+        rc = prove(
             self.hal._h, self.n, self.k, self.nv, self.nc, self.ptrs, self.levels, self.ncomp, C.cast(self.steps, C.c_void_p), self.n_steps,
             C.cast(self.steps_inf, C.c_void_p), self.n_steps_inf, self.degrees, self.zc, self.bc, C.byref(self.z), self.sc, C.byref(self.rb), self.rc,
             self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0, self.message, self.coeffs, self.final,

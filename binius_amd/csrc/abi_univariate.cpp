@@ -5,6 +5,10 @@
 // kernels_univariate.hip produce R_c(omega_j) for 2^k <= j < d_c 2^k, and the host extrapolates to the max domain
 // (extrapolate_round_evals, univariate.rs:571-640) with barycentric Lagrange weights in B8.  Any method is bit-exact here: the
 // polynomial of degree < d_c 2^k through those values and the 2^k zeros in front is unique.
+//
+// bn_zerocheck_univariate_evals_base is the same round for the wide arms (:485-488, 4 => B16 .. 7 => B128): the same host tables,
+// validation and extrapolation -- the domain stays B8 --, with columns up to the base level, constants in the base field and the
+// kernels of kernels_univariate_base.hip.  base_level 3 forwards to the entry point above.
 #include <algorithm>
 
 #include "abi_common.hpp"
@@ -104,13 +108,13 @@ void extrapolate(uint32_t k, uint32_t d, uint32_t D, const f128 *r, f128 *dst)
 	}
 }
 
-} // namespace
+// is the constant an element of T_base (base 3 .. 7)?
+bool const_in_base(const bn_f128 &c, uint32_t base) { return base >= 7 || (c.hi == 0 && (base == 6 || c.lo < ((uint64_t)1 << (1u << base)))); }
 
-extern "C" {
-
-int bn_zerocheck_univariate_evals(bn_ctx *ctx, uint32_t n_vars, uint32_t skip_rounds, const bn_hal_multilinear *mls, uint32_t n_mls,
-                                  const bn_step *steps, const uint32_t *step_offsets, const uint32_t *degrees, uint32_t n_comps, const void *d_eq,
-                                  uint64_t eq_len, uint32_t max_domain_size, const bn_f128 *h_batch_coeff, bn_f128 *h_out)
+// the round over T_base: base 3 is the B8 arm (kernels_univariate.hip), 4 .. 7 the wide arms (kernels_univariate_base.hip)
+int univariate_evals(bn_ctx *ctx, uint32_t base, uint32_t n_vars, uint32_t skip_rounds, const bn_hal_multilinear *mls, uint32_t n_mls, const bn_step *steps,
+                     const uint32_t *step_offsets, const uint32_t *degrees, uint32_t n_comps, const void *d_eq, uint64_t eq_len, uint32_t max_domain_size,
+                     const bn_f128 *h_batch_coeff, bn_f128 *h_out)
 {
 	BN_REQUIRE(ctx && h_out && (mls || n_mls == 0) && (n_comps == 0 || (steps && step_offsets && degrees)), "null argument");
 	BN_ENTER(ctx);
@@ -131,7 +135,10 @@ int bn_zerocheck_univariate_evals(bn_ctx *ctx, uint32_t n_vars, uint32_t skip_ro
 	for (uint32_t i = 0; i < n_mls; i++) {
 		const bn_hal_multilinear &ml = mls[i];
 		BN_REQUIRE(ml.kind == BN_HAL_ML_TRANSPARENT, "univariate round: columns are TRANSPARENT multilinears");
-		BN_REQUIRE(ml.tower_level == 0 || ml.tower_level == 3, "univariate round: column tower level must be 0 (B1) or 3 (B8)");
+		if (base == 3)
+			BN_REQUIRE(ml.tower_level == 0 || ml.tower_level == 3, "univariate round: column tower level must be 0 (B1) or 3 (B8)");
+		else
+			BN_REQUIRE(ml.tower_level == 0 || (ml.tower_level >= 3 && ml.tower_level <= base), "univariate round: column tower level must be 0 (B1) or 3 .. base_level");
 		BN_REQUIRE(ml.n_vars_ml == n_vars, "univariate round: column n_vars_ml must equal n_vars");
 		const uint64_t want = std::max<uint64_t>(1, n_vals >> (7 - ml.tower_level));
 		BN_REQUIRE(ml.len == want && ml.d_evals, "univariate round: packed column length does not match n_vars");
@@ -145,7 +152,12 @@ int bn_zerocheck_univariate_evals(bn_ctx *ctx, uint32_t n_vars, uint32_t skip_ro
 			const uint32_t i = s - s0;
 			switch (st.kind) {
 			case BN_STEP_VAR: BN_REQUIRE(st.a < n_mls, "composition uses more variables than there are columns"); break;
-			case BN_STEP_CONST: BN_REQUIRE(st.cst.hi == 0 && st.cst.lo < 256, "composition constant outside B8"); break;
+			case BN_STEP_CONST:
+				if (base == 3)
+					BN_REQUIRE(st.cst.hi == 0 && st.cst.lo < 256, "composition constant outside B8");
+				else
+					BN_REQUIRE(const_in_base(st.cst, base), "composition constant outside the base field");
+				break;
 			case BN_STEP_ADD:
 			case BN_STEP_MUL: BN_REQUIRE(st.a < i && st.b < i, "composition step refers forward"); break;
 			case BN_STEP_POW: BN_REQUIRE(st.a < i, "composition step refers forward"); break;
@@ -179,10 +191,19 @@ int bn_zerocheck_univariate_evals(bn_ctx *ctx, uint32_t n_vars, uint32_t skip_ro
 					}
 		}
 	}
-	const uint32_t th = nj_max <= 64 ? 64 : nj_max <= 128 ? 128 : 256;
+	// base 3: one workgroup of th lanes per (tile, composition); wide: one wave per (tile, composition, 64 points), th = the chunks' lanes
+	if (base > 3) {
+		// the wide kernel reads log L_u(omega_j) at u * 256 + j: the lanes of a wave (consecutive j) read consecutive bytes
+		std::vector<uint8_t> lgl(256 * 256, 0);
+		for (uint32_t j = K; j < 256; j++)
+			for (uint32_t u = 0; u < K; u++) lgl[(size_t)u * 256 + j] = T.logexp[lag[(size_t)j * 256 + u]];
+		lag.swap(lgl);
+	}
+	const uint32_t th = base > 3 ? (nj_max + bn::kUskipBaseLanes - 1) / bn::kUskipBaseLanes * bn::kUskipBaseLanes : nj_max <= 64 ? 64 : nj_max <= 128 ? 128 : 256;
 	const uint32_t n_x_log = n_vars - k;
 	const uint64_t n_x = (uint64_t)1 << n_x_log;
-	uint64_t n_tiles = std::max<uint64_t>(1, std::min<uint64_t>(n_x, 2048 / n_comps));
+	const uint64_t wg_per_tile = base > 3 ? (uint64_t)n_comps * (th / bn::kUskipBaseLanes) : n_comps;
+	uint64_t n_tiles = std::max<uint64_t>(1, std::min<uint64_t>(n_x, 2048 / wg_per_tile));
 	const uint64_t x_per_tile = (n_x + n_tiles - 1) / n_tiles;
 	n_tiles = (n_x + x_per_tile - 1) / x_per_tile;
 	std::vector<bn::uskip_col> cols(std::max<uint32_t>(1, n_mls));
@@ -234,10 +255,17 @@ int bn_zerocheck_univariate_evals(bn_ctx *ctx, uint32_t n_vars, uint32_t skip_ro
 	a.k = k;
 	a.n_x_log = n_x_log;
 	a.n_tiles = (uint32_t)n_tiles;
+	a.th = th;
 	a.x_per_tile = x_per_tile;
 	{
 		prof_scope ps(ctx, BN_PROF_ROUND_EVAL);
-		BN_HIP(bn::launch_uskip_evals(ctx->stream, a, th, n_comps, scale.empty() ? nullptr : up.dev(s_scale), up.dev(s_out)));
+		if (base > 3) {
+			uint32_t max_steps = 0;
+			for (uint32_t c = 0; c < n_comps; c++) max_steps = std::max(max_steps, step_offsets[c + 1] - step_offsets[c]);
+			BN_HIP(bn::launch_uskip_evals_base(ctx->stream, base, a, max_steps, n_comps, scale.empty() ? nullptr : up.dev(s_scale), up.dev(s_out)));
+		} else {
+			BN_HIP(bn::launch_uskip_evals(ctx->stream, a, th, n_comps, scale.empty() ? nullptr : up.dev(s_scale), up.dev(s_out)));
+		}
 	}
 	std::vector<bn::f128> r((size_t)n_comps * th);
 	BN_HIP(hipMemcpyAsync(r.data(), up.dev(s_out), r.size() * sizeof(bn::f128), hipMemcpyDeviceToHost, ctx->stream));
@@ -269,6 +297,28 @@ int bn_zerocheck_univariate_evals(bn_ctx *ctx, uint32_t n_vars, uint32_t skip_ro
 	}
 	for (uint32_t i = 0; i < n_out; i++) h_out[i] = bn_f128{total[i].lo, total[i].hi};
 	return BN_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int bn_zerocheck_univariate_evals(bn_ctx *ctx, uint32_t n_vars, uint32_t skip_rounds, const bn_hal_multilinear *mls, uint32_t n_mls,
+                                  const bn_step *steps, const uint32_t *step_offsets, const uint32_t *degrees, uint32_t n_comps, const void *d_eq,
+                                  uint64_t eq_len, uint32_t max_domain_size, const bn_f128 *h_batch_coeff, bn_f128 *h_out)
+{
+	return univariate_evals(ctx, 3, n_vars, skip_rounds, mls, n_mls, steps, step_offsets, degrees, n_comps, d_eq, eq_len, max_domain_size, h_batch_coeff, h_out);
+}
+
+int bn_zerocheck_univariate_evals_base(bn_ctx *ctx, uint32_t base_level, uint32_t n_vars, uint32_t skip_rounds, const bn_hal_multilinear *mls, uint32_t n_mls,
+                                       const bn_step *steps, const uint32_t *step_offsets, const uint32_t *degrees, uint32_t n_comps, const void *d_eq,
+                                       uint64_t eq_len, uint32_t max_domain_size, const bn_f128 *h_batch_coeff, bn_f128 *h_out)
+{
+	BN_REQUIRE(ctx, "null argument");
+	BN_REQUIRE(base_level >= 3 && base_level <= 7, "univariate round: base_level must be 3 (B8) .. 7 (B128)");
+	if (base_level == 3) // constructor.create::<B8>(): the existing entry point, unchanged
+		return bn_zerocheck_univariate_evals(ctx, n_vars, skip_rounds, mls, n_mls, steps, step_offsets, degrees, n_comps, d_eq, eq_len, max_domain_size, h_batch_coeff, h_out);
+	return univariate_evals(ctx, base_level, n_vars, skip_rounds, mls, n_mls, steps, step_offsets, degrees, n_comps, d_eq, eq_len, max_domain_size, h_batch_coeff, h_out);
 }
 
 } // extern "C"

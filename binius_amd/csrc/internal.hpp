@@ -668,7 +668,7 @@ hipError_t launch_fri_fold(hipStream_t s, const uint64_t *d_s_evals, uint32_t tw
 constexpr uint32_t kUskipMaxSteps = 64; // steps of one composition (one LDS byte per step and lane)
 struct uskip_col {
 	const void *ptr;
-	uint32_t level, pad; // tower level 0 or 3
+	uint32_t level, pad; // tower level 0 or 3 (kernels_univariate_base.hip: 0 or 3 .. base_level)
 };
 struct uskip_args {
 	const uskip_col *cols;
@@ -676,15 +676,20 @@ struct uskip_args {
 	const uint32_t *step_off; // n_comps + 1 offsets into steps
 	const uint32_t *n_j;      // per composition: its (d_c - 1) 2^k points 2^k <= j < d_c 2^k (0: nothing to evaluate)
 	const uint4 *masks;       // [256][8]: bit u of mask[j][b] = bit b of L_u(omega_j)
-	const uint8_t *lag;       // [256][256]: L_u(omega_j) at j * 256 + u
+	const uint8_t *lag;       // [256][256]: L_u(omega_j) at j * 256 + u (kernels_univariate_base.hip: log L_u(omega_j) at u * 256 + j)
 	const uint8_t *logexp;    // B8 log[256] | exp[512] (exp[i] = g^(i mod 255))
 	const uint4 *eq;          // 2^n_x_log
 	void *partial;            // [n_comps][n_tiles][th] f128
-	uint32_t k, n_x_log, n_tiles, pad;
+	uint32_t k, n_x_log, n_tiles, th; // th: values per (composition, tile) of partial -- read by kernels_univariate_base.hip only
 	uint64_t x_per_tile;
 };
 // out[c][t] (th values per composition) = scale[c] (nullptr: 1) * R_c(omega_{2^k + t}), 0 for t >= n_j[c]
 hipError_t launch_uskip_evals(hipStream_t s, const uskip_args &a, uint32_t th, uint32_t n_comps, const f128 *scale, f128 *d_out);
+// ---- kernels_univariate_base.hip: the same round for the wide arms (base_level 4 .. 7: compositions over B16 .. B128).  One wave per
+// workgroup, grid (tile, composition, a.th / 64); max_steps = the longest composition (sizes the dynamic LDS)
+constexpr uint32_t kUskipBaseLanes = 64;
+uint32_t uskip_base_lds_bytes(uint32_t base_level, uint32_t max_steps);
+hipError_t launch_uskip_evals_base(hipStream_t s, uint32_t base_level, const uskip_args &a, uint32_t max_steps, uint32_t n_comps, const f128 *scale, f128 *d_out);
 
 // is eq[0 .. n) a tensor expansion up to a constant: eq[i] == eq[i - 2^k] * rho[k] (k = top bit of i)?  *d_flag |= 1 if not.
 // d_rho[n_log] and d_first_wg[42] (from check_tensor_layout, which returns the grid size) are read by the kernel from memory.

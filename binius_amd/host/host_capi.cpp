@@ -1164,13 +1164,13 @@ uint64_t bnh_zerocheck_batch_scratch_elems(uint32_t n_tables, uint32_t skip_roun
 	return zerocheck_batch_scratch_elems(nv, nc, skip_rounds);
 }
 
-int bnh_zerocheck_batch_prove(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols, const void *const *d_cols,
+static int zerocheck_batch_prove_c(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols, const void *const *d_cols,
                               const uint32_t *tower_levels, const uint32_t *n_comps, const bn_step *steps, const uint32_t *n_steps, const bn_step *steps_inf,
                               const uint32_t *n_steps_inf, const uint32_t *degrees, const bn_f128 *zerocheck_challenges, const bn_f128 *batch_coeffs,
                               const bn_f128 *univariate_challenge, const bn_f128 *sumcheck_challenges, const bn_f128 *reduction_batch_coeff,
                               const bn_f128 *reduction_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *message_out, bn_f128 *round_coeffs_out,
                               bn_f128 *final_evals_out, bn_f128 *reduction_round_coeffs_out, bn_f128 *reduction_final_evals_out, bn_f128 *skipped_challenges_out,
-                              bn_f128 *unskipped_challenges_out, bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out)
+                              bn_f128 *unskipped_challenges_out, bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out, bool tower)
 {
 	return guarded([&]() -> int {
 		if (!ctx || !n_tables || !n_vars || !n_cols || !n_comps || !batch_coeffs || !univariate_challenge || !reduction_batch_coeff || !reduction_challenges || !final_evals_out ||
@@ -1214,7 +1214,7 @@ int bnh_zerocheck_batch_prove(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_roun
 		const ZerocheckBatchOutput out = zerocheck_batch_prove(hal, tables, skip_rounds, from_raw(zerocheck_challenges, rounds), from_raw(batch_coeffs, n_tables),
 		                                                       from_raw(*univariate_challenge), from_raw(sumcheck_challenges, rounds),
 		                                                       from_raw(*reduction_batch_coeff), from_raw(reduction_challenges, skip_rounds),
-		                                                       FSliceMut{d_scratch, (size_t)scratch_elems});
+		                                                       FSliceMut{d_scratch, (size_t)scratch_elems}, tower);
 		auto put = [](bn_f128 *dst, const std::vector<B128> &v) { return to_raw(v, dst); };
 		if (!out.message.empty()) {
 			if (!message_out) throw Error(Error::InputValidation, "null argument");
@@ -1236,6 +1236,52 @@ int bnh_zerocheck_batch_prove(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_roun
 		}
 		return 0;
 	});
+}
+
+int bnh_zerocheck_batch_prove(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols, const void *const *d_cols,
+                              const uint32_t *tower_levels, const uint32_t *n_comps, const bn_step *steps, const uint32_t *n_steps, const bn_step *steps_inf,
+                              const uint32_t *n_steps_inf, const uint32_t *degrees, const bn_f128 *zerocheck_challenges, const bn_f128 *batch_coeffs,
+                              const bn_f128 *univariate_challenge, const bn_f128 *sumcheck_challenges, const bn_f128 *reduction_batch_coeff,
+                              const bn_f128 *reduction_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *message_out, bn_f128 *round_coeffs_out,
+                              bn_f128 *final_evals_out, bn_f128 *reduction_round_coeffs_out, bn_f128 *reduction_final_evals_out, bn_f128 *skipped_challenges_out,
+                              bn_f128 *unskipped_challenges_out, bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out)
+{
+	return zerocheck_batch_prove_c(ctx, n_tables, skip_rounds, n_vars, n_cols, d_cols, tower_levels, n_comps, steps, n_steps, steps_inf, n_steps_inf, degrees, zerocheck_challenges,
+	                              batch_coeffs, univariate_challenge, sumcheck_challenges, reduction_batch_coeff, reduction_challenges, d_scratch, scratch_elems, message_out,
+	                              round_coeffs_out, final_evals_out, reduction_round_coeffs_out, reduction_final_evals_out, skipped_challenges_out,
+	                              unskipped_challenges_out, concat_multilinear_evals_out, phase_ms_out, phase_calls_out, false);
+}
+
+// the same prover for every arm of constraint_system/prove.rs:483-490: columns at level 0 or 3 .. 7, constants anywhere in B128
+uint64_t bnh_zerocheck_batch_scratch_elems_tower(uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols, const uint32_t *tower_levels)
+{
+	std::vector<size_t> nv;
+	std::vector<std::vector<uint32_t>> levels;
+	size_t at = 0;
+	for (uint32_t p = 0; p < n_tables; p++) {
+		if (n_vars[p] > BN_PE_MAX_VARS + 8) return 0;
+		nv.push_back(n_vars[p]);
+		levels.emplace_back();
+		for (uint32_t c = 0; c < n_cols[p]; c++, at++) {
+			if (tower_levels[at] > 7) return 0;
+			levels.back().push_back(tower_levels[at]);
+		}
+	}
+	return zerocheck_batch_scratch_elems_tower(nv, levels, skip_rounds);
+}
+
+int bnh_zerocheck_batch_prove_tower(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols, const void *const *d_cols,
+                                    const uint32_t *tower_levels, const uint32_t *n_comps, const bn_step *steps, const uint32_t *n_steps, const bn_step *steps_inf,
+                                    const uint32_t *n_steps_inf, const uint32_t *degrees, const bn_f128 *zerocheck_challenges, const bn_f128 *batch_coeffs,
+                                    const bn_f128 *univariate_challenge, const bn_f128 *sumcheck_challenges, const bn_f128 *reduction_batch_coeff,
+                                    const bn_f128 *reduction_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *message_out, bn_f128 *round_coeffs_out,
+                                    bn_f128 *final_evals_out, bn_f128 *reduction_round_coeffs_out, bn_f128 *reduction_final_evals_out, bn_f128 *skipped_challenges_out,
+                                    bn_f128 *unskipped_challenges_out, bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out)
+{
+	return zerocheck_batch_prove_c(ctx, n_tables, skip_rounds, n_vars, n_cols, d_cols, tower_levels, n_comps, steps, n_steps, steps_inf, n_steps_inf, degrees, zerocheck_challenges,
+	                              batch_coeffs, univariate_challenge, sumcheck_challenges, reduction_batch_coeff, reduction_challenges, d_scratch, scratch_elems, message_out,
+	                              round_coeffs_out, final_evals_out, reduction_round_coeffs_out, reduction_final_evals_out, skipped_challenges_out,
+	                              unskipped_challenges_out, concat_multilinear_evals_out, phase_ms_out, phase_calls_out, true);
 }
 
 // ring_switch::prove (crates/core/src/ring_switch/prove.rs:42-144) through the C++ mirror binius_amd/host/ring_switch.hpp; the arguments

@@ -27,8 +27,17 @@
 // 79-119); its projection is the padded column itself.  Columns of less than one 16-byte element are projected on the host as well.
 // Round polynomials are returned with ALL their coefficients (the transcript carries the truncated form), the multilinear rounds'
 // padded to Dmax + 2, Dmax = max(2, largest degree of the batch), as bnh_eqind_sumcheck_prove pads.
+//
+// tower = true (bnh_zerocheck_batch_prove_tower) takes every arm of :483-490: columns at level 0 or 3 .. 7, constants anywhere in
+// B128.  A table's arm is the largest of its column levels and of the levels of its compositions' constants, at least 3 (:458-467):
+// its univariate round is bn_zerocheck_univariate_evals at base 3 and bn_zerocheck_univariate_evals_base above.  The columns of level
+// 0 / 3 of ALL tables stay in the ONE bn_univariate_fold_batch; a wider column takes bn_fold_right with the Lagrange coefficients,
+// which the header defines the fold's result as -- the coefficients are uploaded once per proof (a batched wide fold: DESIGN.md 7).
+// The projection's bn_partial_eval_high_batch takes every level.  Padding and the columns of less than one element are done on the
+// host for every level.
 #pragma once
 #include <chrono>
+#include <cstring>
 
 #include "batch_prover.hpp"
 #include "eq_ind.hpp"
@@ -37,13 +46,13 @@ namespace binius_amd {
 
 struct ZerocheckColumn {
 	const void *d_evals = nullptr; // TRANSPARENT, packed as bn_hal_multilinear says
-	uint32_t tower_level = 0;      // 0 (B1) or 3 (B8)
+	uint32_t tower_level = 0;      // 0 (B1) or 3 (B8); with tower = true: 0 or 3 .. 7
 };
 
 struct ZerocheckTable {
 	size_t n_vars = 0;
 	std::vector<ZerocheckColumn> columns;
-	std::vector<std::vector<bn_step>> base_compositions; // over B8: the univariate round
+	std::vector<std::vector<bn_step>> base_compositions; // over the table's base field (B8 without tower): the univariate round
 	std::vector<EqIndComposition> compositions;          // the same circuits over B128, their leading forms and degrees: the multilinear rounds
 };
 
@@ -71,6 +80,28 @@ inline size_t zerocheck_batch_scratch_elems(const std::vector<size_t> &n_vars, c
 		if (n_vars[p] >= k) total += ((size_t)1 << nr) + (n_cols[p] << k);
 	}
 	return total;
+}
+
+namespace zerocheck_detail {
+inline size_t column_elems(size_t n_vars, uint32_t level);
+}
+
+// The same for zerocheck_batch_prove with tower = true, which depends on the levels: a padded column takes the elements its level
+// needs (a level-7 column at k = 7: 128), and a batch with a column above level 3 holds the 2^k Lagrange coefficients of the wide folds.
+inline size_t zerocheck_batch_scratch_elems_tower(const std::vector<size_t> &n_vars, const std::vector<std::vector<uint32_t>> &levels, size_t k)
+{
+	size_t total = 0;
+	bool wide = false;
+	for (size_t p = 0; p < n_vars.size(); p++) {
+		const size_t n_eff = n_vars[p] > k ? n_vars[p] : k, nr = n_eff - k, n_cols = levels[p].size();
+		for (uint32_t level : levels[p]) {
+			wide = wide || level > 3;
+			if (n_vars[p] < k) total += zerocheck_detail::column_elems(k, level);
+		}
+		total += ((size_t)1 << nr) + (n_cols << nr) + (nr ? (size_t)1 << (nr - 1) : 0);
+		if (n_vars[p] >= k) total += ((size_t)1 << nr) + (n_cols << k);
+	}
+	return total + (wide ? (size_t)1 << k : 0);
 }
 
 namespace zerocheck_detail {
@@ -122,11 +153,40 @@ inline uint8_t packed_value(const std::vector<B128> &col, uint32_t level, size_t
 
 inline size_t column_elems(size_t n_vars, uint32_t level) { return n_vars + level <= 7 ? 1 : (size_t)1 << (n_vars + level - 7); }
 
+// value i of a packed column of any level held on the host, as a field element (a subfield element embeds as itself)
+inline B128 packed_element(const std::vector<B128> &col, uint32_t level, size_t i)
+{
+	if (level <= 3) return B128(packed_value(col, level, i));
+	uint64_t w[2] = {0, 0};
+	std::memcpy(w, reinterpret_cast<const uint8_t *>(col.data()) + (i << (level - 3)), (size_t)1 << (level - 3));
+	return B128(w[0], w[1]);
+}
+
+// binary_tower_level() of a constant: the smallest level whose field holds it
+inline uint32_t const_level(const bn_f128 &c)
+{
+	if (c.hi) return 7;
+	uint32_t level = 0;
+	while (level < 6 && (c.lo >> (1u << level))) level++;
+	return level;
+}
+
+// the arm of a table (core/src/constraint_system/prove.rs:458-467): the largest column level and composition level, 0 .. 3 => 3
+inline uint32_t table_base(const ZerocheckTable &t)
+{
+	uint32_t base = 3;
+	for (const ZerocheckColumn &c : t.columns) base = c.tower_level > base ? c.tower_level : base;
+	for (const auto &steps : t.base_compositions)
+		for (const bn_step &st : steps)
+			if (st.kind == BN_STEP_CONST) base = const_level(st.cst) > base ? const_level(st.cst) : base;
+	return base;
+}
+
 } // namespace zerocheck_detail
 
 inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::vector<ZerocheckTable> &tables, size_t skip_rounds, const std::vector<B128> &zerocheck_challenges,
                                                   const std::vector<B128> &batch_coeffs, B128 univariate_challenge, const std::vector<B128> &sumcheck_challenges,
-                                                  B128 reduction_batch_coeff, const std::vector<B128> &reduction_challenges, FSliceMut scratch)
+                                                  B128 reduction_batch_coeff, const std::vector<B128> &reduction_challenges, FSliceMut scratch, bool tower = false)
 {
 	using namespace zerocheck_detail;
 	using Out = ZerocheckBatchOutput;
@@ -136,6 +196,8 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 	if (k < 1 || k > 8) throw Error(Error::InputValidation, "zerocheck: skip_rounds out of range (1 .. 8)");
 	size_t d_top = 0;
 	std::vector<size_t> nv, nc;
+	std::vector<std::vector<uint32_t>> col_levels;
+	bool any_wide = false;
 	for (size_t p = 0; p < tables.size(); p++) {
 		const ZerocheckTable &t = tables[p];
 		if (p && t.n_vars < tables[p - 1].n_vars) throw Error(Error::InputValidation, "ClaimsOutOfOrder: tables ascend by number of variables");
@@ -143,8 +205,12 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 		if (t.base_compositions.size() != t.compositions.size()) throw Error(Error::InputValidation, "zerocheck: one B8 composition per composition");
 		for (const ZerocheckColumn &c : t.columns) {
 			if (!c.d_evals) throw Error(Error::InputValidation, "zerocheck: null column");
-			if (c.tower_level != 0 && c.tower_level != 3) throw Error(Error::InputValidation, "zerocheck: tower level must be 0 or 3");
+			if (!tower && c.tower_level != 0 && c.tower_level != 3) throw Error(Error::InputValidation, "zerocheck: tower level must be 0 or 3");
+			if (tower && c.tower_level != 0 && (c.tower_level < 3 || c.tower_level > 7)) throw Error(Error::InputValidation, "zerocheck: tower level must be 0 or 3 .. 7");
+			any_wide = any_wide || c.tower_level > 3;
 		}
+		col_levels.emplace_back();
+		for (const ZerocheckColumn &c : t.columns) col_levels.back().push_back(c.tower_level);
 		for (const EqIndComposition &c : t.compositions) {
 			if (c.degree < 1 || (c.degree << k) > 256) throw Error(Error::InputValidation, "zerocheck: a composition's degree d needs 1 <= d and d 2^k <= 256");
 			d_top = c.degree > d_top ? c.degree : d_top;
@@ -158,7 +224,9 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 	if (batch_coeffs.size() != tables.size()) throw Error(Error::InputValidation, "IncorrectNumberOfBatchCoeffs");
 	if (zerocheck_challenges.size() != rounds || sumcheck_challenges.size() != rounds || reduction_challenges.size() != k)
 		throw Error(Error::InputValidation, "zerocheck: max_n - k zerocheck and sumcheck challenges, k reduction challenges");
-	if (scratch.len_ < zerocheck_batch_scratch_elems(nv, nc, k)) throw Error(Error::InputValidation, "scratch holds fewer than zerocheck_batch_scratch_elems elements");
+	if (!tower && scratch.len_ < zerocheck_batch_scratch_elems(nv, nc, k)) throw Error(Error::InputValidation, "scratch holds fewer than zerocheck_batch_scratch_elems elements");
+	if (tower && scratch.len_ < zerocheck_batch_scratch_elems_tower(nv, col_levels, k))
+		throw Error(Error::InputValidation, "scratch holds fewer than zerocheck_batch_scratch_elems_tower elements");
 
 	Out out;
 	Mi355xBackend backend(hal);
@@ -192,11 +260,11 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 			hal.copy_d2h(FSlice{c.d_evals, small.size()}, small);
 			uint8_t *raw = reinterpret_cast<uint8_t *>(padded.data());
 			for (size_t i = 0; i < K; i++) {
-				const uint8_t v = packed_value(small, c.tower_level, i & (((size_t)1 << t.n_vars) - 1));
+				const size_t src = i & (((size_t)1 << t.n_vars) - 1);
 				if (c.tower_level == 0)
-					raw[i >> 3] |= (uint8_t)(v << (i & 7));
-				else
-					raw[i] = v;
+					raw[i >> 3] |= (uint8_t)(packed_value(small, 0, src) << (i & 7));
+				else // (values of 2^(level - 3) bytes)
+					std::memcpy(raw + (i << (c.tower_level - 3)), reinterpret_cast<const uint8_t *>(small.data()) + (src << (c.tower_level - 3)), (size_t)1 << (c.tower_level - 3));
 			}
 			FSliceMut d = alloc.alloc(padded.size());
 			hal.copy_h2d(padded, d);
@@ -223,8 +291,14 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 		}
 		std::vector<B128> per(t.compositions.size() * (D - K) + 1);
 		if (!t.compositions.empty()) {
-			check(bn_zerocheck_univariate_evals(hal.raw_ctx(), (uint32_t)pr.n_eff, (uint32_t)k, mls.data(), (uint32_t)mls.size(), steps.data(), offsets.data(), degrees.data(),
-			                                    (uint32_t)t.compositions.size(), eq.ptr, eq.len_, (uint32_t)D, nullptr, reinterpret_cast<bn_f128 *>(per.data())));
+			const uint32_t base = tower ? table_base(t) : 3;
+			if (base == 3)
+				check(bn_zerocheck_univariate_evals(hal.raw_ctx(), (uint32_t)pr.n_eff, (uint32_t)k, mls.data(), (uint32_t)mls.size(), steps.data(), offsets.data(), degrees.data(),
+				                                    (uint32_t)t.compositions.size(), eq.ptr, eq.len_, (uint32_t)D, nullptr, reinterpret_cast<bn_f128 *>(per.data())));
+			else
+				check(bn_zerocheck_univariate_evals_base(hal.raw_ctx(), base, (uint32_t)pr.n_eff, (uint32_t)k, mls.data(), (uint32_t)mls.size(), steps.data(), offsets.data(),
+				                                         degrees.data(), (uint32_t)t.compositions.size(), eq.ptr, eq.len_, (uint32_t)D, nullptr,
+				                                         reinterpret_cast<bn_f128 *>(per.data())));
 			out.phase_calls[Out::Univariate] += 2 + (pr.nr ? 1 : 0);
 		}
 		// the powers of the coefficient (prove/zerocheck.rs:354-370), times the coefficient (batch_zerocheck.rs:198-206)
@@ -242,15 +316,35 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 	const std::vector<B128> l_sub = lagrange_evals(K, univariate_challenge), l_full = lagrange_evals(D, univariate_challenge);
 	std::vector<bn_pe_column> fold_cols;
 	std::vector<void *> fold_outs;
+	FSliceMut d_l_sub{nullptr, 0}; // the coefficients of the wide folds, uploaded once per proof
+	if (any_wide) {
+		d_l_sub = alloc.alloc(K);
+		hal.copy_h2d(l_sub, d_l_sub);
+	}
 	for (size_t p = 0; p < tables.size(); p++)
 		for (size_t c = 0; c < tables[p].columns.size(); c++) {
-			FSliceMut o = alloc.alloc((size_t)1 << ps[p].nr);
+			const uint32_t level = tables[p].columns[c].tower_level;
+			const size_t n_out = (size_t)1 << ps[p].nr;
+			FSliceMut o = alloc.alloc(n_out);
 			ps[p].folded.push_back(ComputeMemory::as_const(o));
-			fold_cols.push_back(bn_pe_column{ps[p].cols[c], tables[p].columns[c].tower_level, (uint32_t)ps[p].n_eff});
-			fold_outs.push_back(o.ptr);
+			if (level <= 3) {
+				fold_cols.push_back(bn_pe_column{ps[p].cols[c], level, (uint32_t)ps[p].n_eff});
+				fold_outs.push_back(o.ptr);
+			} else if (ps[p].n_eff + level < 7) {
+				// less than one 16-byte element (then n_eff = k and there is one output): on the host
+				std::vector<B128> small(1), folded(n_out, B128::ZERO());
+				hal.copy_d2h(FSlice{ps[p].cols[c], 1}, small);
+				for (size_t i = 0; i < (n_out << k); i++) folded[i >> k] += l_sub[i & (K - 1)] * packed_element(small, level, i);
+				hal.copy_h2d(folded, o);
+			} else {
+				check(bn_fold_right(hal.raw_ctx(), ps[p].cols[c], column_elems(ps[p].n_eff, level), level, d_l_sub.ptr, K, o.ptr, n_out));
+				out.phase_calls[Out::Fold] += 1;
+			}
 		}
-	check(bn_univariate_fold_batch(hal.raw_ctx(), fold_cols.data(), (uint32_t)fold_cols.size(), (uint32_t)k, reinterpret_cast<const bn_f128 *>(l_sub.data()), fold_outs.data()));
-	out.phase_calls[Out::Fold] += fold_cols.empty() ? 0 : 1;
+	if (!tower || !fold_cols.empty()) { // (a batch of wide columns only makes no call)
+		check(bn_univariate_fold_batch(hal.raw_ctx(), fold_cols.data(), (uint32_t)fold_cols.size(), (uint32_t)k, reinterpret_cast<const bn_f128 *>(l_sub.data()), fold_outs.data()));
+		out.phase_calls[Out::Fold] += fold_cols.empty() ? 0 : 1;
+	}
 	out.phase_ms[Out::Fold] = elapsed_ms(t0);
 
 	// ---- the multilinear rounds: front-loaded, pre-batched
@@ -285,7 +379,7 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 		projected.resize(first + t.columns.size(), std::vector<B128>(K));
 		if (t.n_vars < k) {
 			for (size_t c = 0; c < t.columns.size(); c++)
-				for (size_t u = 0; u < K; u++) projected[first + c][u] = B128(packed_value(pr.host_cols[c], t.columns[c].tower_level, u));
+				for (size_t u = 0; u < K; u++) projected[first + c][u] = packed_element(pr.host_cols[c], t.columns[c].tower_level, u);
 			continue;
 		}
 		const B128 *point = out.unskipped_challenges.data() + (rounds - pr.nr); // the last n - k
@@ -302,7 +396,7 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 				const std::vector<B128> eq = eq_expand(point, pr.nr);
 				for (size_t u = 0; u < K; u++) {
 					B128 s = B128::ZERO();
-					for (size_t j = 0; j < eq.size(); j++) s += eq[j] * B128(packed_value(small, t.columns[c].tower_level, j * K + u));
+					for (size_t j = 0; j < eq.size(); j++) s += eq[j] * packed_element(small, t.columns[c].tower_level, j * K + u);
 					projected[first + c][u] = s;
 				}
 				continue;

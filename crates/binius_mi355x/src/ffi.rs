@@ -426,6 +426,23 @@ unsafe extern "C" {
 		h_batch_coeff: *const bn_f128,
 		h_out: *mut bn_f128,
 	) -> c_int;
+	pub fn bn_zerocheck_univariate_evals_base(
+		ctx: *mut bn_ctx,
+		base_level: u32,
+		n_vars: u32,
+		skip_rounds: u32,
+		mls: *const bn_hal_multilinear,
+		n_mls: u32,
+		steps: *const bn_step,
+		step_offsets: *const u32,
+		degrees: *const u32,
+		n_comps: u32,
+		d_eq: *const c_void,
+		eq_len: u64,
+		max_domain_size: u32,
+		h_batch_coeff: *const bn_f128,
+		h_out: *mut bn_f128,
+	) -> c_int;
 
 	pub fn bn_ntt_forward(
 		ctx: *mut bn_ctx,

@@ -439,6 +439,19 @@ int bn_hal_fold_multilinear(bn_ctx *ctx, uint32_t order, uint32_t n_vars, const 
 int bn_zerocheck_univariate_evals(bn_ctx *ctx, uint32_t n_vars, uint32_t skip_rounds, const bn_hal_multilinear *mls, uint32_t n_mls,
                                   const bn_step *steps, const uint32_t *step_offsets, const uint32_t *degrees, uint32_t n_comps,
                                   const void *d_eq, uint64_t eq_len, uint32_t max_domain_size, const bn_f128 *h_batch_coeff, bn_f128 *h_out);
+/* The same round for every arm of core/src/constraint_system/prove.rs:483-490: base_level = 3 .. 7 mirrors constructor.create::<FBase>()
+ * with FBase = B8, B16, B32, B64, B128 (the table's arm: the largest column level and the compositions' binary_tower_level(), :458-467).
+ * The domain and the Lagrange coefficients stay in B8; Mhat_i(omega_j, x) is a B8 x FBase product (the B8 scalar acts on each byte
+ * coordinate), the composition is evaluated in FBase, eq(x) * v is a B128 x FBase product.  base_level 3 forwards to
+ * bn_zerocheck_univariate_evals unchanged.  Above it:
+ *   mls: TRANSPARENT, tower level 0 or 3 .. base_level, mixed freely, packed as bn_hal_multilinear says (little-endian values of
+ *   2^(level - 3) bytes); constants of the compositions in the base field (below 2^(2^base_level)); every other limit, the
+ *   outputs and the h_batch_coeff form as above (kernels_univariate_base.hip).
+ * base_level outside 3 .. 7, a column at level 1, 2 or above base_level and a constant outside the base field are
+ * BN_ERR_INPUT_VALIDATION with nothing launched. */
+int bn_zerocheck_univariate_evals_base(bn_ctx *ctx, uint32_t base_level, uint32_t n_vars, uint32_t skip_rounds, const bn_hal_multilinear *mls,
+                                       uint32_t n_mls, const bn_step *steps, const uint32_t *step_offsets, const uint32_t *degrees, uint32_t n_comps,
+                                       const void *d_eq, uint64_t eq_len, uint32_t max_domain_size, const bn_f128 *h_batch_coeff, bn_f128 *h_out);
 
 int bn_ntt_forward(bn_ctx *ctx, void *d_data, uint32_t elem_level, uint32_t tw_level, const uint64_t *h_s_evals,
                    uint32_t log_domain, uint32_t log_x, uint32_t log_y, uint32_t log_z, uint64_t coset,

@@ -174,6 +174,26 @@ int bnh_zerocheck_batch_prove(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_roun
                               const bn_f128 *reduction_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *message_out, bn_f128 *round_coeffs_out,
                               bn_f128 *final_evals_out, bn_f128 *reduction_round_coeffs_out, bn_f128 *reduction_final_evals_out, bn_f128 *skipped_challenges_out,
                               bn_f128 *unskipped_challenges_out, bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out);
+/* The same prover for every arm of core/src/constraint_system/prove.rs:483-490 (0..=3 => B8, 4 => B16, 5 => B32, 6 => B64, 7 => B128), with
+ * the argument list of bnh_zerocheck_batch_prove.  tower_levels: 0 or 3 .. 7 (little-endian values of 2^(level - 3) bytes); the constants of
+ * the compositions anywhere in B128.  A table's arm is the largest of its column levels and of the levels of its compositions' constants,
+ * at least 3 (:458-467): its univariate round is bn_zerocheck_univariate_evals at 3 and bn_zerocheck_univariate_evals_base above.  The
+ * columns of level 0 / 3 of ALL tables stay in the ONE bn_univariate_fold_batch; a wider column takes one bn_fold_right with the 2^k
+ * Lagrange coefficients (uploaded once per proof), which phase_calls_out[1] counts beside the batched call.  The projection is the one
+ * bn_partial_eval_high_batch per table.  Padding (n_vars < k) and the columns of less than one 16-byte element are done on the host at
+ * every level.
+ *   d_scratch: at least bnh_zerocheck_batch_scratch_elems_tower(n_tables, k, n_vars, n_cols, tower_levels) elements: the formula above with
+ *   column_elems(k, level) = max(1, 2^(k + level - 7)) elements per padded column (a level-7 column at k = 7: 128) and 2^k elements of
+ *   coefficients when some column lies above level 3.  0: an argument out of range.
+ * bnh_zerocheck_batch_prove and its scratch formula are unchanged: it still rejects level 4. */
+uint64_t bnh_zerocheck_batch_scratch_elems_tower(uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols, const uint32_t *tower_levels);
+int bnh_zerocheck_batch_prove_tower(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols, const void *const *d_cols,
+                                    const uint32_t *tower_levels, const uint32_t *n_comps, const bn_step *steps, const uint32_t *n_steps, const bn_step *steps_inf,
+                                    const uint32_t *n_steps_inf, const uint32_t *degrees, const bn_f128 *zerocheck_challenges, const bn_f128 *batch_coeffs,
+                                    const bn_f128 *univariate_challenge, const bn_f128 *sumcheck_challenges, const bn_f128 *reduction_batch_coeff,
+                                    const bn_f128 *reduction_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *message_out, bn_f128 *round_coeffs_out,
+                                    bn_f128 *final_evals_out, bn_f128 *reduction_round_coeffs_out, bn_f128 *reduction_final_evals_out, bn_f128 *skipped_challenges_out,
+                                    bn_f128 *unskipped_challenges_out, bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out);
 
 /* gkr_gpa::batch_prove (crates/core/src/protocols/gkr_gpa/prove.rs:33-296) through the C++ mirror binius_amd/host/gkr_gpa.hpp: the GKR
  * grand-product argument over n_claims witnesses, which the constraint system runs for every flush and non-zero oracle
