@@ -501,11 +501,10 @@ int circuit_multipass_collect(bn_ctx *ctx, const bn_expr *e, const void *const *
 	return BN_OK;
 }
 
-// values[q.out] ^= q.coeff * sum_j q.a[j] q.b[j] (q.b == null: the all-ones row `ones`) for every collected request, n elements each;
+// values[q.out] ^= q.coeff * sum_j q.a[j] q.b[j] (q.b == null: the all-ones row, which the kernels stage themselves) for every collected request, n elements each;
 // as many launches of the group kernel as 32 jobs of two products each take (one, for every request seen so far)
-int circuit_ip_run(bn_ctx *ctx, const ip_collector &col, uint64_t n, const void *ones, f128 *values)
+int circuit_ip_run(bn_ctx *ctx, const ip_collector &col, uint64_t n, f128 *values)
 {
-	(void)ones;
 	for (const auto &c : col.consts) values[c.first] ^= c.second;
 	// At traffic-bound sizes the sum of a LONE row is a streaming XOR (kernels_stream.hip k_xor_sum: 16 B per element at the copy
 	// rate); as a job of the group kernel it would run at the Gram products' rate for nothing (measured: a·b·c + a at n = 24

@@ -150,7 +150,20 @@ struct ip_collector {
 };
 int circuit_multipass_collect(bn_ctx *ctx, const bn_expr *e, const void *const *rows, uint64_t seg, uint32_t n_b, const void *eq, size_t scratch_off,
                               const uint32_t *out_index, ip_collector &col);
-int circuit_ip_run(bn_ctx *ctx, const ip_collector &col, uint64_t n, const void *ones, bn::f128 *values);
+int circuit_ip_run(bn_ctx *ctx, const ip_collector &col, uint64_t n, bn::f128 *values);
+// What a route of an entry point did with the call (abi_kernels.cpp: the fused pair; abi_hal.cpp: the round evaluation).  A route
+// answers by returning the code the entry point returns now -- BN_OK, or the error of a BN_HIP / BN_FLUSH / BN_REQUIRE inside it.
+struct routed {
+	enum kind_t { declined, launched, answered } kind;
+	int rc = BN_OK;
+	hipError_t fe = hipErrorNotSupported; // launched: what the launcher returned (a failure is reported where the routes end)
+	routed(int rc_) : kind(answered), rc(rc_) {} // (implicit only for the error returns of BN_HIP / BN_FLUSH / BN_REQUIRE and `if (rc) return rc`)
+	static routed answer(int rc_) { return routed(rc_); }
+	routed(kind_t k, hipError_t e) : kind(k), fe(e) {}
+	static routed decline() { return routed(declined, hipErrorNotSupported); }
+	// (hipErrorNotSupported from a launcher: that kernel does not take the shape -- the next route is tried)
+	static routed launch(hipError_t e) { return routed(e == hipErrorNotSupported ? declined : launched, e); }
+};
 // ---- evaluate_partial_high (abi_ops.cpp, abi_partial_eval.cpp)
 int fold_left_dispatch(bn_ctx *ctx, const void *d_mat, uint32_t tower_level, const void *d_vec, uint64_t vec_len, void *d_out, uint64_t out_len);
 // validated columns (query_vars <= n_vars each) at the 2^q-entry query d_vec; routed: a bn_fold_left call served as a one-column job

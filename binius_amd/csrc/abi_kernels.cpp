@@ -833,20 +833,6 @@ int prepare_accumulators(launch_call &c)
 }
 
 // ---- the fused pair: two product sums, at 1 and at infinity, in one pass over the data -------------------------------------------
-// What a route of the fused pair did.  A route answers by returning the code bn_kernel_launch returns now -- BN_OK, or the
-// error of a BN_HIP / BN_FLUSH / BN_REQUIRE inside it.
-struct routed {
-	enum kind_t { declined, launched, answered } kind;
-	int rc = BN_OK;
-	hipError_t fe = hipErrorNotSupported; // launched: what the launcher returned (a failure is reported where the routes end)
-	routed(int rc_) : kind(answered), rc(rc_) {} // (implicit only for the error returns of BN_HIP / BN_FLUSH / BN_REQUIRE and `if (rc) return rc`)
-	static routed answer(int rc_) { return routed(rc_); }
-	routed(kind_t k, hipError_t e) : kind(k), fe(e) {}
-	static routed decline() { return routed(declined, hipErrorNotSupported); }
-	// (hipErrorNotSupported from a launcher: that kernel does not take the shape -- the next route is tried)
-	static routed launch(hipError_t e) { return routed(e == hipErrorNotSupported ? declined : launched, e); }
-};
-
 // for factor j, hi[j] are the evaluations at 1; lo[j] != null: the evaluation at infinity is lo[j] + hi[j], null: the factor is
 // the same at both points
 struct pair_req {

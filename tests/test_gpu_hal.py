@@ -58,7 +58,7 @@ def both(hal, oracle, order, n_vars, query, mls, evaluators, points):
 
 
 @pytest.mark.parametrize("order", [0, 1])
-@pytest.mark.parametrize("n_vars", [1, 2, 3, 7, 10, 13])
+@pytest.mark.parametrize("n_vars", [1, 2, 3, 7, 10, 11, 13])  # (half = 1024 at 11: the first size of rows + compiled circuits)
 def test_round_evals_general(hal, oracle, order, n_vars):
     n = 1 << n_vars
     x = [oracle.random_b128(0x11A0 + 16 * n_vars + j, n) for j in range(3)]

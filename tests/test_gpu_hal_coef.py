@@ -25,12 +25,14 @@ MIXED = [("var", 0), ("const", K), ("add", 0, 1), ("var", 1), ("mul", 2, 3), ("v
 MIXED_INF = ABC
 
 
-def run(oracle, n_vars, n_mls, evaluators, points, env=None, expect_path=True, seed=0):
-    """The request on a fresh context (env applied while it is created), the oracle's values beside it."""
+def run(oracle, n_vars, n_mls, evaluators, points, env=None, expect_path=True, seed=0, trunc=None):
+    """The request on a fresh context (env applied while it is created), the oracle's values beside it.
+    trunc: {multilinear: (length, suffix)} -- those multilinears are cut to `length` elements before a constant suffix."""
     import binius_amd
 
     n = 1 << n_vars
     xs = [oracle.random_b128(0xC0EF0000 + 1024 * seed + 64 * n_vars + j, n) for j in range(n_mls)]
+    mls = [("folded", np.ascontiguousarray(v[: trunc[j][0]]), trunc[j][1]) if j in (trunc or {}) else ("folded", v, 0) for j, v in enumerate(xs)]
     old = {}
     for k, v in (env or {}).items():
         old[k] = os.environ.get(k)
@@ -45,7 +47,7 @@ def run(oracle, n_vars, n_mls, evaluators, points, env=None, expect_path=True, s
                 os.environ[k] = v
     try:
         alloc = hal.dev_alloc()
-        d_mls = [("folded", upload(hal, alloc, v), 0) for v in xs]
+        d_mls = [(m[0], upload(hal, alloc, m[1]), m[2]) for m in mls]
         eqs = {}
         exprs, d_evs = [], []
         for e in evaluators:
@@ -65,7 +67,7 @@ def run(oracle, n_vars, n_mls, evaluators, points, env=None, expect_path=True, s
             x.free()
     finally:
         hal.close()
-    rc, want = oracle.hal_round_evals(1, n_vars, None, [("folded", v, 0) for v in xs], evaluators, points)
+    rc, want = oracle.hal_round_evals(1, n_vars, None, mls, evaluators, points)
     assert rc == 0
     assert got == want
     assert again == got
@@ -84,6 +86,25 @@ def test_cubic_at_domain_points(oracle, n_vars, with_eq):
     got = run(oracle, n_vars, 3, evs, pts)
     if n_vars in (5, 12):
         assert run(oracle, n_vars, 3, evs, pts, env={"BN_HAL_COEF": "0"}, expect_path=False) == got
+
+
+@pytest.mark.parametrize("truncated", [False, True])
+@pytest.mark.parametrize("with_eq", [False, True])
+def test_cubic_with_the_form_declined_at_traffic_bound_size(oracle, truncated, with_eq):
+    """The same request at n_vars = 21 where the coefficient form does not answer it: the rows + compiled circuits code with a
+    product pass per point.  No counter names that route; these conditions of bn_hal_round_evals select it: the coefficient form
+    is off (BN_HAL_COEF=0) or declines a truncated multilinear; one domain point keeps the constraint-set path and the monomial
+    route (points 1 and infinity only) away; one evaluator over three multilinears is not wide; half = 2^20 >= 1024 with three
+    values takes rows + circuits, and half > 2^19 takes them point by point.  Full multilinears: the rows of point 1 are the
+    upper halves in place; a truncated one (2^21 - 5 elements, non-zero suffix): every row of it is written by the rows kernel."""
+    n_vars = 21
+    eq = oracle.random_b128(0xC0EA + n_vars, (1 << n_vars) // 2) if with_eq else None
+    pts = oracle.random_scalars(0xC0EB + n_vars, 1)
+    evs = [{"steps": ABC_PLUS_A, "steps_inf": ABC, "start": 1, "end": 4, "eq_ind": eq}]
+    if truncated:
+        run(oracle, n_vars, 3, evs, pts, expect_path=False, trunc={1: ((1 << n_vars) - 5, 0x0F1E2D3C4B5A69788796A5B4C3D2E1F0)})
+    else:
+        run(oracle, n_vars, 3, evs, pts, env={"BN_HAL_COEF": "0"}, expect_path=False)
 
 
 @pytest.mark.parametrize("n_vars", [2, 4, 8, 13, 17])
