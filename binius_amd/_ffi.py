@@ -65,6 +65,21 @@ class PeColumn(C.Structure):
     _fields_ = [("d_evals", C.c_void_p), ("tower_level", C.c_uint32), ("n_vars", C.c_uint32)]
 
 
+class PelTerm(C.Structure):
+    """bn_pel_term: one constituent column of a job of bn_partial_eval_high_lincomb_batch and its coefficient."""
+
+    _fields_ = [("d_evals", C.c_void_p), ("tower_level", C.c_uint32), ("reserved", C.c_uint32), ("coeff", F128)]
+
+
+class PelJob(C.Structure):
+    """bn_pel_job: one linear combination of bn_partial_eval_high_lincomb_batch, its terms a range of the call's term table."""
+
+    _fields_ = [("n_vars", C.c_uint32), ("first_term", C.c_uint32), ("n_terms", C.c_uint32), ("reserved", C.c_uint32), ("offset", F128)]
+
+
+PEL_MAX_TERMS = 64  # BN_PEL_MAX_TERMS
+
+
 class RsJob(C.Structure):
     """bn_rs_job: one equality indicator of bn_ring_switch_eq_ind_batch."""
 
@@ -180,6 +195,8 @@ def lib():
         "bn_flush_counters": [vp, C.POINTER(u64)],
         "bn_partial_eval_high_batch": [vp, vp, u32, vp, u32, C.POINTER(vp)],
         "bn_partial_eval_counters": [vp, C.POINTER(u64)],
+        "bn_partial_eval_high_lincomb_batch": [vp, vp, u32, vp, u32, vp, u32, C.POINTER(vp)],
+        "bn_partial_eval_lincomb_counters": [vp, C.POINTER(u64)],
         "bn_univariate_fold_batch": [vp, vp, u32, u32, PF, C.POINTER(vp)],
         "bn_univariate_fold_counters": [vp, C.POINTER(u64)],
         "bn_ring_switch_eq_ind_batch": [vp, vp, u32, PF, u32, C.POINTER(vp)],
@@ -244,7 +261,7 @@ ABI_SYMBOLS = [
     "bn_product_tree_layers", "bn_pad_with_ones", "bn_exp_circuit_layers", "bn_bits_to_b128", "bn_exp_counters",
     "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
     "bn_univariate_fold_batch", "bn_univariate_fold_counters", "bn_ring_switch_eq_ind_batch", "bn_ring_switch_counters",
-    "bn_mle_evaluate_batch", "bn_mle_evaluate_counters",
+    "bn_mle_evaluate_batch", "bn_mle_evaluate_counters", "bn_partial_eval_high_lincomb_batch", "bn_partial_eval_lincomb_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -928,6 +945,40 @@ class Context:
         _check(lib().bn_partial_eval_counters(self._h, c))
         return {"calls": int(c[0]), "launches": int(c[1]), "cols_kernel": int(c[2]), "cols_fallback": int(c[3]), "max_share": int(c[4]),
                 "fold_left_routed": int(c[5])}
+
+    def partial_eval_high_lincomb_batch(self, jobs, query, query_vars, outs):
+        """The projection of partial_eval_high_batch for linear combinations of columns that are never materialised
+        (bn_partial_eval_high_lincomb_batch; try_build_partial_eval, evalcheck/subclaims.rs:305-346).  jobs: (n_vars, terms, offset) per
+        job, terms a list of (column DevSlice, tower_level, coeff), coefficients and offsets as ints; query: the DevSlice of the
+        2^query_vars-element tensor expansion; outs[j]: a DevSlice of 2^(n_vars - query_vars) elements that receives
+        offset + sum_t coeff_t * fold_left(column_t, level_t, query)."""
+        n = len(jobs)
+        if len(outs) != n:
+            raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: one output per job")
+        table, terms = [], []
+        for n_vars, tms, offset in jobs:
+            table.append(PelJob(n_vars, len(terms), len(tms), 0, to_f128(offset)))
+            terms += [PelTerm(t[0].ptr if t[0] is not None else None, t[1], 0, to_f128(t[2])) for t in tms]
+        for jb, o in zip(jobs, outs):
+            if o is not None and query_vars <= jb[0] <= 40 and o.len != 1 << (jb[0] - query_vars):
+                raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: output has the wrong number of elements")
+        op = (C.c_void_p * max(1, n))(*[(o.ptr if o is not None else None) for o in outs])
+        self.partial_eval_high_lincomb_raw((PelJob * max(1, n))(*table), n, (PelTerm * max(1, len(terms)))(*terms), len(terms), query, query_vars, op)
+
+    def partial_eval_high_lincomb_raw(self, jobs, n_jobs, terms, n_terms, query, query_vars, outs):
+        """bn_partial_eval_high_lincomb_batch on caller-built PelJob / PelTerm arrays (outs: a c_void_p array), nothing checked here."""
+        _check(lib().bn_partial_eval_high_lincomb_batch(self._h, C.cast(jobs, C.c_void_p) if jobs is not None else None, n_jobs,
+                                                        C.cast(terms, C.c_void_p) if terms is not None else None, n_terms,
+                                                        query.ptr if query is not None else None, query_vars, outs))
+
+    def partial_eval_lincomb_counters(self):
+        """bn_partial_eval_lincomb_counters: accepted bn_partial_eval_high_lincomb_batch calls, the kernel launches they made, jobs, terms,
+        classes (row loops planned), jobs served by the one-thread-per-output form, the largest number of workgroups that shared one job
+        in the last call.  Rejected calls count nowhere."""
+        c = (C.c_uint64 * 7)()
+        _check(lib().bn_partial_eval_lincomb_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2]), "terms": int(c[3]), "classes": int(c[4]), "jobs_fallback": int(c[5]),
+                "max_share": int(c[6])}
 
     def univariate_fold_batch(self, columns, k, coeffs, outs):
         """The fold of the univariate round of the univariate-skip zerocheck for a batch of columns in one launch

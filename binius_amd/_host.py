@@ -88,6 +88,9 @@ def host_lib():
         ]
         L.bnh_evalcheck_bivariate_prove.restype = C.c_int
         L.bnh_evalcheck_bivariate_prove.argtypes = [C.c_void_p, C.c_uint32, U32P, U32P, VPP, FP, C.c_uint32, U32P, FP, C.c_void_p, C.c_uint64, FP, FP, FP, FP]
+        L.bnh_evalcheck_bivariate_prove_lc.restype = C.c_int
+        L.bnh_evalcheck_bivariate_prove_lc.argtypes = [C.c_void_p, C.c_uint32, U32P, U32P, VPP, C.c_uint32, U32P, VPP, FP, FP, FP, C.c_uint32, U32P, FP, C.c_void_p,
+                                                       C.c_uint64, FP, FP, FP, FP]
         L.bnh_evalcheck_evaluate_scratch_elems.restype = C.c_uint64
         L.bnh_evalcheck_evaluate_scratch_elems.argtypes = [C.c_uint32, U32P, C.c_uint32]
         L.bnh_evalcheck_evaluate.restype = C.c_int
@@ -700,14 +703,23 @@ class EvalcheckPlan:
       ("proj", column DevSlice, tower_level, n_vars, suffix_off, suffix_len)   the inner column at the suffix pool[suffix_off : + suffix_len]
       ("shift", block_size, shift_offset, variant, r_off, r_len)               variant: 0 circular left, 1 logical left, 2 logical right
       ("basis", k, iota)
+      ("lincomb", terms, offset, n_vars, suffix_off, suffix_len)               offset + sum of coeff * column over terms = [(column DevSlice,
+                                                                               tower_level, coeff), ...], projected from its constituents
+                                                                               (bnh_evalcheck_bivariate_prove_lc; never materialised)
     pool: the shared list of point coordinates; scratch: a device slice of at least scratch_elems(provers) elements.
-    A projection's final evaluation v is the new claim (r' || suffix, v) on its inner column, r' the reversed challenges."""
+    A projection's final evaluation v is the new claim (r' || suffix, v) on its inner column, r' the reversed challenges; a lincomb's is
+    that claim on the linear-combination oracle itself.  Equal term lists share one range of the call's term list, so an identical
+    (terms, offset, suffix) is projected once."""
 
-    KINDS = {"proj": 0, "shift": 1, "basis": 2}
+    KINDS = {"proj": 0, "shift": 1, "basis": 2, "lincomb": 3}
+
+    @staticmethod
+    def _term_key(terms):
+        return tuple((t[0].ptr if t[0] is not None else None, int(t[1]), int(t[2])) for t in terms)
 
     @staticmethod
     def scratch_elems(provers):
-        suffixes, projections, total = set(), set(), 0
+        suffixes, projections, lincombs, total = set(), set(), set(), 0
         for b, mls, _comps, _sums in provers:
             for ml in mls:
                 if ml[0] == "proj":
@@ -717,6 +729,15 @@ class EvalcheckPlan:
                         total += 1 << ml[5]
                     if (ml[1].ptr, ml[2], s) not in projections:
                         projections.add((ml[1].ptr, ml[2], s))
+                        total += 1 << b
+                elif ml[0] == "lincomb":
+                    s = (ml[4], ml[5])
+                    if s not in suffixes:
+                        suffixes.add(s)
+                        total += 1 << ml[5]
+                    key = (EvalcheckPlan._term_key(ml[1]), int(ml[2]), s, int(ml[3]))
+                    if key not in lincombs:
+                        lincombs.add(key)
                         total += 1 << b
                 else:
                     total += 1 << b
@@ -728,9 +749,19 @@ class EvalcheckPlan:
         self.hal, self.scratch, self._keep = hal, scratch, provers
         self.n = len(provers)
         desc, mld, cols, flat, sums = [], [], [], [], []
+        ranges, terms, offsets = {}, [], []
         for b, mls, comps, sm in provers:
             desc += [b, len(mls), len(comps)]
             for ml in mls:
+                offsets.append(int(ml[2]) if ml[0] == "lincomb" else 0)
+                if ml[0] == "lincomb":
+                    key = self._term_key(ml[1])
+                    if key not in ranges:
+                        ranges[key] = len(terms)
+                        terms += list(key)
+                    mld += [self.KINDS["lincomb"], int(ml[3]), int(ml[4]), int(ml[5]), ranges[key], len(key)]
+                    cols.append(None)
+                    continue
                 words = [self.KINDS[ml[0]]] + [int(x) for x in (ml[2:] if ml[0] == "proj" else ml[1:])]
                 mld += words + [0] * (6 - len(words))
                 cols.append(ml[1].ptr if ml[0] == "proj" and ml[1] is not None else None)
@@ -739,6 +770,12 @@ class EvalcheckPlan:
         self.desc = (C.c_uint32 * max(1, len(desc)))(*desc)
         self.mld = (C.c_uint32 * max(1, len(mld)))(*mld)
         self.cols = (C.c_void_p * max(1, len(cols)))(*cols)
+        self.has_lincomb = bool(ranges)
+        self.n_terms = len(terms)
+        self.term_levels = (C.c_uint32 * max(1, len(terms)))(*[t[1] for t in terms])
+        self.term_cols = (C.c_void_p * max(1, len(terms)))(*[t[0] for t in terms])
+        self.term_coeffs = _f128_array([t[2] for t in terms] or [0])
+        self.offsets = _f128_array(offsets or [0])
         self.pool, self.pool_len = _f128_array(list(pool) or [0]), len(pool)
         self.comps = (C.c_uint32 * max(1, len(flat)))(*flat)
         self.sums = _f128_array(sums if sums else [0])
@@ -751,9 +788,13 @@ class EvalcheckPlan:
         self.final = (F128 * max(1, sum(self.m_by_prover)))()
 
     def run(self):
-        rc = host_lib().bnh_evalcheck_bivariate_prove(self.hal._h, self.n, self.desc, self.mld, self.cols, self.pool, self.pool_len, self.comps, self.sums,
-                                                      self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0,
-                                                      self.bcs, self.ch, self.proofs, self.final)
+        tail = (self.pool, self.pool_len, self.comps, self.sums, self.scratch.ptr if self.scratch is not None else None,
+                self.scratch.len if self.scratch is not None else 0, self.bcs, self.ch, self.proofs, self.final)
+        if self.has_lincomb:
+            rc = host_lib().bnh_evalcheck_bivariate_prove_lc(self.hal._h, self.n, self.desc, self.mld, self.cols, self.n_terms, self.term_levels, self.term_cols,
+                                                             self.term_coeffs, self.offsets, *tail)
+        else:
+            rc = host_lib().bnh_evalcheck_bivariate_prove(self.hal._h, self.n, self.desc, self.mld, self.cols, *tail)
         if rc != 0:
             raise BnError(rc, host_lib().bnh_last_error().decode())
 

@@ -81,6 +81,7 @@ struct bn_ctx {
 	uint64_t exp_calls = 0, exp_launches = 0, exp_bits_launches = 0;     // bn_exp_circuit_layers / bn_bits_to_b128 (bn_exp_counters)
 	uint64_t flush_calls = 0, flush_launches = 0, flush_served = 0, flush_multipass = 0; // bn_flush_witness_batch (bn_flush_counters)
 	uint64_t pe_calls = 0, pe_launches = 0, pe_cols_kernel = 0, pe_cols_fallback = 0, pe_max_share = 0, pe_routed = 0; // bn_partial_eval_counters
+	uint64_t pel_calls = 0, pel_launches = 0, pel_jobs = 0, pel_terms = 0, pel_classes = 0, pel_jobs_fallback = 0, pel_max_share = 0; // bn_partial_eval_lincomb_counters
 	uint64_t uf_calls = 0, uf_launches = 0, uf_cols = 0; // bn_univariate_fold_batch (bn_univariate_fold_counters)
 	uint64_t rs_calls = 0, rs_launches = 0, rs_jobs = 0, rs_queries = 0; // bn_ring_switch_eq_ind_batch (bn_ring_switch_counters)
 	uint64_t me_calls = 0, me_launches = 0, me_jobs = 0, me_max_share = 0; // bn_mle_evaluate_batch (bn_mle_evaluate_counters)
@@ -833,6 +834,36 @@ constexpr uint32_t kPeLogVecChunk = 10; // entries of `vec` a workgroup stages i
 // n_groups == 1 && d_groups == nullptr: the group and its single column travel as kernel arguments (no table upload)
 hipError_t launch_partial_eval(hipStream_t s, const pe_group *d_groups, uint32_t n_groups, const pe_col *d_cols, uint32_t n_cols, pe_group one_group,
                                pe_col one_col, const void *vec, uint32_t total_units, bool bits_only);
+
+// ---- kernels_partial_eval_lincomb.hip: the same projection of linear combinations that are never materialised:
+// out_j[i] = offset_j + sum_t coeff_t * sum_q vec[q] * M_t[q * 2^b + i].  The terms of a job with equal (tower level, coefficient) are a
+// CLASS: its columns are XOR-ed as packed words on load and go through one row loop.  A unit (one workgroup) is a chunk of 2^log_ch
+// indices q of ONE job and walks all its classes from one staged chunk of `vec`.
+struct pel_class {
+	f128 coeff;
+	uint32_t first_col, n_cols; // columns [first_col, first_col + n_cols) of the column-pointer table
+	uint32_t level;
+	uint32_t one;               // coeff == ONE: no product
+};
+struct pel_job {
+	f128 offset;
+	uint64_t *out;                    // 2^b elements
+	uint32_t first_class, n_classes;  // classes [first_class, first_class + n_classes) of the class table
+	uint32_t b;
+	uint32_t log_ch;                  // 2^log_ch indices q per unit (<= kPeLogVecChunk, <= log2 |vec|); unused by the wide form
+	uint32_t start;                   // first unit of this job in its launch
+	uint32_t pad_;
+};
+// Two launches, or none when n_init == 0: k_pel_init writes the offsets of the n_init jobs of d_init (all jobs with at most
+// 2^kPeMaxLogOut outputs), k_pel XOR-combines the units of d_jobs (those of them that have a class) into them.  An empty d_jobs under a
+// non-empty d_init is a launch of one workgroup that returns.
+// lds_out: the largest number of outputs of a job of d_jobs (the workgroup's own sums before the atomics); bits_one: every class is at
+// level 0 with coefficient ONE (the instantiation without any product).
+hipError_t launch_partial_eval_lincomb(hipStream_t s, const pel_job *d_init, uint32_t n_init, const pel_job *d_jobs, uint32_t n_jobs, const pel_class *d_classes,
+                                       const uint64_t *const *d_cols, const void *vec, uint32_t total_units, uint32_t lds_out, bool bits_one);
+// the jobs with more outputs: one thread per output, the whole reduction serial in it (correct, not fast); a unit is 256 outputs
+hipError_t launch_partial_eval_lincomb_wide(hipStream_t s, const pel_job *d_jobs, uint32_t n_jobs, const pel_class *d_classes, const uint64_t *const *d_cols,
+                                            const void *vec, uint32_t q, uint32_t total_units);
 
 // ---- kernels_mle_eval.hip: a batch of columns evaluated at their whole points (EvalcheckProver::prove's first step, evalcheck/prove.rs:191-275,
 // 812-879): slot_j = sum_l lo[l] * sum_h hi[h] * M_j[h * 2^b + l].  A unit (one workgroup) is a chunk of 2^log_ch rows h of a GROUP of jobs of

@@ -7,6 +7,9 @@
 //   collect_projected_mles                               subclaims.rs:356-439    evaluate_partial_high of every inner column at the high
 //                                                                                 coordinates of its claim -> ONE bn_partial_eval_high_batch
 //                                                                                 per distinct suffix
+//   try_build_partial_eval                               subclaims.rs:305-346    an inner column that is a LinearCombination: projected from
+//                                                                                 its constituents, never materialised -> ONE
+//                                                                                 bn_partial_eval_high_lincomb_batch per distinct suffix
 //   ShiftIndPartialEval::multilinear_extension           transparent/shift_ind.rs:117-161, 276-366   host table of 2^b elements
 //   TowerBasis::multilinear_extension                    transparent/tower_basis.rs:54-70            host table of 2^k elements
 //   RegularSumcheckProver per constraint set + batch_prove   -> BivariateSumcheckProver + SumcheckBatchProver (sumcheck.hpp, batch_prover.hpp):
@@ -18,7 +21,8 @@
 //
 // What comes out: the truncated round proofs and the final evaluations in finishing order.  A PROJECTION's final evaluation v at
 // the reversed challenges r' (r'[i] = the challenge of round b - 1 - i of its prover) is the new evalcheck claim (r' || suffix, v)
-// on its inner column; a shift indicator's or tower basis's final evaluation is what the verifier recomputes itself.
+// on its inner column (for a LINCOMB: on the linear-combination oracle itself); a shift indicator's or tower basis's final evaluation
+// is what the verifier recomputes itself.
 //
 // evalcheck_evaluate_claims is the step in FRONT of every round: EvalcheckProver::prove evaluates the materialised witness of every leaf
 // oracle whose value is not yet known at its whole claim point ("MLE Fold Full", evalcheck/prove.rs:191-275, make_new_eval_claim :812-879).
@@ -41,7 +45,7 @@ namespace binius_amd {
 enum class ShiftVariant : uint32_t { CircularLeft = 0, LogicalLeft = 1, LogicalRight = 2 };
 
 struct EvalcheckMultilinear {
-	enum Kind : uint32_t { Projection = 0, ShiftInd = 1, TowerBasis = 2 } kind = Projection;
+	enum Kind : uint32_t { Projection = 0, ShiftInd = 1, TowerBasis = 2, LinComb = 3 } kind = Projection;
 	// Projection: the inner column (2^n_vars values of tower_level, packed into F, only read) at the suffix pool[suffix_off .. + suffix_len)
 	const void *d_column = nullptr;
 	uint32_t tower_level = 0, n_vars = 0;
@@ -52,6 +56,17 @@ struct EvalcheckMultilinear {
 	uint32_t r_off = 0, r_len = 0;
 	// TowerBasis: table[i] = basis(iota, i), i < 2^k
 	uint32_t k = 0, iota = 0;
+	// LinComb: offset + sum of coeff * column over the terms [first_term, first_term + n_terms) of the call's term list (nested combinations
+	// flattened by the caller), 2^n_vars values each, at the suffix pool[suffix_off .. + suffix_len)
+	uint32_t first_term = 0, n_terms = 0;
+	B128 offset = B128::ZERO();
+};
+
+// one constituent of a linear combination: a column as it is read (2^n_vars values of tower_level, packed into F) and its coefficient
+struct EvalcheckTerm {
+	const void *d_column = nullptr;
+	uint32_t tower_level = 0;
+	B128 coeff = B128::ONE();
 };
 
 struct EvalcheckProver {
@@ -70,12 +85,20 @@ inline EvalcheckProjection evalcheck_projection_key(const EvalcheckMultilinear &
 	return {{m.d_column, m.tower_level}, {m.suffix_off, m.suffix_len}};
 }
 
-// Exact: the tensor expansion of every distinct suffix, one table per distinct (column, tower level, suffix) projection and per transparent
-// multilinear, and the provers' fold buffers (m * 2^(b-1) each).
+// the identity of a linear-combination projection: (term range, offset, suffix) and the number of variables the terms are read with
+using EvalcheckLinComb = std::pair<std::pair<std::pair<uint32_t, uint32_t>, std::pair<uint64_t, uint64_t>>, std::pair<EvalcheckSuffix, uint32_t>>;
+inline EvalcheckLinComb evalcheck_lincomb_key(const EvalcheckMultilinear &m)
+{
+	return {{{m.first_term, m.n_terms}, {m.offset.lo, m.offset.hi}}, {{m.suffix_off, m.suffix_len}, m.n_vars}};
+}
+
+// Exact: the tensor expansion of every distinct suffix, one table per distinct (column, tower level, suffix) projection, per distinct
+// (term range, offset, suffix) linear combination and per transparent multilinear, and the provers' fold buffers (m * 2^(b-1) each).
 inline size_t evalcheck_scratch_elems(const std::vector<EvalcheckProver> &provers)
 {
 	std::map<EvalcheckSuffix, bool> suffixes;
 	std::map<EvalcheckProjection, bool> projections;
+	std::map<EvalcheckLinComb, bool> lincombs;
 	size_t total = 0;
 	for (const EvalcheckProver &p : provers) {
 		for (const EvalcheckMultilinear &m : p.multilins) {
@@ -83,6 +106,10 @@ inline size_t evalcheck_scratch_elems(const std::vector<EvalcheckProver> &prover
 				const EvalcheckSuffix s{m.suffix_off, m.suffix_len};
 				if (suffixes.emplace(s, true).second) total += (size_t)1 << m.suffix_len;
 				if (projections.emplace(evalcheck_projection_key(m), true).second) total += (size_t)1 << p.n_vars;
+			} else if (m.kind == EvalcheckMultilinear::LinComb) {
+				const EvalcheckSuffix s{m.suffix_off, m.suffix_len};
+				if (suffixes.emplace(s, true).second) total += (size_t)1 << m.suffix_len;
+				if (lincombs.emplace(evalcheck_lincomb_key(m), true).second) total += (size_t)1 << p.n_vars;
 			} else {
 				total += (size_t)1 << p.n_vars;
 			}
@@ -120,7 +147,8 @@ inline std::vector<B128> evalcheck_shift_ind_table(size_t b, size_t offset, Shif
 using EvalcheckOutput = BatchSumcheckOutput;
 
 inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::vector<EvalcheckProver> &provers, const std::vector<B128> &pool, FSliceMut scratch,
-                                                 const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges)
+                                                 const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges,
+                                                 const std::vector<EvalcheckTerm> &terms = {})
 {
 	if (batch_coeffs.size() != provers.size()) throw Error(Error::InputValidation, "IncorrectNumberOfBatchCoeffs");
 	size_t total_m = 0;
@@ -135,6 +163,11 @@ inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::v
 				if (!m.d_column) throw Error(Error::InputValidation, "null inner column");
 				if (m.n_vars != p.n_vars + m.suffix_len) throw Error(Error::InputValidation, "a projection's inner column has b + |suffix| variables");
 				if ((size_t)m.suffix_off + m.suffix_len > pool.size()) throw Error(Error::InputValidation, "a suffix leaves the point pool");
+				break;
+			case EvalcheckMultilinear::LinComb:
+				if (m.n_vars != p.n_vars + m.suffix_len) throw Error(Error::InputValidation, "a linear combination has b + |suffix| variables");
+				if ((size_t)m.suffix_off + m.suffix_len > pool.size()) throw Error(Error::InputValidation, "a suffix leaves the point pool");
+				if ((size_t)m.first_term + m.n_terms > terms.size()) throw Error(Error::InputValidation, "a linear combination's terms leave the term list");
 				break;
 			case EvalcheckMultilinear::ShiftInd:
 				if (m.block_size != p.n_vars || m.r_len != m.block_size) throw Error(Error::InputValidation, "shift indicator: block_size and |r| must equal the prover's number of variables");
@@ -156,21 +189,35 @@ inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::v
 	DeviceBumpAllocator alloc(scratch);
 
 	// ---- collect_projected_mles: distinct suffixes expanded once, all projections of a suffix in one call, duplicates once
+	// (a linear combination is projected from its constituents by the op that XORs them on load; the whole term list travels with
+	// every call, a job names its range)
 	struct SuffixJob {
 		FSlice query;
 		std::vector<bn_pe_column> cols;
 		std::vector<void *> outs;
+		std::vector<bn_pel_job> lc_jobs;
+		std::vector<void *> lc_outs;
 	};
 	std::map<EvalcheckSuffix, SuffixJob> jobs;
 	std::map<EvalcheckProjection, FSlice> projected;
+	std::map<EvalcheckLinComb, FSlice> combined;
 	for (const EvalcheckProver &p : provers) {
 		for (const EvalcheckMultilinear &m : p.multilins) {
-			if (m.kind != EvalcheckMultilinear::Projection) continue;
+			if (m.kind != EvalcheckMultilinear::Projection && m.kind != EvalcheckMultilinear::LinComb) continue;
 			const EvalcheckSuffix s{m.suffix_off, m.suffix_len};
 			auto job = jobs.find(s);
 			if (job == jobs.end()) {
 				const FSliceMut q = ops::eq_ind_partial_eval(hal, alloc, std::vector<B128>(pool.begin() + m.suffix_off, pool.begin() + m.suffix_off + m.suffix_len));
-				job = jobs.emplace(s, SuffixJob{ComputeMemory::as_const(q), {}, {}}).first;
+				job = jobs.emplace(s, SuffixJob{ComputeMemory::as_const(q), {}, {}, {}, {}}).first;
+			}
+			if (m.kind == EvalcheckMultilinear::LinComb) {
+				const auto lc_key = evalcheck_lincomb_key(m);
+				if (combined.count(lc_key)) continue;
+				FSliceMut o = alloc.alloc((size_t)1 << p.n_vars);
+				job->second.lc_jobs.push_back(bn_pel_job{m.n_vars, m.first_term, m.n_terms, 0, m.offset.raw()});
+				job->second.lc_outs.push_back(o.ptr);
+				combined.emplace(lc_key, ComputeMemory::as_const(o));
+				continue;
 			}
 			const auto key = evalcheck_projection_key(m);
 			if (projected.count(key)) continue;
@@ -180,8 +227,15 @@ inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::v
 			projected.emplace(key, ComputeMemory::as_const(o));
 		}
 	}
-	for (auto &kv : jobs)
-		check(bn_partial_eval_high_batch(hal.raw_ctx(), kv.second.cols.data(), (uint32_t)kv.second.cols.size(), kv.second.query.ptr, kv.first.second, kv.second.outs.data()));
+	std::vector<bn_pel_term> raw_terms;
+	for (const EvalcheckTerm &t : terms) raw_terms.push_back(bn_pel_term{t.d_column, t.tower_level, 0, t.coeff.raw()});
+	for (auto &kv : jobs) {
+		if (!kv.second.cols.empty())
+			check(bn_partial_eval_high_batch(hal.raw_ctx(), kv.second.cols.data(), (uint32_t)kv.second.cols.size(), kv.second.query.ptr, kv.first.second, kv.second.outs.data()));
+		if (!kv.second.lc_jobs.empty())
+			check(bn_partial_eval_high_lincomb_batch(hal.raw_ctx(), kv.second.lc_jobs.data(), (uint32_t)kv.second.lc_jobs.size(), raw_terms.data(), (uint32_t)raw_terms.size(),
+			                                         kv.second.query.ptr, kv.first.second, kv.second.lc_outs.data()));
+	}
 
 	// ---- the transparent tables and the provers
 	std::vector<B128> host_mem(total_m + 8);
@@ -192,6 +246,10 @@ inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::v
 		for (const EvalcheckMultilinear &m : p.multilins) {
 			if (m.kind == EvalcheckMultilinear::Projection) {
 				mls.push_back(projected.at(evalcheck_projection_key(m)));
+				continue;
+			}
+			if (m.kind == EvalcheckMultilinear::LinComb) {
+				mls.push_back(combined.at(evalcheck_lincomb_key(m)));
 				continue;
 			}
 			std::vector<B128> table;

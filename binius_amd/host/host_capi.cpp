@@ -1047,10 +1047,12 @@ int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *c
 
 // One round of evalcheck's bivariate sumchecks (evalcheck/subclaims.rs:549-586 with the witness construction in front of it) through
 // the C++ mirror binius_amd/host/evalcheck.hpp; the arguments and the layout of the outputs are described in include/binius_amd_host.h.
-int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const uint32_t *ml_desc, const void *const *d_columns,
-                                  const bn_f128 *point_pool, uint32_t pool_len, const uint32_t *comp_indices, const bn_f128 *sums, void *d_scratch,
-                                  uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges, bn_f128 *round_proofs_out,
-                                  bn_f128 *final_evals_out)
+// (with_lincomb: the _lc entry, which alone accepts BNH_EC_LINCOMB and reads the term arrays and the offsets)
+static int evalcheck_bivariate_prove_capi(bool with_lincomb, bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const uint32_t *ml_desc,
+                                          const void *const *d_columns, uint32_t n_terms, const uint32_t *term_levels, const void *const *d_term_columns,
+                                          const bn_f128 *term_coeffs, const bn_f128 *ml_offsets, const bn_f128 *point_pool, uint32_t pool_len,
+                                          const uint32_t *comp_indices, const bn_f128 *sums, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs,
+                                          const bn_f128 *challenges, bn_f128 *round_proofs_out, bn_f128 *final_evals_out)
 {
 	return guarded([&]() -> int {
 		if (!ctx || (n_provers && (!prover_desc || !batch_coeffs)) || !round_proofs_out || !final_evals_out || (!d_scratch && scratch_elems) || (pool_len && !point_pool))
@@ -1063,7 +1065,10 @@ int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_
 			total_c += prover_desc[3 * i + 2];
 		}
 		if ((total_m && (!ml_desc || !d_columns)) || (total_c && (!comp_indices || !sums)) || (max_b && !challenges)) throw Error(Error::InputValidation, "null argument");
+		if (n_terms && (!term_levels || !d_term_columns || !term_coeffs)) throw Error(Error::InputValidation, "null argument");
 		const std::vector<B128> pool = from_raw(point_pool, pool_len);
+		std::vector<EvalcheckTerm> terms(n_terms);
+		for (uint32_t t = 0; t < n_terms; t++) terms[t] = EvalcheckTerm{d_term_columns[t], term_levels[t], B128(term_coeffs[t].lo, term_coeffs[t].hi)};
 		std::vector<EvalcheckProver> provers(n_provers);
 		size_t at_ml = 0, at_c = 0;
 		for (uint32_t i = 0; i < n_provers; i++) {
@@ -1097,6 +1102,18 @@ int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_
 					ml.k = d[1];
 					ml.iota = d[2];
 					break;
+				case BNH_EC_LINCOMB:
+					if (!with_lincomb) throw Error(Error::InputValidation, "unknown multilinear kind");
+					if (!ml_offsets) throw Error(Error::InputValidation, "null argument");
+					ml.kind = EvalcheckMultilinear::LinComb;
+					ml.n_vars = d[1];
+					ml.suffix_off = d[2];
+					ml.suffix_len = d[3];
+					ml.first_term = d[4];
+					ml.n_terms = d[5];
+					ml.offset = B128(ml_offsets[at_ml].lo, ml_offsets[at_ml].hi);
+					if (ml.suffix_len > 48) throw Error(Error::InputValidation, "a suffix has at most 48 coordinates");
+					break;
 				default: throw Error(Error::InputValidation, "unknown multilinear kind");
 				}
 				p.multilins.push_back(ml);
@@ -1106,10 +1123,30 @@ int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_
 			at_c += nc;
 		}
 		ComputeLayer hal(ctx);
-		const EvalcheckOutput out = evalcheck_bivariate_prove(hal, provers, pool, FSliceMut{d_scratch, (size_t)scratch_elems}, from_raw(batch_coeffs, n_provers), from_raw(challenges, max_b));
+		const EvalcheckOutput out =
+			evalcheck_bivariate_prove(hal, provers, pool, FSliceMut{d_scratch, (size_t)scratch_elems}, from_raw(batch_coeffs, n_provers), from_raw(challenges, max_b), terms);
 		put_batch_output(out, round_proofs_out, final_evals_out);
 		return 0;
 	});
+}
+
+int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const uint32_t *ml_desc, const void *const *d_columns,
+                                  const bn_f128 *point_pool, uint32_t pool_len, const uint32_t *comp_indices, const bn_f128 *sums, void *d_scratch,
+                                  uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges, bn_f128 *round_proofs_out,
+                                  bn_f128 *final_evals_out)
+{
+	return evalcheck_bivariate_prove_capi(false, ctx, n_provers, prover_desc, ml_desc, d_columns, 0, nullptr, nullptr, nullptr, nullptr, point_pool, pool_len, comp_indices,
+	                                      sums, d_scratch, scratch_elems, batch_coeffs, challenges, round_proofs_out, final_evals_out);
+}
+
+int bnh_evalcheck_bivariate_prove_lc(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const uint32_t *ml_desc, const void *const *d_columns,
+                                     uint32_t n_terms, const uint32_t *term_levels, const void *const *d_term_columns, const bn_f128 *term_coeffs,
+                                     const bn_f128 *ml_offsets, const bn_f128 *point_pool, uint32_t pool_len, const uint32_t *comp_indices, const bn_f128 *sums,
+                                     void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges, bn_f128 *round_proofs_out,
+                                     bn_f128 *final_evals_out)
+{
+	return evalcheck_bivariate_prove_capi(true, ctx, n_provers, prover_desc, ml_desc, d_columns, n_terms, term_levels, d_term_columns, term_coeffs, ml_offsets, point_pool,
+	                                      pool_len, comp_indices, sums, d_scratch, scratch_elems, batch_coeffs, challenges, round_proofs_out, final_evals_out);
 }
 
 // The evaluations in front of an evalcheck round (evalcheck/prove.rs:191-275) through evalcheck_evaluate_claims of the same mirror; the

@@ -102,6 +102,15 @@ pub const BN_PE_COLS_FALLBACK: usize = 3;
 pub const BN_PE_MAX_SHARE: usize = 4;
 pub const BN_PE_FOLD_LEFT_ROUTED: usize = 5;
 pub const BN_PE_MAX_VARS: u32 = 40;
+pub const BN_PEL_N: usize = 7;
+pub const BN_PEL_CALLS: usize = 0;
+pub const BN_PEL_LAUNCHES: usize = 1;
+pub const BN_PEL_JOBS: usize = 2;
+pub const BN_PEL_TERMS: usize = 3;
+pub const BN_PEL_CLASSES: usize = 4;
+pub const BN_PEL_JOBS_FALLBACK: usize = 5;
+pub const BN_PEL_MAX_SHARE: usize = 6;
+pub const BN_PEL_MAX_TERMS: u32 = 64;
 pub const BN_UF_N: usize = 3;
 pub const BN_UF_CALLS: usize = 0;
 pub const BN_UF_LAUNCHES: usize = 1;
@@ -136,6 +145,25 @@ pub struct bn_pe_column {
 	pub d_evals: *const c_void,
 	pub tower_level: u32,
 	pub n_vars: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bn_pel_term {
+	pub d_evals: *const c_void,
+	pub tower_level: u32,
+	pub reserved: u32,
+	pub coeff: bn_f128,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bn_pel_job {
+	pub n_vars: u32,
+	pub first_term: u32,
+	pub n_terms: u32,
+	pub reserved: u32,
+	pub offset: bn_f128,
 }
 
 #[repr(C)]
@@ -341,6 +369,17 @@ unsafe extern "C" {
 		d_outs: *const *mut c_void,
 	) -> c_int;
 	pub fn bn_partial_eval_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_partial_eval_high_lincomb_batch(
+		ctx: *mut bn_ctx,
+		jobs: *const c_void,
+		n_jobs: u32,
+		terms: *const c_void,
+		n_terms_total: u32,
+		d_tensor_query: *const c_void,
+		query_vars: u32,
+		d_outs: *const *mut c_void,
+	) -> c_int;
+	pub fn bn_partial_eval_lincomb_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 	pub fn bn_univariate_fold_batch(
 		ctx: *mut bn_ctx,
 		cols: *const c_void,

@@ -248,6 +248,45 @@ int bn_partial_eval_high_batch(bn_ctx *ctx, const void *cols, uint32_t n_cols, c
  * call counts nowhere. */
 enum { BN_PE_CALLS = 0, BN_PE_LAUNCHES = 1, BN_PE_COLS_KERNEL = 2, BN_PE_COLS_FALLBACK = 3, BN_PE_MAX_SHARE = 4, BN_PE_FOLD_LEFT_ROUTED = 5, BN_PE_N = 6 };
 int bn_partial_eval_counters(bn_ctx *ctx, uint64_t *counters /*[BN_PE_N]*/);
+/* The same projection for inner columns that are LINEAR COMBINATIONS of columns and are never materialised (try_build_partial_eval,
+ * core/src/protocols/evalcheck/subclaims.rs:305-346; keccak's c[x], the sum of five state columns, under its shift).  Job j has n_vars
+ * variables and the terms terms[first_term .. first_term + n_terms), n_terms <= BN_PEL_MAX_TERMS; a term is a column of 2^n_vars values
+ * of its own tower level (0 or 3 .. 7, levels may differ inside a job), packed as bn_partial_eval_high_batch takes columns (n_vars +
+ * tower_level >= 7), with a B128 coefficient.  A column may appear in several jobs and more than once in one.  With out_len =
+ * 2^(n_vars - query_vars):
+ *   d_outs[j][i] = offset + sum_t coeff_t * sum_{q < 2^query_vars} query[q] * column_t[q * out_len + i]
+ * bit-exact, overwritten not accumulated, exactly out_len elements.  The offset is added once, unscaled (the tensor expansion of a point
+ * sums to one; the op does not check the query).  n_terms = 0 gives the offset; a zero coefficient contributes nothing; nested
+ * combinations are flattened by the caller.  jobs, terms and d_outs are HOST arrays; pointers are 16-byte aligned; every reserved
+ * field is 0; inputs are only read; an output overlaps no column, not the query and no other output.  Inside a job the terms of equal
+ * (tower level, coefficient) are XOR-ed as packed words when they are loaded and cost ONE pass over the rows; the sums of such a class
+ * are multiplied by the coefficient once per workgroup (never for ONE).  TWO launches serve all jobs of at most 1024 outputs whatever
+ * their number, terms, levels and sizes (neither is made when the call has no such job); jobs with more outputs share ONE further
+ * launch of a one-thread-per-output form.  n_jobs = 0 is a no-op.  The work runs on the context's stream; the outputs are complete when the
+ * call returns. */
+typedef struct {
+	const void *d_evals;
+	uint32_t tower_level;
+	uint32_t reserved;
+	bn_f128 coeff;
+} bn_pel_term;
+typedef struct {
+	uint32_t n_vars;
+	uint32_t first_term;
+	uint32_t n_terms;
+	uint32_t reserved;
+	bn_f128 offset;
+} bn_pel_job;
+#define BN_PEL_MAX_TERMS 64
+/* (jobs points to n_jobs bn_pel_job, terms to n_terms_total bn_pel_term; untyped in the prototype for the same reason as
+ * bn_partial_eval_high_batch's cols.) */
+int bn_partial_eval_high_lincomb_batch(bn_ctx *ctx, const void *jobs, uint32_t n_jobs, const void *terms, uint32_t n_terms_total,
+                                       const void *d_tensor_query, uint32_t query_vars, void *const *d_outs);
+/* Read-only, per context: accepted bn_partial_eval_high_lincomb_batch calls; the kernel launches they made; jobs; terms; classes (row
+ * loops planned, summed over the jobs); jobs served by the one-thread-per-output form; the largest number of workgroups that shared one
+ * job in the last call.  A rejected call counts nowhere; the BN_PE_* counters do not move. */
+enum { BN_PEL_CALLS = 0, BN_PEL_LAUNCHES = 1, BN_PEL_JOBS = 2, BN_PEL_TERMS = 3, BN_PEL_CLASSES = 4, BN_PEL_JOBS_FALLBACK = 5, BN_PEL_MAX_SHARE = 6, BN_PEL_N = 7 };
+int bn_partial_eval_lincomb_counters(bn_ctx *ctx, uint64_t *counters /*[BN_PEL_N]*/);
 /* The fold of the univariate round of the univariate-skip zerocheck, for every column of a call: ZerocheckProverImpl::
  * fold_univariate_round (core/src/protocols/sumcheck/prove/zerocheck.rs:384-434), which is evaluate_partial_low (math/src/
  * multilinear_extension.rs:302-341) at a query whose expansion is overwritten with the Lagrange coefficients of the univariate

@@ -316,13 +316,30 @@ int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *c
  * final evaluations concatenated in finishing (= input) order.  A PROJECTION's final evaluation v is the evaluation of its table at the
  * reversed challenges r' (r'[i] = the challenge of round b - 1 - i): the new evalcheck claim (r' || suffix, v) on the inner column.
  * The caller's columns are only read. */
-enum { BNH_EC_PROJECTION = 0, BNH_EC_SHIFT_IND = 1, BNH_EC_TOWER_BASIS = 2 };
+enum { BNH_EC_PROJECTION = 0, BNH_EC_SHIFT_IND = 1, BNH_EC_TOWER_BASIS = 2, BNH_EC_LINCOMB = 3 };
 enum { BNH_SHIFT_CIRCULAR_LEFT = 0, BNH_SHIFT_LOGICAL_LEFT = 1, BNH_SHIFT_LOGICAL_RIGHT = 2 };
 #define BNH_EC_DESC_WORDS 6
 int bnh_evalcheck_bivariate_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const uint32_t *ml_desc, const void *const *d_columns,
                                   const bn_f128 *point_pool, uint32_t pool_len, const uint32_t *comp_indices, const bn_f128 *sums, void *d_scratch,
                                   uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges, bn_f128 *round_proofs_out,
                                   bn_f128 *final_evals_out);
+/* The same round with inner columns that are LINEAR COMBINATIONS of columns (try_build_partial_eval, evalcheck/subclaims.rs:305-346; keccak's
+ * c[x] under its shift): bnh_evalcheck_bivariate_prove's arguments and one more kind, which bnh_evalcheck_bivariate_prove rejects,
+ *     BNH_EC_LINCOMB    : (kind, n_vars, suffix_off, suffix_len, first_term, n_terms) -- ml_offsets[j] + the sum over the terms
+ *       [first_term, first_term + n_terms) of term_coeffs[t] * the column d_term_columns[t] (2^n_vars values of tower level term_levels[t],
+ *       packed into F, only read), n_vars = b + suffix_len, projected at point_pool[suffix_off .. + suffix_len) from its constituents: the
+ *       combination is never materialised.  Nested combinations are flattened by the caller (coefficients multiplied through).
+ *   term_levels / d_term_columns / term_coeffs: the n_terms terms of the call; ml_offsets: one offset per multilinear, read for kind 3 only
+ *     (all four may be null when no multilinear is of kind 3); d_columns[j] is ignored for kind 3
+ * All BNH_EC_LINCOMB multilinears of one distinct suffix are ONE bn_partial_eval_high_lincomb_batch, beside the one
+ * bn_partial_eval_high_batch of that suffix's plain projections; the suffix expansion is shared; an identical (term range, offset, suffix) is
+ * projected once and counts 2^b elements of scratch once.  A call without kind 3 makes exactly bnh_evalcheck_bivariate_prove's calls.  A
+ * BNH_EC_LINCOMB's final evaluation v is the new evalcheck claim (r' || suffix, v) on the linear-combination oracle itself. */
+int bnh_evalcheck_bivariate_prove_lc(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const uint32_t *ml_desc, const void *const *d_columns,
+                                     uint32_t n_terms, const uint32_t *term_levels, const void *const *d_term_columns, const bn_f128 *term_coeffs,
+                                     const bn_f128 *ml_offsets, const bn_f128 *point_pool, uint32_t pool_len, const uint32_t *comp_indices, const bn_f128 *sums,
+                                     void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges, bn_f128 *round_proofs_out,
+                                     bn_f128 *final_evals_out);
 
 /* The evaluations in front of every evalcheck round: EvalcheckProver::prove evaluates the materialised witness of every leaf oracle whose
  * value is not yet known at its whole claim point ("MLE Fold Full", core/src/protocols/evalcheck/prove.rs:191-275, make_new_eval_claim
