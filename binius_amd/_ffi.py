@@ -26,6 +26,7 @@ ORDER_LOW_TO_HIGH, ORDER_HIGH_TO_LOW = 0, 1  # EvaluationOrder (crates/math/src/
 HAL_ML_FOLDED, HAL_ML_TRANSPARENT = 0, 1
 NTT_MAX_DIM = 64
 BN_ME_MAX_LO_VARS, BN_ME_MAX_JOBS = 10, 4096  # bn_mle_evaluate_batch
+BN_MERGE_TILE_LOG2 = 6  # bn_merge_multilins: multilinears of at least twice as many variables are tiled jobs
 
 
 def lib_path():
@@ -203,6 +204,8 @@ def lib():
         "bn_ring_switch_counters": [vp, C.POINTER(u64)],
         "bn_mle_evaluate_batch": [vp, vp, u32, vp, u32, PF],
         "bn_mle_evaluate_counters": [vp, C.POINTER(u64)],
+        "bn_merge_multilins": [vp, u32, C.POINTER(u32), C.POINTER(vp), vp, u32, u32],
+        "bn_merge_counters": [vp, C.POINTER(u64)],
         "bn_log_chunks_range": [C.POINTER(MemMap), u32, C.POINTER(u32), C.POINTER(u32)],
         "bn_pick_log_chunks": [C.POINTER(MemMap), u32, C.POINTER(u32)],
         "bn_kernel_launch": [vp, C.POINTER(MemMap), u32, C.POINTER(KOp), u32, C.POINTER(u32), u32, u32, PF, vp],
@@ -262,6 +265,7 @@ ABI_SYMBOLS = [
     "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
     "bn_univariate_fold_batch", "bn_univariate_fold_counters", "bn_ring_switch_eq_ind_batch", "bn_ring_switch_counters",
     "bn_mle_evaluate_batch", "bn_mle_evaluate_counters", "bn_partial_eval_high_lincomb_batch", "bn_partial_eval_lincomb_counters",
+    "bn_merge_multilins", "bn_merge_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -1049,6 +1053,29 @@ class Context:
         c = (C.c_uint64 * 4)()
         _check(lib().bn_mle_evaluate_counters(self._h, c))
         return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2]), "max_share": int(c[3])}
+
+    def merge_multilins(self, multilins, message, total_vars, log_repeats=0):
+        """merge_multilins (piop/prove.rs:78-118) of multilinears on the device (bn_merge_multilins): multilins are DevSlices of
+        2^n_vars elements, ascending by length; message, a DevSlice of 2^(total_vars + log_repeats) elements, receives 2^log_repeats
+        copies of: the multilinears in reverse order, each with bit-reversed indices, then zeros up to 2^total_vars."""
+        n = len(multilins)
+        n_vars = []
+        for m in multilins:
+            if m is not None and (m.len == 0 or m.len & (m.len - 1)):
+                raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: merge_multilins: a multilinear holds 2^n_vars elements")
+            n_vars.append(m.len.bit_length() - 1 if m is not None else 0)
+        if message is not None and 0 <= total_vars + log_repeats < 48 and message.len != 1 << (total_vars + log_repeats):
+            raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: merge_multilins: the message holds 2^(total_vars + log_repeats) elements")
+        nv = (C.c_uint32 * max(1, n))(*n_vars)
+        ptrs = (C.c_void_p * max(1, n))(*[(m.ptr if m is not None else None) for m in multilins])
+        _check(lib().bn_merge_multilins(self._h, n, nv, ptrs, message.ptr if message is not None else None, total_vars, log_repeats))
+
+    def merge_counters(self):
+        """bn_merge_counters: accepted bn_merge_multilins calls, the kernel launches they made, the jobs they served (multilinears and
+        zero tails), the tiled and the small multilinears among them.  Rejected calls count nowhere."""
+        c = (C.c_uint64 * 5)()
+        _check(lib().bn_merge_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2]), "jobs_tiled": int(c[3]), "jobs_small": int(c[4])}
 
     # ---- accumulate_kernels / map_kernels
     def pick_log_chunks(self, mem_maps):

@@ -63,6 +63,22 @@ def host_lib():
             C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(F128), C.c_uint32, C.POINTER(F128), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32,
             C.POINTER(C.c_uint32), C.POINTER(F128), C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_double),
         ]
+        U32P_, VPP_, FP_ = C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(F128)
+        L.bnh_piop_message_layout.restype = C.c_int
+        L.bnh_piop_message_layout.argtypes = [C.c_uint32, U32P_, C.POINTER(C.c_uint64), U32P_]
+        L.bnh_piop_commit_elems.restype = C.c_int
+        L.bnh_piop_commit_elems.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, U32P_, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.bnh_piop_commit.restype = C.c_int
+        L.bnh_piop_commit.argtypes = [C.c_void_p, C.c_uint32, U32P_, VPP_, C.c_uint32, C.c_uint32, C.c_uint32, U32P_, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                      C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_double)]
+        L.bnh_piop_commit_last_ms.restype = C.c_double
+        L.bnh_piop_commit_last_ms.argtypes = []
+        L.bnh_piop_prove_committed.restype = C.c_int
+        L.bnh_piop_prove_committed.argtypes = [
+            C.c_void_p, C.c_uint32, U32P_, VPP_, C.c_uint32, U32P_, VPP_, C.c_uint32, U32P_, FP_, C.c_uint32, C.c_uint32, C.c_uint32, U32P_, C.c_uint32, C.c_uint32,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, FP_, C.c_uint32, FP_, C.c_uint32, U32P_, C.c_uint32, U32P_, FP_, C.c_uint64, C.POINTER(C.c_uint64),
+            C.c_void_p, C.c_uint32, U32P_, C.POINTER(C.c_double),
+        ]
         L.bnh_eqind_sumcheck_prove.restype = C.c_int
         L.bnh_eqind_sumcheck_prove.argtypes = [
             C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32),
@@ -393,6 +409,83 @@ class PiopPlan:
                 out.append((kind, [from_f128(self.scalars[at_s + j]) for j in range(cnt)]))
                 at_s += cnt
         return out
+
+
+def _host_check(rc):
+    if rc != 0:
+        raise BnError(rc, host_lib().bnh_last_error().decode())
+
+
+def piop_message_layout(n_varss):
+    """bnh_piop_message_layout: (offsets, total_vars) -- where each committed multilinear (ascending by n_vars) starts in the message
+    of merge_multilins, and CommitMeta::total_vars.  Host arithmetic; needs no context."""
+    n = len(n_varss)
+    nv = (C.c_uint32 * max(1, n))(*n_varss)
+    offs, total = (C.c_uint64 * max(1, n))(), C.c_uint32()
+    _host_check(host_lib().bnh_piop_message_layout(n, nv, offs, C.byref(total)))
+    return [int(offs[i]) for i in range(n)], total.value
+
+
+def piop_commit_elems(params):
+    """bnh_piop_commit_elems: (codeword elements, tree elements) a PiopCommit with these FRIParams needs."""
+    ar = (C.c_uint32 * max(1, len(params.fold_arities)))(*params.fold_arities)
+    code, tree = C.c_uint64(), C.c_uint64()
+    _host_check(host_lib().bnh_piop_commit_elems(params.log_dim, params.log_inv_rate, params.log_batch_size, ar, len(params.fold_arities), C.byref(code), C.byref(tree)))
+    return code.value, tree.value
+
+
+class PiopCommit:
+    """piop::commit on the device (bnh_piop_commit; piop/prove.rs:120-165): merge_multilins of the committed multilinears straight
+    into the codeword with every repeat, the batched NTT, the Merkle tree.  committed: list of (n_vars, device slice), ascending;
+    codeword / tree: device slices of piop_commit_elems(params) elements, which hold the codeword and the flattened tree after
+    run(); commitment: the 32-byte root; phase_ms: merge, encode, Merkle."""
+
+    def __init__(self, hal, committed, params, codeword, tree):
+        import numpy as np
+
+        self.hal, self.p, self.codeword, self.tree = hal, params, codeword, tree
+        self._keep = committed
+        self.nc = len(committed)
+        self.c_nv = (C.c_uint32 * max(1, self.nc))(*[v for v, _ in committed])
+        self.c_ptr = (C.c_void_p * max(1, self.nc))(*[s.ptr for _, s in committed])
+        self.arities = (C.c_uint32 * max(1, len(params.fold_arities)))(*params.fold_arities)
+        self._commitment = np.zeros(32, dtype=np.uint8)
+        self.phase_ms = (C.c_double * 3)()
+
+    def run(self, phases=True):
+        """phases=False: no phase_ms (and none of the synchronisations between the phases that taking them costs)"""
+        p = self.p
+        _host_check(host_lib().bnh_piop_commit(
+            self.hal._h, self.nc, self.c_nv, self.c_ptr, p.log_dim, p.log_inv_rate, p.log_batch_size, self.arities, len(p.fold_arities), p.n_test_queries,
+            self.codeword.ptr, self.codeword.len, self.tree.ptr, self.tree.len, self._commitment.ctypes.data, self.phase_ms if phases else None))
+        self.total_ms = host_lib().bnh_piop_commit_last_ms()  # between the synchronisations around the commit, as PiopPlan's commit phase
+        return tuple(self.phase_ms)
+
+    @property
+    def commitment(self):
+        return bytes(self._commitment)
+
+
+class PiopCommittedPlan(PiopPlan):
+    """piop::prove from the codeword and tree of a PiopCommit (bnh_piop_prove_committed): PiopPlan without the message and without
+    the commit.  It only reads the codeword and the tree: any number of plans may run from one commit.  transcript() as PiopPlan's;
+    phase_ms[0]: the prove."""
+
+    def __init__(self, hal, committed, transparents, claims, params, codeword, tree, scratch, batch_coeffs, challenges):
+        PiopPlan.__init__(self, hal, committed, transparents, claims, params, None, scratch, batch_coeffs, challenges)
+        self.codeword, self.tree = codeword, tree
+        self.commitment = None
+        self.phase_ms = (C.c_double * 1)()
+
+    def run(self):
+        p = self.p
+        _host_check(host_lib().bnh_piop_prove_committed(
+            self.hal._h, self.nc, self.c_nv, self.c_ptr, self.nt, self.t_nv, self.t_ptr, self.n_claims, self.claims, self.sums,
+            p.log_dim, p.log_inv_rate, p.log_batch_size, self.arities, len(p.fold_arities), p.n_test_queries, self.codeword.ptr, self.tree.ptr,
+            self.scratch.ptr, self.scratch.len, self.bcs, self.n_bcs, self.ch, self.n_ch, self.items, self.max_items,
+            C.byref(self.n_items), self.scalars, self.max_scalars, C.byref(self.n_scalars), self.digests.ctypes.data, self.max_digests,
+            C.byref(self.n_digests), self.phase_ms))
+        return self.phase_ms[0]
 
 
 class EqIndPlan:

@@ -85,6 +85,7 @@ struct bn_ctx {
 	uint64_t uf_calls = 0, uf_launches = 0, uf_cols = 0; // bn_univariate_fold_batch (bn_univariate_fold_counters)
 	uint64_t rs_calls = 0, rs_launches = 0, rs_jobs = 0, rs_queries = 0; // bn_ring_switch_eq_ind_batch (bn_ring_switch_counters)
 	uint64_t me_calls = 0, me_launches = 0, me_jobs = 0, me_max_share = 0; // bn_mle_evaluate_batch (bn_mle_evaluate_counters)
+	uint64_t mg_calls = 0, mg_launches = 0, mg_jobs = 0, mg_jobs_tiled = 0, mg_jobs_small = 0; // bn_merge_multilins (bn_merge_counters)
 	bn::f128 *h_me_rets = nullptr, *d_me_rets = nullptr; // pinned: the results of a bn_mle_evaluate_batch call, BN_ME_MAX_JOBS values (the sequence word stays in h_mail[64])
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -931,6 +932,27 @@ constexpr uint32_t kRsRunJobs = 8;  // nibble tables (8 KiB each) a workgroup ke
 // d_coeffs: the first n_staged (<= 128) row-batch coefficients
 hipError_t launch_ring_switch_eq_ind(hipStream_t s, const rs_run *d_runs, uint32_t n_runs, const rs_job *d_jobs, const void *d_coeffs, uint32_t n_staged,
                                      uint32_t span, uint32_t total_units);
+
+// ---- kernels_merge.hip: merge_multilins (piop/prove.rs:78-118) on the device, every multilinear and the zero tail in one launch.
+// A unit (one workgroup) is one mid value of a tiled job (2^t x 2^t elements through LDS), a whole small job, or kMergeZeroChunk
+// elements of the zero tail.
+enum : uint32_t { kMergeTiled = 0, kMergeSmall = 1, kMergeZero = 2 };
+struct merge_job {
+	const void *src;   // the multilinear (null: zero job)
+	uint64_t dst_off;  // elements from the start of a repeat: off_i, or where the tail starts
+	uint64_t first;    // the job's first unit served by this launch (a job with more units than a launch holds continues in the next)
+	uint64_t len;      // zero job: elements of the tail
+	uint32_t log_len;  // n_vars
+	uint32_t kind;     // kMergeTiled / kMergeSmall / kMergeZero
+	uint32_t start;    // first unit of this job in the launch
+	uint32_t pad_;
+};
+constexpr uint32_t kMergeZeroChunk = 2048;      // elements of a unit of the zero job: eight per thread
+constexpr uint32_t kMergeLaunchJobs = 4096;     // jobs in the table of one launch
+constexpr uint32_t kMergeLaunchUnits = 1u << 30; // workgroups of one launch
+// t: 5 or 6 (BN_MERGE_TILE_LOG2 in the shipped library)
+hipError_t launch_merge_multilins(hipStream_t s, uint32_t t, const merge_job *d_jobs, uint32_t n_jobs, void *d_message, uint32_t log_total, uint32_t log_repeats,
+                                  uint32_t total_units);
 
 // ---- kernels_ntt_tiled.hip
 hipError_t launch_build_mul8(hipStream_t s, uint8_t *d_tab);

@@ -778,6 +778,23 @@ public:
 	{
 		check(abi_timed(AbiProf::COPY, [&] { return bn_copy_d2d(ctx_, src.ptr, src.len_, dst.ptr, dst.len_); }));
 	}
+	// merge_multilins (piop/prove.rs:78-118) of device slices, ascending by length, into `message`: 2^log_repeats copies of
+	// 2^total_vars elements each (bn_merge_multilins)
+	void merge_multilins(const std::vector<FSlice> &multilins, FSliceMut &message, size_t total_vars, size_t log_repeats = 0)
+	{
+		std::vector<uint32_t> n_vars;
+		std::vector<const void *> ptrs;
+		for (const FSlice &m : multilins) {
+			uint32_t l = 0;
+			while (((size_t)1 << l) < m.len_) l++;
+			if (((size_t)1 << l) != m.len_) throw Error(Error::InputValidation, "merge_multilins: a multilinear's length is not a power of two");
+			n_vars.push_back(l);
+			ptrs.push_back(m.ptr);
+		}
+		if (total_vars + log_repeats >= 48 || message.len_ != (size_t)1 << (total_vars + log_repeats))
+			throw Error(Error::InputValidation, "merge_multilins: the message holds 2^(total_vars + log_repeats) elements");
+		check(bn_merge_multilins(ctx_, (uint32_t)multilins.size(), n_vars.data(), ptrs.data(), message.ptr, (uint32_t)total_vars, (uint32_t)log_repeats));
+	}
 	ExprEval compile_expr(const ArithCircuit &expr)
 	{
 		bn_expr *h = nullptr;

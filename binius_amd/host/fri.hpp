@@ -14,6 +14,7 @@
 // The reference keeps a host copy of every codeword because its Merkle prover hashes host slices
 // (prove.rs:396-399); here nothing but roots, layers, branches and opened cosets is read back.
 #pragma once
+#include <chrono>
 #include <numeric>
 
 #include "merkle.hpp"
@@ -83,6 +84,18 @@ inline void encode_ext_batch_inplace(ComputeLayer &hal, const AdditiveNTT &ntt, 
 	ntt.forward_transform(code.ptr, kFaLevel, NTTShape{log_batch_size + kLogDegree, p.rs_log_len(), 0}, 0, 0, p.log_inv_rate());
 }
 
+// The same encoding of a buffer that already holds the message 2^log_inv_rate times (bn_merge_multilins with log_repeats =
+// log_inv_rate wrote the copies): the batched NTT alone
+inline void encode_ext_batch_repeated(const AdditiveNTT &ntt, const FRIParams &p, FSliceMut code, size_t log_batch_size)
+{
+	constexpr size_t kFaLevel = 5, kLogDegree = 2;
+	if (p.rs_log_len() > ntt.log_domain_size() || ntt.tower_level() != kFaLevel) throw FriError("EncoderSubspaceMismatch");
+	const size_t want = (size_t)1 << (p.rs_log_len() + log_batch_size);
+	if (code.len() != want)
+		throw FriError("IncorrectBufferLength { expected: " + std::to_string(want) + ", actual: " + std::to_string(code.len()) + " }");
+	ntt.forward_transform(code.ptr, kFaLevel, NTTShape{log_batch_size + kLogDegree, p.rs_log_len(), 0}, 0, 0, p.log_inv_rate());
+}
+
 struct CommitOutput { // prove.rs:70-74
 	Digest commitment;
 	BinaryMerkleTree committed;
@@ -101,6 +114,37 @@ inline CommitOutput commit_interleaved(ComputeLayer &hal, DeviceBumpAllocator &d
 	encode_ext_batch_inplace(hal, ntt, p, encoded, p.log_batch_size());
 	const size_t coset_log_len = p.fold_arities().empty() ? log_elems : p.fold_arities()[0];
 	auto [commitment, tree] = merkle_prover.commit(ComputeMemory::as_const(encoded), (size_t)1 << coset_log_len, dev_alloc);
+	return CommitOutput{commitment.root, tree, encoded};
+}
+
+// piop::commit (piop/prove.rs:120-165) from the committed multilinears on the device: merge_multilins straight into the codeword
+// buffer, all 2^log_inv_rate copies at once, the batched NTT, the tree.  No message buffer, no head copy, no repeat copies.
+//   committed    device slices ascending by length; their merged length is 2^(log_dim + log_batch_size)
+//   tree_alloc   provides the node array (the codeword comes from dev_alloc)
+//   phase_ms     [3] wall-clock milliseconds of merge, encode and Merkle, each up to a synchronisation, or null (no synchronisation)
+inline CommitOutput commit_interleaved(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, DeviceBumpAllocator &tree_alloc, const FRIParams &p,
+                                       const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover, const std::vector<FSlice> &committed,
+                                       double *phase_ms = nullptr)
+{
+	const size_t log_elems = p.log_dim() + p.log_batch_size();
+	FSliceMut encoded = dev_alloc.alloc((size_t)1 << (log_elems + p.log_inv_rate()));
+	auto stamp = [&] {
+		if (phase_ms) hal.sync();
+		return std::chrono::steady_clock::now();
+	};
+	const auto t0 = stamp();
+	hal.merge_multilins(committed, encoded, log_elems, p.log_inv_rate());
+	const auto t1 = stamp();
+	encode_ext_batch_repeated(ntt, p, encoded, p.log_batch_size());
+	const auto t2 = stamp();
+	const size_t coset_log_len = p.fold_arities().empty() ? log_elems : p.fold_arities()[0];
+	auto [commitment, tree] = merkle_prover.commit(ComputeMemory::as_const(encoded), (size_t)1 << coset_log_len, tree_alloc);
+	const auto t3 = stamp();
+	if (phase_ms) {
+		phase_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+		phase_ms[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+		phase_ms[2] = std::chrono::duration<double, std::milli>(t3 - t2).count();
+	}
 	return CommitOutput{commitment.root, tree, encoded};
 }
 

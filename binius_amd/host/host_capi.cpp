@@ -16,6 +16,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -651,24 +652,29 @@ int bnh_fri_commit_fold(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, ui
 	});
 }
 
-// piop::prove (crates/core/src/piop/prove.rs:148-395) through the C++ mirror piop.hpp: commit_interleaved of the merged message,
+// piop::prove (crates/core/src/piop/prove.rs:148-395) through the C++ mirror piop.hpp: commit_interleaved of the merged message
+// (bnh_piop_prove) or the codeword and tree of an earlier bnh_piop_commit (bnh_piop_prove_committed), then
 // one BivariateSumcheckProver per number of variables, the front-loaded batch prover interleaved with the FRI folder.
 // The transcript comes back as a list of items in writing order: items_out[2 i] = kind (0 round proof, 1 final evaluations of a
 // finished prover, 2 FRI round commitment, 3 FRI terminate codeword), items_out[2 i + 1] = number of scalars (kinds 0, 1, 3:
 // consumed from scalars_out in order) or 1 digest (kind 2: consumed from digests_out in order).
-int bnh_piop_prove(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
-                   const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims, const bn_f128 *claim_sums,
-                   uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities, uint32_t n_test_queries,
-                   const void *d_message, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, uint32_t n_batch_coeffs,
-                   const bn_f128 *challenges, uint32_t n_challenges, uint8_t *commitment_out, uint32_t *items_out, uint32_t max_items, uint32_t *n_items_out,
-                   bn_f128 *scalars_out, uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out, uint32_t max_digests, uint32_t *n_digests_out,
-                   double *phase_ms_out)
+namespace {
+// What the two entry points of piop::prove share: everything but where the codeword and its tree come from.  `commit` runs between the
+// first two time stamps and returns them: bnh_piop_prove commits the message there, bnh_piop_prove_committed wraps the caller's buffers.
+// phase_ms[2]: that step, the prove.
+using PiopCommitStep = std::function<std::pair<FSlice, BinaryMerkleTree>(ComputeLayer &, DeviceBumpAllocator &, const FRIParams &, const AdditiveNTT &, BinaryMerkleTreeProver &)>;
+static int piop_prove_body(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
+                    const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims, const bn_f128 *claim_sums,
+                    uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities, uint32_t n_test_queries,
+                    const PiopCommitStep &commit, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, uint32_t n_batch_coeffs,
+                    const bn_f128 *challenges, uint32_t n_challenges, uint32_t *items_out, uint32_t max_items, uint32_t *n_items_out, bn_f128 *scalars_out,
+                    uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out, uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms)
 {
-	return guarded([&]() -> int {
-		if (!ctx || !commitment_out || !items_out || !n_items_out || !scalars_out || !n_scalars_out || !digests_out || !n_digests_out)
+	{
+		if (!ctx || !items_out || !n_items_out || !scalars_out || !n_scalars_out || !digests_out || !n_digests_out)
 			throw Error(Error::InputValidation, "null argument");
 		if ((n_committed && (!committed_n_vars || !d_committed)) || (n_transparent && (!transparent_n_vars || !d_transparent)) || (n_claims && (!claims || !claim_sums)) ||
-		    (n_arities && !fold_arities) || !d_message || (n_batch_coeffs && !batch_coeffs) || (n_challenges && !challenges))
+		    (n_arities && !fold_arities) || (n_batch_coeffs && !batch_coeffs) || (n_challenges && !challenges))
 			throw Error(Error::InputValidation, "null argument");
 		for (uint32_t i = 0; i < n_committed; i++)
 			if (committed_n_vars[i] >= 48 || !d_committed[i]) throw Error(Error::InputValidation, "committed multilinear: null, or its number of variables out of range (< 48)");
@@ -703,13 +709,11 @@ int bnh_piop_prove(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_
 		BinaryMerkleTreeProver merkle(hal);
 		hal.sync();
 		const auto t0 = std::chrono::steady_clock::now();
-		CommitOutput co = commit_interleaved(hal, dev_alloc, p, ntt, merkle, FSlice{d_message, (size_t)1 << (log_dim + log_batch_size)});
+		const std::pair<FSlice, BinaryMerkleTree> co = commit(hal, dev_alloc, p, ntt, merkle);
 		hal.sync();
 		const auto t1 = std::chrono::steady_clock::now();
-		std::memcpy(commitment_out, co.commitment.data(), 32);
 		if (AbiProf::on()) AbiProf::get() = AbiProf{};
-		PiopProveOutput out = piop_prove(hal, dev_alloc, host_alloc, p, ntt, merkle, commit_meta, co.committed, ComputeMemory::as_const(co.codeword), committed,
-		                                 transparents, cl, bcs, chs);
+		PiopProveOutput out = piop_prove(hal, dev_alloc, host_alloc, p, ntt, merkle, commit_meta, co.second, co.first, committed, transparents, cl, bcs, chs);
 		hal.sync();
 		const auto t2 = std::chrono::steady_clock::now();
 		if (AbiProf::on()) {
@@ -737,13 +741,155 @@ int bnh_piop_prove(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_
 		*n_items_out = ni;
 		*n_scalars_out = ns;
 		*n_digests_out = nd;
-		if (phase_ms_out) {
-			phase_ms_out[0] = elapsed_ms(t0, t1);
-			phase_ms_out[1] = elapsed_ms(t1, t2);
+		phase_ms[0] = elapsed_ms(t0, t1);
+		phase_ms[1] = elapsed_ms(t1, t2);
+		return 0;
+	}
+}
+
+// leaves of the tree over a codeword of these parameters: cosets of 2^arity_0, or of the whole message when nothing is folded
+static size_t piop_commit_log_leaves(uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities)
+{
+	const size_t log_elems = (size_t)log_dim + log_batch_size;
+	return log_elems + log_inv_rate - (n_arities ? fold_arities[0] : log_elems);
+}
+
+// the checks of merge_multilins' callers on the sizes alone: ascending, each below 48
+static void piop_check_committed_n_vars(uint32_t n, const uint32_t *n_vars)
+{
+	if (n && !n_vars) throw Error(Error::InputValidation, "null argument");
+	for (uint32_t i = 0; i < n; i++) {
+		if (n_vars[i] >= 48) throw Error(Error::InputValidation, "committed multilinear: its number of variables out of range (< 48)");
+		if (i && n_vars[i] < n_vars[i - 1]) throw PiopError("CommittedsNotSorted");
+	}
+}
+} // namespace
+
+int bnh_piop_prove(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
+                   const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims, const bn_f128 *claim_sums,
+                   uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities, uint32_t n_test_queries,
+                   const void *d_message, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, uint32_t n_batch_coeffs,
+                   const bn_f128 *challenges, uint32_t n_challenges, uint8_t *commitment_out, uint32_t *items_out, uint32_t max_items, uint32_t *n_items_out,
+                   bn_f128 *scalars_out, uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out, uint32_t max_digests, uint32_t *n_digests_out,
+                   double *phase_ms_out)
+{
+	return guarded([&]() -> int {
+		if (!commitment_out || !d_message) throw Error(Error::InputValidation, "null argument");
+		const PiopCommitStep commit = [&](ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, const FRIParams &p, const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle) {
+			CommitOutput co = commit_interleaved(hal, dev_alloc, p, ntt, merkle, FSlice{d_message, (size_t)1 << (log_dim + log_batch_size)});
+			std::memcpy(commitment_out, co.commitment.data(), 32);
+			return std::make_pair(ComputeMemory::as_const(co.codeword), co.committed);
+		};
+		double ms[2] = {0, 0};
+		const int rc = piop_prove_body(ctx, n_committed, committed_n_vars, d_committed, n_transparent, transparent_n_vars, d_transparent, n_claims, claims, claim_sums,
+		                               log_dim, log_inv_rate, log_batch_size, fold_arities, n_arities, n_test_queries, commit, d_scratch, scratch_elems, batch_coeffs,
+		                               n_batch_coeffs, challenges, n_challenges, items_out, max_items, n_items_out, scalars_out, max_scalars, n_scalars_out, digests_out,
+		                               max_digests, n_digests_out, ms);
+		if (phase_ms_out) phase_ms_out[0] = ms[0], phase_ms_out[1] = ms[1];
+		return rc;
+	});
+}
+
+// piop::prove from a commitment made earlier (bnh_piop_commit): the arguments of bnh_piop_prove, with the codeword and the flattened
+// tree that call left in the caller's buffers in place of the message.  Only reads them; never commits.  phase_ms_out[1]: the prove.
+int bnh_piop_prove_committed(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
+                             const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims,
+                             const bn_f128 *claim_sums, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities,
+                             uint32_t n_arities, uint32_t n_test_queries, const void *d_codeword, const void *d_tree, void *d_scratch, uint64_t scratch_elems,
+                             const bn_f128 *batch_coeffs, uint32_t n_batch_coeffs, const bn_f128 *challenges, uint32_t n_challenges, uint32_t *items_out,
+                             uint32_t max_items, uint32_t *n_items_out, bn_f128 *scalars_out, uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out,
+                             uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms_out)
+{
+	return guarded([&]() -> int {
+		if (!d_codeword || !d_tree || (n_arities && !fold_arities)) throw Error(Error::InputValidation, "null argument");
+		const PiopCommitStep commit = [&](ComputeLayer &hal, DeviceBumpAllocator &, const FRIParams &p, const AdditiveNTT &, BinaryMerkleTreeProver &) {
+			BinaryMerkleTree tree;
+			tree.log_len = piop_commit_log_leaves(log_dim, log_inv_rate, log_batch_size, fold_arities, n_arities);
+			tree.nodes = FSlice{d_tree, BinaryMerkleTreeProver::required_device_memory((size_t)1 << tree.log_len)};
+			tree.hal = &hal;
+			return std::make_pair(FSlice{d_codeword, (size_t)1 << p.log_len()}, tree);
+		};
+		double ms[2] = {0, 0};
+		const int rc = piop_prove_body(ctx, n_committed, committed_n_vars, d_committed, n_transparent, transparent_n_vars, d_transparent, n_claims, claims, claim_sums,
+		                               log_dim, log_inv_rate, log_batch_size, fold_arities, n_arities, n_test_queries, commit, d_scratch, scratch_elems, batch_coeffs,
+		                               n_batch_coeffs, challenges, n_challenges, items_out, max_items, n_items_out, scalars_out, max_scalars, n_scalars_out, digests_out,
+		                               max_digests, n_digests_out, ms);
+		if (phase_ms_out) phase_ms_out[0] = ms[1];
+		return rc;
+	});
+}
+
+static thread_local double g_piop_commit_ms = 0;
+
+// CommitMeta::total_vars and each multilinear's offset in the message of merge_multilins: pure host arithmetic
+int bnh_piop_message_layout(uint32_t n, const uint32_t *n_vars, uint64_t *offsets_out, uint32_t *total_vars_out)
+{
+	return guarded([&]() -> int {
+		if ((n && !offsets_out) || !total_vars_out) throw Error(Error::InputValidation, "null argument");
+		piop_check_committed_n_vars(n, n_vars);
+		uint64_t off = 0;
+		for (uint32_t i = n; i-- > 0;) {
+			offsets_out[i] = off;
+			off += (uint64_t)1 << n_vars[i];
 		}
+		*total_vars_out = (uint32_t)CommitMeta::with_vars(std::vector<size_t>(n_vars, n_vars + n)).total_vars();
 		return 0;
 	});
 }
+
+// what bnh_piop_commit's caller provides, in field elements
+int bnh_piop_commit_elems(uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities,
+                          uint64_t *codeword_elems_out, uint64_t *tree_elems_out)
+{
+	return guarded([&]() -> int {
+		if (!codeword_elems_out || !tree_elems_out || (n_arities && !fold_arities)) throw Error(Error::InputValidation, "null argument");
+		if ((uint64_t)log_dim + log_batch_size + log_inv_rate >= 48) throw Error(Error::InputValidation, "FRI parameters out of range");
+		FRIParams p(log_dim, log_inv_rate, log_batch_size, std::vector<size_t>(fold_arities, fold_arities + n_arities), 0);
+		*codeword_elems_out = (uint64_t)1 << p.log_len();
+		*tree_elems_out = BinaryMerkleTreeProver::required_device_memory((size_t)1 << piop_commit_log_leaves(log_dim, log_inv_rate, log_batch_size, fold_arities, n_arities));
+		return 0;
+	});
+}
+
+// piop::commit (crates/core/src/piop/prove.rs:120-165) from the committed multilinears on the device, through fri.hpp's
+// commit_interleaved over device slices: the merge into the codeword with every repeat, the batched NTT, the tree.
+int bnh_piop_commit(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t log_dim, uint32_t log_inv_rate,
+                    uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities, uint32_t n_test_queries, void *d_codeword, uint64_t codeword_elems,
+                    void *d_tree, uint64_t tree_elems, uint8_t *commitment_out, double *phase_ms_out)
+{
+	return guarded([&]() -> int {
+		if (!ctx || !d_codeword || !d_tree || !commitment_out || (n_committed && !d_committed) || (n_arities && !fold_arities))
+			throw Error(Error::InputValidation, "null argument");
+		piop_check_committed_n_vars(n_committed, committed_n_vars);
+		uint64_t want_code = 0, want_tree = 0;
+		if (const int rc = bnh_piop_commit_elems(log_dim, log_inv_rate, log_batch_size, fold_arities, n_arities, &want_code, &want_tree)) return rc;
+		if (codeword_elems != want_code || tree_elems != want_tree)
+			throw Error(Error::InputValidation, "piop commit: codeword_elems / tree_elems are not what bnh_piop_commit_elems states for these parameters");
+		std::vector<FSlice> committed;
+		for (uint32_t i = 0; i < n_committed; i++) {
+			if (!d_committed[i]) throw Error(Error::InputValidation, "null argument");
+			committed.push_back(FSlice{d_committed[i], (size_t)1 << committed_n_vars[i]});
+		}
+		if (CommitMeta::with_vars(std::vector<size_t>(committed_n_vars, committed_n_vars + n_committed)).total_vars() != (size_t)log_dim + log_batch_size)
+			throw PiopError("FRI message length does not match the commit metadata's total_vars");
+		ComputeLayer hal(ctx);
+		DeviceBumpAllocator code_alloc(FSliceMut{d_codeword, (size_t)codeword_elems}), tree_alloc(FSliceMut{d_tree, (size_t)tree_elems});
+		FRIParams p(log_dim, log_inv_rate, log_batch_size, std::vector<size_t>(fold_arities, fold_arities + n_arities), n_test_queries);
+		AdditiveNTT ntt(hal, 5, p.rs_log_len());
+		BinaryMerkleTreeProver merkle(hal);
+		hal.sync();
+		const auto t0 = std::chrono::steady_clock::now();
+		CommitOutput co = commit_interleaved(hal, code_alloc, tree_alloc, p, ntt, merkle, committed, phase_ms_out);
+		hal.sync();
+		g_piop_commit_ms = elapsed_ms(t0, std::chrono::steady_clock::now());
+		std::memcpy(commitment_out, co.commitment.data(), 32);
+		return 0;
+	});
+}
+
+// wall-clock milliseconds of the last bnh_piop_commit of this thread between the synchronisations around its commit_interleaved --
+// what bnh_fri_commit_fold and bnh_piop_prove report as their commit phase; with phase_ms_out NULL there is no synchronisation inside
+double bnh_piop_commit_last_ms(void) { return g_piop_commit_ms; }
 
 // The front-loaded batch prover alone (protocols/sumcheck/prove/front_loaded.rs:33-203: BatchProver::run with the transcript's
 // samples handed in): p BivariateSumcheckProvers on ONE layer, ascending by number of variables.

@@ -122,7 +122,9 @@ inline std::vector<SumcheckClaimDesc> make_sumcheck_claim_descs(const CommitMeta
 }
 
 // merge_multilins (piop/prove.rs:66-104) for P = F (LOG_WIDTH = 0): the multilinears in REVERSE order, each with bit-reversed
-// indices, then zeros up to 2^total_vars.  Host arithmetic on host data, as in the reference (commit runs before any HAL exists).
+// indices, then zeros up to 2^total_vars.  This is the host form, on host data as in the reference; for committed multilinears that
+// are on the device already (zerocheck, evalcheck and ring switch read them there) ComputeLayer::merge_multilins does the same work
+// in one launch, and fri.hpp's commit_interleaved over device slices merges straight into the codeword.
 inline std::vector<B128> merge_multilins(const std::vector<std::vector<B128>> &multilins, size_t total_vars)
 {
 	std::vector<B128> message((size_t)1 << total_vars, B128::ZERO());

@@ -127,6 +127,13 @@ pub const BN_ME_JOBS: usize = 2;
 pub const BN_ME_MAX_SHARE: usize = 3;
 pub const BN_ME_MAX_LO_VARS: u32 = 10;
 pub const BN_ME_MAX_JOBS: u32 = 4096;
+pub const BN_MERGE_N: usize = 5;
+pub const BN_MERGE_CALLS: usize = 0;
+pub const BN_MERGE_LAUNCHES: usize = 1;
+pub const BN_MERGE_JOBS: usize = 2;
+pub const BN_MERGE_JOBS_TILED: usize = 3;
+pub const BN_MERGE_JOBS_SMALL: usize = 4;
+pub const BN_MERGE_TILE_LOG2: u32 = 6;
 pub const BN_UNIVARIATE_FOLD_MAX_SKIP: u32 = 8;
 pub const BN_EXP_STATIC: u32 = 0;
 pub const BN_EXP_DYNAMIC: u32 = 1;
@@ -407,6 +414,16 @@ unsafe extern "C" {
 		h_out: *mut bn_f128,
 	) -> c_int;
 	pub fn bn_mle_evaluate_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_merge_multilins(
+		ctx: *mut bn_ctx,
+		n: u32,
+		n_vars: *const u32,
+		d_multilins: *const *const c_void,
+		d_message: *mut c_void,
+		total_vars: u32,
+		log_repeats: u32,
+	) -> c_int;
+	pub fn bn_merge_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 
 	pub fn bn_log_chunks_range(maps: *const bn_memmap, n_maps: u32, start: *mut u32, end: *mut u32) -> c_int;
 	pub fn bn_pick_log_chunks(maps: *const bn_memmap, n_maps: u32, log_chunks: *mut u32) -> c_int;

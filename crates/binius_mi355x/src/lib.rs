@@ -116,6 +116,34 @@ impl Mi355xLayer {
 		check(unsafe { ffi::bn_sync(self.ctx) })
 	}
 
+	/// `merge_multilins` (core/src/piop/prove.rs:78-118, P = F) for committed multilinears that are on the device: `multilins`
+	/// ascending by length, each a power of two; `message` receives `2^log_repeats` copies of `2^total_vars` elements, the
+	/// multilinears in reverse order with bit-reversed indices, then zeros (`bn_merge_multilins`).
+	pub fn merge_multilins(&self, multilins: &[DevSlice<'_>], message: &mut DevSliceMut<'_>, total_vars: usize, log_repeats: usize) -> Result<(), Error> {
+		let mut n_vars = Vec::with_capacity(multilins.len());
+		for m in multilins {
+			if !m.len.is_power_of_two() {
+				return Err(Error::InputValidation("merge_multilins: a multilinear's length is not a power of two".into()));
+			}
+			n_vars.push(m.len.trailing_zeros());
+		}
+		if total_vars + log_repeats >= 48 || message.len != 1usize << (total_vars + log_repeats) {
+			return Err(Error::InputValidation("merge_multilins: the message holds 2^(total_vars + log_repeats) elements".into()));
+		}
+		let ptrs: Vec<*const std::os::raw::c_void> = multilins.iter().map(|m| m.as_ptr()).collect();
+		check(unsafe {
+			ffi::bn_merge_multilins(
+				self.ctx,
+				multilins.len() as u32,
+				n_vars.as_ptr(),
+				ptrs.as_ptr(),
+				message.ptr.cast(),
+				total_vars as u32,
+				log_repeats as u32,
+			)
+		})
+	}
+
 	/// NUMA node of the host that `device` hangs off, if the platform says.  The thread that drives a context should run
 	/// there: a small sumcheck round is a host -> device -> host round trip through pinned memory, and from the other
 	/// socket of a 2-socket host every one of them also crosses the socket interconnect.  The

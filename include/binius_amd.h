@@ -379,6 +379,30 @@ int bn_mle_evaluate_batch(bn_ctx *ctx, const void *jobs, uint32_t n_jobs, const 
  * BN_PE_* counters do not move. */
 enum { BN_ME_CALLS = 0, BN_ME_LAUNCHES = 1, BN_ME_JOBS = 2, BN_ME_MAX_SHARE = 3, BN_ME_N = 4 };
 int bn_mle_evaluate_counters(bn_ctx *ctx, uint64_t *counters /*[BN_ME_N]*/);
+/* merge_multilins (crates/core/src/piop/prove.rs:78-118, P = F) for multilinears resident on the device: the FRI message that
+ * piop::commit encodes.  n_vars (HOST array, ascending) and d_multilins name n multilinears of 2^n_vars[i] B128 elements; with
+ * off_i = sum_{j > i} 2^n_vars[j] (the last, largest multilinear comes first), for every r < 2^log_repeats and x < 2^n_vars[i]
+ *   message[r * 2^total_vars + off_i + bitrev(x, n_vars[i])] = multilins[i][x],
+ * every other element of message[0 .. 2^(total_vars + log_repeats)) is zero, nothing outside that range is written and the
+ * multilinears are only read.  log_repeats > 0 writes the copies ReedSolomonCode::encode_ext_batch_inplace makes before its NTT, so a
+ * commit can merge straight into the codeword buffer.  The op does not depend on the tower level: packed committed multilinears are
+ * B128 elements already.  n = 0 is a zero fill; the same multilinear may appear twice.  A null or misaligned pointer, n_vars not
+ * ascending (the error text starts "CommittedsNotSorted"), an n_vars[i] >= 48, total_vars + log_repeats >= 48, more than 2^total_vars
+ * elements in all and a multilinear that overlaps the message range are BN_ERR_INPUT_VALIDATION: nothing is launched, nothing is
+ * counted.  Like every op it first brings up to date what it reads (a fold deferred by bn_extrapolate_line_batch on a multilinear is
+ * visible to the merge); the message is complete when the call returns.
+ * ONE launch per call: a multilinear of at least 2 * BN_MERGE_TILE_LOG2 variables is a tiled job (a workgroup transposes a
+ * 2^t x 2^t tile through LDS: both sides of memory see runs of 2^t elements), a smaller one a small job, the zero tail of every repeat
+ * one more job.  (A call whose jobs or workgroups exceed what one launch holds -- 4096 jobs, 2^30 workgroups -- makes further
+ * launches.) */
+#define BN_MERGE_TILE_LOG2 6
+int bn_merge_multilins(bn_ctx *ctx, uint32_t n, const uint32_t *n_vars, const void *const *d_multilins, void *d_message, uint32_t total_vars,
+                       uint32_t log_repeats);
+/* Read-only, per context (not part of the reference interface): accepted bn_merge_multilins calls, the kernel launches they made,
+ * the jobs they served (multilinears and zero tails), and of the multilinears the tiled and the small ones.  A rejected call counts
+ * nowhere. */
+enum { BN_MERGE_CALLS = 0, BN_MERGE_LAUNCHES = 1, BN_MERGE_JOBS = 2, BN_MERGE_JOBS_TILED = 3, BN_MERGE_JOBS_SMALL = 4, BN_MERGE_N = 5 };
+int bn_merge_counters(bn_ctx *ctx, uint64_t *counters /*[BN_MERGE_N]*/);
 
 /* ---- accumulate_kernels / map_kernels (layer.rs:183, 236) + KernelExecutor (layer.rs:518-590).
  * The kernel-spec closure cannot cross an FFI: the host shim runs it ONCE against a recording

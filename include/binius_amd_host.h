@@ -120,6 +120,39 @@ int bnh_piop_prove(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_
                    bn_f128 *scalars_out, uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out, uint32_t max_digests, uint32_t *n_digests_out,
                    double *phase_ms_out);
 
+/* piop::commit (crates/core/src/piop/prove.rs:120-165) apart from piop::prove, for a caller with a live transcript: the commitment
+ * is written before the first challenge of any phase is sampled (constraint_system/prove.rs:232-234), the codeword and its Merkle
+ * tree are kept until piop::prove at the very end.
+ * bnh_piop_message_layout: pure host arithmetic, no context.  offsets_out[i]: where multilinear i starts in the message of
+ * merge_multilins (the sum of the lengths of the multilinears after it); *total_vars_out: CommitMeta::total_vars.  n_vars ascending
+ * ("CommittedsNotSorted" otherwise), each below 48.
+ * bnh_piop_commit_elems: the field elements the caller provides for the codeword, 2^(log_dim + log_batch_size + log_inv_rate), and
+ * for the flattened tree, 2 * (2 * leaves - 1) with one leaf per coset of 2^fold_arities[0] elements (of the whole message when
+ * n_arities = 0).
+ * bnh_piop_commit: merge_multilins of the committed multilinears (on the device, ascending) straight into d_codeword with all
+ * 2^log_inv_rate copies (bn_merge_multilins), the batched NTT, the tree into d_tree in the layout of BinaryMerkleTree{log_len,
+ * nodes}: flattened layers, leaves first, root last (= commitment_out[32]).  codeword_elems and tree_elems must be what
+ * bnh_piop_commit_elems states, total_vars must equal log_dim + log_batch_size; BN_ERR_INPUT_VALIDATION otherwise.
+ * phase_ms_out[3]: merge, encode, Merkle (wall clock, a synchronisation after each), or NULL.
+ * bnh_piop_prove_committed: bnh_piop_prove from that codeword and tree, which it only reads (any number of proves may follow one
+ * commit); no d_message, no commitment_out; phase_ms_out[1]: the prove, or NULL. */
+int bnh_piop_message_layout(uint32_t n, const uint32_t *n_vars, uint64_t *offsets_out, uint32_t *total_vars_out);
+int bnh_piop_commit_elems(uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities,
+                          uint64_t *codeword_elems_out, uint64_t *tree_elems_out);
+int bnh_piop_commit(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t log_dim, uint32_t log_inv_rate,
+                    uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities, uint32_t n_test_queries, void *d_codeword, uint64_t codeword_elems,
+                    void *d_tree, uint64_t tree_elems, uint8_t *commitment_out, double *phase_ms_out);
+/* diagnostic: wall-clock ms of this thread's last bnh_piop_commit between the synchronisations around its commit (the quantity
+ * bnh_piop_prove and bnh_fri_commit_fold report as their commit phase); with phase_ms_out NULL nothing synchronises in between */
+double bnh_piop_commit_last_ms(void);
+int bnh_piop_prove_committed(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
+                             const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims,
+                             const bn_f128 *claim_sums, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities,
+                             uint32_t n_arities, uint32_t n_test_queries, const void *d_codeword, const void *d_tree, void *d_scratch, uint64_t scratch_elems,
+                             const bn_f128 *batch_coeffs, uint32_t n_batch_coeffs, const bn_f128 *challenges, uint32_t n_challenges, uint32_t *items_out,
+                             uint32_t max_items, uint32_t *n_items_out, bn_f128 *scalars_out, uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out,
+                             uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms_out);
+
 /* EqIndSumcheckProver (crates/core/src/protocols/sumcheck/prove/eq_ind.rs:378-644) through the C++ mirror binius_amd/host/eq_ind.hpp,
  * over the old HAL (binius_hal::ComputationBackend: bn_hal_round_evals + the ComputeLayer's folds), evaluation order High-to-Low,
  * compositions of degree 1 .. 8 (degrees[c]; NULL: all 2; evaluation points 1 ..= degree: 1, infinity, the points 2, 3, ... of the default

@@ -168,7 +168,7 @@ def replay(args, checker=None):
 
     import binius_amd
     from binius_amd import synthetic
-    from binius_amd._host import EqIndPlan, FRIParams, PiopPlan
+    from binius_amd._host import EqIndPlan, FRIParams, PiopCommit, PiopCommittedPlan, PiopPlan, piop_commit_elems
 
     F = binius_amd.HostField
     tb = table(getattr(args, "table", "keccak"))
@@ -187,6 +187,8 @@ def replay(args, checker=None):
     code_elems = 1 << (total_vars + args.log_inv_rate)
     ml_elems = (N_COMMITTED + N_TRANSPARENT) * n
     arena = (1 << total_vars) + 4 * code_elems + 3 * ml_elems + (n_z + 2) * n + (1 << 18)
+    if getattr(args, "merge", "host") == "device":
+        arena += code_elems  # (codeword and tree in the caller's buffers; the message's share goes unused)
     rec = {"bench": tb["name"] + "_replay", "log_perms" if tb["name"] == "keccak" else "log_rows": log_rows, "n_vars_packed": v, "committed": N_COMMITTED, "zerocheck": {"multilinears": n_z, "constraints": len(cons)},
            "piop": {"multilinears": N_COMMITTED + N_TRANSPARENT, "claims": len(claims_ct), "total_vars": total_vars,
                     "fri": {"log_inv_rate": args.log_inv_rate, "log_batch": args.log_batch, "arities": arities}}}
@@ -235,29 +237,38 @@ def replay(args, checker=None):
                 hal.fold_right(rs_evals[j], 0, rs_vec, transparents[j])
 
         ring_switch()
-        # ---- piop: merged message (host, as the reference merges: reversed order, bit-reversed indices), claims with their true sums
-        msg = np.zeros((1 << total_vars, 2), dtype=np.uint64)
-        idx = np.arange(n, dtype=np.int64)
-        rev = np.zeros_like(idx)
-        for b in range(v):
-            rev |= ((idx >> b) & 1) << (v - 1 - b)
-        at = 0
-        for s in reversed(committed):
-            x = hal.copy_d2h(s)
-            chunk = np.empty_like(x)
-            chunk[rev] = x
-            msg[at : at + n] = chunk
-            at += n
-        d_msg = alloc.alloc(1 << total_vars)
-        step = 1 << 22
-        for off in range(0, 1 << total_vars, step):
-            hal.copy_h2d(msg[off : off + step], d_msg.slice(off, min(1 << total_vars, off + step)))
-        del msg
+        # ---- piop: merged message (host, as the reference merges: reversed order, bit-reversed indices), claims with their true sums;
+        # --merge device: no message -- the commit merges the committed columns on the device, straight into the codeword
+        merge = getattr(args, "merge", "host")
+        rec["merge"] = merge
+        if merge == "host":
+            msg = np.zeros((1 << total_vars, 2), dtype=np.uint64)
+            idx = np.arange(n, dtype=np.int64)
+            rev = np.zeros_like(idx)
+            for b in range(v):
+                rev |= ((idx >> b) & 1) << (v - 1 - b)
+            at = 0
+            for s in reversed(committed):
+                x = hal.copy_d2h(s)
+                chunk = np.empty_like(x)
+                chunk[rev] = x
+                msg[at : at + n] = chunk
+                at += n
+            d_msg = alloc.alloc(1 << total_vars)
+            step = 1 << 22
+            for off in range(0, 1 << total_vars, step):
+                hal.copy_h2d(msg[off : off + step], d_msg.slice(off, min(1 << total_vars, off + step)))
+            del msg
         claims = [(v, i, j, hal.inner_product(committed[i], 7, transparents[j])) for i, j in claims_ct]
         pstream = synthetic.random_scalars(0x7A0 + v, 1 + total_vars)
         pbcs, pchs = pstream[:1], pstream[1:]
         scratch = alloc.alloc(4 * code_elems + ml_elems + (1 << 14))
-        pplan = PiopPlan(hal, [(v, s) for s in committed], [(v, s) for s in transparents], claims, p, d_msg, scratch, pbcs, pchs)
+        if merge == "host":
+            pplan = PiopPlan(hal, [(v, s) for s in committed], [(v, s) for s in transparents], claims, p, d_msg, scratch, pbcs, pchs)
+        else:
+            d_code, d_tree = (alloc.alloc(e) for e in piop_commit_elems(p))
+            pcommit = PiopCommit(hal, [(v, s) for s in committed], p, d_code, d_tree)
+            pplan = PiopCommittedPlan(hal, [(v, s) for s in committed], [(v, s) for s in transparents], claims, p, d_code, d_tree, scratch, pbcs, pchs)
 
         for it in range(args.steps + 1):
             profile = it == args.steps  # (the last pass under the event profiler: kernel time and launches; its wall time is not kept)
@@ -269,7 +280,11 @@ def replay(args, checker=None):
                 ring_switch()
             c0 = hal.group_counters()
             with phase(hal, tgt, "commit+piop_prove", profile):
-                commit_ms, prove_ms = pplan.run()
+                if merge == "host":
+                    commit_ms, prove_ms = pplan.run()
+                else:
+                    pcommit.run(phases=False)
+                    commit_ms, prove_ms = pcommit.total_ms, pplan.run()  # (both bracketed inside their calls, as PiopPlan's pair)
             c1 = hal.group_counters()
             if profile:
                 for k, r in tgt.items():
@@ -316,7 +331,7 @@ def replay(args, checker=None):
                 n_vars=v, committed=[hal.copy_d2h(s) for s in committed], transparents=[hal.copy_d2h(s) for s in transparents],
                 zerocheck_multilinears=[hal.copy_d2h(s) for s in zc], constraints=cons, degrees=degrees, zerocheck_sums=zsums, eq_ind_challenges=eqc, zerocheck_batch_coeff=zbc,
                 zerocheck_challenges=zch, zerocheck_transcript=(zco, zfin), claims=claims, fri_params=p, piop_batch_coeffs=pbcs, piop_challenges=pchs,
-                commitment=bytes(pplan.commitment), piop_transcript=items))
+                commitment=bytes(pplan.commitment) if merge == "host" else pcommit.commitment, piop_transcript=items))
     return rec
 
 
@@ -329,6 +344,8 @@ def main():
     ap.add_argument("--log-inv-rate", type=int, default=1)
     ap.add_argument("--log-batch", type=int, default=4)
     ap.add_argument("--arity", type=int, default=4)
+    ap.add_argument("--merge", choices=["host", "device"], default="host",
+                    help="host: numpy merge_multilins + upload + bnh_piop_prove (as every earlier record); device: bnh_piop_commit + bnh_piop_prove_committed")
     rec = replay(ap.parse_args())
     print(json.dumps(rec))
     sys.exit(0 if all(rec["verifier_check"].values()) else 1)
