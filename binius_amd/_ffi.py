@@ -87,6 +87,16 @@ class RsJob(C.Structure):
     _fields_ = [("d_query", C.c_void_p), ("n_vars", C.c_uint32), ("kappa", C.c_uint32), ("mixing_coeff", F128)]
 
 
+class FriOracle(C.Structure):
+    """bn_fri_oracle: one committed oracle of bn_fri_query_openings."""
+
+    _fields_ = [("d_codeword", C.c_void_p), ("d_nodes", C.c_void_p), ("log_n_cosets", C.c_uint32), ("log_coset_size", C.c_uint32),
+                ("layer_depth", C.c_uint32), ("index_shift", C.c_uint32)]
+
+
+FRI_QUERY_MAX_ORACLES = 32  # BN_FRI_QUERY_MAX_ORACLES
+
+
 class MePoint(C.Structure):
     """bn_me_point: one point of bn_mle_evaluate_batch, as the tensor expansions of its first lo_vars and its other hi_vars coordinates."""
 
@@ -206,6 +216,9 @@ def lib():
         "bn_mle_evaluate_counters": [vp, C.POINTER(u64)],
         "bn_merge_multilins": [vp, u32, C.POINTER(u32), C.POINTER(vp), vp, u32, u32],
         "bn_merge_counters": [vp, C.POINTER(u64)],
+        "bn_fri_query_proof_elems": [vp, u32, u64, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
+        "bn_fri_query_openings": [vp, vp, u32, vp, u64, C.POINTER(u64), u64, u32, vp, u64],
+        "bn_fri_query_counters": [vp, C.POINTER(u64)],
         "bn_log_chunks_range": [C.POINTER(MemMap), u32, C.POINTER(u32), C.POINTER(u32)],
         "bn_pick_log_chunks": [C.POINTER(MemMap), u32, C.POINTER(u32)],
         "bn_kernel_launch": [vp, C.POINTER(MemMap), u32, C.POINTER(KOp), u32, C.POINTER(u32), u32, u32, PF, vp],
@@ -265,7 +278,7 @@ ABI_SYMBOLS = [
     "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
     "bn_univariate_fold_batch", "bn_univariate_fold_counters", "bn_ring_switch_eq_ind_batch", "bn_ring_switch_counters",
     "bn_mle_evaluate_batch", "bn_mle_evaluate_counters", "bn_partial_eval_high_lincomb_batch", "bn_partial_eval_lincomb_counters",
-    "bn_merge_multilins", "bn_merge_counters",
+    "bn_merge_multilins", "bn_merge_counters", "bn_fri_query_proof_elems", "bn_fri_query_openings", "bn_fri_query_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -273,6 +286,21 @@ ABI_SYMBOLS = [
 def _check(rc):
     if rc != BN_OK:
         raise BnError(rc, lib().bn_last_error().decode())
+
+
+def fri_oracle_table(oracles):
+    """The bn_fri_oracle array of tuples (codeword, nodes, log_n_cosets, log_coset_size, layer_depth, index_shift); codeword and nodes
+    are DevSlices or None (bn_fri_query_proof_elems reads the sizes only)."""
+    return (FriOracle * max(1, len(oracles)))(*[FriOracle(o[0].ptr if o[0] is not None else None, o[1].ptr if o[1] is not None else None, o[2], o[3], o[4], o[5])
+                                                for o in oracles])
+
+
+def fri_query_proof_elems(oracles, terminate_elems, n_queries):
+    """bn_fri_query_proof_elems: (header, per-query record, total) of the block bn_fri_query_openings writes, in field elements.  Pure
+    host arithmetic: no context, no device."""
+    h, r, t = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(lib().bn_fri_query_proof_elems(C.cast(fri_oracle_table(oracles), C.c_void_p), len(oracles), terminate_elems, n_queries, C.byref(h), C.byref(r), C.byref(t)))
+    return h.value, r.value, t.value
 
 
 def device_numa_node(device=0):
@@ -1076,6 +1104,29 @@ class Context:
         c = (C.c_uint64 * 5)()
         _check(lib().bn_merge_counters(self._h, c))
         return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2]), "jobs_tiled": int(c[3]), "jobs_small": int(c[4])}
+
+    def fri_query_openings(self, oracles, terminate, indices, index_bits, out_elems=None):
+        """bn_fri_query_openings: the decommitment of FRIFolder::finish_proof (fri/prove.rs:483-507) in one launch.  oracles: tuples
+        (codeword DevSlice, node-array DevSlice, log_n_cosets, log_coset_size, layer_depth, index_shift); terminate: the DevSlice of the
+        terminate codeword; indices: the query indices, each below 2^index_bits.  Returns the (total, 2) uint64 block: terminate codeword,
+        one layer per oracle, then per query and oracle the coset and its branch.  out_elems: what the caller believes the total is
+        (default: bn_fri_query_proof_elems)."""
+        table = fri_oracle_table(oracles)
+        idx = np.ascontiguousarray(np.asarray(list(indices), dtype=np.uint64))
+        t_len = terminate.len if terminate is not None else 0
+        if out_elems is None:
+            out_elems = fri_query_proof_elems(oracles, t_len, len(idx))[2]
+        out = np.zeros((max(1, out_elems), 2), dtype=np.uint64)
+        _check(lib().bn_fri_query_openings(self._h, C.cast(table, C.c_void_p), len(oracles), terminate.ptr if terminate is not None else None, t_len,
+                                           idx.ctypes.data_as(C.POINTER(C.c_uint64)), len(idx), index_bits, out.ctypes.data, out_elems))
+        return out[:out_elems]
+
+    def fri_query_counters(self):
+        """bn_fri_query_counters: accepted bn_fri_query_openings calls, the kernel launches they made, the (query, oracle) openings they
+        served.  Rejected calls count nowhere."""
+        c = (C.c_uint64 * 3)()
+        _check(lib().bn_fri_query_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "openings": int(c[2])}
 
     # ---- accumulate_kernels / map_kernels
     def pick_log_chunks(self, mem_maps):

@@ -51,6 +51,17 @@ def host_lib():
             C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
             C.c_uint64, C.POINTER(F128), C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
         ]
+        L.bnh_fri_prove.restype = C.c_int
+        L.bnh_fri_prove.argtypes = [
+            C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+            C.c_uint64, C.POINTER(F128), C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
+        ]
+        L.bnh_fri_query_phase_bench.restype = C.c_int
+        L.bnh_fri_query_phase_bench.argtypes = [
+            C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+            C.c_uint64, C.POINTER(F128), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+            C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+        ]
         L.bnh_batch_sumcheck_prove.restype = C.c_int
         L.bnh_batch_sumcheck_prove.argtypes = [
             C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(F128), C.c_void_p, C.c_uint64,
@@ -79,6 +90,8 @@ def host_lib():
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, FP_, C.c_uint32, FP_, C.c_uint32, U32P_, C.c_uint32, U32P_, FP_, C.c_uint64, C.POINTER(C.c_uint64),
             C.c_void_p, C.c_uint32, U32P_, C.POINTER(C.c_double),
         ]
+        L.bnh_piop_prove_committed_open.restype = C.c_int
+        L.bnh_piop_prove_committed_open.argtypes = L.bnh_piop_prove_committed.argtypes + [C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.bnh_eqind_sumcheck_prove.restype = C.c_int
         L.bnh_eqind_sumcheck_prove.argtypes = [
             C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32),
@@ -276,6 +289,38 @@ class FRIParams:
     def n_final_challenges(self):
         return self.n_fold_rounds() - sum(self.fold_arities)
 
+    def log_len(self):
+        return self.rs_log_len() + self.log_batch_size
+
+    def index_bits(self):
+        return self.log_len() - self.fold_arities[0] if self.fold_arities else 0
+
+    def optimal_layer_depths(self):
+        """vcs_optimal_layers_depths_iter (common.rs:174-190) with optimal_verify_layer (merkle_tree/scheme.rs:47-49)"""
+        cap, log_n_cosets, out = max(0, self.n_test_queries - 1).bit_length(), self.log_len(), []
+        for arity in self.fold_arities:
+            log_n_cosets -= arity
+            out.append(min(cap, log_n_cosets))
+        return out
+
+    def query_oracles(self):
+        """(log_n_cosets, log_coset_size, layer_depth, index_shift) of every oracle a query opens, as bn_fri_oracle takes them"""
+        out, log_n_cosets, shift = [], self.log_len(), 0
+        for i, (arity, depth) in enumerate(zip(self.fold_arities, self.optimal_layer_depths())):
+            log_n_cosets -= arity
+            shift += arity if i else 0
+            out.append((log_n_cosets, arity, depth, shift))
+        return out
+
+    def terminate_elems(self):
+        return 1 << (self.log_inv_rate + self.n_final_challenges())
+
+    def advice_elems(self):
+        """(header, per-query record, total) of the decommitment of finish_proof in field elements (bn_fri_query_proof_elems)"""
+        from ._ffi import fri_query_proof_elems
+
+        return fri_query_proof_elems([(None, None) + o for o in self.query_oracles()], self.terminate_elems(), self.n_test_queries)
+
 
 class FriPlan:
     """FRI commit phase + every fold round + finalize through the compiled C++ mirror (bnh_fri_commit_fold,
@@ -300,6 +345,47 @@ class FriPlan:
         if rc != 0:
             raise BnError(rc, host_lib().bnh_last_error().decode())
         return self.phase_ms[0], self.phase_ms[1]
+
+
+class FriProvePlan(FriPlan):
+    """FriPlan with the query phase (bnh_fri_prove): FRIFolder::finish_proof in place of finalize.  query_indices: n_test_queries
+    indices below 2^index_bits, handed in like the challenges.  After run(), `advice` is the decommitment as a (total, 2) uint64 array
+    in transcript order and `terminate` its first terminate_elems rows; phase_ms: commit, fold, query phase."""
+
+    def __init__(self, hal, params, message, scratch, challenges, query_indices, max_advice_elems=None):
+        import numpy as np
+
+        FriPlan.__init__(self, hal, params, message, scratch, challenges)
+        self.indices = np.ascontiguousarray(np.asarray(list(query_indices), dtype=np.uint64))
+        self.max_advice = params.advice_elems()[2] if max_advice_elems is None else max_advice_elems
+        self._advice = np.zeros((max(1, self.max_advice), 2), dtype=np.uint64)
+        self.n_advice = C.c_uint64()
+        self.phase_ms = (C.c_double * 3)()
+
+    def run(self):
+        p = self.p
+        _host_check(host_lib().bnh_fri_prove(
+            self.hal._h, p.log_dim, p.log_inv_rate, p.log_batch_size, self.arities, len(p.fold_arities), p.n_test_queries, self.message.ptr,
+            self.scratch.ptr, self.scratch.len, self.ch, self.roots.ctypes.data, self.indices.ctypes.data_as(C.POINTER(C.c_uint64)),
+            self._advice.ctypes.data, self.max_advice, C.byref(self.n_advice), self.phase_ms))
+        self.advice = self._advice[: self.n_advice.value]
+        self.terminate = self.advice[: p.terminate_elems()]
+        return tuple(self.phase_ms)
+
+
+def fri_query_phase_bench(hal, params, message, scratch, challenges, query_indices, warmup, runs):
+    """bnh_fri_query_phase_bench: (new_ms[runs], old_ms[runs], advice elements, same bytes) -- FRIFolder::finish_proof against the
+    per-opening route on the same resident codewords and trees, alternating, wall clock between synchronisations."""
+    import numpy as np
+
+    ar = (C.c_uint32 * max(1, len(params.fold_arities)))(*params.fold_arities)
+    idx = np.ascontiguousarray(np.asarray(list(query_indices), dtype=np.uint64))
+    new_ms, old_ms = (C.c_double * max(1, runs))(), (C.c_double * max(1, runs))()
+    n_adv, same = C.c_uint64(), C.c_uint32()
+    _host_check(host_lib().bnh_fri_query_phase_bench(
+        hal._h, params.log_dim, params.log_inv_rate, params.log_batch_size, ar, len(params.fold_arities), params.n_test_queries, message.ptr, scratch.ptr,
+        scratch.len, _f128_array(list(challenges)), idx.ctypes.data_as(C.POINTER(C.c_uint64)), warmup, runs, new_ms, old_ms, C.byref(n_adv), C.byref(same)))
+    return list(new_ms)[:runs], list(old_ms)[:runs], n_adv.value, bool(same.value)
 
 
 class BatchSumcheckPlan:
@@ -485,6 +571,32 @@ class PiopCommittedPlan(PiopPlan):
             self.scratch.ptr, self.scratch.len, self.bcs, self.n_bcs, self.ch, self.n_ch, self.items, self.max_items,
             C.byref(self.n_items), self.scalars, self.max_scalars, C.byref(self.n_scalars), self.digests.ctypes.data, self.max_digests,
             C.byref(self.n_digests), self.phase_ms))
+        return self.phase_ms[0]
+
+
+class PiopCommittedOpenPlan(PiopCommittedPlan):
+    """PiopCommittedPlan with the FRI query phase (bnh_piop_prove_committed_open): the same transcript items, and `advice`, the
+    decommitment of FRIFolder::finish_proof for the given query indices, as a (total, 2) uint64 array."""
+
+    def __init__(self, hal, committed, transparents, claims, params, codeword, tree, scratch, batch_coeffs, challenges, query_indices, max_advice_elems=None):
+        import numpy as np
+
+        PiopCommittedPlan.__init__(self, hal, committed, transparents, claims, params, codeword, tree, scratch, batch_coeffs, challenges)
+        self.indices = np.ascontiguousarray(np.asarray(list(query_indices), dtype=np.uint64))
+        self.max_advice = params.advice_elems()[2] if max_advice_elems is None else max_advice_elems
+        self._advice = np.zeros((max(1, self.max_advice), 2), dtype=np.uint64)
+        self.n_advice = C.c_uint64()
+
+    def run(self):
+        p = self.p
+        _host_check(host_lib().bnh_piop_prove_committed_open(
+            self.hal._h, self.nc, self.c_nv, self.c_ptr, self.nt, self.t_nv, self.t_ptr, self.n_claims, self.claims, self.sums,
+            p.log_dim, p.log_inv_rate, p.log_batch_size, self.arities, len(p.fold_arities), p.n_test_queries, self.codeword.ptr, self.tree.ptr,
+            self.scratch.ptr, self.scratch.len, self.bcs, self.n_bcs, self.ch, self.n_ch, self.items, self.max_items,
+            C.byref(self.n_items), self.scalars, self.max_scalars, C.byref(self.n_scalars), self.digests.ctypes.data, self.max_digests,
+            C.byref(self.n_digests), self.phase_ms, self.indices.ctypes.data_as(C.POINTER(C.c_uint64)), self._advice.ctypes.data, self.max_advice,
+            C.byref(self.n_advice)))
+        self.advice = self._advice[: self.n_advice.value]
         return self.phase_ms[0]
 
 

@@ -86,6 +86,7 @@ struct bn_ctx {
 	uint64_t rs_calls = 0, rs_launches = 0, rs_jobs = 0, rs_queries = 0; // bn_ring_switch_eq_ind_batch (bn_ring_switch_counters)
 	uint64_t me_calls = 0, me_launches = 0, me_jobs = 0, me_max_share = 0; // bn_mle_evaluate_batch (bn_mle_evaluate_counters)
 	uint64_t mg_calls = 0, mg_launches = 0, mg_jobs = 0, mg_jobs_tiled = 0, mg_jobs_small = 0; // bn_merge_multilins (bn_merge_counters)
+	uint64_t fq_calls = 0, fq_launches = 0, fq_openings = 0; // bn_fri_query_openings (bn_fri_query_counters)
 	bn::f128 *h_me_rets = nullptr, *d_me_rets = nullptr; // pinned: the results of a bn_mle_evaluate_batch call, BN_ME_MAX_JOBS values (the sequence word stays in h_mail[64])
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -953,6 +954,30 @@ constexpr uint32_t kMergeLaunchUnits = 1u << 30; // workgroups of one launch
 // t: 5 or 6 (BN_MERGE_TILE_LOG2 in the shipped library)
 hipError_t launch_merge_multilins(hipStream_t s, uint32_t t, const merge_job *d_jobs, uint32_t n_jobs, void *d_message, uint32_t log_total, uint32_t log_repeats,
                                   uint32_t total_units);
+
+// ---- kernels_fri_query.hip: the decommitment of FRIFolder::finish_proof (fri/prove.rs:483-507) in one launch.  The output is, in
+// 16-byte units: the terminate codeword, one Merkle layer per oracle, then one record per query with, per oracle, the opened coset and
+// its branch.  The table of oracles travels in the kernel arguments; coset offsets and branch node ids are computed on the device.
+struct fri_query_oracle {
+	const void *codeword; // 2^(log_n_cosets + log_coset_size) elements
+	const void *nodes;    // the flattened tree over its cosets: leaves first, root last (bn_merkle_build)
+	uint32_t log_n_cosets, log_coset_size, layer_depth;
+	uint32_t shift;       // the coset index of query q is indices[q] >> shift
+	uint64_t layer_off;   // units from the start of the output to this oracle's layer
+	uint64_t record_off;  // units from the start of a query's record to this oracle's opening
+};
+constexpr uint32_t kFriQueryMaxOracles = 32;   // (= BN_FRI_QUERY_MAX_ORACLES)
+constexpr uint32_t kFriQueryHeaderChunk = 2048; // units of the header a workgroup copies: eight per thread
+struct fri_query_args {
+	fri_query_oracle o[kFriQueryMaxOracles];
+	const void *terminate;
+	uint64_t terminate_elems, header_elems, record_elems;
+	uint32_t n_oracles, n_queries;
+	uint32_t header_wgs; // workgroups [0, header_wgs) copy the header, the others serve four openings each
+	uint32_t pad_;
+};
+// d_indices: n_queries indices, readable by the device; out: header_elems + n_queries * record_elems units
+hipError_t launch_fri_query(hipStream_t s, const fri_query_args &a, const uint64_t *d_indices, void *out);
 
 // ---- kernels_ntt_tiled.hip
 hipError_t launch_build_mul8(hipStream_t s, uint8_t *d_tab);

@@ -10,6 +10,7 @@
 //                                          crates/core/src/protocols/fri/prove.rs:219-482
 //   FRIQueryProver (prove_query, vcs_optimal_layers), prove_coset_opening
 //                                          crates/core/src/protocols/fri/prove.rs:523-661
+//   FRIFolder::finish_proof                crates/core/src/protocols/fri/prove.rs:483-507
 // with F = BinaryField128b, FA = BinaryField32b (crates/core/src/constraint_system/common.rs:22).
 // The reference keeps a host copy of every codeword because its Merkle prover hashes host slices
 // (prove.rs:396-399); here nothing but roots, layers, branches and opened cosets is read back.
@@ -153,6 +154,14 @@ struct CosetOpening { // what prove_coset_opening writes to the transcript (prov
 	std::vector<Digest> branch;
 };
 
+// The decommitment of finish_proof (prove.rs:483-507) in transcript order: the terminate codeword, one layer per opened oracle, then
+// one record per query (per oracle the coset and its branch).  A digest is two elements.
+struct FriAdvice {
+	std::vector<B128> block;
+	size_t terminate_elems = 0;
+	std::vector<B128> terminate_codeword() const { return std::vector<B128>(block.begin(), block.begin() + (long)terminate_elems); }
+};
+
 // prove.rs:523-628
 class FRIQueryProver {
 public:
@@ -182,6 +191,35 @@ public:
 			index >>= arities[i + 1];
 			out.push_back(open(round_committed_[i].first, round_committed_[i].second, index, arities[i + 1], depths[i + 1]));
 		}
+		return out;
+	}
+	// Every query of a proof at once (bn_fri_query_openings: one launch, one synchronisation): what vcs_optimal_layers and one
+	// prove_query per index write, behind `terminate` (the last oracle, on the device; empty: no terminate codeword in the block).
+	// The indices are handed in like every challenge: the decommitment is not observed, so they can all be sampled first.
+	FriAdvice prove_queries(const std::vector<size_t> &indices, FSlice terminate = FSlice{}) const
+	{
+		const auto &arities = p_.fold_arities();
+		const auto depths = p_.optimal_layer_depths();
+		std::vector<bn_fri_oracle> table;
+		size_t log_n_cosets = p_.log_len(), shift = 0;
+		for (size_t i = 0; i < arities.size() && i <= round_committed_.size(); i++) {
+			log_n_cosets -= arities[i];
+			if (i) shift += arities[i];
+			const FSlice codeword = i == 0 ? codeword_ : round_committed_[i - 1].first;
+			const BinaryMerkleTree &tree = i == 0 ? committed_ : round_committed_[i - 1].second;
+			if (tree.log_len != log_n_cosets || codeword.len() < (size_t)1 << (log_n_cosets + arities[i]))
+				throw FriError("InvalidArgs(a committed oracle does not have the shape the FRI parameters give it)");
+			table.push_back(bn_fri_oracle{codeword.ptr, tree.nodes.ptr, (uint32_t)log_n_cosets, (uint32_t)arities[i], (uint32_t)depths[i], (uint32_t)shift});
+		}
+		const std::vector<uint64_t> idx(indices.begin(), indices.end());
+		FriAdvice out;
+		out.terminate_elems = terminate.len();
+		uint64_t header = 0, record = 0, total = 0;
+		check(bn_fri_query_proof_elems(table.data(), (uint32_t)table.size(), terminate.len(), idx.size(), &header, &record, &total));
+		out.block.resize(total);
+		static_assert(sizeof(B128) == sizeof(bn_f128), "a field element is one bn_f128");
+		check(bn_fri_query_openings(hal_.raw_ctx(), table.data(), (uint32_t)table.size(), terminate.ptr, terminate.len(), idx.data(), idx.size(),
+		                            (uint32_t)p_.index_bits(), reinterpret_cast<bn_f128 *>(out.block.data()), total));
 		return out;
 	}
 
@@ -262,6 +300,17 @@ public:
 		std::vector<B128> terminate(last.len());
 		hal_.copy_d2h(last, terminate);
 		return {std::move(terminate), FRIQueryProver(hal_, p_, merkle_prover_, codeword_, committed_, round_committed_)};
+	}
+
+	// finish_proof (prove.rs:483-507) with the sampled indices handed in: finalize + vcs_optimal_layers + every prove_query, all of it
+	// through one launch -- the terminate codeword comes out of the same block instead of a copy of its own.
+	FriAdvice finish_proof(const std::vector<size_t> &indices)
+	{
+		if (curr_round_ != n_rounds()) throw FriError("EarlyProverFinish");
+		if (indices.size() != p_.n_test_queries())
+			throw FriError("InvalidArgs(got " + std::to_string(indices.size()) + " query indices, expected " + std::to_string(p_.n_test_queries()) + ")");
+		const FSlice last = round_committed_.empty() ? codeword_ : round_committed_.back().first;
+		return FRIQueryProver(hal_, p_, merkle_prover_, codeword_, committed_, round_committed_).prove_queries(indices, last);
 	}
 
 private:

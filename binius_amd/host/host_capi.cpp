@@ -652,6 +652,121 @@ int bnh_fri_commit_fold(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, ui
 	});
 }
 
+// bnh_fri_commit_fold with FRIFolder::finish_proof in place of finalize: the whole decommitment (terminate codeword, layers, every
+// query's openings) from one launch.
+//   query_indices    [n_test_queries], each below 2^index_bits
+//   advice_out       [max_advice_elems]; *n_advice_elems_out: the elements written
+//   phase_ms_out     [3] commit, fold, query phase, or NULL
+int bnh_fri_prove(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities,
+                  uint32_t n_test_queries, const void *d_message, void *d_scratch, uint64_t scratch_elems, const bn_f128 *challenges, uint8_t *roots_out,
+                  const uint64_t *query_indices, bn_f128 *advice_out, uint64_t max_advice_elems, uint64_t *n_advice_elems_out, double *phase_ms_out)
+{
+	return guarded([&]() -> int {
+		if (!ctx || !d_message || !d_scratch || !challenges || !roots_out || !advice_out || !n_advice_elems_out || (n_arities && !fold_arities) ||
+		    (n_test_queries && !query_indices))
+			throw Error(Error::InputValidation, "null argument");
+		if ((uint64_t)log_dim + log_batch_size + log_inv_rate >= 48) throw Error(Error::InputValidation, "FRI parameters out of range");
+		ComputeLayer hal(ctx);
+		DeviceBumpAllocator dev_alloc(FSliceMut{d_scratch, (size_t)scratch_elems});
+		FRIParams p(log_dim, log_inv_rate, log_batch_size, std::vector<size_t>(fold_arities, fold_arities + n_arities), n_test_queries);
+		AdditiveNTT ntt(hal, 5, p.rs_log_len());
+		BinaryMerkleTreeProver merkle(hal);
+		hal.sync();
+		const auto t0 = std::chrono::steady_clock::now();
+		CommitOutput out = commit_interleaved(hal, dev_alloc, p, ntt, merkle, FSlice{d_message, (size_t)1 << (log_dim + log_batch_size)});
+		hal.sync();
+		const auto t1 = std::chrono::steady_clock::now();
+		std::memcpy(roots_out, out.commitment.data(), 32);
+		FRIFolder folder(hal, p, ntt, merkle, ComputeMemory::as_const(out.codeword), out.committed);
+		size_t n_roots = 1;
+		for (size_t r = 0; r < folder.n_rounds(); r++) {
+			auto [has_root, root] = folder.execute_fold_round(dev_alloc, from_raw(challenges[r]));
+			if (has_root) std::memcpy(roots_out + 32 * n_roots++, root.data(), 32);
+		}
+		hal.sync();
+		const auto t2 = std::chrono::steady_clock::now();
+		const FriAdvice advice = folder.finish_proof(std::vector<size_t>(query_indices, query_indices + n_test_queries));
+		const auto t3 = std::chrono::steady_clock::now(); // (finish_proof returns after its synchronisation)
+		if (advice.block.size() > max_advice_elems) throw Error(Error::InputValidation, "the advice has more elements than advice_out holds");
+		to_raw(advice.block, advice_out);
+		*n_advice_elems_out = advice.block.size();
+		if (phase_ms_out) {
+			phase_ms_out[0] = elapsed_ms(t0, t1);
+			phase_ms_out[1] = elapsed_ms(t1, t2);
+			phase_ms_out[2] = elapsed_ms(t2, t3);
+		}
+		return 0;
+	});
+}
+
+// diagnostic: the query phase timed two ways on the same resident codewords and trees (tools/bench_fri_query.py).  One commit and
+// fold, then warmup + runs times, alternating: FRIFolder::finish_proof (one launch), and the per-opening route -- finalize's copy of
+// the terminate codeword and one FRIQueryProver::prove_query per index (a copy_d2h and a bn_gather_d2h per opening; the layers are not
+// part of it).  Wall clock between two synchronisations each.  *equal_out: the per-opening route (with the layers, fetched outside the
+// timed window) returned the bytes of the advice.
+int bnh_fri_query_phase_bench(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities,
+                              uint32_t n_test_queries, const void *d_message, void *d_scratch, uint64_t scratch_elems, const bn_f128 *challenges,
+                              const uint64_t *query_indices, uint32_t warmup, uint32_t runs, double *new_ms_out, double *old_ms_out, uint64_t *advice_elems_out,
+                              uint32_t *equal_out)
+{
+	return guarded([&]() -> int {
+		if (!ctx || !d_message || !d_scratch || !challenges || !new_ms_out || !old_ms_out || !advice_elems_out || !equal_out || (n_arities && !fold_arities) ||
+		    (n_test_queries && !query_indices))
+			throw Error(Error::InputValidation, "null argument");
+		if ((uint64_t)log_dim + log_batch_size + log_inv_rate >= 48) throw Error(Error::InputValidation, "FRI parameters out of range");
+		ComputeLayer hal(ctx);
+		DeviceBumpAllocator dev_alloc(FSliceMut{d_scratch, (size_t)scratch_elems});
+		FRIParams p(log_dim, log_inv_rate, log_batch_size, std::vector<size_t>(fold_arities, fold_arities + n_arities), n_test_queries);
+		AdditiveNTT ntt(hal, 5, p.rs_log_len());
+		BinaryMerkleTreeProver merkle(hal);
+		CommitOutput out = commit_interleaved(hal, dev_alloc, p, ntt, merkle, FSlice{d_message, (size_t)1 << (log_dim + log_batch_size)});
+		FRIFolder folder(hal, p, ntt, merkle, ComputeMemory::as_const(out.codeword), out.committed);
+		for (size_t r = 0; r < folder.n_rounds(); r++) folder.execute_fold_round(dev_alloc, from_raw(challenges[r]));
+		const std::vector<size_t> indices(query_indices, query_indices + n_test_queries);
+		FriAdvice advice;
+		std::vector<B128> terminate;
+		std::vector<std::vector<CosetOpening>> openings;
+		for (uint32_t it = 0; it < warmup + runs; it++) {
+			hal.sync();
+			const auto t0 = std::chrono::steady_clock::now();
+			advice = folder.finish_proof(indices);
+			hal.sync();
+			const auto t1 = std::chrono::steady_clock::now();
+			openings.clear();
+			auto fin = folder.finalize();
+			for (size_t index : indices) openings.push_back(fin.second.prove_query(index));
+			hal.sync();
+			const auto t2 = std::chrono::steady_clock::now();
+			terminate = std::move(fin.first);
+			if (it >= warmup) {
+				new_ms_out[it - warmup] = elapsed_ms(t0, t1);
+				old_ms_out[it - warmup] = elapsed_ms(t1, t2);
+			}
+		}
+		// the same bytes?
+		std::vector<B128> flat = terminate;
+		auto fin = folder.finalize();
+		for (const auto &layer : fin.second.vcs_optimal_layers())
+			for (const Digest &d : layer) {
+				B128 two[2];
+				std::memcpy(two, d.data(), 32);
+				flat.insert(flat.end(), two, two + 2);
+			}
+		for (const auto &query : openings)
+			for (const CosetOpening &o : query) {
+				flat.insert(flat.end(), o.values.begin(), o.values.end());
+				for (const Digest &d : o.branch) {
+					B128 two[2];
+					std::memcpy(two, d.data(), 32);
+					flat.insert(flat.end(), two, two + 2);
+				}
+			}
+		*advice_elems_out = advice.block.size();
+		*equal_out = runs + warmup > 0 && flat.size() == advice.block.size() && std::memcmp(flat.data(), advice.block.data(), flat.size() * sizeof(B128)) == 0;
+		return 0;
+	});
+}
+
 // piop::prove (crates/core/src/piop/prove.rs:148-395) through the C++ mirror piop.hpp: commit_interleaved of the merged message
 // (bnh_piop_prove) or the codeword and tree of an earlier bnh_piop_commit (bnh_piop_prove_committed), then
 // one BivariateSumcheckProver per number of variables, the front-loaded batch prover interleaved with the FRI folder.
@@ -663,12 +778,20 @@ namespace {
 // first two time stamps and returns them: bnh_piop_prove commits the message there, bnh_piop_prove_committed wraps the caller's buffers.
 // phase_ms[2]: that step, the prove.
 using PiopCommitStep = std::function<std::pair<FSlice, BinaryMerkleTree>(ComputeLayer &, DeviceBumpAllocator &, const FRIParams &, const AdditiveNTT &, BinaryMerkleTreeProver &)>;
+// The FRI query phase of an entry point that has one (bnh_piop_prove_committed_open): the indices in, the advice out
+struct PiopQueryPhase {
+	const uint64_t *query_indices;
+	bn_f128 *advice_out;
+	uint64_t max_advice_elems;
+	uint64_t *n_advice_elems_out;
+};
 static int piop_prove_body(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
                     const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims, const bn_f128 *claim_sums,
                     uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities, uint32_t n_test_queries,
                     const PiopCommitStep &commit, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, uint32_t n_batch_coeffs,
                     const bn_f128 *challenges, uint32_t n_challenges, uint32_t *items_out, uint32_t max_items, uint32_t *n_items_out, bn_f128 *scalars_out,
-                    uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out, uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms)
+                    uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out, uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms,
+                    const PiopQueryPhase *query = nullptr)
 {
 	{
 		if (!ctx || !items_out || !n_items_out || !scalars_out || !n_scalars_out || !digests_out || !n_digests_out)
@@ -676,6 +799,7 @@ static int piop_prove_body(bn_ctx *ctx, uint32_t n_committed, const uint32_t *co
 		if ((n_committed && (!committed_n_vars || !d_committed)) || (n_transparent && (!transparent_n_vars || !d_transparent)) || (n_claims && (!claims || !claim_sums)) ||
 		    (n_arities && !fold_arities) || (n_batch_coeffs && !batch_coeffs) || (n_challenges && !challenges))
 			throw Error(Error::InputValidation, "null argument");
+		if (query && (!query->advice_out || !query->n_advice_elems_out || (n_test_queries && !query->query_indices))) throw Error(Error::InputValidation, "null argument");
 		for (uint32_t i = 0; i < n_committed; i++)
 			if (committed_n_vars[i] >= 48 || !d_committed[i]) throw Error(Error::InputValidation, "committed multilinear: null, or its number of variables out of range (< 48)");
 		for (uint32_t i = 0; i < n_transparent; i++)
@@ -713,7 +837,10 @@ static int piop_prove_body(bn_ctx *ctx, uint32_t n_committed, const uint32_t *co
 		hal.sync();
 		const auto t1 = std::chrono::steady_clock::now();
 		if (AbiProf::on()) AbiProf::get() = AbiProf{};
-		PiopProveOutput out = piop_prove(hal, dev_alloc, host_alloc, p, ntt, merkle, commit_meta, co.second, co.first, committed, transparents, cl, bcs, chs);
+		std::vector<size_t> query_indices;
+		if (query) query_indices.assign(query->query_indices, query->query_indices + n_test_queries);
+		PiopProveOutput out = piop_prove_impl(hal, dev_alloc, host_alloc, p, ntt, merkle, commit_meta, co.second, co.first, committed, transparents, cl, bcs, chs,
+		                                      query ? &query_indices : nullptr);
 		hal.sync();
 		const auto t2 = std::chrono::steady_clock::now();
 		if (AbiProf::on()) {
@@ -737,6 +864,11 @@ static int piop_prove_body(bn_ctx *ctx, uint32_t n_committed, const uint32_t *co
 				items_out[2 * ni + 1] = (uint32_t)it.scalars.size();
 			}
 			ni++;
+		}
+		if (query) {
+			if (out.advice.size() > query->max_advice_elems) throw Error(Error::InputValidation, "the advice has more elements than advice_out holds");
+			to_raw(out.advice, query->advice_out);
+			*query->n_advice_elems_out = out.advice.size();
 		}
 		*n_items_out = ni;
 		*n_scalars_out = ns;
@@ -792,13 +924,13 @@ int bnh_piop_prove(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_
 
 // piop::prove from a commitment made earlier (bnh_piop_commit): the arguments of bnh_piop_prove, with the codeword and the flattened
 // tree that call left in the caller's buffers in place of the message.  Only reads them; never commits.  phase_ms_out[1]: the prove.
-int bnh_piop_prove_committed(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
+static int piop_prove_committed_body(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
                              const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims,
                              const bn_f128 *claim_sums, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities,
                              uint32_t n_arities, uint32_t n_test_queries, const void *d_codeword, const void *d_tree, void *d_scratch, uint64_t scratch_elems,
                              const bn_f128 *batch_coeffs, uint32_t n_batch_coeffs, const bn_f128 *challenges, uint32_t n_challenges, uint32_t *items_out,
                              uint32_t max_items, uint32_t *n_items_out, bn_f128 *scalars_out, uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out,
-                             uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms_out)
+                             uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms_out, const PiopQueryPhase *query)
 {
 	return guarded([&]() -> int {
 		if (!d_codeword || !d_tree || (n_arities && !fold_arities)) throw Error(Error::InputValidation, "null argument");
@@ -813,10 +945,41 @@ int bnh_piop_prove_committed(bn_ctx *ctx, uint32_t n_committed, const uint32_t *
 		const int rc = piop_prove_body(ctx, n_committed, committed_n_vars, d_committed, n_transparent, transparent_n_vars, d_transparent, n_claims, claims, claim_sums,
 		                               log_dim, log_inv_rate, log_batch_size, fold_arities, n_arities, n_test_queries, commit, d_scratch, scratch_elems, batch_coeffs,
 		                               n_batch_coeffs, challenges, n_challenges, items_out, max_items, n_items_out, scalars_out, max_scalars, n_scalars_out, digests_out,
-		                               max_digests, n_digests_out, ms);
+		                               max_digests, n_digests_out, ms, query);
 		if (phase_ms_out) phase_ms_out[0] = ms[1];
 		return rc;
 	});
+}
+
+int bnh_piop_prove_committed(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
+                             const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims,
+                             const bn_f128 *claim_sums, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities,
+                             uint32_t n_arities, uint32_t n_test_queries, const void *d_codeword, const void *d_tree, void *d_scratch, uint64_t scratch_elems,
+                             const bn_f128 *batch_coeffs, uint32_t n_batch_coeffs, const bn_f128 *challenges, uint32_t n_challenges, uint32_t *items_out,
+                             uint32_t max_items, uint32_t *n_items_out, bn_f128 *scalars_out, uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out,
+                             uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms_out)
+{
+	return piop_prove_committed_body(ctx, n_committed, committed_n_vars, d_committed, n_transparent, transparent_n_vars, d_transparent, n_claims, claims, claim_sums, log_dim,
+	                                 log_inv_rate, log_batch_size, fold_arities, n_arities, n_test_queries, d_codeword, d_tree, d_scratch, scratch_elems, batch_coeffs,
+	                                 n_batch_coeffs, challenges, n_challenges, items_out, max_items, n_items_out, scalars_out, max_scalars, n_scalars_out, digests_out,
+	                                 max_digests, n_digests_out, phase_ms_out, nullptr);
+}
+
+// bnh_piop_prove_committed with the FRI query phase: the same item list, the decommitment of finish_proof in advice_out
+int bnh_piop_prove_committed_open(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
+                             const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims,
+                             const bn_f128 *claim_sums, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities,
+                             uint32_t n_arities, uint32_t n_test_queries, const void *d_codeword, const void *d_tree, void *d_scratch, uint64_t scratch_elems,
+                             const bn_f128 *batch_coeffs, uint32_t n_batch_coeffs, const bn_f128 *challenges, uint32_t n_challenges, uint32_t *items_out,
+                             uint32_t max_items, uint32_t *n_items_out, bn_f128 *scalars_out, uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out,
+                             uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms_out, const uint64_t *query_indices, bn_f128 *advice_out,
+                             uint64_t max_advice_elems, uint64_t *n_advice_elems_out)
+{
+	const PiopQueryPhase query{query_indices, advice_out, max_advice_elems, n_advice_elems_out};
+	return piop_prove_committed_body(ctx, n_committed, committed_n_vars, d_committed, n_transparent, transparent_n_vars, d_transparent, n_claims, claims, claim_sums, log_dim,
+	                                 log_inv_rate, log_batch_size, fold_arities, n_arities, n_test_queries, d_codeword, d_tree, d_scratch, scratch_elems, batch_coeffs,
+	                                 n_batch_coeffs, challenges, n_challenges, items_out, max_items, n_items_out, scalars_out, max_scalars, n_scalars_out, digests_out,
+	                                 max_digests, n_digests_out, phase_ms_out, &query);
 }
 
 static thread_local double g_piop_commit_ms = 0;

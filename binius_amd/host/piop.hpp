@@ -148,16 +148,19 @@ struct PiopProveOutput {
 	PiopTranscript transcript;
 	std::vector<std::vector<B128>> multilinear_evals; // per prover, in finishing order
 	std::vector<B128> terminate_codeword;
+	std::vector<B128> advice; // the overloads that take query indices: the decommitment of FRIFolder::finish_proof (FriAdvice::block)
 	size_t n_provers = 0;
 	uint64_t phase_ns[3] = {0, 0, 0}; // BNH_PROF=1: send_round_proof, receive_challenge, execute_fold_round over all rounds
 };
 
-// prove_interleaved_fri_sumcheck (piop/prove.rs:306-395); `challenges[round]` is what transcript.sample() would have returned
-inline PiopProveOutput prove_interleaved_fri_sumcheck(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, size_t n_rounds, const FRIParams &fri_params,
-                                                      const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover,
-                                                      std::vector<std::unique_ptr<BivariateSumcheckProver>> sumcheck_provers,
-                                                      const std::vector<B128> &batch_coeffs, FSlice codeword, const BinaryMerkleTree &committed,
-                                                      const std::vector<B128> &challenges)
+// prove_interleaved_fri_sumcheck (piop/prove.rs:306-395); `challenges[round]` is what transcript.sample() would have returned.
+// query_indices: null -- the proof ends at the terminate codeword (finalize); else the n_test_queries indices transcript.sample_bits
+// would have returned -- fri_prover.finish_proof runs whole and its decommitment comes back in `advice`.
+inline PiopProveOutput prove_interleaved_fri_sumcheck_impl(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, size_t n_rounds, const FRIParams &fri_params,
+                                                           const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover,
+                                                           std::vector<std::unique_ptr<BivariateSumcheckProver>> sumcheck_provers,
+                                                           const std::vector<B128> &batch_coeffs, FSlice codeword, const BinaryMerkleTree &committed,
+                                                           const std::vector<B128> &challenges, const std::vector<size_t> *query_indices)
 {
 	if (challenges.size() < n_rounds) throw PiopError("not enough challenges for the rounds of the protocol");
 	PiopProveOutput out;
@@ -194,12 +197,36 @@ inline PiopProveOutput prove_interleaved_fri_sumcheck(ComputeLayer &hal, DeviceB
 	}
 	out.multilinear_evals = sumcheck_batch_prover.finish();
 	write_finished();
-	// fri_prover.finish_proof (fri/prove.rs:484-520): the terminate codeword goes to the transcript; the query phase (index sampling,
-	// openings) is the query prover's and is covered by tests/test_gpu_fri.py
-	auto fin = fri_prover.finalize();
-	out.terminate_codeword = fin.first;
+	// fri_prover.finish_proof (fri/prove.rs:483-507): the terminate codeword goes to the transcript; with query indices the layers and
+	// the openings follow it in the advice, all from one launch, and the transcript item is filled from the same block
+	if (query_indices) {
+		FriAdvice advice = fri_prover.finish_proof(*query_indices);
+		out.terminate_codeword = advice.terminate_codeword();
+		out.advice = std::move(advice.block);
+	} else {
+		auto fin = fri_prover.finalize();
+		out.terminate_codeword = fin.first;
+	}
 	out.transcript.write_scalar_slice(PiopTranscript::Item::FriTerminate, out.terminate_codeword);
 	return out;
+}
+inline PiopProveOutput prove_interleaved_fri_sumcheck(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, size_t n_rounds, const FRIParams &fri_params,
+                                                      const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover,
+                                                      std::vector<std::unique_ptr<BivariateSumcheckProver>> sumcheck_provers,
+                                                      const std::vector<B128> &batch_coeffs, FSlice codeword, const BinaryMerkleTree &committed,
+                                                      const std::vector<B128> &challenges)
+{
+	return prove_interleaved_fri_sumcheck_impl(hal, dev_alloc, n_rounds, fri_params, ntt, merkle_prover, std::move(sumcheck_provers), batch_coeffs, codeword, committed,
+	                                           challenges, nullptr);
+}
+inline PiopProveOutput prove_interleaved_fri_sumcheck(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, size_t n_rounds, const FRIParams &fri_params,
+                                                      const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover,
+                                                      std::vector<std::unique_ptr<BivariateSumcheckProver>> sumcheck_provers,
+                                                      const std::vector<B128> &batch_coeffs, FSlice codeword, const BinaryMerkleTree &committed,
+                                                      const std::vector<B128> &challenges, const std::vector<size_t> &query_indices)
+{
+	return prove_interleaved_fri_sumcheck_impl(hal, dev_alloc, n_rounds, fri_params, ntt, merkle_prover, std::move(sumcheck_provers), batch_coeffs, codeword, committed,
+	                                           challenges, &query_indices);
 }
 
 // prove (piop/prove.rs:148-303) from the point where the committed multilinears are on the device: the sumcheck claim descriptions,
@@ -208,10 +235,12 @@ inline PiopProveOutput prove_interleaved_fri_sumcheck(ComputeLayer &hal, DeviceB
 //   committed       device slices of the packed committed multilinears, ascending by number of variables (commit order)
 //   transparents    device slices, ascending by number of variables
 //   batch_coeffs    one per prover (transcript.sample_vec(provers.len()), front_loaded.rs:63-68)
-inline PiopProveOutput piop_prove(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, const FRIParams &fri_params,
-                                  const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover, const CommitMeta &commit_meta, const BinaryMerkleTree &committed,
-                                  FSlice codeword, const std::vector<FSlice> &committed_multilins, const std::vector<FSlice> &transparent_multilins,
-                                  const std::vector<PIOPSumcheckClaim> &claims, const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges)
+//   query_indices   null, or the indices of the FRI query phase (prove_interleaved_fri_sumcheck_impl)
+inline PiopProveOutput piop_prove_impl(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, const FRIParams &fri_params,
+                                       const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover, const CommitMeta &commit_meta, const BinaryMerkleTree &committed,
+                                       FSlice codeword, const std::vector<FSlice> &committed_multilins, const std::vector<FSlice> &transparent_multilins,
+                                       const std::vector<PIOPSumcheckClaim> &claims, const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges,
+                                       const std::vector<size_t> *query_indices)
 {
 	if (committed_multilins.size() != commit_meta.total_multilins()) throw PiopError("committed multilinears do not match the commit metadata");
 	std::vector<size_t> transparent_n_vars;
@@ -232,8 +261,26 @@ inline PiopProveOutput piop_prove(ComputeLayer &hal, DeviceBumpAllocator &dev_al
 		provers.push_back(std::make_unique<BivariateSumcheckProver>(hal, dev_alloc, host_alloc, n_vars, d.compositions, d.sums, multilins));
 	}
 	if (batch_coeffs.size() != provers.size()) throw PiopError("one batch coefficient per sumcheck prover: " + std::to_string(provers.size()) + " expected");
-	return prove_interleaved_fri_sumcheck(hal, dev_alloc, commit_meta.total_vars(), fri_params, ntt, merkle_prover, std::move(provers), batch_coeffs, codeword,
-	                                      committed, challenges);
+	return prove_interleaved_fri_sumcheck_impl(hal, dev_alloc, commit_meta.total_vars(), fri_params, ntt, merkle_prover, std::move(provers), batch_coeffs, codeword,
+	                                           committed, challenges, query_indices);
+}
+inline PiopProveOutput piop_prove(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, const FRIParams &fri_params,
+                                  const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover, const CommitMeta &commit_meta, const BinaryMerkleTree &committed,
+                                  FSlice codeword, const std::vector<FSlice> &committed_multilins, const std::vector<FSlice> &transparent_multilins,
+                                  const std::vector<PIOPSumcheckClaim> &claims, const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges)
+{
+	return piop_prove_impl(hal, dev_alloc, host_alloc, fri_params, ntt, merkle_prover, commit_meta, committed, codeword, committed_multilins, transparent_multilins, claims,
+	                       batch_coeffs, challenges, nullptr);
+}
+// the same with the FRI query phase: PiopProveOutput::advice holds the decommitment
+inline PiopProveOutput piop_prove(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, const FRIParams &fri_params,
+                                  const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover, const CommitMeta &commit_meta, const BinaryMerkleTree &committed,
+                                  FSlice codeword, const std::vector<FSlice> &committed_multilins, const std::vector<FSlice> &transparent_multilins,
+                                  const std::vector<PIOPSumcheckClaim> &claims, const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges,
+                                  const std::vector<size_t> &query_indices)
+{
+	return piop_prove_impl(hal, dev_alloc, host_alloc, fri_params, ntt, merkle_prover, commit_meta, committed, codeword, committed_multilins, transparent_multilins, claims,
+	                       batch_coeffs, challenges, &query_indices);
 }
 
 } // namespace binius_amd

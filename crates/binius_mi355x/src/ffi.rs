@@ -134,6 +134,11 @@ pub const BN_MERGE_JOBS: usize = 2;
 pub const BN_MERGE_JOBS_TILED: usize = 3;
 pub const BN_MERGE_JOBS_SMALL: usize = 4;
 pub const BN_MERGE_TILE_LOG2: u32 = 6;
+pub const BN_FQ_N: usize = 3;
+pub const BN_FQ_CALLS: usize = 0;
+pub const BN_FQ_LAUNCHES: usize = 1;
+pub const BN_FQ_OPENINGS: usize = 2;
+pub const BN_FRI_QUERY_MAX_ORACLES: u32 = 32;
 pub const BN_UNIVARIATE_FOLD_MAX_SKIP: u32 = 8;
 pub const BN_EXP_STATIC: u32 = 0;
 pub const BN_EXP_DYNAMIC: u32 = 1;
@@ -145,6 +150,18 @@ pub const BN_ORDER_LOW_TO_HIGH: u32 = 0;
 pub const BN_ORDER_HIGH_TO_LOW: u32 = 1;
 pub const BN_HAL_ML_FOLDED: u32 = 0;
 pub const BN_HAL_ML_TRANSPARENT: u32 = 1;
+
+/// One committed oracle of bn_fri_query_openings: the codeword, the flattened Merkle tree over its cosets, and where a query lands in it.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bn_fri_oracle {
+	pub d_codeword: *const c_void,
+	pub d_nodes: *const c_void,
+	pub log_n_cosets: u32,
+	pub log_coset_size: u32,
+	pub layer_depth: u32,
+	pub index_shift: u32,
+}
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -424,6 +441,28 @@ unsafe extern "C" {
 		log_repeats: u32,
 	) -> c_int;
 	pub fn bn_merge_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_fri_query_proof_elems(
+		oracles: *const c_void,
+		n_oracles: u32,
+		terminate_elems: u64,
+		n_queries: u64,
+		header_elems_out: *mut u64,
+		record_elems_out: *mut u64,
+		total_elems_out: *mut u64,
+	) -> c_int;
+	pub fn bn_fri_query_openings(
+		ctx: *mut bn_ctx,
+		oracles: *const c_void,
+		n_oracles: u32,
+		d_terminate: *const c_void,
+		terminate_elems: u64,
+		indices: *const u64,
+		n_queries: u64,
+		index_bits: u32,
+		h_out: *mut bn_f128,
+		out_elems: u64,
+	) -> c_int;
+	pub fn bn_fri_query_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 
 	pub fn bn_log_chunks_range(maps: *const bn_memmap, n_maps: u32, start: *mut u32, end: *mut u32) -> c_int;
 	pub fn bn_pick_log_chunks(maps: *const bn_memmap, n_maps: u32, log_chunks: *mut u32) -> c_int;

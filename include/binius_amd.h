@@ -403,6 +403,47 @@ int bn_merge_multilins(bn_ctx *ctx, uint32_t n, const uint32_t *n_vars, const vo
  * nowhere. */
 enum { BN_MERGE_CALLS = 0, BN_MERGE_LAUNCHES = 1, BN_MERGE_JOBS = 2, BN_MERGE_JOBS_TILED = 3, BN_MERGE_JOBS_SMALL = 4, BN_MERGE_N = 5 };
 int bn_merge_counters(bn_ctx *ctx, uint64_t *counters /*[BN_MERGE_N]*/);
+/* The FRI query phase: everything FRIFolder::finish_proof (crates/core/src/protocols/fri/prove.rs:483-507) writes to the
+ * decommitment, from codewords and Merkle trees resident on the device.  The indices are the caller's, as every challenge is: the
+ * decommitment is not observed by the challenger (transcript/mod.rs:182-195), so all of them can be sampled before any opening is made.
+ * Oracle i (oracles[i], a HOST array of bn_fri_oracle) names a committed codeword of 2^(log_n_cosets + log_coset_size) B128 elements,
+ * the flattened tree over its 2^log_n_cosets cosets as bn_merkle_build writes it (2 * (2^(log_n_cosets + 1) - 1) elements: layers
+ * concatenated, leaves first, root last; a digest is two elements), the depth of the layer the verifier receives
+ * (FRIParams optimal layer depths, common.rs:174-190) and index_shift, the sum of the arities after the first up to this oracle: the
+ * coset of query q in oracle i is indices[q] >> index_shift.  h_out receives, in transcript byte order,
+ *   d_terminate[0 .. terminate_elems)                                             the terminate codeword
+ *   for each oracle i: the 2^layer_depth digests of its layer                     (vcs_optimal_layers, prove.rs:597-610)
+ *   for each query q, for each oracle i:                                          (prove_query, prove.rs:545-595)
+ *       the 2^log_coset_size elements of the coset, then log_n_cosets - layer_depth digests, leaf sibling first
+ * so the header and every query's record have the lengths bn_fri_query_proof_elems states (a pure host function: it reads the sizes
+ * of the descriptors only, pointers may be null).  n_queries = 0 or n_oracles = 0 still copies the header; layer_depth = log_n_cosets
+ * is an empty branch.  Like every op it first brings up to date what it reads (a fold deferred on a codeword is visible); everything
+ * is only read; h_out is complete when the call returns.  ONE launch and one synchronisation per call whatever the number of queries
+ * and oracles: a wave serves one (query, oracle), computing the coset offset and the branch node ids on the device, further
+ * workgroups copy the header; the block comes back through pinned, device-mapped staging that grows on demand.
+ * BN_ERR_INPUT_VALIDATION, with nothing launched and nothing counted: a null or misaligned pointer, an index >= 2^index_bits,
+ * index_shift > index_bits or index_bits - index_shift > log_n_cosets (the shifted index would not be a coset of the oracle),
+ * layer_depth > log_n_cosets, out_elems different from the layout's total, more than BN_FRI_QUERY_MAX_ORACLES oracles (the
+ * descriptor table travels in the kernel arguments; FRI over 2^47 elements with arities of 2 or more has at most 23), a codeword of
+ * 2^48 elements or more, and a total above 2^26 elements (bn_gather_d2h's limit for one call). */
+typedef struct {
+	const void *d_codeword;
+	const void *d_nodes;
+	uint32_t log_n_cosets;
+	uint32_t log_coset_size;
+	uint32_t layer_depth;
+	uint32_t index_shift;
+} bn_fri_oracle;
+#define BN_FRI_QUERY_MAX_ORACLES 32
+/* (oracles points to n_oracles bn_fri_oracle; untyped in the prototype for the same reason as bn_partial_eval_high_batch's cols.) */
+int bn_fri_query_proof_elems(const void *oracles, uint32_t n_oracles, uint64_t terminate_elems, uint64_t n_queries, uint64_t *header_elems_out,
+                             uint64_t *record_elems_out, uint64_t *total_elems_out);
+int bn_fri_query_openings(bn_ctx *ctx, const void *oracles, uint32_t n_oracles, const void *d_terminate, uint64_t terminate_elems,
+                          const uint64_t *indices /*[n_queries]*/, uint64_t n_queries, uint32_t index_bits, bn_f128 *h_out, uint64_t out_elems);
+/* Read-only, per context (not part of the reference interface): accepted bn_fri_query_openings calls, the kernel launches they made,
+ * the (query, oracle) openings they served.  A rejected call counts nowhere. */
+enum { BN_FQ_CALLS = 0, BN_FQ_LAUNCHES = 1, BN_FQ_OPENINGS = 2, BN_FQ_N = 3 };
+int bn_fri_query_counters(bn_ctx *ctx, uint64_t *counters /*[BN_FQ_N]*/);
 
 /* ---- accumulate_kernels / map_kernels (layer.rs:183, 236) + KernelExecutor (layer.rs:518-590).
  * The kernel-spec closure cannot cross an FFI: the host shim runs it ONCE against a recording

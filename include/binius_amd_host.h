@@ -87,6 +87,24 @@ int bnh_mlecheck_last_mode(void);
 int bnh_fri_commit_fold(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities,
                         uint32_t n_arities, uint32_t n_test_queries, const void *d_message, void *d_scratch, uint64_t scratch_elems,
                         const bn_f128 *challenges, uint8_t *roots_out, bn_f128 *terminate_out, double *phase_ms_out);
+/* The same with the query phase: FRIFolder::finish_proof (fri/prove.rs:483-507) in place of finalize, the indices
+ * transcript.sample_bits(index_bits) would have returned handed in like the challenges (query_indices[n_test_queries], each below
+ * 2^index_bits with index_bits = log_dim + log_inv_rate + log_batch_size - fold_arities[0], 0 without arities).  advice_out receives the
+ * decommitment in transcript byte order (bn_fri_query_openings, one launch): terminate codeword, the layer of every opened oracle at
+ * its optimal depth, then per query and oracle the coset and its branch; *n_advice_elems_out: its length in field elements.
+ * BN_ERR_INPUT_VALIDATION when max_advice_elems is smaller than that.  phase_ms_out[3]: commit, fold, query phase, or NULL. */
+int bnh_fri_prove(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities,
+                  uint32_t n_test_queries, const void *d_message, void *d_scratch, uint64_t scratch_elems, const bn_f128 *challenges, uint8_t *roots_out,
+                  const uint64_t *query_indices, bn_f128 *advice_out, uint64_t max_advice_elems, uint64_t *n_advice_elems_out, double *phase_ms_out);
+
+/* diagnostic (tools/bench_fri_query.py): one commit and fold, then the query phase timed warmup + runs times two ways on the same
+ * resident codewords and trees, alternating -- FRIFolder::finish_proof (one launch) into new_ms_out[runs], and finalize's copy plus one
+ * FRIQueryProver::prove_query per index (a copy and a gather per opening) into old_ms_out[runs]; wall clock between two
+ * synchronisations.  *advice_elems_out: the length of the advice; *equal_out: both routes returned the same bytes. */
+int bnh_fri_query_phase_bench(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities,
+                              uint32_t n_test_queries, const void *d_message, void *d_scratch, uint64_t scratch_elems, const bn_f128 *challenges,
+                              const uint64_t *query_indices, uint32_t warmup, uint32_t runs, double *new_ms_out, double *old_ms_out, uint64_t *advice_elems_out,
+                              uint32_t *equal_out);
 
 /* The front-loaded batch prover (SumcheckBatchProver = protocols/sumcheck/prove/front_loaded.rs:33-203, BatchProver::run with the
  * transcript's samples handed in) over p BivariateSumcheckProvers on ONE layer, ascending by number of variables: per round
@@ -152,6 +170,18 @@ int bnh_piop_prove_committed(bn_ctx *ctx, uint32_t n_committed, const uint32_t *
                              const bn_f128 *batch_coeffs, uint32_t n_batch_coeffs, const bn_f128 *challenges, uint32_t n_challenges, uint32_t *items_out,
                              uint32_t max_items, uint32_t *n_items_out, bn_f128 *scalars_out, uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out,
                              uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms_out);
+/* bnh_piop_prove_committed with the FRI query phase (prove_interleaved_fri_sumcheck ending in FRIFolder::finish_proof): the same
+ * arguments and the same item list, then query_indices[n_test_queries] and the advice buffer of bnh_fri_prove.  The advice comes back
+ * in its own buffer; the terminate item of the list is filled from the same block.  BN_ERR_INPUT_VALIDATION when max_advice_elems is
+ * too small. */
+int bnh_piop_prove_committed_open(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
+                                  const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims,
+                                  const bn_f128 *claim_sums, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities,
+                                  uint32_t n_arities, uint32_t n_test_queries, const void *d_codeword, const void *d_tree, void *d_scratch, uint64_t scratch_elems,
+                                  const bn_f128 *batch_coeffs, uint32_t n_batch_coeffs, const bn_f128 *challenges, uint32_t n_challenges, uint32_t *items_out,
+                                  uint32_t max_items, uint32_t *n_items_out, bn_f128 *scalars_out, uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out,
+                                  uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms_out, const uint64_t *query_indices, bn_f128 *advice_out,
+                                  uint64_t max_advice_elems, uint64_t *n_advice_elems_out);
 
 /* EqIndSumcheckProver (crates/core/src/protocols/sumcheck/prove/eq_ind.rs:378-644) through the C++ mirror binius_amd/host/eq_ind.hpp,
  * over the old HAL (binius_hal::ComputationBackend: bn_hal_round_evals + the ComputeLayer's folds), evaluation order High-to-Low,
