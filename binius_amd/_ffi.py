@@ -16,8 +16,8 @@ import os
 
 import numpy as np
 
-BN_OK, BN_ERR_INPUT_VALIDATION, BN_ERR_ALLOC, BN_ERR_DEVICE, BN_ERR_CORE_LIB = range(5)
-_ERR_NAMES = {1: "InputValidation", 2: "Alloc", 3: "DeviceError", 4: "CoreLibError"}
+BN_OK, BN_ERR_INPUT_VALIDATION, BN_ERR_ALLOC, BN_ERR_DEVICE, BN_ERR_CORE_LIB, BN_ERR_CALLBACK = range(6)
+_ERR_NAMES = {1: "InputValidation", 2: "Alloc", 3: "DeviceError", 4: "CoreLibError", 5: "Callback"}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libbinius_amd.so")

@@ -3,8 +3,9 @@
 call, i.e. the prover loop driven at compiled-host speed over the same C ABI."""
 import ctypes as C
 import os
+import threading
 
-from ._ffi import BN_ERR_INPUT_VALIDATION, F128, BnError, _f128_array, from_f128, lib, to_f128
+from ._ffi import BN_ERR_CALLBACK, BN_ERR_INPUT_VALIDATION, F128, BnError, _f128_array, from_f128, lib, to_f128
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libbinius_amd_host.so")
@@ -12,8 +13,227 @@ _lib = None
 
 REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(F128))
 
+# bnh_transcript (include/binius_amd_host.h): the caller's Fiat-Shamir transcript as three callbacks
+TR_MESSAGE, TR_DECOMMITMENT = 0, 1
+TR_EVENT_KINDS = ("write_message", "write_decommitment", "sample", "sample_bits")
+TR_WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64)
+TR_SAMPLE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(F128), C.c_uint32)
+TR_SAMPLE_BITS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64))
+
+
+class BnhTranscript(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("write", TR_WRITE_FN), ("sample", TR_SAMPLE_FN), ("sample_bits", TR_SAMPLE_BITS_FN)]
+
+
+# array entry point -> (its _live form, the positions of its sample arguments, where the transcript stands once they are gone,
+# arguments to splice in first as (position, values): the entry point whose _live form is the superset's).  The positions are checked
+# against the parameter NAMES of include/binius_amd_host.h by tests/test_transcript_abi.py: dropping the named sample arguments of
+# the array form and inserting `transcript` must give the _live form's parameter list, name by name.
+_EVALCHECK_NO_TERMS = (5, (0, None, None, None, None))
+LIVE_FORMS = {
+    "bnh_batch_sumcheck_prove": ("bnh_batch_sumcheck_prove_live", (8, 9), 8, None),
+    "bnh_eqind_sumcheck_prove": ("bnh_eqind_sumcheck_prove_live", (14, 15), 14, None),
+    "bnh_zerocheck_batch_prove_tower": ("bnh_zerocheck_batch_prove_tower_live", (13, 14, 15, 16, 17, 18), 13, None),
+    "bnh_gkr_gpa_prove": ("bnh_gkr_gpa_prove_live", (8, 9, 10), 8, None),
+    "bnh_gkr_exp_prove": ("bnh_gkr_exp_prove_live", (14, 15), 14, None),
+    "bnh_flush_prodcheck_prove": ("bnh_flush_prodcheck_prove_live", (18, 19, 23, 24, 25, 26, 27), 21, None),
+    "bnh_evalcheck_bivariate_prove": ("bnh_evalcheck_bivariate_prove_lc_live", (16, 17), 16, _EVALCHECK_NO_TERMS),
+    "bnh_evalcheck_bivariate_prove_lc": ("bnh_evalcheck_bivariate_prove_lc_live", (16, 17), 16, None),
+    "bnh_ring_switch_prove": ("bnh_ring_switch_prove_live", (12, 13, 14, 15), 12, None),
+    "bnh_fri_prove": ("bnh_fri_prove_live", (10, 12), 10, None),
+    "bnh_piop_prove_committed_open": ("bnh_piop_prove_committed_open_live", (20, 21, 22, 23, 34), 20, None),
+}
+# bnh_zerocheck_batch_prove has no _live form of its own (the tower form is the superset, with its own scratch formula): a plan made
+# with tower=False is refused inside proving() rather than redirected
+NO_LIVE_FORM = {"bnh_zerocheck_batch_prove": "bnh_zerocheck_batch_prove has no _live form: make the ZerocheckBatchPlan with tower=True (and the tower scratch size)"}
+
+
+class _LiveState(threading.local):
+    """the transcripts of the proving() scopes in progress on THIS thread (innermost last)"""
+
+    def __init__(self):
+        self.stack = []
+
+
+_live = _LiveState()
+
+
+class _LiveEntries:
+    """host_lib() as a plan's run() sees it inside Transcript.prove(): every array entry point that has a _live form calls that form
+    with the sample arguments dropped and the transcript's table in their place; everything else is the library's."""
+
+    def __init__(self, L, table):
+        self._L, self._table = L, table
+
+    def __getattr__(self, name):
+        if name in NO_LIVE_FORM:
+            raise BnError(BN_ERR_INPUT_VALIDATION, NO_LIVE_FORM[name])
+        if name not in LIVE_FORMS:
+            return getattr(self._L, name)
+        live, drop, at, splice = LIVE_FORMS[name]
+        fn, table = getattr(self._L, live), self._table
+
+        def call(*args):
+            args = list(args)
+            if splice is not None:
+                args[splice[0]:splice[0]] = list(splice[1])
+            args = [a for i, a in enumerate(args) if i not in drop]
+            args.insert(at, table)
+            return fn(*args)
+
+        return call
+
+
+class _TranscriptBase:
+    def table(self):
+        """the `const bnh_transcript *` to hand to a _live entry point"""
+        raise NotImplementedError
+
+    def proving(self):
+        """Context manager: inside it, every plan of this module whose entry point has a _live form (LIVE_FORMS) runs against this
+        transcript.  The plan's own sample arrays are not read (hand it placeholders of the right lengths); its output arrays are
+        filled as its array form fills them.  A Python exception raised inside a callback ends the proof (the callback returns
+        non-zero, the entry point BN_ERR_CALLBACK) and is re-raised on the way out, after the call has come back: it never unwinds
+        through the library."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            _live.stack.append(_LiveEntries(_plain_host_lib(), self.table()))
+            try:
+                yield self
+            except BnError as e:
+                pending = self._take_exception()
+                if e.code == BN_ERR_CALLBACK and pending is not None:
+                    raise pending from None
+                raise
+            finally:
+                _live.stack.pop()
+
+        return scope()
+
+    def prove(self, plan):
+        """plan.run() inside proving()"""
+        with self.proving():
+            return plan.run()
+
+    def _take_exception(self):
+        return None
+
+
+class TranscriptAbort(Exception):
+    """raised inside a Transcript callback: the callback returns non-zero and nothing is re-raised -- the entry point's
+    BN_ERR_CALLBACK surfaces as BnError"""
+
+
+class Transcript(_TranscriptBase):
+    """A Fiat-Shamir transcript in Python behind the bnh_transcript table.  Subclasses implement
+        write(channel, data)        data: bytes in transcript byte order; channel TR_MESSAGE is observed, TR_DECOMMITMENT is not
+        sample(n) -> n ints         n x transcript.sample() of B128
+        sample_bits(bits, n) -> n ints
+    The callbacks run on the calling thread inside the entry point and must not call the library on the same context."""
+
+    def __init__(self):
+        self._exc = None
+
+        def guard(body):
+            def cb(*args):
+                try:
+                    body(*args)
+                    return 0
+                except TranscriptAbort:
+                    return 1
+                except BaseException as e:  # noqa: BLE001 -- nothing may unwind through the C++ frames above this callback
+                    self._exc = e
+                    return 1
+            return cb
+
+        def on_write(_user, channel, data, n):
+            self.write(int(channel), C.string_at(data, n))
+
+        def on_sample(_user, out, n):
+            vals = list(self.sample(int(n)))
+            assert len(vals) == n
+            for i, v in enumerate(vals):
+                out[i] = to_f128(v)
+
+        def on_sample_bits(_user, bits, n, out):
+            vals = list(self.sample_bits(int(bits), int(n)))
+            assert len(vals) == n
+            for i, v in enumerate(vals):
+                out[i] = int(v)
+
+        self._fns = (TR_WRITE_FN(guard(on_write)), TR_SAMPLE_FN(guard(on_sample)), TR_SAMPLE_BITS_FN(guard(on_sample_bits)))
+        self._table = BnhTranscript(None, *self._fns)
+
+    def table(self):
+        return C.addressof(self._table)
+
+    def _take_exception(self):
+        e, self._exc = self._exc, None
+        return e
+
+    def write(self, channel, data):
+        raise NotImplementedError
+
+    def sample(self, n):
+        raise NotImplementedError
+
+    def sample_bits(self, bits, n):
+        raise NotImplementedError
+
+
+class ReplayTranscript(_TranscriptBase):
+    """The library's array-backed transcript (bnh_transcript_replay_*): serves `samples` and `bit_samples` in order, fails when they
+    run out, records every write.  Host code only; needs no context."""
+
+    def __init__(self, samples, bit_samples=()):
+        samples, bit_samples = list(samples), list(bit_samples)
+        bits = (C.c_uint64 * max(1, len(bit_samples)))(*bit_samples)
+        self._h = C.c_void_p()
+        _host_check(host_lib().bnh_transcript_replay_new(_f128_array(samples), len(samples), bits, len(bit_samples), C.byref(self._h)))
+
+    def table(self):
+        return host_lib().bnh_transcript_replay_table(self._h)
+
+    def callbacks(self):
+        """the table itself: (user, write, sample, sample_bits) as ctypes callables"""
+        t = C.cast(self.table(), C.POINTER(BnhTranscript)).contents
+        return t.user, t.write, t.sample, t.sample_bits
+
+    def written(self, channel):
+        n = C.c_uint64()
+        host_lib().bnh_transcript_replay_written(self._h, channel, None, 0, C.byref(n))  # (the length; fails when it is not zero)
+        buf = (C.c_uint8 * max(1, n.value))()
+        _host_check(host_lib().bnh_transcript_replay_written(self._h, channel, buf, n.value, C.byref(n)))
+        return bytes(buf[: n.value])
+
+    def events(self):
+        """[(kind, count)]: kind in TR_EVENT_KINDS, count in bytes (writes) or samples (draws); neighbours of one kind merged"""
+        n = C.c_uint64()
+        host_lib().bnh_transcript_replay_events(self._h, None, None, 0, C.byref(n))
+        kinds, counts = (C.c_uint32 * max(1, n.value))(), (C.c_uint64 * max(1, n.value))()
+        _host_check(host_lib().bnh_transcript_replay_events(self._h, kinds, counts, n.value, C.byref(n)))
+        return [(TR_EVENT_KINDS[kinds[i]], int(counts[i])) for i in range(n.value)]
+
+    def close(self):
+        if self._h:
+            host_lib().bnh_transcript_replay_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
 
 def host_lib():
+    """the library -- or, inside Transcript.proving(), its entry points redirected to their _live forms"""
+    return _live.stack[-1] if _live.stack else _plain_host_lib()
+
+
+def _plain_host_lib():
     global _lib
     if _lib is None:
         lib()  # libbinius_amd.so first (dependency, resolved through rpath as well)
@@ -140,6 +360,24 @@ def host_lib():
         L.bnh_zerocheck_batch_scratch_elems_tower.argtypes = [C.c_uint32, C.c_uint32, U32P, U32P, U32P]
         L.bnh_zerocheck_batch_prove_tower.restype = C.c_int
         L.bnh_zerocheck_batch_prove_tower.argtypes = L.bnh_zerocheck_batch_prove.argtypes
+        # the _live forms: the array form's arguments without the samples, the transcript's table where LIVE_FORMS says
+        for name, (live, drop, at, _splice) in LIVE_FORMS.items():
+            if name == "bnh_evalcheck_bivariate_prove":
+                continue  # (its _live form is the superset's, declared from it)
+            types = [t for i, t in enumerate(getattr(L, name).argtypes) if i not in drop]
+            types.insert(at, C.c_void_p)
+            getattr(L, live).restype = C.c_int
+            getattr(L, live).argtypes = types
+        L.bnh_transcript_replay_new.restype = C.c_int
+        L.bnh_transcript_replay_new.argtypes = [FP, C.c_uint64, U64P, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.bnh_transcript_replay_table.restype = C.c_void_p
+        L.bnh_transcript_replay_table.argtypes = [C.c_void_p]
+        L.bnh_transcript_replay_written.restype = C.c_int
+        L.bnh_transcript_replay_written.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, U64P]
+        L.bnh_transcript_replay_events.restype = C.c_int
+        L.bnh_transcript_replay_events.argtypes = [C.c_void_p, U32P, U64P, C.c_uint64, U64P]
+        L.bnh_transcript_replay_free.restype = None
+        L.bnh_transcript_replay_free.argtypes = [C.c_void_p]
         L.bnh_rccl_open.argtypes = [C.c_char_p]
         L.bnh_rccl_unique_id.argtypes = [C.c_void_p]
         L.bnh_rccl_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]

@@ -16,6 +16,7 @@
 #include <memory>
 
 #include "sumcheck.hpp"
+#include "transcript.hpp"
 
 namespace binius_amd {
 
@@ -24,6 +25,7 @@ enum class BatchSchedule { FrontLoaded, JoinBySize };
 struct BatchSumcheckOutput {
 	std::vector<std::vector<B128>> round_proofs;      // per round
 	std::vector<std::vector<B128>> multilinear_evals; // per prover, in finishing order
+	std::vector<B128> challenges;                     // per round, as drawn (run over a TranscriptSource)
 };
 
 template <class Prover>
@@ -53,6 +55,7 @@ public:
 			if (round_coeffs.size() < prover_coeffs.size()) round_coeffs.resize(prover_coeffs.size(), B128::ZERO());
 			for (size_t c = 0; c < prover_coeffs.size(); c++) round_coeffs[c] = round_coeffs[c] + prover_coeffs[c] * batch_coeffs_[i];
 		}
+		truncated_len_ = round_coeffs.empty() ? 0 : round_coeffs.size() - 1;
 		if (full_coeffs_)
 			round_coeffs.resize(full_coeffs_, B128::ZERO());
 		else if (!round_coeffs.empty())
@@ -84,6 +87,40 @@ public:
 		return out;
 	}
 
+	// how many coefficients of the last round_proof() the transcript carries: all but the last of the batched polynomial
+	// (RoundCoeffs::truncate) -- with `full_coeffs` fewer than were returned
+	size_t truncated_len() const { return truncated_len_; }
+	// BatchProver::run (front_loaded.rs:175-197; batch_sumcheck.rs:156-199) against a transcript: per round the evaluations of the
+	// provers that finished (front_loaded.rs:109-120), the truncated round polynomial, then ONE sample (stream, first + round); after
+	// the last round the evaluations of the provers that finish then.  Every output is what run(challenges) returns for the samples
+	// drawn.  coeff_stream >= 0 (JoinBySize): the batch coefficients handed to the constructor are placeholders; prover i's is sampled
+	// as (coeff_stream, coeff_first + i) in the round where it joins (batch_sumcheck.rs:143-151), those of the zero-variable provers
+	// after the last round (:173-177).
+	BatchSumcheckOutput run(TranscriptSource &tr, int stream, size_t first = 0, int coeff_stream = -1, size_t coeff_first = 0)
+	{
+		BatchSumcheckOutput out;
+		size_t n_written = 0, n_coeffs = coeff_stream < 0 ? provers_.size() : 0;
+		auto write_finished = [&] {
+			for (; n_written < multilinear_evals_.size(); n_written++) tr.write_scalars(multilinear_evals_[n_written]);
+		};
+		auto sample_coeffs = [&](size_t end) {
+			for (; n_coeffs < end; n_coeffs++) batch_coeffs_[n_coeffs] = tr.sample(coeff_stream, coeff_first + n_coeffs);
+		};
+		for (size_t r = 0; r < total_rounds_; r++) {
+			update_live();
+			sample_coeffs(live_end_);
+			out.round_proofs.push_back(round_proof());
+			write_finished();
+			tr.write_scalars(out.round_proofs.back().data(), truncated_len_);
+			out.challenges.push_back(tr.sample(stream, first + r));
+			receive_challenge(out.challenges.back());
+		}
+		sample_coeffs(provers_.size());
+		out.multilinear_evals = finish();
+		write_finished();
+		return out;
+	}
+
 private:
 	// the provers [live_begin_, live_end_) take part in the round that begins
 	void update_live()
@@ -101,7 +138,7 @@ private:
 	BatchSchedule schedule_;
 	size_t full_coeffs_;
 	std::vector<std::vector<B128>> multilinear_evals_;
-	size_t total_rounds_ = 0, round_ = 0, live_begin_ = 0, live_end_ = 0;
+	size_t total_rounds_ = 0, round_ = 0, live_begin_ = 0, live_end_ = 0, truncated_len_ = 0;
 };
 
 // the front-loaded batch of ONE prover, every round: what a protocol step with a single sumcheck runs
@@ -111,6 +148,13 @@ inline BatchSumcheckOutput prove_batch_of_one(std::unique_ptr<Prover> prover, B1
 	std::vector<std::unique_ptr<Prover>> one;
 	one.push_back(std::move(prover));
 	return SumcheckBatchProver<Prover>(std::move(one), {batch_coeff}).run(challenges);
+}
+template <class Prover>
+inline BatchSumcheckOutput prove_batch_of_one(std::unique_ptr<Prover> prover, B128 batch_coeff, TranscriptSource &tr, int stream, size_t first)
+{
+	std::vector<std::unique_ptr<Prover>> one;
+	one.push_back(std::move(prover));
+	return SumcheckBatchProver<Prover>(std::move(one), {batch_coeff}).run(tr, stream, first);
 }
 
 } // namespace binius_amd

@@ -94,7 +94,7 @@ inline bn_f128 *to_raw(const std::vector<B128> &v, bn_f128 *dst)
 // binius_compute::Error (layer.rs:706-716) + alloc::Error::OutOfMemory (alloc.rs:110-113)
 class Error : public std::runtime_error {
 public:
-	enum Kind { InputValidation = 1, Alloc = 2, DeviceError = 3, CoreLibError = 4 };
+	enum Kind { InputValidation = 1, Alloc = 2, DeviceError = 3, CoreLibError = 4, Callback = 5 };
 	Error(Kind k, const std::string &msg) : std::runtime_error(msg), kind_(k) {}
 	Kind kind() const { return kind_; }
 

@@ -146,11 +146,13 @@ inline std::vector<B128> evalcheck_shift_ind_table(size_t b, size_t offset, Shif
 // per round the truncated coefficients; per prover, in finishing (= input) order, its final evaluations
 using EvalcheckOutput = BatchSumcheckOutput;
 
+// Schedule (subclaims.rs:549-586 = front_loaded::BatchProver::new + run): sample the n_provers batch coefficients (stream
+// EvalcheckBatchCoeffs); per round the evaluations of the provers that finished, the truncated round polynomial (2 coefficients),
+// ONE sample (stream EvalcheckChallenges); after the last round the evaluations of the provers that finish then.
+enum { EvalcheckBatchCoeffs = 0, EvalcheckChallenges = 1 };
 inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::vector<EvalcheckProver> &provers, const std::vector<B128> &pool, FSliceMut scratch,
-                                                 const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges,
-                                                 const std::vector<EvalcheckTerm> &terms = {})
+                                                 TranscriptSource &tr, const std::vector<EvalcheckTerm> &terms = {})
 {
-	if (batch_coeffs.size() != provers.size()) throw Error(Error::InputValidation, "IncorrectNumberOfBatchCoeffs");
 	size_t total_m = 0;
 	for (size_t i = 0; i < provers.size(); i++) {
 		const EvalcheckProver &p = provers[i];
@@ -184,7 +186,6 @@ inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::v
 		total_m += p.multilins.size();
 	}
 	if (provers.empty()) return {};
-	if (challenges.size() < provers.back().n_vars) throw Error(Error::InputValidation, "too few challenges");
 	if (scratch.len_ < evalcheck_scratch_elems(provers)) throw Error(Error::InputValidation, "scratch holds fewer than evalcheck_scratch_elems elements");
 	DeviceBumpAllocator alloc(scratch);
 
@@ -270,7 +271,17 @@ inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::v
 			if (c.indices[0] >= p.multilins.size() || c.indices[1] >= p.multilins.size()) throw Error(Error::InputValidation, "a claim's index leaves its prover's multilinears");
 		sc.push_back(std::make_unique<BivariateSumcheckProver>(hal, alloc, host_alloc, p.n_vars, p.compositions, p.sums, mls));
 	}
-	return SumcheckBatchProver<BivariateSumcheckProver>(std::move(sc), batch_coeffs).run(challenges.data());
+	const std::vector<B128> batch_coeffs = tr.sample_vec(EvalcheckBatchCoeffs, 0, sc.size());
+	return SumcheckBatchProver<BivariateSumcheckProver>(std::move(sc), batch_coeffs).run(tr, EvalcheckChallenges);
+}
+inline EvalcheckOutput evalcheck_bivariate_prove(ComputeLayer &hal, const std::vector<EvalcheckProver> &provers, const std::vector<B128> &pool, FSliceMut scratch,
+                                                 const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges,
+                                                 const std::vector<EvalcheckTerm> &terms = {})
+{
+	if (batch_coeffs.size() != provers.size()) throw Error(Error::InputValidation, "IncorrectNumberOfBatchCoeffs");
+	if (!provers.empty() && challenges.size() < provers.back().n_vars) throw Error(Error::InputValidation, "too few challenges");
+	ArrayTranscript tr({ArrayTranscript::stream(batch_coeffs), ArrayTranscript::stream(challenges)});
+	return evalcheck_bivariate_prove(hal, provers, pool, scratch, tr, terms);
 }
 
 // ---- the evaluations in front of a round (prove.rs:191-275)

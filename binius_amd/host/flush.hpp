@@ -177,12 +177,25 @@ inline void widen(ComputeLayer &hal, const std::vector<Widen> &cols, const std::
 
 } // namespace flush_detail
 
-// gpa_*: the samples gkr_gpa_batch_prove takes, sized by the largest n_vars over flushes and non-zero oracles.
-// red_batch_coeffs[g], red_challenges: per MLE-check (flush_groups order) one batch coefficient and its n_vars challenges, concatenated.
+// The transcript's streams, as the array form names them.  gpa_*: the samples gkr_gpa_batch_prove takes (its streams 0 .. 2), sized by
+// the largest n_vars over flushes and non-zero oracles.  red_batch_coeffs[g], red_challenges: per MLE-check (flush_groups order) one
+// batch coefficient and its n_vars challenges, concatenated.
+// Schedule (constraint_system/prove.rs:309-425): write the non-zero products; sample the mixing challenge, then the n_channels
+// permutation challenges; write the flush products; the grand-product argument's schedule (gkr_gpa.hpp) over chain(flushes, non-zero);
+// per MLE-check a front-loaded batch of one: sample its batch coefficient, n_vars rounds of write / sample, write its evaluations.
+// A system without flushes and without non-zero oracles still writes its (empty) product slices and draws the mixing challenge and
+// the n_channels permutation challenges (prove.rs:318-330 has no other case): against a caller's transcript the two draws are made
+// and dropped, so that the challenger stays in step with the verifier's.  The array form, which has nothing to keep in step, returns
+// at once.
+enum { FlushRedBatchCoeffs = 3, FlushRedChallenges = 4, FlushMixingChallenge = 5, FlushPermutationChallenges = 6 };
+inline void flush_prodcheck_empty(TranscriptSource &tr, size_t n_channels)
+{
+	if (!tr.observes_writes()) return;
+	(void)tr.sample(FlushMixingChallenge, 0);
+	(void)tr.sample_vec(FlushPermutationChallenges, 0, n_channels);
+}
 inline FlushProdcheckOutput flush_prodcheck_prove(ComputeLayer &hal, Mi355xBackend &backend, const std::vector<FlushSpec> &flushes, const std::vector<NonZeroSpec> &nonzero,
-                                                  B128 mixing_challenge, const std::vector<B128> &permutation_challenges, FSliceMut scratch,
-                                                  const std::vector<B128> &gpa_batch_coeffs, const std::vector<B128> &gpa_sumcheck_challenges,
-                                                  const std::vector<B128> &gpa_challenges, const std::vector<B128> &red_batch_coeffs, const std::vector<B128> &red_challenges)
+                                                  size_t n_channels, FSliceMut scratch, TranscriptSource &tr)
 {
 	using namespace flush_detail;
 	const auto t_begin = std::chrono::steady_clock::now();
@@ -190,7 +203,7 @@ inline FlushProdcheckOutput flush_prodcheck_prove(ComputeLayer &hal, Mi355xBacke
 	FlushProdcheckOutput out;
 	// ---- validation (what the ops below would not say in the caller's terms)
 	for (const FlushSpec &f : flushes) {
-		if (f.channel >= permutation_challenges.size()) throw Error(Error::InputValidation, "a flush names a channel without a permutation challenge");
+		if (f.channel >= n_channels) throw Error(Error::InputValidation, "a flush names a channel without a permutation challenge");
 		if (f.n_vars > BN_FLUSH_MAX_VARS) throw Error(Error::InputValidation, "n_vars out of range (0 .. 28)");
 		if (f.selectors.size() + 1 > kEqIndMaxDegree) throw Error(Error::InputValidation, "more than 7 selectors: the composite's degree exceeds the sumcheck's");
 		size_t n_cols = 0;
@@ -200,13 +213,11 @@ inline FlushProdcheckOutput flush_prodcheck_prove(ComputeLayer &hal, Mi355xBacke
 	for (const NonZeroSpec &z : nonzero)
 		if (z.n_vars > BN_PRODUCT_TREE_MAX_VARS) throw Error(Error::InputValidation, "n_vars out of range (0 .. 28)");
 	const std::vector<FlushMleCheck> groups = flush_groups(flushes);
-	{
-		size_t need = 0;
-		for (const FlushMleCheck &g : groups) need += g.n_vars;
-		if (red_batch_coeffs.size() < groups.size() || red_challenges.size() < need) throw Error(Error::InputValidation, "too few transcript samples for the reductions");
-	}
 	if (scratch.len_ < flush_prodcheck_scratch_elems(flushes, nonzero)) throw Error(Error::InputValidation, "scratch holds fewer than flush_prodcheck_scratch_elems elements");
-	if (k == 0) return out;
+	if (k == 0) {
+		flush_prodcheck_empty(tr, n_channels);
+		return out;
+	}
 
 	DeviceBumpAllocator alloc(scratch);
 	FSliceMut d_one = alloc.alloc(1);
@@ -239,7 +250,10 @@ inline FlushProdcheckOutput flush_prodcheck_prove(ComputeLayer &hal, Mi355xBacke
 		check(bn_product_tree_layers(hal.raw_ctx(), (uint32_t)nz, n32.data(), ins.data(), lens.data(), ars.data(), prod.data()));
 		for (size_t i = 0; i < nz; i++)
 			if (prod[i].lo == 0 && prod[i].hi == 0) throw Error(Error::InputValidation, "Zeros: the product of a non-zero oracle is zero");
+		tr.write(BNH_TR_MESSAGE, prod.data(), nz * sizeof(bn_f128)); // (prove.rs:318-320)
 	}
+	const B128 mixing_challenge = tr.sample(FlushMixingChallenge, 0);                                            // (prove.rs:329)
+	const std::vector<B128> permutation_challenges = tr.sample_vec(FlushPermutationChallenges, 0, n_channels); // (prove.rs:330)
 
 	// ---- the flush witnesses: one call for all flushes
 	std::vector<B128> const_terms(nf);
@@ -284,7 +298,8 @@ inline FlushProdcheckOutput flush_prodcheck_prove(ComputeLayer &hal, Mi355xBacke
 		std::vector<FSlice> ins(k);
 		for (size_t t = 0; t < k; t++) ins[t] = FSlice{wit[t].ptr, t < nf ? (size_t)out.prefix_lens[t] : wit[t].len_};
 		const size_t gpa_need = gkr_gpa_scratch_elems(nv);
-		out.gpa = gkr_gpa_batch_prove(hal, backend, nv, ins, arenas, alloc.alloc(gpa_need), gpa_batch_coeffs, gpa_sumcheck_challenges, gpa_challenges);
+		out.gpa = gkr_gpa_batch_prove(hal, backend, nv, ins, arenas, alloc.alloc(gpa_need), tr,
+		                              [&](const std::vector<B128> &products) { tr.write_scalars(products.data(), nf); }); // (prove.rs:378-380)
 	}
 	out.phase_ms[1] = elapsed_ms(t_gpa);
 
@@ -348,17 +363,32 @@ inline FlushProdcheckOutput flush_prodcheck_prove(ComputeLayer &hal, Mi355xBacke
 			sums.push_back(out.gpa.final_evals[f]);
 		}
 		// a front-loaded batch of one; at n = 0 there are no rounds (EqIndPointProver's zero-variable case)
-		BatchSumcheckOutput res =
-		    prove_batch_of_one(std::make_unique<EqIndPointProver>(hal, backend, ra, n, mls, std::move(comps), std::move(sums), point), red_batch_coeffs[g], red_challenges.data() + ch_at);
+		const B128 red_batch_coeff = tr.sample(FlushRedBatchCoeffs, g);
+		BatchSumcheckOutput res = prove_batch_of_one(std::make_unique<EqIndPointProver>(hal, backend, ra, n, mls, std::move(comps), std::move(sums), point), red_batch_coeff, tr,
+		                                             FlushRedChallenges, ch_at);
 		chk.round_proofs = std::move(res.round_proofs);
 		chk.final_evals = std::move(res.multilinear_evals[0]);
-		chk.point.assign(red_challenges.rend() - (ch_at + n), red_challenges.rend() - ch_at); // reversed (subclaims.rs:623-624)
+		chk.point.assign(res.challenges.rbegin(), res.challenges.rend()); // reversed (subclaims.rs:623-624)
 		ch_at += n;
 		out.checks.push_back(std::move(chk));
 	}
 	out.phase_ms[2] = elapsed_ms(t_red);
 	out.phase_ms[3] = elapsed_ms(t_begin);
 	return out;
+}
+inline FlushProdcheckOutput flush_prodcheck_prove(ComputeLayer &hal, Mi355xBackend &backend, const std::vector<FlushSpec> &flushes, const std::vector<NonZeroSpec> &nonzero,
+                                                  B128 mixing_challenge, const std::vector<B128> &permutation_challenges, FSliceMut scratch,
+                                                  const std::vector<B128> &gpa_batch_coeffs, const std::vector<B128> &gpa_sumcheck_challenges,
+                                                  const std::vector<B128> &gpa_challenges, const std::vector<B128> &red_batch_coeffs, const std::vector<B128> &red_challenges)
+{
+	size_t need = 0;
+	const std::vector<FlushMleCheck> groups = flush_groups(flushes);
+	for (const FlushMleCheck &g : groups) need += g.n_vars;
+	if (red_batch_coeffs.size() < groups.size() || red_challenges.size() < need) throw Error(Error::InputValidation, "too few transcript samples for the reductions");
+	ArrayTranscript tr({ArrayTranscript::stream(gpa_batch_coeffs), ArrayTranscript::stream(gpa_sumcheck_challenges), ArrayTranscript::stream(gpa_challenges),
+	                    ArrayTranscript::stream(red_batch_coeffs), ArrayTranscript::stream(red_challenges), ArrayTranscript::Stream{&mixing_challenge, 1},
+	                    ArrayTranscript::stream(permutation_challenges)});
+	return flush_prodcheck_prove(hal, backend, flushes, nonzero, permutation_challenges.size(), scratch, tr);
 }
 
 } // namespace binius_amd

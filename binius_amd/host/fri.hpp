@@ -60,6 +60,19 @@ public:
 		}
 		return out;
 	}
+	// the length of finish_proof's decommitment in field elements (a digest is two): the terminate codeword, one layer per oracle,
+	// per query and oracle a coset and its branch -- what bn_fri_query_proof_elems states for the committed oracles of these parameters
+	size_t advice_elems() const
+	{
+		const std::vector<size_t> depths = optimal_layer_depths();
+		size_t header = (size_t)1 << (log_inv_rate_ + n_final_challenges()), record = 0, log_n_cosets = log_len();
+		for (size_t i = 0; i < fold_arities_.size(); i++) {
+			log_n_cosets -= fold_arities_[i];
+			header += (size_t)2 << depths[i];
+			record += ((size_t)1 << fold_arities_[i]) + 2 * (log_n_cosets - depths[i]);
+		}
+		return header + n_test_queries_ * record;
+	}
 
 private:
 	size_t log_dim_, log_inv_rate_, log_batch_size_;

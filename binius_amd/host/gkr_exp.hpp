@@ -80,8 +80,14 @@ inline size_t gkr_exp_scratch_elems(const std::vector<size_t> &n_vars, const std
 	return total;
 }
 
+// The transcript's streams, as the array form names them: batch_coeffs[L * n_claims + g], the coefficient of the g-th sumcheck prover of
+// layer L; challenges[L * max_n_vars + r], round r of layer L.
+// Schedule of layer L (sumcheck::batch_prove, batch_sumcheck.rs:138-187): per round, first one batch coefficient for every prover that
+// joins in it, then write the truncated round polynomial, sample 1; after the last round one coefficient per zero-variable prover;
+// then every prover's evaluations are written, in order.  A layer without a prover writes and draws nothing.
+enum { GkrExpBatchCoeffs = 0, GkrExpChallenges = 1 };
 inline GkrExpOutput gkr_exp_batch_prove(ComputeLayer &hal, Mi355xBackend &backend, size_t n_witnesses, const std::vector<GkrExpClaim> &claims, FSliceMut scratch,
-                                        const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges)
+                                        TranscriptSource &tr)
 {
 	const size_t k = claims.size();
 	if (n_witnesses != k) throw Error(Error::InputValidation, "MismatchedWitnessClaimLength");
@@ -100,7 +106,6 @@ inline GkrExpOutput gkr_exp_batch_prove(ComputeLayer &hal, Mi355xBackend &backen
 		nv[t] = c.n_vars;
 		dyn[t] = c.dynamic;
 	}
-	if (batch_coeffs.size() < max_w * k || challenges.size() < max_w * max_n) throw Error(Error::InputValidation, "too few transcript samples (max_width x n_claims, max_width x max_n_vars)");
 	if (scratch.len_ < gkr_exp_scratch_elems(nv, dyn)) throw Error(Error::InputValidation, "scratch holds fewer than gkr_exp_scratch_elems elements");
 
 	// ---- the witnesses: every layer of every circuit in one call (which validates widths, n_vars, pointers and overlaps)
@@ -207,11 +212,10 @@ inline GkrExpOutput gkr_exp_batch_prove(ComputeLayer &hal, Mi355xBackend &backen
 			i0 = i1;
 		}
 		// ---- sumcheck::batch_prove: the groups descend by n_vars and join as the rounds reach their size
-		const size_t n_rounds = groups.empty() ? 0 : groups[0]->n_vars(), n_groups = groups.size();
-		BatchSumcheckOutput res = SumcheckBatchProver<EqIndPointProver>(std::move(groups), std::vector<B128>(batch_coeffs.begin() + L * k, batch_coeffs.begin() + L * k + n_groups),
-		                                                                BatchSchedule::JoinBySize)
-		                              .run(challenges.data() + L * max_n);
-		const std::vector<B128> r(challenges.rend() - (L * max_n + n_rounds), challenges.rend() - L * max_n); // reversed
+		const size_t n_groups = groups.size();
+		BatchSumcheckOutput res = SumcheckBatchProver<EqIndPointProver>(std::move(groups), std::vector<B128>(n_groups), BatchSchedule::JoinBySize)
+		                              .run(tr, GkrExpChallenges, L * max_n, GkrExpBatchCoeffs, L * k);
+		const std::vector<B128> r(res.challenges.rbegin(), res.challenges.rend()); // reversed
 		const std::vector<std::vector<B128>> &evals = res.multilinear_evals;
 		// ---- build_layer_exponent_bit_claims
 		std::vector<B128> flat;
@@ -241,6 +245,19 @@ inline GkrExpOutput gkr_exp_batch_prove(ComputeLayer &hal, Mi355xBackend &backen
 		out.layer_ms.push_back(elapsed_ms(t_begin));
 	}
 	return out;
+}
+inline GkrExpOutput gkr_exp_batch_prove(ComputeLayer &hal, Mi355xBackend &backend, size_t n_witnesses, const std::vector<GkrExpClaim> &claims, FSliceMut scratch,
+                                        const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges)
+{
+	size_t max_w = 0, max_n = 0;
+	for (const GkrExpClaim &c : claims) {
+		max_w = std::max(max_w, c.width);
+		max_n = std::max(max_n, c.n_vars);
+	}
+	if (n_witnesses == claims.size() && (batch_coeffs.size() < max_w * claims.size() || challenges.size() < max_w * max_n))
+		throw Error(Error::InputValidation, "too few transcript samples (max_width x n_claims, max_width x max_n_vars)");
+	ArrayTranscript tr({ArrayTranscript::stream(batch_coeffs), ArrayTranscript::stream(challenges)});
+	return gkr_exp_batch_prove(hal, backend, n_witnesses, claims, scratch, tr);
 }
 
 } // namespace binius_amd

@@ -27,6 +27,8 @@
 #include <algorithm>
 #include <chrono>
 
+#include <functional>
+
 #include "batch_prover.hpp"
 #include "eq_ind.hpp"
 
@@ -51,18 +53,17 @@ inline size_t gkr_gpa_scratch_elems(const std::vector<size_t> &n_vars)
 	return total + (max_n >= 1 ? (size_t)1 << (max_n - 1) : 0);
 }
 
-// batch_coeffs[j], gpa_challenges[j]: one per step j < max n_vars (step 0's batch coefficient is sampled and unused);
-// sumcheck_challenges: step j's j challenges, steps concatenated
+// The transcript's streams, as the array form names them: batch_coeffs[j], gpa_challenges[j]: one per step j < max n_vars (step 0's
+// batch coefficient is sampled and unused); sumcheck_challenges: step j's j challenges, steps concatenated.
+// Schedule of step j (prove.rs:79-126): sample the batch coefficient (front_loaded::BatchProver::new, sample_vec(1)); j rounds of
+// write 3 coefficients / sample 1; write the 2 * active layer evaluations and the indicator's; sample the layer challenge.
+enum { GkrGpaBatchCoeffs = 0, GkrGpaSumcheckChallenges = 1, GkrGpaChallenges = 2 };
 inline GkrGpaOutput gkr_gpa_batch_prove(ComputeLayer &hal, Mi355xBackend &backend, const std::vector<size_t> &n_vars, const std::vector<FSlice> &inputs,
-                                        const std::vector<FSliceMut> &arenas, FSliceMut scratch, const std::vector<B128> &batch_coeffs,
-                                        const std::vector<B128> &sumcheck_challenges, const std::vector<B128> &gpa_challenges)
+                                        const std::vector<FSliceMut> &arenas, FSliceMut scratch, TranscriptSource &tr,
+                                        const std::function<void(const std::vector<B128> &)> &on_products = nullptr)
 {
 	const size_t k = n_vars.size();
 	if (inputs.size() != k || arenas.size() != k) throw Error(Error::InputValidation, "MismatchedWitnessClaimLength");
-	size_t max_n = 0;
-	for (size_t n : n_vars) max_n = std::max(max_n, n);
-	if (batch_coeffs.size() < max_n || gpa_challenges.size() < max_n || sumcheck_challenges.size() < max_n * (max_n ? max_n - 1 : 0) / 2)
-		throw Error(Error::InputValidation, "too few transcript samples for the largest claim");
 	if (scratch.len_ < gkr_gpa_scratch_elems(n_vars)) throw Error(Error::InputValidation, "scratch holds fewer than sum 2^n_vars + 2^(max n_vars - 1) elements");
 	GkrGpaOutput out;
 	out.products.resize(k);
@@ -85,6 +86,8 @@ inline GkrGpaOutput gkr_gpa_batch_prove(ComputeLayer &hal, Mi355xBackend &backen
 		}
 		check(bn_product_tree_layers(hal.raw_ctx(), (uint32_t)k, nv.data(), ins.data(), lens.data(), ars.data(), reinterpret_cast<bn_f128 *>(out.products.data())));
 	}
+	// (a caller that writes products to the transcript does it here, before the first sample of the argument)
+	if (on_products) on_products(out.products);
 	// ---- full-length copies of the inputs (the last layer each tree's sumchecks fold)
 	std::vector<FSliceMut> padded(k);
 	size_t used = 0;
@@ -136,7 +139,7 @@ inline GkrGpaOutput gkr_gpa_batch_prove(ComputeLayer &hal, Mi355xBackend &backen
 			if (n_vars[t] > j) active.push_back(t);
 		if (active.empty()) break;
 		const auto t_begin = std::chrono::steady_clock::now();
-		const B128 batch_coeff = batch_coeffs[j], gpa_challenge = gpa_challenges[j];
+		const B128 batch_coeff = tr.sample(GkrGpaBatchCoeffs, j);
 		// layer j + 1 of every active state: its arena, or the padded copy of its input
 		std::vector<const char *> layer(active.size());
 		for (size_t i = 0; i < active.size(); i++) {
@@ -156,11 +159,13 @@ inline GkrGpaOutput gkr_gpa_batch_prove(ComputeLayer &hal, Mi355xBackend &backen
 		// (step 0 has no rounds and takes no composition)
 		auto prover = std::make_unique<EqIndPointProver>(hal, backend, eq_alloc, j, std::move(slices), std::vector<EqIndComposition>(all_comps.begin(), all_comps.begin() + (j ? active.size() : 0)),
 		                                                 std::move(sums), eval_point, j ? 1 : 2);
-		BatchSumcheckOutput res = prove_batch_of_one(std::move(prover), batch_coeff, sumcheck_challenges.data() + ch_at);
+		BatchSumcheckOutput res = prove_batch_of_one(std::move(prover), batch_coeff, tr, GkrGpaSumcheckChallenges, ch_at);
+		// (the layer challenge is drawn after the layer's evaluations are written, prove.rs:113-114)
+		const B128 gpa_challenge = tr.sample(GkrGpaChallenges, j);
 		std::vector<B128> proofs;
 		for (const auto &rp : res.round_proofs) proofs.insert(proofs.end(), rp.begin(), rp.end());
 		const std::vector<B128> finals = std::move(res.multilinear_evals[0]);
-		eval_point.assign(sumcheck_challenges.begin() + ch_at, sumcheck_challenges.begin() + ch_at + j);
+		eval_point = res.challenges;
 		std::reverse(eval_point.begin(), eval_point.end()); // (:106-108)
 		ch_at += j;
 		eval_point.push_back(gpa_challenge);
@@ -173,6 +178,18 @@ inline GkrGpaOutput gkr_gpa_batch_prove(ComputeLayer &hal, Mi355xBackend &backen
 		out.step_ms.push_back(elapsed_ms(t_begin));
 	}
 	return out;
+}
+inline GkrGpaOutput gkr_gpa_batch_prove(ComputeLayer &hal, Mi355xBackend &backend, const std::vector<size_t> &n_vars, const std::vector<FSlice> &inputs,
+                                        const std::vector<FSliceMut> &arenas, FSliceMut scratch, const std::vector<B128> &batch_coeffs,
+                                        const std::vector<B128> &sumcheck_challenges, const std::vector<B128> &gpa_challenges)
+{
+	size_t max_n = 0;
+	for (size_t n : n_vars) max_n = std::max(max_n, n);
+	if (n_vars.size() == inputs.size() && n_vars.size() == arenas.size() &&
+	    (batch_coeffs.size() < max_n || gpa_challenges.size() < max_n || sumcheck_challenges.size() < max_n * (max_n ? max_n - 1 : 0) / 2))
+		throw Error(Error::InputValidation, "too few transcript samples for the largest claim");
+	ArrayTranscript tr({ArrayTranscript::stream(batch_coeffs), ArrayTranscript::stream(sumcheck_challenges), ArrayTranscript::stream(gpa_challenges)});
+	return gkr_gpa_batch_prove(hal, backend, n_vars, inputs, arenas, scratch, tr);
 }
 
 } // namespace binius_amd

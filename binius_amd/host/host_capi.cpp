@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -32,6 +33,7 @@
 #include "piop.hpp"
 #include "ring_switch.hpp"
 #include "sumcheck.hpp"
+#include "transcript.hpp"
 #include "zerocheck.hpp"
 
 using namespace binius_amd;
@@ -86,6 +88,29 @@ void put_gkr_gpa_output(const GkrGpaOutput &out, bn_f128 *products_out, bn_f128 
 	for (const auto &le : out.layer_evals) layer_evals_out = to_raw(le, layer_evals_out);
 }
 
+// The transcript of an entry point: the caller's table (the _live form: a null table or a null callback it needs is rejected at once,
+// before anything is launched) or the sample arrays of the array form, as the streams the mirror numbers.
+struct EntryTranscript {
+	std::unique_ptr<LiveTranscript> live;
+	std::vector<std::vector<B128>> arrays;
+	std::unique_ptr<ArrayTranscript> array;
+	EntryTranscript(bool is_live, const bnh_transcript *table, bool need_bits = false)
+	{
+		if (is_live) live = std::make_unique<LiveTranscript>(table, need_bits);
+	}
+	TranscriptSource &source(std::vector<std::vector<B128>> streams, const uint64_t *bits = nullptr, size_t n_bits = 0)
+	{
+		if (live) return *live;
+		arrays = std::move(streams);
+		std::vector<ArrayTranscript::Stream> views;
+		for (const auto &v : arrays) views.push_back(ArrayTranscript::stream(v));
+		array = std::make_unique<ArrayTranscript>(std::move(views), bits, n_bits);
+		return *array;
+	}
+};
+// a single sample of the array form as a stream of one (empty when the pointer is null: the _live form)
+std::vector<B128> one_sample(const bn_f128 *p) { return from_raw(p, p ? 1 : 0); }
+
 // the body of an entry point: what it throws becomes the return code, the message goes to bnh_last_error()
 template <class F>
 int guarded(F &&body)
@@ -105,6 +130,91 @@ int guarded(F &&body)
 extern "C" {
 
 const char *bnh_last_error(void) { return g_err.c_str(); }
+
+// ---- the array-backed transcript: samples served from arrays, every write recorded; pure host code, no context ------------------
+struct bnh_transcript_replay {
+	bnh_transcript table{};
+	std::vector<bn_f128> samples;
+	std::vector<uint64_t> bit_samples;
+	size_t next_sample = 0, next_bits = 0;
+	std::vector<uint8_t> written[2]; // per channel
+	std::vector<std::pair<uint32_t, uint64_t>> events; // (kind, bytes or samples); neighbours of one kind are one event
+	void log(uint32_t kind, uint64_t count)
+	{
+		if (!events.empty() && events.back().first == kind)
+			events.back().second += count;
+		else
+			events.emplace_back(kind, count);
+	}
+};
+static int replay_write(void *user, uint32_t channel, const void *bytes, uint64_t len)
+{
+	bnh_transcript_replay *h = (bnh_transcript_replay *)user;
+	if (!h || channel > BNH_TR_DECOMMITMENT || (len && !bytes)) return 1;
+	if (!len) return 0;
+	h->written[channel].insert(h->written[channel].end(), (const uint8_t *)bytes, (const uint8_t *)bytes + len);
+	h->log(channel == BNH_TR_MESSAGE ? BNH_TR_EVENT_WRITE_MESSAGE : BNH_TR_EVENT_WRITE_DECOMMITMENT, len);
+	return 0;
+}
+static int replay_sample(void *user, bn_f128 *out, uint32_t n)
+{
+	bnh_transcript_replay *h = (bnh_transcript_replay *)user;
+	if (!h || (n && !out) || h->samples.size() - h->next_sample < n) return 1;
+	for (uint32_t i = 0; i < n; i++) out[i] = h->samples[h->next_sample++];
+	if (n) h->log(BNH_TR_EVENT_SAMPLE, n);
+	return 0;
+}
+static int replay_sample_bits(void *user, uint32_t bits, uint32_t n, uint64_t *out)
+{
+	bnh_transcript_replay *h = (bnh_transcript_replay *)user;
+	if (!h || (n && !out) || bits > 64 || h->bit_samples.size() - h->next_bits < n) return 1;
+	for (uint32_t i = 0; i < n; i++) out[i] = h->bit_samples[h->next_bits++] & (bits == 64 ? ~(uint64_t)0 : (((uint64_t)1 << bits) - 1));
+	if (n) h->log(BNH_TR_EVENT_SAMPLE_BITS, n);
+	return 0;
+}
+
+int bnh_transcript_replay_new(const bn_f128 *samples, uint64_t n_samples, const uint64_t *bit_samples, uint64_t n_bit_samples, bnh_transcript_replay **out)
+{
+	return guarded([&]() -> int {
+		if (!out || (n_samples && !samples) || (n_bit_samples && !bit_samples)) throw Error(Error::InputValidation, "null argument");
+		std::unique_ptr<bnh_transcript_replay> h(new bnh_transcript_replay);
+		h->samples.assign(samples, samples + n_samples);
+		h->bit_samples.assign(bit_samples, bit_samples + n_bit_samples);
+		h->table = bnh_transcript{h.get(), replay_write, replay_sample, replay_sample_bits};
+		*out = h.release();
+		return 0;
+	});
+}
+const bnh_transcript *bnh_transcript_replay_table(bnh_transcript_replay *handle) { return handle ? &handle->table : nullptr; }
+int bnh_transcript_replay_written(bnh_transcript_replay *handle, uint32_t channel, uint8_t *buf, uint64_t max, uint64_t *len_out)
+{
+	return guarded([&]() -> int {
+		if (!handle || !len_out || channel > BNH_TR_DECOMMITMENT) throw Error(Error::InputValidation, "null argument, or an unknown channel");
+		const std::vector<uint8_t> &w = handle->written[channel];
+		*len_out = w.size();
+		if (w.size() > max) throw Error(Error::InputValidation, "the channel holds more bytes than buf");
+		if (!w.empty()) {
+			if (!buf) throw Error(Error::InputValidation, "null argument");
+			std::memcpy(buf, w.data(), w.size());
+		}
+		return 0;
+	});
+}
+int bnh_transcript_replay_events(bnh_transcript_replay *handle, uint32_t *kinds_out, uint64_t *counts_out, uint64_t max_events, uint64_t *n_events_out)
+{
+	return guarded([&]() -> int {
+		if (!handle || !n_events_out) throw Error(Error::InputValidation, "null argument");
+		*n_events_out = handle->events.size();
+		if (handle->events.size() > max_events) throw Error(Error::InputValidation, "the log holds more events than the arrays");
+		if (!handle->events.empty() && (!kinds_out || !counts_out)) throw Error(Error::InputValidation, "null argument");
+		for (size_t i = 0; i < handle->events.size(); i++) {
+			kinds_out[i] = handle->events[i].first;
+			counts_out[i] = handle->events[i].second;
+		}
+		return 0;
+	});
+}
+void bnh_transcript_replay_free(bnh_transcript_replay *handle) { delete handle; }
 
 // ---- RCCL communicator for the sharded prover (one process per GPU) ----------------------------
 int bnh_rccl_open(const char *librccl_path)
@@ -657,18 +767,22 @@ int bnh_fri_commit_fold(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, ui
 //   query_indices    [n_test_queries], each below 2^index_bits
 //   advice_out       [max_advice_elems]; *n_advice_elems_out: the elements written
 //   phase_ms_out     [3] commit, fold, query phase, or NULL
-int bnh_fri_prove(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities,
-                  uint32_t n_test_queries, const void *d_message, void *d_scratch, uint64_t scratch_elems, const bn_f128 *challenges, uint8_t *roots_out,
-                  const uint64_t *query_indices, bn_f128 *advice_out, uint64_t max_advice_elems, uint64_t *n_advice_elems_out, double *phase_ms_out)
+static int fri_prove_body(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities,
+                          uint32_t n_test_queries, const void *d_message, void *d_scratch, uint64_t scratch_elems, const bn_f128 *challenges, uint8_t *roots_out,
+                          const uint64_t *query_indices, bn_f128 *advice_out, uint64_t max_advice_elems, uint64_t *n_advice_elems_out, double *phase_ms_out, bool is_live,
+                          const bnh_transcript *transcript)
 {
 	return guarded([&]() -> int {
-		if (!ctx || !d_message || !d_scratch || !challenges || !roots_out || !advice_out || !n_advice_elems_out || (n_arities && !fold_arities) ||
-		    (n_test_queries && !query_indices))
+		EntryTranscript et(is_live, transcript, n_test_queries != 0);
+		if (!ctx || !d_message || !d_scratch || (!is_live && !challenges) || !roots_out || !advice_out || !n_advice_elems_out || (n_arities && !fold_arities) ||
+		    (n_test_queries && !is_live && !query_indices))
 			throw Error(Error::InputValidation, "null argument");
 		if ((uint64_t)log_dim + log_batch_size + log_inv_rate >= 48) throw Error(Error::InputValidation, "FRI parameters out of range");
 		ComputeLayer hal(ctx);
 		DeviceBumpAllocator dev_alloc(FSliceMut{d_scratch, (size_t)scratch_elems});
 		FRIParams p(log_dim, log_inv_rate, log_batch_size, std::vector<size_t>(fold_arities, fold_arities + n_arities), n_test_queries);
+		// (before anything is launched or written: a caller's transcript must not absorb a proof whose advice it cannot take)
+		if (p.advice_elems() > max_advice_elems) throw Error(Error::InputValidation, "the advice has more elements than advice_out holds");
 		AdditiveNTT ntt(hal, 5, p.rs_log_len());
 		BinaryMerkleTreeProver merkle(hal);
 		hal.sync();
@@ -678,15 +792,27 @@ int bnh_fri_prove(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t
 		const auto t1 = std::chrono::steady_clock::now();
 		std::memcpy(roots_out, out.commitment.data(), 32);
 		FRIFolder folder(hal, p, ntt, merkle, ComputeMemory::as_const(out.codeword), out.committed);
+		// schedule: the commitment; per fold round ONE sample, then the round's commitment when the folder commits in it
+		// (fri/prove.rs:307-432 as piop/prove.rs:343-358 drives it); then FRIFolder::finish_proof (fri/prove.rs:483-507): the terminate
+		// codeword on the decommitment channel, sample_bits(index_bits) n_test_queries times, the layers and the openings on the
+		// decommitment channel
+		TranscriptSource &tr = et.source({from_raw(challenges, folder.n_rounds())}, query_indices, n_test_queries);
+		tr.write_digest(out.commitment);
 		size_t n_roots = 1;
 		for (size_t r = 0; r < folder.n_rounds(); r++) {
-			auto [has_root, root] = folder.execute_fold_round(dev_alloc, from_raw(challenges[r]));
-			if (has_root) std::memcpy(roots_out + 32 * n_roots++, root.data(), 32);
+			auto [has_root, root] = folder.execute_fold_round(dev_alloc, tr.sample(0, r));
+			if (has_root) {
+				std::memcpy(roots_out + 32 * n_roots++, root.data(), 32);
+				tr.write_digest(root);
+			}
 		}
 		hal.sync();
 		const auto t2 = std::chrono::steady_clock::now();
-		const FriAdvice advice = folder.finish_proof(std::vector<size_t>(query_indices, query_indices + n_test_queries));
+		if (tr.observes_writes()) tr.write_scalars(folder.finalize().first, BNH_TR_DECOMMITMENT);
+		const std::vector<uint64_t> drawn = tr.sample_bits_vec((uint32_t)p.index_bits(), 0, n_test_queries);
+		const FriAdvice advice = folder.finish_proof(std::vector<size_t>(drawn.begin(), drawn.end()));
 		const auto t3 = std::chrono::steady_clock::now(); // (finish_proof returns after its synchronisation)
+		tr.write_scalars(advice.block.data() + advice.terminate_elems, advice.block.size() - advice.terminate_elems, BNH_TR_DECOMMITMENT);
 		if (advice.block.size() > max_advice_elems) throw Error(Error::InputValidation, "the advice has more elements than advice_out holds");
 		to_raw(advice.block, advice_out);
 		*n_advice_elems_out = advice.block.size();
@@ -697,6 +823,22 @@ int bnh_fri_prove(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t
 		}
 		return 0;
 	});
+}
+
+int bnh_fri_prove(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities,
+                  uint32_t n_test_queries, const void *d_message, void *d_scratch, uint64_t scratch_elems, const bn_f128 *challenges, uint8_t *roots_out,
+                  const uint64_t *query_indices, bn_f128 *advice_out, uint64_t max_advice_elems, uint64_t *n_advice_elems_out, double *phase_ms_out)
+{
+	return fri_prove_body(ctx, log_dim, log_inv_rate, log_batch_size, fold_arities, n_arities, n_test_queries, d_message, d_scratch, scratch_elems, challenges, roots_out,
+	                      query_indices, advice_out, max_advice_elems, n_advice_elems_out, phase_ms_out, false, nullptr);
+}
+
+int bnh_fri_prove_live(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities,
+                       uint32_t n_test_queries, const void *d_message, void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript, uint8_t *roots_out,
+                       bn_f128 *advice_out, uint64_t max_advice_elems, uint64_t *n_advice_elems_out, double *phase_ms_out)
+{
+	return fri_prove_body(ctx, log_dim, log_inv_rate, log_batch_size, fold_arities, n_arities, n_test_queries, d_message, d_scratch, scratch_elems, nullptr, roots_out, nullptr,
+	                      advice_out, max_advice_elems, n_advice_elems_out, phase_ms_out, true, transcript);
 }
 
 // diagnostic: the query phase timed two ways on the same resident codewords and trees (tools/bench_fri_query.py).  One commit and
@@ -784,6 +926,8 @@ struct PiopQueryPhase {
 	bn_f128 *advice_out;
 	uint64_t max_advice_elems;
 	uint64_t *n_advice_elems_out;
+	bool is_live = false; // the _live form: no sample array is read, everything is drawn from `transcript`
+	const bnh_transcript *transcript = nullptr;
 };
 static int piop_prove_body(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
                     const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims, const bn_f128 *claim_sums,
@@ -794,12 +938,14 @@ static int piop_prove_body(bn_ctx *ctx, uint32_t n_committed, const uint32_t *co
                     const PiopQueryPhase *query = nullptr)
 {
 	{
+		const bool is_live = query && query->is_live;
+		EntryTranscript et(is_live, query ? query->transcript : nullptr, n_test_queries != 0);
 		if (!ctx || !items_out || !n_items_out || !scalars_out || !n_scalars_out || !digests_out || !n_digests_out)
 			throw Error(Error::InputValidation, "null argument");
 		if ((n_committed && (!committed_n_vars || !d_committed)) || (n_transparent && (!transparent_n_vars || !d_transparent)) || (n_claims && (!claims || !claim_sums)) ||
 		    (n_arities && !fold_arities) || (n_batch_coeffs && !batch_coeffs) || (n_challenges && !challenges))
 			throw Error(Error::InputValidation, "null argument");
-		if (query && (!query->advice_out || !query->n_advice_elems_out || (n_test_queries && !query->query_indices))) throw Error(Error::InputValidation, "null argument");
+		if (query && (!query->advice_out || !query->n_advice_elems_out || (n_test_queries && !is_live && !query->query_indices))) throw Error(Error::InputValidation, "null argument");
 		for (uint32_t i = 0; i < n_committed; i++)
 			if (committed_n_vars[i] >= 48 || !d_committed[i]) throw Error(Error::InputValidation, "committed multilinear: null, or its number of variables out of range (< 48)");
 		for (uint32_t i = 0; i < n_transparent; i++)
@@ -829,6 +975,8 @@ static int piop_prove_body(bn_ctx *ctx, uint32_t n_committed, const uint32_t *co
 			cl.push_back(PIOPSumcheckClaim{claims[3 * i], claims[3 * i + 1], claims[3 * i + 2], from_raw(claim_sums[i])});
 		const std::vector<B128> bcs = from_raw(batch_coeffs, n_batch_coeffs), chs = from_raw(challenges, n_challenges);
 		FRIParams p(log_dim, log_inv_rate, log_batch_size, std::vector<size_t>(fold_arities, fold_arities + n_arities), n_test_queries);
+		// (before anything is launched or written: a caller's transcript must not absorb a proof whose advice it cannot take)
+		if (query && p.advice_elems() > query->max_advice_elems) throw Error(Error::InputValidation, "the advice has more elements than advice_out holds");
 		AdditiveNTT ntt(hal, 5, p.rs_log_len());
 		BinaryMerkleTreeProver merkle(hal);
 		hal.sync();
@@ -838,9 +986,11 @@ static int piop_prove_body(bn_ctx *ctx, uint32_t n_committed, const uint32_t *co
 		const auto t1 = std::chrono::steady_clock::now();
 		if (AbiProf::on()) AbiProf::get() = AbiProf{};
 		std::vector<size_t> query_indices;
-		if (query) query_indices.assign(query->query_indices, query->query_indices + n_test_queries);
-		PiopProveOutput out = piop_prove_impl(hal, dev_alloc, host_alloc, p, ntt, merkle, commit_meta, co.second, co.first, committed, transparents, cl, bcs, chs,
-		                                      query ? &query_indices : nullptr);
+		if (query && !is_live) query_indices.assign(query->query_indices, query->query_indices + n_test_queries);
+		PiopProveOutput out = is_live ? piop_prove_live(hal, dev_alloc, host_alloc, p, ntt, merkle, commit_meta, co.second, co.first, committed, transparents, cl,
+		                                                et.source({}), true)
+		                              : piop_prove_impl(hal, dev_alloc, host_alloc, p, ntt, merkle, commit_meta, co.second, co.first, committed, transparents, cl, bcs, chs,
+		                                                query ? &query_indices : nullptr);
 		hal.sync();
 		const auto t2 = std::chrono::steady_clock::now();
 		if (AbiProf::on()) {
@@ -933,6 +1083,7 @@ static int piop_prove_committed_body(bn_ctx *ctx, uint32_t n_committed, const ui
                              uint32_t max_digests, uint32_t *n_digests_out, double *phase_ms_out, const PiopQueryPhase *query)
 {
 	return guarded([&]() -> int {
+		if (query && query->is_live) LiveTranscript(query->transcript, n_test_queries != 0); // (a null table is rejected before anything else is read)
 		if (!d_codeword || !d_tree || (n_arities && !fold_arities)) throw Error(Error::InputValidation, "null argument");
 		const PiopCommitStep commit = [&](ComputeLayer &hal, DeviceBumpAllocator &, const FRIParams &p, const AdditiveNTT &, BinaryMerkleTreeProver &) {
 			BinaryMerkleTree tree;
@@ -980,6 +1131,21 @@ int bnh_piop_prove_committed_open(bn_ctx *ctx, uint32_t n_committed, const uint3
 	                                 log_inv_rate, log_batch_size, fold_arities, n_arities, n_test_queries, d_codeword, d_tree, d_scratch, scratch_elems, batch_coeffs,
 	                                 n_batch_coeffs, challenges, n_challenges, items_out, max_items, n_items_out, scalars_out, max_scalars, n_scalars_out, digests_out,
 	                                 max_digests, n_digests_out, phase_ms_out, &query);
+}
+
+// bnh_piop_prove_committed_open against the caller's transcript
+int bnh_piop_prove_committed_open_live(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
+                                       const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims,
+                                       const bn_f128 *claim_sums, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities,
+                                       uint32_t n_arities, uint32_t n_test_queries, const void *d_codeword, const void *d_tree, void *d_scratch, uint64_t scratch_elems,
+                                       const bnh_transcript *transcript, uint32_t *items_out, uint32_t max_items, uint32_t *n_items_out, bn_f128 *scalars_out,
+                                       uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out, uint32_t max_digests, uint32_t *n_digests_out,
+                                       double *phase_ms_out, bn_f128 *advice_out, uint64_t max_advice_elems, uint64_t *n_advice_elems_out)
+{
+	const PiopQueryPhase query{nullptr, advice_out, max_advice_elems, n_advice_elems_out, true, transcript};
+	return piop_prove_committed_body(ctx, n_committed, committed_n_vars, d_committed, n_transparent, transparent_n_vars, d_transparent, n_claims, claims, claim_sums, log_dim,
+	                                 log_inv_rate, log_batch_size, fold_arities, n_arities, n_test_queries, d_codeword, d_tree, d_scratch, scratch_elems, nullptr, 0, nullptr, 0,
+	                                 items_out, max_items, n_items_out, scalars_out, max_scalars, n_scalars_out, digests_out, max_digests, n_digests_out, phase_ms_out, &query);
 }
 
 static thread_local double g_piop_commit_ms = 0;
@@ -1060,13 +1226,15 @@ double bnh_piop_commit_last_ms(void) { return g_piop_commit_ms; }
 //   comp_indices / sums: likewise concatenated; batch_coeffs[n_provers]; challenges[max n_vars]
 //   round_proofs_out[2 * total_rounds]: the truncated round polynomial of every round (missing coefficients zero);
 //   final_evals_out: the provers' final evaluations concatenated in finishing (= input) order
-int bnh_batch_sumcheck_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const void *const *d_multilins, const uint32_t *comp_indices,
-                             const bn_f128 *sums, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges,
-                             bn_f128 *round_proofs_out, bn_f128 *final_evals_out)
+static int batch_sumcheck_prove_body(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const void *const *d_multilins, const uint32_t *comp_indices,
+                                     const bn_f128 *sums, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges,
+                                     bn_f128 *round_proofs_out, bn_f128 *final_evals_out, bool is_live, const bnh_transcript *transcript)
 {
 	return guarded([&]() -> int {
 		// (public entry point: every pointer it dereferences and every shift amount it derives is checked first -- ADVICE r5)
-		if (!ctx || (n_provers && (!prover_desc || !batch_coeffs)) || !challenges || !round_proofs_out || !final_evals_out || (!d_scratch && scratch_elems))
+		EntryTranscript et(is_live, transcript);
+		if (!ctx || (n_provers && !prover_desc) || (!is_live && ((n_provers && !batch_coeffs) || !challenges)) || !round_proofs_out || !final_evals_out ||
+		    (!d_scratch && scratch_elems))
 			throw Error(Error::InputValidation, "null argument");
 		size_t total_m = 0, total_c = 0;
 		for (uint32_t i = 0; i < n_provers; i++) {
@@ -1093,10 +1261,31 @@ int bnh_batch_sumcheck_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_t *pr
 			at_ml += m;
 			at_c += nc;
 		}
-		SumcheckBatchProver<BivariateSumcheckProver> batch(std::move(provers), from_raw(batch_coeffs, n_provers));
-		put_batch_output(batch.run(from_raw(challenges, batch.total_rounds()).data()), round_proofs_out, final_evals_out);
+		// front_loaded::BatchProver::new (the batch coefficients, front_loaded.rs:51-59), then run (:175-197)
+		const size_t total_rounds = provers.empty() ? 0 : provers.back()->n_vars();
+		enum { BatchCoeffs = 0, Challenges = 1 };
+		TranscriptSource &tr = et.source({from_raw(batch_coeffs, n_provers), from_raw(challenges, total_rounds)});
+		const std::vector<B128> bcs = tr.sample_vec(BatchCoeffs, 0, n_provers);
+		SumcheckBatchProver<BivariateSumcheckProver> batch(std::move(provers), bcs);
+		put_batch_output(batch.run(tr, Challenges), round_proofs_out, final_evals_out);
 		return 0;
 	});
+}
+
+int bnh_batch_sumcheck_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const void *const *d_multilins, const uint32_t *comp_indices,
+                             const bn_f128 *sums, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *challenges,
+                             bn_f128 *round_proofs_out, bn_f128 *final_evals_out)
+{
+	return batch_sumcheck_prove_body(ctx, n_provers, prover_desc, d_multilins, comp_indices, sums, d_scratch, scratch_elems, batch_coeffs, challenges, round_proofs_out,
+	                                 final_evals_out, false, nullptr);
+}
+
+int bnh_batch_sumcheck_prove_live(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const void *const *d_multilins, const uint32_t *comp_indices,
+                                  const bn_f128 *sums, void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript, bn_f128 *round_proofs_out,
+                                  bn_f128 *final_evals_out)
+{
+	return batch_sumcheck_prove_body(ctx, n_provers, prover_desc, d_multilins, comp_indices, sums, d_scratch, scratch_elems, nullptr, nullptr, round_proofs_out,
+	                                 final_evals_out, true, transcript);
 }
 
 // EqIndSumcheckProver (crates/core/src/protocols/sumcheck/prove/eq_ind.rs:378-644; binius_amd/host/eq_ind.hpp) over the old HAL
@@ -1108,14 +1297,15 @@ int bnh_batch_sumcheck_prove(bn_ctx *ctx, uint32_t n_provers, const uint32_t *pr
 //   d_eq_ind: 2^(n_vars - 1) elements of scratch for the indicator's partial evaluations (expanded here, eq_ind.rs:430-446)
 //   round_coeffs_out[(D + 2) * n_vars], D = max(2, largest degree): the round polynomials have degree D + 1 (D = 2 for the tables'
 //   constraints: four coefficients per round); final_evals_out[n_mls + 1] (the last one: the indicator's prefix evaluation)
-int bnh_eqind_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void *const *d_multilins, uint32_t n_comps, const bn_step *steps,
-                             const uint32_t *n_steps, const bn_step *steps_inf, const uint32_t *n_steps_inf, const uint32_t *degrees, const bn_f128 *sums,
-                             const bn_f128 *eq_ind_challenges, void *d_eq_ind, uint64_t eq_ind_elems, const bn_f128 *batch_coeff, const bn_f128 *challenges,
-                             bn_f128 *round_coeffs_out, bn_f128 *final_evals_out)
+static int eqind_sumcheck_prove_body(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void *const *d_multilins, uint32_t n_comps, const bn_step *steps,
+                                     const uint32_t *n_steps, const bn_step *steps_inf, const uint32_t *n_steps_inf, const uint32_t *degrees, const bn_f128 *sums,
+                                     const bn_f128 *eq_ind_challenges, void *d_eq_ind, uint64_t eq_ind_elems, const bn_f128 *batch_coeff, const bn_f128 *challenges,
+                                     bn_f128 *round_coeffs_out, bn_f128 *final_evals_out, bool is_live, const bnh_transcript *transcript)
 {
 	return guarded([&]() -> int {
-		if (!ctx || (!d_multilins && n_mls) || (n_comps && (!steps || !n_steps || !steps_inf || !n_steps_inf || !sums)) || !eq_ind_challenges || !d_eq_ind || !batch_coeff ||
-		    !challenges || !round_coeffs_out || !final_evals_out)
+		EntryTranscript et(is_live, transcript);
+		if (!ctx || (!d_multilins && n_mls) || (n_comps && (!steps || !n_steps || !steps_inf || !n_steps_inf || !sums)) || !eq_ind_challenges || !d_eq_ind ||
+		    (!is_live && (!batch_coeff || !challenges)) || !round_coeffs_out || !final_evals_out)
 			throw Error(Error::InputValidation, "null argument");
 		if (n_vars == 0 || n_vars >= 40) throw Error(Error::InputValidation, "n_vars out of range");
 		if (eq_ind_elems < ((uint64_t)1 << (n_vars - 1))) throw Error(Error::InputValidation, "the indicator's scratch holds fewer than 2^(n_vars - 1) elements");
@@ -1139,7 +1329,11 @@ int bnh_eqind_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void 
 			comps.push_back(ec);
 		}
 		EqIndPointProver prover(hal, backend, dev_alloc, n_vars, std::move(mls), std::move(comps), from_raw(sums, n_comps), from_raw(eq_ind_challenges, n_vars));
-		const B128 bc = from_raw(*batch_coeff);
+		// a front-loaded batch of one: its coefficient first; what a round writes is the prover's polynomial times the coefficient
+		// without its last coefficient (front_loaded.rs:128-135), while round_coeffs_out keeps the prover's own coefficients, all of them
+		enum { BatchCoeff = 0, Challenges = 1 };
+		TranscriptSource &tr = et.source({one_sample(batch_coeff), from_raw(challenges, n_vars)});
+		const B128 bc = tr.sample(BatchCoeff, 0);
 		double us_exec = 0, us_fold = 0;
 		const auto t_setup = now();
 		for (uint32_t r = 0; r < n_vars; r++) {
@@ -1147,14 +1341,21 @@ int bnh_eqind_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void 
 			const std::vector<B128> rc = prover.execute(bc);
 			const auto t1 = prof ? now() : t0;
 			to_raw(rc, round_coeffs_out + rc.size() * r);
-			prover.fold(from_raw(challenges[r]));
+			if (tr.observes_writes()) {
+				std::vector<B128> written(rc.begin(), rc.end() - (rc.empty() ? 0 : 1));
+				for (B128 &c : written) c = c * bc;
+				tr.write_scalars(written);
+			}
+			prover.fold(tr.sample(Challenges, r));
 			if (prof) {
 				us_exec += 1e3 * elapsed_ms(t0, t1);
 				us_fold += 1e3 * elapsed_ms(t1);
 			}
 		}
 		const auto t_rounds = now();
-		to_raw(prover.finish(), final_evals_out);
+		const std::vector<B128> final_evals = prover.finish();
+		tr.write_scalars(final_evals);
+		to_raw(final_evals, final_evals_out);
 		if (prof)
 			fprintf(stderr, "[bnh prof] eq-ind sumcheck, %u rounds, %u multilinears, %u compositions: set-up %.1f us, execute %.1f us, fold %.1f us, finish %.1f us\n", n_vars,
 			        n_mls, n_comps, 1e3 * elapsed_ms(t_begin, t_setup), us_exec, us_fold,
@@ -1163,14 +1364,33 @@ int bnh_eqind_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void 
 	});
 }
 
+int bnh_eqind_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void *const *d_multilins, uint32_t n_comps, const bn_step *steps,
+                             const uint32_t *n_steps, const bn_step *steps_inf, const uint32_t *n_steps_inf, const uint32_t *degrees, const bn_f128 *sums,
+                             const bn_f128 *eq_ind_challenges, void *d_eq_ind, uint64_t eq_ind_elems, const bn_f128 *batch_coeff, const bn_f128 *challenges,
+                             bn_f128 *round_coeffs_out, bn_f128 *final_evals_out)
+{
+	return eqind_sumcheck_prove_body(ctx, n_vars, n_mls, d_multilins, n_comps, steps, n_steps, steps_inf, n_steps_inf, degrees, sums, eq_ind_challenges, d_eq_ind, eq_ind_elems,
+	                                 batch_coeff, challenges, round_coeffs_out, final_evals_out, false, nullptr);
+}
+
+int bnh_eqind_sumcheck_prove_live(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void *const *d_multilins, uint32_t n_comps, const bn_step *steps,
+                                  const uint32_t *n_steps, const bn_step *steps_inf, const uint32_t *n_steps_inf, const uint32_t *degrees, const bn_f128 *sums,
+                                  const bn_f128 *eq_ind_challenges, void *d_eq_ind, uint64_t eq_ind_elems, const bnh_transcript *transcript,
+                                  bn_f128 *round_coeffs_out, bn_f128 *final_evals_out)
+{
+	return eqind_sumcheck_prove_body(ctx, n_vars, n_mls, d_multilins, n_comps, steps, n_steps, steps_inf, n_steps_inf, degrees, sums, eq_ind_challenges, d_eq_ind, eq_ind_elems,
+	                                 nullptr, nullptr, round_coeffs_out, final_evals_out, true, transcript);
+}
+
 // gkr_gpa::batch_prove (crates/core/src/protocols/gkr_gpa/prove.rs:33-296) through the C++ mirror binius_amd/host/gkr_gpa.hpp; the
 // arguments are described in include/binius_amd_host.h.
-int bnh_gkr_gpa_prove(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, const void *const *d_inputs, const uint64_t *input_lens, void *const *d_arenas,
-                      void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *sumcheck_challenges, const bn_f128 *gpa_challenges,
-                      bn_f128 *products_out, bn_f128 *round_proofs_out, bn_f128 *layer_evals_out, bn_f128 *final_points_out, bn_f128 *final_evals_out,
-                      double *step_ms_out)
+static int gkr_gpa_prove_body(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, const void *const *d_inputs, const uint64_t *input_lens, void *const *d_arenas,
+                              void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *sumcheck_challenges, const bn_f128 *gpa_challenges,
+                              bn_f128 *products_out, bn_f128 *round_proofs_out, bn_f128 *layer_evals_out, bn_f128 *final_points_out, bn_f128 *final_evals_out,
+                              double *step_ms_out, bool is_live, const bnh_transcript *transcript)
 {
 	return guarded([&]() -> int {
+		EntryTranscript et(is_live, transcript);
 		if (!ctx) throw Error(Error::InputValidation, "null ctx");
 		if (n_claims == 0) return 0;
 		if (!n_vars || !d_inputs || !input_lens || !d_arenas || !products_out || !final_evals_out) throw Error(Error::InputValidation, "null argument");
@@ -1186,33 +1406,52 @@ int bnh_gkr_gpa_prove(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, co
 			if (nv[t] >= 1 && !d_arenas[t]) throw Error(Error::InputValidation, "null layer arena");
 			ars[t] = FSliceMut{d_arenas[t], (size_t)1 << nv[t]};
 		}
-		if (max_n >= 1 && (!d_scratch || !batch_coeffs || !gpa_challenges || !layer_evals_out || !final_points_out)) throw Error(Error::InputValidation, "null argument");
-		if (max_n >= 2 && (!sumcheck_challenges || !round_proofs_out)) throw Error(Error::InputValidation, "null argument");
+		if (max_n >= 1 && (!d_scratch || (!is_live && (!batch_coeffs || !gpa_challenges)) || !layer_evals_out || !final_points_out)) throw Error(Error::InputValidation, "null argument");
+		if (max_n >= 2 && ((!is_live && !sumcheck_challenges) || !round_proofs_out)) throw Error(Error::InputValidation, "null argument");
 		ComputeLayer hal(ctx);
 		Mi355xBackend backend(hal);
-		const GkrGpaOutput out = gkr_gpa_batch_prove(hal, backend, nv, ins, ars, FSliceMut{d_scratch, (size_t)scratch_elems}, from_raw(batch_coeffs, max_n),
-		                                            from_raw(sumcheck_challenges, max_n * (max_n ? max_n - 1 : 0) / 2), from_raw(gpa_challenges, max_n));
+		TranscriptSource &tr = et.source({from_raw(batch_coeffs, max_n), from_raw(sumcheck_challenges, max_n * (max_n ? max_n - 1 : 0) / 2), from_raw(gpa_challenges, max_n)});
+		const GkrGpaOutput out = gkr_gpa_batch_prove(hal, backend, nv, ins, ars, FSliceMut{d_scratch, (size_t)scratch_elems}, tr);
 		put_gkr_gpa_output(out, products_out, round_proofs_out, layer_evals_out, final_points_out, final_evals_out);
 		for (size_t j = 0; step_ms_out && j < out.step_ms.size(); j++) step_ms_out[j] = out.step_ms[j];
 		return 0;
 	});
 }
 
+int bnh_gkr_gpa_prove(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, const void *const *d_inputs, const uint64_t *input_lens, void *const *d_arenas,
+                      void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs, const bn_f128 *sumcheck_challenges, const bn_f128 *gpa_challenges,
+                      bn_f128 *products_out, bn_f128 *round_proofs_out, bn_f128 *layer_evals_out, bn_f128 *final_points_out, bn_f128 *final_evals_out,
+                      double *step_ms_out)
+{
+	return gkr_gpa_prove_body(ctx, n_claims, n_vars, d_inputs, input_lens, d_arenas, d_scratch, scratch_elems, batch_coeffs, sumcheck_challenges, gpa_challenges, products_out,
+	                          round_proofs_out, layer_evals_out, final_points_out, final_evals_out, step_ms_out, false, nullptr);
+}
+
+int bnh_gkr_gpa_prove_live(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, const void *const *d_inputs, const uint64_t *input_lens, void *const *d_arenas,
+                           void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript, bn_f128 *products_out, bn_f128 *round_proofs_out,
+                           bn_f128 *layer_evals_out, bn_f128 *final_points_out, bn_f128 *final_evals_out, double *step_ms_out)
+{
+	return gkr_gpa_prove_body(ctx, n_claims, n_vars, d_inputs, input_lens, d_arenas, d_scratch, scratch_elems, nullptr, nullptr, nullptr, products_out, round_proofs_out,
+	                          layer_evals_out, final_points_out, final_evals_out, step_ms_out, true, transcript);
+}
+
 // gkr_exp::batch_prove (crates/core/src/protocols/gkr_exp/batch_prove.rs:46-315) through the C++ mirror binius_amd/host/gkr_exp.hpp; the
 // arguments and the layout of the outputs are described in include/binius_amd_host.h.
-int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths, const uint32_t *kinds, const void *const *d_exponent_bits,
-                      const bn_f128 *static_bases, const void *const *d_bases, void *const *d_arenas, uint32_t n_claims, const uint32_t *n_vars,
-                      const bn_f128 *eval_points, const bn_f128 *evals, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs,
-                      const bn_f128 *challenges, uint32_t *n_layers_out, uint32_t *rounds_per_layer_out, uint32_t *coeffs_per_round_out,
-                      bn_f128 *round_proofs_out, uint32_t *provers_per_layer_out, uint32_t *evals_per_prover_out, bn_f128 *multilinear_evals_out,
-                      uint32_t *claims_per_layer_out, uint32_t *claim_n_vars_out, bn_f128 *claim_points_out, bn_f128 *claim_evals_out, double *layer_ms_out)
+static int gkr_exp_prove_body(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths, const uint32_t *kinds, const void *const *d_exponent_bits,
+                              const bn_f128 *static_bases, const void *const *d_bases, void *const *d_arenas, uint32_t n_claims, const uint32_t *n_vars,
+                              const bn_f128 *eval_points, const bn_f128 *evals, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs,
+                              const bn_f128 *challenges, uint32_t *n_layers_out, uint32_t *rounds_per_layer_out, uint32_t *coeffs_per_round_out,
+                              bn_f128 *round_proofs_out, uint32_t *provers_per_layer_out, uint32_t *evals_per_prover_out, bn_f128 *multilinear_evals_out,
+                              uint32_t *claims_per_layer_out, uint32_t *claim_n_vars_out, bn_f128 *claim_points_out, bn_f128 *claim_evals_out, double *layer_ms_out,
+                              bool is_live, const bnh_transcript *transcript)
 {
 	return guarded([&]() -> int {
+		EntryTranscript et(is_live, transcript);
 		if (!ctx) throw Error(Error::InputValidation, "null ctx");
 		if (n_witnesses != n_claims) throw Error(Error::InputValidation, "MismatchedWitnessClaimLength");
 		if (n_layers_out) *n_layers_out = 0;
 		if (n_claims == 0) return 0;
-		if (!widths || !kinds || !d_exponent_bits || !static_bases || !d_bases || !d_arenas || !n_vars || !evals || !batch_coeffs || !n_layers_out ||
+		if (!widths || !kinds || !d_exponent_bits || !static_bases || !d_bases || !d_arenas || !n_vars || !evals || (!is_live && !batch_coeffs) || !n_layers_out ||
 		    !rounds_per_layer_out || !coeffs_per_round_out || !round_proofs_out || !provers_per_layer_out || !evals_per_prover_out || !multilinear_evals_out ||
 		    !claims_per_layer_out || !claim_n_vars_out || !claim_points_out || !claim_evals_out)
 			throw Error(Error::InputValidation, "null argument");
@@ -1239,12 +1478,12 @@ int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths,
 			max_w = std::max(max_w, c.width);
 			max_n = std::max(max_n, c.n_vars);
 		}
-		if (max_n && !challenges) throw Error(Error::InputValidation, "null argument");
+		if (max_n && !is_live && !challenges) throw Error(Error::InputValidation, "null argument");
 		if (!d_scratch && scratch_elems) throw Error(Error::InputValidation, "null argument");
 		ComputeLayer hal(ctx);
 		Mi355xBackend backend(hal);
-		const GkrExpOutput out = gkr_exp_batch_prove(hal, backend, n_witnesses, claims, FSliceMut{d_scratch, (size_t)scratch_elems}, from_raw(batch_coeffs, max_w * k),
-		                                            from_raw(challenges, max_w * max_n));
+		TranscriptSource &tr = et.source({from_raw(batch_coeffs, max_w * k), from_raw(challenges, max_w * max_n)});
+		const GkrExpOutput out = gkr_exp_batch_prove(hal, backend, n_witnesses, claims, FSliceMut{d_scratch, (size_t)scratch_elems}, tr);
 		*n_layers_out = (uint32_t)out.round_proofs.size();
 		for (size_t L = 0; L < out.round_proofs.size(); L++) {
 			rounds_per_layer_out[L] = (uint32_t)out.round_proofs[L].size();
@@ -1270,9 +1509,34 @@ int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths,
 	});
 }
 
+int bnh_gkr_exp_prove(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths, const uint32_t *kinds, const void *const *d_exponent_bits,
+                      const bn_f128 *static_bases, const void *const *d_bases, void *const *d_arenas, uint32_t n_claims, const uint32_t *n_vars,
+                      const bn_f128 *eval_points, const bn_f128 *evals, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs,
+                      const bn_f128 *challenges, uint32_t *n_layers_out, uint32_t *rounds_per_layer_out, uint32_t *coeffs_per_round_out,
+                      bn_f128 *round_proofs_out, uint32_t *provers_per_layer_out, uint32_t *evals_per_prover_out, bn_f128 *multilinear_evals_out,
+                      uint32_t *claims_per_layer_out, uint32_t *claim_n_vars_out, bn_f128 *claim_points_out, bn_f128 *claim_evals_out, double *layer_ms_out)
+{
+	return gkr_exp_prove_body(ctx, n_witnesses, widths, kinds, d_exponent_bits, static_bases, d_bases, d_arenas, n_claims, n_vars, eval_points, evals, d_scratch, scratch_elems,
+	                          batch_coeffs, challenges, n_layers_out, rounds_per_layer_out, coeffs_per_round_out, round_proofs_out, provers_per_layer_out,
+	                          evals_per_prover_out, multilinear_evals_out, claims_per_layer_out, claim_n_vars_out, claim_points_out, claim_evals_out, layer_ms_out, false,
+	                          nullptr);
+}
+
+int bnh_gkr_exp_prove_live(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths, const uint32_t *kinds, const void *const *d_exponent_bits,
+                           const bn_f128 *static_bases, const void *const *d_bases, void *const *d_arenas, uint32_t n_claims, const uint32_t *n_vars,
+                           const bn_f128 *eval_points, const bn_f128 *evals, void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript,
+                           uint32_t *n_layers_out, uint32_t *rounds_per_layer_out, uint32_t *coeffs_per_round_out, bn_f128 *round_proofs_out,
+                           uint32_t *provers_per_layer_out, uint32_t *evals_per_prover_out, bn_f128 *multilinear_evals_out, uint32_t *claims_per_layer_out,
+                           uint32_t *claim_n_vars_out, bn_f128 *claim_points_out, bn_f128 *claim_evals_out, double *layer_ms_out)
+{
+	return gkr_exp_prove_body(ctx, n_witnesses, widths, kinds, d_exponent_bits, static_bases, d_bases, d_arenas, n_claims, n_vars, eval_points, evals, d_scratch, scratch_elems,
+	                          nullptr, nullptr, n_layers_out, rounds_per_layer_out, coeffs_per_round_out, round_proofs_out, provers_per_layer_out, evals_per_prover_out,
+	                          multilinear_evals_out, claims_per_layer_out, claim_n_vars_out, claim_points_out, claim_evals_out, layer_ms_out, true, transcript);
+}
+
 // The product-check phase of the constraint-system prover (core/src/constraint_system/prove.rs:276-428) through the C++ mirror
 // binius_amd/host/flush.hpp; the arguments and the layout of the outputs are described in include/binius_amd_host.h.
-int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *channel_ids, const uint32_t *flush_n_vars, const uint32_t *n_selectors,
+static int flush_prodcheck_prove_body(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *channel_ids, const uint32_t *flush_n_vars, const uint32_t *n_selectors,
                               const uint32_t *selector_ids, const void *const *d_selectors, const uint32_t *n_entries, const uint32_t *entry_kinds,
                               const uint32_t *entry_ids, const void *const *d_entry_columns, const uint32_t *entry_levels, const bn_f128 *entry_consts,
                               uint32_t n_nonzero, const uint32_t *nonzero_ids, const void *const *d_nonzero_columns, const uint32_t *nonzero_levels,
@@ -1282,17 +1546,22 @@ int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *c
                               bn_f128 *products_out, bn_f128 *gpa_round_proofs_out, bn_f128 *gpa_layer_evals_out, bn_f128 *gpa_final_points_out,
                               bn_f128 *gpa_final_evals_out, uint32_t *n_checks_out, uint32_t *check_desc_out, uint32_t *check_ids_out,
                               bn_f128 *check_round_proofs_out, bn_f128 *check_final_evals_out, uint32_t *n_linear_out, uint32_t *linear_flushes_out,
-                              double *phase_ms_out)
+                              double *phase_ms_out, bool is_live, const bnh_transcript *transcript)
 {
 	return guarded([&]() -> int {
+		EntryTranscript et(is_live, transcript);
 		if (!ctx) throw Error(Error::InputValidation, "null ctx");
 		if (n_checks_out) *n_checks_out = 0;
 		if (n_linear_out) *n_linear_out = 0;
-		if (n_flushes + n_nonzero == 0) return 0;
-		if (!mixing_challenge || !d_scratch || !products_out || !gpa_final_evals_out || !n_checks_out || !n_linear_out) throw Error(Error::InputValidation, "null argument");
+		if (n_flushes + n_nonzero == 0) {
+			// (nothing to prove, but the reference still draws the mixing and the permutation challenges here, prove.rs:329-330)
+			if (is_live) flush_prodcheck_empty(*et.live, n_channels);
+			return 0;
+		}
+		if ((!is_live && !mixing_challenge) || !d_scratch || !products_out || !gpa_final_evals_out || !n_checks_out || !n_linear_out) throw Error(Error::InputValidation, "null argument");
 		if (n_flushes && (!channel_ids || !flush_n_vars || !n_selectors || !n_entries || !entry_kinds || !entry_ids || !d_entry_columns || !entry_levels || !entry_consts ||
-		                  !permutation_challenges || !prefix_lens_out || !check_desc_out || !check_ids_out || !check_round_proofs_out || !check_final_evals_out ||
-		                  !linear_flushes_out || !red_batch_coeffs))
+		                  (!is_live && !permutation_challenges) || !prefix_lens_out || !check_desc_out || !check_ids_out || !check_round_proofs_out || !check_final_evals_out ||
+		                  !linear_flushes_out || (!is_live && !red_batch_coeffs)))
 			throw Error(Error::InputValidation, "null argument");
 		if (n_nonzero && (!nonzero_ids || !d_nonzero_columns || !nonzero_levels || !nonzero_n_vars)) throw Error(Error::InputValidation, "null argument");
 		std::vector<FlushSpec> flushes(n_flushes);
@@ -1321,18 +1590,19 @@ int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *c
 			max_n = std::max(max_n, nonzero[i].n_vars);
 		}
 		if (max_n > BN_PRODUCT_TREE_MAX_VARS) throw Error(Error::InputValidation, "n_vars out of range (0 .. 28)");
-		if (max_n >= 1 && (!gpa_batch_coeffs || !gpa_challenges || !gpa_layer_evals_out || !gpa_final_points_out)) throw Error(Error::InputValidation, "null argument");
-		if (max_n >= 2 && (!gpa_sumcheck_challenges || !gpa_round_proofs_out)) throw Error(Error::InputValidation, "null argument");
+		if (max_n >= 1 && ((!is_live && (!gpa_batch_coeffs || !gpa_challenges)) || !gpa_layer_evals_out || !gpa_final_points_out)) throw Error(Error::InputValidation, "null argument");
+		if (max_n >= 2 && ((!is_live && !gpa_sumcheck_challenges) || !gpa_round_proofs_out)) throw Error(Error::InputValidation, "null argument");
 		size_t red_n = 0;
 		const std::vector<FlushMleCheck> groups = flush_groups(flushes);
 		for (const FlushMleCheck &g : groups) red_n += g.n_vars;
-		if (red_n && !red_challenges) throw Error(Error::InputValidation, "null argument");
+		if (red_n && !is_live && !red_challenges) throw Error(Error::InputValidation, "null argument");
 		ComputeLayer hal(ctx);
 		Mi355xBackend backend(hal);
-		const FlushProdcheckOutput out =
-		    flush_prodcheck_prove(hal, backend, flushes, nonzero, from_raw(*mixing_challenge), from_raw(permutation_challenges, n_channels),
-		                          FSliceMut{d_scratch, (size_t)scratch_elems}, from_raw(gpa_batch_coeffs, max_n), from_raw(gpa_sumcheck_challenges, max_n * (max_n ? max_n - 1 : 0) / 2),
-		                          from_raw(gpa_challenges, max_n), from_raw(red_batch_coeffs, groups.size()), from_raw(red_challenges, red_n));
+		// (the streams as flush.hpp numbers them: the grand-product argument's three, the reductions' two, the mixing and the permutation challenges)
+		TranscriptSource &tr = et.source({from_raw(gpa_batch_coeffs, max_n), from_raw(gpa_sumcheck_challenges, max_n * (max_n ? max_n - 1 : 0) / 2), from_raw(gpa_challenges, max_n),
+		                                  from_raw(red_batch_coeffs, groups.size()), from_raw(red_challenges, red_n), one_sample(mixing_challenge),
+		                                  from_raw(permutation_challenges, n_channels)});
+		const FlushProdcheckOutput out = flush_prodcheck_prove(hal, backend, flushes, nonzero, n_channels, FSliceMut{d_scratch, (size_t)scratch_elems}, tr);
 		for (uint32_t f = 0; f < n_flushes; f++) prefix_lens_out[f] = out.prefix_lens[f];
 		put_gkr_gpa_output(out.gpa, products_out, gpa_round_proofs_out, gpa_layer_evals_out, gpa_final_points_out, gpa_final_evals_out);
 		*n_checks_out = (uint32_t)out.checks.size();
@@ -1354,6 +1624,43 @@ int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *c
 	});
 }
 
+int bnh_flush_prodcheck_prove(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *channel_ids, const uint32_t *flush_n_vars, const uint32_t *n_selectors,
+                              const uint32_t *selector_ids, const void *const *d_selectors, const uint32_t *n_entries, const uint32_t *entry_kinds,
+                              const uint32_t *entry_ids, const void *const *d_entry_columns, const uint32_t *entry_levels, const bn_f128 *entry_consts,
+                              uint32_t n_nonzero, const uint32_t *nonzero_ids, const void *const *d_nonzero_columns, const uint32_t *nonzero_levels,
+                              const uint32_t *nonzero_n_vars, const bn_f128 *mixing_challenge, const bn_f128 *permutation_challenges, uint32_t n_channels,
+                              void *d_scratch, uint64_t scratch_elems, const bn_f128 *gpa_batch_coeffs, const bn_f128 *gpa_sumcheck_challenges,
+                              const bn_f128 *gpa_challenges, const bn_f128 *red_batch_coeffs, const bn_f128 *red_challenges, uint64_t *prefix_lens_out,
+                              bn_f128 *products_out, bn_f128 *gpa_round_proofs_out, bn_f128 *gpa_layer_evals_out, bn_f128 *gpa_final_points_out,
+                              bn_f128 *gpa_final_evals_out, uint32_t *n_checks_out, uint32_t *check_desc_out, uint32_t *check_ids_out,
+                              bn_f128 *check_round_proofs_out, bn_f128 *check_final_evals_out, uint32_t *n_linear_out, uint32_t *linear_flushes_out,
+                              double *phase_ms_out)
+{
+	return flush_prodcheck_prove_body(ctx, n_flushes, channel_ids, flush_n_vars, n_selectors, selector_ids, d_selectors, n_entries, entry_kinds, entry_ids, d_entry_columns,
+	                                  entry_levels, entry_consts, n_nonzero, nonzero_ids, d_nonzero_columns, nonzero_levels, nonzero_n_vars, mixing_challenge,
+	                                  permutation_challenges, n_channels, d_scratch, scratch_elems, gpa_batch_coeffs, gpa_sumcheck_challenges, gpa_challenges, red_batch_coeffs,
+	                                  red_challenges, prefix_lens_out, products_out, gpa_round_proofs_out, gpa_layer_evals_out, gpa_final_points_out, gpa_final_evals_out,
+	                                  n_checks_out, check_desc_out, check_ids_out, check_round_proofs_out, check_final_evals_out, n_linear_out, linear_flushes_out, phase_ms_out,
+	                                  false, nullptr);
+}
+
+int bnh_flush_prodcheck_prove_live(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *channel_ids, const uint32_t *flush_n_vars, const uint32_t *n_selectors,
+                                   const uint32_t *selector_ids, const void *const *d_selectors, const uint32_t *n_entries, const uint32_t *entry_kinds,
+                                   const uint32_t *entry_ids, const void *const *d_entry_columns, const uint32_t *entry_levels, const bn_f128 *entry_consts,
+                                   uint32_t n_nonzero, const uint32_t *nonzero_ids, const void *const *d_nonzero_columns, const uint32_t *nonzero_levels,
+                                   const uint32_t *nonzero_n_vars, uint32_t n_channels, void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript,
+                                   uint64_t *prefix_lens_out, bn_f128 *products_out, bn_f128 *gpa_round_proofs_out, bn_f128 *gpa_layer_evals_out,
+                                   bn_f128 *gpa_final_points_out, bn_f128 *gpa_final_evals_out, uint32_t *n_checks_out, uint32_t *check_desc_out, uint32_t *check_ids_out,
+                                   bn_f128 *check_round_proofs_out, bn_f128 *check_final_evals_out, uint32_t *n_linear_out, uint32_t *linear_flushes_out,
+                                   double *phase_ms_out)
+{
+	return flush_prodcheck_prove_body(ctx, n_flushes, channel_ids, flush_n_vars, n_selectors, selector_ids, d_selectors, n_entries, entry_kinds, entry_ids, d_entry_columns,
+	                                  entry_levels, entry_consts, n_nonzero, nonzero_ids, d_nonzero_columns, nonzero_levels, nonzero_n_vars, nullptr, nullptr, n_channels,
+	                                  d_scratch, scratch_elems, nullptr, nullptr, nullptr, nullptr, nullptr, prefix_lens_out, products_out, gpa_round_proofs_out,
+	                                  gpa_layer_evals_out, gpa_final_points_out, gpa_final_evals_out, n_checks_out, check_desc_out, check_ids_out, check_round_proofs_out,
+	                                  check_final_evals_out, n_linear_out, linear_flushes_out, phase_ms_out, true, transcript);
+}
+
 // One round of evalcheck's bivariate sumchecks (evalcheck/subclaims.rs:549-586 with the witness construction in front of it) through
 // the C++ mirror binius_amd/host/evalcheck.hpp; the arguments and the layout of the outputs are described in include/binius_amd_host.h.
 // (with_lincomb: the _lc entry, which alone accepts BNH_EC_LINCOMB and reads the term arrays and the offsets)
@@ -1361,10 +1668,12 @@ static int evalcheck_bivariate_prove_capi(bool with_lincomb, bn_ctx *ctx, uint32
                                           const void *const *d_columns, uint32_t n_terms, const uint32_t *term_levels, const void *const *d_term_columns,
                                           const bn_f128 *term_coeffs, const bn_f128 *ml_offsets, const bn_f128 *point_pool, uint32_t pool_len,
                                           const uint32_t *comp_indices, const bn_f128 *sums, void *d_scratch, uint64_t scratch_elems, const bn_f128 *batch_coeffs,
-                                          const bn_f128 *challenges, bn_f128 *round_proofs_out, bn_f128 *final_evals_out)
+                                          const bn_f128 *challenges, bn_f128 *round_proofs_out, bn_f128 *final_evals_out, bool is_live = false,
+                                          const bnh_transcript *transcript = nullptr)
 {
 	return guarded([&]() -> int {
-		if (!ctx || (n_provers && (!prover_desc || !batch_coeffs)) || !round_proofs_out || !final_evals_out || (!d_scratch && scratch_elems) || (pool_len && !point_pool))
+		EntryTranscript et(is_live, transcript);
+		if (!ctx || (n_provers && (!prover_desc || (!is_live && !batch_coeffs))) || !round_proofs_out || !final_evals_out || (!d_scratch && scratch_elems) || (pool_len && !point_pool))
 			throw Error(Error::InputValidation, "null argument");
 		size_t total_m = 0, total_c = 0, max_b = 0;
 		for (uint32_t i = 0; i < n_provers; i++) {
@@ -1373,7 +1682,7 @@ static int evalcheck_bivariate_prove_capi(bool with_lincomb, bn_ctx *ctx, uint32
 			total_m += prover_desc[3 * i + 1];
 			total_c += prover_desc[3 * i + 2];
 		}
-		if ((total_m && (!ml_desc || !d_columns)) || (total_c && (!comp_indices || !sums)) || (max_b && !challenges)) throw Error(Error::InputValidation, "null argument");
+		if ((total_m && (!ml_desc || !d_columns)) || (total_c && (!comp_indices || !sums)) || (max_b && !is_live && !challenges)) throw Error(Error::InputValidation, "null argument");
 		if (n_terms && (!term_levels || !d_term_columns || !term_coeffs)) throw Error(Error::InputValidation, "null argument");
 		const std::vector<B128> pool = from_raw(point_pool, pool_len);
 		std::vector<EvalcheckTerm> terms(n_terms);
@@ -1432,8 +1741,8 @@ static int evalcheck_bivariate_prove_capi(bool with_lincomb, bn_ctx *ctx, uint32
 			at_c += nc;
 		}
 		ComputeLayer hal(ctx);
-		const EvalcheckOutput out =
-			evalcheck_bivariate_prove(hal, provers, pool, FSliceMut{d_scratch, (size_t)scratch_elems}, from_raw(batch_coeffs, n_provers), from_raw(challenges, max_b), terms);
+		TranscriptSource &tr = et.source({from_raw(batch_coeffs, n_provers), from_raw(challenges, max_b)});
+		const EvalcheckOutput out = evalcheck_bivariate_prove(hal, provers, pool, FSliceMut{d_scratch, (size_t)scratch_elems}, tr, terms);
 		put_batch_output(out, round_proofs_out, final_evals_out);
 		return 0;
 	});
@@ -1456,6 +1765,15 @@ int bnh_evalcheck_bivariate_prove_lc(bn_ctx *ctx, uint32_t n_provers, const uint
 {
 	return evalcheck_bivariate_prove_capi(true, ctx, n_provers, prover_desc, ml_desc, d_columns, n_terms, term_levels, d_term_columns, term_coeffs, ml_offsets, point_pool,
 	                                      pool_len, comp_indices, sums, d_scratch, scratch_elems, batch_coeffs, challenges, round_proofs_out, final_evals_out);
+}
+
+int bnh_evalcheck_bivariate_prove_lc_live(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const uint32_t *ml_desc, const void *const *d_columns,
+                                          uint32_t n_terms, const uint32_t *term_levels, const void *const *d_term_columns, const bn_f128 *term_coeffs,
+                                          const bn_f128 *ml_offsets, const bn_f128 *point_pool, uint32_t pool_len, const uint32_t *comp_indices, const bn_f128 *sums,
+                                          void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript, bn_f128 *round_proofs_out, bn_f128 *final_evals_out)
+{
+	return evalcheck_bivariate_prove_capi(true, ctx, n_provers, prover_desc, ml_desc, d_columns, n_terms, term_levels, d_term_columns, term_coeffs, ml_offsets, point_pool,
+	                                      pool_len, comp_indices, sums, d_scratch, scratch_elems, nullptr, nullptr, round_proofs_out, final_evals_out, true, transcript);
 }
 
 // The evaluations in front of an evalcheck round (evalcheck/prove.rs:191-275) through evalcheck_evaluate_claims of the same mirror; the
@@ -1516,10 +1834,12 @@ static int zerocheck_batch_prove_c(bn_ctx *ctx, uint32_t n_tables, uint32_t skip
                               const bn_f128 *univariate_challenge, const bn_f128 *sumcheck_challenges, const bn_f128 *reduction_batch_coeff,
                               const bn_f128 *reduction_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *message_out, bn_f128 *round_coeffs_out,
                               bn_f128 *final_evals_out, bn_f128 *reduction_round_coeffs_out, bn_f128 *reduction_final_evals_out, bn_f128 *skipped_challenges_out,
-                              bn_f128 *unskipped_challenges_out, bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out, bool tower)
+                              bn_f128 *unskipped_challenges_out, bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out, bool tower,
+                              bool is_live = false, const bnh_transcript *transcript = nullptr)
 {
 	return guarded([&]() -> int {
-		if (!ctx || !n_tables || !n_vars || !n_cols || !n_comps || !batch_coeffs || !univariate_challenge || !reduction_batch_coeff || !reduction_challenges || !final_evals_out ||
+		EntryTranscript et(is_live, transcript);
+		if (!ctx || !n_tables || !n_vars || !n_cols || !n_comps || (!is_live && (!batch_coeffs || !univariate_challenge || !reduction_batch_coeff || !reduction_challenges)) || !final_evals_out ||
 		    !reduction_round_coeffs_out || !reduction_final_evals_out || !skipped_challenges_out || !concat_multilinear_evals_out || (!d_scratch && scratch_elems))
 			throw Error(Error::InputValidation, "null argument");
 		if (skip_rounds < 1 || skip_rounds > 8) throw Error(Error::InputValidation, "zerocheck: skip_rounds out of range (1 .. 8)");
@@ -1536,7 +1856,7 @@ static int zerocheck_batch_prove_c(bn_ctx *ctx, uint32_t n_tables, uint32_t skip
 		if ((total_cols && (!d_cols || !tower_levels)) || (total_comps && (!steps || !n_steps || !steps_inf || !n_steps_inf || !degrees)))
 			throw Error(Error::InputValidation, "null argument");
 		const size_t rounds = max_n - skip_rounds;
-		if (rounds && (!zerocheck_challenges || !sumcheck_challenges || !round_coeffs_out || !unskipped_challenges_out)) throw Error(Error::InputValidation, "null argument");
+		if (rounds && ((!is_live && (!zerocheck_challenges || !sumcheck_challenges)) || !round_coeffs_out || !unskipped_challenges_out)) throw Error(Error::InputValidation, "null argument");
 		ComputeLayer hal(ctx);
 		std::vector<ZerocheckTable> tables(n_tables);
 		size_t at_col = 0, at_comp = 0, at_step = 0, at_inf = 0;
@@ -1557,10 +1877,9 @@ static int zerocheck_batch_prove_c(bn_ctx *ctx, uint32_t n_tables, uint32_t skip
 				at_inf += n_steps_inf[at_comp];
 			}
 		}
-		const ZerocheckBatchOutput out = zerocheck_batch_prove(hal, tables, skip_rounds, from_raw(zerocheck_challenges, rounds), from_raw(batch_coeffs, n_tables),
-		                                                       from_raw(*univariate_challenge), from_raw(sumcheck_challenges, rounds),
-		                                                       from_raw(*reduction_batch_coeff), from_raw(reduction_challenges, skip_rounds),
-		                                                       FSliceMut{d_scratch, (size_t)scratch_elems}, tower);
+		TranscriptSource &tr = et.source({from_raw(zerocheck_challenges, rounds), from_raw(batch_coeffs, n_tables), one_sample(univariate_challenge),
+		                                  from_raw(sumcheck_challenges, rounds), one_sample(reduction_batch_coeff), from_raw(reduction_challenges, skip_rounds)});
+		const ZerocheckBatchOutput out = zerocheck_batch_prove(hal, tables, skip_rounds, tr, FSliceMut{d_scratch, (size_t)scratch_elems}, tower);
 		auto put = [](bn_f128 *dst, const std::vector<B128> &v) { return to_raw(v, dst); };
 		if (!out.message.empty()) {
 			if (!message_out) throw Error(Error::InputValidation, "null argument");
@@ -1630,6 +1949,19 @@ int bnh_zerocheck_batch_prove_tower(bn_ctx *ctx, uint32_t n_tables, uint32_t ski
 	                              unskipped_challenges_out, concat_multilinear_evals_out, phase_ms_out, phase_calls_out, true);
 }
 
+int bnh_zerocheck_batch_prove_tower_live(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols, const void *const *d_cols,
+                                         const uint32_t *tower_levels, const uint32_t *n_comps, const bn_step *steps, const uint32_t *n_steps, const bn_step *steps_inf,
+                                         const uint32_t *n_steps_inf, const uint32_t *degrees, const bnh_transcript *transcript, void *d_scratch, uint64_t scratch_elems,
+                                         bn_f128 *message_out, bn_f128 *round_coeffs_out, bn_f128 *final_evals_out, bn_f128 *reduction_round_coeffs_out,
+                                         bn_f128 *reduction_final_evals_out, bn_f128 *skipped_challenges_out, bn_f128 *unskipped_challenges_out,
+                                         bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out)
+{
+	return zerocheck_batch_prove_c(ctx, n_tables, skip_rounds, n_vars, n_cols, d_cols, tower_levels, n_comps, steps, n_steps, steps_inf, n_steps_inf, degrees, nullptr, nullptr,
+	                              nullptr, nullptr, nullptr, nullptr, d_scratch, scratch_elems, message_out, round_coeffs_out, final_evals_out, reduction_round_coeffs_out,
+	                              reduction_final_evals_out, skipped_challenges_out, unskipped_challenges_out, concat_multilinear_evals_out, phase_ms_out, phase_calls_out, true,
+	                              true, transcript);
+}
+
 // ring_switch::prove (crates/core/src/ring_switch/prove.rs:42-144) through the C++ mirror binius_amd/host/ring_switch.hpp; the arguments
 // are described in include/binius_amd_host.h.
 namespace {
@@ -1654,13 +1986,14 @@ uint64_t bnh_ring_switch_scratch_elems(uint32_t n_suffixes, const uint32_t *suff
 	}
 }
 
-int bnh_ring_switch_prove(bn_ctx *ctx, uint32_t n_columns, const void *const *d_columns, const uint32_t *column_desc, const bn_f128 *point_pool, uint32_t pool_len,
+static int ring_switch_prove_body(bn_ctx *ctx, uint32_t n_columns, const void *const *d_columns, const uint32_t *column_desc, const bn_f128 *point_pool, uint32_t pool_len,
                           uint32_t n_suffixes, const uint32_t *suffix_desc, uint32_t n_prefixes, const uint32_t *prefix_kappas, uint32_t n_claims,
                           const uint32_t *claim_desc, const bn_f128 *mixing_challenges, uint32_t n_mixing_challenges, const bn_f128 *row_batch_challenges,
                           uint32_t n_row_batch_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *mixed_tensor_elems_out, bn_f128 *row_batched_evals_out,
-                          void **d_transparents_out, double *phase_ms_out)
+                          void **d_transparents_out, double *phase_ms_out, bool is_live, const bnh_transcript *transcript)
 {
 	return guarded([&]() -> int {
+		EntryTranscript et(is_live, transcript);
 		if (!ctx || (n_columns && (!d_columns || !column_desc)) || (pool_len && !point_pool) || (n_suffixes && !suffix_desc) || (n_prefixes && (!prefix_kappas || !mixed_tensor_elems_out)) ||
 		    (n_claims && (!claim_desc || !row_batched_evals_out || !d_transparents_out)) || (n_mixing_challenges && !mixing_challenges) ||
 		    (n_row_batch_challenges && !row_batch_challenges) || (!d_scratch && scratch_elems))
@@ -1671,9 +2004,10 @@ int bnh_ring_switch_prove(bn_ctx *ctx, uint32_t n_columns, const void *const *d_
 		std::vector<RingSwitchClaim> claims;
 		ring_switch_descs(n_suffixes, suffix_desc, n_claims, claim_desc, suffixes, claims);
 		ComputeLayer hal(ctx);
+		TranscriptSource &tr = et.source({from_raw(mixing_challenges, n_mixing_challenges), from_raw(row_batch_challenges, n_row_batch_challenges)});
 		const RingSwitchOutput out = ring_switch_prove(hal, columns, from_raw(point_pool, pool_len), suffixes, std::vector<uint32_t>(prefix_kappas, prefix_kappas + n_prefixes), claims,
-		                                               from_raw(mixing_challenges, n_mixing_challenges), from_raw(row_batch_challenges, n_row_batch_challenges),
-		                                               FSliceMut{d_scratch, (size_t)scratch_elems});
+		                                               tr, FSliceMut{d_scratch, (size_t)scratch_elems}, is_live ? -1 : (long)n_mixing_challenges,
+		                                               is_live ? -1 : (long)n_row_batch_challenges);
 		if (!out.mixed_tensor_elems.empty()) to_raw(out.mixed_tensor_elems, mixed_tensor_elems_out);
 		if (!out.row_batched_evals.empty()) to_raw(out.row_batched_evals, row_batched_evals_out);
 		for (size_t i = 0; i < out.transparents.size(); i++) d_transparents_out[i] = const_cast<void *>(out.transparents[i].ptr);
@@ -1681,6 +2015,26 @@ int bnh_ring_switch_prove(bn_ctx *ctx, uint32_t n_columns, const void *const *d_
 			for (int i = 0; i < RingSwitchOutput::NPhases; i++) phase_ms_out[i] = out.phase_ms[i];
 		return 0;
 	});
+}
+
+int bnh_ring_switch_prove(bn_ctx *ctx, uint32_t n_columns, const void *const *d_columns, const uint32_t *column_desc, const bn_f128 *point_pool, uint32_t pool_len,
+                          uint32_t n_suffixes, const uint32_t *suffix_desc, uint32_t n_prefixes, const uint32_t *prefix_kappas, uint32_t n_claims,
+                          const uint32_t *claim_desc, const bn_f128 *mixing_challenges, uint32_t n_mixing_challenges, const bn_f128 *row_batch_challenges,
+                          uint32_t n_row_batch_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *mixed_tensor_elems_out, bn_f128 *row_batched_evals_out,
+                          void **d_transparents_out, double *phase_ms_out)
+{
+	return ring_switch_prove_body(ctx, n_columns, d_columns, column_desc, point_pool, pool_len, n_suffixes, suffix_desc, n_prefixes, prefix_kappas, n_claims, claim_desc,
+	                              mixing_challenges, n_mixing_challenges, row_batch_challenges, n_row_batch_challenges, d_scratch, scratch_elems, mixed_tensor_elems_out,
+	                              row_batched_evals_out, d_transparents_out, phase_ms_out, false, nullptr);
+}
+
+int bnh_ring_switch_prove_live(bn_ctx *ctx, uint32_t n_columns, const void *const *d_columns, const uint32_t *column_desc, const bn_f128 *point_pool, uint32_t pool_len,
+                               uint32_t n_suffixes, const uint32_t *suffix_desc, uint32_t n_prefixes, const uint32_t *prefix_kappas, uint32_t n_claims,
+                               const uint32_t *claim_desc, const bnh_transcript *transcript, void *d_scratch, uint64_t scratch_elems, bn_f128 *mixed_tensor_elems_out,
+                               bn_f128 *row_batched_evals_out, void **d_transparents_out, double *phase_ms_out)
+{
+	return ring_switch_prove_body(ctx, n_columns, d_columns, column_desc, point_pool, pool_len, n_suffixes, suffix_desc, n_prefixes, prefix_kappas, n_claims, claim_desc, nullptr,
+	                              0, nullptr, 0, d_scratch, scratch_elems, mixed_tensor_elems_out, row_batched_evals_out, d_transparents_out, phase_ms_out, true, transcript);
 }
 
 } // extern "C"

@@ -153,25 +153,33 @@ struct PiopProveOutput {
 	uint64_t phase_ns[3] = {0, 0, 0}; // BNH_PROF=1: send_round_proof, receive_challenge, execute_fold_round over all rounds
 };
 
-// prove_interleaved_fri_sumcheck (piop/prove.rs:306-395); `challenges[round]` is what transcript.sample() would have returned.
-// query_indices: null -- the proof ends at the terminate codeword (finalize); else the n_test_queries indices transcript.sample_bits
-// would have returned -- fri_prover.finish_proof runs whole and its decommitment comes back in `advice`.
+// prove_interleaved_fri_sumcheck (piop/prove.rs:306-395) against a transcript.  The array form's streams: PiopBatchCoeffs, one per
+// prover; PiopChallenges, one per round; its bit samples: the n_test_queries query indices.
+// Schedule: sample the batch coefficients (front_loaded::BatchProver::new, :325); per round the evaluations of the provers that
+// finished, the truncated round polynomial (2 coefficients), ONE sample, then the FRI round's commitment (32 bytes) when the folder
+// commits in it (:343-358); after the last round the evaluations of the provers that finish then (:361).  with_queries
+// (FRIFolder::finish_proof, fri/prove.rs:483-507): the terminate codeword goes out on the decommitment channel, then
+// sample_bits(index_bits) n_test_queries times, then the layers and every query's openings on the decommitment channel -- the
+// decommitment is not observed, so the openings of all queries follow the last index; the bytes are the reference's.  Without
+// with_queries the proof ends at the terminate codeword (finalize).
+enum { PiopBatchCoeffs = 0, PiopChallenges = 1 };
 inline PiopProveOutput prove_interleaved_fri_sumcheck_impl(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, size_t n_rounds, const FRIParams &fri_params,
                                                            const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover,
-                                                           std::vector<std::unique_ptr<BivariateSumcheckProver>> sumcheck_provers,
-                                                           const std::vector<B128> &batch_coeffs, FSlice codeword, const BinaryMerkleTree &committed,
-                                                           const std::vector<B128> &challenges, const std::vector<size_t> *query_indices)
+                                                           std::vector<std::unique_ptr<BivariateSumcheckProver>> sumcheck_provers, FSlice codeword,
+                                                           const BinaryMerkleTree &committed, TranscriptSource &tr, bool with_queries)
 {
-	if (challenges.size() < n_rounds) throw PiopError("not enough challenges for the rounds of the protocol");
 	PiopProveOutput out;
 	out.n_provers = sumcheck_provers.size();
 	FRIFolder fri_prover(hal, fri_params, ntt, merkle_prover, codeword, committed);
+	const std::vector<B128> batch_coeffs = tr.sample_vec(PiopBatchCoeffs, 0, sumcheck_provers.size());
 	SumcheckBatchProver<BivariateSumcheckProver> sumcheck_batch_prover(std::move(sumcheck_provers), batch_coeffs);
 	// the evaluations of the provers that finished since the last call, in finishing order (front_loaded.rs:109-120)
 	size_t n_written = 0;
 	auto write_finished = [&] {
-		for (const auto &evals = sumcheck_batch_prover.multilinear_evals(); n_written < evals.size(); n_written++)
+		for (const auto &evals = sumcheck_batch_prover.multilinear_evals(); n_written < evals.size(); n_written++) {
 			out.transcript.write_scalar_slice(PiopTranscript::Item::MultilinearEvals, evals[n_written]);
+			tr.write_scalars(evals[n_written]);
+		}
 	};
 	const bool prof = AbiProf::on(); // BNH_PROF=1: wall time of the three steps of a round, summed (diagnostic)
 	auto now = [] { return std::chrono::steady_clock::now(); };
@@ -183,12 +191,16 @@ inline PiopProveOutput prove_interleaved_fri_sumcheck_impl(ComputeLayer &hal, De
 		const std::vector<B128> round_proof = sumcheck_batch_prover.round_proof();
 		write_finished();
 		out.transcript.write_scalar_slice(PiopTranscript::Item::RoundProof, round_proof);
+		tr.write_scalars(round_proof);
 		const auto t1 = prof ? now() : t0;
-		const B128 challenge = challenges[round];
+		const B128 challenge = tr.sample(PiopChallenges, round);
 		sumcheck_batch_prover.receive_challenge(challenge);
 		const auto t2 = prof ? now() : t0;
 		auto [has_commitment, round_commitment] = fri_prover.execute_fold_round(dev_alloc, challenge);
-		if (has_commitment) out.transcript.write_digest(round_commitment);
+		if (has_commitment) {
+			out.transcript.write_digest(round_commitment);
+			tr.write_digest(round_commitment);
+		}
 		if (prof) {
 			out.phase_ns[0] += ns(t0, t1);
 			out.phase_ns[1] += ns(t1, t2);
@@ -197,11 +209,15 @@ inline PiopProveOutput prove_interleaved_fri_sumcheck_impl(ComputeLayer &hal, De
 	}
 	out.multilinear_evals = sumcheck_batch_prover.finish();
 	write_finished();
-	// fri_prover.finish_proof (fri/prove.rs:483-507): the terminate codeword goes to the transcript; with query indices the layers and
-	// the openings follow it in the advice, all from one launch, and the transcript item is filled from the same block
-	if (query_indices) {
-		FriAdvice advice = fri_prover.finish_proof(*query_indices);
+	// fri_prover.finish_proof (fri/prove.rs:483-507): the terminate codeword goes to the transcript; with queries the layers and
+	// the openings follow it in the advice, all from one launch, and the transcript item is filled from the same block.  A transcript
+	// that observes what is written gets the terminate codeword before the indices are drawn, from a copy of its own.
+	if (with_queries) {
+		if (tr.observes_writes()) tr.write_scalars(fri_prover.finalize().first, BNH_TR_DECOMMITMENT);
+		const std::vector<uint64_t> drawn = tr.sample_bits_vec((uint32_t)fri_params.index_bits(), 0, fri_params.n_test_queries());
+		FriAdvice advice = fri_prover.finish_proof(std::vector<size_t>(drawn.begin(), drawn.end()));
 		out.terminate_codeword = advice.terminate_codeword();
+		tr.write_scalars(advice.block.data() + advice.terminate_elems, advice.block.size() - advice.terminate_elems, BNH_TR_DECOMMITMENT);
 		out.advice = std::move(advice.block);
 	} else {
 		auto fin = fri_prover.finalize();
@@ -209,6 +225,24 @@ inline PiopProveOutput prove_interleaved_fri_sumcheck_impl(ComputeLayer &hal, De
 	}
 	out.transcript.write_scalar_slice(PiopTranscript::Item::FriTerminate, out.terminate_codeword);
 	return out;
+}
+// `challenges[round]` is what transcript.sample() would have returned.  query_indices: null -- the proof ends at the terminate
+// codeword (finalize); else the n_test_queries indices transcript.sample_bits would have returned -- fri_prover.finish_proof runs
+// whole and its decommitment comes back in `advice`.
+inline PiopProveOutput prove_interleaved_fri_sumcheck_impl(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, size_t n_rounds, const FRIParams &fri_params,
+                                                           const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover,
+                                                           std::vector<std::unique_ptr<BivariateSumcheckProver>> sumcheck_provers,
+                                                           const std::vector<B128> &batch_coeffs, FSlice codeword, const BinaryMerkleTree &committed,
+                                                           const std::vector<B128> &challenges, const std::vector<size_t> *query_indices)
+{
+	if (challenges.size() < n_rounds) throw PiopError("not enough challenges for the rounds of the protocol");
+	if (batch_coeffs.size() != sumcheck_provers.size()) throw SumcheckError("IncorrectNumberOfBatchCoeffs");
+	if (query_indices && query_indices->size() != fri_params.n_test_queries())
+		throw FriError("InvalidArgs(got " + std::to_string(query_indices->size()) + " query indices, expected " + std::to_string(fri_params.n_test_queries()) + ")");
+	const std::vector<uint64_t> idx = query_indices ? std::vector<uint64_t>(query_indices->begin(), query_indices->end()) : std::vector<uint64_t>{};
+	ArrayTranscript tr({ArrayTranscript::stream(batch_coeffs), ArrayTranscript::stream(challenges)}, idx.data(), idx.size());
+	return prove_interleaved_fri_sumcheck_impl(hal, dev_alloc, n_rounds, fri_params, ntt, merkle_prover, std::move(sumcheck_provers), codeword, committed, tr,
+	                                           query_indices != nullptr);
 }
 inline PiopProveOutput prove_interleaved_fri_sumcheck(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, size_t n_rounds, const FRIParams &fri_params,
                                                       const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover,
@@ -236,11 +270,10 @@ inline PiopProveOutput prove_interleaved_fri_sumcheck(ComputeLayer &hal, DeviceB
 //   transparents    device slices, ascending by number of variables
 //   batch_coeffs    one per prover (transcript.sample_vec(provers.len()), front_loaded.rs:63-68)
 //   query_indices   null, or the indices of the FRI query phase (prove_interleaved_fri_sumcheck_impl)
-inline PiopProveOutput piop_prove_impl(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, const FRIParams &fri_params,
-                                       const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover, const CommitMeta &commit_meta, const BinaryMerkleTree &committed,
-                                       FSlice codeword, const std::vector<FSlice> &committed_multilins, const std::vector<FSlice> &transparent_multilins,
-                                       const std::vector<PIOPSumcheckClaim> &claims, const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges,
-                                       const std::vector<size_t> *query_indices)
+inline std::vector<std::unique_ptr<BivariateSumcheckProver>> piop_sumcheck_provers(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc,
+                                                                                  const CommitMeta &commit_meta, const std::vector<FSlice> &committed_multilins,
+                                                                                  const std::vector<FSlice> &transparent_multilins,
+                                                                                  const std::vector<PIOPSumcheckClaim> &claims)
 {
 	if (committed_multilins.size() != commit_meta.total_multilins()) throw PiopError("committed multilinears do not match the commit metadata");
 	std::vector<size_t> transparent_n_vars;
@@ -260,9 +293,28 @@ inline PiopProveOutput piop_prove_impl(ComputeLayer &hal, DeviceBumpAllocator &d
 		for (size_t i = d.transparent_begin; i < d.transparent_end; i++) multilins.push_back(transparent_multilins[i]);
 		provers.push_back(std::make_unique<BivariateSumcheckProver>(hal, dev_alloc, host_alloc, n_vars, d.compositions, d.sums, multilins));
 	}
+	return provers;
+}
+inline PiopProveOutput piop_prove_impl(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, const FRIParams &fri_params,
+                                       const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover, const CommitMeta &commit_meta, const BinaryMerkleTree &committed,
+                                       FSlice codeword, const std::vector<FSlice> &committed_multilins, const std::vector<FSlice> &transparent_multilins,
+                                       const std::vector<PIOPSumcheckClaim> &claims, const std::vector<B128> &batch_coeffs, const std::vector<B128> &challenges,
+                                       const std::vector<size_t> *query_indices)
+{
+	std::vector<std::unique_ptr<BivariateSumcheckProver>> provers = piop_sumcheck_provers(hal, dev_alloc, host_alloc, commit_meta, committed_multilins, transparent_multilins, claims);
 	if (batch_coeffs.size() != provers.size()) throw PiopError("one batch coefficient per sumcheck prover: " + std::to_string(provers.size()) + " expected");
 	return prove_interleaved_fri_sumcheck_impl(hal, dev_alloc, commit_meta.total_vars(), fri_params, ntt, merkle_prover, std::move(provers), batch_coeffs, codeword,
 	                                           committed, challenges, query_indices);
+}
+// the same against a transcript (prove_interleaved_fri_sumcheck_impl's schedule)
+inline PiopProveOutput piop_prove_live(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, const FRIParams &fri_params, const AdditiveNTT &ntt,
+                                       BinaryMerkleTreeProver &merkle_prover, const CommitMeta &commit_meta, const BinaryMerkleTree &committed, FSlice codeword,
+                                       const std::vector<FSlice> &committed_multilins, const std::vector<FSlice> &transparent_multilins,
+                                       const std::vector<PIOPSumcheckClaim> &claims, TranscriptSource &tr, bool with_queries)
+{
+	return prove_interleaved_fri_sumcheck_impl(hal, dev_alloc, commit_meta.total_vars(), fri_params, ntt, merkle_prover,
+	                                           piop_sumcheck_provers(hal, dev_alloc, host_alloc, commit_meta, committed_multilins, transparent_multilins, claims), codeword, committed,
+	                                           tr, with_queries);
 }
 inline PiopProveOutput piop_prove(ComputeLayer &hal, DeviceBumpAllocator &dev_alloc, HostBumpAllocator &host_alloc, const FRIParams &fri_params,
                                   const AdditiveNTT &ntt, BinaryMerkleTreeProver &merkle_prover, const CommitMeta &commit_meta, const BinaryMerkleTree &committed,

@@ -24,6 +24,7 @@
 #include <map>
 
 #include "sumcheck.hpp"
+#include "transcript.hpp"
 
 namespace binius_amd {
 
@@ -93,15 +94,18 @@ inline B128 tower_fold_vertical(const std::vector<B128> &elems, size_t kappa, co
 	return acc;
 }
 
+// Schedule (ring_switch/prove.rs:68-104): sample the ceil(log2 n_claims) mixing challenges (stream RingSwitchMixing); write per prefix its
+// 2^kappa mixed vertical elements; sample the max-kappa row-batch challenges (stream RingSwitchRowBatch); write the n_claims row-batched
+// evaluations.  n_mixing / n_row_batch: what the caller of the array form handed in (checked against the claims), or -1.
+enum { RingSwitchMixing = 0, RingSwitchRowBatch = 1 };
 inline RingSwitchOutput ring_switch_prove(ComputeLayer &hal, const std::vector<bn_pe_column> &columns, const std::vector<B128> &pool,
                                           const std::vector<RingSwitchSuffix> &suffixes, const std::vector<uint32_t> &prefix_kappas,
-                                          const std::vector<RingSwitchClaim> &claims, const std::vector<B128> &mixing_challenges,
-                                          const std::vector<B128> &row_batch_challenges, FSliceMut scratch)
+                                          const std::vector<RingSwitchClaim> &claims, TranscriptSource &tr, FSliceMut scratch, long n_mixing = -1, long n_row_batch = -1)
 {
 	// ---- everything is checked before the first device call
 	size_t log_claims = 0, max_kappa = 0;
 	while (((size_t)1 << log_claims) < claims.size()) log_claims++;
-	if (mixing_challenges.size() != log_claims) throw Error(Error::InputValidation, "ring switch: ceil(log2 n_claims) mixing challenges");
+	if (n_mixing >= 0 && (size_t)n_mixing != log_claims) throw Error(Error::InputValidation, "ring switch: ceil(log2 n_claims) mixing challenges");
 	for (const RingSwitchSuffix &s : suffixes) {
 		if (s.kappa > 7 || s.len > BN_PE_MAX_VARS) throw Error(Error::InputValidation, "a suffix descriptor is out of range");
 		if ((size_t)s.off + s.len > pool.size()) throw Error(Error::InputValidation, "a suffix leaves the point pool");
@@ -120,14 +124,16 @@ inline RingSwitchOutput ring_switch_prove(ComputeLayer &hal, const std::vector<b
 		if (prefix_kappas[c.prefix_desc_idx] != s.kappa) throw Error(Error::InputValidation, "TowerLevelMismatch: the claims of a prefix share its kappa");
 		max_kappa = std::max<size_t>(max_kappa, s.kappa);
 	}
-	if (row_batch_challenges.size() != max_kappa) throw Error(Error::InputValidation, "ring switch: max kappa row-batch challenges");
+	if (n_row_batch >= 0 && (size_t)n_row_batch != max_kappa) throw Error(Error::InputValidation, "ring switch: max kappa row-batch challenges");
 	if (scratch.len_ < ring_switch_scratch_elems(suffixes, claims)) throw Error(Error::InputValidation, "scratch holds fewer than ring_switch_scratch_elems elements");
 	RingSwitchOutput out;
 	if (claims.empty()) {
 		for (const uint32_t k : prefix_kappas) out.mixed_tensor_elems.resize(out.mixed_tensor_elems.size() + ((size_t)1 << k), B128::ZERO());
+		tr.write_scalars(out.mixed_tensor_elems);
 		return out;
 	}
 	DeviceBumpAllocator alloc(scratch);
+	const std::vector<B128> mixing_challenges = tr.sample_vec(RingSwitchMixing, 0, log_claims); // (:68-69)
 	const std::vector<B128> mixing_coeffs = eq_expand(mixing_challenges.data(), mixing_challenges.size()); // (:79)
 
 	// ---- compute_partial_evals: distinct suffixes expanded once, the distinct columns of a suffix in one call
@@ -171,9 +177,8 @@ inline RingSwitchOutput ring_switch_prove(ComputeLayer &hal, const std::vector<b
 	const auto t_pe = std::chrono::steady_clock::now();
 	out.phase_ms[RingSwitchOutput::PartialEvals] = elapsed_ms(t_begin, t_pe);
 
-	// ---- scale, mix per prefix, fold with the row-batch coefficients
-	const std::vector<B128> row_batch_coeffs = eq_expand(row_batch_challenges.data(), row_batch_challenges.size()); // (:97-100)
-	std::vector<std::vector<B128>> mixed;
+	// ---- scale and mix per prefix; the mixed elements are written before the row-batch challenges are drawn (:90-97)
+	std::vector<std::vector<B128>> mixed, scaled(claims.size());
 	for (const uint32_t k : prefix_kappas) mixed.emplace_back((size_t)1 << k, B128::ZERO());
 	out.row_batched_evals.resize(claims.size());
 	for (size_t i = 0; i < claims.size(); i++) {
@@ -185,9 +190,15 @@ inline RingSwitchOutput ring_switch_prove(ComputeLayer &hal, const std::vector<b
 		for (B128 &e : elems) e = e * mixing_coeffs[i]; // scale_vertical
 		std::vector<B128> &m = mixed[c.prefix_desc_idx];
 		for (size_t v = 0; v < elems.size(); v++) m[v] += elems[v];
-		out.row_batched_evals[i] = tower_fold_vertical(elems, s.kappa, row_batch_coeffs);
+		scaled[i] = std::move(elems);
 	}
 	for (const std::vector<B128> &m : mixed) out.mixed_tensor_elems.insert(out.mixed_tensor_elems.end(), m.begin(), m.end());
+	tr.write_scalars(out.mixed_tensor_elems);
+	// ---- fold with the row-batch coefficients
+	const std::vector<B128> row_batch_challenges = tr.sample_vec(RingSwitchRowBatch, 0, max_kappa);                   // (:97)
+	const std::vector<B128> row_batch_coeffs = eq_expand(row_batch_challenges.data(), row_batch_challenges.size()); // (:98-100)
+	for (size_t i = 0; i < claims.size(); i++) out.row_batched_evals[i] = tower_fold_vertical(scaled[i], suffixes[claims[i].suffix_desc_idx].kappa, row_batch_coeffs);
+	tr.write_scalars(out.row_batched_evals); // (:104)
 	const auto t_ta = std::chrono::steady_clock::now();
 	out.phase_ms[RingSwitchOutput::TensorAlgebra] = elapsed_ms(t_pe, t_ta);
 
@@ -206,6 +217,14 @@ inline RingSwitchOutput ring_switch_prove(ComputeLayer &hal, const std::vector<b
 	check(bn_ring_switch_eq_ind_batch(hal.raw_ctx(), rs.data(), (uint32_t)rs.size(), raw_coeffs.data(), (uint32_t)raw_coeffs.size(), rs_outs.data()));
 	out.phase_ms[RingSwitchOutput::EqInds] = elapsed_ms(t_ta);
 	return out;
+}
+inline RingSwitchOutput ring_switch_prove(ComputeLayer &hal, const std::vector<bn_pe_column> &columns, const std::vector<B128> &pool,
+                                          const std::vector<RingSwitchSuffix> &suffixes, const std::vector<uint32_t> &prefix_kappas,
+                                          const std::vector<RingSwitchClaim> &claims, const std::vector<B128> &mixing_challenges,
+                                          const std::vector<B128> &row_batch_challenges, FSliceMut scratch)
+{
+	ArrayTranscript tr({ArrayTranscript::stream(mixing_challenges), ArrayTranscript::stream(row_batch_challenges)});
+	return ring_switch_prove(hal, columns, pool, suffixes, prefix_kappas, claims, tr, scratch, (long)mixing_challenges.size(), (long)row_batch_challenges.size());
 }
 
 } // namespace binius_amd

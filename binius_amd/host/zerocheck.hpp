@@ -184,9 +184,16 @@ inline uint32_t table_base(const ZerocheckTable &t)
 
 } // namespace zerocheck_detail
 
-inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::vector<ZerocheckTable> &tables, size_t skip_rounds, const std::vector<B128> &zerocheck_challenges,
-                                                  const std::vector<B128> &batch_coeffs, B128 univariate_challenge, const std::vector<B128> &sumcheck_challenges,
-                                                  B128 reduction_batch_coeff, const std::vector<B128> &reduction_challenges, FSliceMut scratch, bool tower = false)
+// The transcript's streams, as the array form names them.
+// Schedule (constraint_system/prove.rs:470; batch_zerocheck.rs:193-272): sample the max_n - k zerocheck challenges; sample the n_tables
+// batch coefficients; write the univariate round's message (D - 2^k scalars); sample the univariate challenge; the max_n - k multilinear
+// rounds as a front-loaded batch (per round the evaluations of the tables that finished, the truncated round polynomial, ONE sample;
+// then the last tables' evaluations); sample the reduction's batch coefficient; k rounds of write 2 coefficients / sample 1; write the
+// reduction's evaluations (every column's, then the Lagrange multilinear's).
+enum { ZerocheckChallenges = 0, ZerocheckBatchCoeffs = 1, ZerocheckUnivariateChallenge = 2, ZerocheckSumcheckChallenges = 3, ZerocheckReductionBatchCoeff = 4,
+       ZerocheckReductionChallenges = 5 };
+inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::vector<ZerocheckTable> &tables, size_t skip_rounds, TranscriptSource &tr, FSliceMut scratch,
+                                                  bool tower = false)
 {
 	using namespace zerocheck_detail;
 	using Out = ZerocheckBatchOutput;
@@ -221,9 +228,6 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 	const size_t max_n = tables.back().n_vars;
 	if (k > max_n) throw Error(Error::InputValidation, "IncorrectSkippedRoundsCount: skip_rounds exceeds the largest n_vars");
 	const size_t rounds = max_n - k, D = d_top << k, d_max = d_top > 2 ? d_top : 2;
-	if (batch_coeffs.size() != tables.size()) throw Error(Error::InputValidation, "IncorrectNumberOfBatchCoeffs");
-	if (zerocheck_challenges.size() != rounds || sumcheck_challenges.size() != rounds || reduction_challenges.size() != k)
-		throw Error(Error::InputValidation, "zerocheck: max_n - k zerocheck and sumcheck challenges, k reduction challenges");
 	if (!tower && scratch.len_ < zerocheck_batch_scratch_elems(nv, nc, k)) throw Error(Error::InputValidation, "scratch holds fewer than zerocheck_batch_scratch_elems elements");
 	if (tower && scratch.len_ < zerocheck_batch_scratch_elems_tower(nv, col_levels, k))
 		throw Error(Error::InputValidation, "scratch holds fewer than zerocheck_batch_scratch_elems_tower elements");
@@ -231,6 +235,8 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 	Out out;
 	Mi355xBackend backend(hal);
 	DeviceBumpAllocator alloc(scratch);
+	const std::vector<B128> zerocheck_challenges = tr.sample_vec(ZerocheckChallenges, 0, rounds);
+	const std::vector<B128> batch_coeffs = tr.sample_vec(ZerocheckBatchCoeffs, 0, tables.size());
 	struct Prover {
 		size_t n_eff = 0, nr = 0;
 		std::vector<const void *> cols;                // the columns the univariate round and the fold read (padded copies for n < k)
@@ -310,6 +316,8 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 		}
 	}
 	out.phase_ms[Out::Univariate] = elapsed_ms(t0);
+	tr.write_scalars(out.message); // (batch_zerocheck.rs:209-210)
+	const B128 univariate_challenge = tr.sample(ZerocheckUnivariateChallenge, 0);
 
 	// ---- ZerocheckUnivariateEvalsOutput::fold and fold_univariate_round
 	t0 = std::chrono::steady_clock::now();
@@ -362,15 +370,14 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 		provers.push_back(std::make_unique<EqIndPointProver>(hal, backend, alloc, pr.nr, pr.folded, tables[p].compositions, std::move(sums), pr.challenges));
 	}
 	// all coefficients of a round polynomial, padded to Dmax + 2
-	BatchSumcheckOutput res = SumcheckBatchProver<EqIndPointProver>(std::move(provers), batch_coeffs, BatchSchedule::FrontLoaded, d_max + 2).run(sumcheck_challenges.data());
+	BatchSumcheckOutput res = SumcheckBatchProver<EqIndPointProver>(std::move(provers), batch_coeffs, BatchSchedule::FrontLoaded, d_max + 2).run(tr, ZerocheckSumcheckChallenges);
 	out.round_coeffs = std::move(res.round_proofs);
 	out.final_evals = std::move(res.multilinear_evals);
 	out.phase_ms[Out::Multilinear] = elapsed_ms(t0);
 
 	// ---- project_to_skipped_variables
 	t0 = std::chrono::steady_clock::now();
-	out.unskipped_challenges.assign(sumcheck_challenges.rbegin(), sumcheck_challenges.rend());
-	out.skipped_challenges.assign(reduction_challenges.rbegin(), reduction_challenges.rend());
+	out.unskipped_challenges.assign(res.challenges.rbegin(), res.challenges.rend());
 	std::vector<std::vector<B128>> projected; // every column of every table, 2^k values
 	for (size_t p = 0; p < tables.size(); p++) {
 		const ZerocheckTable &t = tables[p];
@@ -419,37 +426,63 @@ inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::
 	t0 = std::chrono::steady_clock::now();
 	std::vector<B128> sums;
 	for (const auto &evals : out.final_evals) sums.insert(sums.end(), evals.begin(), evals.end() - 1);
-	std::vector<B128> lag = l_sub;
+	std::vector<B128> lag = l_sub, reduction_challenges;
+	const B128 reduction_batch_coeff = tr.sample(ZerocheckReductionBatchCoeff, 0); // (front_loaded::BatchProver::new, batch_zerocheck.rs:266-267)
 	for (size_t r = 0; r < k; r++) {
 		const size_t half = (size_t)1 << (k - 1 - r);
-		const B128 z = reduction_challenges[r];
 		std::vector<B128> l_inf(half);
 		for (size_t x = 0; x < half; x++) l_inf[x] = lag[x] + lag[half + x];
 		std::vector<B128> coeffs(3, B128::ZERO());
+		std::vector<std::array<B128, 3>> per(projected.size()); // every claim's round polynomial: the challenge is drawn after the batched one is written
 		B128 scale = reduction_batch_coeff; // the powers of the coefficient, times the coefficient (prove/front_loaded.rs:128-132)
 		for (size_t i = 0; i < projected.size(); i++) {
-			std::vector<B128> &a = projected[i];
+			const std::vector<B128> &a = projected[i];
 			B128 y1 = B128::ZERO(), yinf = B128::ZERO();
 			for (size_t x = 0; x < half; x++) {
 				y1 += a[half + x] * lag[half + x];
 				yinf += (a[x] + a[half + x]) * l_inf[x];
 			}
 			const B128 c0 = sums[i] + y1, c2 = yinf, c1 = y1 + c0 + c2;
+			per[i] = {c0, c1, c2};
 			coeffs[0] += scale * c0;
 			coeffs[1] += scale * c1;
 			coeffs[2] += scale * c2;
 			scale = scale * reduction_batch_coeff;
-			sums[i] = c0 + z * (c1 + z * c2);
+		}
+		tr.write_scalars(coeffs.data(), 2); // (RoundCoeffs::truncate)
+		const B128 z = tr.sample(ZerocheckReductionChallenges, r);
+		reduction_challenges.push_back(z);
+		for (size_t i = 0; i < projected.size(); i++) {
+			std::vector<B128> &a = projected[i];
+			sums[i] = per[i][0] + z * (per[i][1] + z * per[i][2]);
 			for (size_t x = 0; x < half; x++) a[x] = a[x] + z * (a[x] + a[half + x]);
 		}
 		for (size_t x = 0; x < half; x++) lag[x] = lag[x] + z * l_inf[x];
 		out.reduction_round_coeffs.push_back(coeffs);
 	}
+	out.skipped_challenges.assign(reduction_challenges.rbegin(), reduction_challenges.rend());
 	for (const auto &a : projected) out.reduction_final_evals.push_back(a[0]);
 	out.concat_multilinear_evals = out.reduction_final_evals;
 	out.reduction_final_evals.push_back(lag[0]);
+	tr.write_scalars(out.reduction_final_evals);
 	out.phase_ms[Out::Reduction] = elapsed_ms(t0);
 	return out;
+}
+inline ZerocheckBatchOutput zerocheck_batch_prove(ComputeLayer &hal, const std::vector<ZerocheckTable> &tables, size_t skip_rounds, const std::vector<B128> &zerocheck_challenges,
+                                                  const std::vector<B128> &batch_coeffs, B128 univariate_challenge, const std::vector<B128> &sumcheck_challenges,
+                                                  B128 reduction_batch_coeff, const std::vector<B128> &reduction_challenges, FSliceMut scratch, bool tower = false)
+{
+	size_t max_n = 0;
+	for (const ZerocheckTable &t : tables) max_n = t.n_vars > max_n ? t.n_vars : max_n;
+	if (!tables.empty() && skip_rounds <= max_n) { // (otherwise the mirror rejects the call before its first draw)
+		const size_t rounds = max_n - skip_rounds;
+		if (batch_coeffs.size() != tables.size()) throw Error(Error::InputValidation, "IncorrectNumberOfBatchCoeffs");
+		if (zerocheck_challenges.size() != rounds || sumcheck_challenges.size() != rounds || reduction_challenges.size() != skip_rounds)
+			throw Error(Error::InputValidation, "zerocheck: max_n - k zerocheck and sumcheck challenges, k reduction challenges");
+	}
+	ArrayTranscript tr({ArrayTranscript::stream(zerocheck_challenges), ArrayTranscript::stream(batch_coeffs), ArrayTranscript::Stream{&univariate_challenge, 1},
+	                    ArrayTranscript::stream(sumcheck_challenges), ArrayTranscript::Stream{&reduction_batch_coeff, 1}, ArrayTranscript::stream(reduction_challenges)});
+	return zerocheck_batch_prove(hal, tables, skip_rounds, tr, scratch, tower);
 }
 
 } // namespace binius_amd

@@ -18,6 +18,8 @@ pub const BN_ERR_INPUT_VALIDATION: c_int = 1;
 pub const BN_ERR_ALLOC: c_int = 2;
 pub const BN_ERR_DEVICE: c_int = 3;
 pub const BN_ERR_CORE_LIB: c_int = 4;
+/// a caller's transcript callback returned non-zero (`bnh_transcript`, include/binius_amd_host.h)
+pub const BN_ERR_CALLBACK: c_int = 5;
 
 /// Opaque context (stream, scratch, optional arena).
 #[repr(C)]
@@ -597,4 +599,102 @@ unsafe extern "C" {
 	pub fn bn_host_tail_allow_peer(ctx: *mut bn_ctx, on: c_int) -> c_int;
 	pub fn bn_host_tail_active(ctx: *mut bn_ctx, active: *mut c_int) -> c_int;
 	pub fn bn_peer_destroy(ctx: *mut bn_ctx) -> c_int;
+}
+
+// ---- include/binius_amd_host.h, "Against a live transcript": the callback table, the `_live` form of every compiled prover that
+// takes transcript samples, and the library's array-backed transcript.  `src/transcript.rs` adapts `ProverTranscript` to the table.
+pub const BNH_TR_MESSAGE: u32 = 0;
+pub const BNH_TR_DECOMMITMENT: u32 = 1;
+pub const BNH_TR_EVENT_WRITE_MESSAGE: u32 = 0;
+pub const BNH_TR_EVENT_WRITE_DECOMMITMENT: u32 = 1;
+pub const BNH_TR_EVENT_SAMPLE: u32 = 2;
+pub const BNH_TR_EVENT_SAMPLE_BITS: u32 = 3;
+
+/// `bnh_transcript`: the caller's Fiat-Shamir transcript as three callbacks.  A callback returns 0, or non-zero to end the proof
+/// with `BN_ERR_CALLBACK`; it runs on the calling thread and must not re-enter the library on the same context.
+#[repr(C)]
+pub struct bnh_transcript {
+	pub user: *mut c_void,
+	pub write: Option<unsafe extern "C" fn(user: *mut c_void, channel: u32, bytes: *const c_void, len: u64) -> c_int>,
+	pub sample: Option<unsafe extern "C" fn(user: *mut c_void, out: *mut bn_f128, n: u32) -> c_int>,
+	pub sample_bits: Option<unsafe extern "C" fn(user: *mut c_void, bits: u32, n: u32, out: *mut u64) -> c_int>,
+}
+/// Opaque array-backed transcript (`bnh_transcript_replay_*`).
+#[repr(C)]
+pub struct bnh_transcript_replay {
+	_private: [u8; 0],
+}
+
+unsafe extern "C" {
+	pub fn bnh_batch_sumcheck_prove_live(
+		ctx: *mut bn_ctx, n_provers: u32, prover_desc: *const u32, d_multilins: *const *const c_void, comp_indices: *const u32, sums: *const bn_f128,
+		d_scratch: *mut c_void, scratch_elems: u64, transcript: *const bnh_transcript, round_proofs_out: *mut bn_f128, final_evals_out: *mut bn_f128,
+	) -> c_int;
+	pub fn bnh_eqind_sumcheck_prove_live(
+		ctx: *mut bn_ctx, n_vars: u32, n_mls: u32, d_multilins: *const *mut c_void, n_comps: u32, steps: *const bn_step, n_steps: *const u32,
+		steps_inf: *const bn_step, n_steps_inf: *const u32, degrees: *const u32, sums: *const bn_f128, eq_ind_challenges: *const bn_f128, d_eq_ind: *mut c_void,
+		eq_ind_elems: u64, transcript: *const bnh_transcript, round_coeffs_out: *mut bn_f128, final_evals_out: *mut bn_f128,
+	) -> c_int;
+	pub fn bnh_zerocheck_batch_prove_tower_live(
+		ctx: *mut bn_ctx, n_tables: u32, skip_rounds: u32, n_vars: *const u32, n_cols: *const u32, d_cols: *const *const c_void, tower_levels: *const u32,
+		n_comps: *const u32, steps: *const bn_step, n_steps: *const u32, steps_inf: *const bn_step, n_steps_inf: *const u32, degrees: *const u32,
+		transcript: *const bnh_transcript, d_scratch: *mut c_void, scratch_elems: u64, message_out: *mut bn_f128, round_coeffs_out: *mut bn_f128,
+		final_evals_out: *mut bn_f128, reduction_round_coeffs_out: *mut bn_f128, reduction_final_evals_out: *mut bn_f128, skipped_challenges_out: *mut bn_f128,
+		unskipped_challenges_out: *mut bn_f128, concat_multilinear_evals_out: *mut bn_f128, phase_ms_out: *mut f64, phase_calls_out: *mut u64,
+	) -> c_int;
+	pub fn bnh_gkr_gpa_prove_live(
+		ctx: *mut bn_ctx, n_claims: u32, n_vars: *const u32, d_inputs: *const *const c_void, input_lens: *const u64, d_arenas: *const *mut c_void,
+		d_scratch: *mut c_void, scratch_elems: u64, transcript: *const bnh_transcript, products_out: *mut bn_f128, round_proofs_out: *mut bn_f128,
+		layer_evals_out: *mut bn_f128, final_points_out: *mut bn_f128, final_evals_out: *mut bn_f128, step_ms_out: *mut f64,
+	) -> c_int;
+	pub fn bnh_gkr_exp_prove_live(
+		ctx: *mut bn_ctx, n_witnesses: u32, widths: *const u32, kinds: *const u32, d_exponent_bits: *const *const c_void, static_bases: *const bn_f128,
+		d_bases: *const *const c_void, d_arenas: *const *mut c_void, n_claims: u32, n_vars: *const u32, eval_points: *const bn_f128, evals: *const bn_f128,
+		d_scratch: *mut c_void, scratch_elems: u64, transcript: *const bnh_transcript, n_layers_out: *mut u32, rounds_per_layer_out: *mut u32,
+		coeffs_per_round_out: *mut u32, round_proofs_out: *mut bn_f128, provers_per_layer_out: *mut u32, evals_per_prover_out: *mut u32,
+		multilinear_evals_out: *mut bn_f128, claims_per_layer_out: *mut u32, claim_n_vars_out: *mut u32, claim_points_out: *mut bn_f128, claim_evals_out: *mut bn_f128,
+		layer_ms_out: *mut f64,
+	) -> c_int;
+	pub fn bnh_flush_prodcheck_prove_live(
+		ctx: *mut bn_ctx, n_flushes: u32, channel_ids: *const u32, flush_n_vars: *const u32, n_selectors: *const u32, selector_ids: *const u32,
+		d_selectors: *const *const c_void, n_entries: *const u32, entry_kinds: *const u32, entry_ids: *const u32, d_entry_columns: *const *const c_void,
+		entry_levels: *const u32, entry_consts: *const bn_f128, n_nonzero: u32, nonzero_ids: *const u32, d_nonzero_columns: *const *const c_void,
+		nonzero_levels: *const u32, nonzero_n_vars: *const u32, n_channels: u32, d_scratch: *mut c_void, scratch_elems: u64, transcript: *const bnh_transcript,
+		prefix_lens_out: *mut u64, products_out: *mut bn_f128, gpa_round_proofs_out: *mut bn_f128, gpa_layer_evals_out: *mut bn_f128,
+		gpa_final_points_out: *mut bn_f128, gpa_final_evals_out: *mut bn_f128, n_checks_out: *mut u32, check_desc_out: *mut u32, check_ids_out: *mut u32,
+		check_round_proofs_out: *mut bn_f128, check_final_evals_out: *mut bn_f128, n_linear_out: *mut u32, linear_flushes_out: *mut u32, phase_ms_out: *mut f64,
+	) -> c_int;
+	pub fn bnh_evalcheck_bivariate_prove_lc_live(
+		ctx: *mut bn_ctx, n_provers: u32, prover_desc: *const u32, ml_desc: *const u32, d_columns: *const *const c_void, n_terms: u32, term_levels: *const u32,
+		d_term_columns: *const *const c_void, term_coeffs: *const bn_f128, ml_offsets: *const bn_f128, point_pool: *const bn_f128, pool_len: u32,
+		comp_indices: *const u32, sums: *const bn_f128, d_scratch: *mut c_void, scratch_elems: u64, transcript: *const bnh_transcript, round_proofs_out: *mut bn_f128,
+		final_evals_out: *mut bn_f128,
+	) -> c_int;
+	pub fn bnh_ring_switch_prove_live(
+		ctx: *mut bn_ctx, n_columns: u32, d_columns: *const *const c_void, column_desc: *const u32, point_pool: *const bn_f128, pool_len: u32, n_suffixes: u32,
+		suffix_desc: *const u32, n_prefixes: u32, prefix_kappas: *const u32, n_claims: u32, claim_desc: *const u32, transcript: *const bnh_transcript,
+		d_scratch: *mut c_void, scratch_elems: u64, mixed_tensor_elems_out: *mut bn_f128, row_batched_evals_out: *mut bn_f128, d_transparents_out: *mut *mut c_void,
+		phase_ms_out: *mut f64,
+	) -> c_int;
+	pub fn bnh_fri_prove_live(
+		ctx: *mut bn_ctx, log_dim: u32, log_inv_rate: u32, log_batch_size: u32, fold_arities: *const u32, n_arities: u32, n_test_queries: u32,
+		d_message: *const c_void, d_scratch: *mut c_void, scratch_elems: u64, transcript: *const bnh_transcript, roots_out: *mut u8, advice_out: *mut bn_f128,
+		max_advice_elems: u64, n_advice_elems_out: *mut u64, phase_ms_out: *mut f64,
+	) -> c_int;
+	pub fn bnh_piop_prove_committed_open_live(
+		ctx: *mut bn_ctx, n_committed: u32, committed_n_vars: *const u32, d_committed: *const *const c_void, n_transparent: u32, transparent_n_vars: *const u32,
+		d_transparent: *const *const c_void, n_claims: u32, claims: *const u32, claim_sums: *const bn_f128, log_dim: u32, log_inv_rate: u32, log_batch_size: u32,
+		fold_arities: *const u32, n_arities: u32, n_test_queries: u32, d_codeword: *const c_void, d_tree: *const c_void, d_scratch: *mut c_void, scratch_elems: u64,
+		transcript: *const bnh_transcript, items_out: *mut u32, max_items: u32, n_items_out: *mut u32, scalars_out: *mut bn_f128, max_scalars: u64,
+		n_scalars_out: *mut u64, digests_out: *mut u8, max_digests: u32, n_digests_out: *mut u32, phase_ms_out: *mut f64, advice_out: *mut bn_f128,
+		max_advice_elems: u64, n_advice_elems_out: *mut u64,
+	) -> c_int;
+	pub fn bnh_transcript_replay_new(
+		samples: *const bn_f128, n_samples: u64, bit_samples: *const u64, n_bit_samples: u64, handle_out: *mut *mut bnh_transcript_replay,
+	) -> c_int;
+	pub fn bnh_transcript_replay_table(handle: *mut bnh_transcript_replay) -> *const bnh_transcript;
+	pub fn bnh_transcript_replay_written(handle: *mut bnh_transcript_replay, channel: u32, buf: *mut u8, max: u64, len_out: *mut u64) -> c_int;
+	pub fn bnh_transcript_replay_events(handle: *mut bnh_transcript_replay, kinds_out: *mut u32, counts_out: *mut u64, max_events: u64, n_events_out: *mut u64) -> c_int;
+	pub fn bnh_transcript_replay_free(handle: *mut bnh_transcript_replay);
+
 }

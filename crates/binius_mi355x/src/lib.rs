@@ -22,6 +22,8 @@ pub mod memory;
 #[cfg(feature = "provers")]
 pub mod mlecheck;
 pub mod recorder;
+#[cfg(feature = "provers")]
+pub mod transcript;
 
 use std::{ffi::CStr, os::raw::c_int, ptr};
 

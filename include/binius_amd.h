@@ -42,7 +42,8 @@ typedef enum {
 	BN_ERR_INPUT_VALIDATION = 1, /* Error::InputValidation */
 	BN_ERR_ALLOC = 2,            /* Error::Alloc(OutOfMemory) */
 	BN_ERR_DEVICE = 3,           /* Error::DeviceError (hipError_t) */
-	BN_ERR_CORE_LIB = 4          /* Error::CoreLibError */
+	BN_ERR_CORE_LIB = 4,         /* Error::CoreLibError */
+	BN_ERR_CALLBACK = 5          /* a caller's transcript callback returned non-zero (include/binius_amd_host.h, bnh_transcript) */
 } bn_status;
 
 typedef struct bn_ctx bn_ctx;

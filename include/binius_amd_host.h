@@ -451,6 +451,137 @@ int bnh_ring_switch_prove(bn_ctx *ctx, uint32_t n_columns, const void *const *d_
                           uint32_t n_row_batch_challenges, void *d_scratch, uint64_t scratch_elems, bn_f128 *mixed_tensor_elems_out, bn_f128 *row_batched_evals_out,
                           void **d_transparents_out, double *phase_ms_out);
 
+/* ---- Against a live transcript ------------------------------------------------------------------------------------------------------
+ * Every entry point above takes the transcript's samples as arrays, drawn before the call.  In a proof, round r's challenge is a hash
+ * of round r's message, so a prover with a Fiat-Shamir transcript drives the `_live` forms below instead: the library hands each
+ * message to the caller at the moment the reference writes it and asks the caller for each sample at the moment the reference draws
+ * it.  The transcript itself stays with the caller (ProverTranscript<Challenger>, crates/core/src/transcript/mod.rs).
+ *   write        TranscriptWriter: channel BNH_TR_MESSAGE is transcript.message() (observed by the challenger), BNH_TR_DECOMMITMENT is
+ *                transcript.decommitment() (not observed).  `bytes` are in transcript byte order: a scalar is its 16-byte little-endian
+ *                canonical-tower element (the layout of bn_f128), a digest its 32 bytes.  Only the concatenation of the bytes between
+ *                two samples is specified, not how it is cut into calls.
+ *   sample       n x transcript.sample() of B128, in order, into out[n]
+ *   sample_bits  n x transcript.sample_bits(bits), in order, into out[n]
+ * A callback returns 0, or non-zero to end the proof: the call returns BN_ERR_CALLBACK after the unwinding that any error inside a
+ * mirror takes, and the context stays usable.  Callbacks run on the calling thread, inside the call; they MUST NOT re-enter the
+ * library on the same context.  A null table, or a null member that the entry point needs (write and sample always; sample_bits
+ * where indices are drawn), is BN_ERR_INPUT_VALIDATION before anything is launched.
+ * A `_live` form keeps its array form's argument list but for the sample arrays, which go, and the `const bnh_transcript *`, which
+ * stands where the first of them stood.  The output arrays stay: a `_live` call that drew the samples S fills every output array
+ * exactly as the array form fed S (both run the same mirror code over a TranscriptSource, binius_amd/host/transcript.hpp).  Work
+ * computed ahead (armed kernels, the first execute() carrying other provers' claims, the host tail) depends only on past challenges
+ * and is untouched. */
+enum { BNH_TR_MESSAGE = 0, BNH_TR_DECOMMITMENT = 1 }; /* TranscriptWriter: message() is observed, decommitment() is not */
+typedef struct bnh_transcript {
+	void *user;
+	int (*write)(void *user, uint32_t channel, const void *bytes, uint64_t len);  /* transcript byte order */
+	int (*sample)(void *user, bn_f128 *out, uint32_t n);                          /* n x transcript.sample() of B128 */
+	int (*sample_bits)(void *user, uint32_t bits, uint32_t n, uint64_t *out);     /* n x sample_bits(bits) */
+} bnh_transcript;
+
+/* The schedules.  W(k): k scalars written to BNH_TR_MESSAGE; S(k): k samples drawn; "batch run": front_loaded::BatchProver::run
+ * (sumcheck/prove/front_loaded.rs:122-197) -- per round r the final evaluations of every prover whose number of variables is r (m
+ * scalars each, :109-120), the TRUNCATED round polynomial (RoundCoeffs::truncate: all coefficients but the last), S(1); after the last
+ * round the evaluations of the provers that finish then.
+ *
+ * bnh_batch_sumcheck_prove_live (front_loaded.rs:51-59, 175-197): S(n_provers) batch coefficients; batch run with W(2) per round.
+ * bnh_eqind_sumcheck_prove_live (eq_ind.rs:378-644 as a front-loaded batch of one): S(1) the batch coefficient; n_vars rounds of
+ *   W(D + 1), S(1) -- the prover's polynomial TIMES the batch coefficient, without its last coefficient (front_loaded.rs:128-135),
+ *   while round_coeffs_out keeps the prover's own D + 2 coefficients; W(n_mls + 1).
+ * bnh_zerocheck_batch_prove_tower_live (constraint_system/prove.rs:470; batch_zerocheck.rs:193-272), the superset of the B8 form:
+ *   S(max_n - k) zerocheck challenges; S(n_tables) batch coefficients; W(D - 2^k) the univariate round's message; S(1) the univariate
+ *   challenge; batch run over the tables with max(n_p, k) - k variables each, the round polynomial truncated to the live tables'
+ *   largest degree + 1 coefficients (round_coeffs_out keeps all, padded); S(1) the reduction's batch coefficient; k rounds of W(2),
+ *   S(1); W(sum n_cols + 1).
+ * bnh_gkr_gpa_prove_live (gkr_gpa/prove.rs:67-126): step j = 0 .. max n_vars - 1: S(1) the batch coefficient; j rounds of W(3), S(1);
+ *   W(2 * active + 1) the layer evaluations and the indicator's; S(1) the layer challenge, drawn after them (:113-114).
+ * bnh_gkr_exp_prove_live (gkr_exp/batch_prove.rs:101 = sumcheck::batch_prove, prove/batch_sumcheck.rs:138-187): per layer with a
+ *   prover: per round first S(1) for every prover that joins in it (:143-151), then W(truncated round polynomial: 3, or 5 once a
+ *   degree-4 composition is live -- the eq-ind polynomial of a degree-d composition has d + 2 coefficients, d + 1 are written), S(1); after the last round S(1) per zero-variable prover (:173-177); then every prover's evaluations,
+ *   in order.  A layer without a prover writes and draws nothing.
+ * bnh_flush_prodcheck_prove_live (constraint_system/prove.rs:309-425): W(n_nonzero) the non-zero products (:318-320); S(1) the mixing
+ *   challenge; S(n_channels) the permutation challenges (:329-330) -- these two draws are made even when there is neither a flush nor a
+ *   non-zero oracle, and are then all the call does; W(n_flushes) the flush products (:378-380); the schedule of
+ *   bnh_gkr_gpa_prove_live over chain(flushes, non-zero oracles); per MLE-check g: S(1), n_vars rounds of W(check_desc_out[3 g + 2]),
+ *   S(1), then W(m + 1) (evalcheck/subclaims.rs:589-633).
+ * bnh_evalcheck_bivariate_prove_lc_live (evalcheck/subclaims.rs:549-586), the superset of bnh_evalcheck_bivariate_prove: S(n_provers);
+ *   batch run with W(2) per round.
+ * bnh_ring_switch_prove_live (ring_switch/prove.rs:68-104): S(ceil(log2 n_claims)) mixing challenges; W(sum over prefixes of 2^kappa)
+ *   the mixed tensor elements; S(max kappa) row-batch challenges; W(n_claims) the row-batched evaluations.
+ * bnh_fri_prove_live (fri/prove.rs:88-198, 307-432, 483-507): the commitment (32 bytes, MESSAGE); per fold round S(1), then the
+ *   round's commitment (32 bytes) when the folder commits in it; the terminate codeword on BNH_TR_DECOMMITMENT; sample_bits(index_bits)
+ *   n_test_queries times; the layers and every query's openings on BNH_TR_DECOMMITMENT (the decommitment is not observed, so the
+ *   openings of all queries follow the last index; the byte string is the reference's, and equals advice_out).
+ * bnh_piop_prove_committed_open_live (piop/prove.rs:306-395): S(provers) batch coefficients; per round: finished provers' evaluations,
+ *   W(2) (W(0) in the rounds after the largest prover has finished), S(1), the FRI round's commitment (32 bytes) when there is one -- the item list of bnh_piop_prove in order, up to its
+ *   terminate item; then the query phase as in bnh_fri_prove_live.  items_out still ends with the terminate item. */
+int bnh_batch_sumcheck_prove_live(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const void *const *d_multilins, const uint32_t *comp_indices,
+                                  const bn_f128 *sums, void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript, bn_f128 *round_proofs_out,
+                                  bn_f128 *final_evals_out);
+int bnh_eqind_sumcheck_prove_live(bn_ctx *ctx, uint32_t n_vars, uint32_t n_mls, void *const *d_multilins, uint32_t n_comps, const bn_step *steps,
+                                  const uint32_t *n_steps, const bn_step *steps_inf, const uint32_t *n_steps_inf, const uint32_t *degrees, const bn_f128 *sums,
+                                  const bn_f128 *eq_ind_challenges, void *d_eq_ind, uint64_t eq_ind_elems, const bnh_transcript *transcript,
+                                  bn_f128 *round_coeffs_out, bn_f128 *final_evals_out);
+int bnh_zerocheck_batch_prove_tower_live(bn_ctx *ctx, uint32_t n_tables, uint32_t skip_rounds, const uint32_t *n_vars, const uint32_t *n_cols, const void *const *d_cols,
+                                         const uint32_t *tower_levels, const uint32_t *n_comps, const bn_step *steps, const uint32_t *n_steps, const bn_step *steps_inf,
+                                         const uint32_t *n_steps_inf, const uint32_t *degrees, const bnh_transcript *transcript, void *d_scratch, uint64_t scratch_elems,
+                                         bn_f128 *message_out, bn_f128 *round_coeffs_out, bn_f128 *final_evals_out, bn_f128 *reduction_round_coeffs_out,
+                                         bn_f128 *reduction_final_evals_out, bn_f128 *skipped_challenges_out, bn_f128 *unskipped_challenges_out,
+                                         bn_f128 *concat_multilinear_evals_out, double *phase_ms_out, uint64_t *phase_calls_out);
+int bnh_gkr_gpa_prove_live(bn_ctx *ctx, uint32_t n_claims, const uint32_t *n_vars, const void *const *d_inputs, const uint64_t *input_lens, void *const *d_arenas,
+                           void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript, bn_f128 *products_out, bn_f128 *round_proofs_out,
+                           bn_f128 *layer_evals_out, bn_f128 *final_points_out, bn_f128 *final_evals_out, double *step_ms_out);
+int bnh_gkr_exp_prove_live(bn_ctx *ctx, uint32_t n_witnesses, const uint32_t *widths, const uint32_t *kinds, const void *const *d_exponent_bits,
+                           const bn_f128 *static_bases, const void *const *d_bases, void *const *d_arenas, uint32_t n_claims, const uint32_t *n_vars,
+                           const bn_f128 *eval_points, const bn_f128 *evals, void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript,
+                           uint32_t *n_layers_out, uint32_t *rounds_per_layer_out, uint32_t *coeffs_per_round_out, bn_f128 *round_proofs_out,
+                           uint32_t *provers_per_layer_out, uint32_t *evals_per_prover_out, bn_f128 *multilinear_evals_out, uint32_t *claims_per_layer_out,
+                           uint32_t *claim_n_vars_out, bn_f128 *claim_points_out, bn_f128 *claim_evals_out, double *layer_ms_out);
+int bnh_flush_prodcheck_prove_live(bn_ctx *ctx, uint32_t n_flushes, const uint32_t *channel_ids, const uint32_t *flush_n_vars, const uint32_t *n_selectors,
+                                   const uint32_t *selector_ids, const void *const *d_selectors, const uint32_t *n_entries, const uint32_t *entry_kinds,
+                                   const uint32_t *entry_ids, const void *const *d_entry_columns, const uint32_t *entry_levels, const bn_f128 *entry_consts,
+                                   uint32_t n_nonzero, const uint32_t *nonzero_ids, const void *const *d_nonzero_columns, const uint32_t *nonzero_levels,
+                                   const uint32_t *nonzero_n_vars, uint32_t n_channels, void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript,
+                                   uint64_t *prefix_lens_out, bn_f128 *products_out, bn_f128 *gpa_round_proofs_out, bn_f128 *gpa_layer_evals_out,
+                                   bn_f128 *gpa_final_points_out, bn_f128 *gpa_final_evals_out, uint32_t *n_checks_out, uint32_t *check_desc_out, uint32_t *check_ids_out,
+                                   bn_f128 *check_round_proofs_out, bn_f128 *check_final_evals_out, uint32_t *n_linear_out, uint32_t *linear_flushes_out,
+                                   double *phase_ms_out);
+int bnh_evalcheck_bivariate_prove_lc_live(bn_ctx *ctx, uint32_t n_provers, const uint32_t *prover_desc, const uint32_t *ml_desc, const void *const *d_columns,
+                                          uint32_t n_terms, const uint32_t *term_levels, const void *const *d_term_columns, const bn_f128 *term_coeffs,
+                                          const bn_f128 *ml_offsets, const bn_f128 *point_pool, uint32_t pool_len, const uint32_t *comp_indices, const bn_f128 *sums,
+                                          void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript, bn_f128 *round_proofs_out, bn_f128 *final_evals_out);
+int bnh_ring_switch_prove_live(bn_ctx *ctx, uint32_t n_columns, const void *const *d_columns, const uint32_t *column_desc, const bn_f128 *point_pool, uint32_t pool_len,
+                               uint32_t n_suffixes, const uint32_t *suffix_desc, uint32_t n_prefixes, const uint32_t *prefix_kappas, uint32_t n_claims,
+                               const uint32_t *claim_desc, const bnh_transcript *transcript, void *d_scratch, uint64_t scratch_elems, bn_f128 *mixed_tensor_elems_out,
+                               bn_f128 *row_batched_evals_out, void **d_transparents_out, double *phase_ms_out);
+int bnh_fri_prove_live(bn_ctx *ctx, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities, uint32_t n_arities,
+                       uint32_t n_test_queries, const void *d_message, void *d_scratch, uint64_t scratch_elems, const bnh_transcript *transcript, uint8_t *roots_out,
+                       bn_f128 *advice_out, uint64_t max_advice_elems, uint64_t *n_advice_elems_out, double *phase_ms_out);
+int bnh_piop_prove_committed_open_live(bn_ctx *ctx, uint32_t n_committed, const uint32_t *committed_n_vars, const void *const *d_committed, uint32_t n_transparent,
+                                       const uint32_t *transparent_n_vars, const void *const *d_transparent, uint32_t n_claims, const uint32_t *claims,
+                                       const bn_f128 *claim_sums, uint32_t log_dim, uint32_t log_inv_rate, uint32_t log_batch_size, const uint32_t *fold_arities,
+                                       uint32_t n_arities, uint32_t n_test_queries, const void *d_codeword, const void *d_tree, void *d_scratch, uint64_t scratch_elems,
+                                       const bnh_transcript *transcript, uint32_t *items_out, uint32_t max_items, uint32_t *n_items_out, bn_f128 *scalars_out,
+                                       uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out, uint32_t max_digests, uint32_t *n_digests_out,
+                                       double *phase_ms_out, bn_f128 *advice_out, uint64_t max_advice_elems, uint64_t *n_advice_elems_out);
+
+/* An array-backed transcript, for C callers, benchmarks and tests: it serves samples[n_samples] to `sample` and
+ * bit_samples[n_bit_samples] (masked to `bits`) to `sample_bits`, in order, returns non-zero when they run out, and records every
+ * write.  Pure host code, no context.
+ * bnh_transcript_replay_table: the table to hand to a `_live` entry point; valid until bnh_transcript_replay_free.
+ * bnh_transcript_replay_written: the bytes written to `channel` so far, concatenated; *len_out is set even when buf (max bytes) is too
+ *   small, which is BN_ERR_INPUT_VALIDATION.
+ * bnh_transcript_replay_events: the alternation log.  kinds_out[i] is a BNH_TR_EVENT_*; counts_out[i] its bytes (writes) or its
+ *   samples (draws).  Neighbouring events of one kind are one event: the log does not depend on how writes or draws were cut into
+ *   calls.  *n_events_out is set even when max_events is too small, which is BN_ERR_INPUT_VALIDATION. */
+enum { BNH_TR_EVENT_WRITE_MESSAGE = 0, BNH_TR_EVENT_WRITE_DECOMMITMENT = 1, BNH_TR_EVENT_SAMPLE = 2, BNH_TR_EVENT_SAMPLE_BITS = 3 };
+typedef struct bnh_transcript_replay bnh_transcript_replay;
+int bnh_transcript_replay_new(const bn_f128 *samples, uint64_t n_samples, const uint64_t *bit_samples, uint64_t n_bit_samples, bnh_transcript_replay **handle_out);
+const bnh_transcript *bnh_transcript_replay_table(bnh_transcript_replay *handle);
+int bnh_transcript_replay_written(bnh_transcript_replay *handle, uint32_t channel, uint8_t *buf, uint64_t max, uint64_t *len_out);
+int bnh_transcript_replay_events(bnh_transcript_replay *handle, uint32_t *kinds_out, uint64_t *counts_out, uint64_t max_events, uint64_t *n_events_out);
+void bnh_transcript_replay_free(bnh_transcript_replay *handle);
+
 /* shared-memory exchange: rank 0 creates the segment `name` ("/..."), the others open it afterwards */
 int bnh_shm_open(const char *name, int world, int rank, int create, void **handle_out);
 int bnh_shm_close(void *handle);
