@@ -81,6 +81,18 @@ class PelJob(C.Structure):
 PEL_MAX_TERMS = 64  # BN_PEL_MAX_TERMS
 
 
+class DeriveJob(C.Structure):
+    """bn_derive_job: one virtual column of bn_derive_columns_batch."""
+
+    _fields_ = [("kind", C.c_uint32), ("tower_level", C.c_uint32), ("n_vars", C.c_uint32), ("inner_n_vars", C.c_uint32), ("d_inner", C.c_void_p),
+                ("d_out", C.c_void_p), ("block_size", C.c_uint32), ("shift_variant", C.c_uint32), ("shift_offset", C.c_uint64), ("start_index", C.c_uint32),
+                ("reserved", C.c_uint32), ("nonzero_index", C.c_uint64), ("first_term", C.c_uint32), ("n_terms", C.c_uint32), ("offset", F128)]
+
+
+DERIVE_SHIFTED, DERIVE_REPEATING, DERIVE_ZERO_PADDED, DERIVE_XOR_COMBINATION = range(4)  # BN_DERIVE_*
+SHIFT_CIRCULAR_LEFT, SHIFT_LOGICAL_LEFT, SHIFT_LOGICAL_RIGHT = range(3)  # BN_SHIFT_* (ShiftVariant)
+
+
 class RsJob(C.Structure):
     """bn_rs_job: one equality indicator of bn_ring_switch_eq_ind_batch."""
 
@@ -216,6 +228,8 @@ def lib():
         "bn_mle_evaluate_counters": [vp, C.POINTER(u64)],
         "bn_merge_multilins": [vp, u32, C.POINTER(u32), C.POINTER(vp), vp, u32, u32],
         "bn_merge_counters": [vp, C.POINTER(u64)],
+        "bn_derive_columns_batch": [vp, vp, u32, C.POINTER(vp), u32],
+        "bn_derive_counters": [vp, C.POINTER(u64)],
         "bn_fri_query_proof_elems": [vp, u32, u64, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
         "bn_fri_query_openings": [vp, vp, u32, vp, u64, C.POINTER(u64), u64, u32, vp, u64],
         "bn_fri_query_counters": [vp, C.POINTER(u64)],
@@ -278,7 +292,7 @@ ABI_SYMBOLS = [
     "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
     "bn_univariate_fold_batch", "bn_univariate_fold_counters", "bn_ring_switch_eq_ind_batch", "bn_ring_switch_counters",
     "bn_mle_evaluate_batch", "bn_mle_evaluate_counters", "bn_partial_eval_high_lincomb_batch", "bn_partial_eval_lincomb_counters",
-    "bn_merge_multilins", "bn_merge_counters", "bn_fri_query_proof_elems", "bn_fri_query_openings", "bn_fri_query_counters",
+    "bn_merge_multilins", "bn_merge_counters", "bn_derive_columns_batch", "bn_derive_counters", "bn_fri_query_proof_elems", "bn_fri_query_openings", "bn_fri_query_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -1104,6 +1118,44 @@ class Context:
         c = (C.c_uint64 * 5)()
         _check(lib().bn_merge_counters(self._h, c))
         return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2]), "jobs_tiled": int(c[3]), "jobs_small": int(c[4])}
+
+    @staticmethod
+    def derive_job_table(jobs):
+        """The arguments of bn_derive_columns_batch, marshalled once: (DeriveJob array, n_jobs, c_void_p term array, n_terms) for
+        derive_columns_raw.  jobs: dicts with kind ("shifted", "repeating", "zero_padded", "xor"), level, n_vars, out (a DevSlice of
+        2^(n_vars + level - 7) elements) and, by kind: inner (DevSlice), block_size, shift_offset, variant ("circular_left", "logical_left",
+        "logical_right"); inner, inner_n_vars; inner, inner_n_vars, start_index, nonzero_index; terms (DevSlices of the output's level and
+        n_vars), offset (an int of the output's level)."""
+        kinds = {"shifted": DERIVE_SHIFTED, "repeating": DERIVE_REPEATING, "zero_padded": DERIVE_ZERO_PADDED, "xor": DERIVE_XOR_COMBINATION}
+        variants = {"circular_left": SHIFT_CIRCULAR_LEFT, "logical_left": SHIFT_LOGICAL_LEFT, "logical_right": SHIFT_LOGICAL_RIGHT}
+        table, terms = [], []
+        for jb in jobs:
+            out, inner = jb.get("out"), jb.get("inner")
+            if out is not None and jb["n_vars"] <= 40 and jb["level"] <= 7 and jb["n_vars"] + jb["level"] >= 7 and out.len != 1 << (jb["n_vars"] + jb["level"] - 7):
+                raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: output has the wrong number of elements")
+            tms = jb.get("terms", [])
+            table.append(DeriveJob(kinds.get(jb["kind"], jb["kind"]), jb["level"], jb["n_vars"], jb.get("inner_n_vars", 0), inner.ptr if inner is not None else None,
+                                   out.ptr if out is not None else None, jb.get("block_size", 0), variants.get(jb.get("variant", 0), jb.get("variant", 0)),
+                                   jb.get("shift_offset", 0), jb.get("start_index", 0), jb.get("reserved", 0), jb.get("nonzero_index", 0), len(terms), len(tms),
+                                   to_f128(jb.get("offset", 0))))
+            terms += [(t.ptr if t is not None else None) for t in tms]
+        return (DeriveJob * max(1, len(table)))(*table), len(table), (C.c_void_p * max(1, len(terms)))(*terms), len(terms)
+
+    def derive_columns_batch(self, jobs):
+        """The virtual columns of a constraint system built on the device in one launch (bn_derive_columns_batch; validate.rs:151-279,
+        fold.rs:27-77).  jobs: as derive_job_table takes them."""
+        self.derive_columns_raw(*self.derive_job_table(jobs))
+
+    def derive_columns_raw(self, jobs, n_jobs, terms, n_terms):
+        """bn_derive_columns_batch on a caller-built DeriveJob array and c_void_p term array, nothing checked here."""
+        _check(lib().bn_derive_columns_batch(self._h, C.cast(jobs, C.c_void_p) if jobs is not None else None, n_jobs, terms, n_terms))
+
+    def derive_counters(self):
+        """bn_derive_counters: accepted bn_derive_columns_batch calls, the kernel launches they made, the jobs they served.  Rejected
+        calls count nowhere."""
+        c = (C.c_uint64 * 3)()
+        _check(lib().bn_derive_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2])}
 
     def fri_query_openings(self, oracles, terminate, indices, index_bits, out_elems=None):
         """bn_fri_query_openings: the decommitment of FRIFolder::finish_proof (fri/prove.rs:483-507) in one launch.  oracles: tuples

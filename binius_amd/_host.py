@@ -360,6 +360,10 @@ def _plain_host_lib():
         L.bnh_zerocheck_batch_scratch_elems_tower.argtypes = [C.c_uint32, C.c_uint32, U32P, U32P, U32P]
         L.bnh_zerocheck_batch_prove_tower.restype = C.c_int
         L.bnh_zerocheck_batch_prove_tower.argtypes = L.bnh_zerocheck_batch_prove.argtypes
+        L.bnh_witness_derive_scratch_elems.restype = C.c_uint64
+        L.bnh_witness_derive_scratch_elems.argtypes = [C.c_uint32, U32P, U64P, U32P, FP, C.c_uint32, FP]
+        L.bnh_witness_derive.restype = C.c_int
+        L.bnh_witness_derive.argtypes = [C.c_void_p, C.c_uint32, U32P, U64P, VPP, U32P, FP, C.c_uint32, FP, C.c_void_p, C.c_uint64, VPP, U32P, U32P, U32P, U32P]
         # the _live forms: the array form's arguments without the samples, the transcript's table where LIVE_FORMS says
         for name, (live, drop, at, _splice) in LIVE_FORMS.items():
             if name == "bnh_evalcheck_bivariate_prove":
@@ -1598,3 +1602,75 @@ class ZerocheckBatchPlan:
 
     def phases(self):
         return {name: (float(self.phase_ms[i]), int(self.phase_calls[i])) for i, name in enumerate(self.PHASES)}
+
+
+class WitnessPlan:
+    """The virtual columns of a constraint system derived on the device (bnh_witness_derive = binius_amd/host/witness.hpp): the
+    witness-side reading of a MultilinearOracleSet (multilinear.rs of core's oracle module).  columns, in oracle-id order, each one of
+      ("given", DevSlice, tower_level, n_vars)
+      ("shifted", inner, block_size, shift_offset, variant)       variant: "circular_left" / "logical_left" / "logical_right" or 0 / 1 / 2
+      ("repeating", inner, log_count)
+      ("zero_padded", inner, n_pad_vars, start_index, nonzero_index)
+      ("packed", inner, log_degree)                               an alias: the inner's pointer, no launch
+      ("lincomb", [(inner, coeff), ...], offset, n_vars)          coefficients and offset as ints
+    with inner an index smaller than the column's own.  scratch: a device slice of at least scratch_elems(columns) elements.  run()
+    returns [(DevSlice, tower_level, n_vars)] per column; n_waves and n_launches afterwards."""
+
+    KINDS = {"given": 0, "shifted": 1, "repeating": 2, "zero_padded": 3, "packed": 4, "lincomb": 5}
+    VARIANTS = {"circular_left": 0, "logical_left": 1, "logical_right": 2}
+
+    @classmethod
+    def _marshal(cls, columns):
+        desc, args, given, terms, coeffs, offsets = [], [], [], [], [], []
+        for c in columns:
+            kind = cls.KINDS.get(c[0], c[0])
+            d, arg, ptr, off = [0, 0, 0], 0, None, 0
+            if kind == 0:
+                ptr, d = (c[1].ptr if c[1] is not None else None), [c[2], c[3], 0]
+            elif kind == 1:
+                d, arg = [c[1], c[2], cls.VARIANTS.get(c[4], c[4])], c[3]
+            elif kind in (2, 4):
+                d = [c[1], c[2], 0]
+            elif kind == 3:
+                d, arg = [c[1], c[2], c[3]], c[4]
+            elif kind == 5:
+                d, off = [len(terms), len(c[1]), c[3]], c[2]
+                terms += [t[0] for t in c[1]]
+                coeffs += [t[1] for t in c[1]]
+            desc += [kind] + [int(x) for x in d]
+            args.append(int(arg))
+            given.append(ptr)
+            offsets.append(off)
+        n = len(columns)
+        return (n, (C.c_uint32 * max(1, 4 * n))(*desc), (C.c_uint64 * max(1, n))(*args), (C.c_void_p * max(1, n))(*given),
+                (C.c_uint32 * max(1, len(terms)))(*terms), _f128_array(coeffs or [0]), len(terms), _f128_array(offsets or [0]))
+
+    @classmethod
+    def scratch_elems(cls, columns):
+        n, desc, args, _given, terms, coeffs, n_terms, offsets = cls._marshal(columns)
+        return int(host_lib().bnh_witness_derive_scratch_elems(n, desc, args, terms, coeffs, n_terms, offsets))
+
+    def __init__(self, hal, columns, scratch):
+        self.hal, self.scratch, self._keep = hal, scratch, columns
+        self.n, self.desc, self.args, self.given, self.terms, self.coeffs, self.n_terms, self.offsets = self._marshal(columns)
+        self.ptrs = (C.c_void_p * max(1, self.n))()
+        self.levels, self.n_vars = (C.c_uint32 * max(1, self.n))(), (C.c_uint32 * max(1, self.n))()
+        self._waves, self._launches = C.c_uint32(0), C.c_uint32(0)
+
+    def run(self):
+        from ._ffi import DevSlice
+
+        rc = host_lib().bnh_witness_derive(self.hal._h, self.n, self.desc, self.args, self.given, self.terms, self.coeffs, self.n_terms, self.offsets,
+                                           self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0,
+                                           self.ptrs, self.levels, self.n_vars, C.byref(self._waves), C.byref(self._launches))
+        if rc != 0:
+            raise BnError(rc, host_lib().bnh_last_error().decode())
+        return [(DevSlice(self.ptrs[i], max(1, (1 << (self.n_vars[i] + self.levels[i])) >> 7)), int(self.levels[i]), int(self.n_vars[i])) for i in range(self.n)]
+
+    @property
+    def n_waves(self):
+        return int(self._waves.value)
+
+    @property
+    def n_launches(self):
+        return int(self._launches.value)

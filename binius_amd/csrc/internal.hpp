@@ -87,6 +87,7 @@ struct bn_ctx {
 	uint64_t me_calls = 0, me_launches = 0, me_jobs = 0, me_max_share = 0; // bn_mle_evaluate_batch (bn_mle_evaluate_counters)
 	uint64_t mg_calls = 0, mg_launches = 0, mg_jobs = 0, mg_jobs_tiled = 0, mg_jobs_small = 0; // bn_merge_multilins (bn_merge_counters)
 	uint64_t fq_calls = 0, fq_launches = 0, fq_openings = 0; // bn_fri_query_openings (bn_fri_query_counters)
+	uint64_t dv_calls = 0, dv_launches = 0, dv_jobs = 0; // bn_derive_columns_batch (bn_derive_counters)
 	bn::f128 *h_me_rets = nullptr, *d_me_rets = nullptr; // pinned: the results of a bn_mle_evaluate_batch call, BN_ME_MAX_JOBS values (the sequence word stays in h_mail[64])
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -978,6 +979,44 @@ struct fri_query_args {
 };
 // d_indices: n_queries indices, readable by the device; out: header_elems + n_queries * record_elems units
 hipError_t launch_fri_query(hipStream_t s, const fri_query_args &a, const uint64_t *d_indices, void *out);
+
+// ---- kernels_derive.hip: virtual columns of the constraint system (Shifted, Repeating, ZeroPadded, and LinearCombination with unit
+// coefficients: multilinear.rs of core's oracle module, constraint_system/validate.rs:151-279, math/src/fold.rs:27-77) built from columns on the
+// device, at their own tower level.  A job is one output column in one FORM; the host resolves kind, tower level and sizes into a form and
+// its parameters in BIT coordinates (a value of level l is 2^l bits), so the kernel has no notion of a tower level.  A unit (one
+// workgroup) is kDeriveUnitElems contiguous 16-byte outputs of one job.  The meaning of p0 .. p3 / m0, m1 per form:
+//   kDvShiftWord   blocks of 2 .. 64 bits: every 64-bit word w of the inner becomes ((w << p0) & m0) | ((w >> p1) & m1)
+//   kDvShiftElem   blocks of 2^p0 elements: output element e of a block is the 128-bit window that starts p2 bits into element
+//                  e + m0 of the inner block (indices taken modulo the block); an element whose unreduced index q fails
+//                  m1 <= q < m1 + 2^p0 counts as zero unless p1 (circular)
+//   kDvRepeat      out[j] = in[j & m0]; p0 != 0: the low p0 (< 128) bits of that element, repeated
+//   kDvPadElem     runs of 2^p0 elements in periods of 2^p1: out[j] = in[(j >> p1 << p0) + (j & (2^p0 - 1))] where
+//                  (j & (2^p1 - 1)) >> p0 == m0, else zero
+//   kDvPadField    runs of 2^p0 (< 128) bits in periods of 2^p1 elements: element m0 of a period holds, at bit p2, the run of period
+//                  r = j >> p1, which is bits [r 2^p0, (r + 1) 2^p0) of the inner; every other element is zero
+//   kDvPadSpread   runs of 2^p0 bits in periods of 2^p1 <= 64 bits, p2 = log2 of the periods-per-run ratio (n_pad_vars): output
+//                  word W takes the 64 >> p2 bits at bit (W & (2^p2 - 1)) * (64 >> p2) of inner word W >> p2 and puts run k at bit
+//                  k 2^p1 + p3
+//   kDvXor         out[j] = (m0, m1) ^ XOR over terms [first_term, first_term + n_terms) of the term table of term[j]
+enum : uint32_t { kDvShiftWord = 0, kDvShiftElem = 1, kDvRepeat = 2, kDvPadElem = 3, kDvPadField = 4, kDvPadSpread = 5, kDvXor = 6 };
+struct derive_job {
+	const void *in; // the inner column (kDvXor: unused)
+	uint4 *out;
+	uint64_t out_elems;
+	uint64_t m0, m1;
+	uint32_t p0, p1, p2, p3;
+	uint32_t form;
+	uint32_t first_term, n_terms;
+	uint32_t start; // first unit of this job in the launch
+};
+// 16-byte outputs of a unit: a multiple of 1024, taken 1024 at a time.  4096 against 1024: profiles/r22/unit_elems_ab.txt (a measurement
+// build sets the other value with -DBN_DERIVE_UNIT_ELEMS=...)
+#ifndef BN_DERIVE_UNIT_ELEMS
+#define BN_DERIVE_UNIT_ELEMS 4096
+#endif
+constexpr uint32_t kDeriveUnitElems = BN_DERIVE_UNIT_ELEMS;
+static_assert(kDeriveUnitElems % 1024 == 0 && kDeriveUnitElems > 0, "a unit is whole chunks of 1024 elements");
+hipError_t launch_derive_columns(hipStream_t s, const derive_job *d_jobs, uint32_t n_jobs, const void *const *d_terms, uint32_t total_units);
 
 // ---- kernels_ntt_tiled.hip
 hipError_t launch_build_mul8(hipStream_t s, uint8_t *d_tab);

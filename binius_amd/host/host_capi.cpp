@@ -34,6 +34,7 @@
 #include "ring_switch.hpp"
 #include "sumcheck.hpp"
 #include "transcript.hpp"
+#include "witness.hpp"
 #include "zerocheck.hpp"
 
 using namespace binius_amd;
@@ -2035,6 +2036,91 @@ int bnh_ring_switch_prove_live(bn_ctx *ctx, uint32_t n_columns, const void *cons
 {
 	return ring_switch_prove_body(ctx, n_columns, d_columns, column_desc, point_pool, pool_len, n_suffixes, suffix_desc, n_prefixes, prefix_kappas, n_claims, claim_desc, nullptr,
 	                              0, nullptr, 0, d_scratch, scratch_elems, mixed_tensor_elems_out, row_batched_evals_out, d_transparents_out, phase_ms_out, true, transcript);
+}
+
+// The virtual columns of a constraint system derived on the device through the C++ mirror binius_amd/host/witness.hpp; the arguments are
+// described in include/binius_amd_host.h.
+namespace {
+std::vector<WitnessColumn> witness_columns(uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
+                                           const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets)
+{
+	if (n_columns && (!col_desc || !col_args || !lc_offsets)) throw Error(Error::InputValidation, "null argument");
+	if (n_lc_terms && (!lc_terms || !lc_coeffs)) throw Error(Error::InputValidation, "null argument");
+	std::vector<WitnessColumn> cols(n_columns);
+	for (uint32_t i = 0; i < n_columns; i++) {
+		const uint32_t *d = col_desc + 4 * i;
+		WitnessColumn &c = cols[i];
+		c.kind = d[0];
+		switch (c.kind) {
+		case WitnessColumn::Given:
+			c.d_evals = d_given ? d_given[i] : reinterpret_cast<const void *>(16); // (the scratch formula reads no pointer)
+			c.tower_level = d[1];
+			c.n_vars = d[2];
+			break;
+		case WitnessColumn::Shifted:
+			c.inner = d[1];
+			c.block_size = d[2];
+			c.shift_variant = d[3];
+			c.shift_offset = col_args[i];
+			break;
+		case WitnessColumn::Repeating:
+			c.inner = d[1];
+			c.log_count = d[2];
+			break;
+		case WitnessColumn::ZeroPadded:
+			c.inner = d[1];
+			c.n_pad_vars = d[2];
+			c.start_index = d[3];
+			c.nonzero_index = col_args[i];
+			break;
+		case WitnessColumn::Packed:
+			c.inner = d[1];
+			c.log_degree = d[2];
+			break;
+		case WitnessColumn::LinearCombination:
+			if (d[1] > n_lc_terms || d[2] > n_lc_terms - d[1]) throw Error(Error::InputValidation, "witness: a combination's terms leave the term list");
+			c.terms.assign(lc_terms + d[1], lc_terms + d[1] + d[2]);
+			c.coefficients = from_raw(lc_coeffs + d[1], d[2]);
+			c.n_vars = d[3];
+			c.offset = B128(lc_offsets[i].lo, lc_offsets[i].hi);
+			break;
+		default:
+			break; // (witness_shapes rejects it)
+		}
+	}
+	return cols;
+}
+} // namespace
+
+uint64_t bnh_witness_derive_scratch_elems(uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const uint32_t *lc_terms, const bn_f128 *lc_coeffs,
+                                          uint32_t n_lc_terms, const bn_f128 *lc_offsets)
+{
+	try {
+		return witness_derive_scratch_elems(witness_columns(n_columns, col_desc, col_args, nullptr, lc_terms, lc_coeffs, n_lc_terms, lc_offsets));
+	} catch (const Error &) {
+		return 0;
+	}
+}
+
+int bnh_witness_derive(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
+                       const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
+                       uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out)
+{
+	return guarded([&]() -> int {
+		if (!ctx || (n_columns && (!d_given || !d_columns_out || !tower_levels_out || !n_vars_out)) || (!d_scratch && scratch_elems))
+			throw Error(Error::InputValidation, "null argument");
+		const std::vector<WitnessColumn> cols = witness_columns(n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets);
+		ComputeLayer hal(ctx);
+		const WitnessOutput out = witness_derive(hal, cols, FSliceMut{d_scratch, (size_t)scratch_elems});
+		for (uint32_t i = 0; i < n_columns; i++) {
+			d_columns_out[i] = const_cast<void *>(out.columns[i].ptr);
+			tower_levels_out[i] = out.columns[i].tower_level;
+			n_vars_out[i] = out.columns[i].n_vars;
+		}
+		if (n_waves_out) *n_waves_out = out.n_waves;
+		if (n_launches_out) *n_launches_out = out.n_launches;
+		return 0;
+	});
 }
 
 } // extern "C"

@@ -1,0 +1,313 @@
+// binius_amd/host/witness.hpp -- C++ mirror of the witness-side reading of a MultilinearOracleSet (multilinear.rs of core's oracle module): the
+// virtual columns that are pure functions of columns already on the device are built there, instead of being filled on the host and
+// uploaded.  The caller lists the columns in oracle-id order; a column is one of
+//
+//   Given              a device pointer, tower level, n_vars (committed columns, and whatever the caller did upload)
+//   Shifted            add_shifted        same level and n_vars as the inner                       BN_DERIVE_SHIFTED
+//   Repeating          add_repeating      same level, n_vars = inner + log_count                    BN_DERIVE_REPEATING
+//   ZeroPadded         add_zero_padded    same level, n_vars = inner + n_pad_vars                   BN_DERIVE_ZERO_PADDED
+//   Packed             add_packed         level = inner + log_degree, n_vars = inner - log_degree   an ALIAS: the inner's pointer, no launch
+//   LinearCombination  add_linear_combination[_with_offset]: level = the maximum over its terms' levels and the minimal levels of its
+//                      coefficients and offset (multilinear.rs:91-266); all coefficients ONE and every term at that level:
+//                      BN_DERIVE_XOR_COMBINATION; otherwise, at level 7, bn_partial_eval_high_lincomb_batch at query_vars = 0 (the
+//                      one-element query ONE sits in scratch); otherwise InputValidation
+//
+// and refers to its inner columns by index, always smaller than its own, as OracleIds are.  NOT taken: Projected
+// (bn_partial_eval_high_batch / bn_fold_right are the ops for it), Composite (bn_compute_composite), transparent and structured
+// polynomials -- the caller derives or uploads those and lists them as Given.
+//
+// Waves: a column's wave is one more than its deepest inner (Given: 0; a Packed alias adds nothing).  ONE bn_derive_columns_batch per
+// wave, plus ONE lincomb call per wave that has a B128 combination outside the XOR form.  Columns of less than one 16-byte element
+// are host work (one element down, one up), as zerocheck.hpp does for its padding; they make no launch.
+#pragma once
+#include <algorithm>
+#include <cstring>
+
+#include "compute_layer.hpp"
+
+namespace binius_amd {
+
+struct WitnessColumn {
+	enum Kind : uint32_t { Given = 0, Shifted = 1, Repeating = 2, ZeroPadded = 3, Packed = 4, LinearCombination = 5 };
+	uint32_t kind = Given;
+	// Given
+	const void *d_evals = nullptr;
+	uint32_t tower_level = 0, n_vars = 0; // (LinearCombination: n_vars, which a combination without terms cannot take from them)
+	// Shifted / Repeating / ZeroPadded / Packed
+	uint32_t inner = 0;
+	uint32_t block_size = 0, shift_variant = 0; // Shifted
+	uint64_t shift_offset = 0;
+	uint32_t log_count = 0;                     // Repeating
+	uint32_t n_pad_vars = 0, start_index = 0;   // ZeroPadded
+	uint64_t nonzero_index = 0;
+	uint32_t log_degree = 0;                    // Packed
+	// LinearCombination
+	std::vector<uint32_t> terms;
+	std::vector<B128> coefficients;
+	B128 offset = B128::ZERO();
+};
+struct WitnessResolved {
+	const void *ptr = nullptr;
+	uint32_t tower_level = 0, n_vars = 0, wave = 0;
+};
+struct WitnessOutput {
+	std::vector<WitnessResolved> columns;
+	uint32_t n_waves = 0;    // the largest wave of a column
+	uint32_t n_launches = 0; // bn_derive_columns_batch and lincomb calls made
+};
+
+inline size_t witness_column_elems(size_t n_vars, uint32_t level) { return n_vars + level <= 7 ? 1 : (size_t)1 << (n_vars + level - 7); }
+// binary_tower_level() of a field element: the smallest level whose field holds it
+inline uint32_t witness_min_level(B128 c)
+{
+	if (c.hi) return 7;
+	uint32_t level = 0;
+	while (level < 6 && (c.lo >> (1u << level))) level++;
+	return level;
+}
+
+// How a column is made: by the derive op, by the lincomb op, on the host, or not at all (Given, Packed)
+enum class WitnessRoute { None, Derive, Lincomb, Host };
+struct WitnessShape {
+	uint32_t tower_level = 0, n_vars = 0, wave = 0;
+	WitnessRoute route = WitnessRoute::None;
+};
+
+// Levels, sizes, waves and routes of every column; every rule of the header is checked here, before the first device call.
+inline std::vector<WitnessShape> witness_shapes(const std::vector<WitnessColumn> &cols)
+{
+	auto bad = [](const char *msg) { return Error(Error::InputValidation, msg); };
+	std::vector<WitnessShape> sh(cols.size());
+	for (size_t i = 0; i < cols.size(); i++) {
+		const WitnessColumn &c = cols[i];
+		WitnessShape &s = sh[i];
+		if (c.kind >= WitnessColumn::Shifted && c.kind <= WitnessColumn::Packed && c.inner >= i) throw bad("witness: an inner index is smaller than the column's own");
+		switch (c.kind) {
+		case WitnessColumn::Given:
+			if (!c.d_evals) throw bad("witness: null given column");
+			if (c.tower_level > 7 || c.tower_level == 1 || c.tower_level == 2) throw bad("witness: unsupported tower level");
+			s = WitnessShape{c.tower_level, c.n_vars, 0, WitnessRoute::None};
+			break;
+		case WitnessColumn::Shifted:
+			s = WitnessShape{sh[c.inner].tower_level, sh[c.inner].n_vars, sh[c.inner].wave + 1, WitnessRoute::Derive};
+			if (c.shift_variant > BN_SHIFT_LOGICAL_RIGHT) throw bad("witness: unknown shift variant");
+			if (c.block_size > s.n_vars || c.shift_offset == 0 || c.block_size > BN_PE_MAX_VARS || c.shift_offset >= ((uint64_t)1 << c.block_size))
+				throw bad("witness: Shifted needs block_size <= n_vars and 1 <= shift_offset < 2^block_size");
+			break;
+		case WitnessColumn::Repeating:
+			if (c.log_count > BN_PE_MAX_VARS) throw bad("witness: log_count out of range");
+			s = WitnessShape{sh[c.inner].tower_level, sh[c.inner].n_vars + c.log_count, sh[c.inner].wave + 1, WitnessRoute::Derive};
+			break;
+		case WitnessColumn::ZeroPadded:
+			if (c.n_pad_vars > BN_PE_MAX_VARS) throw bad("witness: n_pad_vars out of range");
+			s = WitnessShape{sh[c.inner].tower_level, sh[c.inner].n_vars + c.n_pad_vars, sh[c.inner].wave + 1, WitnessRoute::Derive};
+			if (c.start_index > sh[c.inner].n_vars) throw bad("IncorrectStartIndex: start_index > inner n_vars");
+			if (c.nonzero_index >= ((uint64_t)1 << c.n_pad_vars)) throw bad("IncorrectNonZeroIndex: nonzero_index >= 2^n_pad_vars");
+			break;
+		case WitnessColumn::Packed:
+			if (c.log_degree > sh[c.inner].n_vars || sh[c.inner].tower_level + c.log_degree > 7) throw bad("witness: Packed leaves the tower or the column");
+			s = WitnessShape{sh[c.inner].tower_level + c.log_degree, sh[c.inner].n_vars - c.log_degree, sh[c.inner].wave, WitnessRoute::None};
+			if (s.tower_level == 1 || s.tower_level == 2) throw bad("witness: unsupported tower level");
+			break;
+		case WitnessColumn::LinearCombination: {
+			if (c.terms.size() != c.coefficients.size()) throw bad("witness: one coefficient per term");
+			if (c.terms.size() > BN_PEL_MAX_TERMS) throw bad("witness: too many terms in a combination");
+			uint32_t level = witness_min_level(c.offset), wave = 0;
+			bool unit = true;
+			for (size_t t = 0; t < c.terms.size(); t++) {
+				if (c.terms[t] >= i) throw bad("witness: an inner index is smaller than the column's own");
+				if (sh[c.terms[t]].n_vars != c.n_vars) throw bad("witness: the terms of a combination have its n_vars");
+				level = std::max({level, sh[c.terms[t]].tower_level, witness_min_level(c.coefficients[t])});
+				wave = std::max(wave, sh[c.terms[t]].wave);
+				unit = unit && c.coefficients[t] == B128::ONE();
+			}
+			if (level == 1 || level == 2) level = 3; // (the packed levels of this backend: a B2 / B4 constant lives in a B8 column)
+			for (const uint32_t t : c.terms) unit = unit && sh[t].tower_level == level;
+			s = WitnessShape{level, c.n_vars, wave + 1, unit ? WitnessRoute::Derive : WitnessRoute::Lincomb};
+			if (!unit && level != 7)
+				throw bad("witness: a combination is either all ONE coefficients over terms of its own level or a B128 one (Projected, Composite, transparent and "
+				          "structured columns are not taken either: list them as Given)");
+			break;
+		}
+		default:
+			throw bad("witness: unknown column kind");
+		}
+		if (s.n_vars > BN_PE_MAX_VARS) throw bad("witness: a column has at most 2^40 values");
+		if (s.route == WitnessRoute::Derive && s.n_vars + s.tower_level < 7) s.route = WitnessRoute::Host;
+	}
+	return sh;
+}
+
+// Exact: one element for the query ONE when a combination goes to the lincomb op, then every derived column at its packed size.
+inline size_t witness_derive_scratch_elems(const std::vector<WitnessColumn> &cols)
+{
+	const std::vector<WitnessShape> sh = witness_shapes(cols);
+	size_t total = 0;
+	bool one = false;
+	for (const WitnessShape &s : sh) {
+		if (s.route == WitnessRoute::None) continue;
+		one = one || s.route == WitnessRoute::Lincomb;
+		total += witness_column_elems(s.n_vars, s.tower_level);
+	}
+	return total + (one ? 1 : 0);
+}
+
+namespace witness_detail {
+// value i (2^level <= 64 bits) of a packed column of at most 128 bits
+inline uint64_t get(const B128 &e, uint32_t level, size_t i)
+{
+	const size_t w = (size_t)1 << level, bit = i * w;
+	const uint64_t word = bit < 64 ? e.lo : e.hi;
+	return w == 64 ? word : (word >> (bit & 63)) & (((uint64_t)1 << w) - 1);
+}
+inline void put(B128 &e, uint32_t level, size_t i, uint64_t v)
+{
+	const size_t bit = (i << level);
+	(bit < 64 ? e.lo : e.hi) |= v << (bit & 63);
+}
+} // namespace witness_detail
+
+// A column of less than one element, value by value (validate.rs:151-279, fold.rs:52-75) from its inner columns' single elements
+inline B128 witness_small_column(const WitnessColumn &c, const WitnessShape &s, const std::vector<WitnessShape> &sh, const std::vector<B128> &inners)
+{
+	using witness_detail::get;
+	using witness_detail::put;
+	const uint32_t l = s.tower_level;
+	const size_t n = (size_t)1 << s.n_vars;
+	B128 out = B128::ZERO();
+	for (size_t i = 0; i < n; i++) {
+		uint64_t v = 0;
+		switch (c.kind) {
+		case WitnessColumn::Shifted: {
+			const size_t B = (size_t)1 << c.block_size, o = i & (B - 1), blk = i - o, sft = (size_t)c.shift_offset;
+			if (c.shift_variant == BN_SHIFT_CIRCULAR_LEFT)
+				v = get(inners[0], l, blk + ((o + B - sft) & (B - 1)));
+			else if (c.shift_variant == BN_SHIFT_LOGICAL_LEFT)
+				v = o >= sft ? get(inners[0], l, blk + o - sft) : 0;
+			else
+				v = o + sft < B ? get(inners[0], l, blk + o + sft) : 0;
+			break;
+		}
+		case WitnessColumn::Repeating:
+			v = get(inners[0], l, i & (((size_t)1 << sh[c.inner].n_vars) - 1));
+			break;
+		case WitnessColumn::ZeroPadded: {
+			const size_t run = (size_t)1 << c.start_index, period = run << c.n_pad_vars, col = i & (period - 1), row = i / period, z = (size_t)c.nonzero_index * run;
+			v = col >= z && col < z + run ? get(inners[0], l, row * run + col - z) : 0;
+			break;
+		}
+		default:
+			v = c.offset.lo;
+			for (const B128 &t : inners) v ^= get(t, l, i);
+			break;
+		}
+		put(out, l, i, v);
+	}
+	return out;
+}
+
+inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch)
+{
+	const std::vector<WitnessShape> sh = witness_shapes(cols);
+	if (scratch.len_ < witness_derive_scratch_elems(cols)) throw Error(Error::InputValidation, "scratch holds fewer than witness_derive_scratch_elems elements");
+	DeviceBumpAllocator alloc(scratch);
+	WitnessOutput out;
+	out.columns.resize(cols.size());
+	FSliceMut d_one;
+	if (std::any_of(sh.begin(), sh.end(), [](const WitnessShape &s) { return s.route == WitnessRoute::Lincomb; })) {
+		d_one = alloc.alloc(1);
+		hal.fill(d_one, B128::ONE());
+	}
+	for (size_t i = 0; i < cols.size(); i++) {
+		WitnessResolved &r = out.columns[i];
+		r.tower_level = sh[i].tower_level;
+		r.n_vars = sh[i].n_vars;
+		r.wave = sh[i].wave;
+		out.n_waves = std::max(out.n_waves, r.wave);
+		if (cols[i].kind == WitnessColumn::Given)
+			r.ptr = cols[i].d_evals;
+		else if (cols[i].kind == WitnessColumn::Packed)
+			r.ptr = out.columns[cols[i].inner].ptr; // (inner < i: resolved, and a derived inner already has its place in scratch)
+		else
+			r.ptr = alloc.alloc(witness_column_elems(r.n_vars, r.tower_level)).ptr;
+	}
+	for (uint32_t wave = 1; wave <= out.n_waves; wave++) {
+		std::vector<bn_derive_job> jobs;
+		std::vector<const void *> terms;
+		std::vector<bn_pel_job> pel_jobs;
+		std::vector<bn_pel_term> pel_terms;
+		std::vector<void *> pel_outs;
+		std::vector<size_t> on_host;
+		for (size_t i = 0; i < cols.size(); i++) {
+			if (sh[i].wave != wave || sh[i].route == WitnessRoute::None) continue;
+			const WitnessColumn &c = cols[i];
+			if (sh[i].route == WitnessRoute::Host) {
+				on_host.push_back(i);
+				continue;
+			}
+			if (sh[i].route == WitnessRoute::Lincomb) {
+				pel_jobs.push_back(bn_pel_job{sh[i].n_vars, (uint32_t)pel_terms.size(), (uint32_t)c.terms.size(), 0, c.offset.raw()});
+				for (size_t t = 0; t < c.terms.size(); t++)
+					pel_terms.push_back(bn_pel_term{out.columns[c.terms[t]].ptr, sh[c.terms[t]].tower_level, 0, c.coefficients[t].raw()});
+				pel_outs.push_back(const_cast<void *>(out.columns[i].ptr));
+				continue;
+			}
+			bn_derive_job jb{};
+			jb.tower_level = sh[i].tower_level;
+			jb.n_vars = sh[i].n_vars;
+			jb.d_out = const_cast<void *>(out.columns[i].ptr);
+			if (c.kind != WitnessColumn::LinearCombination) {
+				jb.d_inner = out.columns[c.inner].ptr;
+				jb.inner_n_vars = sh[c.inner].n_vars;
+			}
+			switch (c.kind) {
+			case WitnessColumn::Shifted:
+				jb.kind = BN_DERIVE_SHIFTED;
+				jb.block_size = c.block_size;
+				jb.shift_variant = c.shift_variant;
+				jb.shift_offset = c.shift_offset;
+				break;
+			case WitnessColumn::Repeating:
+				jb.kind = BN_DERIVE_REPEATING;
+				break;
+			case WitnessColumn::ZeroPadded:
+				jb.kind = BN_DERIVE_ZERO_PADDED;
+				jb.start_index = c.start_index;
+				jb.nonzero_index = c.nonzero_index;
+				break;
+			default:
+				jb.kind = BN_DERIVE_XOR_COMBINATION;
+				jb.first_term = (uint32_t)terms.size();
+				jb.n_terms = (uint32_t)c.terms.size();
+				jb.offset = c.offset.raw();
+				for (const uint32_t t : c.terms) terms.push_back(out.columns[t].ptr);
+				break;
+			}
+			jobs.push_back(jb);
+		}
+		if (!jobs.empty()) {
+			check(bn_derive_columns_batch(hal.raw_ctx(), jobs.data(), (uint32_t)jobs.size(), terms.data(), (uint32_t)terms.size()));
+			out.n_launches++;
+		}
+		if (!pel_jobs.empty()) {
+			check(bn_partial_eval_high_lincomb_batch(hal.raw_ctx(), pel_jobs.data(), (uint32_t)pel_jobs.size(), pel_terms.data(), (uint32_t)pel_terms.size(), d_one.ptr, 0,
+			                                         pel_outs.data()));
+			out.n_launches++;
+		}
+		for (const size_t i : on_host) {
+			const WitnessColumn &c = cols[i];
+			std::vector<uint32_t> ids = c.kind == WitnessColumn::LinearCombination ? c.terms : std::vector<uint32_t>{c.inner};
+			std::vector<B128> inners(ids.size()), one(1);
+			for (size_t t = 0; t < ids.size(); t++) {
+				hal.copy_d2h(FSlice{out.columns[ids[t]].ptr, 1}, one);
+				inners[t] = one[0];
+			}
+			one[0] = witness_small_column(c, sh[i], sh, inners);
+			FSliceMut dst{const_cast<void *>(out.columns[i].ptr), 1};
+			hal.copy_h2d(one, dst);
+		}
+	}
+	return out;
+}
+
+} // namespace binius_amd

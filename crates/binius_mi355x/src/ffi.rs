@@ -192,6 +192,35 @@ pub struct bn_pel_job {
 	pub offset: bn_f128,
 }
 
+/// One virtual column of bn_derive_columns_batch (Shifted, Repeating, ZeroPadded, or a LinearCombination with unit coefficients).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bn_derive_job {
+	pub kind: u32,
+	pub tower_level: u32,
+	pub n_vars: u32,
+	pub inner_n_vars: u32,
+	pub d_inner: *const c_void,
+	pub d_out: *mut c_void,
+	pub block_size: u32,
+	pub shift_variant: u32,
+	pub shift_offset: u64,
+	pub start_index: u32,
+	pub reserved: u32,
+	pub nonzero_index: u64,
+	pub first_term: u32,
+	pub n_terms: u32,
+	pub offset: bn_f128,
+}
+pub const BN_DERIVE_SHIFTED: u32 = 0;
+pub const BN_DERIVE_REPEATING: u32 = 1;
+pub const BN_DERIVE_ZERO_PADDED: u32 = 2;
+pub const BN_DERIVE_XOR_COMBINATION: u32 = 3;
+pub const BN_SHIFT_CIRCULAR_LEFT: u32 = 0;
+pub const BN_SHIFT_LOGICAL_LEFT: u32 = 1;
+pub const BN_SHIFT_LOGICAL_RIGHT: u32 = 2;
+pub const BN_DERIVE_N: usize = 3;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct bn_rs_job {
@@ -443,6 +472,14 @@ unsafe extern "C" {
 		log_repeats: u32,
 	) -> c_int;
 	pub fn bn_merge_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_derive_columns_batch(
+		ctx: *mut bn_ctx,
+		jobs: *const c_void,
+		n_jobs: u32,
+		d_terms: *const *const c_void,
+		n_terms_total: u32,
+	) -> c_int;
+	pub fn bn_derive_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 	pub fn bn_fri_query_proof_elems(
 		oracles: *const c_void,
 		n_oracles: u32,

@@ -146,6 +146,17 @@ impl Mi355xLayer {
 		})
 	}
 
+	/// The virtual columns of a constraint system built on the device in one launch (`bn_derive_columns_batch`): Shifted, Repeating,
+	/// ZeroPadded and unit-coefficient LinearCombination oracles (core/src/oracle/multilinear.rs), value by value as
+	/// constraint_system/validate.rs:151-279 defines them.  `jobs` name device pointers; `terms` is the pointer list that the XOR
+	/// combinations' `first_term .. first_term + n_terms` ranges index.  An output overlaps no inner column or term of any job.
+	///
+	/// # Safety
+	/// Every pointer in `jobs` and `terms` is device memory of the size the job's level and `n_vars` imply.
+	pub unsafe fn derive_columns_batch(&self, jobs: &[ffi::bn_derive_job], terms: &[*const std::os::raw::c_void]) -> Result<(), Error> {
+		check(ffi::bn_derive_columns_batch(self.ctx, jobs.as_ptr().cast(), jobs.len() as u32, terms.as_ptr(), terms.len() as u32))
+	}
+
 	/// NUMA node of the host that `device` hangs off, if the platform says.  The thread that drives a context should run
 	/// there: a small sumcheck round is a host -> device -> host round trip through pinned memory, and from the other
 	/// socket of a 2-socket host every one of them also crosses the socket interconnect.  The

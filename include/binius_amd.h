@@ -404,6 +404,69 @@ int bn_merge_multilins(bn_ctx *ctx, uint32_t n, const uint32_t *n_vars, const vo
  * nowhere. */
 enum { BN_MERGE_CALLS = 0, BN_MERGE_LAUNCHES = 1, BN_MERGE_JOBS = 2, BN_MERGE_JOBS_TILED = 3, BN_MERGE_JOBS_SMALL = 4, BN_MERGE_N = 5 };
 int bn_merge_counters(bn_ctx *ctx, uint64_t *counters /*[BN_MERGE_N]*/);
+/* The virtual columns of a constraint system that are pure functions of columns already on the device, built there at their own
+ * tower level: MultilinearPolyVariant::{Shifted, Repeating, ZeroPadded} and a LinearCombination whose coefficients are all ONE
+ * (core/src/oracle/multilinear.rs), value by value as validate_witness defines them (core/src/constraint_system/validate.rs:151-279;
+ * zero_pad: math/src/fold.rs:27-77).  u32_add's cin = cout << 1, keccak's rotations and c[x] sums and every repeated constant are of
+ * these forms; a caller no longer fills them on the host and uploads them.
+ * Job j (jobs[j], a HOST array of bn_derive_job) writes the column d_out of 2^n_vars values at tower_level (0 or 3 .. 7), n_vars <=
+ * BN_PE_MAX_VARS, packed as bn_hal_multilinear says, at least one element (n_vars + tower_level >= 7): exactly 2^(n_vars + tower_level - 7)
+ * elements are overwritten.  Indices below are value indices.
+ *   BN_DERIVE_SHIFTED          d_inner has the output's level and n_vars.  block_size <= n_vars, 1 <= shift_offset < 2^block_size
+ *                              (Shifted::new, multilinear.rs:805-816).  Inside every aligned block of B = 2^block_size values, with
+ *                              s = shift_offset and o the index inside the block (validate.rs:177-238):
+ *                                BN_SHIFT_CIRCULAR_LEFT   out[o] = in[(o + B - s) mod B]
+ *                                BN_SHIFT_LOGICAL_LEFT    out[o] = in[o - s] for o >= s, else 0
+ *                                BN_SHIFT_LOGICAL_RIGHT   out[o] = in[o + s] for o < B - s, else 0
+ *   BN_DERIVE_REPEATING        d_inner has the output's level and inner_n_vars <= n_vars variables (it may be less than one element:
+ *                              the low bits of one 16-byte element).  out[i] = in[i mod 2^inner_n_vars]  (validate.rs:167-176)
+ *   BN_DERIVE_ZERO_PADDED      d_inner has the output's level and inner_n_vars <= n_vars variables, n_pad_vars = n_vars - inner_n_vars,
+ *                              start_index <= inner_n_vars, nonzero_index < 2^n_pad_vars (the strict bound of
+ *                              MultilinearExtension::zero_pad, not the `>` of ZeroPadded::new).  With col = i mod 2^(start_index +
+ *                              n_pad_vars), row = i div 2^(start_index + n_pad_vars) and z = nonzero_index 2^start_index:
+ *                              out[i] = in[row 2^start_index + col - z] for z <= col < z + 2^start_index, else 0  (fold.rs:52-75)
+ *   BN_DERIVE_XOR_COMBINATION  out[i] = offset + sum of d_terms[first_term + t][i], t < n_terms <= BN_PEL_MAX_TERMS: the terms are
+ *                              columns of the output's own level and n_vars from the call's term list (a HOST array of n_terms_total
+ *                              device pointers), the offset a value of the output's level (below 2^(2^tower_level)).  A column may
+ *                              appear in several jobs and more than once in one (twice cancels); n_terms = 0 is the constant column.
+ * Fields a kind does not use are ignored; reserved is 0.  Everything is bit-exact; inner columns and terms are only read; pointers are
+ * 16-byte aligned.  An output overlaps no inner column or term of ANY job of the call and no other output: a call holds no dependency
+ * between its jobs (a column derived from a derived column goes into the next call).  Like every op it first brings up to date what it
+ * reads; the outputs are complete when the call returns.  n_jobs = 0 is a no-op that counts nowhere.
+ * ONE launch per call whatever the number, kinds, sizes and levels of the jobs: a streaming kernel over a job table, a workgroup
+ * 4096 contiguous output elements of one job (1024 at a time), in bit coordinates (a value is 2^tower_level bits) so that one code
+ * path serves every level (kernels_derive.hip).
+ * BN_ERR_INPUT_VALIDATION with nothing launched and no counter moved: an unknown kind or shift variant, tower level 1 or 2 or above 7,
+ * a null or misaligned pointer, a forbidden overlap, an output below one element, n_vars above BN_PE_MAX_VARS, reserved != 0, a job's
+ * terms outside the term list, an offset outside the level's field and every bound stated above.
+ * NOT taken here: any other LinearCombination (a B128 one with arbitrary coefficients is bn_partial_eval_high_lincomb_batch at
+ * query_vars = 0), Projected (bn_partial_eval_high_batch / bn_fold_right), Composite (bn_compute_composite), Packed (the same bytes: an
+ * alias), transparent and structured polynomials. */
+enum { BN_DERIVE_SHIFTED = 0, BN_DERIVE_REPEATING = 1, BN_DERIVE_ZERO_PADDED = 2, BN_DERIVE_XOR_COMBINATION = 3 };
+enum { BN_SHIFT_CIRCULAR_LEFT = 0, BN_SHIFT_LOGICAL_LEFT = 1, BN_SHIFT_LOGICAL_RIGHT = 2 }; /* ShiftVariant, multilinear.rs */
+typedef struct {
+	uint32_t kind;
+	uint32_t tower_level;
+	uint32_t n_vars;
+	uint32_t inner_n_vars;
+	const void *d_inner;
+	void *d_out;
+	uint32_t block_size;
+	uint32_t shift_variant;
+	uint64_t shift_offset;
+	uint32_t start_index;
+	uint32_t reserved;
+	uint64_t nonzero_index;
+	uint32_t first_term;
+	uint32_t n_terms;
+	bn_f128 offset;
+} bn_derive_job;
+/* (jobs points to n_jobs bn_derive_job; untyped in the prototype for the same reason as bn_partial_eval_high_batch's cols.) */
+int bn_derive_columns_batch(bn_ctx *ctx, const void *jobs, uint32_t n_jobs, const void *const *d_terms, uint32_t n_terms_total);
+/* Read-only, per context (not part of the reference interface): accepted bn_derive_columns_batch calls, the kernel launches they made,
+ * the jobs they served.  A rejected call counts nowhere. */
+enum { BN_DERIVE_CALLS = 0, BN_DERIVE_LAUNCHES = 1, BN_DERIVE_JOBS = 2, BN_DERIVE_N = 3 };
+int bn_derive_counters(bn_ctx *ctx, uint64_t *counters /*[BN_DERIVE_N]*/);
 /* The FRI query phase: everything FRIFolder::finish_proof (crates/core/src/protocols/fri/prove.rs:483-507) writes to the
  * decommitment, from codewords and Merkle trees resident on the device.  The indices are the caller's, as every challenge is: the
  * decommitment is not observed by the challenger (transcript/mod.rs:182-195), so all of them can be sampled before any opening is made.

@@ -565,6 +565,40 @@ int bnh_piop_prove_committed_open_live(bn_ctx *ctx, uint32_t n_committed, const 
                                        uint64_t max_scalars, uint64_t *n_scalars_out, uint8_t *digests_out, uint32_t max_digests, uint32_t *n_digests_out,
                                        double *phase_ms_out, bn_f128 *advice_out, uint64_t max_advice_elems, uint64_t *n_advice_elems_out);
 
+/* The virtual columns of a constraint system derived on the device (binius_amd/host/witness.hpp): the witness-side reading of a
+ * MultilinearOracleSet (core/src/oracle/multilinear.rs).  The n_columns columns come in oracle-id order; column i is
+ * col_desc[4 i .. 4 i + 4) = (kind, a, b, c), with col_args[i] and lc_offsets[i] (both [n_columns]; 0 where unused):
+ *   BNH_WIT_GIVEN        a = tower level, b = n_vars; d_given[i] = the column on the device (d_given[i] of other kinds is not read)
+ *   BNH_WIT_SHIFTED      a = inner, b = block_size, c = BN_SHIFT_* variant, col_args[i] = shift_offset        (add_shifted)
+ *   BNH_WIT_REPEATING    a = inner, b = log_count                                                             (add_repeating)
+ *   BNH_WIT_ZERO_PADDED  a = inner, b = n_pad_vars, c = start_index, col_args[i] = nonzero_index              (add_zero_padded)
+ *   BNH_WIT_PACKED       a = inner, b = log_degree                                                            (add_packed)
+ *   BNH_WIT_LINCOMB      a = first term, b = number of terms (<= BN_PEL_MAX_TERMS) in lc_terms / lc_coeffs [n_lc_terms], c = n_vars,
+ *                        lc_offsets[i] = the offset                                       (add_linear_combination_with_offset)
+ * An inner index (and a term) is smaller than the column's own index, as OracleIds are.  Levels follow multilinear.rs:91-266: shifted,
+ * repeating and padded columns keep the inner's; packed is inner + log_degree with n_vars - log_degree; a combination has the maximum of
+ * its terms' levels and the minimal levels of its coefficients and offset.  How the plan runs:
+ *   - Packed is an alias: the inner's pointer, no launch.
+ *   - A column's wave is one more than its deepest inner (given: 0; an alias adds nothing).  ONE bn_derive_columns_batch per wave
+ *     serves its shifted, repeating and padded columns and the combinations in XOR form (all coefficients ONE, every term at the
+ *     combination's level).
+ *   - The B128 combinations outside the XOR form share, per wave, ONE bn_partial_eval_high_lincomb_batch at query_vars = 0, its
+ *     one-element query ONE in scratch.
+ *   - A combination that is neither is BN_ERR_INPUT_VALIDATION.  Projected (bn_partial_eval_high_batch / bn_fold_right are the ops for
+ *     it), Composite (bn_compute_composite) and transparent or structured polynomials are NOT taken: list them as given columns.
+ *   - Columns of less than one 16-byte element are host work (one element read, one written) and make no launch.
+ * d_columns_out / tower_levels_out / n_vars_out [n_columns]: every column's pointer (a given column's own, an alias's inner's, a derived
+ * column's place in d_scratch), level and n_vars; *n_waves_out: the largest wave; *n_launches_out: the op calls made (either may be null).
+ * bnh_witness_derive_scratch_elems is exact: every derived column at its packed size (one element below 2^7 bits), plus one element
+ * when a combination goes to the lincomb op; 0 for a plan that bnh_witness_derive would reject.  Everything is checked before the first
+ * device call. */
+enum { BNH_WIT_GIVEN = 0, BNH_WIT_SHIFTED = 1, BNH_WIT_REPEATING = 2, BNH_WIT_ZERO_PADDED = 3, BNH_WIT_PACKED = 4, BNH_WIT_LINCOMB = 5 };
+uint64_t bnh_witness_derive_scratch_elems(uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const uint32_t *lc_terms, const bn_f128 *lc_coeffs,
+                                          uint32_t n_lc_terms, const bn_f128 *lc_offsets);
+int bnh_witness_derive(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
+                       const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
+                       uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out);
+
 /* An array-backed transcript, for C callers, benchmarks and tests: it serves samples[n_samples] to `sample` and
  * bit_samples[n_bit_samples] (masked to `bits`) to `sample_bits`, in order, returns non-zero when they run out, and records every
  * write.  Pure host code, no context.
