@@ -93,6 +93,18 @@ DERIVE_SHIFTED, DERIVE_REPEATING, DERIVE_ZERO_PADDED, DERIVE_XOR_COMBINATION = r
 SHIFT_CIRCULAR_LEFT, SHIFT_LOGICAL_LEFT, SHIFT_LOGICAL_RIGHT = range(3)  # BN_SHIFT_* (ShiftVariant)
 
 
+class GenerateJob(C.Structure):
+    """bn_generate_job: one generated column of bn_generate_columns_batch."""
+
+    _fields_ = [("kind", C.c_uint32), ("tower_level", C.c_uint32), ("n_vars", C.c_uint32), ("start_index", C.c_uint32), ("d_inner", C.c_void_p),
+                ("d_out", C.c_void_p), ("query_size", C.c_uint32), ("reserved", C.c_uint32), ("query_bits", C.c_uint64), ("index", C.c_uint64), ("value", F128)]
+
+
+GEN_PROJECTED_BITS, GEN_CONSTANT, GEN_STEP_DOWN, GEN_STEP_UP, GEN_SELECT_ROW, GEN_INCREMENTING, GEN_POWERS = range(7)  # BN_GEN_*
+GEN_KINDS = {"projected_bits": GEN_PROJECTED_BITS, "constant": GEN_CONSTANT, "step_down": GEN_STEP_DOWN, "step_up": GEN_STEP_UP, "select_row": GEN_SELECT_ROW,
+             "incrementing": GEN_INCREMENTING, "powers": GEN_POWERS}
+
+
 class RsJob(C.Structure):
     """bn_rs_job: one equality indicator of bn_ring_switch_eq_ind_batch."""
 
@@ -230,6 +242,8 @@ def lib():
         "bn_merge_counters": [vp, C.POINTER(u64)],
         "bn_derive_columns_batch": [vp, vp, u32, C.POINTER(vp), u32],
         "bn_derive_counters": [vp, C.POINTER(u64)],
+        "bn_generate_columns_batch": [vp, vp, u32],
+        "bn_generate_counters": [vp, C.POINTER(u64)],
         "bn_fri_query_proof_elems": [vp, u32, u64, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
         "bn_fri_query_openings": [vp, vp, u32, vp, u64, C.POINTER(u64), u64, u32, vp, u64],
         "bn_fri_query_counters": [vp, C.POINTER(u64)],
@@ -292,7 +306,7 @@ ABI_SYMBOLS = [
     "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
     "bn_univariate_fold_batch", "bn_univariate_fold_counters", "bn_ring_switch_eq_ind_batch", "bn_ring_switch_counters",
     "bn_mle_evaluate_batch", "bn_mle_evaluate_counters", "bn_partial_eval_high_lincomb_batch", "bn_partial_eval_lincomb_counters",
-    "bn_merge_multilins", "bn_merge_counters", "bn_derive_columns_batch", "bn_derive_counters", "bn_fri_query_proof_elems", "bn_fri_query_openings", "bn_fri_query_counters",
+    "bn_merge_multilins", "bn_merge_counters", "bn_derive_columns_batch", "bn_derive_counters", "bn_generate_columns_batch", "bn_generate_counters", "bn_fri_query_proof_elems", "bn_fri_query_openings", "bn_fri_query_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -1155,6 +1169,38 @@ class Context:
         calls count nowhere."""
         c = (C.c_uint64 * 3)()
         _check(lib().bn_derive_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2])}
+
+    @staticmethod
+    def generate_job_table(jobs):
+        """The arguments of bn_generate_columns_batch, marshalled once: (GenerateJob array, n_jobs) for generate_columns_raw.  jobs: dicts
+        with kind ("projected_bits", "constant", "step_down", "step_up", "select_row", "incrementing", "powers"), level, n_vars, out (a
+        DevSlice of 2^(n_vars + level - 7) elements) and, by kind: inner (DevSlice), start_index, query_size, query_bits; value (an int of
+        the level: a constant's value, a power's base); index."""
+        table = []
+        for jb in jobs:
+            out, inner = jb.get("out"), jb.get("inner")
+            if out is not None and jb["n_vars"] <= 40 and jb["level"] <= 7 and jb["n_vars"] + jb["level"] >= 7 and out.len != 1 << (jb["n_vars"] + jb["level"] - 7):
+                raise BnError(BN_ERR_INPUT_VALIDATION, "input validation: output has the wrong number of elements")
+            table.append(GenerateJob(GEN_KINDS.get(jb["kind"], jb["kind"]), jb["level"], jb["n_vars"], jb.get("start_index", 0), inner.ptr if inner is not None else None,
+                                     out.ptr if out is not None else None, jb.get("query_size", 0), jb.get("reserved", 0), jb.get("query_bits", 0), jb.get("index", 0),
+                                     to_f128(jb.get("value", 0))))
+        return (GenerateJob * max(1, len(table)))(*table), len(table)
+
+    def generate_columns_batch(self, jobs):
+        """The projected-bit, transparent and incrementing columns of a constraint system written on the device in one launch
+        (bn_generate_columns_batch).  jobs: as generate_job_table takes them."""
+        self.generate_columns_raw(*self.generate_job_table(jobs))
+
+    def generate_columns_raw(self, jobs, n_jobs):
+        """bn_generate_columns_batch on a caller-built GenerateJob array, nothing checked here."""
+        _check(lib().bn_generate_columns_batch(self._h, C.cast(jobs, C.c_void_p) if jobs is not None else None, n_jobs))
+
+    def generate_counters(self):
+        """bn_generate_counters: accepted bn_generate_columns_batch calls, the kernel launches they made, the jobs they served.  Rejected
+        calls count nowhere."""
+        c = (C.c_uint64 * 3)()
+        _check(lib().bn_generate_counters(self._h, c))
         return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2])}
 
     def fri_query_openings(self, oracles, terminate, indices, index_bits, out_elems=None):

@@ -364,6 +364,10 @@ def _plain_host_lib():
         L.bnh_witness_derive_scratch_elems.argtypes = [C.c_uint32, U32P, U64P, U32P, FP, C.c_uint32, FP]
         L.bnh_witness_derive.restype = C.c_int
         L.bnh_witness_derive.argtypes = [C.c_void_p, C.c_uint32, U32P, U64P, VPP, U32P, FP, C.c_uint32, FP, C.c_void_p, C.c_uint64, VPP, U32P, U32P, U32P, U32P]
+        L.bnh_witness_build_scratch_elems.restype = C.c_uint64
+        L.bnh_witness_build_scratch_elems.argtypes = L.bnh_witness_derive_scratch_elems.argtypes
+        L.bnh_witness_build.restype = C.c_int
+        L.bnh_witness_build.argtypes = L.bnh_witness_derive.argtypes
         # the _live forms: the array form's arguments without the samples, the transcript's table where LIVE_FORMS says
         for name, (live, drop, at, _splice) in LIVE_FORMS.items():
             if name == "bnh_evalcheck_bivariate_prove":
@@ -1663,6 +1667,77 @@ class WitnessPlan:
         rc = host_lib().bnh_witness_derive(self.hal._h, self.n, self.desc, self.args, self.given, self.terms, self.coeffs, self.n_terms, self.offsets,
                                            self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0,
                                            self.ptrs, self.levels, self.n_vars, C.byref(self._waves), C.byref(self._launches))
+        if rc != 0:
+            raise BnError(rc, host_lib().bnh_last_error().decode())
+        return [(DevSlice(self.ptrs[i], max(1, (1 << (self.n_vars[i] + self.levels[i])) >> 7)), int(self.levels[i]), int(self.n_vars[i])) for i in range(self.n)]
+
+    @property
+    def n_waves(self):
+        return int(self._waves.value)
+
+    @property
+    def n_launches(self):
+        return int(self._launches.value)
+
+
+class WitnessBuild:
+    """WitnessPlan with the columns that a few integers, one field element or a 0/1 projection determine generated on the device as
+    well (bnh_witness_build = witness_build of binius_amd/host/witness.hpp, over bn_generate_columns_batch).  columns: WitnessPlan's, and
+      ("projected_bits", inner, start_index, query_size, query_bits)   add_projected / add_selected at query values ZERO / ONE
+      ("constant", tower_level, n_vars, value)
+      ("step_down", n_vars, index) / ("step_up", n_vars, index) / ("select_row", n_vars, index)     B1 columns
+      ("incrementing", tower_level, n_vars)
+      ("powers", tower_level, n_vars, base)
+    A generated column without an inner is wave 0; every wave with generated columns makes one more launch.  run(), n_waves and
+    n_launches as WitnessPlan's."""
+
+    KINDS = dict(WitnessPlan.KINDS, projected_bits=6, constant=7, step_down=8, step_up=9, select_row=10, incrementing=11, powers=12)
+    VARIANTS = WitnessPlan.VARIANTS
+    _SCRATCH, _RUN = "bnh_witness_build_scratch_elems", "bnh_witness_build"
+
+    @classmethod
+    def _marshal(cls, columns):
+        """WitnessPlan's marshalling of the kinds 0 .. 5 (their rows are taken from it), the further kinds encoded here."""
+        old = [c if cls.KINDS.get(c[0], c[0]) <= 5 else ("packed", 0, 0) for c in columns]
+        n, desc, args, given, terms, coeffs, n_terms, offsets = WitnessPlan._marshal(old)
+        for i, c in enumerate(columns):
+            kind = cls.KINDS.get(c[0], c[0])
+            if kind <= 5:
+                continue
+            d, arg, value = [0, 0, 0], 0, 0
+            if kind == 6:
+                d, arg = [c[1], c[2], c[3]], c[4]
+            elif kind == 7:
+                d, value = [c[1], c[2], 0], c[3]
+            elif kind in (8, 9, 10):
+                d, arg = [0, c[1], 0], c[2]
+            elif kind == 11:
+                d = [c[1], c[2], 0]
+            elif kind == 12:
+                d, value = [c[1], c[2], 0], c[3]
+            desc[4 * i : 4 * i + 4] = [kind] + [int(x) for x in d]
+            args[i] = int(arg)
+            offsets[i].lo, offsets[i].hi = int(value) & ((1 << 64) - 1), int(value) >> 64
+        return n, desc, args, given, terms, coeffs, n_terms, offsets
+
+    @classmethod
+    def scratch_elems(cls, columns):
+        n, desc, args, _given, terms, coeffs, n_terms, offsets = cls._marshal(columns)
+        return int(getattr(host_lib(), cls._SCRATCH)(n, desc, args, terms, coeffs, n_terms, offsets))
+
+    def __init__(self, hal, columns, scratch):
+        self.hal, self.scratch, self._keep = hal, scratch, columns
+        self.n, self.desc, self.args, self.given, self.terms, self.coeffs, self.n_terms, self.offsets = self._marshal(columns)
+        self.ptrs = (C.c_void_p * max(1, self.n))()
+        self.levels, self.n_vars = (C.c_uint32 * max(1, self.n))(), (C.c_uint32 * max(1, self.n))()
+        self._waves, self._launches = C.c_uint32(0), C.c_uint32(0)
+
+    def run(self):
+        from ._ffi import DevSlice
+
+        rc = getattr(host_lib(), self._RUN)(self.hal._h, self.n, self.desc, self.args, self.given, self.terms, self.coeffs, self.n_terms, self.offsets,
+                                            self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0,
+                                            self.ptrs, self.levels, self.n_vars, C.byref(self._waves), C.byref(self._launches))
         if rc != 0:
             raise BnError(rc, host_lib().bnh_last_error().decode())
         return [(DevSlice(self.ptrs[i], max(1, (1 << (self.n_vars[i] + self.levels[i])) >> 7)), int(self.levels[i]), int(self.n_vars[i])) for i in range(self.n)]

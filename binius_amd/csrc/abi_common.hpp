@@ -1,7 +1,7 @@
 // binius_amd/csrc/abi_common.hpp -- pieces shared by the translation units of the extern "C" boundary
 // (abi.cpp: context, copies, deferral; abi_kernels.cpp: the recorded-kernel dispatcher; abi_ops.cpp: the
 // executor ops, Merkle and NTT entry points; the batched ops -- abi_prodtree.cpp, abi_expcircuit.cpp, abi_partial_eval.cpp,
-// abi_flush.cpp, abi_univariate_fold.cpp, abi_ring_switch.cpp, abi_mle_eval.cpp, abi_univariate.cpp, abi_partial_eval_lincomb.cpp, abi_merge.cpp, abi_fri_query.cpp, abi_derive.cpp -- use the helpers and call_upload at the end).  Not part of the
+// abi_flush.cpp, abi_univariate_fold.cpp, abi_ring_switch.cpp, abi_mle_eval.cpp, abi_univariate.cpp, abi_partial_eval_lincomb.cpp, abi_merge.cpp, abi_fri_query.cpp, abi_derive.cpp, abi_generate.cpp -- use the helpers and call_upload at the end).  Not part of the
 // public interface.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -88,6 +88,7 @@ struct bn_ctx {
 	uint64_t mg_calls = 0, mg_launches = 0, mg_jobs = 0, mg_jobs_tiled = 0, mg_jobs_small = 0; // bn_merge_multilins (bn_merge_counters)
 	uint64_t fq_calls = 0, fq_launches = 0, fq_openings = 0; // bn_fri_query_openings (bn_fri_query_counters)
 	uint64_t dv_calls = 0, dv_launches = 0, dv_jobs = 0; // bn_derive_columns_batch (bn_derive_counters)
+	uint64_t gn_calls = 0, gn_launches = 0, gn_jobs = 0; // bn_generate_columns_batch (bn_generate_counters)
 	bn::f128 *h_me_rets = nullptr, *d_me_rets = nullptr; // pinned: the results of a bn_mle_evaluate_batch call, BN_ME_MAX_JOBS values (the sequence word stays in h_mail[64])
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1017,6 +1018,43 @@ struct derive_job {
 constexpr uint32_t kDeriveUnitElems = BN_DERIVE_UNIT_ELEMS;
 static_assert(kDeriveUnitElems % 1024 == 0 && kDeriveUnitElems > 0, "a unit is whole chunks of 1024 elements");
 hipError_t launch_derive_columns(hipStream_t s, const derive_job *d_jobs, uint32_t n_jobs, const void *const *d_terms, uint32_t total_units);
+
+// ---- kernels_generate.hip: the columns of a constraint system that are determined by a few integers, one field element or a 0/1
+// projection of a column on the device (Projected at a hypercube vertex: math/src/multilinear_extension.rs:193-237; Constant, StepDown,
+// StepUp, SelectRow, Powers: core/src/transparent/; the incrementing column: m3/src/builder/structured.rs:64-81), written at their own
+// tower level.  As in kernels_derive.hip a job is one output column in one FORM with its parameters in BIT coordinates, a unit (one
+// workgroup) unit_elems contiguous 16-byte outputs of one job.  The meaning of p0 .. p3 / m0, m1 per form:
+//   kGnProjElem    runs of 2^p0 elements at a stride of 2^p1: out[j] = in[m0 + (j & (2^p0 - 1)) + (j >> p0 << p1)]
+//   kGnProjField   runs of 2^p0 (< 128) bits at a stride of 2^p1 elements: piece k < 2^(7 - p0) of out[j] is the 2^p0 bits at bit p2 of
+//                  in[m0 + ((j 2^(7 - p0) + k) << p1)]
+//   kGnProjSpread  runs of 2^p0 bits at a stride of 2^p1 <= 64 bits, p2 = log2 of the stride-per-run ratio (query_size), p3 = the bit
+//                  of a stride where its run starts: piece k < 2^p2 of out[j] is the 128 >> p2 bits that the runs of in[(j << p2) + k]
+//                  make when they are pushed together
+//   kGnConst       out[j] = (m0, m1)
+//   kGnStep        bit b of the column is (b < m0) ^ (m1 & 1)            (m1 = 0: step down; all ones: step up)
+//   kGnSelect      bit b of the column is b == m0
+//   kGnIncrement   values of p0 <= 64 bits: 64-bit word W of the column is its first value index W (64 / p0) repeated every p0 bits, or m0
+//                  (the offsets 0, 1, ... of the values of a word, at their places); p0 = 128: out[j] = (j, 0)
+//   kGnPowers      values of 2^p0 bits, p0 = 3 .. 7: value i is the product of the entries b of the call's power table (64 entries per
+//                  job from `table`: base^(2^b)) over the set bits b of i
+enum : uint32_t { kGnProjElem = 0, kGnProjField = 1, kGnProjSpread = 2, kGnConst = 3, kGnStep = 4, kGnSelect = 5, kGnIncrement = 6, kGnPowers = 7 };
+struct generate_job {
+	const void *in; // the inner column of a projection (other forms: unused)
+	uint4 *out;
+	uint64_t out_elems;
+	uint64_t m0, m1;
+	uint32_t p0, p1, p2, p3;
+	uint32_t form;
+	uint32_t table; // kGnPowers: first entry of the job in the power table
+	uint32_t start; // first unit of this job in the launch
+	uint32_t unit_elems; // 16-byte outputs of a unit of this job: a multiple of 1024
+};
+// 16-byte outputs of a unit, taken 1024 at a time: the derive op's value (profiles/r22) where an output element costs at most one load;
+// one chunk where it is put together from 2 .. 128 input elements (kGnProjField, kGnProjSpread) or costs field products (kGnPowers),
+// whose jobs would otherwise be a few long-running workgroups
+constexpr uint32_t kGenerateUnitElems = 4096, kGeneratePieceUnitElems = 1024;
+constexpr uint32_t kGeneratePowerEntries = 64; // power table entries of one kGnPowers job
+hipError_t launch_generate_columns(hipStream_t s, const generate_job *d_jobs, uint32_t n_jobs, const f128 *d_powers, uint32_t total_units);
 
 // ---- kernels_ntt_tiled.hip
 hipError_t launch_build_mul8(hipStream_t s, uint8_t *d_tab);

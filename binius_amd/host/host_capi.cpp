@@ -2084,11 +2084,49 @@ std::vector<WitnessColumn> witness_columns(uint32_t n_columns, const uint32_t *c
 			c.n_vars = d[3];
 			c.offset = B128(lc_offsets[i].lo, lc_offsets[i].hi);
 			break;
+		case WitnessColumn::ProjectedBits:
+			c.inner = d[1];
+			c.start_index = d[2];
+			c.query_size = d[3];
+			c.query_bits = col_args[i];
+			break;
+		case WitnessColumn::Constant:
+		case WitnessColumn::StepDown:
+		case WitnessColumn::StepUp:
+		case WitnessColumn::SelectRow:
+		case WitnessColumn::Incrementing:
+		case WitnessColumn::Powers:
+			c.tower_level = d[1];
+			c.n_vars = d[2];
+			c.index = col_args[i];
+			c.value = B128(lc_offsets[i].lo, lc_offsets[i].hi);
+			break;
 		default:
 			break; // (witness_shapes rejects it)
 		}
 	}
 	return cols;
+}
+
+int witness_run(bool generate, bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
+                const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
+                uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out)
+{
+	return guarded([&]() -> int {
+		if (!ctx || (n_columns && (!d_given || !d_columns_out || !tower_levels_out || !n_vars_out)) || (!d_scratch && scratch_elems))
+			throw Error(Error::InputValidation, "null argument");
+		const std::vector<WitnessColumn> cols = witness_columns(n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets);
+		ComputeLayer hal(ctx);
+		const WitnessOutput out = witness_derive(hal, cols, FSliceMut{d_scratch, (size_t)scratch_elems}, generate);
+		for (uint32_t i = 0; i < n_columns; i++) {
+			d_columns_out[i] = const_cast<void *>(out.columns[i].ptr);
+			tower_levels_out[i] = out.columns[i].tower_level;
+			n_vars_out[i] = out.columns[i].n_vars;
+		}
+		if (n_waves_out) *n_waves_out = out.n_waves;
+		if (n_launches_out) *n_launches_out = out.n_launches;
+		return 0;
+	});
 }
 } // namespace
 
@@ -2106,21 +2144,26 @@ int bnh_witness_derive(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc
                        const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
                        uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out)
 {
-	return guarded([&]() -> int {
-		if (!ctx || (n_columns && (!d_given || !d_columns_out || !tower_levels_out || !n_vars_out)) || (!d_scratch && scratch_elems))
-			throw Error(Error::InputValidation, "null argument");
-		const std::vector<WitnessColumn> cols = witness_columns(n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets);
-		ComputeLayer hal(ctx);
-		const WitnessOutput out = witness_derive(hal, cols, FSliceMut{d_scratch, (size_t)scratch_elems});
-		for (uint32_t i = 0; i < n_columns; i++) {
-			d_columns_out[i] = const_cast<void *>(out.columns[i].ptr);
-			tower_levels_out[i] = out.columns[i].tower_level;
-			n_vars_out[i] = out.columns[i].n_vars;
-		}
-		if (n_waves_out) *n_waves_out = out.n_waves;
-		if (n_launches_out) *n_launches_out = out.n_launches;
+	return witness_run(false, ctx, n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets, d_scratch, scratch_elems, d_columns_out, tower_levels_out,
+	                   n_vars_out, n_waves_out, n_launches_out);
+}
+
+uint64_t bnh_witness_build_scratch_elems(uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const uint32_t *lc_terms, const bn_f128 *lc_coeffs,
+                                         uint32_t n_lc_terms, const bn_f128 *lc_offsets)
+{
+	try {
+		return witness_build_scratch_elems(witness_columns(n_columns, col_desc, col_args, nullptr, lc_terms, lc_coeffs, n_lc_terms, lc_offsets));
+	} catch (const Error &) {
 		return 0;
-	});
+	}
+}
+
+int bnh_witness_build(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
+                      const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
+                      uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out)
+{
+	return witness_run(true, ctx, n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets, d_scratch, scratch_elems, d_columns_out, tower_levels_out,
+	                   n_vars_out, n_waves_out, n_launches_out);
 }
 
 } // extern "C"

@@ -12,13 +12,23 @@
 //                      BN_DERIVE_XOR_COMBINATION; otherwise, at level 7, bn_partial_eval_high_lincomb_batch at query_vars = 0 (the
 //                      one-element query ONE sits in scratch); otherwise InputValidation
 //
-// and refers to its inner columns by index, always smaller than its own, as OracleIds are.  NOT taken: Projected
-// (bn_partial_eval_high_batch / bn_fold_right are the ops for it), Composite (bn_compute_composite), transparent and structured
-// polynomials -- the caller derives or uploads those and lists them as Given.
+// and refers to its inner columns by index, always smaller than its own, as OracleIds are.  witness_build takes these and, through
+// bn_generate_columns_batch, the columns that a few integers, one field element or a 0/1 projection determine:
 //
-// Waves: a column's wave is one more than its deepest inner (Given: 0; a Packed alias adds nothing).  ONE bn_derive_columns_batch per
-// wave, plus ONE lincomb call per wave that has a B128 combination outside the XOR form.  Columns of less than one 16-byte element
-// are host work (one element down, one up), as zerocheck.hpp does for its padding; they make no launch.
+//   ProjectedBits      add_projected / add_selected at query values ZERO / ONE: the inner's level, n_vars = inner - query_size
+//                                                                                                  BN_GEN_PROJECTED_BITS
+//   Constant, StepDown, StepUp, SelectRow, Powers   the transparents of core/src/transparent/ that their parameters determine
+//   Incrementing       add_structured(Incrementing)                                                BN_GEN_INCREMENTING
+//
+// witness_derive keeps rejecting them as unknown kinds.  NOT taken by either: Projected at other query values
+// (bn_partial_eval_high_batch / bn_fold_right are the ops for it), Composite (bn_compute_composite), general circuit transparents and
+// StructuredFixedSize, TowerBasis, EqIndPartialEval (bn_tensor_expand), ShiftIndPartialEval, DisjointProduct -- the caller derives or
+// uploads those and lists them as Given.
+//
+// Waves: a column's wave is one more than its deepest inner (Given and a generated column without an inner: 0; a Packed alias adds
+// nothing).  ONE bn_derive_columns_batch per wave, plus ONE lincomb call per wave that has a B128 combination outside the XOR form,
+// plus ONE bn_generate_columns_batch per wave that has generated columns.  Columns of less than one 16-byte element are host work
+// (their inner down, one element up), as zerocheck.hpp does for its padding; they make no launch.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -28,7 +38,11 @@
 namespace binius_amd {
 
 struct WitnessColumn {
-	enum Kind : uint32_t { Given = 0, Shifted = 1, Repeating = 2, ZeroPadded = 3, Packed = 4, LinearCombination = 5 };
+	enum Kind : uint32_t {
+		Given = 0, Shifted = 1, Repeating = 2, ZeroPadded = 3, Packed = 4, LinearCombination = 5,
+		// witness_build only
+		ProjectedBits = 6, Constant = 7, StepDown = 8, StepUp = 9, SelectRow = 10, Incrementing = 11, Powers = 12
+	};
 	uint32_t kind = Given;
 	// Given
 	const void *d_evals = nullptr;
@@ -45,6 +59,10 @@ struct WitnessColumn {
 	std::vector<uint32_t> terms;
 	std::vector<B128> coefficients;
 	B128 offset = B128::ZERO();
+	// ProjectedBits (inner, start_index above) / StepDown, StepUp, SelectRow (tower_level, n_vars above)
+	uint32_t query_size = 0;
+	uint64_t query_bits = 0, index = 0;
+	B128 value = B128::ZERO(); // Constant: the value; Powers: the base
 };
 struct WitnessResolved {
 	const void *ptr = nullptr;
@@ -53,7 +71,7 @@ struct WitnessResolved {
 struct WitnessOutput {
 	std::vector<WitnessResolved> columns;
 	uint32_t n_waves = 0;    // the largest wave of a column
-	uint32_t n_launches = 0; // bn_derive_columns_batch and lincomb calls made
+	uint32_t n_launches = 0; // bn_derive_columns_batch, lincomb and bn_generate_columns_batch calls made
 };
 
 inline size_t witness_column_elems(size_t n_vars, uint32_t level) { return n_vars + level <= 7 ? 1 : (size_t)1 << (n_vars + level - 7); }
@@ -66,22 +84,31 @@ inline uint32_t witness_min_level(B128 c)
 	return level;
 }
 
-// How a column is made: by the derive op, by the lincomb op, on the host, or not at all (Given, Packed)
-enum class WitnessRoute { None, Derive, Lincomb, Host };
+// How a column is made: by the derive op, by the lincomb op, by the generate op, on the host, or not at all (Given, Packed)
+enum class WitnessRoute { None, Derive, Lincomb, Host, Generate };
 struct WitnessShape {
 	uint32_t tower_level = 0, n_vars = 0, wave = 0;
 	WitnessRoute route = WitnessRoute::None;
 };
 
 // Levels, sizes, waves and routes of every column; every rule of the header is checked here, before the first device call.
-inline std::vector<WitnessShape> witness_shapes(const std::vector<WitnessColumn> &cols)
+// generate: witness_build's kinds are taken (otherwise they are unknown kinds).
+inline std::vector<WitnessShape> witness_shapes(const std::vector<WitnessColumn> &cols, bool generate = false)
 {
 	auto bad = [](const char *msg) { return Error(Error::InputValidation, msg); };
 	std::vector<WitnessShape> sh(cols.size());
 	for (size_t i = 0; i < cols.size(); i++) {
 		const WitnessColumn &c = cols[i];
 		WitnessShape &s = sh[i];
-		if (c.kind >= WitnessColumn::Shifted && c.kind <= WitnessColumn::Packed && c.inner >= i) throw bad("witness: an inner index is smaller than the column's own");
+		if (c.kind > WitnessColumn::LinearCombination && !generate) throw bad("witness: unknown column kind");
+		if (((c.kind >= WitnessColumn::Shifted && c.kind <= WitnessColumn::Packed) || c.kind == WitnessColumn::ProjectedBits) && c.inner >= i)
+			throw bad("witness: an inner index is smaller than the column's own");
+		const bool in_level = c.tower_level >= 7 || (c.value.hi == 0 && (c.tower_level == 6 || c.value.lo < ((uint64_t)1 << (1u << c.tower_level))));
+		if (c.kind >= WitnessColumn::Constant && c.kind <= WitnessColumn::Powers) {
+			if (c.tower_level > 7 || c.tower_level == 1 || c.tower_level == 2) throw bad("witness: unsupported tower level");
+			if (c.n_vars > BN_PE_MAX_VARS) throw bad("witness: a column has at most 2^40 values");
+			s = WitnessShape{c.tower_level, c.n_vars, 0, WitnessRoute::Generate};
+		}
 		switch (c.kind) {
 		case WitnessColumn::Given:
 			if (!c.d_evals) throw bad("witness: null given column");
@@ -129,19 +156,44 @@ inline std::vector<WitnessShape> witness_shapes(const std::vector<WitnessColumn>
 				          "structured columns are not taken either: list them as Given)");
 			break;
 		}
+		case WitnessColumn::ProjectedBits:
+			if (c.query_size < 1 || c.query_size > sh[c.inner].n_vars || c.start_index > sh[c.inner].n_vars - c.query_size)
+				throw bad("witness: ProjectedBits needs query_size >= 1 and start_index + query_size <= inner n_vars");
+			if (c.query_bits >= ((uint64_t)1 << c.query_size)) throw bad("witness: query_bits >= 2^query_size");
+			s = WitnessShape{sh[c.inner].tower_level, sh[c.inner].n_vars - c.query_size, sh[c.inner].wave + 1, WitnessRoute::Generate};
+			break;
+		case WitnessColumn::Constant:
+			if (!in_level) throw bad("witness: the value of a Constant is a value of its tower level");
+			break;
+		case WitnessColumn::StepDown:
+		case WitnessColumn::StepUp:
+			if (c.tower_level != 0) throw bad("witness: a step column is a B1 column");
+			if (c.index > ((uint64_t)1 << c.n_vars)) throw bad("witness: a step's index is at most 2^n_vars");
+			break;
+		case WitnessColumn::SelectRow:
+			if (c.tower_level != 0) throw bad("witness: a select-row column is a B1 column");
+			if (c.index >= ((uint64_t)1 << c.n_vars)) throw bad("witness: a selected row is below 2^n_vars");
+			break;
+		case WitnessColumn::Incrementing:
+			if (c.n_vars > (1u << c.tower_level)) throw bad("witness: an incrementing column has n_vars <= 2^tower_level");
+			break;
+		case WitnessColumn::Powers:
+			if (c.tower_level < 3) throw bad("witness: a column of powers has tower level 3 .. 7");
+			if (!in_level) throw bad("witness: the base of Powers is a value of its tower level");
+			break;
 		default:
 			throw bad("witness: unknown column kind");
 		}
 		if (s.n_vars > BN_PE_MAX_VARS) throw bad("witness: a column has at most 2^40 values");
-		if (s.route == WitnessRoute::Derive && s.n_vars + s.tower_level < 7) s.route = WitnessRoute::Host;
+		if ((s.route == WitnessRoute::Derive || s.route == WitnessRoute::Generate) && s.n_vars + s.tower_level < 7) s.route = WitnessRoute::Host;
 	}
 	return sh;
 }
 
 // Exact: one element for the query ONE when a combination goes to the lincomb op, then every derived column at its packed size.
-inline size_t witness_derive_scratch_elems(const std::vector<WitnessColumn> &cols)
+inline size_t witness_derive_scratch_elems(const std::vector<WitnessColumn> &cols, bool generate = false)
 {
-	const std::vector<WitnessShape> sh = witness_shapes(cols);
+	const std::vector<WitnessShape> sh = witness_shapes(cols, generate);
 	size_t total = 0;
 	bool one = false;
 	for (const WitnessShape &s : sh) {
@@ -160,12 +212,44 @@ inline uint64_t get(const B128 &e, uint32_t level, size_t i)
 	const uint64_t word = bit < 64 ? e.lo : e.hi;
 	return w == 64 ? word : (word >> (bit & 63)) & (((uint64_t)1 << w) - 1);
 }
+// value i (2^level <= 64 bits) of a packed column of any number of elements
+inline uint64_t get(const std::vector<B128> &col, uint32_t level, size_t i) { return get(col[(i << level) >> 7], level, i & ((128u >> level) - 1)); }
 inline void put(B128 &e, uint32_t level, size_t i, uint64_t v)
 {
 	const size_t bit = (i << level);
 	(bit < 64 ? e.lo : e.hi) |= v << (bit & 63);
 }
 } // namespace witness_detail
+
+// A generated column of less than one element, value by value (the definitions bn_generate_columns_batch cites); inner: the whole inner
+// column of a projection
+inline B128 witness_small_generated(const WitnessColumn &c, const WitnessShape &s, const std::vector<B128> &inner)
+{
+	const uint32_t l = s.tower_level;
+	const size_t n = (size_t)1 << s.n_vars;
+	B128 out = B128::ZERO(), power = B128::ONE();
+	for (size_t i = 0; i < n; i++) {
+		uint64_t v = 0;
+		switch (c.kind) {
+		case WitnessColumn::ProjectedBits: {
+			const size_t run = (size_t)1 << c.start_index, lo = i & (run - 1), hi = i >> c.start_index;
+			v = witness_detail::get(inner, l, lo + ((size_t)c.query_bits << c.start_index) + (hi << (c.start_index + c.query_size)));
+			break;
+		}
+		case WitnessColumn::Constant: v = c.value.lo; break;
+		case WitnessColumn::StepDown: v = i < c.index; break;
+		case WitnessColumn::StepUp: v = i >= c.index; break;
+		case WitnessColumn::SelectRow: v = i == c.index; break;
+		case WitnessColumn::Incrementing: v = i; break;
+		default: // Powers
+			v = power.lo;
+			power = power * c.value;
+			break;
+		}
+		witness_detail::put(out, l, i, v);
+	}
+	return out;
+}
 
 // A column of less than one element, value by value (validate.rs:151-279, fold.rs:52-75) from its inner columns' single elements
 inline B128 witness_small_column(const WitnessColumn &c, const WitnessShape &s, const std::vector<WitnessShape> &sh, const std::vector<B128> &inners)
@@ -206,10 +290,10 @@ inline B128 witness_small_column(const WitnessColumn &c, const WitnessShape &s, 
 	return out;
 }
 
-inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch)
+inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch, bool generate = false)
 {
-	const std::vector<WitnessShape> sh = witness_shapes(cols);
-	if (scratch.len_ < witness_derive_scratch_elems(cols)) throw Error(Error::InputValidation, "scratch holds fewer than witness_derive_scratch_elems elements");
+	const std::vector<WitnessShape> sh = witness_shapes(cols, generate);
+	if (scratch.len_ < witness_derive_scratch_elems(cols, generate)) throw Error(Error::InputValidation, "scratch holds fewer than witness_derive_scratch_elems elements");
 	DeviceBumpAllocator alloc(scratch);
 	WitnessOutput out;
 	out.columns.resize(cols.size());
@@ -231,8 +315,9 @@ inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<Witness
 		else
 			r.ptr = alloc.alloc(witness_column_elems(r.n_vars, r.tower_level)).ptr;
 	}
-	for (uint32_t wave = 1; wave <= out.n_waves; wave++) {
+	for (uint32_t wave = 0; wave <= out.n_waves; wave++) { // (wave 0 has work only where a generated column has no inner)
 		std::vector<bn_derive_job> jobs;
+		std::vector<bn_generate_job> gen_jobs;
 		std::vector<const void *> terms;
 		std::vector<bn_pel_job> pel_jobs;
 		std::vector<bn_pel_term> pel_terms;
@@ -243,6 +328,24 @@ inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<Witness
 			const WitnessColumn &c = cols[i];
 			if (sh[i].route == WitnessRoute::Host) {
 				on_host.push_back(i);
+				continue;
+			}
+			if (sh[i].route == WitnessRoute::Generate) {
+				bn_generate_job jb{};
+				static_assert(BN_GEN_PROJECTED_BITS == 0 && BN_GEN_POWERS == WitnessColumn::Powers - WitnessColumn::ProjectedBits, "BN_GEN_* in WitnessColumn's order");
+				jb.kind = c.kind - WitnessColumn::ProjectedBits;
+				jb.tower_level = sh[i].tower_level;
+				jb.n_vars = sh[i].n_vars;
+				jb.d_out = const_cast<void *>(out.columns[i].ptr);
+				if (c.kind == WitnessColumn::ProjectedBits) {
+					jb.d_inner = out.columns[c.inner].ptr;
+					jb.start_index = c.start_index;
+					jb.query_size = c.query_size;
+					jb.query_bits = c.query_bits;
+				}
+				jb.index = c.index;
+				jb.value = c.value.raw();
+				gen_jobs.push_back(jb);
 				continue;
 			}
 			if (sh[i].route == WitnessRoute::Lincomb) {
@@ -294,8 +397,23 @@ inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<Witness
 			                                         pel_outs.data()));
 			out.n_launches++;
 		}
+		if (!gen_jobs.empty()) {
+			check(bn_generate_columns_batch(hal.raw_ctx(), gen_jobs.data(), (uint32_t)gen_jobs.size()));
+			out.n_launches++;
+		}
 		for (const size_t i : on_host) {
 			const WitnessColumn &c = cols[i];
+			if (c.kind >= WitnessColumn::ProjectedBits) {
+				std::vector<B128> inner, one(1);
+				if (c.kind == WitnessColumn::ProjectedBits) {
+					inner.resize(witness_column_elems(sh[c.inner].n_vars, sh[c.inner].tower_level));
+					hal.copy_d2h(FSlice{out.columns[c.inner].ptr, inner.size()}, inner);
+				}
+				one[0] = witness_small_generated(c, sh[i], inner);
+				FSliceMut dst{const_cast<void *>(out.columns[i].ptr), 1};
+				hal.copy_h2d(one, dst);
+				continue;
+			}
 			std::vector<uint32_t> ids = c.kind == WitnessColumn::LinearCombination ? c.terms : std::vector<uint32_t>{c.inner};
 			std::vector<B128> inners(ids.size()), one(1);
 			for (size_t t = 0; t < ids.size(); t++) {
@@ -309,5 +427,9 @@ inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<Witness
 	}
 	return out;
 }
+
+// witness_derive with the generated kinds taken (the header)
+inline size_t witness_build_scratch_elems(const std::vector<WitnessColumn> &cols) { return witness_derive_scratch_elems(cols, true); }
+inline WitnessOutput witness_build(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch) { return witness_derive(hal, cols, scratch, true); }
 
 } // namespace binius_amd

@@ -221,6 +221,32 @@ pub const BN_SHIFT_LOGICAL_LEFT: u32 = 1;
 pub const BN_SHIFT_LOGICAL_RIGHT: u32 = 2;
 pub const BN_DERIVE_N: usize = 3;
 
+/// One generated column of bn_generate_columns_batch (a projection at a hypercube vertex, a transparent that its parameters determine, or
+/// the incrementing column).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bn_generate_job {
+	pub kind: u32,
+	pub tower_level: u32,
+	pub n_vars: u32,
+	pub start_index: u32,
+	pub d_inner: *const c_void,
+	pub d_out: *mut c_void,
+	pub query_size: u32,
+	pub reserved: u32,
+	pub query_bits: u64,
+	pub index: u64,
+	pub value: bn_f128,
+}
+pub const BN_GEN_PROJECTED_BITS: u32 = 0;
+pub const BN_GEN_CONSTANT: u32 = 1;
+pub const BN_GEN_STEP_DOWN: u32 = 2;
+pub const BN_GEN_STEP_UP: u32 = 3;
+pub const BN_GEN_SELECT_ROW: u32 = 4;
+pub const BN_GEN_INCREMENTING: u32 = 5;
+pub const BN_GEN_POWERS: u32 = 6;
+pub const BN_GENERATE_N: usize = 3;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct bn_rs_job {
@@ -480,6 +506,8 @@ unsafe extern "C" {
 		n_terms_total: u32,
 	) -> c_int;
 	pub fn bn_derive_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_generate_columns_batch(ctx: *mut bn_ctx, jobs: *const c_void, n_jobs: u32) -> c_int;
+	pub fn bn_generate_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 	pub fn bn_fri_query_proof_elems(
 		oracles: *const c_void,
 		n_oracles: u32,

@@ -157,6 +157,17 @@ impl Mi355xLayer {
 		check(ffi::bn_derive_columns_batch(self.ctx, jobs.as_ptr().cast(), jobs.len() as u32, terms.as_ptr(), terms.len() as u32))
 	}
 
+	/// The columns of a constraint system that a few integers, one field element or a 0/1 projection of a column on the device
+	/// determine, written there in one launch (`bn_generate_columns_batch`): Projected oracles whose query values are ZERO or ONE
+	/// (m3's `add_selected` / `add_projected`), Constant, StepDown, StepUp, SelectRow and Powers (core/src/transparent/) and the
+	/// incrementing column of `add_structured`.  An output overlaps no inner column of any job and no other output.
+	///
+	/// # Safety
+	/// Every pointer in `jobs` is device memory of the size the job's level and `n_vars` (the inner: `n_vars + query_size`) imply.
+	pub unsafe fn generate_columns_batch(&self, jobs: &[ffi::bn_generate_job]) -> Result<(), Error> {
+		check(ffi::bn_generate_columns_batch(self.ctx, jobs.as_ptr().cast(), jobs.len() as u32))
+	}
+
 	/// NUMA node of the host that `device` hangs off, if the platform says.  The thread that drives a context should run
 	/// there: a small sumcheck round is a host -> device -> host round trip through pinned memory, and from the other
 	/// socket of a 2-socket host every one of them also crosses the socket interconnect.  The

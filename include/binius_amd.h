@@ -440,8 +440,9 @@ int bn_merge_counters(bn_ctx *ctx, uint64_t *counters /*[BN_MERGE_N]*/);
  * a null or misaligned pointer, a forbidden overlap, an output below one element, n_vars above BN_PE_MAX_VARS, reserved != 0, a job's
  * terms outside the term list, an offset outside the level's field and every bound stated above.
  * NOT taken here: any other LinearCombination (a B128 one with arbitrary coefficients is bn_partial_eval_high_lincomb_batch at
- * query_vars = 0), Projected (bn_partial_eval_high_batch / bn_fold_right), Composite (bn_compute_composite), Packed (the same bytes: an
- * alias), transparent and structured polynomials. */
+ * query_vars = 0), Projected (at ZERO / ONE query values and the transparent and structured columns that a few parameters determine:
+ * bn_generate_columns_batch below; at other query values: bn_partial_eval_high_batch / bn_fold_right), Composite
+ * (bn_compute_composite), Packed (the same bytes: an alias), general circuit transparents. */
 enum { BN_DERIVE_SHIFTED = 0, BN_DERIVE_REPEATING = 1, BN_DERIVE_ZERO_PADDED = 2, BN_DERIVE_XOR_COMBINATION = 3 };
 enum { BN_SHIFT_CIRCULAR_LEFT = 0, BN_SHIFT_LOGICAL_LEFT = 1, BN_SHIFT_LOGICAL_RIGHT = 2 }; /* ShiftVariant, multilinear.rs */
 typedef struct {
@@ -467,6 +468,68 @@ int bn_derive_columns_batch(bn_ctx *ctx, const void *jobs, uint32_t n_jobs, cons
  * the jobs they served.  A rejected call counts nowhere. */
 enum { BN_DERIVE_CALLS = 0, BN_DERIVE_LAUNCHES = 1, BN_DERIVE_JOBS = 2, BN_DERIVE_N = 3 };
 int bn_derive_counters(bn_ctx *ctx, uint64_t *counters /*[BN_DERIVE_N]*/);
+/* The columns of a constraint system that a few integers, one field element or a 0/1 projection of a column on the device determine,
+ * generated there at their own tower level.  It replaces filling them on the host and uploading them at column size: the Projected
+ * oracles of m3's add_selected / add_projected (m3/src/builder/constraint_system.rs:445-483), whose query values are only ever ZERO or
+ * ONE, the StepDown selector of every table whose size is not a power of two (core/src/constraint_system/prove.rs:653-), the
+ * incrementing column of add_structured (m3/src/builder/structured.rs:64-81) and the transparents of core/src/transparent/ that are
+ * determined by such parameters.  (bn_partial_eval_high_batch is no substitute for the projection: it returns B128 values.)
+ * Job j (jobs[j], a HOST array of bn_generate_job) writes the column d_out of 2^n_vars values at tower_level (0 or 3 .. 7), n_vars <=
+ * BN_PE_MAX_VARS, packed as bn_hal_multilinear says, at least one element (n_vars + tower_level >= 7): exactly 2^(n_vars + tower_level - 7)
+ * elements are overwritten.  Indices below are value indices.
+ *   BN_GEN_PROJECTED_BITS  d_inner has the output's level and inner_n_vars = n_vars + query_size variables; query_size >= 1, query_bits <
+ *                          2^query_size, start_index + query_size <= inner_n_vars.  With s = start_index, lo = i mod 2^s, hi = i div 2^s:
+ *                          out[i] = in[lo + query_bits 2^s + hi 2^(s + query_size)]: Projected, which is MultilinearExtension::
+ *                          evaluate_partial at the hypercube vertex whose coordinates are the bits of query_bits, lowest first
+ *                          (math/src/multilinear_extension.rs:193-237, validate.rs:239-254).  d_inner is only read and overlaps no output.
+ *   BN_GEN_CONSTANT        out[i] = value, below 2^(2^tower_level)                                      (transparent/constant.rs)
+ *   BN_GEN_STEP_DOWN       level 0: out[i] = 1 for i < index, else 0; index <= 2^n_vars                 (step_down.rs:38-70)
+ *   BN_GEN_STEP_UP         level 0: out[i] = 0 for i < index, else 1; index <= 2^n_vars                 (step_up.rs:39-66)
+ *   BN_GEN_SELECT_ROW      level 0: out[i] = 1 at i = index, else 0; index < 2^n_vars                   (select_row.rs:37)
+ *   BN_GEN_INCREMENTING    out[i] = the value whose bit b is bit b of i (the integer i in the tower basis); n_vars <= 2^tower_level
+ *                          (incrementing_expr, structured.rs:73-81)
+ *   BN_GEN_POWERS          level 3 .. 7: out[i] = value^i in the level's field, out[0] = 1 also for value = 0; value (the base) below
+ *                          2^(2^tower_level)                                                            (powers.rs:35-57)
+ * Fields a kind does not use are ignored; reserved is 0.  Everything is bit-exact; pointers are 16-byte aligned; no output overlaps
+ * another output or an inner column of ANY job of the call.  Like every op it first brings up to date what it reads; the outputs are
+ * complete when the call returns.  n_jobs = 0 is a no-op that counts nowhere.
+ * ONE launch per call whatever the number, kinds, sizes and levels of the jobs (kernels_generate.hip): the frame of
+ * bn_derive_columns_batch.  A projection whose runs are whole elements is a strided copy; below that an output element is put together
+ * from one piece per input element; the other kinds load nothing.  The powers base^(2^b) come from the host in a table of the call.
+ * BN_ERR_INPUT_VALIDATION with nothing launched and no counter moved: an unknown kind, tower level 1 or 2 or above 7 (or not the
+ * kind's), a null or misaligned pointer, a forbidden overlap, an output below one element, n_vars above BN_PE_MAX_VARS, reserved != 0
+ * and every bound stated above.
+ * NOT taken here: Projected at query values other than ZERO and ONE (bn_partial_eval_high_batch / bn_fold_right), Composite
+ * (bn_compute_composite), general circuit transparents and StructuredFixedSize, TowerBasis, EqIndPartialEval (bn_tensor_expand),
+ * ShiftIndPartialEval, DisjointProduct. */
+enum {
+	BN_GEN_PROJECTED_BITS = 0,
+	BN_GEN_CONSTANT = 1,
+	BN_GEN_STEP_DOWN = 2,
+	BN_GEN_STEP_UP = 3,
+	BN_GEN_SELECT_ROW = 4,
+	BN_GEN_INCREMENTING = 5,
+	BN_GEN_POWERS = 6
+};
+typedef struct {
+	uint32_t kind;
+	uint32_t tower_level;
+	uint32_t n_vars;
+	uint32_t start_index;
+	const void *d_inner;
+	void *d_out;
+	uint32_t query_size;
+	uint32_t reserved;
+	uint64_t query_bits;
+	uint64_t index;
+	bn_f128 value;
+} bn_generate_job;
+/* (jobs points to n_jobs bn_generate_job; untyped in the prototype for the same reason as bn_partial_eval_high_batch's cols.) */
+int bn_generate_columns_batch(bn_ctx *ctx, const void *jobs, uint32_t n_jobs);
+/* Read-only, per context (not part of the reference interface): accepted bn_generate_columns_batch calls, the kernel launches they
+ * made, the jobs they served.  A rejected call counts nowhere. */
+enum { BN_GENERATE_CALLS = 0, BN_GENERATE_LAUNCHES = 1, BN_GENERATE_JOBS = 2, BN_GENERATE_N = 3 };
+int bn_generate_counters(bn_ctx *ctx, uint64_t *counters /*[BN_GENERATE_N]*/);
 /* The FRI query phase: everything FRIFolder::finish_proof (crates/core/src/protocols/fri/prove.rs:483-507) writes to the
  * decommitment, from codewords and Merkle trees resident on the device.  The indices are the caller's, as every challenge is: the
  * decommitment is not observed by the challenger (transcript/mod.rs:182-195), so all of them can be sampled before any opening is made.

@@ -584,8 +584,8 @@ int bnh_piop_prove_committed_open_live(bn_ctx *ctx, uint32_t n_committed, const 
  *     combination's level).
  *   - The B128 combinations outside the XOR form share, per wave, ONE bn_partial_eval_high_lincomb_batch at query_vars = 0, its
  *     one-element query ONE in scratch.
- *   - A combination that is neither is BN_ERR_INPUT_VALIDATION.  Projected (bn_partial_eval_high_batch / bn_fold_right are the ops for
- *     it), Composite (bn_compute_composite) and transparent or structured polynomials are NOT taken: list them as given columns.
+ *   - A combination that is neither is BN_ERR_INPUT_VALIDATION.  Projected, transparent and structured polynomials are NOT taken HERE
+ *     (bnh_witness_build below takes those that its kinds name), Composite (bn_compute_composite) by neither: list them as given columns.
  *   - Columns of less than one 16-byte element are host work (one element read, one written) and make no launch.
  * d_columns_out / tower_levels_out / n_vars_out [n_columns]: every column's pointer (a given column's own, an alias's inner's, a derived
  * column's place in d_scratch), level and n_vars; *n_waves_out: the largest wave; *n_launches_out: the op calls made (either may be null).
@@ -598,6 +598,31 @@ uint64_t bnh_witness_derive_scratch_elems(uint32_t n_columns, const uint32_t *co
 int bnh_witness_derive(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
                        const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
                        uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out);
+
+/* bnh_witness_derive with the columns that a few integers, one field element or a 0/1 projection determine generated on the device as
+ * well (bn_generate_columns_batch): with it a caller uploads the committed columns and nothing else for the column kinds m3 emits.
+ * Arguments, encoding, outputs and the kinds 0 .. 5 are bnh_witness_derive's; lc_offsets[i] also carries a constant's value or a
+ * power's base.  The further kinds:
+ *   BNH_WIT_PROJECTED_BITS  a = inner, b = start_index, c = query_size, col_args[i] = query_bits: add_projected / add_selected at query
+ *                           values ZERO / ONE, bit k of query_bits the k-th; the inner's level, n_vars = inner - query_size
+ *   BNH_WIT_CONSTANT        a = tower level, b = n_vars, lc_offsets[i] = the value                              (transparent/constant.rs)
+ *   BNH_WIT_STEP_DOWN       a = 0 (the level), b = n_vars, col_args[i] = index <= 2^n_vars                      (step_down.rs)
+ *   BNH_WIT_STEP_UP         the same                                                                            (step_up.rs)
+ *   BNH_WIT_SELECT_ROW      a = 0, b = n_vars, col_args[i] = index < 2^n_vars                                   (select_row.rs)
+ *   BNH_WIT_INCREMENTING    a = tower level, b = n_vars <= 2^level                              (add_structured(Incrementing))
+ *   BNH_WIT_POWERS          a = tower level 3 .. 7, b = n_vars, lc_offsets[i] = the base                        (powers.rs)
+ * with the bounds of bn_generate_columns_batch.  A generated column without an inner is wave 0, a projection one more than its inner;
+ * every wave that has such columns makes ONE bn_generate_columns_batch beside its derive and lincomb calls (wave 0 makes no other
+ * call).  Columns below one 16-byte element stay host work (a projection's inner is read back whole).  The scratch formula stays
+ * exact: every derived or generated column at its packed size, plus the lincomb op's one element.  bnh_witness_derive itself rejects
+ * these kinds as before.  NOT taken: Projected at other query values, Composite, general circuit transparents and StructuredFixedSize,
+ * TowerBasis, EqIndPartialEval, ShiftIndPartialEval, DisjointProduct: list them as given columns. */
+enum { BNH_WIT_PROJECTED_BITS = 6, BNH_WIT_CONSTANT = 7, BNH_WIT_STEP_DOWN = 8, BNH_WIT_STEP_UP = 9, BNH_WIT_SELECT_ROW = 10, BNH_WIT_INCREMENTING = 11, BNH_WIT_POWERS = 12 };
+uint64_t bnh_witness_build_scratch_elems(uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const uint32_t *lc_terms, const bn_f128 *lc_coeffs,
+                                         uint32_t n_lc_terms, const bn_f128 *lc_offsets);
+int bnh_witness_build(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
+                      const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
+                      uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out);
 
 /* An array-backed transcript, for C callers, benchmarks and tests: it serves samples[n_samples] to `sample` and
  * bit_samples[n_bit_samples] (masked to `bits`) to `sample_bits`, in order, returns non-zero when they run out, and records every
