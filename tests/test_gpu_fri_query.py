@@ -127,37 +127,54 @@ def test_header_alone_and_staging_growth(oracle):
         assert hal.fri_query_counters() == {"calls": 4, "launches": 4, "openings": (len(many) + p.n_test_queries) * p.n_oracles()}
 
 
-def test_deferred_fold_on_the_codeword_is_visible(oracle):
-    """On the context's own stream bn_extrapolate_line_batch is left deferred; the openings that follow read the folded codeword."""
-    import binius_amd
+def _deferred_fold_case(oracle, state):
+    import deferred_states as ds
 
     p = SHAPES[0]
     _message, _chs, idx, pr = fv.case(oracle, p)
     code = np.array(pr.codewords[0])
-    z = oracle.random_scalars(0xF01D, 1)[0]
-    # lo + z (hi - lo) = code  <=>  lo = code + z * hi' with hi' = hi - lo chosen at random
+    log_n = code.shape[0].bit_length()  # the prover's first multilinear folds to the codeword
     diff = oracle.random_b128(0xD1FF, code.shape[0])
-    lo = np.array(code)
-    zd = oracle.ints_to_arr([oracle.mul(z, d) for d in fv.ints(diff)])
-    lo ^= zd
-    hi = lo ^ diff
-    folded = lo.copy()
-    assert oracle.extrapolate_line(folded, hi.copy(), z) == 0 and np.array_equal(folded, code)
-    with binius_amd.Context(0, 1 << 16) as hal:
-        alloc = hal.dev_alloc()
-        d_full = upload(hal, alloc, np.concatenate([lo, hi]))
-        d_nodes = upload(hal, alloc, fv.units(pr.trees[0]))
-        d_term = upload(hal, alloc, pr.codewords[-1])
-        e0, e1 = d_full.split_half()
-        hal.extrapolate_line_batch([e0], [e1], z)
+    box = {}
+
+    def stage(pv, st):
+        z = st.challenges[0]
+        # lo + z (hi - lo) = code  <=>  lo = code + z * hi' with hi' = hi - lo chosen at random
+        lo = np.array(code)
+        lo ^= oracle.ints_to_arr([oracle.mul(z, d) for d in fv.ints(diff)])
+        hi = lo ^ diff
+        folded = lo.copy()
+        assert oracle.extrapolate_line(folded, hi.copy(), z) == 0 and np.array_equal(folded, code)
+        st.inputs[0].host[:] = np.concatenate([lo, hi])
+        box["nodes"] = st.take(fv.units(pr.trees[0]).shape[0], "tree")
+        box["nodes"].host[:] = fv.units(pr.trees[0])
+        box["term"] = st.take(pr.codewords[-1].shape[0], "terminate")
+        box["term"].host[:] = pr.codewords[-1]
+
+    hal = ds.make_context(state, ds.region_elems(3, log_n) + 4096)
+    try:
+        st = ds.reach(hal, oracle, state, seed=0xF01D, stage=stage, log_n=log_n)
+        e0 = st.live[0]
+        assert np.array_equal(e0.host, code), "the model's fold is not the codeword"
         o = host_params(p).query_oracles()[0]
-        got = hal.fri_query_openings([(e0, d_nodes) + o], d_term, idx, p.index_bits())
+        got = hal.fri_query_openings([(e0.dev, box["nodes"].dev) + o], box["term"].dev, idx, p.index_bits())
+        st.continuation()
+        st.check_bytes()
+    finally:
+        hal.close()
     depth, arity, L = o[2], o[1], o[0]
     want = [pr.codewords[-1], fv.units(fv.tree_layer(pr.trees[0], depth))]
     for i in idx:
         want.append(code[i << arity : (i + 1) << arity])
         want.append(fv.units(np.stack(fv.tree_branch(pr.trees[0], i, depth))))
     assert L - depth > 0 and np.array_equal(got, np.concatenate(want))
+
+
+def test_deferred_fold_on_the_codeword_is_visible(oracle):
+    """On the context's own stream bn_extrapolate_line_batch is left deferred -- pending in the single-claim state (S1) or parked as
+    a claim-group fold (S2), reached and proven by tests/deferred_states.py; the openings that follow read the folded codeword."""
+    for state in ("S1", "S2"):
+        _deferred_fold_case(oracle, state)
 
 
 def test_rejections_launch_nothing_and_count_nowhere(hal, oracle):

@@ -133,29 +133,42 @@ def test_repeats(hal, oracle, name, log_repeats):
     run_case(hal, oracle, mixes()[name], log_repeats=log_repeats)
 
 
-def test_deferred_fold_is_visible(oracle):
-    """On the context's own stream bn_extrapolate_line_batch is left deferred; the merge that follows reads the folded array."""
-    import binius_amd
+def _deferred_fold_case(oracle, state):
+    import deferred_states as ds
     from oracle import piop_ref
 
     T = _t()
     for k in (3, 2 * T):
-        full = np.array(data(oracle, 7, k + 1))
         other = data(oracle, 8, k + 1)
-        z = oracle.random_scalars(0x3E26 + k, 1)[0]
-        lo, hi = full[: 1 << k].copy(), full[1 << k :].copy()
-        assert oracle.extrapolate_line(lo, hi, z) == 0
-        with binius_amd.Context(0, 8 << (k + 1)) as hal:
-            alloc = hal.dev_alloc()
-            d_full = upload(hal, alloc, full)
-            d_other = upload(hal, alloc, other)
-            msg = alloc.alloc(1 << (k + 2))
-            hal.fill(msg, PATTERN)
-            e0, e1 = d_full.split_half()
-            hal.extrapolate_line_batch([e0], [e1], z)
-            hal.merge_multilins([e0, d_other], msg, k + 2)
-            got = hal.copy_d2h(msg)
-        assert np.array_equal(got, piop_ref.merge_multilins([lo, np.array(other)], k + 2))
+        box = {}
+
+        def stage(pv, st):
+            box["other"] = st.take(1 << (k + 1), "other")
+            box["other"].host[:] = other
+            box["msg"] = st.take(1 << (k + 2), "message")
+            box["msg"].host[:] = (PATTERN & ((1 << 64) - 1), PATTERN >> 64)
+
+        hal = ds.make_context(state, ds.region_elems(3, k + 1) + 4096)
+        try:
+            st = ds.reach(hal, oracle, state, seed=0x3E26 + k, stage=stage, log_n=k + 1)
+            e0 = st.live[0]
+            lo = np.array(e0.host)  # (the model: evals_0 folded with evals_1 by oracle.extrapolate_line)
+            assert e0.n == 1 << k and not np.array_equal(lo, st.inputs[0].host[: 1 << k])
+            hal.merge_multilins([e0.dev, box["other"].dev], box["msg"].dev, k + 2)
+            got = hal.copy_d2h(box["msg"].dev)
+            box["msg"].host[:] = piop_ref.merge_multilins([lo, np.array(other)], k + 2)
+            assert np.array_equal(got, box["msg"].host)
+            st.continuation()
+            st.check_bytes()
+        finally:
+            hal.close()
+
+
+def test_deferred_fold_is_visible(oracle):
+    """On the context's own stream bn_extrapolate_line_batch is left deferred -- pending in the single-claim state (S1) or parked as
+    a claim-group fold (S2), reached and proven by tests/deferred_states.py; the merge that follows reads the folded array."""
+    for state in ("S1", "S2"):
+        _deferred_fold_case(oracle, state)
 
 
 def test_validation(hal, oracle):
