@@ -266,6 +266,8 @@ def lib():
         "bn_fp4_last_grids": [vp, C.POINTER(u64)],
         "bn_ntt_counters": [vp, C.POINTER(u64)],
         "bn_fri_counters": [vp, C.POINTER(u64)],
+        "bn_fold_counters": [vp, C.POINTER(u64)],
+        "bn_inner_product_counters": [vp, C.POINTER(u64)],
         "bn_xor_reduce": [vp, vp, u32, u32, PF],
         "bn_host_scratch": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)],
         "bn_device_numa_node": [C.c_int, C.POINTER(C.c_int)],
@@ -299,7 +301,7 @@ ABI_SYMBOLS = [
     "bn_extrapolate_line", "bn_extrapolate_line_batch", "bn_tensor_expand", "bn_inner_product", "bn_fold_left", "bn_fold_right", "bn_fri_fold",
     "bn_compute_composite", "bn_pairwise_product_reduce", "bn_log_chunks_range", "bn_pick_log_chunks",
     "bn_kernel_launch", "bn_ntt_forward", "bn_ntt_inverse", "bn_ntt_s_evals", "bn_scalar_mul", "bn_scalar_invert",
-    "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_ntt_counters", "bn_fri_counters", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
+    "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_ntt_counters", "bn_fri_counters", "bn_fold_counters", "bn_inner_product_counters", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
     "bn_merkle_build", "bn_groestl256_leaves", "bn_groestl256_compress_layer", "bn_gather_d2h",
     "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals", "bn_zerocheck_univariate_evals_base",
     "bn_product_tree_layers", "bn_pad_with_ones", "bn_exp_circuit_layers", "bn_bits_to_b128", "bn_exp_counters",
@@ -691,6 +693,27 @@ class Context:
         c = (C.c_uint64 * 6)()
         _check(lib().bn_fri_counters(self._h, c))
         return {k: int(c[i]) for i, k in enumerate(("one", "inter2", "inter3", "ntt2", "ntt3", "copies"))}
+
+    FOLD_COUNTERS = ("right_mfma", "right_tab", "right_scalar", "left_pe", "left_mfma", "left_tab", "left_scalar", "ring2", "ring4", "ring8",
+                     "ring_left2", "ring_left4", "ring_left8", "last_grid", "last_prep", "n_cu")
+
+    def fold_counters(self):
+        """Which kernel answered the bn_fold_right / bn_fold_left calls of this context (bn_fold_counters).  Every accepted call counts
+        in exactly one of right_mfma / right_tab / right_scalar (the matrix cores, the nibble tables, the scalar kernel), left_pe (handed
+        to the partial-evaluation kernel), left_mfma / left_tab / left_scalar; ring<R> / ring_left<R> split the matrix-core calls by
+        kernel instantiation; last_grid / last_prep are the workgroups of the last matrix-core launch and the tower level of its table
+        preparation, n_cu the compute units of the device, by which the launchers size their grids.  Rejected calls move nothing."""
+        c = (C.c_uint64 * len(self.FOLD_COUNTERS))()
+        _check(lib().bn_fold_counters(self._h, c))
+        return {k: int(c[i]) for i, k in enumerate(self.FOLD_COUNTERS)}
+
+    def inner_product_counters(self):
+        """Which kernel answered the bn_inner_product calls of this context (bn_inner_product_counters): the F x F split sum on the
+        matrix cores, the 9-lane split kernel, the bit-sliced B32 kernel (k_ip32), the scalar kernel (k_inner_product).  Rejected
+        calls count nowhere."""
+        c = (C.c_uint64 * 4)()
+        _check(lib().bn_inner_product_counters(self._h, c))
+        return {k: int(c[i]) for i, k in enumerate(("mfma_split", "split9", "ip32", "scalar"))}
 
     # ---- ComputeLayer
     def copy_h2d(self, src, dst):

@@ -165,7 +165,8 @@ struct routed {
 	static routed launch(hipError_t e) { return routed(e == hipErrorNotSupported ? declined : launched, e); }
 };
 // ---- evaluate_partial_high (abi_ops.cpp, abi_partial_eval.cpp)
-int fold_left_dispatch(bn_ctx *ctx, const void *d_mat, uint32_t tower_level, const void *d_vec, uint64_t vec_len, void *d_out, uint64_t out_len);
+int fold_left_dispatch(bn_ctx *ctx, const void *d_mat, uint32_t tower_level, const void *d_vec, uint64_t vec_len, void *d_out, uint64_t out_len,
+                       uint64_t *counted = nullptr /*[BN_FOLD_N] of a bn_fold_left call*/);
 // validated columns (query_vars <= n_vars each) at the 2^q-entry query d_vec; routed: a bn_fold_left call served as a one-column job
 int partial_eval_run(bn_ctx *ctx, const bn_pe_column *cols, uint32_t n_cols, const void *d_vec, uint32_t q, void *const *d_outs, bool routed);
 // ---- small helpers shared by the op entry points (abi.cpp)

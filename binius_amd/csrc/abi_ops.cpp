@@ -5,18 +5,35 @@
 #include "abi_common.hpp"
 
 namespace bnabi {
+// a matrix-core fold that was launched, in the counters of bn_fold_counters
+static void count_linmap(uint64_t *counted, int route, int ring2, const bn::linmap_launch &l)
+{
+	counted[route] += 1;
+	if (l.ring_r == 2 || l.ring_r == 4 || l.ring_r == 8) counted[ring2 + (l.ring_r == 2 ? 0 : l.ring_r == 4 ? 1 : 2)] += 1;
+	counted[BN_FOLD_LAST_GRID] = l.grid;
+	counted[BN_FOLD_LAST_PREP] = l.prep_level;
+}
+
 // fold_left on the kernels of kernels_misc.hip / kernels_linmap.hip (arguments validated by the caller)
-int fold_left_dispatch(bn_ctx *ctx, const void *d_mat, uint32_t tower_level, const void *d_vec, uint64_t vec_len, void *d_out, uint64_t out_len)
+// counted: the BN_FOLD_* counters of a bn_fold_left call (nullptr: a column of bn_partial_eval_high_batch, which has its own)
+int fold_left_dispatch(bn_ctx *ctx, const void *d_mat, uint32_t tower_level, const void *d_vec, uint64_t vec_len, void *d_out, uint64_t out_len,
+                       uint64_t *counted)
 {
 	if (tower_level == 5 && out_len >= 4096 && (vec_len == 16 || vec_len == 32 || vec_len == 64)) {
 		void *tab = bn::ctx_scratch(ctx, bn::linmap_table_bytes(vec_len * 32));
 		if (tab) {
-			const hipError_t e = bn::launch_fold_left_mfma(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len, tab);
-			if (e == hipSuccess) return BN_OK;
+			bn::linmap_launch l;
+			const hipError_t e = bn::launch_fold_left_mfma(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len, tab, &l);
+			if (e == hipSuccess) {
+				if (counted) count_linmap(counted, BN_FOLD_LEFT_MFMA, BN_FOLD_RING_LEFT2, l);
+				return BN_OK;
+			}
 			if (e != hipErrorNotSupported) BN_HIP(e);
 		}
 	}
-	BN_HIP(bn::launch_fold_left(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len));
+	bool by_tab = false;
+	BN_HIP(bn::launch_fold_left(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len, &by_tab));
+	if (counted) counted[by_tab ? BN_FOLD_LEFT_TAB : BN_FOLD_LEFT_SCALAR] += 1;
 	return BN_OK;
 }
 } // namespace bnabi
@@ -48,19 +65,31 @@ int bn_inner_product(bn_ctx *ctx, const void *d_a, uint64_t a_len, uint32_t towe
 	BN_HIP(hipMemsetAsync(ctx->d_result, 0, 2 * sizeof(f128), ctx->stream));
 	if (tower_level == 7 && b_len >= 2 && (b_len & 1) == 0) {
 		// F x F: a plain sum of products -> the bit-sliced product-sum kernel (two half-range streams)
-		if (bn::mfma_applies(ctx->n_cu, b_len / 2))
+		const bool mfma = bn::mfma_applies(ctx->n_cu, b_len / 2);
+		if (mfma)
 			BN_HIP(bn::launch_roundeval_mfma_split(ctx->stream, ctx->n_cu, d_a, d_b, b_len / 2, b_len / 2, ctx->d_result));
 		else
 			BN_HIP(bn::launch_roundeval9_split(ctx->stream, ctx->n_cu, d_a, d_b, b_len / 2, b_len / 2, ctx->d_result));
+		ctx->ip_calls[mfma ? BN_IP_MFMA_SPLIT : BN_IP_SPLIT9] += 1;
 		return publish_result(ctx, 2, h_out);
 	}
 	if (tower_level == 5 && b_len >= 8192 && b_len % 512 == 0) {
 		// B32 x F: four independent bit-sliced GF(2^32) inner products (kernels_ip32.hip)
 		BN_HIP(bn::launch_ip32(ctx->stream, ctx->n_cu, d_a, d_b, b_len, ctx->d_result));
+		ctx->ip_calls[BN_IP_IP32] += 1;
 		return publish_result(ctx, 1, h_out);
 	}
 	BN_HIP(bn::launch_inner_product(ctx->stream, ctx->n_cu, d_a, tower_level, d_b, b_len, ctx->d_result));
+	ctx->ip_calls[BN_IP_SCALAR] += 1;
 	return publish_result(ctx, 1, h_out);
+}
+
+int bn_inner_product_counters(bn_ctx *ctx, uint64_t *counters)
+{
+	BN_REQUIRE(ctx && counters, "null argument");
+	BN_ENTER(ctx);
+	for (int i = 0; i < BN_IP_N; i++) counters[i] = ctx->ip_calls[i];
+	return BN_OK;
 }
 
 static int fold_common(bn_ctx *ctx, bool left, const void *d_mat, uint64_t mat_len, uint32_t tower_level, const void *d_vec,
@@ -84,21 +113,38 @@ static int fold_common(bn_ctx *ctx, bool left, const void *d_mat, uint64_t mat_l
 		if (out_len <= ((uint64_t)1 << bn::kPeMaxLogOut) && vec_len >= 4096 && !(no_pe && no_pe[0] == '1')) {
 			const bn_pe_column col{d_mat, tower_level, log_evals};
 			void *const out = d_out;
-			return partial_eval_run(ctx, &col, 1, d_vec, log_q, &out, /*routed=*/true);
+			const int rc = partial_eval_run(ctx, &col, 1, d_vec, log_q, &out, /*routed=*/true);
+			if (rc == BN_OK) ctx->fold_calls[BN_FOLD_LEFT_PE] += 1;
+			return rc;
 		}
-		return fold_left_dispatch(ctx, d_mat, tower_level, d_vec, vec_len, d_out, out_len);
+		return fold_left_dispatch(ctx, d_mat, tower_level, d_vec, vec_len, d_out, out_len, ctx->fold_calls);
 	}
 	// rows of 512 .. 2048 bits: the linear map on the matrix cores (kernels_linmap.hip); every other shape: nibble tables
 	const uint64_t row_bits = vec_len << tower_level;
 	if (out_len >= 4096 && (row_bits == 512 || row_bits == 1024 || row_bits == 2048)) {
 		void *tab = bn::ctx_scratch(ctx, bn::linmap_table_bytes(row_bits));
 		if (tab) {
-			const hipError_t e = bn::launch_fold_right_mfma(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len, tab);
-			if (e == hipSuccess) return BN_OK;
+			bn::linmap_launch l;
+			const hipError_t e = bn::launch_fold_right_mfma(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len, tab, &l);
+			if (e == hipSuccess) {
+				bnabi::count_linmap(ctx->fold_calls, BN_FOLD_RIGHT_MFMA, BN_FOLD_RING2, l);
+				return BN_OK;
+			}
 			if (e != hipErrorNotSupported) BN_HIP(e);
 		}
 	}
-	BN_HIP(bn::launch_fold_right(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len));
+	bool by_tab = false;
+	BN_HIP(bn::launch_fold_right(ctx->stream, ctx->n_cu, d_mat, tower_level, d_vec, vec_len, d_out, out_len, &by_tab));
+	ctx->fold_calls[by_tab ? BN_FOLD_RIGHT_TAB : BN_FOLD_RIGHT_SCALAR] += 1;
+	return BN_OK;
+}
+
+int bn_fold_counters(bn_ctx *ctx, uint64_t *counters)
+{
+	BN_REQUIRE(ctx && counters, "null argument");
+	BN_ENTER(ctx);
+	for (int i = 0; i < BN_FOLD_N; i++) counters[i] = ctx->fold_calls[i];
+	counters[BN_FOLD_N_CU] = (uint64_t)ctx->n_cu;
 	return BN_OK;
 }
 

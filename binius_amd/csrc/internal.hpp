@@ -78,6 +78,8 @@ struct bn_ctx {
 	std::vector<uint64_t> h_s_evals;   // ... and its host copy: an NTT instance's basis is uploaded once, not per call
 	uint64_t ntt_calls_bs = 0, ntt_calls_tiled = 0, ntt_calls_layer = 0; // bn_ntt_* calls served per kernel family (bn_ntt_counters)
 	uint64_t fri_passes[BN_FRI_N] = {}; // bn_fri_fold passes launched per form, and its copies (bn_fri_counters)
+	uint64_t fold_calls[BN_FOLD_N] = {}; // bn_fold_left / bn_fold_right calls per answering kernel, the last matrix-core launch (bn_fold_counters)
+	uint64_t ip_calls[BN_IP_N] = {};     // bn_inner_product calls per answering kernel (bn_inner_product_counters)
 	uint64_t exp_calls = 0, exp_launches = 0, exp_bits_launches = 0;     // bn_exp_circuit_layers / bn_bits_to_b128 (bn_exp_counters)
 	uint64_t flush_calls = 0, flush_launches = 0, flush_served = 0, flush_multipass = 0; // bn_flush_witness_batch (bn_flush_counters)
 	uint64_t pe_calls = 0, pe_launches = 0, pe_cols_kernel = 0, pe_cols_fallback = 0, pe_max_share = 0, pe_routed = 0; // bn_partial_eval_counters
@@ -651,17 +653,23 @@ hipError_t launch_hal_row(hipStream_t s, int n_cu, const void *evals, uint64_t l
 // ---- kernels_misc.hip
 hipError_t launch_inner_product(hipStream_t s, int n_cu, const void *a, uint32_t tower_level, const void *b,
                                 uint64_t b_len, f128 *d_out);
+// (*tab, where given: whether the nibble-table kernel was launched -- the scalar kernel otherwise)
 hipError_t launch_fold_left(hipStream_t s, int n_cu, const void *mat, uint32_t tower_level, const void *vec,
-                            uint64_t vec_len, void *out, uint64_t out_len);
+                            uint64_t vec_len, void *out, uint64_t out_len, bool *tab = nullptr);
 // fold_right as a GF(2)-linear map on the matrix cores (kernels_linmap.hip): rows of 512 / 1024 / 2048 bits; hipErrorNotSupported
 // for every other shape.  d_table: linmap_table_bytes(row_bits) bytes of scratch.
 size_t linmap_table_bytes(uint64_t row_bits);
+struct linmap_launch { // what a matrix-core fold launched (bn_fold_counters)
+	uint32_t ring_r = 0;     // R of k_linmap_ring<R> / k_linmap_ring_left<R>; 0: k_linmap (rows prefetched in registers)
+	uint32_t grid = 0;       // its workgroups
+	uint32_t prep_level = 0; // IOTA of the k_linmap_prep<IOTA> in front of it
+};
 hipError_t launch_fold_right_mfma(hipStream_t s, int n_cu, const void *mat, uint32_t tower_level, const void *vec, uint64_t vec_len, void *out,
-                                  uint64_t out_len, void *d_table);
+                                  uint64_t out_len, void *d_table, linmap_launch *launched = nullptr);
 hipError_t launch_fold_left_mfma(hipStream_t s, int n_cu, const void *mat, uint32_t tower_level, const void *vec, uint64_t vec_len, void *out,
-                                 uint64_t out_len, void *d_table); // B32 entries, vec_len 16 / 32 / 64
+                                 uint64_t out_len, void *d_table, linmap_launch *launched = nullptr); // B32 entries, vec_len 16 / 32 / 64
 hipError_t launch_fold_right(hipStream_t s, int n_cu, const void *mat, uint32_t tower_level, const void *vec,
-                             uint64_t vec_len, void *out, uint64_t out_len);
+                             uint64_t vec_len, void *out, uint64_t out_len, bool *tab = nullptr);
 hipError_t launch_compute_composite_generic(hipStream_t s, const void *const *d_rows_dev, uint32_t n_rows,
                                             uint64_t row_len, void *out, const bn_step *d_steps, uint32_t n_steps);
 hipError_t launch_fri_fold(hipStream_t s, const uint64_t *d_s_evals, uint32_t tw_level, uint32_t log_domain,

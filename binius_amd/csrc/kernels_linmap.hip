@@ -410,7 +410,7 @@ size_t linmap_table_bytes(uint64_t row_bits) { return (size_t)(row_bits / 64) * 
 // fold_right on the matrix cores for rows of 512, 1024 or 2048 bits; hipErrorNotSupported otherwise (the caller runs the
 // nibble-table kernel).  d_table: linmap_table_bytes(row_bits) bytes of scratch.
 hipError_t launch_fold_right_mfma(hipStream_t s, int n_cu, const void *mat, uint32_t tower_level, const void *vec, uint64_t vec_len, void *out,
-                                  uint64_t out_len, void *d_table)
+                                  uint64_t out_len, void *d_table, linmap_launch *launched)
 {
 	static const bool on = [] {
 		const char *e = bn::settled_knob("BN_FOLD_MFMA"); // 0: the nibble-table kernel everywhere
@@ -452,6 +452,7 @@ hipError_t launch_fold_right_mfma(hipStream_t s, int n_cu, const void *mat, uint
 		case 1024: hipLaunchKernelGGL(k_linmap_ring<4>, grid, dim3(256), lds, s, (const char *)mat, (const uint4 *)d_table, (uint32_t *)out, out_len); break;
 		default: hipLaunchKernelGGL(k_linmap_ring<8>, grid, dim3(256), lds, s, (const char *)mat, (const uint4 *)d_table, (uint32_t *)out, out_len); break;
 		}
+		if (launched) *launched = linmap_launch{(uint32_t)(row_bits / 256), grid.x, tower_level};
 		return hipGetLastError();
 	}
 	switch (row_bits) {
@@ -459,12 +460,13 @@ hipError_t launch_fold_right_mfma(hipStream_t s, int n_cu, const void *mat, uint
 	case 1024: hipLaunchKernelGGL(k_linmap<4>, grid, dim3(256), 0, s, (const char *)mat, (const uint4 *)d_table, (uint32_t *)out, out_len); break;
 	default: hipLaunchKernelGGL(k_linmap<8>, grid, dim3(256), 0, s, (const char *)mat, (const uint4 *)d_table, (uint32_t *)out, out_len); break;
 	}
+	if (launched) *launched = linmap_launch{0, grid.x, tower_level};
 	return hipGetLastError();
 }
 
 // fold_left on the matrix cores: B32 entries, vec_len = 16, 32 or 64 (gathered rows of 512 / 1024 / 2048 bits)
 hipError_t launch_fold_left_mfma(hipStream_t s, int n_cu, const void *mat, uint32_t tower_level, const void *vec, uint64_t vec_len, void *out,
-                                 uint64_t out_len, void *d_table)
+                                 uint64_t out_len, void *d_table, linmap_launch *launched)
 {
 	static const bool on = [] {
 		const char *e = bn::settled_knob("BN_FOLD_MFMA");
@@ -488,6 +490,7 @@ hipError_t launch_fold_left_mfma(hipStream_t s, int n_cu, const void *mat, uint3
 	case 32: hipLaunchKernelGGL(k_linmap_ring_left<4>, grid, dim3(256), lds, s, (const uint32_t *)mat, (const uint4 *)d_table, (uint32_t *)out, out_len); break;
 	default: hipLaunchKernelGGL(k_linmap_ring_left<8>, grid, dim3(256), lds, s, (const uint32_t *)mat, (const uint4 *)d_table, (uint32_t *)out, out_len); break;
 	}
+	if (launched) *launched = linmap_launch{(uint32_t)(vec_len / 8), grid.x, 5};
 	return hipGetLastError();
 }
 

@@ -204,7 +204,7 @@ __global__ __launch_bounds__(TH) void k_fold_tab(const uint64_t *mat, const uint
 }
 
 template <int IOTA, bool LEFT>
-static hipError_t run_fold_tab(hipStream_t s, const void *mat, const void *vec, uint64_t vec_len, void *out, uint64_t out_len)
+static hipError_t run_fold_tab(hipStream_t s, const void *mat, const void *vec, uint64_t vec_len, void *out, uint64_t out_len, bool *tab)
 {
 	constexpr int R = 1, TH = 1024;
 	constexpr int NB = 1 << IOTA, P = NB / 4, J = 256 / P;
@@ -214,6 +214,7 @@ static hipError_t run_fold_tab(hipStream_t s, const void *mat, const void *vec, 
 	if (attr != hipSuccess) return attr;
 	hipLaunchKernelGGL((k_fold_tab<IOTA, LEFT, R, TH>), dim3((unsigned)blocks), dim3(TH), lds, s, (const uint64_t *)mat, (const uint4 *)vec, vec_len,
 	                   (uint4 *)out, out_len);
+	if (tab) *tab = true; // (the launch it reports on; its error is the caller's to look at)
 	return hipGetLastError();
 }
 
@@ -269,13 +270,14 @@ struct foldr_launcher {
 };
 
 hipError_t launch_fold_left(hipStream_t s, int n_cu, const void *mat, uint32_t tower_level, const void *vec,
-                            uint64_t vec_len, void *out, uint64_t out_len)
+                            uint64_t vec_len, void *out, uint64_t out_len, bool *tab)
 {
+	if (tab) *tab = false;
 	if (out_len == 0) return hipSuccess;
 	if (out_len >= 1024) {
-		if (tower_level == 3) return run_fold_tab<3, true>(s, mat, vec, vec_len, out, out_len);
-		if (tower_level == 4) return run_fold_tab<4, true>(s, mat, vec, vec_len, out, out_len);
-		if (tower_level == 5) return run_fold_tab<5, true>(s, mat, vec, vec_len, out, out_len);
+		if (tower_level == 3) return run_fold_tab<3, true>(s, mat, vec, vec_len, out, out_len, tab);
+		if (tower_level == 4) return run_fold_tab<4, true>(s, mat, vec, vec_len, out, out_len, tab);
+		if (tower_level == 5) return run_fold_tab<5, true>(s, mat, vec, vec_len, out, out_len, tab);
 	}
 	uint64_t want = (out_len + 255) / 256;
 	unsigned g = (unsigned)(want < (uint64_t)n_cu * 8 ? want : (uint64_t)n_cu * 8);
@@ -283,13 +285,14 @@ hipError_t launch_fold_left(hipStream_t s, int n_cu, const void *mat, uint32_t t
 }
 
 hipError_t launch_fold_right(hipStream_t s, int n_cu, const void *mat, uint32_t tower_level, const void *vec,
-                             uint64_t vec_len, void *out, uint64_t out_len)
+                             uint64_t vec_len, void *out, uint64_t out_len, bool *tab)
 {
+	if (tab) *tab = false;
 	if (out_len == 0) return hipSuccess;
 	if (out_len >= 1024) {
-		if (tower_level == 3) return run_fold_tab<3, false>(s, mat, vec, vec_len, out, out_len);
-		if (tower_level == 4) return run_fold_tab<4, false>(s, mat, vec, vec_len, out, out_len);
-		if (tower_level == 5) return run_fold_tab<5, false>(s, mat, vec, vec_len, out, out_len);
+		if (tower_level == 3) return run_fold_tab<3, false>(s, mat, vec, vec_len, out, out_len, tab);
+		if (tower_level == 4) return run_fold_tab<4, false>(s, mat, vec, vec_len, out, out_len, tab);
+		if (tower_level == 5) return run_fold_tab<5, false>(s, mat, vec, vec_len, out, out_len, tab);
 	}
 	uint64_t want = (out_len + 255) / 256;
 	unsigned g = (unsigned)(want < (uint64_t)n_cu * 8 ? want : (uint64_t)n_cu * 8);

@@ -833,6 +833,28 @@ int bn_ntt_counters(bn_ctx *ctx, uint64_t *counters /*[BN_NTT_N]*/);
  * rejected call counts nowhere. */
 enum { BN_FRI_PASS_ONE = 0, BN_FRI_PASS_INTER2 = 1, BN_FRI_PASS_INTER3 = 2, BN_FRI_PASS_NTT2 = 3, BN_FRI_PASS_NTT3 = 4, BN_FRI_COPIES = 5, BN_FRI_N = 6 };
 int bn_fri_counters(bn_ctx *ctx, uint64_t *counters /*[BN_FRI_N]*/);
+/* Which kernel answered the bn_fold_right / bn_fold_left calls of this context since it was created: fold_right on the matrix cores
+ * (RIGHT_MFMA: rows of 512 / 1024 / 2048 bits, 4096 outputs and more), by the nibble-table kernel (RIGHT_TAB: B8 .. B32 entries, 1024
+ * outputs and more) or by the scalar kernel (RIGHT_SCALAR); fold_left handed to the partial-evaluation kernel (LEFT_PE: at most 1024
+ * outputs under a vector of 4096 elements and more; bn_partial_eval_counters counts the same calls as FOLD_LEFT_ROUTED), on the matrix
+ * cores (LEFT_MFMA: B32 entries, 16 / 32 / 64 vector elements, 4096 outputs and more), by the nibble-table kernel (LEFT_TAB) or by
+ * the scalar kernel (LEFT_SCALAR).  Every accepted call counts in exactly one of the seven.  RING2 / RING4 / RING8 and RING_LEFT2 /
+ * RING_LEFT4 / RING_LEFT8 split the matrix-core calls by the kernel's row width in 256-bit units; LAST_GRID and LAST_PREP are the
+ * workgroups of the last matrix-core launch and the tower level of its table preparation (0 before the first); N_CU is the number of
+ * compute units of the context's device, which the launchers size their grids by (a matrix-core fold: at most two workgroups per unit,
+ * the scalar kernel: at most eight).  Read-only; a rejected call moves nothing. */
+enum {
+	BN_FOLD_RIGHT_MFMA = 0, BN_FOLD_RIGHT_TAB = 1, BN_FOLD_RIGHT_SCALAR = 2, BN_FOLD_LEFT_PE = 3, BN_FOLD_LEFT_MFMA = 4, BN_FOLD_LEFT_TAB = 5,
+	BN_FOLD_LEFT_SCALAR = 6, BN_FOLD_RING2 = 7, BN_FOLD_RING4 = 8, BN_FOLD_RING8 = 9, BN_FOLD_RING_LEFT2 = 10, BN_FOLD_RING_LEFT4 = 11,
+	BN_FOLD_RING_LEFT8 = 12, BN_FOLD_LAST_GRID = 13, BN_FOLD_LAST_PREP = 14, BN_FOLD_N_CU = 15, BN_FOLD_N = 16
+};
+int bn_fold_counters(bn_ctx *ctx, uint64_t *counters /*[BN_FOLD_N]*/);
+/* Which kernel answered the bn_inner_product calls of this context: the F x F split sum on the matrix cores (MFMA_SPLIT: level 7, even
+ * length, at least one 256-point tile per CU in each half), the 9-lane split kernel (SPLIT9: level 7, every other even length), the
+ * bit-sliced B32 kernel (IP32: level 5, 8192 elements and more, a multiple of 512) or the scalar kernel (SCALAR: everything else).
+ * Read-only; a rejected call counts nowhere. */
+enum { BN_IP_MFMA_SPLIT = 0, BN_IP_SPLIT9 = 1, BN_IP_IP32 = 2, BN_IP_SCALAR = 3, BN_IP_N = 4 };
+int bn_inner_product_counters(bn_ctx *ctx, uint64_t *counters /*[BN_IP_N]*/);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,13 @@ def test_inner_product_ragged_lengths_matrix_core_path(hal, oracle, n_b):
     assert got == xor_sum(oracle.mul_vec(a, b))
 
 
+# the kernel that answers a fold of 2^20 values with 16 vector elements (2^16 outputs): fold_right on the matrix cores where the 16 entries
+# are a row of 512, 1024 or 2048 bits, fold_left for B32 entries; the nibble tables for the other B8 .. B32 shapes; the scalar kernel
+ROUTE_2P20 = {(False, 0): {"right_scalar": 1}, (False, 3): {"right_tab": 1}, (False, 4): {"right_tab": 1}, (False, 5): {"right_mfma": 1, "ring2": 1},
+              (False, 6): {"right_mfma": 1, "ring4": 1}, (False, 7): {"right_mfma": 1, "ring8": 1}, (True, 0): {"left_scalar": 1}, (True, 3): {"left_tab": 1},
+              (True, 4): {"left_tab": 1}, (True, 5): {"left_mfma": 1, "ring_left2": 1}, (True, 6): {"left_scalar": 1}, (True, 7): {"left_scalar": 1}}
+
+
 @pytest.mark.parametrize("level", [0, 3, 4, 5, 6, 7])
 @pytest.mark.parametrize("left", [True, False])
 def test_fold_left_right_2p20(hal, oracle, level, left):
@@ -63,12 +70,15 @@ def test_fold_left_right_2p20(hal, oracle, level, left):
     out_len = 1 << (LOG - log_q)
     dm, dv, do = upload(hal, alloc, mat), upload(hal, alloc, vec), alloc.alloc(out_len)
     exp = oracle.arr(out_len)
+    c0 = hal.fold_counters()
     if left:
         hal.fold_left(dm, level, dv, do)
         assert oracle.fold_left(mat, level, vec, exp) == 0
     else:
         hal.fold_right(dm, level, dv, do)
         assert oracle.fold_right(mat, level, vec, exp) == 0
+    c1 = hal.fold_counters()
+    assert {k: c1[k] - c0[k] for k in c0 if c1[k] != c0[k] and not k.startswith("last_")} == ROUTE_2P20[(left, level)]
     assert np.array_equal(hal.copy_d2h(do), exp)
 
 

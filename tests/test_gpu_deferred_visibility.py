@@ -889,16 +889,24 @@ EXEMPT = {
     "bn_kernel_launch": "the prover's own evaluation: every case's execute() and continuation",
 }
 
+# Entry points that are declared with a context but no device memory among their arguments: outside the tables by construction.  Listed here so
+# that one which grows a device pointer has to move into a table, each with the reason.
+NO_DEVICE_MEMORY = {
+    "bn_fold_counters": "read-only query of host counters (which kernel answered bn_fold_left / bn_fold_right): no device memory, launches and flushes nothing",
+    "bn_inner_product_counters": "read-only query of host counters (which kernel answered bn_inner_product): no device memory, launches and flushes nothing",
+}
+
 DEVICE_ARG = re.compile(r"\bvoid\s*\*\s*(?:const\s*)?\*?\s*d_\w+|\b(?:void|bn_hal_multilinear|bn_memmap)\s*\*\s*(?:jobs|cols|points|mls|ml|maps|oracles)\b")
 
 
-def device_entry_points():
-    """every `int bn_*(bn_ctx *ctx, ...)` of the public header with a device pointer, or a table of them, among its arguments"""
+def device_entry_points(device=True):
+    """every `int bn_*(bn_ctx *ctx, ...)` of the public header with a device pointer, or a table of them, among its arguments
+    (device=False: those without one)"""
     text = open(os.path.join(ROOT, "include", "binius_amd.h")).read()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     names = []
     for m in re.finditer(r"\bint\s+(bn_\w+)\s*\(\s*bn_ctx\s*\*\s*ctx\s*,([^;]*?)\)\s*;", text, flags=re.S):
-        if DEVICE_ARG.search(m.group(2)):
+        if bool(DEVICE_ARG.search(m.group(2))) == device:
             names.append(m.group(1))
     return names
 
@@ -915,6 +923,10 @@ def test_entry_point_tables_are_complete():
     stale = [n for n in list(covered) + list(EXEMPT) if n not in names]
     assert not stale, "names in the tables that the header no longer declares: %s" % stale
     assert all(isinstance(r, str) and len(r) > 10 for r in EXEMPT.values())
+    # the queries that take no device memory are declared, are in no table, and stay without a device pointer
+    hostonly = device_entry_points(device=False)
+    for n, reason in NO_DEVICE_MEMORY.items():
+        assert n in hostonly and n not in names and n not in covered and n not in EXEMPT and len(reason) > 10, n
     # the issue's list for B
     for op in ("inner_product", "fold_left", "fold_right", "tensor_expand", "compute_composite", "pairwise_product_reduce", "ntt_forward", "groestl256_leaves",
                "hal_fold_multilinear", "hal_round_evals", "mle_evaluate_batch", "partial_eval_high_batch", "partial_eval_high_lincomb_batch", "merge_multilins",

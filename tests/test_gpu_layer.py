@@ -35,6 +35,11 @@ def upload(hal, alloc, arr):
     return d
 
 
+def fold_routes_moved(before, after):
+    """The counters of Context.fold_counters() that differ between two readings (its record of the last matrix-core launch apart)."""
+    return {k: after[k] - before[k] for k in before if after[k] != before[k] and not k.startswith("last_")}
+
+
 # ---- crates/compute/src/layer.rs:792-825 test_copy_host_device
 def test_copy_host_device(hal, oracle):
     alloc = hal.dev_alloc()
@@ -245,12 +250,14 @@ def test_fold_left_right_table_path(hal, oracle, level, log_q, left):
     assert out_len >= 1024
     dm, dv, do = upload(hal, alloc, mat), upload(hal, alloc, vec), alloc.alloc(out_len)
     exp = oracle.arr(out_len)
+    c0 = hal.fold_counters()
     if left:
         hal.fold_left(dm, level, dv, do)
         assert oracle.fold_left(mat, level, vec, exp) == 0
     else:
         hal.fold_right(dm, level, dv, do)
         assert oracle.fold_right(mat, level, vec, exp) == 0
+    assert fold_routes_moved(c0, hal.fold_counters()) == {"left_tab" if left else "right_tab": 1}
     assert np.array_equal(hal.copy_d2h(do), exp)
 
 
@@ -270,7 +277,11 @@ def test_fold_right_on_the_matrix_cores(hal, oracle, level, log_q, log_out):
     guard = alloc.alloc(8)
     hal.fill(guard, 0x77)
     exp = oracle.arr(out_len)
+    c0 = hal.fold_counters()
     hal.fold_right(dm, level, dv, do)
+    c1 = hal.fold_counters()
+    assert fold_routes_moved(c0, c1) == {"right_mfma": 1, "ring%d" % (((1 << log_q) << level) // 256): 1}
+    assert c1["last_prep"] == level and 1 <= c1["last_grid"] <= out_len // 64
     assert oracle.fold_right(mat, level, vec, exp) == 0
     assert np.array_equal(hal.copy_d2h(do), exp)
     assert (hal.copy_d2h(guard)[:, 0] == 0x77).all()
@@ -290,7 +301,9 @@ def test_fold_left_on_the_matrix_cores(hal, oracle, log_q, log_out):
     guard = alloc.alloc(8)
     hal.fill(guard, 0x66)
     exp = oracle.arr(out_len)
+    c0 = hal.fold_counters()
     hal.fold_left(dm, level, dv, do)
+    assert fold_routes_moved(c0, hal.fold_counters()) == {"left_mfma": 1, "ring_left%d" % ((1 << log_q) // 8): 1}
     assert oracle.fold_left(mat, level, vec, exp) == 0
     assert np.array_equal(hal.copy_d2h(do), exp)
     assert (hal.copy_d2h(guard)[:, 0] == 0x66).all()
