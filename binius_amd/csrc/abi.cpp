@@ -51,8 +51,6 @@ void *ctx_scratch(bn_ctx *ctx, size_t bytes)
 } // namespace bn
 
 namespace bnabi {
-// Launch a deferred extrapolate_line batch (see bn_extrapolate_line_batch).  Every entry point
-// that can observe device memory or the stream calls this first, so the deferral is invisible.
 // ---- resident tail kernel: host side of the protocol (device side: kernels_foldeval9.hip)
 // command block in the pinned mailbox page: h_mail[80].lo = command word, h_mail[81] = z,
 // h_mail[82].lo = status (the id of the last tail kernel that exited)
@@ -218,137 +216,6 @@ void side_join(bn_ctx *ctx)
 	ctx->side_busy = false;
 }
 
-bool ranges_overlap(const void *p, uint64_t n_p, const void *q, uint64_t n_q)
-{
-	const char *a = (const char *)p, *b = (const char *)q;
-	return n_p && n_q && a < b + n_q * sizeof(f128) && b < a + n_p * sizeof(f128);
-}
-
-// [p, p + n) touches none of the arrays the deferred fold reads or writes, nor the weighted shadow
-bool independent_of_pending(bn_ctx *ctx, const void *p, uint64_t n)
-{
-	const bn_ctx::pending_fold &pf = ctx->pend;
-	for (uint32_t i = 0; i < pf.count; i++)
-		if (ranges_overlap(p, n, pf.x0[i], pf.n) || ranges_overlap(p, n, pf.x1[i], pf.n) || ranges_overlap(p, n, pf.src0[i], pf.n)) return false;
-	if (ctx->shadow.valid && ctx->shadow.S && ranges_overlap(p, n, ctx->shadow.S, ctx->shadow.S_cap)) return false;
-	return true;
-}
-
-// [p, p + n) overlaps an array the MLE-check shadow describes: the halves of the caller's a and b the next evaluation will
-// pass, the indicator table (and the noted copy of its lower half, which the caller's next add turns into the table), S
-bool shadow_touched_by_write(bn_ctx *ctx, const void *p, uint64_t n)
-{
-	const bn_ctx::shadow_state &sh = ctx->shadow;
-	if (!sh.valid) return false;
-	for (const void *q : {sh.a_lo, sh.a_hi, sh.b_lo, sh.b_hi})
-		if (q && ranges_overlap(p, n, q, sh.half)) return true;
-	if (sh.eq && ranges_overlap(p, n, sh.eq, sh.eq_len)) return true;
-	if (sh.eq_copy_dst && ranges_overlap(p, n, sh.eq_copy_dst, sh.eq_len / 2)) return true;
-	if (sh.S && ranges_overlap(p, n, sh.S, sh.S_cap)) return true;
-	return false;
-}
-
-bool pre_matches(const bn_ctx::precomp_state &pre, const bn_ctx::pending_fold &pf)
-{
-	if (!pre.valid || pre.consumed || pf.count != 2 || pf.scale_mask || 2 * pf.n != pre.m) return false;
-	auto is = [&](uint32_t i, int j) { return pf.src0[i] == pre.lo[j] && pf.x1[i] == pre.hi[j]; };
-	return (is(0, 0) && is(1, 1)) || (is(0, 1) && is(1, 0));
-}
-
-// ---- host tail (abi_kernels.cpp): the device catches up with the folds the host performed on its own copy
-// publish: the caller is a host read -- when the arrays are down to one element each, the answer is already here
-int host_tail_flush(bn_ctx *ctx, bool publish)
-{
-	bn_ctx::host_tail_state &ht = ctx->ht;
-	if (!ht.active) return BN_OK;
-	// (ht.active is cleared only once the write-back is enqueued: if the launch fails the host's folded copy is still the only
-	// up-to-date one, and every later call comes back here and reports the error again instead of reading stale arrays)
-	if (ht.n_levels) {
-		// the host copy's first n0 elements per array ARE the caller's buffers after the folds (the host folds in place exactly as
-		// the device would): into the pinned staging, then one launch maps them back to the tower basis and stores them
-		uint64_t *stg = (uint64_t *)ctx->h_tail + 2 * (2 * bn::kHtMaxM);
-		const uint32_t n0 = ht.chain.n0;
-		for (int j = 0; j < 2; j++) std::memcpy(stg + 2 * (size_t)n0 * j, ht.y[j].data(), (size_t)n0 * 16);
-		std::atomic_thread_fence(std::memory_order_seq_cst);
-		prof_scope ps(ctx, BN_PROF_FOLD);
-		BN_HIP(bn::launch_tail_writeback(ctx->stream, ht.chain, (const char *)ctx->d_tail + 2 * bn::kHtMaxM * sizeof(f128), (const char *)ctx->d_phi + 512 * sizeof(f128)));
-		ctx->ht_flushed++;
-	}
-	ht.active = false;
-	if (publish && ht.cur_m == 1 && !ht.evaluated && ht.n_levels) {
-		ctx->mirror.valid = true;
-		ctx->mirror.host = true;
-		ctx->mirror.seq = 0;
-		ctx->mirror.count = 2;
-		ctx->mirror.n = 1;
-		for (int j = 0; j < 2; j++) {
-			ctx->mirror.ptr[j] = ht.cur_lo[j];
-			ctx->mirror.host_vals[j] = bn::hostpoly_to_tower(bn::hp128{ht.y[j][0], ht.y[j][1]});
-		}
-	}
-	ht.n_levels = 0;
-	return BN_OK;
-}
-
-// The fold batch (src0 | x1 -> x0, n elements each) is the fold of the host tail's current arrays: performed on the host
-// copy, recorded for the device (true), or not the expected call (false: the caller flushes).
-bool host_tail_fold(bn_ctx *ctx, void *const *x0, const void *const *src0, const void *const *x1, uint32_t count, uint64_t n, uint32_t scale_mask, f128 z)
-{
-	bn_ctx::host_tail_state &ht = ctx->ht;
-	if (!ht.active || !ht.evaluated || ctx->pend.active || count != 2 || scale_mask || 2 * n != ht.cur_m) return false;
-	auto is = [&](uint32_t i, int j) { return src0[i] == ht.cur_lo[j] && x1[i] == ht.cur_hi[j]; };
-	int perm = -1;
-	if (is(0, 0) && is(1, 1)) perm = 0;
-	else if (is(0, 1) && is(1, 0)) perm = 1;
-	if (perm < 0 || x0[0] == x0[1]) return false;
-	// later folds are in place on the first fold's output (what the write-back of the host copy assumes)
-	if (ht.n_levels > 0)
-		for (uint32_t i = 0; i < 2; i++)
-			if (x0[i] != src0[i]) return false;
-	for (uint32_t i = 0; i < 2; i++) { // the output must not overlap what the batch reads of the OTHER array, nor x1 of its own
-		const uint32_t o = 1 - i;
-		if (ranges_overlap(x0[i], n, src0[o], n) || ranges_overlap(x0[i], n, x1[o], n) || ranges_overlap(x0[i], n, x1[i], n)) return false;
-		if (x0[i] != src0[i] && ranges_overlap(x0[i], n, src0[i], n)) return false;
-	}
-	if (ht.n_levels == 0) {
-		if (n > bn::kHtMaxM / 2) return false;
-		for (uint32_t i = 0; i < 2; i++) ht.chain.out[perm ? 1 - (int)i : (int)i] = x0[i];
-		ht.chain.n0 = (uint32_t)n;
-	}
-	ht.n_levels++;
-	const bn::hp128 pz = bn::hostpoly_from_tower(z);
-	for (int j = 0; j < 2; j++) bn::hostpoly_fold(reinterpret_cast<bn::hp128 *>(ht.y[j].data()), n, pz);
-	for (uint32_t i = 0; i < 2; i++) {
-		const int j = perm ? 1 - (int)i : (int)i;
-		ht.cur_lo[j] = x0[i];
-		ht.cur_hi[j] = (const char *)x0[i] + (n / 2) * sizeof(f128);
-	}
-	ht.cur_m = n;
-	ht.evaluated = false;
-	return true;
-}
-
-int flush_first_fold(bn_ctx *ctx)
-{
-	if (!ctx->pend.active || !ctx->pend2.active) return BN_OK;
-	arm_cancel(ctx); // (a kernel armed for the pair of folds cannot run half of it)
-	const bn_ctx::pending_fold &pf = ctx->pend;
-	bn::fold_batch fb{};
-	for (uint32_t i = 0; i < pf.count; i++) {
-		fb.x0[i] = pf.x0[i];
-		fb.x1[i] = pf.x1[i];
-		fb.src0[i] = pf.src0[i] != pf.x0[i] ? pf.src0[i] : nullptr;
-	}
-	{
-		prof_scope ps(ctx, BN_PROF_FOLD);
-		BN_HIP(bn::launch_extrapolate_line_batch(ctx->stream, ctx->n_cu, fb, pf.count, pf.n, pf.z));
-	}
-	ctx->pend = ctx->pend2; // (pend2 keeps its fields: callers may still hold a reference to them)
-	ctx->pend2.active = false;
-	ctx->pre.valid = false;
-	return BN_OK;
-}
-
 std::vector<unsigned char> recipe_bytes(const bn::fin_args &a)
 {
 	bn::fin_args r;
@@ -368,128 +235,6 @@ std::vector<unsigned char> recipe_bytes(const bn::fin_args &a)
 	return std::vector<unsigned char>(p, p + sizeof(r));
 }
 
-int flush_copies(bn_ctx *ctx)
-{
-	for (const auto &c : ctx->pend_copies)
-		BN_HIP(hipMemcpyAsync(c.dst, c.src, c.n * sizeof(f128), hipMemcpyDeviceToDevice, ctx->stream));
-	ctx->pend_copies.clear();
-	return BN_OK;
-}
-
-// everything deferred runs: the claim groups' folds (abi_group.cpp), then the single-claim state.  (The two sets of arrays are
-// disjoint -- a batch only joins either side while it is independent of everything waiting -- so the order is free.)
-int flush_pending(bn_ctx *ctx, bool keep_tail, bool publish_tiny, bool keep_shadow)
-{
-	{
-		// (also with nothing deferred: a hosted prover may be owed its write-back, sums computed ahead die)
-		const int rc = group_flush(ctx);
-		if (rc) return rc;
-	}
-	return flush_legacy(ctx, keep_tail, publish_tiny, keep_shadow);
-}
-
-int flush_legacy(bn_ctx *ctx, bool keep_tail, bool publish_tiny, bool keep_shadow)
-{
-	if (ctx->ht.active) {
-		int rc = host_tail_flush(ctx, publish_tiny);
-		if (rc) return rc;
-	}
-	if (!(keep_shadow && !ctx->pend.active)) side_join(ctx); // whatever follows may read what the side stream writes
-	if (ctx->tail.active && !keep_tail) {
-		int rc = tail_cancel(ctx);
-		if (rc) return rc;
-	}
-	if (!keep_tail) arm_cancel(ctx);
-	if (!ctx->pend_copies.empty()) {
-		int rc = flush_copies(ctx);
-		if (rc) return rc;
-	}
-	ctx->pre.valid = false; // the precomputed next-round sums die with any call that is not the one they were made for
-	// (keep_shadow: the end of a round evaluation that the shadow itself answered -- nothing is deferred any more;
-	// bn_extrapolate_line_batch restores the shadow when the batch is the fold it expects)
-	if (ctx->shadow.valid && !(keep_shadow && !ctx->pend.active)) {
-		BN_SHDBG("flush_pending: dropped (fold_pending=%d, pend.active=%d)", (int)ctx->shadow.fold_pending, (int)ctx->pend.active);
-		ctx->shadow.valid = false;
-		ctx->shadow.fold_pending = false;
-		ctx->shadow_dropped++;
-	}
-	if (!ctx->pend.active) return BN_OK;
-	ctx->pend.active = false;
-	if (ctx->pend2.active) {
-		// two folds were deferred (a round in between was answered from precomputed sums): in place, one after the other
-		// -- or, when the caller is a host read of a handful of elements, both in ONE launch that also mirrors the results
-		ctx->pend2.active = false;
-		const bn_ctx::pending_fold &p1 = ctx->pend, &p2 = ctx->pend2;
-		if (publish_tiny && (uint64_t)p2.count * p2.n <= 64 && !p1.scale_mask && !p2.scale_mask) {
-			const uint64_t seq = ++ctx->mail_seq;
-			prof_scope ps(ctx, BN_PROF_FOLD);
-			BN_HIP(bn::launch_fold2_publish(ctx->stream, p1.x0, p1.src0, p1.x1, p1.count, (uint32_t)p2.n, p1.z, p2.z, ctx->d_mail, seq));
-			ctx->mirror.valid = true;
-			ctx->mirror.host = false;
-			ctx->mirror.seq = seq;
-			ctx->mirror.count = p2.count;
-			ctx->mirror.n = (uint32_t)p2.n;
-			for (uint32_t i = 0; i < p2.count; i++) ctx->mirror.ptr[i] = p2.x0[i];
-			// the arrays are the four elements the last two-round launch published: the same two folds on the host (the kernel
-			// above still runs -- the caller's memory ends up as always --, nobody waits for it)
-			bn_ctx::final_y_state &fy = ctx->fin_y;
-			if (fy.valid && p1.count == 2 && p1.n == 2 && p2.n == 1) {
-				bool same = true;
-				for (uint32_t i = 0; i < 2 && same; i++)
-					same = p1.x0[i] == fy.lo[i] && p1.src0[i] == fy.lo[i] && (const char *)p1.x1[i] == (const char *)fy.lo[i] + 2 * sizeof(f128) && p2.x0[i] == fy.lo[i] &&
-					       (const char *)p2.x1[i] == (const char *)fy.lo[i] + sizeof(f128);
-				if (same) {
-					for (uint32_t i = 0; i < 2; i++) {
-						const f128 *y = fy.y[i];
-						const f128 u = y[0] ^ bn::mul_host(p1.z, y[0] ^ y[2]), v = y[1] ^ bn::mul_host(p1.z, y[1] ^ y[3]);
-						ctx->mirror.host_vals[i] = u ^ bn::mul_host(p2.z, u ^ v);
-					}
-					ctx->mirror.host = true;
-				}
-			}
-			fy.valid = false;
-			return BN_OK;
-		}
-		for (int k = 0; k < 2; k++) {
-			const bn_ctx::pending_fold &pf = k ? p2 : p1;
-			bn::fold_batch fb{};
-			for (uint32_t i = 0; i < pf.count; i++) {
-				fb.x0[i] = pf.x0[i];
-				fb.x1[i] = pf.x1[i];
-				fb.src0[i] = pf.src0[i] != pf.x0[i] ? pf.src0[i] : nullptr; // (absorbed copy: read there, write here)
-			}
-			prof_scope ps(ctx, BN_PROF_FOLD);
-			BN_HIP(bn::launch_extrapolate_line_batch(ctx->stream, ctx->n_cu, fb, pf.count, pf.n, pf.z));
-		}
-		return BN_OK;
-	}
-	if (publish_tiny && (uint64_t)ctx->pend.count * ctx->pend.n <= 64) {
-		// the caller is a host read: fold and mirror the (few) results into the mailbox in one launch
-		const uint64_t seq = ++ctx->mail_seq;
-		prof_scope ps(ctx, BN_PROF_FOLD);
-		BN_HIP(bn::launch_fold_publish(ctx->stream, ctx->pend.x0, ctx->pend.src0, ctx->pend.x1, ctx->pend.count, (uint32_t)ctx->pend.n,
-		                               ctx->pend.z, ctx->d_mail, seq, ctx->pend.scale_mask, ctx->pend.hi_scale));
-		ctx->mirror.valid = true;
-		ctx->mirror.host = false;
-		ctx->mirror.seq = seq;
-		ctx->mirror.count = ctx->pend.count;
-		ctx->mirror.n = (uint32_t)ctx->pend.n;
-		for (uint32_t i = 0; i < ctx->pend.count; i++) ctx->mirror.ptr[i] = ctx->pend.x0[i];
-		return BN_OK;
-	}
-	bn::fold_batch fb{};
-	for (uint32_t i = 0; i < ctx->pend.count; i++) {
-		fb.x0[i] = ctx->pend.x0[i];
-		fb.x1[i] = ctx->pend.x1[i];
-		fb.src0[i] = ctx->pend.src0[i] != ctx->pend.x0[i] ? ctx->pend.src0[i] : nullptr; // absorbed copy: read there, write here
-	}
-	prof_scope ps(ctx, BN_PROF_FOLD);
-	BN_HIP(bn::launch_extrapolate_line_batch(ctx->stream, ctx->n_cu, fb, ctx->pend.count, ctx->pend.n, ctx->pend.z));
-	for (uint32_t i = 0; i < ctx->pend.count; i++)
-		if ((ctx->pend.scale_mask >> i) & 1)
-			BN_HIP(bn::launch_scale(ctx->stream, ctx->n_cu, (char *)ctx->pend.x0[i] + (ctx->pend.n / 2) * sizeof(f128), ctx->pend.n / 2, ctx->pend.hi_scale));
-	return BN_OK;
-}
 // Waits for the sequence word the publishing kernel writes after its values (fine-grained host memory): a bounded spin, then a
 // stream synchronisation so that device errors surface instead of hanging.  cancel_armed: an armed kernel queued behind the
 // launch would sit out its whole timeout inside that synchronisation -- it is told to leave first.
@@ -1174,233 +919,6 @@ int bn_expr_n_vars(const bn_expr *expr, uint32_t *n_vars)
 {
 	BN_REQUIRE(expr && n_vars, "null argument");
 	*n_vars = expr->n_vars;
-	return BN_OK;
-}
-
-// ---------------------------------------------------------------------------------- executor ops
-int bn_extrapolate_line(bn_ctx *ctx, void *d_evals_0, uint64_t n0, const void *d_evals_1, uint64_t n1, const bn_f128 *z)
-{
-	BN_REQUIRE(ctx && z, "null argument");
-	BN_ENTER(ctx);
-	BN_FLUSH(ctx);
-	BN_REQUIRE(n0 == n1, "evals_0 and evals_1 must be the same length");
-	prof_scope ps(ctx, BN_PROF_FOLD);
-	BN_HIP(bn::launch_extrapolate_line(ctx->stream, ctx->n_cu, d_evals_0, d_evals_1, n0, to_f(z)));
-	return BN_OK;
-}
-
-int bn_extrapolate_line_batch(bn_ctx *ctx, void *const *d_evals_0, const void *const *d_evals_1, uint32_t count, uint64_t n,
-                              const bn_f128 *z)
-{
-	return bn_extrapolate_line_batch_scaled(ctx, d_evals_0, d_evals_1, count, n, z, 0, nullptr);
-}
-
-int bn_extrapolate_line_batch_scaled(bn_ctx *ctx, void *const *d_evals_0, const void *const *d_evals_1, uint32_t count, uint64_t n,
-                                     const bn_f128 *z, uint32_t scale_mask, const bn_f128 *hi_scale)
-{
-	BN_REQUIRE(ctx && z && d_evals_0 && d_evals_1, "null argument");
-	BN_ENTER(ctx);
-	BN_REQUIRE(count <= (uint32_t)bn::kFoldCallMax, "too many slices in one extrapolate_line batch");
-	BN_REQUIRE(scale_mask == 0 || (hi_scale && (n & 1) == 0 && count <= 32 && (count >= 32 || (scale_mask >> count) == 0)),
-	           "scaled fold: needs a scale, an even length and a mask within the batch (at most 32 slices)");
-	if (count == 0) return BN_OK;
-	ctx->mirror.valid = false;
-	// A batch wider than one launch's (a prover with more than kFoldBatchMax multilinears, piop/prove.rs:262-287) is the claim
-	// groups' (abi_group.cpp: deferred whole, folded by the jobs of the next evaluation's launch); where they do not apply it is
-	// the same folds in pieces of kFoldBatchMax, each through the machinery below.
-	if (count > (uint32_t)bn::kFoldBatchMax && !group_fold_applies(ctx, count, scale_mask)) {
-		for (uint32_t at = 0; at < count; at += (uint32_t)bn::kFoldBatchMax) {
-			const uint32_t c = count - at < (uint32_t)bn::kFoldBatchMax ? count - at : (uint32_t)bn::kFoldBatchMax;
-			const int rc_p = bn_extrapolate_line_batch_scaled(ctx, d_evals_0 + at, d_evals_1 + at, c, n, z, 0, nullptr);
-			if (rc_p) return rc_p;
-		}
-		return BN_OK;
-	}
-	// A fold is already deferred, the round evaluation of its output has just been answered from the precomputed sums of
-	// a two-round launch (abi_kernels.cpp), and this batch folds that output in place: keep BOTH -- the next round
-	// evaluation folds twice in one pass (kernels_foldeval8.hip).
-	if (ctx->pend.active && !ctx->pend2.active && ctx->pre.valid && ctx->pre.consumed && ctx->lazy_fold && count == 2 && ctx->pend.count == 2 &&
-	    scale_mask == 0 && ctx->pend.scale_mask == 0 && 2 * n == ctx->pend.n && ctx->pend_copies.empty()) {
-		bool chained = true;
-		for (uint32_t i = 0; i < 2 && chained; i++)
-			chained = d_evals_0[i] == ctx->pend.x0[i] && (const char *)d_evals_1[i] == (const char *)ctx->pend.x0[i] + n * sizeof(f128);
-		if (chained) {
-			bn_ctx::pending_fold &p2 = ctx->pend2;
-			p2.active = true;
-			p2.count = 2;
-			p2.n = n;
-			p2.z = to_f(z);
-			p2.scale_mask = 0;
-			p2.hi_scale = f128{0, 0};
-			for (uint32_t i = 0; i < 2; i++) {
-				p2.x0[i] = d_evals_0[i];
-				p2.x1[i] = d_evals_1[i];
-				p2.src0[i] = d_evals_0[i];
-			}
-			return BN_OK; // (an armed two-round kernel keeps waiting: it is armed for exactly this pair of folds)
-		}
-	}
-	// deferred copies whose destination is one of the evals_0 are absorbed (every one of them must
-	// be, otherwise they all run now, in issue order)
-	const void *src0[bn::kFoldCallMax];
-	for (uint32_t i = 0; i < count; i++) src0[i] = d_evals_0[i];
-	if (!ctx->pend_copies.empty() && !ctx->pend.active) {
-		size_t absorbed = 0;
-		for (const auto &c : ctx->pend_copies)
-			for (uint32_t i = 0; i < count; i++)
-				if (c.dst == d_evals_0[i] && c.n == n && src0[i] == d_evals_0[i]) {
-					src0[i] = c.src;
-					absorbed++;
-					break;
-				}
-		// an absorbed copy is read while the fold writes: its source must not overlap any array the
-		// batch writes (e.g. a copy chain s -> d1 -> d2 followed by a fold of both)
-		bool clash = false;
-		auto overlaps = [&](const void *p, const void *q) {
-			const char *a = (const char *)p, *b = (const char *)q;
-			return a < b + n * sizeof(f128) && b < a + n * sizeof(f128);
-		};
-		for (uint32_t i = 0; i < count && !clash; i++)
-			if (src0[i] != d_evals_0[i])
-				for (uint32_t j = 0; j < count; j++)
-					if (overlaps(src0[i], d_evals_0[j])) clash = true;
-		if (absorbed == ctx->pend_copies.size() && !clash) {
-			ctx->pend_copies.clear();
-		} else {
-			for (uint32_t i = 0; i < count; i++) src0[i] = d_evals_0[i];
-		}
-	}
-	// ---- claim groups (abi_group.cpp): a batch that is not the lone two-array shape of the single-claim machinery -- more than
-	// two arrays, other batches already waiting, or a second prover's batch arriving while the first one's is deferred -- waits
-	// beside the others; the next evaluations pick their folds up in one launch
-	{
-		bool to_group = group_fold_applies(ctx, count, scale_mask);
-		if (!to_group && ctx->grp.enabled && ctx->lazy_fold && !ctx->peer.active && !scale_mask && !ctx->tail_max_n_in && ctx->pend.active && !ctx->pend2.active &&
-		    !ctx->pend.scale_mask && !ctx->ht.active && !ctx->tail.active && !ctx->shadow.valid) {
-			bool indep = true;
-			for (uint32_t i = 0; i < count && indep; i++)
-				indep = independent_of_pending(ctx, d_evals_0[i], n) && independent_of_pending(ctx, d_evals_1[i], n) && independent_of_pending(ctx, src0[i], n);
-			to_group = indep;
-		}
-		if (to_group) {
-			if (!ctx->pend_copies.empty()) { // (copies the batch did not absorb: issued before it, they run before it)
-				int rc_c = flush_copies(ctx);
-				if (rc_c) return rc_c;
-			}
-			return group_defer_fold(ctx, d_evals_0, src0, d_evals_1, count, n, to_f(z));
-		}
-	}
-	if (ctx->ht.active) {
-		// (deferred copies the batch did not absorb -- possible only while the device is still in step with the host copy --
-		// were issued BEFORE this fold and may read what its write-back will overwrite: they run now, in issue order)
-		if (!ctx->pend_copies.empty()) {
-			int rc_c = flush_copies(ctx);
-			if (rc_c) return rc_c;
-		}
-		if (host_tail_fold(ctx, d_evals_0, src0, d_evals_1, count, n, scale_mask, to_f(z)))
-			return BN_OK; // (performed on the host's copy; the device catches up in one launch, host_tail_flush)
-	}
-	{
-		// a resident tail kernel survives this call only if the batch is the fold it is parked for
-		bool keep_tail = false;
-		if (ctx->tail.active && count == 2 && 2 * n == ctx->tail.n_in_next) {
-			auto continues = [&](uint32_t i, uint32_t j) {
-				return d_evals_0[i] == ctx->tail.out[j] && src0[i] == d_evals_0[i] &&
-				       (const char *)d_evals_1[i] == (const char *)d_evals_0[i] + n * sizeof(f128);
-			};
-			keep_tail = (continues(0, 0) && continues(1, 1)) || (continues(0, 1) && continues(1, 0));
-		}
-		// ... and so does an armed round (same order of the two arrays, same scale mask; z and the scale are its input)
-		if (ctx->arm.active) {
-			const bn_ctx::arm_state &am = ctx->arm;
-			// (a two-fold kernel is armed for the pair pend + pend2: this batch would be its FIRST fold)
-			bool same = count == 2 && 2 * n == am.n_in && scale_mask == am.scale_mask && !ctx->pend.active;
-			for (uint32_t j = 0; j < 2 && same; j++)
-				same = d_evals_0[j] == am.out[j] && src0[j] == am.x0[j] && d_evals_1[j] == am.x1[j];
-			if (same)
-				keep_tail = true;
-			else
-				arm_cancel(ctx);
-		}
-		// the next-round sums of a two-round launch survive exactly one call: the fold of the arrays they describe
-		bn_ctx::pending_fold probe;
-		probe.count = count;
-		probe.n = n;
-		probe.scale_mask = scale_mask;
-		for (uint32_t i = 0; i < count; i++) {
-			probe.src0[i] = src0[i];
-			probe.x1[i] = d_evals_1[i];
-		}
-		// (deferred copies that were not absorbed run inside flush_pending and may write the very arrays the sums describe)
-		const bool keep_pre = !ctx->pend.active && ctx->lazy_fold && ctx->pend_copies.empty() && pre_matches(ctx->pre, probe);
-		if (!keep_pre) ctx->fin_y.valid = false; // (Y's four elements describe the arrays the sums describe)
-		// ... and the weighted shadow of an MLE-check (abi_kernels.cpp) survives the fold of exactly its two arrays
-		bn_ctx::shadow_state &sh = ctx->shadow;
-		int sh_ia = -1;
-		if (sh.valid && !sh.fold_pending && !ctx->pend.active && ctx->lazy_fold && count == 2 && scale_mask == 0 && n == sh.half) {
-			auto is = [&](uint32_t i, const void *lo, const void *hi) { return src0[i] == lo && d_evals_1[i] == hi; };
-			if (is(0, sh.a_lo, sh.a_hi) && is(1, sh.b_lo, sh.b_hi)) sh_ia = 0;
-			else if (is(1, sh.a_lo, sh.a_hi) && is(0, sh.b_lo, sh.b_hi)) sh_ia = 1;
-		}
-		// (deferred copies that the batch did not absorb run inside flush_pending, on the main stream and in issue order: they
-		// may write what the shadow describes or race the side stream's fold of b -- the shadow does not survive them)
-		if (sh_ia >= 0 && !ctx->pend_copies.empty()) sh_ia = -1;
-		if (sh_ia >= 0 && !sh.checked && n >= 2) {
-			// the caller goes on with this instance: is its table a tensor expansion (what the later rounds rely on)?
-			bool ok = false;
-			int rc_c = shadow_check_table(ctx, &ok);
-			if (rc_c) return rc_c;
-			if (!ok) {
-				sh_ia = -1; // (no: the shadow ends with the flush below and the literal kernels answer from here on)
-				sh.blocked_below = sh.half;
-			}
-		}
-		if (sh.valid)
-			BN_SHDBG("fold batch: count=%u n=%llu half=%llu pend=%d fp=%d match=%d (src0 %p %p x1 %p %p | a %p %p b %p %p)", count, (unsigned long long)n,
-			         (unsigned long long)sh.half, (int)ctx->pend.active, (int)sh.fold_pending, sh_ia, src0[0], count > 1 ? src0[1] : nullptr, d_evals_1[0],
-			         count > 1 ? d_evals_1[1] : nullptr, sh.a_lo, sh.a_hi, sh.b_lo, sh.b_hi);
-		// (the shadow's own fold: nothing is deferred, the shadow stays and the side stream is not joined -- its work, the folds
-		// of b and of the table, depends on nothing the main stream does in between)
-		int rc_ = flush_pending(ctx, keep_tail, false, /*keep_shadow=*/sh_ia >= 0);
-		if (rc_) return rc_;
-		ctx->pre.valid = keep_pre;
-		if (sh_ia >= 0) {
-			if (n < 2) { // the fold to one element: nothing is evaluated after it, the shadow has done its work
-				sh.valid = false;
-				side_join(ctx);
-			}
-			if (n >= 2) {
-				// the folded arrays (n elements) split next round by the variable of bit log2(n) - 1 of the table's index
-				const uint32_t kvar = ilog2(n) - 1;
-				sh.valid = true;
-				sh.fold_pending = true;
-				sh.z = to_f(z);
-				sh.ia = (uint32_t)sh_ia;
-				sh.ib = 1 - sh.ia;
-				sh.hi_scale = sh.rho_inv[kvar];
-				sh.lambda_next = bn::mul_host(sh.lambda, sh.one_minus_zeta[kvar]);
-				sh.a_lo = d_evals_0[sh.ia];
-				sh.a_hi = (const char *)d_evals_0[sh.ia] + (n / 2) * sizeof(f128);
-				sh.b_lo = d_evals_0[sh.ib];
-				sh.b_hi = (const char *)d_evals_0[sh.ib] + (n / 2) * sizeof(f128);
-				sh.half = n / 2;
-			} // else: the fold to one element -- nothing is evaluated after it, the shadow has done its work
-		}
-	}
-	// Deferred: the next API call launches it -- or, if that call is the round evaluation of exactly
-	// these arrays, both run as one kernel (kernels_foldeval9.hip).
-	ctx->pend.active = true;
-	ctx->pend.count = count;
-	ctx->pend.n = n;
-	ctx->pend.z = to_f(z);
-	ctx->pend.scale_mask = scale_mask;
-	ctx->pend.hi_scale = scale_mask ? to_f(hi_scale) : f128{0, 0};
-	for (uint32_t i = 0; i < count; i++) {
-		ctx->pend.x0[i] = d_evals_0[i];
-		ctx->pend.x1[i] = d_evals_1[i];
-		ctx->pend.src0[i] = src0[i];
-	}
-	if (!ctx->lazy_fold) BN_FLUSH(ctx);
 	return BN_OK;
 }
 

@@ -1,5 +1,5 @@
 // binius_amd/csrc/abi_common.hpp -- pieces shared by the translation units of the extern "C" boundary
-// (abi.cpp: context, copies, deferral; abi_kernels.cpp: the recorded-kernel dispatcher; abi_ops.cpp: the
+// (abi.cpp: context, copies; abi_fold.cpp: the fold entry points and the single-claim deferral; abi_kernels.cpp: the recorded-kernel dispatcher; abi_ops.cpp: the
 // executor ops, Merkle and NTT entry points; the batched ops -- abi_prodtree.cpp, abi_expcircuit.cpp, abi_partial_eval.cpp,
 // abi_flush.cpp, abi_univariate_fold.cpp, abi_ring_switch.cpp, abi_mle_eval.cpp, abi_univariate.cpp, abi_partial_eval_lincomb.cpp, abi_merge.cpp, abi_fri_query.cpp, abi_derive.cpp, abi_generate.cpp -- use the helpers and call_upload at the end).  Not part of the
 // public interface.
@@ -70,7 +70,7 @@ inline bool shadow_debug()
 	} while (0)
 
 namespace bnabi {
-// ---- deferral machinery (defined in abi.cpp)
+// ---- deferral machinery (the single-claim deferred fold: abi_fold.cpp; side stream, tail / arm cancel, shadow table check: abi.cpp)
 int flush_copies(bn_ctx *ctx);
 int flush_pending(bn_ctx *ctx, bool keep_tail = false, bool publish_tiny = false, bool keep_shadow = false);
 int tail_cancel(bn_ctx *ctx);
@@ -90,6 +90,8 @@ int side_run_queue(bn_ctx *ctx);
 void side_join(bn_ctx *ctx);
 bool ranges_overlap(const void *p, uint64_t n_p, const void *q, uint64_t n_q);
 bool independent_of_pending(bn_ctx *ctx, const void *p, uint64_t n);
+// [p, p + n) overlaps an array the MLE-check shadow describes
+bool shadow_touched_by_write(bn_ctx *ctx, const void *p, uint64_t n);
 // the MLE-check shadow's table: read eq[0], eq[2^k] to the host, derive the ratios rho_k, check the whole table against them
 // (one gather + one pass + two stream synchronisations); false: not a tensor expansion (or a coordinate 0 / 1)
 int shadow_check_table(bn_ctx *ctx, bool *ok);
@@ -117,6 +119,9 @@ int circuit_multipass_sum(bn_ctx *ctx, const bn_expr *e, const void *const *rows
 int flush_legacy(bn_ctx *ctx, bool keep_tail = false, bool publish_tiny = false, bool keep_shadow = false);
 // is any of that state alive?
 bool legacy_state_active(const bn_ctx *ctx);
+// that state is nothing but a plain deferred fold: one unscaled batch in ctx->pend -- no second chained fold, no host tail, no
+// resident kernel (what a site needs to know about the shadow it adds itself)
+bool plain_fold_deferred(const bn_ctx *ctx);
 // the pinned tables / accumulator slots / value mailbox of the group kernel's launches (allocated on first use)
 int group_res_alloc(bn_ctx *ctx);
 // a batch of folds can be deferred on the group path

@@ -7,7 +7,7 @@
 //     execute(P_1) .. execute(P_p)  |  challenge  |  fold(P_1) .. fold(P_p)  |  (FRI: nothing, or fri_fold + commit)  |  execute(P_1) ..
 //
 // and each execute records  SUM(c_0, at 1) .. SUM(c_{k-1}, at 1), ADD x m, SUM(c_0, at inf) .. SUM(c_{k-1}, at inf)
-// (protocols/sumcheck/v3/bivariate_product.rs:345-399).  The single-claim machinery of abi.cpp / abi_kernels.cpp (ONE deferred
+// (protocols/sumcheck/v3/bivariate_product.rs:345-399).  The single-claim machinery of abi_fold.cpp / abi_kernels.cpp (ONE deferred
 // fold per context, two arrays, one claim) drops every one of these to eager launches.  Here
 //
 //   * a fold batch is deferred PER PROVER: any number of batches wait side by side as long as their arrays are disjoint
@@ -755,12 +755,17 @@ bool legacy_state_active(const bn_ctx *ctx)
 	       ctx->side_busy || !ctx->side_queue.empty();
 }
 
+bool plain_fold_deferred(const bn_ctx *ctx)
+{
+	return ctx->pend.active && !ctx->pend2.active && !ctx->pend.scale_mask && !ctx->ht.active && !ctx->tail.active;
+}
+
 bool group_fold_applies(const bn_ctx *ctx, uint32_t count, uint32_t scale_mask)
 {
 	const auto &g = ctx->grp;
 	if (!g.enabled || !ctx->lazy_fold || ctx->peer.active || scale_mask || ctx->tail_max_n_in || count == 0 || count > kMaxArrays) return false;
 	// (a lone batch of two arrays with nothing else waiting is the single-claim shape: the armed / two-round / host-tail machinery
-	// of abi.cpp keeps it)
+	// of abi_fold.cpp keeps it)
 	return g.on || !g.folds.empty() || count != 2;
 }
 
@@ -898,8 +903,7 @@ static int legacy_to_group(bn_ctx *ctx)
 	if (!legacy_state_active(ctx)) return BN_OK;
 	bn_ctx::group_fold moved;
 	bool have = false;
-	if (ctx->pend.active && !ctx->pend2.active && !ctx->pend.scale_mask && !ctx->ht.active && !ctx->tail.active && !(ctx->shadow.valid && ctx->shadow.fold_pending) &&
-	    ctx->pend.count <= kMaxArrays) {
+	if (plain_fold_deferred(ctx) && !(ctx->shadow.valid && ctx->shadow.fold_pending) && ctx->pend.count <= kMaxArrays) {
 		const auto &pf = ctx->pend;
 		moved.n = pf.n;
 		moved.z = pf.z;

@@ -103,7 +103,7 @@ struct bn_ctx {
 	};
 	std::vector<prof_rec> prof;
 	std::vector<hipEvent_t> ev_pool;
-	// deferred extrapolate_line batch (abi.cpp): launched by the next API call, or folded into the
+	// deferred extrapolate_line batch (abi_fold.cpp): launched by the next API call, or folded into the
 	// next round-evaluation launch when that launch reads exactly the folded arrays
 	struct pending_fold {
 		bool active = false;
