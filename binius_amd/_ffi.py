@@ -268,6 +268,7 @@ def lib():
         "bn_fri_counters": [vp, C.POINTER(u64)],
         "bn_fold_counters": [vp, C.POINTER(u64)],
         "bn_inner_product_counters": [vp, C.POINTER(u64)],
+        "bn_hal_counters": [vp, C.POINTER(u64)],
         "bn_xor_reduce": [vp, vp, u32, u32, PF],
         "bn_host_scratch": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)],
         "bn_device_numa_node": [C.c_int, C.POINTER(C.c_int)],
@@ -301,7 +302,7 @@ ABI_SYMBOLS = [
     "bn_extrapolate_line", "bn_extrapolate_line_batch", "bn_tensor_expand", "bn_inner_product", "bn_fold_left", "bn_fold_right", "bn_fri_fold",
     "bn_compute_composite", "bn_pairwise_product_reduce", "bn_log_chunks_range", "bn_pick_log_chunks",
     "bn_kernel_launch", "bn_ntt_forward", "bn_ntt_inverse", "bn_ntt_s_evals", "bn_scalar_mul", "bn_scalar_invert",
-    "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_ntt_counters", "bn_fri_counters", "bn_fold_counters", "bn_inner_product_counters", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
+    "bn_timer_begin", "bn_timer_end_ms", "bn_prof_begin", "bn_prof_end", "bn_arm_counters", "bn_group_counters", "bn_fp4_last_grids", "bn_ntt_counters", "bn_fri_counters", "bn_fold_counters", "bn_inner_product_counters", "bn_hal_counters", "bn_xor_reduce", "bn_host_scratch", "bn_device_numa_node",
     "bn_merkle_build", "bn_groestl256_leaves", "bn_groestl256_compress_layer", "bn_gather_d2h",
     "bn_hal_round_evals", "bn_hal_fold_multilinear", "bn_extrapolate_line_batch_scaled", "bn_zerocheck_univariate_evals", "bn_zerocheck_univariate_evals_base",
     "bn_product_tree_layers", "bn_pad_with_ones", "bn_exp_circuit_layers", "bn_bits_to_b128", "bn_exp_counters",
@@ -714,6 +715,21 @@ class Context:
         c = (C.c_uint64 * 4)()
         _check(lib().bn_inner_product_counters(self._h, c))
         return {k: int(c[i]) for i, k in enumerate(("mfma_split", "split9", "ip32", "scalar"))}
+
+    HAL_COUNTERS = ("coef", "eq_set", "in_parts", "monomials", "rows_batched", "rows_per_point", "interpreter", "mono_strided", "mono_product2",
+                    "mono_product3", "mono_xor_sum", "mono_const", "rows_launches", "rows_written", "rows_in_place", "transparent", "n_cu")
+
+    def hal_counters(self):
+        """Which route answered the bn_hal_round_evals calls of this context (bn_hal_counters): every request answered with BN_OK that
+        asked for a value counts in exactly one of coef / eq_set / in_parts / monomials / rows_batched / rows_per_point / interpreter (the
+        parts of a request counted under in_parts come back through the entry point and count again, under their own routes).  mono_*:
+        the monomial route's jobs by kind (the strided matrix-core launch of Low-to-High pairs, the product-sum kernels over two / three
+        factors, launches of the lone column's streaming sum, constants skipped); rows_launches / rows_written / rows_in_place: launches
+        of the rows kernel, the rows they wrote, the halves read where they lie; transparent: multilinears partially evaluated into
+        scratch; n_cu: the compute units of the device.  A call that returns an error moves nothing."""
+        c = (C.c_uint64 * len(self.HAL_COUNTERS))()
+        _check(lib().bn_hal_counters(self._h, c))
+        return {k: int(c[i]) for i, k in enumerate(self.HAL_COUNTERS)}
 
     # ---- ComputeLayer
     def copy_h2d(self, src, dst):

@@ -1005,6 +1005,8 @@ struct hal_request {
 	bool all_full = true;
 	acc_scope acc;
 	f128 *d_acc = nullptr;
+	// what this request adds to bn_hal_counters once it has been answered with BN_OK (answered_by)
+	uint64_t cnt[BN_HALCNT_N] = {};
 
 	bool l2h() const { return order == BN_ORDER_LOW_TO_HIGH; }
 	size_t rows_off() const { return tr_elems * sizeof(f128); }
@@ -1020,12 +1022,28 @@ routed route_coef(hal_request &r)
 	return rc == kCoefDeclined ? routed::decline() : routed::answer(rc);
 }
 
-// more than one pass of the general code carries
-bool is_wide(const hal_request &r)
+// the values the evaluators ask for (before validate_evaluators: an inverted range asks for none)
+uint32_t values_asked(const hal_request &r)
 {
 	uint32_t pts = 0;
 	for (uint32_t e = 0; e < r.n_evs; e++) pts += r.evs[e].eval_point_end > r.evs[e].eval_point_start ? r.evs[e].eval_point_end - r.evs[e].eval_point_start : 0;
-	return r.n_mls > (uint32_t)bn::kHalMaxMl || r.n_evs > (uint32_t)bn::kHalMaxEv || pts > 32;
+	return pts;
+}
+
+// The request has been answered by `route` with `rc`: BN_OK moves the route's counter and what the route noted on its way
+// (bn_hal_counters); an error, or a request that asked for no value, moves nothing.
+int answered_by(hal_request &r, int route, int rc)
+{
+	if (rc != BN_OK || values_asked(r) == 0) return rc;
+	r.cnt[route] += 1;
+	for (int i = 0; i < BN_HALCNT_N; i++) r.ctx->hal_calls[i] += r.cnt[i];
+	return rc;
+}
+
+// more than one pass of the general code carries
+bool is_wide(const hal_request &r)
+{
+	return r.n_mls > (uint32_t)bn::kHalMaxMl || r.n_evs > (uint32_t)bn::kHalMaxEv || values_asked(r) > 32;
 }
 
 // a constraint set's two launches: a wide request, or any request under an indicator
@@ -1117,6 +1135,7 @@ int resolve_multilinears(hal_request &r)
 			void *dst = r.scr + (size_t)t++ * r.full * sizeof(f128);
 			int rc = materialise(ctx, r.order, r.n_vars, r.mls[k], r.d_tensor_query, r.query_vars, one, dst);
 			if (rc) return rc;
+			r.cnt[BN_HALCNT_TRANSPARENT] += 1;
 			a.ml[k].evals = (const uint4 *)dst;
 			a.ml[k].len = r.full;
 			a.ml[k].suffix = bn::f128_zero();
@@ -1181,8 +1200,12 @@ int launch_monomial(hal_request &r, const term_job &job, const char *ones, const
 	bn_ctx *ctx = r.ctx;
 	const uint64_t half = r.half;
 	const bool l2h = r.l2h();
-	if (job.vars.empty() && !job.eq) return BN_OK; // constant monomial: both sums are zero (the slots are)
+	if (job.vars.empty() && !job.eq) { // constant monomial: both sums are zero (the slots are)
+		r.cnt[BN_HALCNT_MONO_CONST] += 1;
+		return BN_OK;
+	}
 	if (!l2h && !job.eq && job.vars.size() == 1 && half >= ((uint64_t)1 << 18)) {
+		r.cnt[BN_HALCNT_MONO_XOR_SUM] += job.at_inf ? 3 : 1; // (launches)
 		// a lone column: its sums at streaming speed (k_xor_sum) -- as a product with the all-ones table it is a pass over twice
 		// the bytes, and over its lower half even where no form at infinity holds it (a b + c at n = 24: 0.31 -> 0.2 ms)
 		const char *p = (const char *)r.a.ml[job.vars[0]].evals;
@@ -1207,6 +1230,7 @@ int launch_monomial(hal_request &r, const term_job &job, const char *ones, const
 	if (k == 2)
 		for (uint32_t f = 0; f < 2; f++)
 			if (!lo[f]) lo[f] = zeros;
+	r.cnt[l2h ? BN_HALCNT_MONO_STRIDED : k == 2 ? BN_HALCNT_MONO_PRODUCT2 : BN_HALCNT_MONO_PRODUCT3] += 1;
 	if (l2h)
 		BN_HIP(bn::launch_roundeval_mfma_pair_strided(ctx->stream, ctx->n_cu, hi[0], lo[0], shift[0], hi[1], lo[1], shift[1], half, d_out));
 	else
@@ -1286,7 +1310,11 @@ int build_rows(hal_request &r, row_table &row)
 	ra.half = half;
 	ra.n_out = half;
 	auto flush_rows = [&]() -> int {
-		if (ra.n_jobs) BN_HIP(bn::launch_hal_rows(ctx->stream, ctx->n_cu, ra));
+		if (ra.n_jobs) {
+			BN_HIP(bn::launch_hal_rows(ctx->stream, ctx->n_cu, ra));
+			r.cnt[BN_HALCNT_ROWS_LAUNCHES] += 1;
+			r.cnt[BN_HALCNT_ROWS_WRITTEN] += ra.n_jobs;
+		}
 		ra.n_jobs = 0;
 		return BN_OK;
 	};
@@ -1300,6 +1328,7 @@ int build_rows(hal_request &r, row_table &row)
 			char *dst = rows_base + ((size_t)ku * n_pts + pos_of(p)) * half * sizeof(f128);
 			if (!r.batch_points && !r.l2h() && r.a.ml[k].len == r.full && p <= 1) {
 				row[p][k] = (const char *)r.a.ml[k].evals + (p ? half * 16 : 0); // the half itself
+				r.cnt[BN_HALCNT_ROWS_IN_PLACE] += 1;
 				continue;
 			}
 			// (all the rows of the request in one launch, kernels_hal.hip k_hal_rows)
@@ -1437,11 +1466,12 @@ int bn_hal_round_evals(bn_ctx *ctx, uint32_t order, uint32_t n_vars, const void 
 	r.d_acc = ctx->d_result;
 	// ---- the paths that take a whole request, wide ones included; they decline on input they do not know -- the checks come after
 	routed res = route_coef(r);
-	if (res.kind != routed::declined) return res.rc;
+	if (res.kind != routed::declined) return answered_by(r, BN_HALCNT_COEF, res.rc);
 	const bool wide = is_wide(r);
 	res = route_eq_set(r, wide);
-	if (res.kind == routed::declined) res = route_in_parts(r, wide);
-	if (res.kind != routed::declined) return res.rc;
+	if (res.kind != routed::declined) return answered_by(r, BN_HALCNT_EQ_SET, res.rc);
+	res = route_in_parts(r, wide);
+	if (res.kind != routed::declined) return answered_by(r, BN_HALCNT_IN_PARTS, res.rc);
 	// ---- one pass of the general code
 	int rc = validate_evaluators(evs, n_evs, n_mls, h_points, n_points, /*one_pass=*/true, r.pts);
 	if (rc) return rc;
@@ -1454,14 +1484,26 @@ int bn_hal_round_evals(bn_ctx *ctx, uint32_t order, uint32_t n_vars, const void 
 	if (rc) return rc;
 	rc = r.acc.begin();
 	if (rc) return rc;
-	res = route_monomials(r);
-	if (res.kind == routed::declined) res = route_rows_batched(r);
-	if (res.kind == routed::declined) res = route_rows_per_point(r);
-	if (res.kind == routed::declined) res = route_interpreter(r);
-	if (res.kind != routed::launched) return res.rc;
+	routed (*const routes[])(hal_request &) = {route_monomials, route_rows_batched, route_rows_per_point, route_interpreter};
+	static_assert(BN_HALCNT_ROWS_BATCHED == BN_HALCNT_MONOMIALS + 1 && BN_HALCNT_ROWS_PER_POINT == BN_HALCNT_MONOMIALS + 2 &&
+	                  BN_HALCNT_INTERPRETER == BN_HALCNT_MONOMIALS + 3,
+	              "the counters of the four routes follow each other in the order the routes are tried");
+	int route = BN_HALCNT_MONOMIALS;
+	res = routes[0](r);
+	while (res.kind == routed::declined && route < BN_HALCNT_INTERPRETER) res = routes[++route - BN_HALCNT_MONOMIALS](r);
+	if (res.kind != routed::launched) return answered_by(r, route, res.rc);
 	BN_HIP(hipMemcpyAsync(h_out, r.d_acc, r.pts.total * sizeof(f128), hipMemcpyDeviceToHost, ctx->stream));
 	BN_HIP(hipStreamSynchronize(ctx->stream));
-	return r.acc.end();
+	return answered_by(r, route, r.acc.end());
+}
+
+int bn_hal_counters(bn_ctx *ctx, uint64_t *counters)
+{
+	BN_REQUIRE(ctx && counters, "null argument");
+	BN_ENTER(ctx);
+	for (int i = 0; i < BN_HALCNT_N; i++) counters[i] = ctx->hal_calls[i];
+	counters[BN_HALCNT_N_CU] = (uint64_t)ctx->n_cu;
+	return BN_OK;
 }
 
 int bn_hal_fold_multilinear(bn_ctx *ctx, uint32_t order, uint32_t n_vars, const bn_hal_multilinear *ml, const bn_f128 *challenge,

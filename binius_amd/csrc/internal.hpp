@@ -80,6 +80,7 @@ struct bn_ctx {
 	uint64_t fri_passes[BN_FRI_N] = {}; // bn_fri_fold passes launched per form, and its copies (bn_fri_counters)
 	uint64_t fold_calls[BN_FOLD_N] = {}; // bn_fold_left / bn_fold_right calls per answering kernel, the last matrix-core launch (bn_fold_counters)
 	uint64_t ip_calls[BN_IP_N] = {};     // bn_inner_product calls per answering kernel (bn_inner_product_counters)
+	uint64_t hal_calls[BN_HALCNT_N] = {}; // bn_hal_round_evals requests per answering route, the branches inside the routes (bn_hal_counters)
 	uint64_t exp_calls = 0, exp_launches = 0, exp_bits_launches = 0;     // bn_exp_circuit_layers / bn_bits_to_b128 (bn_exp_counters)
 	uint64_t flush_calls = 0, flush_launches = 0, flush_served = 0, flush_multipass = 0; // bn_flush_witness_batch (bn_flush_counters)
 	uint64_t pe_calls = 0, pe_launches = 0, pe_cols_kernel = 0, pe_cols_fallback = 0, pe_max_share = 0, pe_routed = 0; // bn_partial_eval_counters

@@ -97,6 +97,7 @@ pub const BN_NTT_N: usize = 3;
 pub const BN_FRI_N: usize = 6;
 pub const BN_FOLD_N: usize = 16;
 pub const BN_IP_N: usize = 4;
+pub const BN_HALCNT_N: usize = 17;
 pub const BN_EXP_N: usize = 3;
 pub const BN_PE_N: usize = 6;
 pub const BN_PE_CALLS: usize = 0;
@@ -660,6 +661,7 @@ unsafe extern "C" {
 	pub fn bn_fri_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 	pub fn bn_fold_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 	pub fn bn_inner_product_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_hal_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 	// cross-rank reduction of the round evaluations inside the kernels' finalize step (one process per GPU)
 	pub fn bn_peer_create(ctx: *mut bn_ctx, world: u32, rank: u32, handle_out: *mut u8) -> c_int;
 	pub fn bn_peer_connect(ctx: *mut bn_ctx, handles: *const u8) -> c_int;

@@ -855,6 +855,25 @@ int bn_fold_counters(bn_ctx *ctx, uint64_t *counters /*[BN_FOLD_N]*/);
  * Read-only; a rejected call counts nowhere. */
 enum { BN_IP_MFMA_SPLIT = 0, BN_IP_SPLIT9 = 1, BN_IP_IP32 = 2, BN_IP_SCALAR = 3, BN_IP_N = 4 };
 int bn_inner_product_counters(bn_ctx *ctx, uint64_t *counters /*[BN_IP_N]*/);
+/* Which route answered the bn_hal_round_evals calls of this context, and which branches ran inside it.  One counter per route -- COEF
+ * (the coefficient form), EQ_SET (a constraint set's two launches), IN_PARTS (a wide request dealt out; every part comes back through
+ * the entry point and counts under the route that answered it), MONOMIALS (one product-sum pass per distinct monomial), ROWS_BATCHED /
+ * ROWS_PER_POINT (rows + compiled circuits, the points side by side up to 2^19 points a row / point by point above), INTERPRETER --:
+ * requests the route answered with BN_OK; a request that asks for no value counts nowhere.  The jobs of the monomial route by kind:
+ * MONO_STRIDED (Low-to-High pairs read with an element stride of two by the matrix-core kernel), MONO_PRODUCT2 / MONO_PRODUCT3 (the
+ * product-sum kernels over two / three factors, the indicator and the all-ones table counted), MONO_XOR_SUM (launches of the streaming
+ * sum of a lone column from 2^18 points: one, or three where a form at infinity holds the column), MONO_CONST (constants without an
+ * indicator: no pass).  ROWS_LAUNCHES / ROWS_WRITTEN: launches of the rows kernel and the rows they wrote (at most 24 a launch);
+ * ROWS_IN_PLACE: halves of full multilinears read where they lie.  TRANSPARENT: Transparent multilinears partially evaluated into
+ * scratch.  N_CU: the compute units of the device, by which the launchers size their grids and the matrix-core threshold is set.
+ * Counted on the host where the route is decided; read-only; a call that returns an error moves nothing. */
+enum {
+	BN_HALCNT_COEF = 0, BN_HALCNT_EQ_SET = 1, BN_HALCNT_IN_PARTS = 2, BN_HALCNT_MONOMIALS = 3, BN_HALCNT_ROWS_BATCHED = 4,
+	BN_HALCNT_ROWS_PER_POINT = 5, BN_HALCNT_INTERPRETER = 6, BN_HALCNT_MONO_STRIDED = 7, BN_HALCNT_MONO_PRODUCT2 = 8, BN_HALCNT_MONO_PRODUCT3 = 9,
+	BN_HALCNT_MONO_XOR_SUM = 10, BN_HALCNT_MONO_CONST = 11, BN_HALCNT_ROWS_LAUNCHES = 12, BN_HALCNT_ROWS_WRITTEN = 13, BN_HALCNT_ROWS_IN_PLACE = 14,
+	BN_HALCNT_TRANSPARENT = 15, BN_HALCNT_N_CU = 16, BN_HALCNT_N = 17
+};
+int bn_hal_counters(bn_ctx *ctx, uint64_t *counters /*[BN_HALCNT_N]*/);
 
 #ifdef __cplusplus
 }

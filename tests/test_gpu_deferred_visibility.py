@@ -894,6 +894,7 @@ EXEMPT = {
 NO_DEVICE_MEMORY = {
     "bn_fold_counters": "read-only query of host counters (which kernel answered bn_fold_left / bn_fold_right): no device memory, launches and flushes nothing",
     "bn_inner_product_counters": "read-only query of host counters (which kernel answered bn_inner_product): no device memory, launches and flushes nothing",
+    "bn_hal_counters": "read-only query of host counters (which route answered bn_hal_round_evals, the branches inside it): no device memory, launches and flushes nothing",
 }
 
 DEVICE_ARG = re.compile(r"\bvoid\s*\*\s*(?:const\s*)?\*?\s*d_\w+|\b(?:void|bn_hal_multilinear|bn_memmap)\s*\*\s*(?:jobs|cols|points|mls|ml|maps|oracles)\b")

@@ -10,6 +10,8 @@ kernels, and from 2^17 points the matrix-core kernels); the switchover fold; the
 import numpy as np
 import pytest
 
+import hal_cases as H
+
 pytestmark = pytest.mark.gpu
 
 AB = [("var", 0), ("var", 1), ("mul", 0, 1)]
@@ -36,24 +38,44 @@ def upload(hal, alloc, arr):
     return d.slice(0, arr.shape[0])
 
 
-def both(hal, oracle, order, n_vars, query, mls, evaluators, points):
-    """mls: ('folded', array, suffix) | ('transparent', array, level, n_vars_ml); evaluators: oracle-style dicts."""
+def both(hal, oracle, order, n_vars, query, mls, evaluators, points, share_eq=False, route=None):
+    """mls: ('folded', array, suffix) | ('transparent', array, level, n_vars_ml); evaluators: oracle-style dicts.  Every evaluator's
+    indicator is uploaded on its own -- as many tables on the device as evaluators under one -- or, with share_eq, once per host array (a
+    constraint set's evaluators share ONE table).  The counters of Context.hal_counters() move by what tests/hal_cases.py derives from the
+    request (the routing predicates of abi_hal.cpp restated; pinned by tests/test_oracle_hal_cases.py), and `route`, where a test names
+    the route it is there for, is the route that answered."""
     alloc = hal.dev_alloc()
     d_mls = [(m[0], upload(hal, alloc, m[1])) + tuple(m[2:]) for m in mls]
     d_q = upload(hal, alloc, query) if query is not None else None
-    exprs, d_evs = [], []
-    for e in evaluators:
+    exprs, d_evs, tokens, shared = [], [], [], {}
+    for k, e in enumerate(evaluators):
         c, ci = hal.compile_expr(e["steps"]), hal.compile_expr(e["steps_inf"])
         exprs += [c, ci]
-        d_evs.append({"composition": c, "composition_at_infinity": ci, "start": e["start"], "end": e["end"],
-                      "eq_ind": upload(hal, alloc, e["eq_ind"]) if e.get("eq_ind") is not None else None})
+        d_eq = token = None
+        if e.get("eq_ind") is not None:
+            if share_eq:
+                token = ("shared", id(e["eq_ind"]))
+                if token not in shared:
+                    shared[token] = upload(hal, alloc, e["eq_ind"])
+                d_eq = shared[token]
+            else:
+                d_eq, token = upload(hal, alloc, e["eq_ind"]), ("own", k)
+        tokens.append(token)
+        d_evs.append({"composition": c, "composition_at_infinity": ci, "start": e["start"], "end": e["end"], "eq_ind": d_eq})
+    before = hal.hal_counters()
     try:
         got = hal.hal_round_evals(order, n_vars, d_q, d_mls, d_evs, points)
     finally:
         for x in exprs:
             x.free()
+    after = hal.hal_counters()
     rc, want = oracle.hal_round_evals(order, n_vars, query, mls, evaluators, points)
     assert rc == 0
+    req = H.request_of(order, n_vars, mls, [dict(e, eq=t) for e, t in zip(evaluators, tokens)], len(points))
+    moved = {k: after[k] - before[k] for k in before if k not in H.HAL_INFO}
+    assert moved == H.hal_counters(req, after["n_cu"]), "the call moved %s" % H.moved(moved)
+    if route is not None:
+        assert H.hal_route(req, after["n_cu"]) == route and moved[route] == 1, "answered by %s" % H.hal_route(req, after["n_cu"])
     return got, want
 
 
@@ -80,15 +102,20 @@ def test_round_evals_general(hal, oracle, order, n_vars):
 @pytest.mark.parametrize("n_vars", [2, 6, 12, 16, 18, 19])
 @pytest.mark.parametrize("with_eq", [False, True])
 def test_round_evals_fast_shape(hal, oracle, n_vars, with_eq):
-    """Every evaluator a * b at X = 1, infinity over full multilinears, High-to-Low: the ComputeLayer kernels
-    (from n_vars = 18 the 2^17-point halves run on the matrix cores when there is no equality indicator)."""
+    """Every evaluator a * b at X = 1, infinity over full multilinears, High-to-Low: the monomial route, one pass of the ComputeLayer
+    kernels per product (from n_vars = 18 the 2^17-point halves run on the matrix cores when there is no equality indicator) -- under
+    indicator tables of their own the products are three-factor jobs of that route; under ONE shared table the request is a constraint
+    set and takes its two launches (eq_set)."""
     n = 1 << n_vars
     x = [oracle.random_b128(0x12A0 + j, n) for j in range(3)]
     eq = oracle.random_b128(0x12C0, n // 2) if with_eq else None
     evaluators = [{"steps": [("var", a), ("var", b), ("mul", 0, 1)], "steps_inf": [("var", a), ("var", b), ("mul", 0, 1)], "start": s, "end": 3, "eq_ind": eq}
                   for a, b, s in ((0, 1, 1), (2, 0, 1), (1, 2, 2))]
-    got, want = both(hal, oracle, 1, n_vars, None, [("folded", v, 0) for v in x], evaluators, [])
+    got, want = both(hal, oracle, 1, n_vars, None, [("folded", v, 0) for v in x], evaluators, [], route="monomials")
     assert got == want
+    if with_eq:
+        got1, _ = both(hal, oracle, 1, n_vars, None, [("folded", v, 0) for v in x], evaluators, [], share_eq=True, route="eq_set")
+        assert got1 == want
     # the same request through the general kernel (Low-to-High of the interleaved arrays) gives the same sums
     if n_vars <= 16:
         inter = []
@@ -103,8 +130,9 @@ def test_round_evals_fast_shape(hal, oracle, n_vars, with_eq):
 @pytest.mark.parametrize("n_vars", [3, 9, 14])
 @pytest.mark.parametrize("with_eq", [False, True])
 def test_round_evals_fast_shape_three_factors(hal, oracle, n_vars, with_eq):
-    """Products of three full multilinears (a * b * c, a^2 * b), with or without the equality indicator: routed to the
-    bit-sliced product-sum kernel."""
+    """Products of three full multilinears (a * b * c, a^2 * b): degree 3 at X = 1, infinity is the coefficient form's (coef), without
+    an indicator and under ONE shared table; under indicator tables of their own the evaluators keep the general code (four factors
+    are more than a monomial job takes)."""
     n = 1 << n_vars
     x = [oracle.random_b128(0x12E0 + j, n) for j in range(3)]
     eq = oracle.random_b128(0x12F0, n // 2) if with_eq else None
@@ -112,15 +140,19 @@ def test_round_evals_fast_shape_three_factors(hal, oracle, n_vars, with_eq):
     aab = [("var", 0), ("var", 0), ("mul", 0, 1), ("var", 1), ("mul", 2, 3)]
     evaluators = [{"steps": abc, "steps_inf": abc, "start": 1, "end": 3, "eq_ind": eq},
                   {"steps": aab, "steps_inf": aab, "start": 2, "end": 3, "eq_ind": eq}]
-    got, want = both(hal, oracle, 1, n_vars, None, [("folded", v, 0) for v in x], evaluators, [])
+    got, want = both(hal, oracle, 1, n_vars, None, [("folded", v, 0) for v in x], evaluators, [], route=None if with_eq else "coef")
     assert got == want
+    if with_eq:
+        got1, _ = both(hal, oracle, 1, n_vars, None, [("folded", v, 0) for v in x], evaluators, [], share_eq=True, route="coef")
+        assert got1 == want
 
 
 @pytest.mark.parametrize("n_vars", [2, 5, 11, 18, 19])
 def test_round_evals_routed_sums_of_products(hal, oracle, n_vars):
     """Compositions that are sums of monomials (a * b + c, a * b * c + a, K * b^3 + a, a * b + K, a single variable),
     with and without an equality indicator, at X = 1 and infinity over full multilinears: one product-sum pass per
-    distinct monomial, coefficients applied on the host.  (Zerocheck-style constraints take this route.)"""
+    distinct monomial, coefficients applied on the host.  (Zerocheck-style constraints take this route.)  Nine evaluators are more
+    than one pass carries: the request is dealt out (in_parts) to eight evaluators and one, and both parts take the monomial route."""
     n = 1 << n_vars
     x = [oracle.random_b128(0x18A0 + j, n) for j in range(3)]
     eq = oracle.random_b128(0x18B0, n // 2)
@@ -139,8 +171,12 @@ def test_round_evals_routed_sums_of_products(hal, oracle, n_vars):
         {"steps": kab, "steps_inf": kab, "start": 1, "end": 3, "eq_ind": None},
         {"steps": lin, "steps_inf": lin, "start": 1, "end": 3, "eq_ind": None},  # (a lone column at both points: streaming sums from 2^18 points)
     ]
-    got, want = both(hal, oracle, 1, n_vars, None, [("folded", v, 0) for v in x], evaluators, [])
+    before = hal.hal_counters()
+    got, want = both(hal, oracle, 1, n_vars, None, [("folded", v, 0) for v in x], evaluators, [], route="in_parts")
     assert got == want
+    after = hal.hal_counters()
+    assert after["monomials"] - before["monomials"] == 2 and after["mono_product3"] > before["mono_product3"]   # (jobs under an indicator among them)
+    assert (after["mono_xor_sum"] > before["mono_xor_sum"]) == (n_vars >= 19)
 
 
 def test_round_evals_routed_with_transparent_inputs(hal, oracle):
@@ -154,7 +190,7 @@ def test_round_evals_routed_with_transparent_inputs(hal, oracle):
     other = [oracle.random_b128(0x19C0 + j, 1 << n_vars) for j in range(2)]
     evaluators = [{"steps": AB_PLUS_C, "steps_inf": AB, "start": 1, "end": 3, "eq_ind": None}]
     mls = [("transparent", packed, level, n_ml), ("folded", other[0], 0), ("folded", other[1], 0)]
-    got, want = both(hal, oracle, 1, n_vars, query, mls, evaluators, [])
+    got, want = both(hal, oracle, 1, n_vars, query, mls, evaluators, [], route="monomials")
     assert got == want
 
 

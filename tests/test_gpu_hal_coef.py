@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import hal_cases as H
 from test_gpu_hal import upload
 
 pytestmark = pytest.mark.gpu
@@ -25,9 +26,11 @@ MIXED = [("var", 0), ("const", K), ("add", 0, 1), ("var", 1), ("mul", 2, 3), ("v
 MIXED_INF = ABC
 
 
-def run(oracle, n_vars, n_mls, evaluators, points, env=None, expect_path=True, seed=0, trunc=None):
+def run(oracle, n_vars, n_mls, evaluators, points, env=None, expect_path=True, seed=0, trunc=None, route=None):
     """The request on a fresh context (env applied while it is created), the oracle's values beside it.
-    trunc: {multilinear: (length, suffix)} -- those multilinears are cut to `length` elements before a constant suffix."""
+    trunc: {multilinear: (length, suffix)} -- those multilinears are cut to `length` elements before a constant suffix.
+    expect_path: the coefficient form answers (its two group launches, and the `coef` counter of Context.hal_counters()) or does not;
+    route: the route that answers instead.  Either way the counters move by what tests/hal_cases.py derives from the request."""
     import binius_amd
 
     n = 1 << n_vars
@@ -59,10 +62,10 @@ def run(oracle, n_vars, n_mls, evaluators, points, env=None, expect_path=True, s
                     eqs[id(e["eq_ind"])] = upload(hal, alloc, e["eq_ind"])
                 d_eq = eqs[id(e["eq_ind"])]
             d_evs.append({"composition": c, "composition_at_infinity": ci, "start": e["start"], "end": e["end"], "eq_ind": d_eq})
-        before = hal.group_counters()["launches"]
+        before, routes0 = hal.group_counters()["launches"], hal.hal_counters()
         got = hal.hal_round_evals(1, n_vars, None, d_mls, d_evs, points)
         again = hal.hal_round_evals(1, n_vars, None, d_mls, d_evs, points)
-        taken = hal.group_counters()["launches"] - before
+        taken, routes1 = hal.group_counters()["launches"] - before, hal.hal_counters()
         for x in exprs:
             x.free()
     finally:
@@ -73,6 +76,14 @@ def run(oracle, n_vars, n_mls, evaluators, points, env=None, expect_path=True, s
     assert again == got
     if expect_path is not None:
         assert (taken == 2) == expect_path, "coefficient-form path %s (group launches: %d)" % ("not taken" if expect_path else "taken", taken)
+    moved = {k: routes1[k] - routes0[k] for k in routes0 if k not in H.HAL_INFO}
+    if expect_path is not None:
+        assert moved["coef"] == (2 if expect_path else 0), "the two calls moved %s" % H.moved(moved)
+    req = H.request_of(1, n_vars, mls, [dict(e, eq=id(e["eq_ind"]) if e.get("eq_ind") is not None else None) for e in evaluators], len(points), env)
+    once = H.hal_counters(req, routes1["n_cu"])
+    assert moved == {k: 2 * v for k, v in once.items()}, "the two calls moved %s" % H.moved(moved)
+    if route is not None:
+        assert moved[route] == 2 and H.hal_route(req, routes1["n_cu"]) == route
     return got
 
 
@@ -92,7 +103,7 @@ def test_cubic_at_domain_points(oracle, n_vars, with_eq):
 @pytest.mark.parametrize("with_eq", [False, True])
 def test_cubic_with_the_form_declined_at_traffic_bound_size(oracle, truncated, with_eq):
     """The same request at n_vars = 21 where the coefficient form does not answer it: the rows + compiled circuits code with a
-    product pass per point.  No counter names that route; these conditions of bn_hal_round_evals select it: the coefficient form
+    product pass per point (the `rows_per_point` counter).  These conditions of bn_hal_round_evals select it: the coefficient form
     is off (BN_HAL_COEF=0) or declines a truncated multilinear; one domain point keeps the constraint-set path and the monomial
     route (points 1 and infinity only) away; one evaluator over three multilinears is not wide; half = 2^20 >= 1024 with three
     values takes rows + circuits, and half > 2^19 takes them point by point.  Full multilinears: the rows of point 1 are the
@@ -102,9 +113,9 @@ def test_cubic_with_the_form_declined_at_traffic_bound_size(oracle, truncated, w
     pts = oracle.random_scalars(0xC0EB + n_vars, 1)
     evs = [{"steps": ABC_PLUS_A, "steps_inf": ABC, "start": 1, "end": 4, "eq_ind": eq}]
     if truncated:
-        run(oracle, n_vars, 3, evs, pts, expect_path=False, trunc={1: ((1 << n_vars) - 5, 0x0F1E2D3C4B5A69788796A5B4C3D2E1F0)})
+        run(oracle, n_vars, 3, evs, pts, expect_path=False, trunc={1: ((1 << n_vars) - 5, 0x0F1E2D3C4B5A69788796A5B4C3D2E1F0)}, route="rows_per_point")
     else:
-        run(oracle, n_vars, 3, evs, pts, env={"BN_HAL_COEF": "0"}, expect_path=False)
+        run(oracle, n_vars, 3, evs, pts, env={"BN_HAL_COEF": "0"}, expect_path=False, route="rows_per_point")
 
 
 @pytest.mark.parametrize("n_vars", [2, 4, 8, 13, 17])
