@@ -20,6 +20,23 @@
 //     their execute() without a launch;
 //   * the batch coefficients are applied on the host (value = init + sum_c coeff_c * S_c, compute/src/cpu/layer.rs:512).
 //
+// The route order of an evaluation (group_eval; each step a function of its own, the first that applies answers):
+//
+//   1. the gate         group path off, eager folds, a peer exchange, a resident tail, no host output: not ours
+//   2. parse            the op list as a request; not the shape: not ours
+//   3. hosted hit       a hosted prover's evaluation of exactly its current halves: host arithmetic (hosted_hit, host_answer)
+//   4. ahead hit        sums computed ahead for exactly this request (ahead_hit: answer, record; spec_hits)
+//   5. not ours         one claim, nothing deferred, the group path idle: the single-claim dispatcher.  Nothing up to here touches
+//                       state or allocates: every single-claim launch of the headline benchmark passes through 1, 2 and 5
+//   6. make room        the single-claim state gives way (legacy_to_group), deferred copies run (flush_copies)
+//   7. match            ref[i] = the deferred fold whose output array i is; folds the request reads otherwise run first; owed
+//                       write-backs it reads run; the pinned tables exist (match)
+//   8. hand-over        small enough for the host: one launch folds and mirrors the arrays, the session is hosted (hand_over)
+//   9. launch           riders, loose arrays, the jobs (with chains, then without; neither fits: the eager kernels answer),
+//                       plain folds in front, the group launch, retirement, the answer, the riders' sums (launch_round)
+//
+// The writers of a session: record (what was evaluated), record_ahead (sums computed ahead), the hosted start in hand_over.
+//
 // One invalidation rule: a call that reads or writes device memory the deferred folds touch, or that the library cannot see
 // through, runs them first as plain fold launches (group_flush / group_flush_touching) -- the caller's memory is then exactly
 // what eager execution leaves -- and forgets the sums computed ahead.  A session is only a description (pointers and claim
@@ -67,8 +84,20 @@ bool fold_touches(const bn_ctx::group_fold &f, const void *p, uint64_t n)
 	return false;
 }
 
-// a deferred fold as plain launches (kFoldBatchMax arrays each: the batch rides in the kernel arguments)
-int launch_fold(bn_ctx *ctx, const bn_ctx::group_fold &f)
+// entries [at, at + c) of a deferred fold as the kernel arguments of a plain launch, from argument `to` on
+template <class Batch>
+void fill_batch(Batch &b, uint32_t to, const bn_ctx::group_fold &f, uint32_t at, uint32_t c)
+{
+	for (uint32_t i = 0; i < c; i++) {
+		b.x0[to + i] = f.x0[at + i];
+		b.x1[to + i] = f.x1[at + i];
+		b.src0[to + i] = f.src0[at + i] != f.x0[at + i] ? f.src0[at + i] : nullptr; // (absorbed copy: read there, write here)
+	}
+}
+
+// a deferred fold as plain launches (kFoldBatchMax arrays each: the batch rides in the kernel arguments).  flush: the fold was
+// forced out (flushed_folds) -- not one that a round launches in front of its group launch or beside its hand-over
+int launch_fold(bn_ctx *ctx, const bn_ctx::group_fold &f, bool flush)
 {
 	uint32_t at = 0;
 	// (more than one launch's worth: 128 arrays at a time through the wide form)
@@ -76,11 +105,7 @@ int launch_fold(bn_ctx *ctx, const bn_ctx::group_fold &f)
 		const uint32_t c = std::min<uint32_t>(f.count - at, (uint32_t)bn::kFoldWideMax);
 		static bn::fold_batch_wide fw_zero{};
 		bn::fold_batch_wide fw = fw_zero;
-		for (uint32_t i = 0; i < c; i++) {
-			fw.x0[i] = f.x0[at + i];
-			fw.x1[i] = f.x1[at + i];
-			fw.src0[i] = f.src0[at + i] != f.x0[at + i] ? f.src0[at + i] : nullptr;
-		}
+		fill_batch(fw, 0, f, at, c);
 		prof_scope ps(ctx, BN_PROF_FOLD);
 		BN_HIP(bn::launch_extrapolate_line_wide(ctx->stream, ctx->n_cu, fw, c, f.n, f.z));
 		at += c;
@@ -88,45 +113,24 @@ int launch_fold(bn_ctx *ctx, const bn_ctx::group_fold &f)
 	for (; at < f.count; at += (uint32_t)bn::kFoldBatchMax) {
 		const uint32_t c = std::min<uint32_t>(f.count - at, (uint32_t)bn::kFoldBatchMax);
 		bn::fold_batch fb{};
-		for (uint32_t i = 0; i < c; i++) {
-			fb.x0[i] = f.x0[at + i];
-			fb.x1[i] = f.x1[at + i];
-			fb.src0[i] = f.src0[at + i] != f.x0[at + i] ? f.src0[at + i] : nullptr; // (absorbed copy: read there, write here)
-		}
+		fill_batch(fb, 0, f, at, c);
 		prof_scope ps(ctx, BN_PROF_FOLD);
 		BN_HIP(bn::launch_extrapolate_line_batch(ctx->stream, ctx->n_cu, fb, c, f.n, f.z));
 	}
-	ctx->grp.flushed_folds++;
+	if (flush) ctx->grp.flushed_folds++;
 	return BN_OK;
 }
 
-// the pinned tables, accumulator slots and value mailbox of the group launches (allocated with the first of them)
-int res_alloc(bn_ctx *ctx)
+// `bytes` of pinned, device-mapped host memory.  what == nullptr: a bare status without an error message (the hand-over's staging:
+// a failure there means "do not host")
+int pinned_mapped_alloc(void **h, void **d, size_t bytes, const char *what)
 {
-	auto &g = ctx->grp;
-	if (g.h_tables && g.d_S && g.h_gmail) return BN_OK;
-	if (!g.h_tables) {
-		if (hipHostMalloc(&g.h_tables, sizeof(bn::group_tables), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-			(void)hipGetLastError();
-			g.h_tables = nullptr;
-			return bn::fail(BN_ERR_ALLOC, "claim groups: pinned job table");
-		}
-		std::memset(g.h_tables, 0, sizeof(bn::group_tables));
-		BN_HIP(hipHostGetDevicePointer(&g.d_tables, g.h_tables, 0));
+	if (hipHostMalloc(h, bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+		(void)hipGetLastError();
+		*h = nullptr;
+		return what ? bn::fail(BN_ERR_ALLOC, what) : BN_ERR_ALLOC;
 	}
-	if (!g.h_gmail) {
-		if (hipHostMalloc((void **)&g.h_gmail, sizeof(f128) * bn::kGroupMaxSlots, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-			(void)hipGetLastError();
-			g.h_gmail = nullptr;
-			return bn::fail(BN_ERR_ALLOC, "claim groups: pinned value mailbox");
-		}
-		std::memset(g.h_gmail, 0, sizeof(f128) * bn::kGroupMaxSlots);
-		BN_HIP(hipHostGetDevicePointer((void **)&g.d_gmail, g.h_gmail, 0));
-	}
-	if (!g.d_S) {
-		BN_HIP(hipMalloc((void **)&g.d_S, sizeof(f128) * bn::kGroupMaxSlots));
-		BN_HIP(hipMemsetAsync(g.d_S, 0, sizeof(f128) * bn::kGroupMaxSlots, ctx->stream));
-	}
+	BN_HIP(hipHostGetDevicePointer(d, *h, 0));
 	return BN_OK;
 }
 
@@ -153,19 +157,25 @@ struct request {
 	std::vector<term> terms;
 	uint32_t n_values = 0;
 	f128 init[bn::kFinMaxValues] = {};
+	const uint32_t *ret_values = nullptr; // the values asked for ...
+	uint32_t n_ret = 0;
+	bn_f128 *h_out = nullptr;             // ... and where they go (both set by group_eval)
 };
+
+// a slice of a mapped (not Local) buffer: where it starts
+bool mapped_slice(const bn_memmap *maps, uint32_t n_maps, const bn_kslice &sl, const char *&p)
+{
+	if (sl.buf >= n_maps || maps[sl.buf].kind == BN_MAP_LOCAL || !maps[sl.buf].d_data) return false;
+	if (sl.off + sl.len > maps[sl.buf].len) return false;
+	p = (const char *)maps[sl.buf].d_data + sl.off * sizeof(f128);
+	return true;
+}
 
 // Parses the op list.  false: not the shape (the single-claim dispatcher validates and answers it).
 bool parse(const bn_memmap *maps, uint32_t n_maps, const bn_kop *ops, uint32_t n_ops, const uint32_t *ret_values, uint32_t n_ret, request &rq)
 {
 	if (n_ret == 0 || n_ret > (uint32_t)bn::kFinMaxRets) return false;
 	std::vector<int> local_array(n_maps, -1); // Local buffer -> the array whose lo + hi it holds
-	auto plain = [&](const bn_kslice &sl, const char *&p) {
-		if (sl.buf >= n_maps || maps[sl.buf].kind == BN_MAP_LOCAL || !maps[sl.buf].d_data) return false;
-		if (sl.off + sl.len > maps[sl.buf].len) return false;
-		p = (const char *)maps[sl.buf].d_data + sl.off * sizeof(f128);
-		return true;
-	};
 	// (a, b) -> claim.  The reference records the claims in ONE order, first at 1, then at infinity (v3/bivariate_product.rs:355-399):
 	// a cursor that walks the claims found so far answers every look-up of the second half; whatever it misses goes through a
 	// linear search (few claims) or a hash map built on the first miss (many) -- this parser runs in front of EVERY kernel launch,
@@ -212,7 +222,7 @@ bool parse(const bn_memmap *maps, uint32_t n_maps, const bn_kop *ops, uint32_t n
 			const uint64_t len = (uint64_t)1 << maps[op.dst.buf].log_size;
 			if (op.dst.off != 0 || op.dst.len != len || op.src1.len != len || op.src2.len != len) return false;
 			const char *p = nullptr, *q = nullptr;
-			if (!plain(op.src1, p) || !plain(op.src2, q)) return false;
+			if (!mapped_slice(maps, n_maps, op.src1, p) || !mapped_slice(maps, n_maps, op.src2, q)) return false;
 			if (local_array[op.dst.buf] >= 0 || rq.m >= kMaxArrays) return false; // (defined twice: not this shape)
 			if (rq.m && len != rq.row_len) return false;
 			rq.row_len = len;
@@ -276,7 +286,7 @@ bool parse(const bn_memmap *maps, uint32_t n_maps, const bn_kop *ops, uint32_t n
 				n_local++;
 			} else {
 				const char *p = nullptr;
-				if (!plain(sl, p)) return false;
+				if (!mapped_slice(maps, n_maps, sl, p)) return false;
 				arr[j] = array_of_hi(p, j); // the evaluation at 1 is the array's upper half
 				if (arr[j] < 0) return false;
 				hi_last[j] = (uint32_t)arr[j];
@@ -292,7 +302,8 @@ bool parse(const bn_memmap *maps, uint32_t n_maps, const bn_kop *ops, uint32_t n
 	return rq.k > 0 && rq.k <= kMaxClaims; // (two accumulator slots per claim, bn::kGroupMaxSlots per launch)
 }
 
-void answer(const request &rq, const f128 *raw, const uint32_t *ret_values, uint32_t n_ret, bn_f128 *h_out)
+// the values of the request from the raw sums of its claims ([2 c] at 1, [2 c + 1] at infinity)
+void answer(const request &rq, const f128 *raw)
 {
 	f128 vals[bn::kFinMaxValues];
 	for (uint32_t v = 0; v < rq.n_values; v++) vals[v] = rq.init[v];
@@ -300,7 +311,7 @@ void answer(const request &rq, const f128 *raw, const uint32_t *ret_values, uint
 		const f128 s = raw[2 * t.claim + t.at_inf];
 		vals[t.value] ^= (t.coeff == f128{1, 0}) ? s : bn::mul_host(t.coeff, s);
 	}
-	for (uint32_t r = 0; r < n_ret; r++) h_out[r] = bn_f128{vals[ret_values[r]].lo, vals[ret_values[r]].hi};
+	for (uint32_t r = 0; r < rq.n_ret; r++) rq.h_out[r] = bn_f128{vals[rq.ret_values[r]].lo, vals[rq.ret_values[r]].hi};
 }
 
 // where array (lo, hi, row_len) comes out of a deferred fold: the batch and the index inside it.  The deferred folds are disjoint
@@ -379,8 +390,108 @@ struct fold_index {
 	}
 };
 
-// the jobs of one prover's evaluation: arrays (lo, hi) of row_len points each, array i coming out of deferred fold ref[i]
-// (f < 0: it is up to date in memory); appends the jobs (slot = slot0 + 2 * claim).
+// one flag per entry of every deferred fold, clear at first: shaped like grp.folds at the moment it is made
+struct fold_mask {
+	std::vector<std::vector<char>> bit;
+	explicit fold_mask(const std::vector<bn_ctx::group_fold> &folds) : bit(folds.size())
+	{
+		for (size_t f = 0; f < folds.size(); f++) bit[f].assign(folds[f].count, 0);
+	}
+	char &operator[](fold_ref r) { return bit[r.f][r.j]; }
+	bool any(size_t f) const { return std::find(bit[f].begin(), bit[f].end(), 1) != bit[f].end(); }
+};
+
+// the entries of batch f whose flag is `set`, as a batch of their own
+bn_ctx::group_fold entries_where(const bn_ctx::group_fold &f, const std::vector<char> &flags, bool set)
+{
+	bn_ctx::group_fold part;
+	part.n = f.n;
+	part.z = f.z;
+	for (uint32_t j = 0; j < f.count; j++)
+		if ((flags[j] != 0) == set) part.push(f.x0[j], f.x1[j], f.src0[j]);
+	return part;
+}
+
+// The marked entries leave the deferred folds (something has performed them, or is about to): every batch that holds one, back to
+// front, is cut down to the rest of its entries -- which stays deferred, or (launch_rest) is folded by a plain launch of the round,
+// not a flush.  A batch without a marked entry is left alone.
+int drop_marked(bn_ctx *ctx, const fold_mask &marked, bool launch_rest)
+{
+	auto &folds = ctx->grp.folds;
+	for (size_t f = folds.size(); f-- > 0;) {
+		if (!marked.any(f)) continue;
+		bn_ctx::group_fold rest = entries_where(folds[f], marked.bit[f], false);
+		if (rest.count && !launch_rest) {
+			folds[f] = std::move(rest);
+			continue;
+		}
+		folds.erase(folds.begin() + (long)f);
+		if (rest.count) {
+			const int rc = launch_fold(ctx, rest, /*flush=*/false);
+			if (rc) return rc;
+		}
+	}
+	return BN_OK;
+}
+
+// one prover of a launch: m arrays (lo, hi) of row_len points each under k claims (pa, pb), array i coming out of deferred fold
+// ref[i] (f < 0: it is up to date in memory); its sums go to slots slot0 + 2 * claim.  Built once from the request, once per rider.
+struct prover_view {
+	uint32_t m = 0, k = 0;
+	const uint16_t *pa = nullptr, *pb = nullptr;
+	const void *const *lo = nullptr, *const *hi = nullptr;
+	uint64_t row_len = 0;
+	const fold_ref *ref = nullptr;
+	uint32_t slot0 = 0;
+	// in how many claims array i stands
+	std::vector<uint32_t> degrees() const
+	{
+		std::vector<uint32_t> deg(m, 0);
+		for (uint32_t c = 0; c < k; c++) {
+			deg[pa[c]]++;
+			deg[pb[c]]++;
+		}
+		return deg;
+	}
+};
+// another prover whose next evaluation rides on the launch: its session, its arrays as its deferred fold will leave them
+struct rider {
+	bn_ctx::group_session *s;
+	prover_view v;
+	std::vector<fold_ref> ref;
+	std::vector<const void *> lo, hi;
+};
+// what the planners count besides the jobs
+struct plan_counts {
+	uint64_t fused = 0, fold_only = 0, chains = 0;
+};
+
+// side sd of job j folds entry r of the deferred folds: src0 | x1 -> x0 under that batch's challenge
+void fold_side(const bn_ctx *ctx, bn::group_job &j, int sd, fold_ref r)
+{
+	const auto &f = ctx->grp.folds[r.f];
+	j.x0[sd] = f.src0[r.j];
+	j.x1[sd] = f.x1[r.j];
+	j.out[sd] = f.x0[r.j];
+	j.z = f.z;
+}
+// a job of claim c of prover v
+bn::group_job claim_job(const prover_view &v, uint32_t kind, uint32_t c)
+{
+	bn::group_job j{};
+	j.kind = kind;
+	j.n = v.row_len;
+	j.slot = v.slot0 + 2 * c;
+	return j;
+}
+// an evaluating side: the array as it is
+void plain_side(bn::group_job &j, int sd, const prover_view &v, uint32_t i)
+{
+	j.x0[sd] = v.lo[i];
+	j.x1[sd] = v.hi[i];
+}
+
+// the jobs of one prover's evaluation, appended to `jobs`.
 //
 //   * a claim whose two arrays both wait for their fold (one challenge) and are not yet folded by another job: fold + evaluate
 //     (kind 0) -- a matching of the claim graph, the claims over arrays of degree one first (a prover with disjoint claims: all);
@@ -396,15 +507,13 @@ struct fold_index {
 //     Everything else stays a job of its own.
 //
 // false (nothing appended): more than `room` jobs -- the caller falls back to plan_prefold.
-bool plan_chained(const bn_ctx *ctx, uint32_t m, uint32_t k, const uint16_t *pa, const uint16_t *pb, const void *const *lo, const void *const *hi, uint64_t row_len,
-                  const fold_ref *ref, uint32_t slot0, size_t room, std::vector<bn::group_job> &jobs, uint64_t &n_fused, uint64_t &n_fold_only, uint64_t &n_chains)
+bool plan_chained(const bn_ctx *ctx, const prover_view &v, size_t room, std::vector<bn::group_job> &jobs, plan_counts &cnt)
 {
 	const auto &folds = ctx->grp.folds;
-	std::vector<uint32_t> deg(m, 0);
-	for (uint32_t c = 0; c < k; c++) {
-		deg[pa[c]]++;
-		deg[pb[c]]++;
-	}
+	const uint32_t m = v.m, k = v.k;
+	const uint16_t *const pa = v.pa, *const pb = v.pb;
+	const fold_ref *const ref = v.ref;
+	const std::vector<uint32_t> deg = v.degrees();
 	std::vector<char> matched(m, 0), fused_claim(k, 0);
 	auto fusable = [&](uint32_t c) {
 		const uint32_t a = pa[c], b = pb[c];
@@ -447,72 +556,46 @@ bool plan_chained(const bn_ctx *ctx, uint32_t m, uint32_t k, const uint16_t *pa,
 	std::vector<uint32_t> left[2]; // arrays to fold only: [1] = read back (chain), [0] = not
 	for (uint32_t i = 0; i < m; i++)
 		if (ref[i].f >= 0 && !matched[i] && !halved[i]) left[read_back[i] ? 1 : 0].push_back(i);
-	auto fold_only_jobs = [&](const std::vector<uint32_t> &v) {
-		// (two arrays per job where they share the challenge)
-		size_t n = 0;
-		for (size_t q = 0; q < v.size();) {
-			const bool two = q + 1 < v.size() && folds[ref[v[q]].f].z == folds[ref[v[q + 1]].f].z;
-			q += two ? 2 : 1;
-			n++;
-		}
-		return n;
-	};
-	if ((size_t)k + fold_only_jobs(left[0]) + fold_only_jobs(left[1]) > room) return false;
-	auto fold_side = [&](bn::group_job &j, int sd, uint32_t i) {
-		const auto &f = folds[ref[i].f];
-		j.x0[sd] = f.src0[ref[i].j];
-		j.x1[sd] = f.x1[ref[i].j];
-		j.out[sd] = f.x0[ref[i].j];
-		j.z = f.z;
-	};
-	std::vector<bn::group_job> chain_w, chain_h, chain_e, alone;
-	for (uint32_t c = 0; c < k; c++) {
-		if (!fused_claim[c]) continue;
-		bn::group_job j{};
-		j.kind = 0;
-		j.n = row_len;
-		j.slot = slot0 + 2 * c;
-		fold_side(j, 0, pa[c]);
-		fold_side(j, 1, pb[c]);
-		(read_back[pa[c]] || read_back[pb[c]] ? chain_w : alone).push_back(j);
-		n_fused++;
-	}
+	std::vector<bn::group_job> chain_w, chain_h, chain_e, alone, fold_only[2];
 	for (int rb = 0; rb < 2; rb++)
 		for (size_t q = 0; q < left[rb].size();) {
 			bn::group_job j{};
 			j.kind = 3;
-			j.n = row_len;
-			fold_side(j, 0, left[rb][q]);
+			j.n = v.row_len;
+			fold_side(ctx, j, 0, ref[left[rb][q]]);
+			// (two arrays per job where they share the challenge)
 			const bool two = q + 1 < left[rb].size() && folds[ref[left[rb][q]].f].z == folds[ref[left[rb][q + 1]].f].z;
-			if (two) fold_side(j, 1, left[rb][q + 1]);
+			if (two) fold_side(ctx, j, 1, ref[left[rb][q + 1]]);
 			q += two ? 2 : 1;
-			(rb ? chain_w : alone).push_back(j);
-			n_fold_only++;
+			fold_only[rb].push_back(j);
 		}
+	if ((size_t)k + fold_only[0].size() + fold_only[1].size() > room) return false;
+	cnt.fold_only += fold_only[0].size() + fold_only[1].size();
+	for (uint32_t c = 0; c < k; c++) {
+		if (!fused_claim[c]) continue;
+		bn::group_job j = claim_job(v, 0, c);
+		fold_side(ctx, j, 0, ref[pa[c]]);
+		fold_side(ctx, j, 1, ref[pb[c]]);
+		(read_back[pa[c]] || read_back[pb[c]] ? chain_w : alone).push_back(j);
+		cnt.fused++;
+	}
+	alone.insert(alone.end(), fold_only[0].begin(), fold_only[0].end());
+	chain_w.insert(chain_w.end(), fold_only[1].begin(), fold_only[1].end());
 	for (uint32_t c = 0; c < k; c++) {
 		if (!half[c]) continue;
 		const uint32_t a = half[c] == 1 ? pa[c] : pb[c], b = half[c] == 1 ? pb[c] : pa[c];
-		bn::group_job j{};
-		j.kind = 4;
-		j.n = row_len;
-		j.slot = slot0 + 2 * c;
-		fold_side(j, 0, a);
-		j.x0[1] = lo[b];
-		j.x1[1] = hi[b];
+		bn::group_job j = claim_job(v, 4, c);
+		fold_side(ctx, j, 0, ref[a]);
+		plain_side(j, 1, v, b);
 		(ref[b].f >= 0 || read_back[a] ? chain_h : alone).push_back(j);
-		n_fused++;
+		cnt.fused++;
 	}
 	for (uint32_t c = 0; c < k; c++) {
 		if (fused_claim[c] || half[c]) continue;
 		const uint32_t a = pa[c], b = pb[c];
-		bn::group_job j{};
-		j.kind = 1;
-		j.n = row_len;
-		j.slot = slot0 + 2 * c;
-		j.x0[0] = lo[a];
-		j.x1[0] = hi[a];
-		j.x0[1] = lo[b];
-		j.x1[1] = hi[b];
+		bn::group_job j = claim_job(v, 1, c);
+		plain_side(j, 0, v, a);
+		plain_side(j, 1, v, b);
 		(ref[a].f >= 0 || ref[b].f >= 0 ? chain_e : alone).push_back(j);
 	}
 	if (!chain_w.empty() || !chain_h.empty() || !chain_e.empty()) {
@@ -524,7 +607,7 @@ bool plan_chained(const bn_ctx *ctx, uint32_t m, uint32_t k, const uint16_t *pa,
 		jobs.insert(jobs.end(), chain_h.begin(), chain_h.end());
 		jobs.insert(jobs.end(), chain_e.begin(), chain_e.end());
 		jobs[at].chain = (uint32_t)(jobs.size() - at) - 1;
-		if (jobs[at].chain) n_chains++;
+		if (jobs[at].chain) cnt.chains++;
 	}
 	jobs.insert(jobs.end(), alone.begin(), alone.end());
 	return true;
@@ -532,83 +615,77 @@ bool plan_chained(const bn_ctx *ctx, uint32_t m, uint32_t k, const uint16_t *pa,
 
 // without chains (arrays below the size where chains pay, or more jobs than a launch carries): claims over arrays of degree one
 // are fused (kind 0); a claim over an array of degree one and a shared one folds the former on the way (kind 4) -- the shared
-// array, like every other waiting array, is folded by a plain launch in front (prefold)
-void plan_prefold(const bn_ctx *ctx, uint32_t m, uint32_t k, const uint16_t *pa, const uint16_t *pb, const void *const *lo, const void *const *hi, uint64_t row_len,
-                  const fold_ref *ref, uint32_t slot0, std::vector<bn::group_job> &jobs, std::vector<char> &prefold /*[m]*/, uint64_t &n_fused)
+// array, like every other waiting array, is folded by a plain launch in front: marked in `plain`
+void plan_prefold(const bn_ctx *ctx, const prover_view &v, std::vector<bn::group_job> &jobs, fold_mask &plain, plan_counts &cnt)
 {
-	std::vector<uint32_t> deg(m, 0);
-	for (uint32_t c = 0; c < k; c++) {
-		deg[pa[c]]++;
-		deg[pb[c]]++;
-	}
-	std::vector<char> fused_arr(m, 0);
-	for (uint32_t c = 0; c < k; c++) {
-		const uint32_t a = pa[c], b = pb[c];
-		bn::group_job j{};
-		j.n = row_len;
-		j.slot = slot0 + 2 * c;
-		auto waits_alone = [&](uint32_t i) { return deg[i] == 1 && ref[i].f >= 0; };
-		if (a != b && waits_alone(a) && waits_alone(b) && ctx->grp.folds[ref[a].f].z == ctx->grp.folds[ref[b].f].z) {
-			const auto &fa = ctx->grp.folds[ref[a].f], &fb = ctx->grp.folds[ref[b].f];
+	const auto &folds = ctx->grp.folds;
+	const std::vector<uint32_t> deg = v.degrees();
+	std::vector<char> fused_arr(v.m, 0);
+	auto waits_alone = [&](uint32_t i) { return deg[i] == 1 && v.ref[i].f >= 0; };
+	for (uint32_t c = 0; c < v.k; c++) {
+		const uint32_t a = v.pa[c], b = v.pb[c];
+		bn::group_job j = claim_job(v, 1, c);
+		if (a != b && waits_alone(a) && waits_alone(b) && folds[v.ref[a].f].z == folds[v.ref[b].f].z) {
 			j.kind = 0;
-			j.z = fa.z;
-			j.x0[0] = fa.src0[ref[a].j];
-			j.x1[0] = fa.x1[ref[a].j];
-			j.out[0] = fa.x0[ref[a].j];
-			j.x0[1] = fb.src0[ref[b].j];
-			j.x1[1] = fb.x1[ref[b].j];
-			j.out[1] = fb.x0[ref[b].j];
+			fold_side(ctx, j, 0, v.ref[a]);
+			fold_side(ctx, j, 1, v.ref[b]);
 			fused_arr[a] = fused_arr[b] = 1;
-			n_fused++;
+			cnt.fused++;
 		} else if (a != b && (waits_alone(a) || waits_alone(b))) {
 			// (the other array is shared, or up to date, or waits under another challenge: final by the time this launch runs)
 			const uint32_t own = waits_alone(a) ? a : b, other = own == a ? b : a;
-			const auto &fo = ctx->grp.folds[ref[own].f];
 			j.kind = 4;
-			j.z = fo.z;
-			j.x0[0] = fo.src0[ref[own].j];
-			j.x1[0] = fo.x1[ref[own].j];
-			j.out[0] = fo.x0[ref[own].j];
-			j.x0[1] = lo[other];
-			j.x1[1] = hi[other];
+			fold_side(ctx, j, 0, v.ref[own]);
+			plain_side(j, 1, v, other);
 			fused_arr[own] = 1;
-			n_fused++;
+			cnt.fused++;
 		} else {
-			j.kind = 1;
-			j.x0[0] = lo[a];
-			j.x1[0] = hi[a];
-			j.x0[1] = lo[b];
-			j.x1[1] = hi[b];
+			plain_side(j, 0, v, a);
+			plain_side(j, 1, v, b);
 		}
 		jobs.push_back(j);
 	}
-	for (uint32_t i = 0; i < m; i++) prefold[i] = (ref[i].f >= 0 && !fused_arr[i]) ? 1 : 0;
+	for (uint32_t i = 0; i < v.m; i++)
+		if (v.ref[i].f >= 0 && !fused_arr[i]) plain[v.ref[i]] = 1;
 }
 
 int unhost(bn_ctx *ctx, bn_ctx::group_session &s);
 
+// "The same prover": session s has the request's claims ...
+bool same_claims(const bn_ctx::group_session &s, const request &rq)
+{
+	if (s.m != rq.m || s.k != rq.k) return false;
+	for (uint32_t c = 0; c < rq.k; c++)
+		if (s.pa[c] != rq.pa[c] || s.pb[c] != rq.pb[c]) return false;
+	return true;
+}
+// ... over the request's arrays, (lo, hi) of len points being the view of the session's arrays that is meant: as last evaluated
+// (lo, hi, row_len), as the sums computed ahead saw them (pre_*), as the host holds them (h_lo, h_hi, h_len / 2)
+bool same_prover(const bn_ctx::group_session &s, const std::vector<const void *> &lo, const std::vector<const void *> &hi, uint64_t len, const request &rq)
+{
+	if (len != rq.row_len || !same_claims(s, rq)) return false;
+	for (uint32_t i = 0; i < rq.m; i++)
+		if (lo[i] != rq.lo[i] || hi[i] != rq.hi[i]) return false;
+	return true;
+}
+
+// the session of the request's prover: the one that evaluated these arrays last, or the arrays they were folded from (ref); a new
+// one otherwise.  nullptr (*rc_out set): making room needed a write-back and that failed.
 bn_ctx::group_session *session_for(bn_ctx *ctx, const request &rq, const fold_ref *ref, int *rc_out)
 {
 	auto &ss = ctx->grp.sessions;
-	auto same_claims = [&](const bn_ctx::group_session &s) {
-		if (s.m != rq.m || s.k != rq.k) return false;
-		for (uint32_t c = 0; c < rq.k; c++)
-			if (s.pa[c] != rq.pa[c] || s.pb[c] != rq.pb[c]) return false;
-		return true;
-	};
 	for (auto &s : ss) {
-		if (!same_claims(s)) continue;
-		bool cont = true, same = s.row_len == rq.row_len;
-		for (uint32_t i = 0; i < rq.m; i++) {
+		if (same_prover(s, s.lo, s.hi, s.row_len, rq)) return &s;
+		bool cont = same_claims(s, rq);
+		for (uint32_t i = 0; i < rq.m && cont; i++) {
 			if (ref[i].f < 0) {
 				cont = false;
 			} else {
 				const auto &g = ctx->grp.folds[ref[i].f];
-				if (g.src0[ref[i].j] != s.lo[i] || g.x1[ref[i].j] != s.hi[i] || g.n != s.row_len) cont = false;
+				cont = g.src0[ref[i].j] == s.lo[i] && g.x1[ref[i].j] == s.hi[i] && g.n == s.row_len;
 			}
-			if (s.lo[i] != rq.lo[i] || s.hi[i] != rq.hi[i]) same = false;
 		}
-		if (cont || same) return &s;
+		if (cont) return &s;
 	}
 	if (ss.size() >= kMaxSessions) {
 		// the least recently used description goes -- never one the host still owes a write-back for (its folded copies are the only
@@ -667,19 +744,6 @@ bool session_touches(const bn_ctx::group_session &s, const void *p, uint64_t n, 
 	return false;
 }
 
-int stage_alloc(bn_ctx *ctx)
-{
-	auto &g = ctx->grp;
-	if (g.h_stage) return BN_OK;
-	if (hipHostMalloc(&g.h_stage, 2 * bn::kGroupTailMaxElems * sizeof(f128), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-		(void)hipGetLastError();
-		g.h_stage = nullptr;
-		return BN_ERR_ALLOC;
-	}
-	BN_HIP(hipHostGetDevicePointer(&g.d_stage, g.h_stage, 0));
-	return BN_OK;
-}
-
 // the device catches up with the folds the host performed for session s; the session is an ordinary one again
 int unhost(bn_ctx *ctx, bn_ctx::group_session &s)
 {
@@ -711,6 +775,34 @@ int unhost(bn_ctx *ctx, bn_ctx::group_session &s)
 	return BN_OK;
 }
 
+// The host's copies of a hand-over (launch `seq`: count arrays of n elements) out of the pinned staging, into s.hy.  The staging
+// validates itself (kernels_group.hip k_group_mirror): accepted only when the tag computed from what is read is the tag the
+// kernel published.
+int read_staging(bn_ctx *ctx, bn_ctx::group_session &s, uint32_t count, uint64_t n, uint64_t seq)
+{
+	s.hy.resize(count); // (the copies keep their capacity from prove to prove)
+	for (uint32_t j = 0; j < count; j++) s.hy[j].resize(2 * (size_t)n);
+	const uint64_t *src = (const uint64_t *)ctx->grp.h_stage;
+	for (int tries = 0; tries < 4096; tries++) {
+		if (tries == 2048) BN_HIP(hipStreamSynchronize(ctx->stream));
+		const uint64_t want = __atomic_load_n(&ctx->h_mail[66].lo, __ATOMIC_ACQUIRE);
+		uint64_t t = seq, idx = 0;
+		for (uint32_t j = 0; j < count; j++) {
+			uint64_t *dst = s.hy[j].data();
+			const uint64_t *sj = src + 2 * (uint64_t)j * n;
+			for (uint64_t i = 0; i < n; i++, idx++) {
+				const uint64_t lo = __atomic_load_n(&sj[2 * i], __ATOMIC_RELAXED), hi = __atomic_load_n(&sj[2 * i + 1], __ATOMIC_RELAXED);
+				dst[2 * i] = lo;
+				dst[2 * i + 1] = hi;
+				const unsigned r1 = (unsigned)(idx & 63), r2 = (unsigned)((idx * 7 + 17) & 63);
+				t ^= ((lo << r1) | (lo >> ((64 - r1) & 63))) ^ ((hi << r2) | (hi >> ((64 - r2) & 63))) ^ (idx + 1) * 0x9E3779B97F4A7C15ull;
+			}
+		}
+		if (t == want) return BN_OK;
+	}
+	return bn::fail(BN_ERR_DEVICE, "device error: a hosted prover's staging never became consistent");
+}
+
 int unhost_touching(bn_ctx *ctx, const void *p, uint64_t n, bool write)
 {
 	for (auto &s : ctx->grp.sessions)
@@ -730,7 +822,7 @@ int unhost_all(bn_ctx *ctx)
 	return BN_OK;
 }
 
-void host_answer(bn_ctx *ctx, const bn_ctx::group_session &s, const request &rq, const uint32_t *ret_values, uint32_t n_ret, bn_f128 *h_out)
+void host_answer(bn_ctx *ctx, const bn_ctx::group_session &s, const request &rq)
 {
 	std::vector<f128> raw(2 * (size_t)rq.k);
 	const size_t half = (size_t)(s.h_len / 2);
@@ -740,14 +832,34 @@ void host_answer(bn_ctx *ctx, const bn_ctx::group_session &s, const request &rq,
 		raw[2 * c] = bn::hostpoly_to_tower(y1);
 		raw[2 * c + 1] = bn::hostpoly_to_tower(yi);
 	}
-	answer(rq, raw.data(), ret_values, n_ret, h_out);
+	answer(rq, raw.data());
 	ctx->grp.hosted_evals++;
 	ctx->grp.evals++;
 }
 
 } // namespace
 
-int group_res_alloc(bn_ctx *ctx) { return res_alloc(ctx); }
+// the pinned tables, accumulator slots and value mailbox of the group launches (allocated with the first of them)
+int group_res_alloc(bn_ctx *ctx)
+{
+	auto &g = ctx->grp;
+	if (g.h_tables && g.d_S && g.h_gmail) return BN_OK;
+	if (!g.h_tables) {
+		const int rc = pinned_mapped_alloc(&g.h_tables, &g.d_tables, sizeof(bn::group_tables), "claim groups: pinned job table");
+		if (rc) return rc;
+		std::memset(g.h_tables, 0, sizeof(bn::group_tables));
+	}
+	if (!g.h_gmail) {
+		const int rc = pinned_mapped_alloc((void **)&g.h_gmail, (void **)&g.d_gmail, sizeof(f128) * bn::kGroupMaxSlots, "claim groups: pinned value mailbox");
+		if (rc) return rc;
+		std::memset(g.h_gmail, 0, sizeof(f128) * bn::kGroupMaxSlots);
+	}
+	if (!g.d_S) {
+		BN_HIP(hipMalloc((void **)&g.d_S, sizeof(f128) * bn::kGroupMaxSlots));
+		BN_HIP(hipMemsetAsync(g.d_S, 0, sizeof(f128) * bn::kGroupMaxSlots, ctx->stream));
+	}
+	return BN_OK;
+}
 
 bool legacy_state_active(const bn_ctx *ctx)
 {
@@ -934,9 +1046,7 @@ int group_defer_fold(bn_ctx *ctx, void *const *x0, const void *const *src0, cons
 	bool clash = false;
 	for (uint32_t i = 0; i < count && !clash; i++)
 		clash = !group_independent(ctx, x0[i], n, true) || !group_independent(ctx, x1[i], n, false) || !group_independent(ctx, src0[i], n, false);
-	// ... and so is one that overlaps ITSELF: an output against any other range of the batch (the jobs of a launch run concurrently;
-	// an out-of-place fold whose output overlaps its own inputs).  One sweep over the ranges sorted by address: a range overlaps
-	// an earlier one exactly when it starts before the furthest end seen so far.
+	// ... and so is one that overlaps ITSELF (the jobs of a launch run concurrently)
 	if (!clash) clash = batch_overlaps_itself(x0, src0, x1, count, n);
 	bn_ctx::group_fold f;
 	f.n = n;
@@ -945,7 +1055,7 @@ int group_defer_fold(bn_ctx *ctx, void *const *x0, const void *const *src0, cons
 	if (clash) {
 		rc = group_flush(ctx);
 		if (rc) return rc;
-		return launch_fold(ctx, f);
+		return launch_fold(ctx, f, /*flush=*/true);
 	}
 	// the sums computed ahead describe arrays BEFORE this fold: a prover that folds without having asked for them has moved on
 	for (uint32_t i = 0; i < count; i++) drop_predictions_touching(ctx, x0[i], n);
@@ -967,7 +1077,7 @@ int group_flush(bn_ctx *ctx)
 	std::vector<bn_ctx::group_fold> todo;
 	todo.swap(g.folds);
 	for (const auto &f : todo) {
-		const int rc = launch_fold(ctx, f);
+		const int rc = launch_fold(ctx, f, /*flush=*/true);
 		if (rc) return rc;
 	}
 	return BN_OK;
@@ -1001,7 +1111,7 @@ int group_flush_touching(bn_ctx *ctx, const void *p, uint64_t n, bool publish_ti
 				for (uint32_t q = 0; q < f.count; q++) ctx->mirror.ptr[q] = f.x0[q];
 				continue;
 			}
-			const int rc = launch_fold(ctx, f);
+			const int rc = launch_fold(ctx, f, /*flush=*/true);
 			if (rc) return rc;
 		} else {
 			i++;
@@ -1013,55 +1123,42 @@ int group_flush_touching(bn_ctx *ctx, const void *p, uint64_t n, bool publish_ti
 
 void group_note_write(bn_ctx *ctx, const void *p, uint64_t n) { drop_predictions_touching(ctx, p, n); }
 
-int group_eval(bn_ctx *ctx, const bn_memmap *maps, uint32_t n_maps, const bn_kop *ops, uint32_t n_ops, const uint32_t *ret_values, uint32_t n_ret,
-               bn_f128 *h_out, bool *handled)
+// ---- group_eval: the routes of an evaluation, in the order they are tried -------------------------------------------------------
+
+// Route 3, hosted hit: a hosted prover's evaluation of exactly its current halves is host arithmetic.  Touches no other state.
+static bool hosted_hit(bn_ctx *ctx, const request &rq)
 {
-	*handled = false;
-	auto &g = ctx->grp;
-	if (!g.enabled || !ctx->lazy_fold || ctx->peer.active || ctx->tail_max_n_in || !h_out) return BN_OK;
-	phase_clock pc(g);
-	request rq;
-	if (!parse(maps, n_maps, ops, n_ops, ret_values, n_ret, rq)) return BN_OK;
-	pc.lap(bn_ctx::group_state::P_PARSE);
-	// ---- a hosted prover's evaluation of exactly its current halves: host arithmetic
-	for (auto &s : g.sessions) {
-		if (!s.hosted || s.m != rq.m || s.k != rq.k || s.h_len != 2 * rq.row_len) continue;
-		bool same = true;
-		for (uint32_t i = 0; i < rq.m && same; i++) same = s.h_lo[i] == rq.lo[i] && s.h_hi[i] == rq.hi[i];
-		for (uint32_t c = 0; c < rq.k && same; c++) same = s.pa[c] == rq.pa[c] && s.pb[c] == rq.pb[c];
-		if (!same) continue;
-		host_answer(ctx, s, rq, ret_values, n_ret, h_out);
-		s.stamp = ++g.stamp;
-		*handled = true;
-		pc.lap(bn_ctx::group_state::P_HOSTED);
-		return BN_OK;
+	for (auto &s : ctx->grp.sessions) {
+		if (!s.hosted || !same_prover(s, s.h_lo, s.h_hi, s.h_len / 2, rq)) continue;
+		host_answer(ctx, s, rq);
+		s.stamp = ++ctx->grp.stamp;
+		return true;
 	}
-	// ---- sums computed ahead for exactly this request?
+	return false;
+}
+
+// Route 4, ahead hit: an earlier launch computed the sums of exactly this request (its prover rode along).  The session now
+// describes the arrays just evaluated, so that the prover's next fold makes it a rider again.
+static bool ahead_hit(bn_ctx *ctx, const request &rq)
+{
+	auto &g = ctx->grp;
 	for (auto &s : g.sessions) {
-		if (!s.pre_valid || s.m != rq.m || s.k != rq.k || s.pre_row_len != rq.row_len) continue;
-		bool same = true;
-		for (uint32_t i = 0; i < rq.m && same; i++) same = s.pre_lo[i] == rq.lo[i] && s.pre_hi[i] == rq.hi[i];
-		for (uint32_t c = 0; c < rq.k && same; c++) same = s.pa[c] == rq.pa[c] && s.pb[c] == rq.pb[c];
-		if (!same) continue;
-		answer(rq, s.pre_raw.data(), ret_values, n_ret, h_out);
+		if (!s.pre_valid || !same_prover(s, s.pre_lo, s.pre_hi, s.pre_row_len, rq)) continue;
+		answer(rq, s.pre_raw.data());
 		record(ctx, s, rq);
 		g.spec_hits++;
 		g.evals++;
-		*handled = true;
-		return BN_OK;
+		return true;
 	}
-	// ---- is this a request for the group path at all?  One claim with nothing waiting is the single-claim machinery's.
-	// (one claim asked for by more than one pair of sums -- duplicate compositions -- is not: its look-ahead pairs nothing)
-	if (rq.k < 2 && rq.terms.size() <= 2 && g.folds.empty() && !g.on) return BN_OK;
-	int rc = legacy_to_group(ctx);
-	if (rc) return rc;
-	if (!ctx->pend_copies.empty()) {
-		rc = flush_copies(ctx); // (independent of every deferred fold, checked when they were deferred: any order)
-		if (rc) return rc;
-	}
-	// ---- the request's arrays against the deferred folds
-	fold_index fidx;
-	fold_ref ref[kMaxArrays];
+	return false;
+}
+
+// Step 7, match: ref[i] = the deferred fold whose output array i is (f < 0: the array is up to date in memory).  Leaves no
+// deferred fold that the request reads other than as its output, no write-back owed for memory it reads, and the launch's
+// pinned tables allocated.
+static int match(bn_ctx *ctx, const request &rq, fold_index &fidx, fold_ref *ref)
+{
+	int rc = BN_OK;
 	for (uint32_t i = 0; i < rq.m; i++) {
 		ref[i] = fidx.output(ctx, rq.lo[i], rq.hi[i], rq.row_len);
 		if (ref[i].f < 0 && (!group_independent(ctx, rq.lo[i], rq.row_len, false) || !group_independent(ctx, rq.hi[i], rq.row_len, false))) {
@@ -1073,348 +1170,301 @@ int group_eval(bn_ctx *ctx, const bn_memmap *maps, uint32_t n_maps, const bn_kop
 			for (uint32_t q = 0; q <= i; q++) ref[q] = fidx.output(ctx, rq.lo[q], rq.hi[q], rq.row_len);
 		}
 	}
-	// a request that reads what a hosted prover's pending write-back covers (but is not that prover's expected call, answered above)
+	// a request that reads what a hosted prover's pending write-back covers (but is not that prover's expected call: hosted_hit)
 	for (uint32_t i = 0; i < rq.m; i++) {
 		rc = unhost_touching(ctx, rq.lo[i], rq.row_len, false);
 		if (!rc) rc = unhost_touching(ctx, rq.hi[i], rq.row_len, false);
 		if (rc) return rc;
 	}
-	rc = group_res_alloc(ctx);
-	if (rc) return rc;
-	pc.lap(bn_ctx::group_state::P_MATCH);
+	return group_res_alloc(ctx);
+}
+
+// Route 8, hand-over: the prover is small enough to finish on the host -- all arrays contiguous, their deferred folds (if any)
+// under one challenge.  (The host's rounds cost products in proportion to (claims + arrays / 2) x elements: eight arrays under
+// four claims of 4096 elements each is the measured break-even, bn::kGroupTailWorkElems.)  ONE launch performs those folds and
+// mirrors the arrays into the staging; the prover's session is hosted from here on and answers this request.  Not this route
+// (*handled stays false, nothing touched): too large, not contiguous, two challenges, or no staging to be had.
+static int hand_over(bn_ctx *ctx, const request &rq, const fold_ref *ref, phase_clock &pc, bool *handled)
+{
+	auto &g = ctx->grp;
+	if (!(g.ht_max && 2 * rq.row_len <= g.ht_max && (uint64_t)rq.m * 2 * rq.row_len <= bn::kGroupTailMaxElems &&
+	      ((uint64_t)rq.k + (rq.m + 1) / 2) * 2 * rq.row_len <= g.ht_work &&
+	      (g.h_stage || pinned_mapped_alloc(&g.h_stage, &g.d_stage, 2 * bn::kGroupTailMaxElems * sizeof(f128), nullptr) == BN_OK)))
+		return BN_OK;
+	bn::group_mirror_args ma{};
+	bool any_fold = false;
+	for (uint32_t i = 0; i < rq.m; i++) {
+		if (rq.hi[i] != (const void *)at(rq.lo[i], rq.row_len)) return BN_OK;
+		if (ref[i].f < 0) continue;
+		const f128 zi = g.folds[ref[i].f].z;
+		if (any_fold && !(zi == ma.z)) return BN_OK;
+		ma.z = zi;
+		any_fold = true;
+	}
+	// (the session first: finding room for it may write another hosted prover's copies back, and that can fail -- before anything
+	// of this hand-over has been enqueued, so that a failure leaves every deferred fold exactly as it was)
+	int rc = BN_OK;
+	bn_ctx::group_session *hs = session_for(ctx, rq, ref, &rc);
+	if (!hs) return rc;
 	bn::group_tables *const h_tb = (bn::group_tables *)g.h_tables;
-	const bn::group_tables *const d_tb = (const bn::group_tables *)g.d_tables;
-	// ---- small enough to finish on the host?  (all arrays contiguous, their deferred folds -- if any -- with one challenge)
-	// (the host's rounds cost products in proportion to (claims + arrays / 2) x elements: eight arrays under four claims of 4096
-	// elements each is the measured break-even, bn::kGroupTailWorkElems)
-	if (g.ht_max && 2 * rq.row_len <= g.ht_max && (uint64_t)rq.m * 2 * rq.row_len <= bn::kGroupTailMaxElems &&
-	    ((uint64_t)rq.k + (rq.m + 1) / 2) * 2 * rq.row_len <= g.ht_work && stage_alloc(ctx) == BN_OK) {
-		bool ok = true, any_fold = false;
-		f128 z{0, 0};
-		for (uint32_t i = 0; i < rq.m && ok; i++) {
-			ok = rq.hi[i] == (const void *)at(rq.lo[i], rq.row_len);
-			if (ok && ref[i].f >= 0) {
-				const f128 zi = g.folds[ref[i].f].z;
-				if (any_fold && !(zi == z)) ok = false;
-				z = zi;
-				any_fold = true;
-			}
+	fold_mask done(g.folds); // the folds the hand-over performs
+	for (uint32_t i = 0; i < rq.m; i++) {
+		bn::group_job side{}; // (a job's side is the triple the mirror kernel reads; x1 == null: the array itself, nothing to fold)
+		if (ref[i].f >= 0) {
+			fold_side(ctx, side, 0, ref[i]);
+			done[ref[i]] = 1;
+		} else {
+			side.x0[0] = rq.lo[i];
 		}
-		// (the session first: finding room for it may write another hosted prover's copies back, and that can fail -- before anything
-		// of this hand-over has been enqueued, so that a failure leaves every deferred fold exactly as it was)
-		bn_ctx::group_session *hs = ok ? session_for(ctx, rq, ref, &rc) : nullptr;
-		if (ok && !hs) return rc;
-		if (ok) {
-			bn::group_mirror_args ma{};
-			ma.count = rq.m;
-			ma.n = (uint32_t)(2 * rq.row_len);
-			ma.z = z;
-			for (uint32_t i = 0; i < rq.m; i++) {
-				if (ref[i].f >= 0) {
-					const auto &f = g.folds[ref[i].f];
-					h_tb->mirror.src0[i] = f.src0[ref[i].j];
-					h_tb->mirror.x1[i] = f.x1[ref[i].j];
-					h_tb->mirror.out[i] = f.x0[ref[i].j];
-				} else {
-					h_tb->mirror.src0[i] = rq.lo[i];
-					h_tb->mirror.x1[i] = nullptr;
-					h_tb->mirror.out[i] = nullptr;
-				}
-			}
-			ma.ptrs = &d_tb->mirror;
-			ma.staging = (f128 *)g.d_stage;
-			ma.phi_tab = (const uint4 *)ctx->d_phi;
-			ma.tag_acc = ctx->d_ht_tag;
-			ma.counter = ctx->d_ticket;
-			ma.mail = ctx->d_mail;
-			ctx->mirror.valid = false;
-			ma.seq = ++ctx->mail_seq;
-			{
-				prof_scope ps(ctx, BN_PROF_FOLD_EVAL8);
-				const hipError_t e = bn::launch_group_mirror(ctx->stream, ma);
-				if (e != hipSuccess) {
-					--ctx->mail_seq; // (nothing was enqueued, nothing is retired)
-					return bn::hip_fail(e, "launch_group_mirror");
-				}
-			}
-			// retire the folds the hand-over performed; arrays of those batches that the request does not name are folded plainly
-			std::vector<std::vector<char>> done(g.folds.size());
-			for (size_t f = 0; f < g.folds.size(); f++) done[f].assign(g.folds[f].count, 0);
-			for (uint32_t i = 0; i < rq.m; i++)
-				if (ref[i].f >= 0) done[ref[i].f][ref[i].j] = 1;
-			for (size_t f = g.folds.size(); f-- > 0;) {
-				bool any = false;
-				for (uint32_t j = 0; j < g.folds[f].count; j++) any = any || done[f][j];
-				if (!any) continue;
-				bn_ctx::group_fold rest;
-				rest.n = g.folds[f].n;
-				rest.z = g.folds[f].z;
-				for (uint32_t j = 0; j < g.folds[f].count; j++)
-					if (!done[f][j]) rest.push(g.folds[f].x0[j], g.folds[f].x1[j], g.folds[f].src0[j]);
-				g.folds.erase(g.folds.begin() + (long)f);
-				if (rest.count) {
-					rc = launch_fold(ctx, rest);
-					ctx->grp.flushed_folds--;
-					if (rc) return rc;
-				}
-			}
-			g.on = true;
-			rc = mail_wait(ctx, ma.seq);
-			if (rc) return rc;
-			pc.lap(bn_ctx::group_state::P_HOST_WAIT);
-			// the staging validates itself (kernels_group.hip k_group_mirror): accepted only when the tag computed from what is read is
-			// the tag the kernel published
-			record(ctx, *hs, rq);
-			hs->hy.resize(rq.m); // (the copies keep their capacity from prove to prove)
-			for (uint32_t j = 0; j < rq.m; j++) hs->hy[j].resize(2 * (size_t)ma.n);
-			const uint64_t *src = (const uint64_t *)g.h_stage;
-			bool valid = false;
-			for (int tries = 0; tries < 4096 && !valid; tries++) {
-				if (tries == 2048) BN_HIP(hipStreamSynchronize(ctx->stream));
-				const uint64_t want = __atomic_load_n(&ctx->h_mail[66].lo, __ATOMIC_ACQUIRE);
-				uint64_t t = ma.seq, idx = 0;
-				for (uint32_t j = 0; j < rq.m; j++) {
-					uint64_t *dst = hs->hy[j].data();
-					const uint64_t *sj = src + 2 * (uint64_t)j * ma.n;
-					for (uint64_t i = 0; i < ma.n; i++, idx++) {
-						const uint64_t lo = __atomic_load_n(&sj[2 * i], __ATOMIC_RELAXED), hi = __atomic_load_n(&sj[2 * i + 1], __ATOMIC_RELAXED);
-						dst[2 * i] = lo;
-						dst[2 * i + 1] = hi;
-						const unsigned r1 = (unsigned)(idx & 63), r2 = (unsigned)((idx * 7 + 17) & 63);
-						t ^= ((lo << r1) | (lo >> ((64 - r1) & 63))) ^ ((hi << r2) | (hi >> ((64 - r2) & 63))) ^ (idx + 1) * 0x9E3779B97F4A7C15ull;
-					}
-				}
-				valid = t == want;
-			}
-			if (!valid) return bn::fail(BN_ERR_DEVICE, "device error: a hosted prover's staging never became consistent");
-			pc.lap(bn_ctx::group_state::P_HOST_COPY);
-			hs->hosted = true;
-			hs->h_len = ma.n;
-			hs->h_levels = 0;
-			hs->h_n0 = 0;
-			hs->h_lo.assign(rq.lo, rq.lo + rq.m);
-			hs->h_hi.assign(rq.hi, rq.hi + rq.m);
-			hs->h_out.assign(rq.m, nullptr);
-			g.hosted_started++;
-			host_answer(ctx, *hs, rq, ret_values, n_ret, h_out);
-			*handled = true;
-			pc.lap(bn_ctx::group_state::P_HOSTED);
-			return BN_OK;
+		h_tb->mirror.src0[i] = side.x0[0];
+		h_tb->mirror.x1[i] = side.x1[0];
+		h_tb->mirror.out[i] = side.out[0];
+	}
+	ma.count = rq.m;
+	ma.n = (uint32_t)(2 * rq.row_len);
+	ma.ptrs = &((const bn::group_tables *)g.d_tables)->mirror;
+	ma.staging = (f128 *)g.d_stage;
+	ma.phi_tab = (const uint4 *)ctx->d_phi;
+	ma.tag_acc = ctx->d_ht_tag;
+	ma.counter = ctx->d_ticket;
+	ma.mail = ctx->d_mail;
+	ctx->mirror.valid = false;
+	ma.seq = ++ctx->mail_seq;
+	{
+		prof_scope ps(ctx, BN_PROF_FOLD_EVAL8);
+		const hipError_t e = bn::launch_group_mirror(ctx->stream, ma);
+		if (e != hipSuccess) {
+			--ctx->mail_seq; // (nothing was enqueued, nothing is retired)
+			return bn::hip_fail(e, "launch_group_mirror");
 		}
 	}
+	// retire the folds the hand-over performed; arrays of those batches that the request does not name are folded plainly
+	rc = drop_marked(ctx, done, /*launch_rest=*/true);
+	if (rc) return rc;
+	g.on = true;
+	rc = mail_wait(ctx, ma.seq);
+	if (rc) return rc;
+	pc.lap(bn_ctx::group_state::P_HOST_WAIT);
+	record(ctx, *hs, rq);
+	rc = read_staging(ctx, *hs, rq.m, ma.n, ma.seq);
+	if (rc) return rc;
+	pc.lap(bn_ctx::group_state::P_HOST_COPY);
+	hs->hosted = true;
+	hs->h_len = ma.n;
+	hs->h_levels = 0;
+	hs->h_n0 = 0;
+	hs->h_lo.assign(rq.lo, rq.lo + rq.m);
+	hs->h_hi.assign(rq.hi, rq.hi + rq.m);
+	hs->h_out.assign(rq.m, nullptr);
+	g.hosted_started++;
+	host_answer(ctx, *hs, rq);
+	*handled = true;
+	pc.lap(bn_ctx::group_state::P_HOSTED);
+	return BN_OK;
+}
+
+// The other provers whose fold is waiting (every array of the last evaluation the input of a deferred fold that nobody has taken)
+// and whose claims are known.  Marks their folds consumed; their sums go to the slots from n_slots on.
+static std::vector<rider> collect_riders(bn_ctx *ctx, const bn_ctx::group_session *self, uint32_t n_claims, fold_index &fidx, fold_mask &consumed, uint32_t &n_slots)
+{
+	auto &g = ctx->grp;
+	std::vector<rider> riders;
+	for (auto &s : g.sessions) {
+		if (&s == self || s.hosted || s.k == 0 || s.row_len < 2) continue;
+		if (n_claims + s.k > (uint32_t)bn::kGroupMaxJobs || n_slots + 2 * s.k > (uint32_t)bn::kGroupMaxSlots) continue;
+		rider r{&s, {}, std::vector<fold_ref>(s.m), std::vector<const void *>(s.m), std::vector<const void *>(s.m)};
+		bool ok = true;
+		fidx.hint = fold_ref{};
+		for (uint32_t i = 0; i < s.m && ok; i++) {
+			r.ref[i] = fidx.input(ctx, s.lo[i], s.hi[i], s.row_len);
+			ok = r.ref[i].f >= 0 && !consumed[r.ref[i]];
+			if (ok) {
+				r.lo[i] = g.folds[r.ref[i].f].x0[r.ref[i].j];
+				r.hi[i] = at(r.lo[i], s.row_len / 2);
+			}
+		}
+		if (!ok) continue;
+		r.v = prover_view{s.m, s.k, s.pa.data(), s.pb.data(), r.lo.data(), r.hi.data(), s.row_len / 2, r.ref.data(), n_slots};
+		n_slots += 2 * s.k;
+		n_claims += s.k;
+		for (uint32_t i = 0; i < s.m; i++) consumed[r.ref[i]] = 1;
+		riders.push_back(std::move(r)); // (a moved vector keeps its elements where they are: the view stays good)
+	}
+	return riders;
+}
+
+// the jobs of one prover, chained where the arrays are large enough and chains are allowed, with plain folds in front otherwise
+static bool plan_prover(bn_ctx *ctx, bool allow_chains, const prover_view &v, std::vector<bn::group_job> &jobs, fold_mask &plain, plan_counts &cnt)
+{
+	const size_t cap = (size_t)bn::kGroupMaxJobs; // (more jobs than workgroups: the launcher packs them, kernels_group.hip)
+	if (jobs.size() > cap) return false;
+	if (allow_chains && v.row_len >= ctx->grp.chain_min_rows) return plan_chained(ctx, v, cap - jobs.size(), jobs, cnt);
+	plan_prefold(ctx, v, jobs, plain, cnt);
+	return jobs.size() <= cap;
+}
+
+// The jobs of the launch: the caller's, the riders', the loose arrays'.  Chained planning (large arrays): every waiting fold is
+// a job of the launch; otherwise: marked in `plain` -- a plain fold launch in front -- whatever a fused job does not fold.
+// Chains pay where the arrays are large -- the shared arrays' folds cost no pass of their own -- and lose where a launch is
+// latency-bound: the jobs of a chain run one after the other on one set of workgroups (measured, 2 x 2 claims: 474 against
+// 537 us at 2^24 elements per array, 152 against 143 at 2^22, 39 against 17 at 2^14; profiles/r05).  Per prover by size.
+// false: more than kGroupMaxJobs jobs.
+static bool plan_round(bn_ctx *ctx, bool allow_chains, const prover_view &self, const std::vector<rider> &riders, const std::vector<fold_ref> &loose,
+                       std::vector<bn::group_job> &jobs, fold_mask &plain, plan_counts &cnt)
+{
+	const auto &g = ctx->grp;
+	jobs.clear();
+	cnt = plan_counts{};
+	plain = fold_mask(g.folds);
+	if (!plan_prover(ctx, allow_chains, self, jobs, plain, cnt)) return false;
+	for (const auto &r : riders)
+		if (!plan_prover(ctx, allow_chains, r.v, jobs, plain, cnt)) return false;
+	for (size_t q = 0; q < loose.size();) {
+		const auto &f = g.folds[loose[q].f];
+		if (!allow_chains || f.n / 2 < g.chain_min_rows || f.n < 2 || (f.n & 1)) {
+			plain[loose[q]] = 1;
+			q++;
+			continue;
+		}
+		bn::group_job j{};
+		j.kind = 3;
+		j.n = f.n / 2;
+		const bool two = q + 1 < loose.size() && loose[q + 1].f == loose[q].f;
+		fold_side(ctx, j, 0, loose[q]);
+		if (two) fold_side(ctx, j, 1, loose[q + 1]);
+		jobs.push_back(j);
+		cnt.fold_only++;
+		q += two ? 2 : 1;
+	}
+	return jobs.size() <= (size_t)bn::kGroupMaxJobs;
+}
+
+// The plain fold launches in front of the group launch (prefolds): the marked entries of every batch.  The provers of a batch
+// round fold by ONE challenge (front_loaded.rs:122-155): their plain folds -- arrays of different lengths -- are one launch
+// while the whole is launch-bound.  The entries stay in grp.folds: the caller retires them with everything the launch consumed.
+static int launch_prefolds(bn_ctx *ctx, const fold_mask &plain)
+{
+	auto &g = ctx->grp;
+	std::vector<bn_ctx::group_fold> parts;
+	for (size_t f = 0; f < g.folds.size(); f++) {
+		bn_ctx::group_fold part = entries_where(g.folds[f], plain.bit[f], true);
+		if (part.count) parts.push_back(std::move(part));
+	}
+	bool merged = parts.size() >= 2;
+	uint64_t arrays = 0, elems = 0;
+	for (const auto &pt : parts) {
+		merged = merged && pt.z == parts[0].z;
+		arrays += pt.count;
+		elems += (uint64_t)pt.count * pt.n;
+	}
+	merged = merged && arrays <= (uint64_t)bn::kFoldBatchMax && elems < ((uint64_t)1 << 25);
+	if (merged) {
+		bn::fold_batch fb{};
+		bn::fold_lengths fl{};
+		uint32_t c = 0;
+		for (const auto &pt : parts) {
+			fill_batch(fb, c, pt, 0, pt.count);
+			for (uint32_t i = 0; i < pt.count; i++) fl.n[c++] = pt.n;
+		}
+		prof_scope ps(ctx, BN_PROF_FOLD);
+		BN_HIP(bn::launch_extrapolate_line_ragged(ctx->stream, ctx->n_cu, fb, fl, c, parts[0].z));
+		g.prefolds++;
+		return BN_OK;
+	}
+	for (const auto &pt : parts) {
+		const int rc = launch_fold(ctx, pt, /*flush=*/false); // (part of the round)
+		if (rc) return rc;
+		g.prefolds++;
+	}
+	return BN_OK;
+}
+
+// launch_group failed with e and enqueued nothing: the folds its jobs would have performed are still deferred; those a plain
+// launch in front has performed (`plain`: all of them were enqueued) are retired.  Then everything runs eagerly.
+static int launch_refused(bn_ctx *ctx, const fold_mask &plain, hipError_t e)
+{
+	--ctx->mail_seq;
+	(void)hipGetLastError();
+	int rc = drop_marked(ctx, plain, /*launch_rest=*/false);
+	if (!rc) rc = group_flush(ctx);
+	if (rc) return rc;
+	if (e == hipErrorNotSupported) return BN_OK; // (the eager kernels answer from up-to-date memory)
+	return bn::hip_fail(e, "launch_group");
+}
+
+// the rider's session learns the sums computed ahead for it, and of which arrays: what ahead_hit compares and what a write
+// into those arrays (drop_predictions_touching, by the hull first) ends
+static void record_ahead(const rider &r, const std::vector<f128> &raw)
+{
+	bn_ctx::group_session &s = *r.s;
+	s.pre_valid = true;
+	s.pre_row_len = r.v.row_len;
+	s.pre_lo = r.lo;
+	s.pre_hi = r.hi;
+	s.pre_hull_b = s.pre_hull_e = nullptr;
+	for (uint32_t i = 0; i < s.m; i++)
+		for (const void *q : {r.lo[i], r.hi[i]}) {
+			const char *b0 = (const char *)q, *e0 = b0 + r.v.row_len * sizeof(f128);
+			if (!s.pre_hull_b || b0 < s.pre_hull_b) s.pre_hull_b = b0;
+			if (!s.pre_hull_e || e0 > s.pre_hull_e) s.pre_hull_e = e0;
+		}
+	s.pre_raw.assign(raw.begin() + r.v.slot0, raw.begin() + r.v.slot0 + 2 * s.k);
+}
+
+// Route 9, launch: ONE launch of kernels_group.hip evaluates the request's claims, performs the deferred folds its arrays wait
+// for, and carries the riders.  *handled stays false where the jobs do not fit a launch's table, or the launcher does not
+// support the shape: nothing is left deferred that the eager kernels would miss.
+static int launch_round(bn_ctx *ctx, const request &rq, const fold_ref *ref, fold_index &fidx, phase_clock &pc, bool *handled)
+{
+	auto &g = ctx->grp;
+	int rc = BN_OK;
 	bn_ctx::group_session *self = session_for(ctx, rq, ref, &rc);
 	if (!self) return rc;
-	// consumed[f][j]: array j of deferred fold f is brought up to date by this launch (a job of it, or a plain launch in front)
-	std::vector<std::vector<char>> consumed(g.folds.size());
-	for (size_t f = 0; f < g.folds.size(); f++) consumed[f].assign(g.folds[f].count, 0);
+	const prover_view me{rq.m, rq.k, rq.pa, rq.pb, rq.lo, rq.hi, rq.row_len, ref, 0};
+	// consumed: the entries of the deferred folds this launch brings up to date (a job of it, or a plain launch in front)
+	fold_mask consumed(g.folds);
 	for (uint32_t i = 0; i < rq.m; i++)
-		if (ref[i].f >= 0) consumed[ref[i].f][ref[i].j] = 1;
-	// ---- the other provers whose fold is waiting and whose claims are known: their next evaluation rides along
-	struct rider {
-		bn_ctx::group_session *s;
-		uint32_t slot0;
-		std::vector<fold_ref> ref;
-		std::vector<const void *> lo, hi;
-		uint64_t row_len;
-	};
+		if (ref[i].f >= 0) consumed[ref[i]] = 1;
+	uint32_t n_slots = 2 * rq.k;
 	std::vector<rider> riders;
-	uint32_t n_slots = 2 * rq.k, n_claims = rq.k;
-	if (g.speculate) {
-		for (auto &s : g.sessions) {
-			if (&s == self || s.hosted || s.k == 0 || s.row_len < 2) continue;
-			if (n_claims + s.k > (uint32_t)bn::kGroupMaxJobs || n_slots + 2 * s.k > (uint32_t)bn::kGroupMaxSlots) continue;
-			rider r{};
-			r.s = &s;
-			r.row_len = s.row_len / 2;
-			r.ref.resize(s.m);
-			r.lo.resize(s.m);
-			r.hi.resize(s.m);
-			bool ok = true;
-			fidx.hint = fold_ref{};
-			for (uint32_t i = 0; i < s.m && ok; i++) {
-				r.ref[i] = fidx.input(ctx, s.lo[i], s.hi[i], s.row_len);
-				ok = r.ref[i].f >= 0 && !consumed[r.ref[i].f][r.ref[i].j];
-				if (ok) {
-					r.lo[i] = g.folds[r.ref[i].f].x0[r.ref[i].j];
-					r.hi[i] = at(r.lo[i], r.row_len);
-				}
-			}
-			if (!ok) continue;
-			r.slot0 = n_slots;
-			n_slots += 2 * s.k;
-			n_claims += s.k;
-			for (uint32_t i = 0; i < s.m; i++) consumed[r.ref[i].f][r.ref[i].j] = 1;
-			riders.push_back(std::move(r));
-		}
-	}
+	if (g.speculate) riders = collect_riders(ctx, self, rq.k, fidx, consumed, n_slots);
 	// arrays of the participating provers' batches that appear in no request (an unconstrained column) are folded with them, so
 	// that the batch can be retired
-	std::vector<std::pair<int, int>> loose;
+	std::vector<fold_ref> loose;
 	for (size_t f = 0; f < g.folds.size(); f++) {
-		bool any = false;
-		for (uint32_t j = 0; j < g.folds[f].count; j++) any = any || consumed[f][j];
-		if (!any) continue;
+		if (!consumed.any(f)) continue;
 		for (uint32_t j = 0; j < g.folds[f].count; j++)
-			if (!consumed[f][j]) {
-				consumed[f][j] = 1;
-				loose.push_back({(int)f, (int)j});
+			if (!consumed.bit[f][j]) {
+				consumed.bit[f][j] = 1;
+				loose.push_back(fold_ref{(int)f, (int)j});
 			}
 	}
-	// ---- the jobs.  Chained planning (large arrays): every waiting fold is a job of the launch; otherwise, and where that does not
-	// fit (more than kGroupMaxJobs jobs): plain fold launches in front for everything a fused job does not fold
 	std::vector<bn::group_job> jobs;
-	uint64_t n_fused = 0, n_fold_only = 0, n_chains = 0;
-	std::vector<std::vector<char>> ran(g.folds.size()); // folded by a plain launch that has been enqueued
-	for (size_t f = 0; f < g.folds.size(); f++) ran[f].assign(g.folds[f].count, 0);
-	std::vector<std::vector<char>> plain(g.folds.size()); // folded by a plain launch in front of the group launch
-	// Chains pay where the arrays are large -- the shared arrays' folds cost no pass of their own -- and lose where a launch is
-	// latency-bound: the jobs of a chain run one after the other on one set of workgroups (measured, 2 x 2 claims: 474 against
-	// 537 us at 2^24 elements per array, 152 against 143 at 2^22, 39 against 17 at 2^14; profiles/r05).  Per prover by size.
-	const size_t cap = (size_t)bn::kGroupMaxJobs; // (more jobs than workgroups: the launcher packs them, kernels_group.hip)
-	auto plan_all = [&](bool allow_chains) {
-		jobs.clear();
-		n_fused = n_fold_only = n_chains = 0;
-		for (size_t f = 0; f < g.folds.size(); f++) plain[f].assign(g.folds[f].count, 0);
-		auto one = [&](uint32_t m, uint32_t k, const uint16_t *pa, const uint16_t *pb, const void *const *lo, const void *const *hi, uint64_t row_len, const fold_ref *rf,
-		               uint32_t slot0) {
-			if (jobs.size() > cap) return false;
-			if (allow_chains && row_len >= g.chain_min_rows)
-				return plan_chained(ctx, m, k, pa, pb, lo, hi, row_len, rf, slot0, cap - jobs.size(), jobs, n_fused, n_fold_only, n_chains);
-			std::vector<char> pf(m, 0);
-			plan_prefold(ctx, m, k, pa, pb, lo, hi, row_len, rf, slot0, jobs, pf, n_fused);
-			for (uint32_t i = 0; i < m; i++)
-				if (pf[i]) plain[rf[i].f][rf[i].j] = 1;
-			return jobs.size() <= cap;
-		};
-		if (!one(rq.m, rq.k, rq.pa, rq.pb, rq.lo, rq.hi, rq.row_len, ref, 0)) return false;
-		for (const auto &r : riders)
-			if (!one(r.s->m, r.s->k, r.s->pa.data(), r.s->pb.data(), r.lo.data(), r.hi.data(), r.row_len, r.ref.data(), r.slot0)) return false;
-		for (size_t q = 0; q < loose.size();) {
-			const auto &f = g.folds[loose[q].first];
-			if (!allow_chains || f.n / 2 < g.chain_min_rows || f.n < 2 || (f.n & 1)) {
-				plain[loose[q].first][loose[q].second] = 1;
-				q++;
-				continue;
-			}
-			bn::group_job j{};
-			j.kind = 3;
-			j.n = f.n / 2;
-			j.z = f.z;
-			const bool two = q + 1 < loose.size() && loose[q + 1].first == loose[q].first;
-			for (int sd = 0; sd < (two ? 2 : 1); sd++) {
-				const int jj = loose[q + sd].second;
-				j.x0[sd] = f.src0[jj];
-				j.x1[sd] = f.x1[jj];
-				j.out[sd] = f.x0[jj];
-			}
-			jobs.push_back(j);
-			n_fold_only++;
-			q += two ? 2 : 1;
-		}
-		return jobs.size() <= cap;
-	};
-	if (!plan_all(true) && !plan_all(false)) return BN_OK; // (more jobs than a launch's table holds; nothing has been enqueued: the eager kernels answer)
-	{
-		std::vector<bn_ctx::group_fold> parts;
-		std::vector<size_t> part_of;
-		for (size_t f = 0; f < g.folds.size(); f++) {
-			bn_ctx::group_fold part;
-			part.n = g.folds[f].n;
-			part.z = g.folds[f].z;
-			for (uint32_t j = 0; j < g.folds[f].count; j++)
-				if (plain[f][j]) part.push(g.folds[f].x0[j], g.folds[f].x1[j], g.folds[f].src0[j]);
-			if (part.count) {
-				parts.push_back(std::move(part));
-				part_of.push_back(f);
-			}
-		}
-		// the provers of a batch round fold by ONE challenge (front_loaded.rs:122-155): their plain folds -- arrays of different
-		// lengths -- are one launch while the whole is launch-bound
-		bool merged = parts.size() >= 2;
-		uint64_t arrays = 0, elems = 0;
-		for (const auto &pt : parts) {
-			merged = merged && pt.z == parts[0].z;
-			arrays += pt.count;
-			elems += (uint64_t)pt.count * pt.n;
-		}
-		merged = merged && arrays <= (uint64_t)bn::kFoldBatchMax && elems < ((uint64_t)1 << 25);
-		if (merged) {
-			bn::fold_batch fb{};
-			bn::fold_lengths fl{};
-			uint32_t c = 0;
-			for (const auto &pt : parts)
-				for (uint32_t i = 0; i < pt.count; i++, c++) {
-					fb.x0[c] = pt.x0[i];
-					fb.x1[c] = pt.x1[i];
-					fb.src0[c] = pt.src0[i] != pt.x0[i] ? pt.src0[i] : nullptr;
-					fl.n[c] = pt.n;
-				}
-			{
-				prof_scope ps(ctx, BN_PROF_FOLD);
-				BN_HIP(bn::launch_extrapolate_line_ragged(ctx->stream, ctx->n_cu, fb, fl, c, parts[0].z));
-			}
-			g.prefolds++;
-		} else {
-			for (const auto &pt : parts) {
-				rc = launch_fold(ctx, pt);
-				ctx->grp.flushed_folds--; // (not a flush: part of the round)
-				if (rc) return rc;
-				g.prefolds++;
-			}
-		}
-		for (size_t q = 0; q < parts.size(); q++)
-			for (uint32_t j = 0; j < g.folds[part_of[q]].count; j++)
-				if (plain[part_of[q]][j]) ran[part_of[q]][j] = 1;
-	}
+	plan_counts cnt;
+	fold_mask plain(g.folds); // folded by a plain launch in front of the group launch
+	if (!plan_round(ctx, true, me, riders, loose, jobs, plain, cnt) && !plan_round(ctx, false, me, riders, loose, jobs, plain, cnt))
+		return BN_OK; // (more jobs than a launch's table holds; nothing has been enqueued: the eager kernels answer)
+	rc = launch_prefolds(ctx, plain);
+	if (rc) return rc;
 	for (const auto &r : riders) g.spec_jobs += r.s->k;
 	pc.lap(bn_ctx::group_state::P_PLAN);
-	// ---- the launch
 	ctx->mirror.valid = false;
 	const uint64_t seq = ++ctx->mail_seq;
 	{
-		prof_scope ps(ctx, (n_fused || n_fold_only) ? BN_PROF_FOLD_EVAL_MFMA : BN_PROF_ROUND_EVAL_MFMA); // (a launch without a fold: round 0)
+		prof_scope ps(ctx, (cnt.fused || cnt.fold_only) ? BN_PROF_FOLD_EVAL_MFMA : BN_PROF_ROUND_EVAL_MFMA); // (a launch without a fold: round 0)
+		bn::group_tables *const h_tb = (bn::group_tables *)g.h_tables;
 		const hipError_t e = bn::launch_group(ctx->stream, ctx->n_cu, jobs.data(), (uint32_t)jobs.size(), n_slots, g.d_S, g.d_gmail, ctx->d_mail, ctx->d_ticket, seq,
-		                                      h_tb->jobs, d_tb->jobs);
-		if (e != hipSuccess) {
-			// nothing was enqueued by the failed launch: the folds its jobs would have performed are still deferred; those a plain
-			// launch in front has performed (the fallback) are retired.  Then everything runs eagerly.
-			--ctx->mail_seq;
-			(void)hipGetLastError();
-			for (size_t f = g.folds.size(); f-- > 0;) {
-				bn_ctx::group_fold rest;
-				rest.n = g.folds[f].n;
-				rest.z = g.folds[f].z;
-				for (uint32_t j = 0; j < g.folds[f].count; j++)
-					if (!ran[f][j]) rest.push(g.folds[f].x0[j], g.folds[f].x1[j], g.folds[f].src0[j]);
-				if (rest.count)
-					g.folds[f] = std::move(rest);
-				else
-					g.folds.erase(g.folds.begin() + (long)f);
-			}
-			rc = group_flush(ctx);
-			if (rc) return rc;
-			if (e == hipErrorNotSupported) return BN_OK; // (the eager kernels answer from up-to-date memory)
-			return bn::hip_fail(e, "launch_group");
-		}
+		                                      h_tb->jobs, ((const bn::group_tables *)g.d_tables)->jobs);
+		if (e != hipSuccess) return launch_refused(ctx, plain, e);
 	}
 	g.launches++;
-	g.jobs_fused += n_fused;
-	g.jobs_fold += n_fold_only;
-	g.chain_count += n_chains;
-	g.jobs_eval += jobs.size() - n_fused - n_fold_only;
-	// retire the consumed arrays
-	for (size_t f = g.folds.size(); f-- > 0;) {
-		bn_ctx::group_fold rest;
-		rest.n = g.folds[f].n;
-		rest.z = g.folds[f].z;
-		for (uint32_t j = 0; j < g.folds[f].count; j++)
-			if (!consumed[f][j]) rest.push(g.folds[f].x0[j], g.folds[f].x1[j], g.folds[f].src0[j]);
-		if (rest.count)
-			g.folds[f] = std::move(rest);
-		else
-			g.folds.erase(g.folds.begin() + (long)f);
-	}
-	g.on = true;
+	g.jobs_fused += cnt.fused;
+	g.jobs_fold += cnt.fold_only;
+	g.chain_count += cnt.chains;
+	g.jobs_eval += jobs.size() - cnt.fused - cnt.fold_only;
+	rc = drop_marked(ctx, consumed, /*launch_rest=*/false); // retire what the launch consumed ...
+	if (rc) return rc;
+	g.on = true; // ... and only then
 	pc.lap(bn_ctx::group_state::P_LAUNCH);
 	rc = mail_wait(ctx, seq);
 	if (rc) return rc;
@@ -1424,27 +1474,59 @@ int group_eval(bn_ctx *ctx, const bn_memmap *maps, uint32_t n_maps, const bn_kop
 		raw[i].lo = __atomic_load_n(&g.h_gmail[i].lo, __ATOMIC_RELAXED);
 		raw[i].hi = __atomic_load_n(&g.h_gmail[i].hi, __ATOMIC_RELAXED);
 	}
-	answer(rq, raw.data(), ret_values, n_ret, h_out);
+	answer(rq, raw.data());
 	record(ctx, *self, rq);
-	for (const auto &r : riders) {
-		bn_ctx::group_session &s = *r.s;
-		s.pre_valid = true;
-		s.pre_row_len = r.row_len;
-		s.pre_lo = r.lo;
-		s.pre_hi = r.hi;
-		s.pre_hull_b = s.pre_hull_e = nullptr;
-		for (uint32_t i = 0; i < s.m; i++)
-			for (const void *q : {r.lo[i], r.hi[i]}) {
-				const char *b0 = (const char *)q, *e0 = b0 + r.row_len * sizeof(f128);
-				if (!s.pre_hull_b || b0 < s.pre_hull_b) s.pre_hull_b = b0;
-				if (!s.pre_hull_e || e0 > s.pre_hull_e) s.pre_hull_e = e0;
-			}
-		s.pre_raw.assign(raw.begin() + r.slot0, raw.begin() + r.slot0 + 2 * s.k);
-	}
+	for (const auto &r : riders) record_ahead(r, raw);
 	g.evals++;
 	*handled = true;
 	pc.lap(bn_ctx::group_state::P_ANSWER);
 	return BN_OK;
+}
+
+// The route order of an evaluation request (the header comment of this file).  *handled == false with BN_OK: the single-claim
+// dispatcher answers.
+int group_eval(bn_ctx *ctx, const bn_memmap *maps, uint32_t n_maps, const bn_kop *ops, uint32_t n_ops, const uint32_t *ret_values, uint32_t n_ret,
+               bn_f128 *h_out, bool *handled)
+{
+	*handled = false;
+	auto &g = ctx->grp;
+	// 1. the gate
+	if (!g.enabled || !ctx->lazy_fold || ctx->peer.active || ctx->tail_max_n_in || !h_out) return BN_OK;
+	phase_clock pc(g);
+	// 2. parse.  (Up to "not ours" this runs in front of EVERY kernel launch, the single-claim benchmark's included: no state is
+	// touched, nothing is allocated, hashed or copied for it.)
+	request rq;
+	if (!parse(maps, n_maps, ops, n_ops, ret_values, n_ret, rq)) return BN_OK;
+	rq.ret_values = ret_values;
+	rq.n_ret = n_ret;
+	rq.h_out = h_out;
+	pc.lap(bn_ctx::group_state::P_PARSE);
+	// 3. hosted hit
+	if ((*handled = hosted_hit(ctx, rq))) {
+		pc.lap(bn_ctx::group_state::P_HOSTED);
+		return BN_OK;
+	}
+	// 4. ahead hit
+	if ((*handled = ahead_hit(ctx, rq))) return BN_OK;
+	// 5. not ours: one claim with nothing waiting is the single-claim machinery's.  (One claim asked for by more than one pair of
+	// sums -- duplicate compositions -- is ours: the single-claim look-ahead pairs nothing there.)
+	if (rq.k < 2 && rq.terms.size() <= 2 && g.folds.empty() && !g.on) return BN_OK;
+	// 6. make room: the single-claim state gives way; deferred copies run (independent of every deferred fold, checked when they
+	// were deferred: any order)
+	int rc = legacy_to_group(ctx);
+	if (!rc && !ctx->pend_copies.empty()) rc = flush_copies(ctx);
+	if (rc) return rc;
+	// 7. match
+	fold_index fidx;
+	fold_ref ref[kMaxArrays];
+	rc = match(ctx, rq, fidx, ref);
+	if (rc) return rc;
+	pc.lap(bn_ctx::group_state::P_MATCH);
+	// 8. hand-over
+	rc = hand_over(ctx, rq, ref, pc, handled);
+	if (rc || *handled) return rc;
+	// 9. launch
+	return launch_round(ctx, rq, ref, fidx, pc, handled);
 }
 
 } // namespace bnabi
