@@ -116,9 +116,21 @@ __device__ __forceinline__ void acc4_zero(v16f (&acc)[kAccTiles])
 			acc[t][r] = 0.0f;
 }
 
-#define BN_GRAM4_MFMA(t, A, B)                                                                                                             \
-	acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(v8i{(A).x, (A).y, (A).z, (A).w, 0, 0, 0, 0}, v8i{(B).x, (B).y, (B).z, (B).w, 0, 0, 0, 0}, \
-	                                                         acc[t], 4, 4, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F)
+// The one FP4 matrix instruction of the library (the Gram steps here and kernels_linmap.hip): 32 x 32 x 64, both operands E2M1, no
+// block scales.  With both scale arguments 0 the builtin compiles to the 8-byte v_mfma_f32_32x32x64_f8f6f4 cbsz:4 blgp:4 alone;
+// with scales of 2^0 (0x7F in every byte) it compiles to the 16-byte scaled form, whose first word loads the scales from a
+// register that holds 0x7F7F7F7F.  The accumulators are the same bit for bit (tools/fp4_probe.hip).  -DBN_FP4_SCALED_MFMA builds
+// the scaled form: the A/B of profiles/r26.
+#ifdef BN_FP4_SCALED_MFMA
+#define BN_FP4_MFMA_SCALES 0x7F7F7F7F
+#else
+#define BN_FP4_MFMA_SCALES 0
+#endif
+#define BN_FP4_MFMA(ACC, VT, A, B)                                                                                                         \
+	ACC = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(VT{(int)(A).x, (int)(A).y, (int)(A).z, (int)(A).w, 0, 0, 0, 0},                  \
+	                                                      VT{(int)(B).x, (int)(B).y, (int)(B).z, (int)(B).w, 0, 0, 0, 0}, ACC, 4, 4, 0,    \
+	                                                      BN_FP4_MFMA_SCALES, 0, BN_FP4_MFMA_SCALES)
+#define BN_GRAM4_MFMA(t, A, B) BN_FP4_MFMA(acc[t], v8i, A, B)
 
 // One k-step (64 points): 6 ds_read_b128, 36 bitwise VALU, 6 MFMAs.  No second operand register set (three waves per SIMD
 // at <= 168 registers hide the LDS latency of a k-step better than a prefetch at two waves does).
@@ -211,9 +223,7 @@ __device__ __forceinline__ v4i x4and4(v4i a, v4i b, v4i c, v4i d, uint32_t m) //
 {
 	return xand4(xor3_4(a, b, c), d, m);
 }
-#define BN_GRAM4K_MFMA(t, A, B)                                                                                                            \
-	acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(v8i{(A).x, (A).y, (A).z, (A).w, 0, 0, 0, 0}, v8i{(B).x, (B).y, (B).z, (B).w, 0, 0, 0, 0}, \
-	                                                         acc[t], 4, 4, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F)
+#define BN_GRAM4K_MFMA(t, A, B) BN_FP4_MFMA(acc[t], v8i, A, B)
 // Q = 0: blocks 0 .. 4 (five accumulator tiles), Q = 1: blocks 5 .. 8 (four).
 // N k-steps in a row (step ks reads tile ks / 4 of a run of tiles kTile4kW words apart), software-pipelined for a Gram wave that has
 // the SIMD's matrix pipe to itself (kernels_roundeval_fp4.hip, wave-specialised form): two operand register sets of four limbs each,

@@ -7,7 +7,7 @@
 // parity of every entry is wanted -- the same observation that put the round evaluations on the matrix cores (gram.hpp), with
 // the roles changed: here the CONSTANT is one operand and the data the other, and the data needs no staging at all.
 //
-//  * v_mfma_scale_f32_32x32x64_f8f6f4, both operands FP4 (E2M1): K = 64 nibbles per instruction.  The B operand is the row
+//  * v_mfma_f32_32x32x64_f8f6f4, both operands FP4 (E2M1), no block scales (BN_FP4_MFMA, gram_fp4.hpp): K = 64 nibbles per instruction.  The B operand is the row
 //    itself: lane (n, kh) -- n = row of a 32-row block, kh = K half -- loads the 16 bytes at offset 32 t + 16 kh of ITS row (32
 //    nibbles, in place), and keeps one bit of every nibble with one AND: bit s = 0, 1, 2 decodes to 0.5, 1, 2; bit 3 is the sign
 //    bit of the format, so it is moved to bit 2 first ((x >> 1) & 0x44444444: two instructions).
@@ -30,6 +30,7 @@
 #include <cstdlib>
 
 #include "ctable.hpp"
+#include "gram_fp4.hpp"
 #include "internal.hpp"
 
 namespace bn {
@@ -70,11 +71,7 @@ __global__ __launch_bounds__(256) void k_linmap_prep(const uint4 *__restrict__ v
 	A[((size_t)w * steps + 4 * t + s) * 64 + lane] = uint4{regs[0], regs[1], regs[2], regs[3]};
 }
 
-#define BN_LM_MFMA(ACC, A, B) BN_LM_MFMA_(ACC, A, B)
-#define BN_LM_MFMA_(ACC, A, B)                                                                                                              \
-	ACC = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(lm_v8i{(int)(A).x, (int)(A).y, (int)(A).z, (int)(A).w, 0, 0, 0, 0},               \
-	                                                      lm_v8i{(int)(B).x, (int)(B).y, (int)(B).z, (int)(B).w, 0, 0, 0, 0}, ACC, 4, 4, 0, \
-	                                                      0x7F7F7F7F, 0, 0x7F7F7F7F)
+#define BN_LM_MFMA(ACC, A, B) BN_FP4_MFMA(ACC, lm_v8i, A, B) // gram_fp4.hpp: the scale-free form
 
 __device__ __forceinline__ uint4 lm_bit(uint4 x, int s)
 {

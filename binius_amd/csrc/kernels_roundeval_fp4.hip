@@ -1,6 +1,8 @@
 // binius_amd/csrc/kernels_roundeval_fp4.hip -- round evaluation of the bivariate product (round 0: no fold before it)
-// with the GF(2) Gram products of gram.hpp on the FP4 matrix path: v_mfma_scale_f32_32x32x64_f8f6f4 with both operands
-// E2M1 runs K = 64 in the time the int8 instruction takes for K = 32 (tools/fp4_probe.hip: 14.6 ns against 15.4 ns per
+// with the GF(2) Gram products of gram.hpp on the FP4 matrix path: v_mfma_f32_32x32x64_f8f6f4 cbsz:4 blgp:4 (both operands
+// E2M1, no block scales: BN_FP4_MFMA in gram_fp4.hpp; the scaled mnemonic v_mfma_scale_f32_32x32x64_f8f6f4 with scales of 2^0
+// gives the same accumulators and costs a second 8-byte word, -DBN_FP4_SCALED_MFMA) runs K = 64 in the time the int8
+// instruction takes for K = 32 (tools/fp4_probe.hip: 14.6 ns against 15.4 ns per
 // instruction and SIMD), and a register holds eight K-entries instead of four, so the operand masks per point halve
 // as well.  Same mathematics as kernels_roundeval_mfma.hip (one Karatsuba level, six accumulator tiles per wave, the
 // tail of gram.hpp); what changes is the operand encoding:
@@ -164,6 +166,11 @@ __global__ __launch_bounds__(256, 3) void k_roundeval_fp4(const uint4 *__restric
 // accumulator tiles, which leaves room for a second operand register set) with the k-steps software-pipelined, so that a Gram wave
 // keeps the matrix pipe of its SIMD busy by itself; one workgroup barrier per pair, no LDS round trip for the raw elements.  Whole
 // tiles only, at least two tiles per CU.
+// -DBN_FP4_WS_STAGER_PRIO=0 .. 3: the s_setprio level of the stager waves, for the sweep (profiles/r26: 3 stays, also with the
+// scale-free MFMA)
+#ifndef BN_FP4_WS_STAGER_PRIO
+#define BN_FP4_WS_STAGER_PRIO 3
+#endif
 namespace {
 constexpr unsigned kWsGramWaves = 4, kWsGroups = 2, kWsThreads = 64 * kWsGramWaves * (1 + kWsGroups);
 typedef unsigned int ws_v4u __attribute__((ext_vector_type(4)));
@@ -203,7 +210,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_roundeval_fp4_ws(const uint4 
 	const uint64_t n_seq = t0 < tlimit ? (tlimit - t0 + tstride - 1) / tstride : 0;
 	const uint64_t n_pairs = (n_seq + 1) >> 1;
 	if (stages) {
-		__builtin_amdgcn_s_setprio(3); // the stager waves issue ahead of their SIMD's Gram wave
+		__builtin_amdgcn_s_setprio(BN_FP4_WS_STAGER_PRIO); // the stager waves issue ahead of their SIMD's Gram wave
 		const stage4_role sr = make_stage4_role(stid);
 		uint4 xa[4], xb[4]; // the group's tile of pair p (even p: xa, odd p: xb), loaded two pairs ahead
 		auto load = [&](uint4 (&x)[4], uint64_t p) {

@@ -5,14 +5,17 @@
 # MI355X_MICROARCH.md section HBM) + WRITE_SIZE, both in KiB.
 # usage: tools/pmc_bench.sh <build-id> <n_vars> [<n_vars> ...]
 BUILD=$1; shift
+R=$(cd "$(dirname "$0")/.." && pwd) # the repository: this script's own tools/ directory sits in it
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/pmc_bench
 rm -rf $OUT; mkdir -p $OUT
 for NV in "$@"; do
   for C in FETCH_SIZE WRITE_SIZE; do
     # (BN_ARM=0: under counter collection every dispatch is serialised; no kernel should sit waiting for the host)
-    BN_ARM=0 rocprofv3 --pmc $C --output-format csv -d $OUT/n${NV}_$C -- python $R/bench.py --n-vars $NV --steps 1 --warmup 1 --no-cpu-baseline --no-claim-groups --no-prof > $OUT/n${NV}_$C.log 2>&1
+    # (every pass under its own time limit; a pass that fails ends the script: nothing more is started on the device)
+    BN_ARM=0 timeout -k 10 600 rocprofv3 --pmc $C --output-format csv -d $OUT/n${NV}_$C -- python $R/bench.py --n-vars $NV --steps 1 --warmup 1 --no-cpu-baseline --no-claim-groups --no-prof > $OUT/n${NV}_$C.log 2>&1
+    rc=$?
+    if [ $rc -ne 0 ]; then echo "pass $C at n_vars = $NV: exit $rc"; tail -20 $OUT/n${NV}_$C.log; exit $rc; fi
   done
 done
 python3 - "$OUT" "$BUILD" "$@" <<'PY'
