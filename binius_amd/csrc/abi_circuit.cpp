@@ -562,16 +562,11 @@ int circuit_ip_run(bn_ctx *ctx, const ip_collector &col, uint64_t n, f128 *value
 			ctx->s_clean = true;
 		}
 		ctx->mirror.valid = false;
-		const uint64_t seq = ++ctx->mail_seq;
-		{
-			prof_scope ps(ctx, BN_PROF_ROUND_EVAL_MFMA);
-			const int rc_a = group_res_alloc(ctx);
-			if (rc_a) return rc_a;
-			bn::group_tables *h_tb = (bn::group_tables *)ctx->grp.h_tables;
-			const bn::group_tables *d_tb = (const bn::group_tables *)ctx->grp.d_tables;
-			const hipError_t e = bn::launch_group(ctx->stream, ctx->n_cu, gj, nj, 2 * nj, ctx->d_result, ctx->d_mail, ctx->d_mail, ctx->d_ticket, seq, h_tb->jobs, d_tb->jobs);
-			if (e != hipSuccess) return bn::hip_fail(e, "launch_group (inner products of compiled circuits)");
-		}
+		const int rc_a = group_res_alloc(ctx);
+		if (rc_a) return rc_a;
+		uint64_t seq = 0;
+		const hipError_t e = group_launch(ctx, BN_PROF_ROUND_EVAL_MFMA, gj, nj, 2 * nj, ctx->d_result, ctx->d_mail, &seq);
+		if (e != hipSuccess) return bn::hip_fail(e, "launch_group (inner products of compiled circuits)"); // (the sequence number stays taken)
 		const int rc_w = mail_wait(ctx, seq);
 		if (rc_w) return rc_w;
 		for (uint32_t i = 0; i < n_ip; i++) {

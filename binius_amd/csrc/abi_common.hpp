@@ -48,6 +48,18 @@ struct prof_scope {
 	}
 };
 
+// ONE launch of the claim groups' kernel (kernels_group.hip) through the context's pinned job table (group_res_alloc has run): takes
+// the next mailbox sequence number into *seq -- what mail_wait waits for -- and brackets the launch for the profile.  What a
+// failure means is the caller's: the sequence number is NOT taken back here.
+inline hipError_t group_launch(bn_ctx *ctx, int prof_class, const bn::group_job *jobs, uint32_t n_jobs, uint32_t n_slots, f128 *d_S, f128 *d_vals, uint64_t *seq)
+{
+	bn::group_tables *h_tb = (bn::group_tables *)ctx->grp.h_tables;
+	const bn::group_tables *d_tb = (const bn::group_tables *)ctx->grp.d_tables;
+	*seq = ++ctx->mail_seq;
+	prof_scope ps(ctx, prof_class);
+	return bn::launch_group(ctx->stream, ctx->n_cu, jobs, n_jobs, n_slots, d_S, d_vals, ctx->d_mail, ctx->d_ticket, *seq, h_tb->jobs, d_tb->jobs);
+}
+
 #define BN_REQUIRE(cond, msg)                                                  \
 	do {                                                                       \
 		if (!(cond))                                                           \

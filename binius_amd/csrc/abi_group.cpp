@@ -1449,14 +1449,10 @@ static int launch_round(bn_ctx *ctx, const request &rq, const fold_ref *ref, fol
 	for (const auto &r : riders) g.spec_jobs += r.s->k;
 	pc.lap(bn_ctx::group_state::P_PLAN);
 	ctx->mirror.valid = false;
-	const uint64_t seq = ++ctx->mail_seq;
-	{
-		prof_scope ps(ctx, (cnt.fused || cnt.fold_only) ? BN_PROF_FOLD_EVAL_MFMA : BN_PROF_ROUND_EVAL_MFMA); // (a launch without a fold: round 0)
-		bn::group_tables *const h_tb = (bn::group_tables *)g.h_tables;
-		const hipError_t e = bn::launch_group(ctx->stream, ctx->n_cu, jobs.data(), (uint32_t)jobs.size(), n_slots, g.d_S, g.d_gmail, ctx->d_mail, ctx->d_ticket, seq,
-		                                      h_tb->jobs, ((const bn::group_tables *)g.d_tables)->jobs);
-		if (e != hipSuccess) return launch_refused(ctx, plain, e);
-	}
+	uint64_t seq = 0;
+	const hipError_t e = group_launch(ctx, (cnt.fused || cnt.fold_only) ? BN_PROF_FOLD_EVAL_MFMA : BN_PROF_ROUND_EVAL_MFMA, // (a launch without a fold: round 0)
+	                                  jobs.data(), (uint32_t)jobs.size(), n_slots, g.d_S, g.d_gmail, &seq);
+	if (e != hipSuccess) return launch_refused(ctx, plain, e);
 	g.launches++;
 	g.jobs_fused += cnt.fused;
 	g.jobs_fold += cnt.fold_only;

@@ -227,13 +227,8 @@ int ensure_mul_jobs(bn_ctx *ctx, int declined)
 // kernel does not take the jobs); *seq is what mail_wait waits for
 int launch_group_sums(bn_ctx *ctx, const std::vector<bn::group_job> &jobs, uint32_t n_slots, int declined, const char *what, uint64_t *seq)
 {
-	bn::group_tables *h_tb = (bn::group_tables *)ctx->grp.h_tables;
-	const bn::group_tables *d_tb = (const bn::group_tables *)ctx->grp.d_tables;
 	ctx->mirror.valid = false;
-	*seq = ++ctx->mail_seq;
-	prof_scope ps(ctx, BN_PROF_ROUND_EVAL_MFMA);
-	const hipError_t e = bn::launch_group(ctx->stream, ctx->n_cu, jobs.data(), (uint32_t)jobs.size(), n_slots, ctx->grp.d_S, ctx->grp.d_gmail, ctx->d_mail, ctx->d_ticket, *seq,
-	                                      h_tb->jobs, d_tb->jobs);
+	const hipError_t e = group_launch(ctx, BN_PROF_ROUND_EVAL_MFMA, jobs.data(), (uint32_t)jobs.size(), n_slots, ctx->grp.d_S, ctx->grp.d_gmail, seq);
 	if (e == hipSuccess) return BN_OK;
 	--ctx->mail_seq;
 	(void)hipGetLastError();

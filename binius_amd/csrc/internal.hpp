@@ -13,6 +13,7 @@
 
 #include "../../include/binius_amd.h"
 #include "gf128.hpp"
+#include "group_plan.hpp"
 
 struct bn_expr {
 	std::vector<bn_step> steps;
@@ -38,9 +39,7 @@ constexpr int kFoldBatchMax = 32;    // arrays of ONE plain fold launch (fold_ba
 constexpr int kFoldCallMax = 256;    // arrays of one bn_extrapolate_line_batch CALL (the shims' FOLD_BATCH_MAX): split into launches of kFoldBatchMax where it runs eagerly
 constexpr int kGroupMaxArrays = 256; // multilinears of one prover on the claim-group path (abi_group.cpp) = arrays of one deferred group fold
 constexpr int kGroupMaxClaims = 384; // product claims of one prover on that path (keccak: every committed column against up to three evaluation points)
-constexpr int kGroupMaxJobs = 1024;  // jobs of one launch of kernels_group.hip (the table lives in pinned memory, not in the kernel arguments)
-constexpr int kGroupMaxSlots = 1024; // accumulator slots of one launch: two per claim, the calling prover's and the riders'
-constexpr int kGroupMaxGrid = 512;   // workgroups of one launch (the head-of-workgroup table in the kernel arguments)
+// (kGroupMaxJobs, kGroupMaxSlots, kGroupMaxGrid -- the widths of one launch of kernels_group.hip: group_plan.hpp)
 static_assert(kFoldCallMax == kGroupMaxArrays, "a prover's fold arrives as ONE batch: hosted sessions fold whole batches");
 static_assert(kFoldCallMax == BN_FOLD_CALL_MAX, "include/binius_amd.h states the limit the shims split at");
 static_assert(kGroupMaxArrays <= kGroupMaxJobs && 2 * kGroupMaxClaims <= kGroupMaxSlots && kGroupMaxClaims <= kGroupMaxJobs, "group widths");
@@ -553,21 +552,7 @@ hipError_t launch_foldeval_mfma(hipStream_t s, int n_cu, const foldeval_args &fa
 hipError_t func_lds_limit(const void *fn, int bytes);
 
 // ---- kernels_group.hip: the product claims of a whole batch round of sumchecks as jobs of ONE launch; returns raw sums
-struct group_job {
-	const void *x0[2], *x1[2]; // kind 0: lower / upper half of the two arrays BEFORE the fold (2 n elements each); kind 1: lower half (evaluations
-	                           // at 0) / upper half (evaluations at 1) of the two arrays as they are (n elements each)
-	void *out[2];              // kind 0: where the folded arrays (2 n elements each) are written (may be x0)
-	f128 z;                    // kind 0: the fold's challenge
-	uint64_t n;                // evaluation points of the job
-	uint32_t kind;             // 0 = fold + evaluate, 1 = evaluate, 2 = two plain inner products: rows x0[0] . x0[1] -> S[slot], x1[0] . x1[1] -> S[slot + 1] (x1 null: one),
-	                           // 3 = fold only: arrays x0[sd] / x1[sd] -> out[sd] as kind 0, no sums (x0[1] null: one array)
-	uint32_t slot;             // the job's sums are XORed into S[slot] (at 1) and S[slot + 1] (at infinity)
-	uint32_t wg_begin, wg_count; // (filled in by the launcher; wg_count = 0: a follower of the chain in front of it)
-	uint32_t chain;            // the `chain` jobs that follow this one in the table are run by THIS job's workgroups, one after the other, each on
-	                           // the tiles the workgroup had in this job (all jobs of a chain: the same n)
-	uint32_t acquire;          // 1: the job reads what earlier jobs of its chain wrote (a workgroup reads back only its own tiles: its stores are
-	                           // awaited and its vector cache invalidated first)
-};
+// (group_job, the rows of the launch's table: group_plan.hpp)
 // hosted provers (abi_group.cpp): hand-over of a prover's arrays to the host (with its deferred fold performed on the way) and the
 // write-back of the host's folded copies
 constexpr uint64_t kGroupTailMaxElems = 32 * 4096; // elements of one hand-over / write-back: the pinned staging holds that many
@@ -605,7 +590,7 @@ struct group_writeback_args {
 	const uint4 *phi_inv; // nibble table of the inverse basis change
 };
 hipError_t launch_group_writeback(hipStream_t s, const group_writeback_args &a);
-// jobs_in[0 .. n_jobs) (n_jobs <= kGroupMaxJobs): dealt out to workgroups, sorted and written to h_table (pinned; d_table = its device view),
+// jobs_in[0 .. n_jobs) (n_jobs <= kGroupMaxJobs): dealt out to workgroups and sorted (group_plan.hpp), written to h_table (pinned; d_table = its device view),
 // which the launch reads.  The raw sums S[0 .. n_slots) (n_slots <= kGroupMaxSlots; zero before, zero after) go to d_vals[0 .. n_slots),
 // then the sequence number to d_mail[64].
 hipError_t launch_group(hipStream_t s, int n_cu, const group_job *jobs_in, uint32_t n_jobs, uint32_t n_slots, f128 *d_S, f128 *d_vals, f128 *d_mail,

@@ -451,318 +451,88 @@ __global__ __launch_bounds__(kThreads, 1) void k_group_fp4(group_kargs ga)
 	}
 }
 
-// Deals the workgroups of one launch out to the UNITS of the job list -- a job with its chain (jobs_in[i].chain followers directly
-// behind it), or a lone job -- in proportion to their traffic, eight at a time where a unit gets at least eight so that its tiles
-// keep the XCD-aware order; sorts the table by first workgroup and launches.  jobs[i].slot is the caller's; wg_begin / wg_count are
-// filled in here.  Every job: n >= 1; all jobs of a chain: the same n; kind 0 / 3 / 4 jobs write out[] (2 n elements each).
-//
-// PACKED launches.  With more units than a launch has workgroups to give each a sensible share (a prover of the keccak width: a
-// hundred claims and more, piop/prove.rs:262-287), the units are packed into U super-units of n_cu / U workgroups each, U a power
-// of two: every workgroup of a super-unit runs ALL its jobs one after the other, each job on the workgroup's share of that
-// job's tiles -- the chain mechanism of the kernel, used for jobs that do not depend on each other (chains that do stay whole
-// and in order inside one super-unit).  Against one unit per job this costs a parity reduction per job and workgroup (~2 us) and
-// buys (1) any number of jobs per launch, (2) balance -- 100 equal jobs on 256 workgroups are 2.56 workgroups each, i.e. 78 % of the
-// chip busy; as 4 super-units of 25 jobs on 64 workgroups they are 100 % --, (3) the XCD-aware tile order (ranges in multiples of
-// eight), and (4) every workgroup of the chip walks the jobs in the same order, so that an array shared by many claims (a
-// transparent against every committed column) is re-read while it is still in the Infinity Cache.  U is chosen by a cost
-// model (time per pair of tiles by job kind at the measured per-CU rate, fixed cost per job) over the longest super-unit.
+// The launch: the planner (group_plan.hpp) deals the workgroups out to the jobs and orders the table; the table goes to the pinned
+// block, the kernel arguments are filled and one of three instantiations is launched.
 namespace {
-struct pack_item {
-	uint32_t first, len;
-	double weight;
-};
-inline double pair_us(const group_job &j) // one pair of tiles (512 points) of this job on one workgroup at ~ 5 TB/s / 256 CUs: microseconds
-{
-	const bool one = j.kind == 3 && !j.x0[1];
-	switch (j.kind) {
-	case 0: return 5.0;              // 192 B per point
-	case 3: return one ? 2.5 : 5.0;
-	case 4: return 3.4;              // 128 B per point
-	default: return 1.7;             // 64 B per point
+// read once per process
+struct group_knobs {
+	uint32_t prio, adj_tiles;
+	int nt_log2;      // streaming accesses from 4 << nt_log2 elements touched
+	bool pack_forced; // BN_GROUP_PACK_U (measurement builds: that many super-units; -1: one unit per job -- tools/r06_pack_sweep.sh)
+	int pack_u;
+	bool prof;        // BN_GROUP_PROF (diagnostic: host time of launch_group by step, and of the runtime's launch call itself)
+	group_knobs()
+	{
+		auto knob = [](const char *name, int unset) {
+			const char *e = bn::settled_knob(name);
+			return e ? atoi(e) : unset;
+		};
+		prio = (uint32_t)knob("BN_FE_FP4_PRIO", 3) & 3u;
+		adj_tiles = (uint32_t)(knob("BN_GROUP_ADJ", 0) != 0); // (round-5 A/B, profiles/DEAD_ENDS.md: adjacent tiles per pair of fold groups -- no difference)
+		// (the single-claim kernels' threshold is 2^25 elements per array = 2^27 elements touched; BN_GROUP_NT_MIN_LOG2, measurement
+		// builds: the same threshold for launches of the group kernel only; A/B of round 6 within the noise in both directions,
+		// profiles/r06/README.md)
+		const int nt_group_log2 = knob("BN_GROUP_NT_MIN_LOG2", -1);
+		nt_log2 = nt_group_log2 >= 0 ? nt_group_log2 : knob("BN_FE_NT_MIN_LOG2", 25);
+		const char *pack = bn::settled_knob("BN_GROUP_PACK_U");
+		pack_forced = pack != nullptr;
+		pack_u = pack ? atoi(pack) : 0;
+		prof = getenv("BN_GROUP_PROF") != nullptr;
 	}
-}
-// what a further job costs a workgroup besides its tiles: the pipeline of loads, staging and Gram steps drains and refills, the
-// parity words are reduced (measured: 50 equal jobs as 2 x 25 at 0.45 of the HBM peak against 0.52 for 64 jobs of 4 workgroups each)
-inline double fixed_us(const group_job &j) { return j.kind == 3 ? 3.0 : 10.0; }
+};
+// BN_GROUP_PROF: laps 0 .. 2 in front of the launch call; lap 3 the call itself, from launch_begin() to the end of the scope, which
+// completes a counted call; one line on stderr every 64 of them
+struct group_prof {
+	typedef std::chrono::steady_clock clock;
+	const bool on;
+	bool launching = false;
+	clock::time_point t;
+	explicit group_prof(bool on_) : on(on_), t(on_ ? clock::now() : clock::time_point{}) {}
+	void lap(int i)
+	{
+		static double us[4] = {0, 0, 0, 0};
+		static uint64_t calls = 0;
+		if (!on) return;
+		const auto now = clock::now();
+		us[i] += std::chrono::duration<double, std::micro>(now - t).count();
+		t = now;
+		if (i == 3 && (++calls & 63) == 0)
+			fprintf(stderr, "[bn group prof] hipLaunchKernel of the group kernel: %.2f us per call over %llu calls; in front of it, us per call: weights + decision %.2f, dealing %.2f, table copy %.2f\n",
+			        us[3] / calls, (unsigned long long)calls, us[0] / calls, us[1] / calls, us[2] / calls);
+	}
+	void launch_begin()
+	{
+		launching = on;
+		if (on) t = clock::now();
+	}
+	~group_prof()
+	{
+		if (launching) lap(3);
+	}
+};
+hipError_t plan_error(group_plan::status_t st) { return st == group_plan::ok ? hipSuccess : st == group_plan::invalid ? hipErrorInvalidValue : hipErrorNotSupported; }
+static_assert(kGroupTilePoints == (uint32_t)kTP, "the planner counts the kernel's tiles");
 } // namespace
 
 hipError_t launch_group(hipStream_t s, int n_cu, const group_job *jobs_in, uint32_t n_jobs, uint32_t n_slots, f128 *d_S, f128 *d_vals, f128 *d_mail,
                         unsigned *d_counter, uint64_t seq, group_job *h_table, const group_job *d_table)
 {
-	if (n_jobs == 0 || n_jobs > (uint32_t)kGroupMaxJobs || n_slots > (uint32_t)kGroupMaxSlots || !h_table || !d_table) return hipErrorNotSupported;
-	if (n_cu > kGroupMaxGrid) n_cu = kGroupMaxGrid;
-	static const bool prof_launch = getenv("BN_GROUP_PROF") != nullptr; // (diagnostic: host time of this function by step, and of the runtime's launch call itself)
-	static double prof_step_us[3] = {0, 0, 0};
-	auto t_step = prof_launch ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point{};
-	auto step_lap = [&](int i) {
-		if (!prof_launch) return;
-		const auto now = std::chrono::steady_clock::now();
-		prof_step_us[i] += std::chrono::duration<double, std::micro>(now - t_step).count();
-		t_step = now;
-	};
-	static const uint32_t prio = [] {
-		const char *e = bn::settled_knob("BN_FE_FP4_PRIO");
-		return e ? (uint32_t)atoi(e) & 3u : 3u;
-	}();
-	static group_kargs ga_zero{};
-	group_kargs ga = ga_zero;
-	bool full = true;
-	uint64_t total_elems = 0;
-	std::vector<double> w;
-	std::vector<uint32_t> tiles, cap, cnt, first, len;
-	w.reserve(n_jobs);
-	tiles.reserve(n_jobs);
-	cap.reserve(n_jobs);
-	first.reserve(n_jobs);
-	len.reserve(n_jobs);
-	double W = 0;
-	uint32_t n_units = 0, max_tiles = 0;
-	for (uint32_t i = 0; i < n_jobs;) {
-		const uint32_t l = 1 + jobs_in[i].chain;
-		if (i + l > n_jobs) return hipErrorInvalidValue;
-		n_units++;
-		first.push_back(i);
-		len.push_back(l);
-		double wu = 0;
-		const uint64_t nt = (jobs_in[i].n + kTP - 1) / kTP;
-		for (uint32_t q = i; q < i + l; q++) {
-			const group_job &j = jobs_in[q];
-			if (j.n == 0 || j.kind > 4 || (j.kind != 3 && j.slot + 2 > n_slots) || j.n != jobs_in[i].n || (q > i && j.chain)) return hipErrorInvalidValue;
-			if (q == i && j.acquire) return hipErrorInvalidValue; // (nothing in front of it to read back)
-			if (j.n % kTP) full = false;
-			const bool one = j.kind == 3 && !j.x0[1];
-			wu += (double)nt * (j.kind == 0 ? 3.0 : j.kind == 3 ? (one ? 1.5 : 3.0) : j.kind == 4 ? 2.0 : 1.0);
-			total_elems += j.n * (j.kind == 0 ? 8 : j.kind == 3 ? (one ? 3 : 6) : j.kind == 4 ? 6 : 4);
-		}
-		if (nt > (1ull << 14) * (uint64_t)n_cu) return hipErrorNotSupported; // 2^22 points per workgroup and job: the f32 counts stay exact
-		w.push_back(wu);
-		tiles.push_back((uint32_t)nt);
-		cap.push_back((uint32_t)(nt >= 2 ? nt / 2 : 1)); // a workgroup wants a pair of tiles
-		if ((uint32_t)nt > max_tiles) max_tiles = (uint32_t)nt;
-		W += wu;
-		i += l;
-	}
-	uint32_t at = 0;
-	bool packed = n_units > 32 || (int)n_units > n_cu;
-	// (one unit per job where that is no worse by the same model: every unit its proportional share of the workgroups)
-	double unpacked_cost = -1;
-	if (packed && (int)n_units <= n_cu) { // (cheap: one pass over the jobs)
-		unpacked_cost = 0;
-		for (uint32_t i = 0; i < n_units; i++) {
-			uint32_t c = (uint32_t)((double)n_cu * w[i] / W);
-			if (c < 1) c = 1;
-			if (c > cap[i]) c = cap[i];
-			double cu = 0;
-			for (uint32_t q = first[i]; q < first[i] + len[i]; q++) cu += (double)(((uint64_t)tiles[i] + 2 * c - 1) / (2 * c)) * pair_us(jobs_in[q]) + fixed_us(jobs_in[q]);
-			if (cu > unpacked_cost) unpacked_cost = cu;
-		}
-	}
-	uint32_t best_U = 0;
-	double best_cost = 0;
-	std::vector<uint32_t> best_assign;
-	// (a prover's rounds repeat one shape with halving sizes: the decision for "these many units of this much weight on this many
-	// tiles" is remembered -- the model costs ~10 us of host time per launch at a hundred units)
-	struct decision {
-		uint32_t n_units = 0, max_tiles = 0, U = 0;
-		int n_cu = 0;
-		double W = 0;
-		bool packed = false;
-		std::vector<uint32_t> assign;
-	};
-	// (one entry per round size: a prove walks max_tiles down by halves, the next prove of the shape finds every one of them)
-	static thread_local std::vector<decision> remembered_decisions(64);
-	decision &last = remembered_decisions[(n_units * 31u + max_tiles * 7u + (uint32_t)n_cu) & 63u];
-	static const bool pack_forced = bn::settled_knob("BN_GROUP_PACK_U") != nullptr;
-	const bool remembered = packed && last.n_units == n_units && last.max_tiles == max_tiles && last.W == W && last.n_cu == n_cu && !pack_forced;
-	if (remembered) {
-		packed = last.packed;
-		best_U = last.U;
-		best_assign = last.assign;
-	}
-	if (packed && !remembered) {
-		// ---- U super-units of g = n_cu / U workgroups; items (units) dealt out heaviest first to the least loaded super-unit
-		std::vector<uint32_t> by_weight(n_units);
-		for (uint32_t i = 0; i < n_units; i++) by_weight[i] = i;
-		std::stable_sort(by_weight.begin(), by_weight.end(), [&](uint32_t a, uint32_t b) { return w[a] > w[b]; });
-		const uint32_t g_min = (max_tiles + (1u << 14) - 1) >> 14; // the exactness bound
-		std::vector<uint32_t> assign(n_units);
-		for (uint32_t U = 1; U <= (uint32_t)n_cu && U <= n_units; U <<= 1) {
-			const uint32_t g = (uint32_t)n_cu / U;
-			if (g < g_min || g == 0) break;
-			std::vector<double> cost(U, 0.0);
-			// (least loaded super-unit first: a heap -- a constraint set's request is hundreds of units)
-			typedef std::pair<double, uint32_t> lu;
-			std::priority_queue<lu, std::vector<lu>, std::greater<lu>> heap;
-			for (uint32_t q = 0; q < U; q++) heap.push(lu{0.0, q});
-			for (uint32_t o = 0; o < n_units; o++) {
-				const uint32_t it = by_weight[o];
-				const lu top = heap.top();
-				heap.pop();
-				const uint32_t u = top.second;
-				assign[it] = u;
-				heap.push(lu{top.first + w[it], u});
-				for (uint32_t q = first[it]; q < first[it] + len[it]; q++) {
-					const uint64_t steps = ((uint64_t)tiles[it] + 2 * g - 1) / (2 * g);
-					cost[u] += (double)steps * pair_us(jobs_in[q]) + fixed_us(jobs_in[q]);
-				}
-			}
-			double c = 0;
-			for (uint32_t u = 0; u < U; u++)
-				if (cost[u] > c) c = cost[u];
-			if (!best_U || c < best_cost) {
-				best_U = U;
-				best_cost = c;
-				best_assign = assign;
-			}
-		}
-		if (!best_U && unpacked_cost < 0) return hipErrorNotSupported;
-		if (unpacked_cost >= 0 && (!best_U || unpacked_cost <= best_cost)) packed = false;
-		static const int force_u = [] { // (BN_GROUP_PACK_U, measurement builds: that many super-units; -1: one unit per job -- tools/r06_pack_sweep.sh)
-			const char *e = bn::settled_knob("BN_GROUP_PACK_U");
-			return e ? atoi(e) : 0;
-		}();
-		if (force_u < 0 && unpacked_cost >= 0) packed = false;
-		if (force_u > 0 && (uint32_t)force_u <= n_units && (uint32_t)n_cu / (uint32_t)force_u >= (g_min ? g_min : 1)) {
-			packed = true;
-			best_U = (uint32_t)force_u;
-			std::vector<double> load(best_U, 0.0);
-			best_assign.assign(n_units, 0);
-			for (uint32_t o = 0; o < n_units; o++) {
-				const uint32_t it = by_weight[o];
-				uint32_t u = 0;
-				for (uint32_t q = 1; q < best_U; q++)
-					if (load[q] < load[u]) u = q;
-				best_assign[it] = u;
-				load[u] += w[it];
-			}
-		}
-	}
-	if (!remembered && (n_units > 32 || (int)n_units > n_cu)) {
-		last.n_units = n_units;
-		last.n_cu = n_cu;
-		last.max_tiles = max_tiles;
-		last.W = W;
-		last.packed = packed;
-		last.U = best_U;
-		last.assign = best_assign;
-	}
-	step_lap(0);
-	static thread_local std::vector<group_job> staged;
-	if (staged.size() < n_jobs) staged.resize(n_jobs);
-	if (packed) {
-		const uint32_t U = best_U, g = (uint32_t)n_cu / U;
-		// the items of every super-unit, in the caller's order (a chain's jobs stay in order): one counting pass -- a scan of all items
-		// per super-unit was 20 us of host time per launch at three hundred jobs on 128 super-units
-		std::vector<uint32_t> u_begin(U + 1, 0), by_unit(n_units);
-		for (uint32_t it = 0; it < n_units; it++) u_begin[best_assign[it] + 1]++;
-		for (uint32_t u = 0; u < U; u++) u_begin[u + 1] += u_begin[u];
-		{
-			std::vector<uint32_t> fill(u_begin.begin(), u_begin.end() - 1);
-			for (uint32_t it = 0; it < n_units; it++) by_unit[fill[best_assign[it]]++] = it;
-		}
-		uint32_t k = 0;
-		for (uint32_t u = 0; u < U; u++) {
-			const uint32_t head = k;
-			for (uint32_t o = u_begin[u]; o < u_begin[u + 1]; o++) {
-				const uint32_t it = by_unit[o];
-				for (uint32_t q = 0; q < len[it]; q++, k++) {
-					staged[k] = jobs_in[first[it] + q];
-					staged[k].wg_begin = u * g;
-					staged[k].wg_count = 0;
-					staged[k].chain = 0;
-				}
-			}
-			if (k == head) continue; // (more super-units than items cannot happen: U <= n_units and the heaviest-first deal fills every one)
-			staged[head].wg_count = g;
-			staged[head].chain = k - head - 1;
-			for (uint32_t x = u * g; x < (u + 1) * g; x++) ga.head_of_wg[x >> 1] |= head << (16 * (x & 1));
-		}
-		at = U * g;
-	} else {
-		if (n_cu < (int)n_units) return hipErrorNotSupported;
-		// the workgroups of every unit: its proportional share -- in multiples of eight where that costs nothing (the XCD-aware tile order
-		// wants ranges in multiples of eight), plainly where the rounding would leave the launch out of balance: twelve equal jobs on
-		// 256 workgroups are 21.3 each; as 8 x 24 + 4 x 16 the launch lasts as long as its 16-workgroup jobs (measured, k = 12 / n = 24:
-		// the fused launches at 0.47 - 0.50 of the HBM peak against 0.58 for k = 3 and 0.55 for k = 50), as 4 x 22 + 8 x 21 it is
-		// balanced to 1.6 % (0.56)
-		auto deal = [&](bool round8, std::vector<uint32_t> &c_out, double &max_load) -> bool {
-			c_out.assign(n_units, 0);
-			// first pass: the proportional share, rounded down (round8: to a multiple of eight from eight on), at least the workgroups
-			// the exactness bound asks for, at most one per pair of tiles
-			uint32_t used = 0;
-			for (uint32_t i = 0; i < n_units; i++) {
-				uint32_t c = (uint32_t)((double)n_cu * w[i] / W);
-				if (round8 && c >= 8) c &= ~7u;
-				const uint32_t need = (tiles[i] + (1u << 14) - 1) >> 14;
-				if (c < need) c = need;
-				if (c > cap[i]) c = cap[i];
-				if (c < 1) c = 1;
-				c_out[i] = c;
-				used += c;
-			}
-			// (minimums can overshoot only with very many very uneven units: take from the largest)
-			while (used > (uint32_t)n_cu) {
-				uint32_t big = 0;
-				for (uint32_t i = 1; i < n_units; i++)
-					if (c_out[i] > c_out[big]) big = i;
-				if (c_out[big] <= 1) return false;
-				const uint32_t need = (tiles[big] + (1u << 14) - 1) >> 14;
-				if (c_out[big] - 1 < need) return false;
-				c_out[big]--;
-				used--;
-			}
-			// the rest goes to whoever has the most work per workgroup (round8: eight at a time for units in multiples of eight)
-			// (a heap: the heaviest load first, the lower index among equals -- a unit that cannot grow any more never can again, counts
-			// and `used` only rise; the scan of all units per workgroup handed out was 25 us of host time per launch at 175 units)
-			{
-				typedef std::pair<double, uint32_t> lu; // (load, n_units - 1 - index)
-				std::priority_queue<lu> heap;
-				for (uint32_t i = 0; i < n_units; i++)
-					if (w[i] > 0) heap.push(lu{w[i] / c_out[i], n_units - 1 - i});
-				while (!heap.empty() && used < (uint32_t)n_cu) {
-					const uint32_t i = n_units - 1 - heap.top().second;
-					heap.pop();
-					const uint32_t step = (round8 && c_out[i] >= 8 && (c_out[i] & 7) == 0) ? 8 : 1;
-					if (c_out[i] + step > cap[i] || used + step > (uint32_t)n_cu) continue;
-					c_out[i] += step;
-					used += step;
-					heap.push(lu{w[i] / c_out[i], n_units - 1 - i});
-				}
-			}
-			max_load = 0;
-			for (uint32_t i = 0; i < n_units; i++)
-				if (w[i] / c_out[i] > max_load) max_load = w[i] / c_out[i];
-			return true;
-		};
-		double load8 = 0, load1 = 0;
-		std::vector<uint32_t> cnt1;
-		const bool ok8 = deal(true, cnt, load8), ok1 = n_units > 1 && deal(false, cnt1, load1);
-		if (!ok8 && !ok1) return hipErrorNotSupported;
-		if (ok1 && (!ok8 || load1 < 0.97 * load8)) cnt.swap(cnt1); // (the XCD-aware order is worth a few per cent, measured on the single-claim kernels)
-		// table order: the units whose count is a multiple of eight first (their ranges then start on multiples of eight)
-		std::vector<uint32_t> order;
-		for (uint32_t i = 0; i < n_units; i++)
-			if ((cnt[i] & 7) == 0) order.push_back(i);
-		for (uint32_t i = 0; i < n_units; i++)
-			if ((cnt[i] & 7) != 0) order.push_back(i);
-		uint32_t k = 0;
-		for (uint32_t o = 0; o < n_units; o++) {
-			const uint32_t u = order[o];
-			for (uint32_t g = at; g < at + cnt[u]; g++) ga.head_of_wg[g >> 1] |= k << (16 * (g & 1));
-			for (uint32_t q = 0; q < len[u]; q++, k++) {
-				staged[k] = jobs_in[first[u] + q];
-				staged[k].wg_begin = at;
-				staged[k].wg_count = q == 0 ? cnt[u] : 0;
-			}
-			at += cnt[u];
-		}
-	}
+	if (!h_table || !d_table) return hipErrorNotSupported;
+	static const group_knobs knobs;
+	static thread_local group_planner planner;
+	group_prof prof(knobs.prof);
+	const group_plan &plan = planner.decide(jobs_in, n_jobs, n_slots, n_cu, knobs.pack_forced, knobs.pack_u); // (the planner's: deal() completes it)
+	if (plan.status != group_plan::ok) return plan_error(plan.status);
+	prof.lap(0);
+	if (planner.deal().status != group_plan::ok) return plan_error(plan.status);
 	// (the table is put together in ordinary memory and goes to the pinned block in one sequential copy: the block is written once,
 	// front to back, never read or patched by the host)
-	step_lap(1);
-	std::memcpy(h_table, staged.data(), (size_t)n_jobs * sizeof(group_job));
+	prof.lap(1);
+	std::memcpy(h_table, plan.table, (size_t)n_jobs * sizeof(group_job));
 	__atomic_thread_fence(__ATOMIC_SEQ_CST); // (the table is in memory before the doorbell rings)
-	step_lap(2);
+	prof.lap(2);
+	group_kargs ga;
+	std::memcpy(ga.head_of_wg, plan.head_of_wg, sizeof(ga.head_of_wg));
 	ga.table = d_table;
 	ga.S = d_S;
 	ga.vals = d_vals;
@@ -771,54 +541,21 @@ hipError_t launch_group(hipStream_t s, int n_cu, const group_job *jobs_in, uint3
 	ga.seq = seq;
 	ga.n_jobs = n_jobs;
 	ga.n_slots = n_slots;
-	static const uint32_t adj_tiles = [] {
-		const char *e = settled_knob("BN_GROUP_ADJ"); // (round-5 A/B, profiles/DEAD_ENDS.md: adjacent tiles per pair of fold groups -- no difference)
-		return e ? (uint32_t)(atoi(e) != 0) : 0u;
-	}();
-	ga.prio = prio | (adj_tiles << 2);
-	static const int nt_min_log2 = [] {
-		const char *e = bn::settled_knob("BN_FE_NT_MIN_LOG2");
-		return e ? atoi(e) : 25;
-	}();
-	// streaming accesses once the launch's arrays cannot stay in the caches anyway (the single-claim kernels' threshold is 2^25
-	// elements per array = 2^27 elements touched)
-	// (BN_GROUP_NT_MIN_LOG2, measurement builds: the same threshold for launches of the group kernel only; A/B of round 6 within the
-	// noise in both directions, profiles/r06/README.md)
-	static const int nt_group_log2 = [] {
-		const char *e = bn::settled_knob("BN_GROUP_NT_MIN_LOG2");
-		return e ? atoi(e) : -1;
-	}();
-	const int nt_log2 = nt_group_log2 >= 0 ? nt_group_log2 : nt_min_log2;
-	const bool nt = full && nt_log2 < 62 && total_elems >= (4ull << nt_log2);
+	ga.prio = knobs.prio | (knobs.adj_tiles << 2);
+	ga.pad = 0;
 	constexpr unsigned lds = 2 * kFoldGroups * kTile4W * 4;
-	{
-		const void *fn[4] = {reinterpret_cast<const void *>(&k_group_fp4<false, false>), reinterpret_cast<const void *>(&k_group_fp4<true, false>),
-		                     reinterpret_cast<const void *>(&k_group_fp4<true, true>), nullptr};
-		for (int i = 0; fn[i]; i++) {
-			const hipError_t e = func_lds_limit(fn[i], lds);
-			if (e != hipSuccess) return e;
-		}
+	for (const void *fn : {reinterpret_cast<const void *>(&k_group_fp4<false, false>), reinterpret_cast<const void *>(&k_group_fp4<true, false>),
+	                       reinterpret_cast<const void *>(&k_group_fp4<true, true>)}) {
+		const hipError_t e = func_lds_limit(fn, lds);
+		if (e != hipSuccess) return e;
 	}
-	const auto t_l0 = prof_launch ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point{};
-	struct launch_timer {
-		bool on;
-		std::chrono::steady_clock::time_point t0;
-		~launch_timer()
-		{
-			if (!on) return;
-			static uint64_t ns = 0, calls = 0;
-			ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-			if ((++calls & 63) == 0)
-				fprintf(stderr, "[bn group prof] hipLaunchKernel of the group kernel: %.2f us per call over %llu calls; in front of it, us per call: weights + decision %.2f, dealing %.2f, table copy %.2f\n",
-				        ns / 1e3 / calls, (unsigned long long)calls, prof_step_us[0] / calls, prof_step_us[1] / calls, prof_step_us[2] / calls);
-		}
-	} lt{prof_launch, t_l0};
-	if (nt)
-		hipLaunchKernelGGL((k_group_fp4<true, true>), dim3(at), dim3(kThreads), lds, s, ga);
-	else if (full)
-		hipLaunchKernelGGL((k_group_fp4<true, false>), dim3(at), dim3(kThreads), lds, s, ga);
+	prof.launch_begin();
+	if (group_plan_streams(plan, knobs.nt_log2))
+		hipLaunchKernelGGL((k_group_fp4<true, true>), dim3(plan.grid), dim3(kThreads), lds, s, ga);
+	else if (plan.full)
+		hipLaunchKernelGGL((k_group_fp4<true, false>), dim3(plan.grid), dim3(kThreads), lds, s, ga);
 	else
-		hipLaunchKernelGGL((k_group_fp4<false, false>), dim3(at), dim3(kThreads), lds, s, ga);
+		hipLaunchKernelGGL((k_group_fp4<false, false>), dim3(plan.grid), dim3(kThreads), lds, s, ga);
 	return hipGetLastError();
 }
 
