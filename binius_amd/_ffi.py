@@ -27,6 +27,8 @@ HAL_ML_FOLDED, HAL_ML_TRANSPARENT = 0, 1
 NTT_MAX_DIM = 64
 BN_ME_MAX_LO_VARS, BN_ME_MAX_JOBS = 10, 4096  # bn_mle_evaluate_batch
 BN_MERGE_TILE_LOG2 = 6  # bn_merge_multilins: multilinears of at least twice as many variables are tiled jobs
+BN_TOWER_EXPR_MAX_STEPS, BN_TOWER_EXPR_MAX_INPUTS, BN_TOWER_EXPR_MAX_LIVE = 1024, 256, 16  # bn_expr_compile_tower
+BN_CC_TOWER_CALLS, BN_CC_TOWER_LAUNCHES, BN_CC_TOWER_BITWISE, BN_CC_TOWER_VALUES, BN_CC_N = 0, 1, 2, 3, 4  # bn_compute_composite_counters
 
 
 def lib_path():
@@ -210,6 +212,8 @@ def lib():
         "bn_expr_compile": [vp, C.POINTER(Step), u64, C.POINTER(vp)],
         "bn_expr_free": [vp],
         "bn_expr_n_vars": [vp, C.POINTER(u32)],
+        "bn_expr_compile_tower": [vp, C.POINTER(Step), u64, C.POINTER(u32), u32, u32, C.POINTER(vp)],
+        "bn_compute_composite_counters": [vp, C.POINTER(u64)],
         "bn_extrapolate_line": [vp, vp, u64, vp, u64, PF],
         "bn_extrapolate_line_batch": [vp, C.POINTER(vp), C.POINTER(vp), u32, u64, PF],
         "bn_extrapolate_line_batch_scaled": [vp, C.POINTER(vp), C.POINTER(vp), u32, u64, PF, u32, PF],
@@ -309,7 +313,7 @@ ABI_SYMBOLS = [
     "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
     "bn_univariate_fold_batch", "bn_univariate_fold_counters", "bn_ring_switch_eq_ind_batch", "bn_ring_switch_counters",
     "bn_mle_evaluate_batch", "bn_mle_evaluate_counters", "bn_partial_eval_high_lincomb_batch", "bn_partial_eval_lincomb_counters",
-    "bn_merge_multilins", "bn_merge_counters", "bn_derive_columns_batch", "bn_derive_counters", "bn_generate_columns_batch", "bn_generate_counters", "bn_fri_query_proof_elems", "bn_fri_query_openings", "bn_fri_query_counters",
+    "bn_merge_multilins", "bn_merge_counters", "bn_derive_columns_batch", "bn_derive_counters", "bn_generate_columns_batch", "bn_generate_counters", "bn_expr_compile_tower", "bn_compute_composite_counters", "bn_fri_query_proof_elems", "bn_fri_query_openings", "bn_fri_query_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -759,6 +763,25 @@ class Context:
         self._exprs.append(e)
         return e
 
+    def expr_compile_tower(self, steps, input_levels, out_level):
+        """bn_expr_compile_tower: a tower-typed expression for compute_composite_tower.  steps as for compile_expr; input_levels[v] is
+        the tower level (0 or 3 .. 7) at which input v is packed, out_level the output's.  Every other consumer of an Expr rejects it."""
+        st = make_steps(steps)
+        lv = (C.c_uint32 * max(1, len(input_levels)))(*input_levels)
+        h = C.c_void_p()
+        _check(lib().bn_expr_compile_tower(self._h, st, len(steps), lv, len(input_levels), out_level, C.byref(h)))
+        e = Expr(h, steps)
+        e.input_levels, e.out_level = list(input_levels), out_level
+        self._exprs.append(e)
+        return e
+
+    def compute_composite_counters(self):
+        """bn_compute_composite_counters: accepted compute_composite calls with a tower-typed expression, their launches, how many ran
+        at level 0 (bitwise) and at levels 3 .. 7 (per value).  Rejected calls count nowhere."""
+        c = (C.c_uint64 * 4)()
+        _check(lib().bn_compute_composite_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "bitwise": int(c[2]), "values": int(c[3])}
+
     # ---- ComputeLayerExecutor
     def extrapolate_line(self, evals_0, evals_1, z):
         zz = to_f128(z)
@@ -922,6 +945,12 @@ class Context:
         for r in inputs:
             assert r.len == row_len  # SlicesBatch::new
         _check(lib().bn_compute_composite(self._h, rows, len(inputs), row_len, output.ptr, output.len, composition.handle))
+
+    def compute_composite_tower(self, inputs, output, expr, n_values):
+        """bn_compute_composite with an expression of expr_compile_tower: inputs[v] holds n_values values packed at the expression's
+        input level v (at least one element), output n_values values at its output level."""
+        rows = (C.c_void_p * max(1, len(inputs)))(*[r.ptr for r in inputs])
+        _check(lib().bn_compute_composite(self._h, rows, len(inputs), n_values, output.ptr, n_values, expr.handle))
 
     def pairwise_product_reduce(self, inp, round_outputs):
         outs = (C.c_void_p * max(1, len(round_outputs)))(*[r.ptr for r in round_outputs])

@@ -368,6 +368,13 @@ def _plain_host_lib():
         L.bnh_witness_build_scratch_elems.argtypes = L.bnh_witness_derive_scratch_elems.argtypes
         L.bnh_witness_build.restype = C.c_int
         L.bnh_witness_build.argtypes = L.bnh_witness_derive.argtypes
+        from ._ffi import Step
+
+        expr_args = [C.POINTER(Step), U32P, U32P, U32P, C.c_uint32]
+        L.bnh_witness_compute_scratch_elems.restype = C.c_uint64
+        L.bnh_witness_compute_scratch_elems.argtypes = L.bnh_witness_derive_scratch_elems.argtypes + expr_args
+        L.bnh_witness_compute.restype = C.c_int
+        L.bnh_witness_compute.argtypes = L.bnh_witness_derive.argtypes + expr_args
         # the _live forms: the array form's arguments without the samples, the transcript's table where LIVE_FORMS says
         for name, (live, drop, at, _splice) in LIVE_FORMS.items():
             if name == "bnh_evalcheck_bivariate_prove":
@@ -1749,3 +1756,59 @@ class WitnessBuild:
     @property
     def n_launches(self):
         return int(self._launches.value)
+
+
+class WitnessCompute(WitnessBuild):
+    """WitnessBuild with the columns of m3's add_computed computed on the device as well (bnh_witness_compute = witness_compute of
+    binius_amd/host/witness.hpp): each is one bn_compute_composite with a tower-typed expression.  columns: WitnessBuild's, and
+      ("computed", steps, [inputs], n_vars, tower_level)   steps as Context.compile_expr takes them; variable v is column inputs[v]
+    ("lincomb", ...) is unchanged, but a combination that is neither in XOR form nor a B128 one now runs as the expression sum of
+    coeff * term + offset at its own level instead of being rejected.  run(), n_waves and n_launches as WitnessPlan's."""
+
+    KINDS = dict(WitnessBuild.KINDS, computed=13)
+    _SCRATCH, _RUN = "bnh_witness_compute_scratch_elems", "bnh_witness_compute"
+
+    @classmethod
+    def _marshal_exprs(cls, columns):
+        """(columns with every computed column replaced by a placeholder, its rows, the expression tables)"""
+        from ._ffi import make_steps
+
+        flat, step_off, inputs, input_off, rows = [], [0], [], [0], {}
+        for i, c in enumerate(columns):
+            if cls.KINDS.get(c[0], c[0]) != 13:
+                continue
+            rows[i] = [13, len(step_off) - 1, int(c[3]), int(c[4])]
+            flat += list(c[1])
+            inputs += [int(v) for v in c[2]]
+            step_off.append(len(flat))
+            input_off.append(len(inputs))
+        U32 = C.c_uint32
+        tables = (make_steps(flat), (U32 * len(step_off))(*step_off), (U32 * max(1, len(inputs)))(*inputs), (U32 * len(input_off))(*input_off), len(step_off) - 1)
+        return [("packed", 0, 0) if i in rows else c for i, c in enumerate(columns)], rows, tables
+
+    @classmethod
+    def _marshal(cls, columns):
+        plain, rows, _tables = cls._marshal_exprs(columns)
+        out = WitnessBuild._marshal.__func__(cls, plain)
+        for i, row in rows.items():
+            out[1][4 * i : 4 * i + 4] = row
+        return out
+
+    @classmethod
+    def scratch_elems(cls, columns):
+        n, desc, args, _given, terms, coeffs, n_terms, offsets = cls._marshal(columns)
+        return int(host_lib().bnh_witness_compute_scratch_elems(n, desc, args, terms, coeffs, n_terms, offsets, *cls._marshal_exprs(columns)[2]))
+
+    def __init__(self, hal, columns, scratch):
+        super().__init__(hal, columns, scratch)
+        self.exprs = self._marshal_exprs(columns)[2]
+
+    def run(self):
+        from ._ffi import DevSlice
+
+        rc = host_lib().bnh_witness_compute(self.hal._h, self.n, self.desc, self.args, self.given, self.terms, self.coeffs, self.n_terms, self.offsets,
+                                            self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0,
+                                            self.ptrs, self.levels, self.n_vars, C.byref(self._waves), C.byref(self._launches), *self.exprs)
+        if rc != 0:
+            raise BnError(rc, host_lib().bnh_last_error().decode())
+        return [(DevSlice(self.ptrs[i], max(1, (1 << (self.n_vars[i] + self.levels[i])) >> 7)), int(self.levels[i]), int(self.n_vars[i])) for i in range(self.n)]

@@ -897,6 +897,24 @@ int bn_expr_compile(bn_ctx *ctx, const bn_step *steps, uint64_t n_steps, bn_expr
 	return BN_OK;
 }
 
+// (the compiler itself -- level inference, dead-step removal, slot assignment -- is compose_tower.hpp; the program goes to the
+// device at the first bn_compute_composite, as d_steps does)
+int bn_expr_compile_tower(bn_ctx *ctx, const bn_step *steps, uint64_t n_steps, const uint32_t *input_levels, uint32_t n_inputs, uint32_t out_level,
+                          bn_expr **out)
+{
+	BN_REQUIRE(ctx && out && steps && input_levels, "null argument");
+	BN_ENTER(ctx);
+	std::unique_ptr<bn::ct_program> prog(new bn::ct_program());
+	const char *why = bn::ct_compile(steps, n_steps, input_levels, n_inputs, out_level, *prog);
+	if (why) return bn::fail(BN_ERR_INPUT_VALIDATION, std::string("input validation: tower expression: ") + why);
+	bn_expr *e = new bn_expr();
+	e->device = ctx->device;
+	e->steps.assign(steps, steps + n_steps);
+	e->n_vars = n_inputs;
+	e->tower = std::move(prog);
+	*out = e;
+	return BN_OK;
+}
 
 } // extern "C"
 namespace bn {
@@ -911,6 +929,7 @@ int bn_expr_free(bn_expr *expr)
 	if (!expr) return BN_OK;
 	bn::expr_epoch_bump();
 	if (expr->d_steps) hipFree(expr->d_steps);
+	if (expr->d_tower) hipFree(expr->d_tower);
 	delete expr;
 	return BN_OK;
 }

@@ -1456,6 +1456,9 @@ int bn_hal_round_evals(bn_ctx *ctx, uint32_t order, uint32_t n_vars, const void 
 	BN_FLUSH(ctx);
 	BN_REQUIRE(order == BN_ORDER_LOW_TO_HIGH || order == BN_ORDER_HIGH_TO_LOW, "unknown evaluation order");
 	BN_REQUIRE(n_vars > 0 && n_vars < 40, "computing round evaluations requires at least a single variable");
+	for (uint32_t e = 0; e < n_evs; e++) // (before any route looks at a composition)
+		BN_REQUIRE(!(evs[e].composition && evs[e].composition->is_tower()) && !(evs[e].composition_at_infinity && evs[e].composition_at_infinity->is_tower()),
+		           "a tower-typed expression is taken by bn_compute_composite alone");
 	hal_request r{ctx, order, n_vars, d_tensor_query, query_vars, mls, n_mls, evs, n_evs, h_points, n_points, h_out, (uint64_t)1 << n_vars, (uint64_t)1 << (n_vars - 1)};
 	r.acc = acc_scope{ctx};
 	r.d_acc = ctx->d_result;

@@ -1673,6 +1673,8 @@ int bn_kernel_launch(bn_ctx *ctx, const bn_memmap *maps, uint32_t n_maps, const 
 	if (rc) return rc;
 	BN_REQUIRE(log_chunks == 0, "this backend records kernels with log_chunks = bn_pick_log_chunks() = 0");
 	BN_REQUIRE(n_ret <= 64, "too many returned values");
+	for (uint32_t o = 0; ops && o < n_ops; o++) // (before anything is settled or launched)
+		BN_REQUIRE(!(ops[o].kind == BN_KOP_SUM_COMPOSITION && ops[o].expr && ops[o].expr->is_tower()), "a tower-typed expression is taken by bn_compute_composite alone");
 
 	// ---- claim groups (abi_group.cpp): k product claims over m arrays, several provers' folds waiting -- the shape piop::prove
 	// issues.  Declines (handled = false) everything else, and a lone single-claim prover, which the machinery below keeps.

@@ -221,6 +221,83 @@ int bn_fri_counters(bn_ctx *ctx, uint64_t *counters)
 	return BN_OK;
 }
 
+} // extern "C"
+
+namespace bnabi {
+// the device copy of a tower expression's program: ops, constants, input levels, each section 16-byte aligned (made once)
+static size_t tower_consts_off(const bn::ct_program &p) { return p.ops.size() * sizeof(bn::ct_op); }
+static size_t tower_levels_off(const bn::ct_program &p) { return tower_consts_off(p) + p.consts.size() * sizeof(f128); }
+static int ensure_d_tower(bn_ctx *ctx, const bn_expr *e)
+{
+	if (e->d_tower) return BN_OK;
+	const bn::ct_program &p = *e->tower;
+	std::vector<char> img(tower_levels_off(p) + (p.input_levels.size() + 4) * sizeof(uint32_t), 0);
+	if (!p.ops.empty()) std::memcpy(img.data(), p.ops.data(), p.ops.size() * sizeof(bn::ct_op));
+	if (!p.consts.empty()) std::memcpy(img.data() + tower_consts_off(p), p.consts.data(), p.consts.size() * sizeof(f128));
+	if (!p.input_levels.empty()) std::memcpy(img.data() + tower_levels_off(p), p.input_levels.data(), p.input_levels.size() * sizeof(uint32_t));
+	void *d = nullptr;
+	hipError_t err = hipMalloc(&d, img.size());
+	if (err != hipSuccess) return bn::fail(BN_ERR_ALLOC, "allocation error: allocator is out of memory (tower expression)");
+	err = hipMemcpyAsync(d, img.data(), img.size(), hipMemcpyHostToDevice, ctx->stream);
+	if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream); // (the source is pageable and goes away)
+	if (err != hipSuccess) {
+		hipFree(d);
+		return bn::hip_fail(err, "bn_expr upload");
+	}
+	e->d_tower = d;
+	return BN_OK;
+}
+
+// bn_compute_composite with an expression of bn_expr_compile_tower: packed subfield rows, ONE launch of kernels_compose_tower.hip
+static int compute_composite_tower(bn_ctx *ctx, const void *const *d_rows, uint32_t n_rows, uint64_t row_len, void *d_out, uint64_t out_len, const bn_expr *expr)
+{
+	const bn::ct_program &p = *expr->tower;
+	const uint32_t L = p.out_level, n_inputs = (uint32_t)p.input_levels.size();
+	BN_REQUIRE(d_rows && d_out, "null argument");
+	BN_REQUIRE(row_len == out_len, "inputs and output must be the same length");
+	BN_REQUIRE(n_inputs <= n_rows, "composition not match with input");
+	BN_REQUIRE(is_pow2(row_len) && ilog2(row_len) <= BN_PE_MAX_VARS && ilog2(row_len) + L >= 7, "the number of values is no power of two, or the output is below one element");
+	const uint32_t n_vars = ilog2(row_len);
+	const uint64_t out_elems = column_elems(n_vars, L);
+	BN_REQUIRE(aligned16(d_out), "misaligned pointer");
+	for (uint32_t v = 0; v < n_inputs; v++) {
+		BN_REQUIRE(d_rows[v] && aligned16(d_rows[v]), "null or misaligned row");
+		BN_REQUIRE(!ranges_overlap(d_out, out_elems, d_rows[v], column_elems(n_vars, p.input_levels[v])), "the output overlaps a row");
+	}
+	BN_REQUIRE(ctx->device == expr->device, "the expression was compiled for another device");
+	const void **d_ptrs = nullptr;
+	int rc = ensure_d_tower(ctx, expr);
+	if (rc) return rc;
+	rc = upload_ptrs(ctx, d_rows, n_inputs, &d_ptrs);
+	if (rc) return rc;
+	bn::compose_tower_args a{};
+	a.rows = d_ptrs;
+	a.ops = expr->d_tower;
+	a.consts = (const char *)expr->d_tower + tower_consts_off(p);
+	a.in_levels = (const uint32_t *)((const char *)expr->d_tower + tower_levels_off(p));
+	a.n_ops = (uint32_t)p.ops.size();
+	a.result = p.result;
+	a.out_level = L;
+	a.out_elems = out_elems;
+	a.out = d_out;
+	BN_HIP(bn::launch_compose_tower(ctx->stream, a, p.n_slots));
+	ctx->cc_tower[BN_CC_TOWER_CALLS] += 1;
+	ctx->cc_tower[BN_CC_TOWER_LAUNCHES] += 1;
+	ctx->cc_tower[L == 0 ? BN_CC_TOWER_BITWISE : BN_CC_TOWER_VALUES] += 1;
+	return BN_OK;
+}
+} // namespace bnabi
+
+extern "C" {
+
+int bn_compute_composite_counters(bn_ctx *ctx, uint64_t *counters)
+{
+	BN_REQUIRE(ctx && counters, "null argument");
+	BN_ENTER(ctx);
+	for (int i = 0; i < BN_CC_N; i++) counters[i] = ctx->cc_tower[i];
+	return BN_OK;
+}
+
 // rows -> device array of row pointers, staged in the tail of the result mailbox area
 int bn_compute_composite(bn_ctx *ctx, const void *const *d_rows, uint32_t n_rows, uint64_t row_len, void *d_out,
                          uint64_t out_len, const bn_expr *expr)
@@ -228,6 +305,7 @@ int bn_compute_composite(bn_ctx *ctx, const void *const *d_rows, uint32_t n_rows
 	BN_REQUIRE(ctx && expr, "null argument");
 	BN_ENTER(ctx);
 	BN_FLUSH(ctx);
+	if (expr->is_tower()) return compute_composite_tower(ctx, d_rows, n_rows, row_len, d_out, out_len, expr);
 	BN_REQUIRE(row_len == out_len, "inputs and output must be the same length");
 	BN_REQUIRE(expr->n_vars == n_rows || (expr->n_vars <= n_rows), "composition not match with input");
 	BN_REQUIRE(expr->steps.size() <= 64, "circuit too large for this backend (max 64 steps)");

@@ -13,6 +13,7 @@
 
 #include "../../include/binius_amd.h"
 #include "gf128.hpp"
+#include "compose_tower.hpp"
 #include "group_plan.hpp"
 
 struct bn_expr {
@@ -31,6 +32,11 @@ struct bn_expr {
 	};
 	mutable int poly_state = 0;
 	mutable std::vector<monomial> poly;
+	// bn_expr_compile_tower: the program of kernels_compose_tower.hip.  Such an expression is taken by bn_compute_composite alone
+	// (is_tower: every other consumer rejects it); d_tower is its device copy -- ops, constants, input levels -- made on first use
+	std::unique_ptr<bn::ct_program> tower;
+	mutable void *d_tower = nullptr;
+	bool is_tower() const { return tower != nullptr; }
 };
 
 namespace bn {
@@ -91,6 +97,7 @@ struct bn_ctx {
 	uint64_t fq_calls = 0, fq_launches = 0, fq_openings = 0; // bn_fri_query_openings (bn_fri_query_counters)
 	uint64_t dv_calls = 0, dv_launches = 0, dv_jobs = 0; // bn_derive_columns_batch (bn_derive_counters)
 	uint64_t gn_calls = 0, gn_launches = 0, gn_jobs = 0; // bn_generate_columns_batch (bn_generate_counters)
+	uint64_t cc_tower[BN_CC_N] = {}; // bn_compute_composite calls with a tower-typed expression (bn_compute_composite_counters)
 	bn::f128 *h_me_rets = nullptr, *d_me_rets = nullptr; // pinned: the results of a bn_mle_evaluate_batch call, BN_ME_MAX_JOBS values (the sequence word stays in h_mail[64])
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1012,6 +1019,24 @@ struct derive_job {
 constexpr uint32_t kDeriveUnitElems = BN_DERIVE_UNIT_ELEMS;
 static_assert(kDeriveUnitElems % 1024 == 0 && kDeriveUnitElems > 0, "a unit is whole chunks of 1024 elements");
 hipError_t launch_derive_columns(hipStream_t s, const derive_job *d_jobs, uint32_t n_jobs, const void *const *d_terms, uint32_t total_units);
+
+// ---- kernels_compose_tower.hip: bn_compute_composite with a tower-typed expression.  A workgroup takes kComposeUnitElems contiguous
+// output elements; ops / consts / in_levels are the device copy of a ct_program (compose_tower.hpp), rows the call's input columns.
+constexpr uint32_t kComposeUnitElems = 1024;
+struct compose_tower_args {
+	const void *const *rows;
+	const void *ops;    // ct_op[n_ops]
+	const void *consts; // f128[]
+	const uint32_t *in_levels;
+	uint32_t n_ops;
+	uint32_t result;
+	uint32_t out_level;
+	uint32_t reserved;
+	uint64_t out_elems;
+	void *out;
+};
+uint32_t compose_tower_per_thread(uint32_t n_slots); // output elements a thread holds at a time
+hipError_t launch_compose_tower(hipStream_t s, const compose_tower_args &a, uint32_t n_slots);
 
 // ---- kernels_generate.hip: the columns of a constraint system that are determined by a few integers, one field element or a 0/1
 // projection of a column on the device (Projected at a hypercube vertex: math/src/multilinear_extension.rs:193-237; Constant, StepDown,

@@ -801,6 +801,14 @@ public:
 		check(bn_expr_compile(ctx_, expr.steps().data(), expr.steps().size(), &h));
 		return ExprEval(h, expr.n_vars());
 	}
+	// Extension: a tower-typed expression (bn_expr_compile_tower) -- input v packed at input_levels[v], the output at out_level.  Only
+	// compute_composite takes it (rows of packed subfield columns, the lengths counted in VALUES); every other consumer rejects it.
+	ExprEval compile_expr_tower(const ArithCircuit &expr, const std::vector<uint32_t> &input_levels, uint32_t out_level)
+	{
+		bn_expr *h = nullptr;
+		check(bn_expr_compile_tower(ctx_, expr.steps().data(), expr.steps().size(), input_levels.data(), (uint32_t)input_levels.size(), out_level, &h));
+		return ExprEval(h, input_levels.size());
+	}
 	// execute (layer.rs:65-72): f receives the executor and returns the scalars it wants resolved
 	template <class Fn>
 	std::vector<B128> execute(Fn &&f)

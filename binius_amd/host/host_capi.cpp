@@ -2041,11 +2041,23 @@ int bnh_ring_switch_prove_live(bn_ctx *ctx, uint32_t n_columns, const void *cons
 // The virtual columns of a constraint system derived on the device through the C++ mirror binius_amd/host/witness.hpp; the arguments are
 // described in include/binius_amd_host.h.
 namespace {
+// the expressions of bnh_witness_compute's BNH_WIT_COMPUTED columns: expression e is steps[step_off[e] .. step_off[e + 1]) over the
+// columns expr_inputs[expr_input_off[e] .. expr_input_off[e + 1])
+struct witness_exprs {
+	const bn_step *steps = nullptr;
+	const uint32_t *step_off = nullptr, *inputs = nullptr, *input_off = nullptr;
+	uint32_t n_exprs = 0;
+};
 std::vector<WitnessColumn> witness_columns(uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
-                                           const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets)
+                                           const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, const witness_exprs &ex = witness_exprs{})
 {
 	if (n_columns && (!col_desc || !col_args || !lc_offsets)) throw Error(Error::InputValidation, "null argument");
 	if (n_lc_terms && (!lc_terms || !lc_coeffs)) throw Error(Error::InputValidation, "null argument");
+	if (ex.n_exprs && (!ex.step_off || !ex.input_off)) throw Error(Error::InputValidation, "null argument");
+	for (uint32_t e = 0; e < ex.n_exprs; e++) {
+		if (ex.step_off[e + 1] < ex.step_off[e] || ex.input_off[e + 1] < ex.input_off[e]) throw Error(Error::InputValidation, "witness: expression offsets decrease");
+		if ((ex.step_off[e + 1] > ex.step_off[e] && !ex.steps) || (ex.input_off[e + 1] > ex.input_off[e] && !ex.inputs)) throw Error(Error::InputValidation, "null argument");
+	}
 	std::vector<WitnessColumn> cols(n_columns);
 	for (uint32_t i = 0; i < n_columns; i++) {
 		const uint32_t *d = col_desc + 4 * i;
@@ -2101,6 +2113,15 @@ std::vector<WitnessColumn> witness_columns(uint32_t n_columns, const uint32_t *c
 			c.index = col_args[i];
 			c.value = B128(lc_offsets[i].lo, lc_offsets[i].hi);
 			break;
+		case WitnessColumn::Computed:
+			c.n_vars = d[2];
+			c.tower_level = d[3];
+			if (ex.step_off) { // (without expressions -- bnh_witness_derive / _build -- witness_shapes rejects the kind)
+				if (d[1] >= ex.n_exprs) throw Error(Error::InputValidation, "witness: a computed column names an expression that is not there");
+				c.steps.assign(ex.steps + ex.step_off[d[1]], ex.steps + ex.step_off[d[1] + 1]);
+				c.inputs.assign(ex.inputs + ex.input_off[d[1]], ex.inputs + ex.input_off[d[1] + 1]);
+			}
+			break;
 		default:
 			break; // (witness_shapes rejects it)
 		}
@@ -2110,14 +2131,14 @@ std::vector<WitnessColumn> witness_columns(uint32_t n_columns, const uint32_t *c
 
 int witness_run(bool generate, bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
                 const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
-                uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out)
+                uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out, const witness_exprs *ex = nullptr)
 {
 	return guarded([&]() -> int {
 		if (!ctx || (n_columns && (!d_given || !d_columns_out || !tower_levels_out || !n_vars_out)) || (!d_scratch && scratch_elems))
 			throw Error(Error::InputValidation, "null argument");
-		const std::vector<WitnessColumn> cols = witness_columns(n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets);
+		const std::vector<WitnessColumn> cols = witness_columns(n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets, ex ? *ex : witness_exprs{});
 		ComputeLayer hal(ctx);
-		const WitnessOutput out = witness_derive(hal, cols, FSliceMut{d_scratch, (size_t)scratch_elems}, generate);
+		const WitnessOutput out = witness_derive(hal, cols, FSliceMut{d_scratch, (size_t)scratch_elems}, generate, /*compute=*/ex != nullptr);
 		for (uint32_t i = 0; i < n_columns; i++) {
 			d_columns_out[i] = const_cast<void *>(out.columns[i].ptr);
 			tower_levels_out[i] = out.columns[i].tower_level;
@@ -2164,6 +2185,30 @@ int bnh_witness_build(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc,
 {
 	return witness_run(true, ctx, n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets, d_scratch, scratch_elems, d_columns_out, tower_levels_out,
 	                   n_vars_out, n_waves_out, n_launches_out);
+}
+
+uint64_t bnh_witness_compute_scratch_elems(uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const uint32_t *lc_terms, const bn_f128 *lc_coeffs,
+                                           uint32_t n_lc_terms, const bn_f128 *lc_offsets, const bn_step *steps, const uint32_t *step_off, const uint32_t *expr_inputs,
+                                           const uint32_t *expr_input_off, uint32_t n_exprs)
+{
+	try {
+		const uint32_t zero[2] = {0, 0}; // (no expressions: empty offset tables of our own, so that the kind is known and its index checked)
+		const witness_exprs ex{steps, n_exprs ? step_off : zero, expr_inputs, n_exprs ? expr_input_off : zero, n_exprs};
+		return witness_compute_scratch_elems(witness_columns(n_columns, col_desc, col_args, nullptr, lc_terms, lc_coeffs, n_lc_terms, lc_offsets, ex));
+	} catch (const Error &) {
+		return 0;
+	}
+}
+
+int bnh_witness_compute(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
+                        const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
+                        uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out, const bn_step *steps, const uint32_t *step_off,
+                        const uint32_t *expr_inputs, const uint32_t *expr_input_off, uint32_t n_exprs)
+{
+	const uint32_t zero[2] = {0, 0};
+	const witness_exprs ex{steps, n_exprs ? step_off : zero, expr_inputs, n_exprs ? expr_input_off : zero, n_exprs};
+	return witness_run(true, ctx, n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets, d_scratch, scratch_elems, d_columns_out, tower_levels_out,
+	                   n_vars_out, n_waves_out, n_launches_out, &ex);
 }
 
 } // extern "C"

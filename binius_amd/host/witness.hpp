@@ -20,19 +20,30 @@
 //   Constant, StepDown, StepUp, SelectRow, Powers   the transparents of core/src/transparent/ that their parameters determine
 //   Incrementing       add_structured(Incrementing)                                                BN_GEN_INCREMENTING
 //
-// witness_derive keeps rejecting them as unknown kinds.  NOT taken by either: Projected at other query values
-// (bn_partial_eval_high_batch / bn_fold_right are the ops for it), Composite (bn_compute_composite), general circuit transparents and
-// StructuredFixedSize, TowerBasis, EqIndPartialEval (bn_tensor_expand), ShiftIndPartialEval, DisjointProduct -- the caller derives or
-// uploads those and lists them as Given.
+// witness_derive keeps rejecting them as unknown kinds.  witness_compute takes all of these and the columns of m3's add_computed
+// (m3/src/builder/constraint_system.rs:515-540), each ONE bn_compute_composite with a tower-typed expression (bn_expr_compile_tower):
+//
+//   Computed           add_computed -> composite_mle: an expression over columns of its n_vars, at the tower level the caller names
+//                      (every step's level at most that: the rules of bn_expr_compile_tower)
+//   LinearCombination  add_computed -> linear_combination_with_offset, widened: what is neither the XOR form nor a B128 combination
+//                      becomes the expression sum of coeff * term + offset, left-deep, at the combination's level (pack_fp / pack_b8:
+//                      B1 terms, coefficients in B8 / B32 / B64); a level of 1 or 2 cannot be packed and is InputValidation
+//
+// witness_derive and witness_build keep rejecting those.  NOT taken by any: Projected at other query values
+// (bn_partial_eval_high_batch / bn_fold_right are the ops for it), general circuit transparents and StructuredFixedSize, TowerBasis,
+// EqIndPartialEval (bn_tensor_expand), ShiftIndPartialEval, DisjointProduct -- the caller derives or uploads those and lists them as
+// Given.
 //
 // Waves: a column's wave is one more than its deepest inner (Given and a generated column without an inner: 0; a Packed alias adds
 // nothing).  ONE bn_derive_columns_batch per wave, plus ONE lincomb call per wave that has a B128 combination outside the XOR form,
-// plus ONE bn_generate_columns_batch per wave that has generated columns.  Columns of less than one 16-byte element are host work
+// plus ONE bn_generate_columns_batch per wave that has generated columns, plus ONE bn_compute_composite per expression column of the
+// wave (batching them is left to a later change: n_launches shows the difference).  Columns of less than one 16-byte element are host work
 // (their inner down, one element up), as zerocheck.hpp does for its padding; they make no launch.
 #pragma once
 #include <algorithm>
 #include <cstring>
 
+#include "../csrc/compose_tower.hpp"
 #include "compute_layer.hpp"
 
 namespace binius_amd {
@@ -41,7 +52,9 @@ struct WitnessColumn {
 	enum Kind : uint32_t {
 		Given = 0, Shifted = 1, Repeating = 2, ZeroPadded = 3, Packed = 4, LinearCombination = 5,
 		// witness_build only
-		ProjectedBits = 6, Constant = 7, StepDown = 8, StepUp = 9, SelectRow = 10, Incrementing = 11, Powers = 12
+		ProjectedBits = 6, Constant = 7, StepDown = 8, StepUp = 9, SelectRow = 10, Incrementing = 11, Powers = 12,
+		// witness_compute only
+		Computed = 13
 	};
 	uint32_t kind = Given;
 	// Given
@@ -63,6 +76,9 @@ struct WitnessColumn {
 	uint32_t query_size = 0;
 	uint64_t query_bits = 0, index = 0;
 	B128 value = B128::ZERO(); // Constant: the value; Powers: the base
+	// Computed (tower_level, n_vars above): the expression's steps; variable v is column inputs[v]
+	std::vector<bn_step> steps;
+	std::vector<uint32_t> inputs;
 };
 struct WitnessResolved {
 	const void *ptr = nullptr;
@@ -71,7 +87,7 @@ struct WitnessResolved {
 struct WitnessOutput {
 	std::vector<WitnessResolved> columns;
 	uint32_t n_waves = 0;    // the largest wave of a column
-	uint32_t n_launches = 0; // bn_derive_columns_batch, lincomb and bn_generate_columns_batch calls made
+	uint32_t n_launches = 0; // bn_derive_columns_batch, lincomb, bn_generate_columns_batch and bn_compute_composite calls made
 };
 
 inline size_t witness_column_elems(size_t n_vars, uint32_t level) { return n_vars + level <= 7 ? 1 : (size_t)1 << (n_vars + level - 7); }
@@ -84,23 +100,73 @@ inline uint32_t witness_min_level(B128 c)
 	return level;
 }
 
-// How a column is made: by the derive op, by the lincomb op, by the generate op, on the host, or not at all (Given, Packed)
-enum class WitnessRoute { None, Derive, Lincomb, Host, Generate };
+// How a column is made: by the derive op, by the lincomb op, by the generate op, by bn_compute_composite with a tower-typed
+// expression, on the host, or not at all (Given, Packed)
+enum class WitnessRoute { None, Derive, Lincomb, Host, Generate, Compose };
 struct WitnessShape {
 	uint32_t tower_level = 0, n_vars = 0, wave = 0;
 	WitnessRoute route = WitnessRoute::None;
+	bool expr = false; // made from witness_expr (a Compose column, or one below one element that the host evaluates)
 };
 
+// The expression of a column that goes to bn_compute_composite: a Computed column's own; a combination's sum of coeff * term + offset,
+// left-deep (a coefficient ONE costs no product), variable t its term t
+struct WitnessExpr {
+	std::vector<bn_step> steps;
+	std::vector<uint32_t> inputs;
+};
+inline WitnessExpr witness_expr(const WitnessColumn &c)
+{
+	if (c.kind == WitnessColumn::Computed) return WitnessExpr{c.steps, c.inputs};
+	WitnessExpr e;
+	e.inputs = c.terms;
+	auto push = [&](uint32_t kind, uint32_t a, uint64_t b, B128 cst) {
+		bn_step st{};
+		st.kind = kind;
+		st.a = a;
+		st.b = b;
+		st.cst = cst.raw();
+		e.steps.push_back(st);
+		return (uint32_t)e.steps.size() - 1;
+	};
+	uint32_t acc = 0;
+	for (size_t t = 0; t < c.terms.size(); t++) {
+		uint32_t term = push(BN_STEP_VAR, (uint32_t)t, 0, B128::ZERO());
+		if (c.coefficients[t] != B128::ONE()) term = push(BN_STEP_MUL, term, push(BN_STEP_CONST, 0, 0, c.coefficients[t]), B128::ZERO());
+		acc = t ? push(BN_STEP_ADD, acc, term, B128::ZERO()) : term;
+	}
+	if (c.terms.empty() || c.offset != B128::ZERO()) {
+		const uint32_t off = push(BN_STEP_CONST, 0, 0, c.offset);
+		if (!c.terms.empty()) push(BN_STEP_ADD, acc, off, B128::ZERO());
+	}
+	return e;
+}
+
 // Levels, sizes, waves and routes of every column; every rule of the header is checked here, before the first device call.
-// generate: witness_build's kinds are taken (otherwise they are unknown kinds).
-inline std::vector<WitnessShape> witness_shapes(const std::vector<WitnessColumn> &cols, bool generate = false)
+// generate: witness_build's kinds are taken (otherwise they are unknown kinds); compute: witness_compute's as well.
+inline std::vector<WitnessShape> witness_shapes(const std::vector<WitnessColumn> &cols, bool generate = false, bool compute = false)
 {
 	auto bad = [](const char *msg) { return Error(Error::InputValidation, msg); };
 	std::vector<WitnessShape> sh(cols.size());
+	// an expression column: the rules of bn_expr_compile_tower over the levels of its inputs, checked by its compiler
+	auto check_expr = [&](const WitnessColumn &c, uint32_t out_level, size_t i) {
+		const WitnessExpr e = witness_expr(c);
+		std::vector<uint32_t> levels;
+		for (const uint32_t v : e.inputs) {
+			if (v >= i) throw bad("witness: an inner index is smaller than the column's own");
+			if (sh[v].n_vars != c.n_vars) throw bad("witness: the inputs of an expression column have its n_vars");
+			levels.push_back(sh[v].tower_level);
+		}
+		bn::ct_program prog;
+		const uint32_t none = 0;
+		const char *why = bn::ct_compile(e.steps.data(), e.steps.size(), levels.empty() ? &none : levels.data(), (uint32_t)levels.size(), out_level, prog);
+		if (why) throw Error(Error::InputValidation, std::string("witness: expression column: ") + why);
+	};
 	for (size_t i = 0; i < cols.size(); i++) {
 		const WitnessColumn &c = cols[i];
 		WitnessShape &s = sh[i];
 		if (c.kind > WitnessColumn::LinearCombination && !generate) throw bad("witness: unknown column kind");
+		if (c.kind > WitnessColumn::Powers && !compute) throw bad("witness: unknown column kind");
 		if (((c.kind >= WitnessColumn::Shifted && c.kind <= WitnessColumn::Packed) || c.kind == WitnessColumn::ProjectedBits) && c.inner >= i)
 			throw bad("witness: an inner index is smaller than the column's own");
 		const bool in_level = c.tower_level >= 7 || (c.value.hi == 0 && (c.tower_level == 6 || c.value.lo < ((uint64_t)1 << (1u << c.tower_level))));
@@ -140,6 +206,7 @@ inline std::vector<WitnessShape> witness_shapes(const std::vector<WitnessColumn>
 			if (c.terms.size() != c.coefficients.size()) throw bad("witness: one coefficient per term");
 			if (c.terms.size() > BN_PEL_MAX_TERMS) throw bad("witness: too many terms in a combination");
 			uint32_t level = witness_min_level(c.offset), wave = 0;
+			uint32_t raw_level = 0;
 			bool unit = true;
 			for (size_t t = 0; t < c.terms.size(); t++) {
 				if (c.terms[t] >= i) throw bad("witness: an inner index is smaller than the column's own");
@@ -148,9 +215,17 @@ inline std::vector<WitnessShape> witness_shapes(const std::vector<WitnessColumn>
 				wave = std::max(wave, sh[c.terms[t]].wave);
 				unit = unit && c.coefficients[t] == B128::ONE();
 			}
+			raw_level = level;
 			if (level == 1 || level == 2) level = 3; // (the packed levels of this backend: a B2 / B4 constant lives in a B8 column)
 			for (const uint32_t t : c.terms) unit = unit && sh[t].tower_level == level;
 			s = WitnessShape{level, c.n_vars, wave + 1, unit ? WitnessRoute::Derive : WitnessRoute::Lincomb};
+			if (!unit && level != 7 && compute) {
+				// the reference's level (multilinear.rs:91-266), as a tower-typed expression
+				if (raw_level == 1 || raw_level == 2) throw bad("witness: a combination of tower level 1 or 2 cannot be packed");
+				check_expr(c, raw_level, i);
+				s = WitnessShape{raw_level, c.n_vars, wave + 1, WitnessRoute::Compose, true};
+				break;
+			}
 			if (!unit && level != 7)
 				throw bad("witness: a combination is either all ONE coefficients over terms of its own level or a B128 one (Projected, Composite, transparent and "
 				          "structured columns are not taken either: list them as Given)");
@@ -181,19 +256,28 @@ inline std::vector<WitnessShape> witness_shapes(const std::vector<WitnessColumn>
 			if (c.tower_level < 3) throw bad("witness: a column of powers has tower level 3 .. 7");
 			if (!in_level) throw bad("witness: the base of Powers is a value of its tower level");
 			break;
+		case WitnessColumn::Computed: {
+			if (c.n_vars > BN_PE_MAX_VARS) throw bad("witness: a column has at most 2^40 values");
+			check_expr(c, c.tower_level, i);
+			uint32_t wave = 0;
+			for (const uint32_t v : c.inputs) wave = std::max(wave, sh[v].wave);
+			s = WitnessShape{c.tower_level, c.n_vars, wave + 1, WitnessRoute::Compose, true};
+			break;
+		}
 		default:
 			throw bad("witness: unknown column kind");
 		}
 		if (s.n_vars > BN_PE_MAX_VARS) throw bad("witness: a column has at most 2^40 values");
-		if ((s.route == WitnessRoute::Derive || s.route == WitnessRoute::Generate) && s.n_vars + s.tower_level < 7) s.route = WitnessRoute::Host;
+		if ((s.route == WitnessRoute::Derive || s.route == WitnessRoute::Generate || s.route == WitnessRoute::Compose) && s.n_vars + s.tower_level < 7)
+			s.route = WitnessRoute::Host;
 	}
 	return sh;
 }
 
 // Exact: one element for the query ONE when a combination goes to the lincomb op, then every derived column at its packed size.
-inline size_t witness_derive_scratch_elems(const std::vector<WitnessColumn> &cols, bool generate = false)
+inline size_t witness_derive_scratch_elems(const std::vector<WitnessColumn> &cols, bool generate = false, bool compute = false)
 {
-	const std::vector<WitnessShape> sh = witness_shapes(cols, generate);
+	const std::vector<WitnessShape> sh = witness_shapes(cols, generate, compute);
 	size_t total = 0;
 	bool one = false;
 	for (const WitnessShape &s : sh) {
@@ -290,10 +374,39 @@ inline B128 witness_small_column(const WitnessColumn &c, const WitnessShape &s, 
 	return out;
 }
 
-inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch, bool generate = false)
+// An expression column of less than one element, value by value in B128 (bn_scalar_mul) from its inputs' single elements
+inline B128 witness_small_expr(const WitnessExpr &e, const WitnessShape &s, const std::vector<uint32_t> &in_levels, const std::vector<B128> &inners)
 {
-	const std::vector<WitnessShape> sh = witness_shapes(cols, generate);
-	if (scratch.len_ < witness_derive_scratch_elems(cols, generate)) throw Error(Error::InputValidation, "scratch holds fewer than witness_derive_scratch_elems elements");
+	B128 out = B128::ZERO();
+	std::vector<B128> val(e.steps.size());
+	for (size_t i = 0; i < ((size_t)1 << s.n_vars); i++) {
+		for (size_t k = 0; k < e.steps.size(); k++) {
+			const bn_step &st = e.steps[k];
+			switch (st.kind) {
+			case BN_STEP_VAR: val[k] = B128(witness_detail::get(inners[st.a], in_levels[st.a], i)); break;
+			case BN_STEP_CONST: val[k] = B128(st.cst.lo, st.cst.hi); break;
+			case BN_STEP_ADD: val[k] = val[st.a] + val[st.b]; break;
+			case BN_STEP_MUL: val[k] = val[st.a] * val[st.b]; break;
+			default: { // POW
+				B128 r = B128::ONE();
+				for (int b = 63; b >= 0; b--) {
+					r = r * r;
+					if ((st.b >> b) & 1) r = r * val[st.a];
+				}
+				val[k] = r;
+				break;
+			}
+			}
+		}
+		witness_detail::put(out, s.tower_level, i, val.back().lo); // (below one element: the level is at most 6, and subfields are closed)
+	}
+	return out;
+}
+
+inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch, bool generate = false, bool compute = false)
+{
+	const std::vector<WitnessShape> sh = witness_shapes(cols, generate, compute);
+	if (scratch.len_ < witness_derive_scratch_elems(cols, generate, compute)) throw Error(Error::InputValidation, "scratch holds fewer than witness_derive_scratch_elems elements");
 	DeviceBumpAllocator alloc(scratch);
 	WitnessOutput out;
 	out.columns.resize(cols.size());
@@ -322,12 +435,16 @@ inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<Witness
 		std::vector<bn_pel_job> pel_jobs;
 		std::vector<bn_pel_term> pel_terms;
 		std::vector<void *> pel_outs;
-		std::vector<size_t> on_host;
+		std::vector<size_t> on_host, composed;
 		for (size_t i = 0; i < cols.size(); i++) {
 			if (sh[i].wave != wave || sh[i].route == WitnessRoute::None) continue;
 			const WitnessColumn &c = cols[i];
 			if (sh[i].route == WitnessRoute::Host) {
 				on_host.push_back(i);
+				continue;
+			}
+			if (sh[i].route == WitnessRoute::Compose) {
+				composed.push_back(i);
 				continue;
 			}
 			if (sh[i].route == WitnessRoute::Generate) {
@@ -401,8 +518,41 @@ inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<Witness
 			check(bn_generate_columns_batch(hal.raw_ctx(), gen_jobs.data(), (uint32_t)gen_jobs.size()));
 			out.n_launches++;
 		}
+		for (const size_t i : composed) { // one bn_compute_composite per expression column
+			const WitnessExpr e = witness_expr(cols[i]);
+			std::vector<uint32_t> levels;
+			std::vector<const void *> rows;
+			for (const uint32_t v : e.inputs) {
+				levels.push_back(sh[v].tower_level);
+				rows.push_back(out.columns[v].ptr);
+			}
+			const uint32_t none = 0;
+			bn_expr *h = nullptr;
+			check(bn_expr_compile_tower(hal.raw_ctx(), e.steps.data(), e.steps.size(), levels.empty() ? &none : levels.data(), (uint32_t)levels.size(), sh[i].tower_level, &h));
+			const void *no_row = nullptr;
+			const uint64_t n_values = (uint64_t)1 << sh[i].n_vars;
+			const int rc = bn_compute_composite(hal.raw_ctx(), rows.empty() ? &no_row : rows.data(), (uint32_t)rows.size(), n_values, const_cast<void *>(out.columns[i].ptr),
+			                                    n_values, h);
+			bn_expr_free(h);
+			check(rc);
+			out.n_launches++;
+		}
 		for (const size_t i : on_host) {
 			const WitnessColumn &c = cols[i];
+			if (sh[i].expr) {
+				const WitnessExpr e = witness_expr(c);
+				std::vector<uint32_t> levels;
+				std::vector<B128> inners(e.inputs.size()), one(1);
+				for (size_t t = 0; t < e.inputs.size(); t++) {
+					levels.push_back(sh[e.inputs[t]].tower_level);
+					hal.copy_d2h(FSlice{out.columns[e.inputs[t]].ptr, 1}, one);
+					inners[t] = one[0];
+				}
+				one[0] = witness_small_expr(e, sh[i], levels, inners);
+				FSliceMut dst{const_cast<void *>(out.columns[i].ptr), 1};
+				hal.copy_h2d(one, dst);
+				continue;
+			}
 			if (c.kind >= WitnessColumn::ProjectedBits) {
 				std::vector<B128> inner, one(1);
 				if (c.kind == WitnessColumn::ProjectedBits) {
@@ -431,5 +581,8 @@ inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<Witness
 // witness_derive with the generated kinds taken (the header)
 inline size_t witness_build_scratch_elems(const std::vector<WitnessColumn> &cols) { return witness_derive_scratch_elems(cols, true); }
 inline WitnessOutput witness_build(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch) { return witness_derive(hal, cols, scratch, true); }
+// witness_build with the expression columns taken as well (the header)
+inline size_t witness_compute_scratch_elems(const std::vector<WitnessColumn> &cols) { return witness_derive_scratch_elems(cols, true, true); }
+inline WitnessOutput witness_compute(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch) { return witness_derive(hal, cols, scratch, true, true); }
 
 } // namespace binius_amd

@@ -224,6 +224,16 @@ pub const BN_SHIFT_LOGICAL_LEFT: u32 = 1;
 pub const BN_SHIFT_LOGICAL_RIGHT: u32 = 2;
 pub const BN_DERIVE_N: usize = 3;
 
+/// bn_expr_compile_tower: the caps of a tower-typed expression; bn_compute_composite_counters: what its calls did.
+pub const BN_TOWER_EXPR_MAX_STEPS: usize = 1024;
+pub const BN_TOWER_EXPR_MAX_INPUTS: usize = 256;
+pub const BN_TOWER_EXPR_MAX_LIVE: usize = 16;
+pub const BN_CC_TOWER_CALLS: usize = 0;
+pub const BN_CC_TOWER_LAUNCHES: usize = 1;
+pub const BN_CC_TOWER_BITWISE: usize = 2;
+pub const BN_CC_TOWER_VALUES: usize = 3;
+pub const BN_CC_N: usize = 4;
+
 /// One generated column of bn_generate_columns_batch (a projection at a hypercube vertex, a transparent that its parameters determine, or
 /// the incrementing column).
 #[repr(C)]
@@ -318,6 +328,16 @@ unsafe extern "C" {
 	pub fn bn_expr_compile(ctx: *mut bn_ctx, steps: *const bn_step, n_steps: u64, out: *mut *mut bn_expr) -> c_int;
 	pub fn bn_expr_free(expr: *mut bn_expr) -> c_int;
 	pub fn bn_expr_n_vars(expr: *const bn_expr, n_vars: *mut u32) -> c_int;
+	pub fn bn_expr_compile_tower(
+		ctx: *mut bn_ctx,
+		steps: *const bn_step,
+		n_steps: u64,
+		input_levels: *const u32,
+		n_inputs: u32,
+		out_level: u32,
+		out: *mut *mut bn_expr,
+	) -> c_int;
+	pub fn bn_compute_composite_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 
 	pub fn bn_extrapolate_line(ctx: *mut bn_ctx, d_evals_0: *mut c_void, n0: u64, d_evals_1: *const c_void, n1: u64, z: *const bn_f128) -> c_int;
 	pub fn bn_extrapolate_line_batch(

@@ -105,6 +105,27 @@ impl Mi355xLayer {
 		Ok(Self { ctx })
 	}
 
+	/// Extension (not a trait method): a tower-typed expression for `compute_composite` on PACKED SUBFIELD rows -- the computed
+	/// columns of m3's `add_computed` (`pack_fp`, B1 composites).  `input_levels[v]` is the tower level (0 or 3 ..= 7) input `v` is
+	/// packed at, `out_level` the output's; the lengths of the rows and of the output are then counted in VALUES.  Every other
+	/// consumer of an expression rejects it (bn_expr_compile_tower, include/binius_amd.h).
+	pub fn compile_expr_tower(&self, expr: &ArithCircuit<B128>, input_levels: &[u32], out_level: u32) -> Result<Mi355xExpr, Error> {
+		let steps: Vec<bn_step> = expr.steps().iter().map(step_to_ffi).collect();
+		let mut handle = ptr::null_mut();
+		check(unsafe {
+			ffi::bn_expr_compile_tower(
+				self.ctx,
+				steps.as_ptr(),
+				steps.len() as u64,
+				input_levels.as_ptr(),
+				input_levels.len() as u32,
+				out_level,
+				&mut handle,
+			)
+		})?;
+		Ok(Mi355xExpr(handle))
+	}
+
 	/// Base address and size (in elements) of the context's arena.
 	pub(crate) fn arena(&self) -> (*mut u8, usize) {
 		let mut base = ptr::null_mut();

@@ -94,6 +94,27 @@ typedef struct {
 int bn_expr_compile(bn_ctx *ctx, const bn_step *steps, uint64_t n_steps, bn_expr **out);
 int bn_expr_free(bn_expr *expr);
 int bn_expr_n_vars(const bn_expr *expr, uint32_t *n_vars);
+/* Extension (not a trait method): a TOWER-TYPED expression, for bn_compute_composite on packed subfield columns -- the computed
+ * columns of m3's add_computed (m3/src/builder/constraint_system.rs:515-540): pack_fp / pack_b8 (sum of bit_i * beta_i: B1 terms,
+ * coefficients and output in B8 / B32 / B64) and composites such as prod_high[bit] + x_is_negative * (prod_high[bit] + zout[bit]) at B1
+ * (m3/src/gadgets/mul.rs:466-489).  Steps as for bn_expr_compile: topological order, the last step is the result.  input_levels[v]
+ * (variable v) and out_level are packable tower levels, 0 or 3 .. 7.  Every step has a level: VAR its input's; CONST the smallest l
+ * in 0 .. 7 with cst < 2^(2^l) (1 and 2 are fine for a constant); ADD / MUL the maximum of its operands'; POW its base's; none may
+ * exceed out_level.  A value of a lower level is zero-extended (the tower embedding is the identity on the low bits), so the result
+ * equals evaluating in B128 and truncating to 2^out_level bits.
+ * VAR and CONST steps hold no slot; an ADD / MUL / POW result holds one from its step to its last use, and at most
+ * BN_TOWER_EXPR_MAX_LIVE may be live at once (the kernel's LDS: 16 slots x 16 B x 256 threads = 64 KiB).  Steps that do not feed the
+ * result are dropped first.
+ * BN_ERR_INPUT_VALIDATION with nothing allocated: null arguments, n_steps = 0 or above BN_TOWER_EXPR_MAX_STEPS, n_inputs above
+ * BN_TOWER_EXPR_MAX_INPUTS, an operand that is not an earlier step, a VAR index >= n_inputs, an unknown kind, level 1, 2 or > 7 for an
+ * input or the output, a step above out_level, too many live slots.
+ * bn_expr_n_vars answers n_inputs; bn_expr_free frees it.  ONLY bn_compute_composite takes such an expression: every other consumer
+ * of a bn_expr (bn_kernel_launch, bn_hal_round_evals) answers BN_ERR_INPUT_VALIDATION before it launches anything. */
+#define BN_TOWER_EXPR_MAX_STEPS 1024
+#define BN_TOWER_EXPR_MAX_INPUTS 256
+#define BN_TOWER_EXPR_MAX_LIVE 16
+int bn_expr_compile_tower(bn_ctx *ctx, const bn_step *steps, uint64_t n_steps, const uint32_t *input_levels, uint32_t n_inputs,
+                          uint32_t out_level, bn_expr **out);
 
 /* ---- ComputeLayerExecutor ---- */
 /* extrapolate_line (layer.rs:421): evals_0[i] += (evals_1[i] - evals_0[i]) * z */
@@ -138,9 +159,19 @@ int bn_fold_right(bn_ctx *ctx, const void *d_mat, uint64_t mat_len, uint32_t tow
 int bn_fri_fold(bn_ctx *ctx, const uint64_t *h_s_evals, uint32_t tw_level, uint32_t log_domain, uint32_t log_len,
                 uint32_t log_batch_size, const bn_f128 *h_challenges, uint32_t n_challenges, const void *d_in,
                 uint64_t in_len, void *d_out, uint64_t out_len);
-/* compute_composite (layer.rs:459) */
+/* compute_composite (layer.rs:459)
+ * With an expression of bn_expr_compile_tower the rows are PACKED SUBFIELD columns: row_len = out_len = the number of VALUES, a power of
+ * two with row_len * 2^out_level >= 128; d_rows[v] is input v packed at input_levels[v] as bn_hal_multilinear says (a row below one
+ * element: the low bits of one 16-byte element); d_out receives exactly row_len * 2^out_level / 128 elements, out[i] = expr(in_0[i], ...)
+ * in T_out_level.  Bit-exact, overwritten; inputs are only read; d_out overlaps no row; pointers 16-byte aligned; n_inputs <= n_rows.
+ * Everything else is BN_ERR_INPUT_VALIDATION with nothing launched and no counter moved.  ONE launch per call (kernels_compose_tower.hip):
+ * a thread owns whole output elements, level 0 is bitwise on the whole element, a product walks the bits of its operand of lower level. */
 int bn_compute_composite(bn_ctx *ctx, const void *const *d_rows, uint32_t n_rows, uint64_t row_len, void *d_out,
                          uint64_t out_len, const bn_expr *expr);
+/* Read-only, per context (not part of the reference interface): accepted bn_compute_composite calls with a tower-typed expression, the
+ * launches they made, how many of them ran at level 0 (bitwise) and at levels 3 .. 7 (per value).  A rejected call counts nowhere. */
+enum { BN_CC_TOWER_CALLS = 0, BN_CC_TOWER_LAUNCHES = 1, BN_CC_TOWER_BITWISE = 2, BN_CC_TOWER_VALUES = 3, BN_CC_N = 4 };
+int bn_compute_composite_counters(bn_ctx *ctx, uint64_t *counters /*[BN_CC_N]*/);
 /* pairwise_product_reduce (layer.rs:505) */
 int bn_pairwise_product_reduce(bn_ctx *ctx, const void *d_in, uint64_t n, void *const *d_round_outs,
                                const uint64_t *round_lens, uint32_t n_rounds);
@@ -441,8 +472,9 @@ int bn_merge_counters(bn_ctx *ctx, uint64_t *counters /*[BN_MERGE_N]*/);
  * terms outside the term list, an offset outside the level's field and every bound stated above.
  * NOT taken here: any other LinearCombination (a B128 one with arbitrary coefficients is bn_partial_eval_high_lincomb_batch at
  * query_vars = 0), Projected (at ZERO / ONE query values and the transparent and structured columns that a few parameters determine:
- * bn_generate_columns_batch below; at other query values: bn_partial_eval_high_batch / bn_fold_right), Composite
- * (bn_compute_composite), Packed (the same bytes: an alias), general circuit transparents. */
+ * bn_generate_columns_batch below; at other query values: bn_partial_eval_high_batch / bn_fold_right), Packed (the same bytes: an alias),
+ * general circuit transparents.  A subfield LinearCombination with other coefficients (pack_fp: B1 terms, B32 coefficients) and Composite
+ * at the column's own level are bn_compute_composite with an expression of bn_expr_compile_tower (the plan: bnh_witness_compute). */
 enum { BN_DERIVE_SHIFTED = 0, BN_DERIVE_REPEATING = 1, BN_DERIVE_ZERO_PADDED = 2, BN_DERIVE_XOR_COMBINATION = 3 };
 enum { BN_SHIFT_CIRCULAR_LEFT = 0, BN_SHIFT_LOGICAL_LEFT = 1, BN_SHIFT_LOGICAL_RIGHT = 2 }; /* ShiftVariant, multilinear.rs */
 typedef struct {
@@ -500,7 +532,7 @@ int bn_derive_counters(bn_ctx *ctx, uint64_t *counters /*[BN_DERIVE_N]*/);
  * kind's), a null or misaligned pointer, a forbidden overlap, an output below one element, n_vars above BN_PE_MAX_VARS, reserved != 0
  * and every bound stated above.
  * NOT taken here: Projected at query values other than ZERO and ONE (bn_partial_eval_high_batch / bn_fold_right), Composite
- * (bn_compute_composite), general circuit transparents and StructuredFixedSize, TowerBasis, EqIndPartialEval (bn_tensor_expand),
+ * (bn_compute_composite with an expression of bn_expr_compile_tower: bnh_witness_compute), general circuit transparents and StructuredFixedSize, TowerBasis, EqIndPartialEval (bn_tensor_expand),
  * ShiftIndPartialEval, DisjointProduct. */
 enum {
 	BN_GEN_PROJECTED_BITS = 0,

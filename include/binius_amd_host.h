@@ -585,7 +585,8 @@ int bnh_piop_prove_committed_open_live(bn_ctx *ctx, uint32_t n_committed, const 
  *   - The B128 combinations outside the XOR form share, per wave, ONE bn_partial_eval_high_lincomb_batch at query_vars = 0, its
  *     one-element query ONE in scratch.
  *   - A combination that is neither is BN_ERR_INPUT_VALIDATION.  Projected, transparent and structured polynomials are NOT taken HERE
- *     (bnh_witness_build below takes those that its kinds name), Composite (bn_compute_composite) by neither: list them as given columns.
+ *     (bnh_witness_build below takes those that its kinds name), Composite and the other subfield combinations by neither
+ *     (bnh_witness_compute further below takes both): list them as given columns.
  *   - Columns of less than one 16-byte element are host work (one element read, one written) and make no launch.
  * d_columns_out / tower_levels_out / n_vars_out [n_columns]: every column's pointer (a given column's own, an alias's inner's, a derived
  * column's place in d_scratch), level and n_vars; *n_waves_out: the largest wave; *n_launches_out: the op calls made (either may be null).
@@ -615,14 +616,42 @@ int bnh_witness_derive(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc
  * every wave that has such columns makes ONE bn_generate_columns_batch beside its derive and lincomb calls (wave 0 makes no other
  * call).  Columns below one 16-byte element stay host work (a projection's inner is read back whole).  The scratch formula stays
  * exact: every derived or generated column at its packed size, plus the lincomb op's one element.  bnh_witness_derive itself rejects
- * these kinds as before.  NOT taken: Projected at other query values, Composite, general circuit transparents and StructuredFixedSize,
- * TowerBasis, EqIndPartialEval, ShiftIndPartialEval, DisjointProduct: list them as given columns. */
+ * these kinds as before.  NOT taken: Projected at other query values, general circuit transparents and StructuredFixedSize,
+ * TowerBasis, EqIndPartialEval, ShiftIndPartialEval, DisjointProduct: list them as given columns; Composite and subfield combinations
+ * outside the XOR form (m3's add_computed): bnh_witness_compute below. */
 enum { BNH_WIT_PROJECTED_BITS = 6, BNH_WIT_CONSTANT = 7, BNH_WIT_STEP_DOWN = 8, BNH_WIT_STEP_UP = 9, BNH_WIT_SELECT_ROW = 10, BNH_WIT_INCREMENTING = 11, BNH_WIT_POWERS = 12 };
 uint64_t bnh_witness_build_scratch_elems(uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const uint32_t *lc_terms, const bn_f128 *lc_coeffs,
                                          uint32_t n_lc_terms, const bn_f128 *lc_offsets);
 int bnh_witness_build(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
                       const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
                       uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out);
+
+/* bnh_witness_build with the columns of m3's add_computed computed on the device as well (m3/src/builder/constraint_system.rs:515-540),
+ * each by ONE bn_compute_composite with a tower-typed expression (bn_expr_compile_tower, include/binius_amd.h): the last kind of witness
+ * column that crossed PCIe at column size.  The arguments of bnh_witness_build, then the expressions: expression e is
+ * steps[step_off[e] .. step_off[e + 1]) over the columns expr_inputs[expr_input_off[e] .. expr_input_off[e + 1]) (variable v of the steps
+ * is the v-th of them); step_off and expr_input_off hold n_exprs + 1 entries.
+ *   BNH_WIT_COMPUTED  a = expression index, b = n_vars, c = the column's tower level (0 or 3 .. 7): add_computed -> composite_mle, e.g.
+ *                     prod_high[bit] + x_is_negative * (prod_high[bit] + zout[bit]) at B1 (m3/src/gadgets/mul.rs:466-489).  The inputs are
+ *                     column indices smaller than the column's own, all of n_vars = b; levels follow bn_expr_compile_tower (no step above c).
+ *   BNH_WIT_LINCOMB   widened: the XOR form and the B128 form run as in bnh_witness_derive; every other combination -- pack_fp / pack_b8:
+ *                     sum of bit_i * beta_i with B1 terms and coefficients in B8 / B32 / B64 -- becomes the expression sum of coeff * term +
+ *                     offset, left-deep, at the reference's level: the maximum of the terms' levels and the minimal levels of coefficients
+ *                     and offset.  A level of 1 or 2 cannot be packed: BN_ERR_INPUT_VALIDATION.
+ * Such a column's wave is one more than its deepest input's; each is one bn_compute_composite call of its wave, counted in
+ * *n_launches_out (batching several into one launch is left to a later change: the counter shows the difference).  Below one 16-byte
+ * element it is host work like the other kinds: its inputs' single elements read back, evaluated value by value with bn_scalar_mul, one
+ * element written.  bnh_witness_compute_scratch_elems is exact -- every derived, generated or computed column at its packed size, plus the
+ * lincomb op's one element -- and 0 for a plan that bnh_witness_compute would reject.  bnh_witness_derive and bnh_witness_build keep
+ * rejecting kind 13 and the combinations they rejected. */
+enum { BNH_WIT_COMPUTED = 13 };
+uint64_t bnh_witness_compute_scratch_elems(uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const uint32_t *lc_terms, const bn_f128 *lc_coeffs,
+                                           uint32_t n_lc_terms, const bn_f128 *lc_offsets, const bn_step *steps, const uint32_t *step_off, const uint32_t *expr_inputs,
+                                           const uint32_t *expr_input_off, uint32_t n_exprs);
+int bnh_witness_compute(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
+                        const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
+                        uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out, const bn_step *steps, const uint32_t *step_off,
+                        const uint32_t *expr_inputs, const uint32_t *expr_input_off, uint32_t n_exprs);
 
 /* An array-backed transcript, for C callers, benchmarks and tests: it serves samples[n_samples] to `sample` and
  * bit_samples[n_bit_samples] (masked to `bits`) to `sample_bits`, in order, returns non-zero when they run out, and records every
