@@ -29,6 +29,8 @@ BN_ME_MAX_LO_VARS, BN_ME_MAX_JOBS = 10, 4096  # bn_mle_evaluate_batch
 BN_MERGE_TILE_LOG2 = 6  # bn_merge_multilins: multilinears of at least twice as many variables are tiled jobs
 BN_TOWER_EXPR_MAX_STEPS, BN_TOWER_EXPR_MAX_INPUTS, BN_TOWER_EXPR_MAX_LIVE = 1024, 256, 16  # bn_expr_compile_tower
 BN_CC_TOWER_CALLS, BN_CC_TOWER_LAUNCHES, BN_CC_TOWER_BITWISE, BN_CC_TOWER_VALUES, BN_CC_N = 0, 1, 2, 3, 4  # bn_compute_composite_counters
+BN_COMPOSE_BATCH_MAX_JOBS, BN_COMPOSE_JOB_DESC_WORDS = 4096, 4  # bn_expr_compile_tower_batch
+BN_CCB_CALLS, BN_CCB_LAUNCHES, BN_CCB_JOBS, BN_CCB_PROGRAMS, BN_CCB_N = 0, 1, 2, 3, 4  # bn_compute_composite_batch_counters
 
 
 def lib_path():
@@ -214,6 +216,8 @@ def lib():
         "bn_expr_n_vars": [vp, C.POINTER(u32)],
         "bn_expr_compile_tower": [vp, C.POINTER(Step), u64, C.POINTER(u32), u32, u32, C.POINTER(vp)],
         "bn_compute_composite_counters": [vp, C.POINTER(u64)],
+        "bn_expr_compile_tower_batch": [vp, C.POINTER(vp), u32, C.POINTER(u32), C.POINTER(u64), u32, C.POINTER(vp)],
+        "bn_compute_composite_batch_counters": [vp, C.POINTER(u64)],
         "bn_extrapolate_line": [vp, vp, u64, vp, u64, PF],
         "bn_extrapolate_line_batch": [vp, C.POINTER(vp), C.POINTER(vp), u32, u64, PF],
         "bn_extrapolate_line_batch_scaled": [vp, C.POINTER(vp), C.POINTER(vp), u32, u64, PF, u32, PF],
@@ -313,7 +317,7 @@ ABI_SYMBOLS = [
     "bn_partial_eval_high_batch", "bn_partial_eval_counters", "bn_flush_witness_batch", "bn_flush_counters",
     "bn_univariate_fold_batch", "bn_univariate_fold_counters", "bn_ring_switch_eq_ind_batch", "bn_ring_switch_counters",
     "bn_mle_evaluate_batch", "bn_mle_evaluate_counters", "bn_partial_eval_high_lincomb_batch", "bn_partial_eval_lincomb_counters",
-    "bn_merge_multilins", "bn_merge_counters", "bn_derive_columns_batch", "bn_derive_counters", "bn_generate_columns_batch", "bn_generate_counters", "bn_expr_compile_tower", "bn_compute_composite_counters", "bn_fri_query_proof_elems", "bn_fri_query_openings", "bn_fri_query_counters",
+    "bn_merge_multilins", "bn_merge_counters", "bn_derive_columns_batch", "bn_derive_counters", "bn_generate_columns_batch", "bn_generate_counters", "bn_expr_compile_tower", "bn_compute_composite_counters", "bn_expr_compile_tower_batch", "bn_compute_composite_batch_counters", "bn_fri_query_proof_elems", "bn_fri_query_openings", "bn_fri_query_counters",
     "bn_peer_create", "bn_peer_connect", "bn_peer_set_active", "bn_peer_stats", "bn_peer_destroy", "bn_host_tail_allow_peer", "bn_host_tail_active",
 ]
 
@@ -775,6 +779,29 @@ class Context:
         self._exprs.append(e)
         return e
 
+    def expr_compile_tower_batch(self, exprs, jobs):
+        """bn_expr_compile_tower_batch: one handle for a batch of expr_compile_tower expressions, for compute_composite_tower_batch.
+        jobs: (expr index, first_row, n_vars, out_offset) each, or a 5-tuple with `reserved` last.  The batch copies the members'
+        programs: they may be freed right after."""
+        hs = (C.c_void_p * max(1, len(exprs)))(*[e.handle for e in exprs])
+        desc = (C.c_uint32 * max(4, 4 * len(jobs)))()
+        offs = (C.c_uint64 * max(1, len(jobs)))()
+        for i, j in enumerate(jobs):
+            desc[4 * i : 4 * i + 4] = [j[0], j[1], j[2], j[4] if len(j) > 4 else 0]
+            offs[i] = j[3]
+        h = C.c_void_p()
+        _check(lib().bn_expr_compile_tower_batch(self._h, hs, len(exprs), desc, offs, len(jobs), C.byref(h)))
+        e = Expr(h, [])
+        self._exprs.append(e)
+        return e
+
+    def compute_composite_batch_counters(self):
+        """bn_compute_composite_batch_counters: accepted compute_composite calls with a batch, their launches, the jobs they served, the
+        distinct programs they uploaded.  Rejected calls count nowhere."""
+        c = (C.c_uint64 * BN_CCB_N)()
+        _check(lib().bn_compute_composite_batch_counters(self._h, c))
+        return {"calls": int(c[0]), "launches": int(c[1]), "jobs": int(c[2]), "programs": int(c[3])}
+
     def compute_composite_counters(self):
         """bn_compute_composite_counters: accepted compute_composite calls with a tower-typed expression, their launches, how many ran
         at level 0 (bitwise) and at levels 3 .. 7 (per value).  Rejected calls count nowhere."""
@@ -951,6 +978,12 @@ class Context:
         input level v (at least one element), output n_values values at its output level."""
         rows = (C.c_void_p * max(1, len(inputs)))(*[r.ptr for r in inputs])
         _check(lib().bn_compute_composite(self._h, rows, len(inputs), n_values, output.ptr, n_values, expr.handle))
+
+    def compute_composite_tower_batch(self, rows, arena, batch):
+        """bn_compute_composite with a batch of expr_compile_tower_batch: rows are the input columns of all jobs (job j's input v is
+        rows[first_row_j + v]), arena the slice the jobs' out_offsets count from.  One launch."""
+        ptrs = (C.c_void_p * max(1, len(rows)))(*[r.ptr for r in rows])
+        _check(lib().bn_compute_composite(self._h, ptrs, len(rows), arena.len, arena.ptr, arena.len, batch.handle))
 
     def pairwise_product_reduce(self, inp, round_outputs):
         outs = (C.c_void_p * max(1, len(round_outputs)))(*[r.ptr for r in round_outputs])

@@ -375,6 +375,8 @@ def _plain_host_lib():
         L.bnh_witness_compute_scratch_elems.argtypes = L.bnh_witness_derive_scratch_elems.argtypes + expr_args
         L.bnh_witness_compute.restype = C.c_int
         L.bnh_witness_compute.argtypes = L.bnh_witness_derive.argtypes + expr_args
+        L.bnh_witness_compute_batched.restype = C.c_int
+        L.bnh_witness_compute_batched.argtypes = L.bnh_witness_compute.argtypes
         # the _live forms: the array form's arguments without the samples, the transcript's table where LIVE_FORMS says
         for name, (live, drop, at, _splice) in LIVE_FORMS.items():
             if name == "bnh_evalcheck_bivariate_prove":
@@ -1806,9 +1808,17 @@ class WitnessCompute(WitnessBuild):
     def run(self):
         from ._ffi import DevSlice
 
-        rc = host_lib().bnh_witness_compute(self.hal._h, self.n, self.desc, self.args, self.given, self.terms, self.coeffs, self.n_terms, self.offsets,
+        rc = getattr(host_lib(), self._RUN)(self.hal._h, self.n, self.desc, self.args, self.given, self.terms, self.coeffs, self.n_terms, self.offsets,
                                             self.scratch.ptr if self.scratch is not None else None, self.scratch.len if self.scratch is not None else 0,
                                             self.ptrs, self.levels, self.n_vars, C.byref(self._waves), C.byref(self._launches), *self.exprs)
         if rc != 0:
             raise BnError(rc, host_lib().bnh_last_error().decode())
         return [(DevSlice(self.ptrs[i], max(1, (1 << (self.n_vars[i] + self.levels[i])) >> 7)), int(self.levels[i]), int(self.n_vars[i])) for i in range(self.n)]
+
+
+class WitnessComputeBatched(WitnessCompute):
+    """WitnessCompute with the expression columns of a wave in one launch (bnh_witness_compute_batched = witness_compute_batched of
+    binius_amd/host/witness.hpp, over Context.expr_compile_tower_batch's op): the same columns, bytes and rejections; n_launches counts
+    one per wave that has expression columns.  scratch_elems is WitnessCompute's."""
+
+    _RUN = "bnh_witness_compute_batched"

@@ -916,6 +916,37 @@ int bn_expr_compile_tower(bn_ctx *ctx, const bn_step *steps, uint64_t n_steps, c
 	return BN_OK;
 }
 
+// (the plan -- duplicate programs dropped, job table, classes, LDS, the sweep over the outputs, the upload layout -- is
+// compose_batch.hpp; nothing goes to the device here: the tables travel with each bn_compute_composite)
+int bn_expr_compile_tower_batch(bn_ctx *ctx, const bn_expr *const *exprs, uint32_t n_exprs, const uint32_t *job_desc, const uint64_t *out_offsets, uint32_t n_jobs,
+                                bn_expr **out)
+{
+	BN_REQUIRE(ctx && out && exprs && job_desc && out_offsets, "null argument");
+	BN_ENTER(ctx);
+	BN_REQUIRE(n_jobs >= 1 && n_jobs <= BN_COMPOSE_BATCH_MAX_JOBS, "tower batch: the number of jobs is 0 or above BN_COMPOSE_BATCH_MAX_JOBS");
+	std::vector<bn_compose_job> jobs(n_jobs);
+	for (uint32_t j = 0; j < n_jobs; j++) {
+		const uint32_t *d = job_desc + (size_t)BN_COMPOSE_JOB_DESC_WORDS * j;
+		jobs[j] = bn_compose_job{d[0], d[1], d[2], d[3], out_offsets[j]};
+	}
+	std::vector<const bn::ct_program *> progs(n_exprs, nullptr);
+	for (uint32_t i = 0; i < n_exprs; i++) {
+		BN_REQUIRE(exprs[i], "null argument");
+		BN_REQUIRE(exprs[i]->tower != nullptr, "tower batch: a member is not a tower expression");
+		BN_REQUIRE(exprs[i]->device == ctx->device, "tower batch: a member was compiled for another device");
+		progs[i] = exprs[i]->tower.get();
+	}
+	std::unique_ptr<bn::compose_batch_plan> plan(new bn::compose_batch_plan());
+	const char *why = bn::cb_plan(progs.data(), n_exprs, jobs.data(), n_jobs, *plan);
+	if (why) return bn::fail(BN_ERR_INPUT_VALIDATION, std::string("input validation: tower batch: ") + why);
+	bn_expr *e = new bn_expr();
+	e->device = ctx->device;
+	e->n_vars = plan->n_rows;
+	e->tower_batch = std::move(plan);
+	*out = e;
+	return BN_OK;
+}
+
 } // extern "C"
 namespace bn {
 static std::atomic<uint64_t> g_expr_epoch{1};

@@ -286,9 +286,55 @@ static int compute_composite_tower(bn_ctx *ctx, const void *const *d_rows, uint3
 	ctx->cc_tower[L == 0 ? BN_CC_TOWER_BITWISE : BN_CC_TOWER_VALUES] += 1;
 	return BN_OK;
 }
+
+// bn_compute_composite with a batch of bn_expr_compile_tower_batch: d_out is the arena, one upload
+// [job table][ops][constants][input levels][row pointers], ONE launch of k_compose_tower_batch
+static int compute_composite_tower_batch(bn_ctx *ctx, const void *const *d_rows, uint32_t n_rows, uint64_t row_len, void *d_out, uint64_t out_len, const bn_expr *expr)
+{
+	const bn::compose_batch_plan &p = *expr->tower_batch;
+	BN_REQUIRE(d_rows && d_out, "null argument");
+	BN_REQUIRE(ctx->device == expr->device, "the expression was compiled for another device");
+	static_assert(sizeof(uint64_t) == sizeof(const void *), "row pointers are read as addresses");
+	const char *why = bn::cb_check_call(p, (const uint64_t *)d_rows, n_rows, row_len, (uint64_t)(uintptr_t)d_out, out_len);
+	if (why) return bn::fail(BN_ERR_INPUT_VALIDATION, std::string("input validation: tower batch: ") + why);
+	call_upload up(ctx);
+	const auto s_jobs = up.reserve<bn::compose_batch_job>(p.jobs.size());
+	const auto s_ops = up.reserve<bn::ct_op>(p.n_ops);
+	const auto s_consts = up.reserve<f128>(p.n_consts);
+	const auto s_levels = up.reserve<uint32_t>(p.n_levels);
+	const auto s_rows = up.reserve<const void *>(p.n_rows);
+	if (const int rc = up.alloc()) return rc;
+	std::copy(p.jobs.begin(), p.jobs.end(), up.host(s_jobs));
+	bn::cb_fill(p, up.host(s_ops), up.host(s_consts), up.host(s_levels));
+	std::copy(d_rows, d_rows + p.n_rows, up.host(s_rows));
+	BN_HIP(up.send());
+	bn::compose_batch_args a{};
+	a.jobs = up.dev(s_jobs);
+	a.ops = up.dev(s_ops);
+	a.consts = up.dev(s_consts);
+	a.in_levels = up.dev(s_levels);
+	a.rows = up.dev(s_rows);
+	a.out = d_out;
+	a.n_jobs = (uint32_t)p.jobs.size();
+	BN_HIP(bn::launch_compose_tower_batch(ctx->stream, a, p.total_units, p.lds_bytes));
+	BN_HIP(hipStreamSynchronize(ctx->stream)); // (the tables are pageable host memory that goes out of scope)
+	ctx->cc_batch[BN_CCB_CALLS] += 1;
+	ctx->cc_batch[BN_CCB_LAUNCHES] += 1;
+	ctx->cc_batch[BN_CCB_JOBS] += p.jobs.size();
+	ctx->cc_batch[BN_CCB_PROGRAMS] += p.programs.size();
+	return BN_OK;
+}
 } // namespace bnabi
 
 extern "C" {
+
+int bn_compute_composite_batch_counters(bn_ctx *ctx, uint64_t *counters)
+{
+	BN_REQUIRE(ctx && counters, "null argument");
+	BN_ENTER(ctx);
+	for (int i = 0; i < BN_CCB_N; i++) counters[i] = ctx->cc_batch[i];
+	return BN_OK;
+}
 
 int bn_compute_composite_counters(bn_ctx *ctx, uint64_t *counters)
 {
@@ -305,6 +351,7 @@ int bn_compute_composite(bn_ctx *ctx, const void *const *d_rows, uint32_t n_rows
 	BN_REQUIRE(ctx && expr, "null argument");
 	BN_ENTER(ctx);
 	BN_FLUSH(ctx);
+	if (expr->is_tower_batch()) return compute_composite_tower_batch(ctx, d_rows, n_rows, row_len, d_out, out_len, expr);
 	if (expr->is_tower()) return compute_composite_tower(ctx, d_rows, n_rows, row_len, d_out, out_len, expr);
 	BN_REQUIRE(row_len == out_len, "inputs and output must be the same length");
 	BN_REQUIRE(expr->n_vars == n_rows || (expr->n_vars <= n_rows), "composition not match with input");

@@ -40,6 +40,12 @@ struct ct_program {
 	uint32_t result = 0;  // operand that holds the value of the expression
 };
 
+// A workgroup of the kernel takes kComposeUnitElems contiguous output elements, a thread `compose_tower_per_thread` of them at a time:
+// the LDS of a slot is 16 B x 256 threads per element, so up to 4, 8 or 16 live slots fit 64 KiB at 4, 2 or 1 elements per thread.
+constexpr uint32_t kComposeUnitElems = 1024;
+BN_HD inline uint32_t compose_tower_per_thread(uint32_t n_slots) { return n_slots <= 4 ? 4 : n_slots <= 8 ? 2 : 1; }
+BN_HD inline uint32_t compose_tower_lds_bytes(uint32_t n_slots) { return (n_slots ? n_slots : 1) * compose_tower_per_thread(n_slots) * 16 * 256; }
+
 // the smallest l with c < 2^(2^l)
 inline uint32_t ct_const_level(uint64_t lo, uint64_t hi)
 {

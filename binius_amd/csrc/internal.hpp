@@ -14,6 +14,7 @@
 #include "../../include/binius_amd.h"
 #include "gf128.hpp"
 #include "compose_tower.hpp"
+#include "compose_batch.hpp"
 #include "group_plan.hpp"
 
 struct bn_expr {
@@ -36,7 +37,11 @@ struct bn_expr {
 	// (is_tower: every other consumer rejects it); d_tower is its device copy -- ops, constants, input levels -- made on first use
 	std::unique_ptr<bn::ct_program> tower;
 	mutable void *d_tower = nullptr;
-	bool is_tower() const { return tower != nullptr; }
+	// bn_expr_compile_tower_batch: the plan of a batch of such programs (compose_batch.hpp); no device memory, its tables travel with
+	// each call.  Rejected wherever a tower expression is.
+	std::unique_ptr<bn::compose_batch_plan> tower_batch;
+	bool is_tower_batch() const { return tower_batch != nullptr; }
+	bool is_tower() const { return tower != nullptr || tower_batch != nullptr; }
 };
 
 namespace bn {
@@ -98,6 +103,7 @@ struct bn_ctx {
 	uint64_t dv_calls = 0, dv_launches = 0, dv_jobs = 0; // bn_derive_columns_batch (bn_derive_counters)
 	uint64_t gn_calls = 0, gn_launches = 0, gn_jobs = 0; // bn_generate_columns_batch (bn_generate_counters)
 	uint64_t cc_tower[BN_CC_N] = {}; // bn_compute_composite calls with a tower-typed expression (bn_compute_composite_counters)
+	uint64_t cc_batch[BN_CCB_N] = {}; // ... with a batch of them (bn_compute_composite_batch_counters)
 	bn::f128 *h_me_rets = nullptr, *d_me_rets = nullptr; // pinned: the results of a bn_mle_evaluate_batch call, BN_ME_MAX_JOBS values (the sequence word stays in h_mail[64])
 	unsigned *d_ticket = nullptr;      // device-scope ticket counter for the fused finalize
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1022,7 +1028,6 @@ hipError_t launch_derive_columns(hipStream_t s, const derive_job *d_jobs, uint32
 
 // ---- kernels_compose_tower.hip: bn_compute_composite with a tower-typed expression.  A workgroup takes kComposeUnitElems contiguous
 // output elements; ops / consts / in_levels are the device copy of a ct_program (compose_tower.hpp), rows the call's input columns.
-constexpr uint32_t kComposeUnitElems = 1024;
 struct compose_tower_args {
 	const void *const *rows;
 	const void *ops;    // ct_op[n_ops]
@@ -1035,8 +1040,20 @@ struct compose_tower_args {
 	uint64_t out_elems;
 	void *out;
 };
-uint32_t compose_tower_per_thread(uint32_t n_slots); // output elements a thread holds at a time
 hipError_t launch_compose_tower(hipStream_t s, const compose_tower_args &a, uint32_t n_slots);
+// A batch (compose_batch.hpp): one workgroup per unit of the job table, the sections of the call's upload; a job's row v is
+// rows[first_row + v], its output starts at out + 16 * out_offset.
+struct compose_batch_args {
+	const compose_batch_job *jobs;
+	const void *ops;    // ct_op[]: the programs one after the other
+	const void *consts; // f128[]
+	const uint32_t *in_levels;
+	const void *const *rows;
+	void *out; // the arena
+	uint32_t n_jobs;
+	uint32_t reserved;
+};
+hipError_t launch_compose_tower_batch(hipStream_t s, const compose_batch_args &a, uint32_t total_units, uint32_t lds_bytes);
 
 // ---- kernels_generate.hip: the columns of a constraint system that are determined by a few integers, one field element or a 0/1
 // projection of a column on the device (Projected at a hypercube vertex: math/src/multilinear_extension.rs:193-237; Constant, StepDown,

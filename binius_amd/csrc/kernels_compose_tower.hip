@@ -12,8 +12,13 @@
 // expression's live count: Q = 4, 2 or 1 elements per thread for up to 4, 8 or 16 slots (64 KiB at most).  Indices of elements past
 // the end are clamped to the last element and only the store is predicated.  Every loop bound comes from the program or the levels,
 // never from the data; 64-bit element offsets throughout.
+//
+// k_compose_tower_batch serves a TABLE of such jobs in one launch (bn_expr_compile_tower_batch, compose_batch.hpp): the grid is the
+// jobs' units one after the other, a workgroup finds its job by bisection (batch.hpp) and runs the same chunk loop on the job's
+// program, rows and output range.
 #include <hip/hip_runtime.h>
 
+#include "batch.hpp"
 #include "compose_tower.hpp"
 #include "internal.hpp"
 
@@ -82,20 +87,20 @@ struct ct_frame {
 	}
 };
 
+// One unit -- kComposeUnitElems output elements from `unit_first` on -- of the program `ops[0 .. n_ops)` at Q elements per thread: the
+// chunk loop of both kernels.  `len` is the column's (the job's) element count: indices past it are clamped for the loads, and only
+// the store is predicated.
 template <uint32_t Q>
-__global__ __launch_bounds__(256) void k_compose_tower(compose_tower_args A)
+__device__ __forceinline__ void ct_run_unit(uint32_t *lds, const void *const *rows, const f128 *consts, const uint32_t *in_levels, const ct_op *ops, uint32_t n_ops,
+                                            uint32_t result, uint32_t L, uint64_t len, void *out, uint64_t unit_first)
 {
-	extern __shared__ __attribute__((aligned(16))) uint32_t ct_lds[];
 	ct_frame<Q> F;
-	F.lds = ct_lds;
+	F.lds = lds;
 	F.tid = threadIdx.x;
-	F.rows = A.rows;
-	F.consts = (const f128 *)A.consts;
-	F.in_levels = A.in_levels;
-	F.L = A.out_level;
-	const ct_op *ops = (const ct_op *)A.ops;
-	const uint64_t len = A.out_elems;
-	const uint64_t unit_first = (uint64_t)blockIdx.x * kComposeUnitElems;
+	F.rows = rows;
+	F.consts = consts;
+	F.in_levels = in_levels;
+	F.L = L;
 	constexpr uint32_t kChunk = 256 * Q;
 #pragma unroll 1
 	for (uint32_t c = 0; c < kComposeUnitElems / kChunk; c++) {
@@ -108,7 +113,7 @@ __global__ __launch_bounds__(256) void k_compose_tower(compose_tower_args A)
 			F.at[q] = j[q] < len ? j[q] : len - 1;
 		}
 #pragma unroll 1
-		for (uint32_t i = 0; i < A.n_ops; i++) {
+		for (uint32_t i = 0; i < n_ops; i++) {
 			const ct_op op = ops[i];
 			f128 a[Q], b[Q];
 			F.fetch(op.a, a);
@@ -127,14 +132,44 @@ __global__ __launch_bounds__(256) void k_compose_tower(compose_tower_args A)
 			F.put(op.dst, a);
 		}
 		f128 r[Q];
-		F.fetch(A.result, r);
+		F.fetch(result, r);
 #pragma unroll
 		for (uint32_t q = 0; q < Q; q++)
-			if (j[q] < len) ct_gstore(A.out, j[q], r[q]);
+			if (j[q] < len) ct_gstore(out, j[q], r[q]);
 	}
 }
 
-uint32_t compose_tower_per_thread(uint32_t n_slots) { return n_slots <= 4 ? 4 : n_slots <= 8 ? 2 : 1; }
+template <uint32_t Q>
+__global__ __launch_bounds__(256) void k_compose_tower(compose_tower_args A)
+{
+	extern __shared__ __attribute__((aligned(16))) uint32_t ct_lds[];
+	ct_run_unit<Q>(ct_lds, A.rows, (const f128 *)A.consts, A.in_levels, (const ct_op *)A.ops, A.n_ops, A.result, A.out_level, A.out_elems, A.out,
+	               (uint64_t)blockIdx.x * kComposeUnitElems);
+}
+
+// A batch (compose_batch.hpp): workgroup u serves unit u - start of the job that owns it.  The job's fields are the same in every lane
+// and go to scalar registers; the branch on its class is workgroup-uniform.  The LDS of the launch is the largest job's: a job of a
+// smaller class indexes [slot][q][word][thread] with its own Q inside it.
+__global__ __launch_bounds__(256) void k_compose_tower_batch(compose_batch_args A)
+{
+	extern __shared__ __attribute__((aligned(16))) uint32_t ct_lds[];
+	const uint32_t unit = blockIdx.x;
+	const compose_batch_job *job = A.jobs + uni32(find_job(A.jobs, A.n_jobs, unit));
+	const uint32_t q = uni32(job->q), n_ops = uni32(job->n_ops), result = uni32(job->result), L = uni32(job->out_level);
+	const uint64_t len = uni64(job->out_elems);
+	const uint64_t unit_first = (uint64_t)(unit - uni32(job->start)) * kComposeUnitElems;
+	const ct_op *ops = (const ct_op *)A.ops + uni32(job->ops_off);
+	const f128 *consts = (const f128 *)A.consts + uni32(job->consts_off);
+	const uint32_t *in_levels = A.in_levels + uni32(job->levels_off);
+	const void *const *rows = A.rows + uni32(job->first_row);
+	void *out = (char *)A.out + 16 * uni64(job->out_offset);
+	if (q == 4)
+		ct_run_unit<4>(ct_lds, rows, consts, in_levels, ops, n_ops, result, L, len, out, unit_first);
+	else if (q == 2)
+		ct_run_unit<2>(ct_lds, rows, consts, in_levels, ops, n_ops, result, L, len, out, unit_first);
+	else
+		ct_run_unit<1>(ct_lds, rows, consts, in_levels, ops, n_ops, result, L, len, out, unit_first);
+}
 
 hipError_t launch_compose_tower(hipStream_t s, const compose_tower_args &a, uint32_t n_slots)
 {
@@ -143,13 +178,21 @@ hipError_t launch_compose_tower(hipStream_t s, const compose_tower_args &a, uint
 	const uint64_t units = (a.out_elems + kComposeUnitElems - 1) / kComposeUnitElems;
 	if (units > 0x7fffffffull) return hipErrorInvalidValue;
 	const uint32_t q = compose_tower_per_thread(n_slots);
-	const size_t lds = (size_t)(n_slots ? n_slots : 1) * q * 16 * 256; // <= 64 KiB
+	const size_t lds = compose_tower_lds_bytes(n_slots); // <= 64 KiB
 	if (q == 4)
 		hipLaunchKernelGGL(k_compose_tower<4>, dim3((uint32_t)units), dim3(256), lds, s, a);
 	else if (q == 2)
 		hipLaunchKernelGGL(k_compose_tower<2>, dim3((uint32_t)units), dim3(256), lds, s, a);
 	else
 		hipLaunchKernelGGL(k_compose_tower<1>, dim3((uint32_t)units), dim3(256), lds, s, a);
+	return hipGetLastError();
+}
+
+hipError_t launch_compose_tower_batch(hipStream_t s, const compose_batch_args &a, uint32_t total_units, uint32_t lds_bytes)
+{
+	if (total_units == 0 || a.n_jobs == 0) return hipSuccess;
+	if (total_units > 0x7fffffffu || lds_bytes > (64u << 10)) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(k_compose_tower_batch, dim3(total_units), dim3(256), lds_bytes, s, a);
 	return hipGetLastError();
 }
 

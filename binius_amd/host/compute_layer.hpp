@@ -809,6 +809,22 @@ public:
 		check(bn_expr_compile_tower(ctx_, expr.steps().data(), expr.steps().size(), input_levels.data(), (uint32_t)input_levels.size(), out_level, &h));
 		return ExprEval(h, input_levels.size());
 	}
+	// Extension: a batch of compile_expr_tower expressions (bn_expr_compile_tower_batch) that compute_composite serves in ONE launch: the
+	// rows are the input columns of all jobs, the output the arena the jobs' out_offsets count from.  The members may be freed right after.
+	ExprEval compile_expr_tower_batch(const std::vector<const bn_expr *> &exprs, const std::vector<bn_compose_job> &jobs)
+	{
+		std::vector<uint32_t> desc;
+		std::vector<uint64_t> offsets;
+		for (const bn_compose_job &j : jobs) {
+			desc.insert(desc.end(), {j.expr, j.first_row, j.n_vars, j.reserved});
+			offsets.push_back(j.out_offset);
+		}
+		bn_expr *h = nullptr;
+		check(bn_expr_compile_tower_batch(ctx_, exprs.data(), (uint32_t)exprs.size(), desc.data(), offsets.data(), (uint32_t)jobs.size(), &h));
+		uint32_t n_rows = 0;
+		check(bn_expr_n_vars(h, &n_rows));
+		return ExprEval(h, n_rows);
+	}
 	// execute (layer.rs:65-72): f receives the executor and returns the scalars it wants resolved
 	template <class Fn>
 	std::vector<B128> execute(Fn &&f)

@@ -2131,14 +2131,14 @@ std::vector<WitnessColumn> witness_columns(uint32_t n_columns, const uint32_t *c
 
 int witness_run(bool generate, bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
                 const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
-                uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out, const witness_exprs *ex = nullptr)
+                uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out, const witness_exprs *ex = nullptr, bool batched = false)
 {
 	return guarded([&]() -> int {
 		if (!ctx || (n_columns && (!d_given || !d_columns_out || !tower_levels_out || !n_vars_out)) || (!d_scratch && scratch_elems))
 			throw Error(Error::InputValidation, "null argument");
 		const std::vector<WitnessColumn> cols = witness_columns(n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets, ex ? *ex : witness_exprs{});
 		ComputeLayer hal(ctx);
-		const WitnessOutput out = witness_derive(hal, cols, FSliceMut{d_scratch, (size_t)scratch_elems}, generate, /*compute=*/ex != nullptr);
+		const WitnessOutput out = witness_derive(hal, cols, FSliceMut{d_scratch, (size_t)scratch_elems}, generate, /*compute=*/ex != nullptr, batched);
 		for (uint32_t i = 0; i < n_columns; i++) {
 			d_columns_out[i] = const_cast<void *>(out.columns[i].ptr);
 			tower_levels_out[i] = out.columns[i].tower_level;
@@ -2209,6 +2209,17 @@ int bnh_witness_compute(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_des
 	const witness_exprs ex{steps, n_exprs ? step_off : zero, expr_inputs, n_exprs ? expr_input_off : zero, n_exprs};
 	return witness_run(true, ctx, n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets, d_scratch, scratch_elems, d_columns_out, tower_levels_out,
 	                   n_vars_out, n_waves_out, n_launches_out, &ex);
+}
+
+int bnh_witness_compute_batched(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
+                                const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
+                                uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out, const bn_step *steps, const uint32_t *step_off,
+                                const uint32_t *expr_inputs, const uint32_t *expr_input_off, uint32_t n_exprs)
+{
+	const uint32_t zero[2] = {0, 0};
+	const witness_exprs ex{steps, n_exprs ? step_off : zero, expr_inputs, n_exprs ? expr_input_off : zero, n_exprs};
+	return witness_run(true, ctx, n_columns, col_desc, col_args, d_given, lc_terms, lc_coeffs, n_lc_terms, lc_offsets, d_scratch, scratch_elems, d_columns_out, tower_levels_out,
+	                   n_vars_out, n_waves_out, n_launches_out, &ex, /*batched=*/true);
 }
 
 } // extern "C"

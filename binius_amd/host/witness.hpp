@@ -29,6 +29,8 @@
 //                      becomes the expression sum of coeff * term + offset, left-deep, at the combination's level (pack_fp / pack_b8:
 //                      B1 terms, coefficients in B8 / B32 / B64); a level of 1 or 2 cannot be packed and is InputValidation
 //
+// witness_compute_batched is witness_compute with the expression columns of a wave in ONE bn_compute_composite over a batch
+// (bn_expr_compile_tower_batch): the same columns, the same bytes, one launch per wave that has such columns.
 // witness_derive and witness_build keep rejecting those.  NOT taken by any: Projected at other query values
 // (bn_partial_eval_high_batch / bn_fold_right are the ops for it), general circuit transparents and StructuredFixedSize, TowerBasis,
 // EqIndPartialEval (bn_tensor_expand), ShiftIndPartialEval, DisjointProduct -- the caller derives or uploads those and lists them as
@@ -403,7 +405,74 @@ inline B128 witness_small_expr(const WitnessExpr &e, const WitnessShape &s, cons
 	return out;
 }
 
-inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch, bool generate = false, bool compute = false)
+// The expression columns `composed` of one wave in ONE bn_compute_composite: every distinct (steps, input levels, output level) is
+// compiled once, the batch's arena is the plan's scratch and a job's out_offset its column's place in it; a job's rows are its inputs,
+// one after the other in the call's row list.  The handles live for the call alone.
+inline void witness_compose_wave(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, const std::vector<WitnessShape> &sh, const WitnessOutput &out,
+                                 const std::vector<size_t> &composed, FSliceMut scratch)
+{
+	struct Compiled {
+		WitnessExpr e;
+		std::vector<uint32_t> levels;
+		uint32_t out_level;
+	};
+	auto same_steps = [](const std::vector<bn_step> &x, const std::vector<bn_step> &y) {
+		if (x.size() != y.size()) return false;
+		for (size_t k = 0; k < x.size(); k++)
+			if (x[k].kind != y[k].kind || x[k].a != y[k].a || x[k].b != y[k].b || x[k].cst.lo != y[k].cst.lo || x[k].cst.hi != y[k].cst.hi) return false;
+		return true;
+	};
+	std::vector<Compiled> distinct;
+	std::vector<bn_expr *> handles;
+	std::vector<bn_compose_job> jobs;
+	std::vector<const void *> rows;
+	auto free_all = [&]() {
+		for (bn_expr *h : handles) bn_expr_free(h);
+		handles.clear();
+	};
+	try {
+		for (const size_t i : composed) {
+			Compiled c{witness_expr(cols[i]), {}, sh[i].tower_level};
+			for (const uint32_t v : c.e.inputs) c.levels.push_back(sh[v].tower_level);
+			uint32_t k = 0;
+			while (k < distinct.size() && !(distinct[k].out_level == c.out_level && distinct[k].levels == c.levels && same_steps(distinct[k].e.steps, c.e.steps))) k++;
+			if (k == distinct.size()) {
+				const uint32_t none = 0;
+				bn_expr *h = nullptr;
+				check(bn_expr_compile_tower(hal.raw_ctx(), c.e.steps.data(), c.e.steps.size(), c.levels.empty() ? &none : c.levels.data(), (uint32_t)c.levels.size(), c.out_level, &h));
+				handles.push_back(h);
+				distinct.push_back(c);
+			}
+			bn_compose_job jb{};
+			jb.expr = k;
+			jb.first_row = (uint32_t)rows.size();
+			jb.n_vars = sh[i].n_vars;
+			jb.out_offset = (uint64_t)((const char *)out.columns[i].ptr - (const char *)scratch.ptr) / 16;
+			jobs.push_back(jb);
+			for (const uint32_t v : c.e.inputs) rows.push_back(out.columns[v].ptr);
+		}
+		std::vector<uint32_t> desc;
+		std::vector<uint64_t> offsets;
+		for (const bn_compose_job &j : jobs) {
+			desc.insert(desc.end(), {j.expr, j.first_row, j.n_vars, j.reserved});
+			offsets.push_back(j.out_offset);
+		}
+		bn_expr *batch = nullptr;
+		check(bn_expr_compile_tower_batch(hal.raw_ctx(), handles.data(), (uint32_t)handles.size(), desc.data(), offsets.data(), (uint32_t)jobs.size(), &batch));
+		free_all(); // (the batch holds copies of the programs)
+		const void *no_row = nullptr;
+		const int rc = bn_compute_composite(hal.raw_ctx(), rows.empty() ? &no_row : rows.data(), (uint32_t)rows.size(), scratch.len_, scratch.ptr, scratch.len_, batch);
+		bn_expr_free(batch);
+		check(rc);
+	} catch (...) {
+		free_all();
+		throw;
+	}
+}
+
+// batched: the expression columns of a wave go through witness_compose_wave, one launch, instead of one bn_compute_composite each
+inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch, bool generate = false, bool compute = false,
+                                    bool batched = false)
 {
 	const std::vector<WitnessShape> sh = witness_shapes(cols, generate, compute);
 	if (scratch.len_ < witness_derive_scratch_elems(cols, generate, compute)) throw Error(Error::InputValidation, "scratch holds fewer than witness_derive_scratch_elems elements");
@@ -518,6 +587,11 @@ inline WitnessOutput witness_derive(ComputeLayer &hal, const std::vector<Witness
 			check(bn_generate_columns_batch(hal.raw_ctx(), gen_jobs.data(), (uint32_t)gen_jobs.size()));
 			out.n_launches++;
 		}
+		if (batched && !composed.empty()) {
+			witness_compose_wave(hal, cols, sh, out, composed, scratch);
+			out.n_launches++;
+			composed.clear();
+		}
 		for (const size_t i : composed) { // one bn_compute_composite per expression column
 			const WitnessExpr e = witness_expr(cols[i]);
 			std::vector<uint32_t> levels;
@@ -584,5 +658,10 @@ inline WitnessOutput witness_build(ComputeLayer &hal, const std::vector<WitnessC
 // witness_build with the expression columns taken as well (the header)
 inline size_t witness_compute_scratch_elems(const std::vector<WitnessColumn> &cols) { return witness_derive_scratch_elems(cols, true, true); }
 inline WitnessOutput witness_compute(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch) { return witness_derive(hal, cols, scratch, true, true); }
+// witness_compute with the expression columns of a wave in one launch (bn_expr_compile_tower_batch); witness_compute_scratch_elems serves both
+inline WitnessOutput witness_compute_batched(ComputeLayer &hal, const std::vector<WitnessColumn> &cols, FSliceMut scratch)
+{
+	return witness_derive(hal, cols, scratch, true, true, true);
+}
 
 } // namespace binius_amd

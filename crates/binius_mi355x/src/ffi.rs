@@ -234,6 +234,25 @@ pub const BN_CC_TOWER_BITWISE: usize = 2;
 pub const BN_CC_TOWER_VALUES: usize = 3;
 pub const BN_CC_N: usize = 4;
 
+/// bn_expr_compile_tower_batch: one job of a batch of tower-typed expressions (it crosses the C interface as BN_COMPOSE_JOB_DESC_WORDS
+/// integers of `job_desc` and one of `out_offsets`); bn_compute_composite_batch_counters: what its calls did.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct bn_compose_job {
+	pub expr: u32,
+	pub first_row: u32,
+	pub n_vars: u32,
+	pub reserved: u32,
+	pub out_offset: u64,
+}
+pub const BN_COMPOSE_BATCH_MAX_JOBS: usize = 4096;
+pub const BN_COMPOSE_JOB_DESC_WORDS: usize = 4;
+pub const BN_CCB_CALLS: usize = 0;
+pub const BN_CCB_LAUNCHES: usize = 1;
+pub const BN_CCB_JOBS: usize = 2;
+pub const BN_CCB_PROGRAMS: usize = 3;
+pub const BN_CCB_N: usize = 4;
+
 /// One generated column of bn_generate_columns_batch (a projection at a hypercube vertex, a transparent that its parameters determine, or
 /// the incrementing column).
 #[repr(C)]
@@ -338,6 +357,16 @@ unsafe extern "C" {
 		out: *mut *mut bn_expr,
 	) -> c_int;
 	pub fn bn_compute_composite_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
+	pub fn bn_expr_compile_tower_batch(
+		ctx: *mut bn_ctx,
+		exprs: *const *const bn_expr,
+		n_exprs: u32,
+		job_desc: *const u32,
+		out_offsets: *const u64,
+		n_jobs: u32,
+		out: *mut *mut bn_expr,
+	) -> c_int;
+	pub fn bn_compute_composite_batch_counters(ctx: *mut bn_ctx, counters: *mut u64) -> c_int;
 
 	pub fn bn_extrapolate_line(ctx: *mut bn_ctx, d_evals_0: *mut c_void, n0: u64, d_evals_1: *const c_void, n1: u64, z: *const bn_f128) -> c_int;
 	pub fn bn_extrapolate_line_batch(

@@ -126,6 +126,20 @@ impl Mi355xLayer {
 		Ok(Mi355xExpr(handle))
 	}
 
+	/// Extension (not a trait method): a batch of `compile_expr_tower` expressions -- the expression columns of one wave of a witness
+	/// plan -- that `compute_composite` serves in ONE launch: the rows are the input columns of all jobs, the output the arena that the
+	/// jobs' `out_offset`s count from (bn_expr_compile_tower_batch, include/binius_amd.h).  The batch copies the members' programs.
+	pub fn compile_expr_tower_batch(&self, exprs: &[&Mi355xExpr], jobs: &[ffi::bn_compose_job]) -> Result<Mi355xExpr, Error> {
+		let handles: Vec<*const ffi::bn_expr> = exprs.iter().map(|e| e.0 as *const ffi::bn_expr).collect();
+		let desc: Vec<u32> = jobs.iter().flat_map(|j| [j.expr, j.first_row, j.n_vars, j.reserved]).collect();
+		let offsets: Vec<u64> = jobs.iter().map(|j| j.out_offset).collect();
+		let mut handle = ptr::null_mut();
+		check(unsafe {
+			ffi::bn_expr_compile_tower_batch(self.ctx, handles.as_ptr(), handles.len() as u32, desc.as_ptr(), offsets.as_ptr(), jobs.len() as u32, &mut handle)
+		})?;
+		Ok(Mi355xExpr(handle))
+	}
+
 	/// Base address and size (in elements) of the context's arena.
 	pub(crate) fn arena(&self) -> (*mut u8, usize) {
 		let mut base = ptr::null_mut();

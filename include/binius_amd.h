@@ -172,6 +172,42 @@ int bn_compute_composite(bn_ctx *ctx, const void *const *d_rows, uint32_t n_rows
  * launches they made, how many of them ran at level 0 (bitwise) and at levels 3 .. 7 (per value).  A rejected call counts nowhere. */
 enum { BN_CC_TOWER_CALLS = 0, BN_CC_TOWER_LAUNCHES = 1, BN_CC_TOWER_BITWISE = 2, BN_CC_TOWER_VALUES = 3, BN_CC_N = 4 };
 int bn_compute_composite_counters(bn_ctx *ctx, uint64_t *counters /*[BN_CC_N]*/);
+/* Extension (not a trait method): a BATCH of tower-typed expressions -- the expression columns of one wave of a witness plan in ONE
+ * launch, as bn_derive_columns_batch, bn_generate_columns_batch and bn_partial_eval_high_lincomb_batch serve theirs.  exprs[] are handles of
+ * bn_expr_compile_tower; the batch COPIES their compiled programs (duplicates are dropped), so the members may be freed right after.  The
+ * result is a bn_expr of a third kind that owns no device memory: its tables travel with each call.  bn_expr_free frees it; bn_expr_n_vars
+ * answers the number of rows a call must pass, the maximum over jobs of first_row + the job expression's input count; bn_kernel_launch
+ * and bn_hal_round_evals reject it as they reject a tower-typed expression.
+ * bn_compute_composite with such a batch: d_rows[0 .. n_rows) are the input columns of ALL jobs -- job j's input v is
+ * d_rows[first_row_j + v], 2^n_vars_j values packed at that input's level (below one element: the low bits of one element); the
+ * batch's row count is <= n_rows.  d_out is the base of an output ARENA of out_len 16-byte elements and row_len = out_len; job j writes
+ * exactly 2^(n_vars_j + L_j - 7) elements at d_out + 16 * out_offset_j, inside the arena.  Rows may lie inside the arena (a wave's inputs are
+ * an earlier wave's outputs in the same scratch), but no job's output overlaps any row of any job, each row at its own packed size.
+ * Bit-exact, overwritten, inputs only read, pointers 16-byte aligned.  One upload and ONE launch per call (k_compose_tower_batch: a
+ * workgroup finds its job by bisection over the job table; the dynamic LDS is the maximum over the jobs).
+ * BN_ERR_INPUT_VALIDATION at compile time with nothing allocated: null arguments, n_jobs = 0 or above BN_COMPOSE_BATCH_MAX_JOBS, expr >=
+ * n_exprs, a member that is no tower expression or belongs to another device, reserved != 0, n_vars > BN_PE_MAX_VARS, n_vars + out_level
+ * < 7, two jobs' output ranges overlapping, units (1024 output elements each, rounded up per job) that leave 31 bits.  At the call, with
+ * nothing launched or written and no counter moved: every violation of the paragraph above. */
+typedef struct {
+	uint32_t expr;       /* index into exprs[]: several jobs may share one */
+	uint32_t first_row;  /* the job's input v is the call's d_rows[first_row + v] */
+	uint32_t n_vars;     /* the job computes 2^n_vars values */
+	uint32_t reserved;   /* 0 */
+	uint64_t out_offset; /* where the job's output starts, in 16-byte elements from the call's d_out */
+} bn_compose_job;
+#define BN_COMPOSE_BATCH_MAX_JOBS 4096
+/* The job table crosses this interface as two arrays of integers, as the column tables of bnh_witness_* do: job j is
+ * job_desc[4 j .. 4 j + 4) = { expr, first_row, n_vars, reserved } and out_offsets[j] -- the fields of bn_compose_job, which is what the
+ * planner (csrc/compose_batch.hpp) and the C++ and Rust wrappers take. */
+#define BN_COMPOSE_JOB_DESC_WORDS 4
+int bn_expr_compile_tower_batch(bn_ctx *ctx, const bn_expr *const *exprs, uint32_t n_exprs, const uint32_t *job_desc, const uint64_t *out_offsets,
+                                uint32_t n_jobs, bn_expr **out);
+/* Read-only, per context: accepted bn_compute_composite calls with a batch, the launches they made, the jobs they served and the
+ * programs they uploaded (distinct ones, after dropping duplicates).  A batch call moves none of BN_CC_TOWER_*; a rejected call counts
+ * nowhere. */
+enum { BN_CCB_CALLS = 0, BN_CCB_LAUNCHES = 1, BN_CCB_JOBS = 2, BN_CCB_PROGRAMS = 3, BN_CCB_N = 4 };
+int bn_compute_composite_batch_counters(bn_ctx *ctx, uint64_t *counters /*[BN_CCB_N]*/);
 /* pairwise_product_reduce (layer.rs:505) */
 int bn_pairwise_product_reduce(bn_ctx *ctx, const void *d_in, uint64_t n, void *const *d_round_outs,
                                const uint64_t *round_lens, uint32_t n_rounds);

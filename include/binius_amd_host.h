@@ -639,7 +639,7 @@ int bnh_witness_build(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc,
  *                     offset, left-deep, at the reference's level: the maximum of the terms' levels and the minimal levels of coefficients
  *                     and offset.  A level of 1 or 2 cannot be packed: BN_ERR_INPUT_VALIDATION.
  * Such a column's wave is one more than its deepest input's; each is one bn_compute_composite call of its wave, counted in
- * *n_launches_out (batching several into one launch is left to a later change: the counter shows the difference).  Below one 16-byte
+ * *n_launches_out (bnh_witness_compute_batched below serves a wave in one launch: the counter shows the difference).  Below one 16-byte
  * element it is host work like the other kinds: its inputs' single elements read back, evaluated value by value with bn_scalar_mul, one
  * element written.  bnh_witness_compute_scratch_elems is exact -- every derived, generated or computed column at its packed size, plus the
  * lincomb op's one element -- and 0 for a plan that bnh_witness_compute would reject.  bnh_witness_derive and bnh_witness_build keep
@@ -652,6 +652,15 @@ int bnh_witness_compute(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_des
                         const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
                         uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out, const bn_step *steps, const uint32_t *step_off,
                         const uint32_t *expr_inputs, const uint32_t *expr_input_off, uint32_t n_exprs);
+/* bnh_witness_compute with the expression columns of a wave in ONE launch: per wave every distinct (steps, input levels, output level) is
+ * compiled once, one batch is built (bn_expr_compile_tower_batch, include/binius_amd.h) whose arena is the plan's scratch and whose
+ * out_offset is each column's place in it, one bn_compute_composite serves it, the handles are freed.  *n_launches_out counts one per
+ * wave that has expression columns.  Same parameters, same columns, same bytes, same rejections; bnh_witness_compute_scratch_elems serves
+ * both.  Columns below one element stay host work. */
+int bnh_witness_compute_batched(bn_ctx *ctx, uint32_t n_columns, const uint32_t *col_desc, const uint64_t *col_args, const void *const *d_given, const uint32_t *lc_terms,
+                                const bn_f128 *lc_coeffs, uint32_t n_lc_terms, const bn_f128 *lc_offsets, void *d_scratch, uint64_t scratch_elems, void **d_columns_out,
+                                uint32_t *tower_levels_out, uint32_t *n_vars_out, uint32_t *n_waves_out, uint32_t *n_launches_out, const bn_step *steps, const uint32_t *step_off,
+                                const uint32_t *expr_inputs, const uint32_t *expr_input_off, uint32_t n_exprs);
 
 /* An array-backed transcript, for C callers, benchmarks and tests: it serves samples[n_samples] to `sample` and
  * bit_samples[n_bit_samples] (masked to `bits`) to `sample_bits`, in order, returns non-zero when they run out, and records every

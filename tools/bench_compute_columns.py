@@ -9,6 +9,10 @@ The shapes are what a table of 2^20 rows shaped like m3's mul gadget computes be
   product    (c) a B32 x B32 product column of 2^20 values
   plan       (d) the plan of the table (WitnessCompute): 65 given B1 columns, 32 composites a_k + s (a_k + b_k), pack_fp of them into
              B32, one shifted column of a composite: 33 bn_compute_composite calls and one bn_derive_columns_batch
+  plan_batched (e) plan (d) through WitnessComputeBatched: the expression columns of a wave in one launch (bn_expr_compile_tower_batch),
+             3 launches.  (d) and (e) run ALTERNATELY in the same process -- d, e, the copy, d, e -- and (e)'s record carries (d)'s
+             figures of that session, the call of the wave-1 batch alone (32 composites of 2^20 bits: compile, batch, call, frees as
+             the plan does them, and the call by itself on a resident batch) and a copy of the bytes that wave reads plus writes
 
 and the comparisons, per shape
 
@@ -21,7 +25,9 @@ and the comparisons, per shape
 Every figure: 3 warm-up runs, then the median of the timed runs (host clock between two synchronisations), with min, max and the
 interquartile range.  One JSON line per record.
 
-  python tools/bench_compute_columns.py [--runs 20] [--out profiles/r28/compute_columns.jsonl] [--only select]"""
+  python tools/bench_compute_columns.py [--runs 20] [--out profiles/r28/compute_columns.jsonl] [--only select]
+  python tools/bench_compute_columns.py --only plan_batched --out profiles/r29/compute_columns.jsonl     (d) and (e), alternately
+  python tools/bench_compute_columns.py --only wave1 --runs 5      the wave-1 batch call alone: for a counter run of its kernel"""
 import argparse
 import json
 import os
@@ -134,16 +140,48 @@ def host_plan(np, ins):
     return sel, packed, (w << np.uint32(3))  # (logical left by 3 inside blocks of 2^5 values)
 
 
+def wave1_batch(hal, given, out):
+    """(the batch of plan (d)'s wave 1 on a resident handle, its rows): 32 composites a_k + s (a_k + b_k) of 2^20 bits into `out`"""
+    e = hal.expr_compile_tower(SELECT, [0, 0, 0], 0)
+    n = elems(0, ROWS)
+    batch = hal.expr_compile_tower_batch([e], [(0, 3 * k, ROWS, k * n) for k in range(32)])
+    rows = [r for k in range(32) for r in (given[k], given[32 + k], given[64])]
+    return batch, rows
+
+
+def wave1_with_a_wide_job(hal, given, out):
+    """the same 32 jobs plus ONE 16-slot job of one output element (15 products of bit pairs, all before the first sum): it sets the
+    launch's LDS to 64 KiB for every workgroup -- what that costs the two-slot jobs"""
+    k = 15
+    wide = [("var", i) for i in range(2 * k)] + [("mul", 2 * i, 2 * i + 1) for i in range(k)] + [("add", 2 * k, 2 * k + 1)]
+    for i in range(2, k):
+        wide.append(("add", len(wide) - 1, 2 * k + i))
+    members = [hal.expr_compile_tower(SELECT, [0, 0, 0], 0), hal.expr_compile_tower(wide, [0] * (2 * k), 0)]
+    n = elems(0, ROWS)
+    batch = hal.expr_compile_tower_batch(members, [(0, 3 * k2, ROWS, k2 * n) for k2 in range(32)] + [(1, 96, 7, 32 * n)])
+    rows = [r for k2 in range(32) for r in (given[k2], given[32 + k2], given[64])] + given[: 2 * k]
+    return batch, rows
+
+
+def wave1_as_the_plan_does_it(hal, given, out):
+    """compile, batch, call, frees: what one wave of the batched plan costs"""
+    batch, rows = wave1_batch(hal, given, out)
+    hal.compute_composite_tower_batch(rows, out, batch)
+    for e in hal._exprs[-2:]:
+        e.free()
+    del hal._exprs[-2:]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", default=None, help="one shape (select, pack_fp, product, plan): for a counter run of that kernel alone")
+    ap.add_argument("--only", default=None, help="one shape (select, pack_fp, product, plan, plan_batched, wave1): for a counter run of that kernel alone")
     args = ap.parse_args()
     import numpy as np
 
     import binius_amd
-    from binius_amd._host import WitnessCompute
+    from binius_amd._host import WitnessCompute, WitnessComputeBatched
 
     lines = []
 
@@ -181,6 +219,55 @@ def main():
             assert out_host.shape[0] == written
             rec = {"shape": "plan", "columns": len(cols), "waves": plan.n_waves, "launches_per_run": plan.n_launches}
             emit(finish(hal, alloc, rec, timings, read, written, fill_ms, out_host, args.runs))
+        if want("plan_batched") or args.only == "wave1":
+            cols, given = plan_columns(hal, alloc)
+            n_scratch = WitnessCompute.scratch_elems(cols)
+            plan_d, plan_e = WitnessCompute(hal, cols, alloc.alloc(n_scratch)), WitnessComputeBatched(hal, cols, alloc.alloc(n_scratch))
+            wave_out = alloc.alloc(32 * elems(0, ROWS) + 1)
+            batch, rows = wave1_batch(hal, given, wave_out)
+            wave_call = lambda: hal.compute_composite_tower_batch(rows, wave_out, batch)  # noqa: E731
+            if args.only == "wave1":
+                t = timed(hal, wave_call, args.runs)
+                emit({"shape": "wave1", "jobs": 32, "call": stats(t)})
+            else:
+                read = 32 * 3 * elems(0, ROWS) + 32 * elems(0, ROWS) + elems(0, ROWS)
+                written = 32 * elems(0, ROWS) + elems(5, ROWS) + elems(0, ROWS)
+                wave_both = (32 * 3 * elems(0, ROWS) + 32 * elems(0, ROWS)) // 2
+                d1 = timed(hal, plan_d.run, args.runs)
+                e1 = timed(hal, plan_e.run, args.runs)
+                both = (read + written) // 2
+                copy = timed(hal, lambda: hal.copy_d2d(src.slice(0, both), dst.slice(0, both)), args.runs)
+                d2 = timed(hal, plan_d.run, args.runs)
+                e2 = timed(hal, plan_e.run, args.runs)
+                c0 = hal.compute_composite_batch_counters()
+                w_call = timed(hal, wave_call, args.runs)
+                c1 = hal.compute_composite_batch_counters()
+                w_copy = timed(hal, lambda: hal.copy_d2d(src.slice(0, wave_both), dst.slice(0, wave_both)), args.runs)
+                w_plan = timed(hal, lambda: wave1_as_the_plan_does_it(hal, given, wave_out), args.runs)
+                wide_batch, wide_rows = wave1_with_a_wide_job(hal, given, wave_out)
+                w_wide = timed(hal, lambda: hal.compute_composite_tower_batch(wide_rows, wave_out, wide_batch), args.runs)
+                w_call2 = timed(hal, wave_call, args.runs)
+                got_d, got_e = plan_d.run(), plan_e.run()
+                host_ins = [np.ascontiguousarray(hal.copy_d2h(d)) for d in given]
+                sel, packed, shifted = host_plan(np, host_ins)
+                for name, got in (("per column", got_d), ("batched", got_e)):
+                    assert np.array_equal(hal.copy_d2h(got[97][0]).reshape(-1), packed.view(np.uint64)), "%s plan: the host path and the device disagree (pack_fp)" % name
+                    assert np.array_equal(hal.copy_d2h(got[98][0]).reshape(-1), shifted.view(np.uint64)), "%s plan: the host path and the device disagree (shifted)" % name
+                    for k in range(32):
+                        assert np.array_equal(hal.copy_d2h(got[65 + k][0]).reshape(-1), sel[k]), "%s plan: the host path and the device disagree (composite %d)" % (name, k)
+                n = elems(0, ROWS)
+                for k in range(32):
+                    assert np.array_equal(hal.copy_d2h(wave_out.slice(k * n, (k + 1) * n)).reshape(-1), sel[k]), "the wave-1 batch and the host path disagree (%d)" % k
+                d, e, f = stats(d1 + d2), stats(e1 + e2), stats(copy)
+                wc, wf = stats(w_call), stats(w_copy)
+                emit({"shape": "plan_batched", "columns": len(cols), "waves": plan_e.n_waves, "launches_per_run": plan_e.n_launches, "per_column_launches_per_run": plan_d.n_launches,
+                      "bytes_read": 16 * read, "bytes_written": 16 * written, "compute": e, "compute_first_window": stats(e1), "compute_second_window": stats(e2),
+                      "per_column_plan_same_session": d, "per_column_first_window": stats(d1), "per_column_second_window": stats(d2),
+                      "per_column_over_batched": round(d["median_ms"] / e["median_ms"], 2), "batched_median_below_per_column_min": e["median_ms"] < d["min_ms"],
+                      "copy_read_plus_written_bytes": f, "compute_over_copy": round(e["median_ms"] / f["median_ms"], 3),
+                      "wave1_bytes": 32 * wave_both, "wave1_call": wc, "wave1_launches_per_call": (c1["launches"] - c0["launches"]) // (c1["calls"] - c0["calls"]),
+                      "wave1_copy_read_plus_written_bytes": wf, "wave1_call_over_copy": round(wc["median_ms"] / wf["median_ms"], 3),
+                      "wave1_compile_batch_call_free": stats(w_plan), "wave1_call_again": stats(w_call2), "wave1_call_with_one_16_slot_job_64KiB_lds": stats(w_wide)})
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
