@@ -27,6 +27,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -128,6 +129,24 @@ inline double elapsed_ms(std::chrono::steady_clock::time_point t0, std::chrono::
 {
 	return std::chrono::duration<double, std::milli>(t1 - t0).count();
 }
+// BNH_PROF=1 around one prove: the counters start from zero; report() says where its wall time went (us): inside the C ABI by
+// kind of call, and the rest
+struct AbiProfSpan {
+	std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+	AbiProfSpan()
+	{
+		if (AbiProf::on()) AbiProf::get() = AbiProf{};
+	}
+	void report(unsigned n_vars) const
+	{
+		if (!AbiProf::on()) return;
+		const AbiProf &p = AbiProf::get();
+		const double tot = 1e3 * elapsed_ms(t0);
+		fprintf(stderr, "[bnh prof] n_vars %u: total %.2f us; kernel_launch %.2f (%llu calls), extrapolate_line %.2f (%llu), copies %.2f (%llu); outside the ABI %.2f\n",
+		        n_vars, tot, p.ns[0] / 1e3, (unsigned long long)p.calls[0], p.ns[1] / 1e3, (unsigned long long)p.calls[1], p.ns[2] / 1e3,
+		        (unsigned long long)p.calls[2], tot - (p.ns[0] + p.ns[1] + p.ns[2]) / 1e3);
+	}
+};
 template <class F>
 inline int abi_timed(AbiProf::Kind k, F &&f)
 {

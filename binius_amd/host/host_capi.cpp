@@ -3,7 +3,7 @@
 // The compiled form of the C++ host mirror: a complete prover run behind one C call, so a benchmark or a test times the prover
 // loop the way a compiled (Rust) host would drive the HAL -- for the BivariateSumcheckProver per round one accumulate_kernels, two
 // scalar multiplications, one extrapolate_line per multilinear -- without interpreter overhead between HAL calls.  One entry point
-// per mirror (sumcheck.hpp, batch_prover.hpp, eq_ind.hpp, fri.hpp, piop.hpp, gkr_gpa.hpp, gkr_exp.hpp, flush.hpp, evalcheck.hpp,
+// per mirror (sumcheck.hpp, sharded_sumcheck.hpp, batch_prover.hpp, eq_ind.hpp, fri.hpp, piop.hpp, gkr_gpa.hpp, gkr_exp.hpp, flush.hpp, evalcheck.hpp,
 // zerocheck.hpp, ring_switch.hpp): it converts the C arrays (from_raw / to_raw), runs inside guarded(), which turns what is thrown into the return
 // code and bnh_last_error().  Links only against the C ABI of include/binius_amd.h.
 #include <dlfcn.h>
@@ -32,6 +32,7 @@
 #include "gkr_gpa.hpp"
 #include "piop.hpp"
 #include "ring_switch.hpp"
+#include "sharded_sumcheck.hpp"
 #include "sumcheck.hpp"
 #include "transcript.hpp"
 #include "witness.hpp"
@@ -125,6 +126,60 @@ int guarded(F &&body)
 		g_err = e.what();
 		return BN_ERR_CORE_LIB;
 	}
+}
+
+// rccl, the fourth transport of the sharded prover (sharded_sumcheck.hpp), for ranks that do not share a node: the partial stays on
+// the device; ONE collective per round, ncclAllGather of the rank's 32 bytes on the context's stream (stream-ordered after the
+// kernels), then the XOR of the partials on the device, its result through the zero-copy mailbox
+class RcclExchange : public RoundExchange {
+public:
+	RcclExchange(bn_ctx *ctx, void *comm, void *d_partial, void *d_gathered, int world)
+	    : ctx_(ctx), comm_(comm), d_partial_(d_partial), d_gathered_(d_gathered), world_(world)
+	{
+	}
+	void *device_partial() const override { return d_partial_; }
+	std::vector<B128> combine(const std::vector<B128> &) override
+	{
+		if (g_rccl.all_gather(d_partial_, d_gathered_, 32, kNcclUint8, comm_, stream()) != 0) throw Error(Error::DeviceError, "ncclAllGather failed");
+		bn_f128 ev[2];
+		check(bn_xor_reduce(ctx_, d_gathered_, (uint32_t)world_, 2, ev));
+		return from_raw(ev, 2);
+	}
+	// one ncclAllGather per multilinear (16 bytes per rank) rebuilds the residual multilinears in device scratch
+	std::vector<FSlice> gather_residual(ComputeLayer &, DeviceBumpAllocator &dev_alloc, const std::vector<FSlice> &finals) override
+	{
+		void *s = stream(); // flushes the deferred last fold
+		std::vector<FSliceMut> res;
+		for (size_t j = 0; j < finals.size(); j++) res.push_back(dev_alloc.alloc((size_t)world_));
+		for (size_t j = 0; j < finals.size(); j++)
+			if (g_rccl.all_gather(finals[j].ptr, res[j].ptr, 16, kNcclUint8, comm_, s) != 0)
+				throw Error(Error::DeviceError, "ncclAllGather (residual multilinears) failed");
+		std::vector<FSlice> out;
+		for (const auto &r : res) out.push_back(ComputeMemory::as_const(r));
+		return out;
+	}
+
+private:
+	void *stream() const
+	{
+		void *s = nullptr;
+		check(bn_ctx_get_stream(ctx_, &s));
+		return s;
+	}
+	bn_ctx *ctx_;
+	void *comm_, *d_partial_, *d_gathered_;
+	int world_;
+};
+
+// the transport of one sharded prove, by what the caller passed: the peer mailboxes, else the shared-memory segment, else the RCCL
+// communicator, else the reduce callback
+std::unique_ptr<RoundExchange> choose_exchange(bn_ctx *ctx, bool peer, void *shm, void *rccl_comm, bnh_round_reduce_fn reduce, void *reduce_user,
+                                               void *d_partial, void *d_gathered, int world)
+{
+	if (peer) return std::make_unique<PeerExchange>(ctx, shm, world);
+	if (shm) return std::make_unique<ShmExchange>(ctx, shm, world);
+	if (rccl_comm) return std::make_unique<RcclExchange>(ctx, rccl_comm, d_partial, d_gathered, world);
+	return std::make_unique<CallbackExchange>(reduce, reduce_user, d_partial);
 }
 } // namespace
 
@@ -353,35 +408,17 @@ int bnh_shm_allgather(void *hv, const uint64_t *in, uint32_t n_words, uint64_t *
 //   challenges[n_vars]  stand-in for the Fiat-Shamir transcript
 //   round_coeffs_out    3 per round ; final_evals_out m
 //   reduce              NULL on a single GPU
+// With a transport (reduce, rccl_comm, shm, or the peer bit of tail_rounds) this rank proves its shard of a world's instance
+// (sharded_sumcheck.hpp): the round evaluations pass through the exchange, and the residual rounds run inside this call when asked.
 int bnh_bivariate_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t m, const void *const *d_multilins, void *d_scratch,
                                  uint64_t scratch_elems, uint32_t n_comps, const uint32_t *comp_indices, const bn_f128 *sums,
                                  const bn_f128 *batch_coeff, const bn_f128 *challenges, bn_f128 *round_coeffs_out,
                                  bn_f128 *final_evals_out, bnh_round_reduce_fn reduce, void *reduce_user, void *d_partial,
                                  void *rccl_comm, int world, void *d_gathered, void *shm, int tail_rounds)
 {
-	// tail_rounds: bit 0 = run the residual rounds inside this call; bit 1 = "peer" exchange: the ranks' partial round
-	// evaluations are XORed on the devices, inside the kernels' finalize step (bn_peer_*; the context must be connected),
-	// and the host sees the global (y_1, y_inf) in its own mailbox -- `shm` then only carries the one-off rebuild of the
-	// residual instance
-	const bool peer = (tail_rounds & 2) != 0;
-	tail_rounds &= 1;
-	struct peer_scope { // local rounds reduced, everything else local
-		bn_ctx *c;
-		bool on = false;
-		void set(bool v)
-		{
-			if (v != on) {
-				if (bn_peer_set_active(c, v ? 1 : 0) != 0) throw Error(Error::DeviceError, bn_last_error());
-				on = v;
-			}
-		}
-		~peer_scope()
-		{
-			if (on) (void)bn_peer_set_active(c, 0);
-			(void)bn_host_tail_allow_peer(c, 0);
-		}
-	} peer_guard{ctx};
-	return guarded([&]() -> int {
+	// tail_rounds: bit 0 = run the residual rounds inside this call; bit 1 = the "peer" exchange
+	const bool residual_rounds = (tail_rounds & 1) != 0, peer = (tail_rounds & 2) != 0;
+	const int rc = guarded([&]() -> int {
 		ComputeLayer hal(ctx);
 		DeviceBumpAllocator dev_alloc(FSliceMut{d_scratch, (size_t)scratch_elems});
 		std::vector<B128> host_mem(m + 4);
@@ -392,8 +429,7 @@ int bnh_bivariate_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t m, const
 		const std::vector<B128> sv = from_raw(sums, n_comps);
 		const B128 bc = from_raw(*batch_coeff);
 		if (!reduce && !rccl_comm && !shm && !peer) {
-			const auto t_prof = std::chrono::steady_clock::now();
-			if (AbiProf::on()) AbiProf::get() = AbiProf{};
+			const AbiProfSpan prof;
 			BivariateSumcheckProver prover(hal, dev_alloc, host_alloc, n_vars, comps, sv, mls);
 			for (uint32_t r = 0; r < n_vars; r++) {
 				std::vector<B128> rc = prover.execute(bc);
@@ -401,194 +437,28 @@ int bnh_bivariate_sumcheck_prove(bn_ctx *ctx, uint32_t n_vars, uint32_t m, const
 				prover.fold(from_raw(challenges[r]));
 			}
 			to_raw(prover.finish(), final_evals_out);
-			if (AbiProf::on()) { // BNH_PROF=1: where the wall time of this prove went (us): inside the C ABI by kind of call, and the rest
-				const AbiProf &p = AbiProf::get();
-				const double tot = 1e3 * elapsed_ms(t_prof);
-				fprintf(stderr, "[bnh prof] n_vars %u: total %.2f us; kernel_launch %.2f (%llu calls), extrapolate_line %.2f (%llu), copies %.2f (%llu); outside the ABI %.2f\n",
-				        n_vars, tot, p.ns[0] / 1e3, (unsigned long long)p.calls[0], p.ns[1] / 1e3, (unsigned long long)p.calls[1], p.ns[2] / 1e3,
-				        (unsigned long long)p.calls[2], tot - (p.ns[0] + p.ns[1] + p.ns[2]) / 1e3);
-			}
+			prof.report(n_vars);
 			return 0;
 		}
-		// sharded variant: same state machine, round evals combined across ranks by `reduce`
-		std::vector<ExprEval> evaluators;
-		for (const auto &c : comps) evaluators.push_back(hal.compile_expr(c.expression()));
-		std::vector<FSliceMut> cur;
-		for (const auto &ml : mls) cur.push_back(ComputeMemory::to_mut(ml));
-		bool pre_fold = true;
-		B128 running = evaluate_univariate(sv, bc);
-		const std::vector<B128> coeffs = powers(bc, n_comps);
-		// `n_rounds` rounds on the arrays in `cur` (2^n_rounds elements each); exchange: combine the
-		// ranks' partial round evaluations (local rounds) or not (residual rounds, identical everywhere)
-		// peer exchange + host tail: from the launch after which the library holds the arrays on the host (bn_host_tail_active)
-		// the rounds' LOCAL partial sums come back from host arithmetic and meet in the shared-memory segment instead
-		bool host_rounds = false;
-		auto do_rounds = [&](uint32_t n_rounds, bool exchange, const bn_f128 *ch, bn_f128 *coeffs_out) {
-		for (uint32_t r = 0; r < n_rounds; r++) {
-			const size_t rem = n_rounds - r, split = rem - 1;
-			std::vector<KernelMemMap> maps;
-			for (auto &ml : cur) {
-				auto h = ComputeMemory::split_half(ComputeMemory::as_const(ml));
-				maps.push_back(KernelMemMap::chunked(h.first, 0));
-				maps.push_back(KernelMemMap::chunked(h.second, 0));
-				maps.push_back(KernelMemMap::local(split));
-			}
-			bn_f128 ev[2];
-			if (shm || !exchange) {
-				// device side identical to the single-GPU round (result through the mailbox); the
-				// partials of the ranks are combined in host shared memory
-				std::vector<FSlice> cmls;
-				for (auto &ml : cur) cmls.push_back(ComputeMemory::as_const(ml));
-				const std::vector<B128> part = calculate_round_evals(hal, rem, bc, cmls, evaluators);
-				const uint64_t mine[4] = {part[0].raw().lo, part[0].raw().hi, part[1].raw().lo, part[1].raw().hi};
-				std::vector<uint64_t> all((size_t)4 * world);
-				const bool via_shm = exchange && (!peer || host_rounds);
-				const int n_src = via_shm ? world : 1;
-				if (via_shm) {
-					if (bnh_shm_allgather(shm, mine, 4, all.data())) throw Error(Error::DeviceError, g_err);
-				} else {
-					for (int i = 0; i < 4; i++) all[i] = mine[i];
-				}
-				if (exchange && peer && !host_rounds) {
-					int active = 0;
-					check(bn_host_tail_active(ctx, &active));
-					if (active) { // (every rank sees this after the same launch: the shards have the same size)
-						host_rounds = true;
-						peer_guard.set(false);
-					}
-				}
-				ev[0] = bn_f128{0, 0};
-				ev[1] = bn_f128{0, 0};
-				for (int w = 0; w < n_src; w++) {
-					ev[0].lo ^= all[4 * w + 0];
-					ev[0].hi ^= all[4 * w + 1];
-					ev[1].lo ^= all[4 * w + 2];
-					ev[1].hi ^= all[4 * w + 3];
-				}
-			} else {
-				hal.execute([&](ComputeLayerExecutor &exec) {
-					exec.accumulate_kernels_to_device(
-					    [&](KernelExecutor &ke, size_t log_chunks, std::vector<KernelBuffer> &b) {
-						    const size_t lcs = split - log_chunks;
-						    KernelValue a1 = ke.decl_value(B128::ZERO());
-						    std::vector<KSlice> rows;
-						    for (uint32_t i = 0; i < m; i++) rows.push_back(b[3 * i + 1].to_ref());
-						    SlicesBatch<KSlice> e1(rows, (size_t)1 << lcs);
-						    for (uint32_t c = 0; c < n_comps; c++) ke.sum_composition_evals(e1, evaluators[c], coeffs[c], a1);
-						    for (uint32_t i = 0; i < m; i++) ke.add(lcs, b[3 * i].to_ref(), b[3 * i + 1].to_ref(), b[3 * i + 2].as_mut());
-						    KernelValue ai = ke.decl_value(B128::ZERO());
-						    rows.clear();
-						    for (uint32_t i = 0; i < m; i++) rows.push_back(b[3 * i + 2].to_ref());
-						    SlicesBatch<KSlice> ei(rows, (size_t)1 << lcs);
-						    for (uint32_t c = 0; c < n_comps; c++) ke.sum_composition_evals(ei, evaluators[c], coeffs[c], ai);
-						    return std::vector<KernelValue>{a1, ai};
-					    },
-					    maps, d_partial);
-					return std::vector<B128>{};
-				});
-				if (rccl_comm) {
-					// ONE RCCL collective per round: all_gather of this rank's 32-byte partial on the
-					// context's stream (stream-ordered after the kernels), then XOR of the G partials
-					void *stream = nullptr;
-					check(bn_ctx_get_stream(ctx, &stream));
-					if (g_rccl.all_gather(d_partial, d_gathered, 32, kNcclUint8, rccl_comm, stream) != 0)
-						throw Error(Error::DeviceError, "ncclAllGather failed");
-					// XOR of the G partials on the device, result through the zero-copy mailbox
-					check(bn_xor_reduce(ctx, d_gathered, (uint32_t)world, 2, ev));
-				} else if (reduce(reduce_user, d_partial, ev)) {
-					throw Error(Error::CoreLibError, "round reduce callback failed");
-				}
-			}
-			std::vector<B128> rc = calculate_round_coeffs_from_evals(running, from_raw(ev, 2));
-			to_raw(rc, coeffs_out + 3 * r);
-			const B128 z = from_raw(ch[r]);
-			running = evaluate_univariate(rc, z);
-			struct FoldArgs {
-				FSliceMut evals_0;
-				FSlice evals_1;
-			};
-			std::vector<FoldArgs> prepared;
-			for (auto &ml : cur) {
-				auto h = ComputeMemory::split_half_mut(ml);
-				FSliceMut e0 = h.first;
-				if (pre_fold) {
-					e0 = dev_alloc.alloc(h.first.len_);
-					hal.copy_d2d(ComputeMemory::as_const(h.first), e0);
-				}
-				prepared.push_back(FoldArgs{e0, ComputeMemory::as_const(h.second)});
-				ml = e0;
-			}
-			// one `map` scope over the multilinears (v3/bivariate_product.rs:217-228): one fold batch,
-			// which the ABI runs together with the next round's evaluation
-			hal.execute([&](ComputeLayerExecutor &exec) {
-				exec.map(prepared.begin(), prepared.end(), [&](ComputeLayerExecutor &e, FoldArgs &a) {
-					e.extrapolate_line(a.evals_0, a.evals_1, z);
-					return 0;
-				});
-				return std::vector<B128>{};
-			});
-			pre_fold = false;
+		ShardedBivariateSumcheckProver prover(hal, dev_alloc, host_alloc, n_vars, comps, sv, mls, [&] {
+			return choose_exchange(ctx, peer, shm, rccl_comm, reduce, reduce_user, d_partial, d_gathered, world);
+		});
+		for (uint32_t r = 0; r < n_vars; r++) {
+			to_raw(prover.execute(bc), round_coeffs_out + 3 * r);
+			prover.fold(from_raw(challenges[r]));
 		}
-		};
-		if (peer) {
-			if (!shm) throw Error(Error::InputValidation, "the peer exchange needs the shared-memory segment for the residual instance");
-			check(bn_host_tail_allow_peer(ctx, 1)); // (the host rounds' partials are exchanged here, through the segment)
-			peer_guard.set(true);
-		}
-		do_rounds(n_vars, true, challenges, round_coeffs_out);
-		peer_guard.set(false);
 		uint32_t log_world = 0;
 		while ((1 << (log_world + 1)) <= world) log_world++;
-		if (rccl_comm && !shm && tail_rounds && log_world > 0) {
-			// ---- residual rounds, RCCL transport: every rank is down to one element per multilinear on the
-			// device.  One ncclAllGather per multilinear (16 bytes per rank, on the context's stream) rebuilds
-			// the residual multilinears of `world` elements (index = rank) in device memory; the last
-			// log2(world) rounds run on them, identically on every rank, with no further exchange.
-			void *stream = nullptr;
-			check(bn_ctx_get_stream(ctx, &stream)); // flushes the deferred last fold
-			std::vector<FSliceMut> res;
-			for (uint32_t j = 0; j < m; j++) res.push_back(dev_alloc.alloc((size_t)world));
-			for (uint32_t j = 0; j < m; j++)
-				if (g_rccl.all_gather(cur[j].ptr, res[j].ptr, 16, kNcclUint8, rccl_comm, stream) != 0)
-					throw Error(Error::DeviceError, "ncclAllGather (residual multilinears) failed");
-			for (uint32_t j = 0; j < m; j++) cur[j] = res[j];
-			pre_fold = true; // fold into fresh scratch, as in the first local round
-			do_rounds(log_world, false, challenges + n_vars, round_coeffs_out + 3 * n_vars);
-		} else if (shm && tail_rounds && log_world > 0) {
-			// ---- residual rounds: every rank is down to one element per multilinear.  One exchange of
-			// the m local finals rebuilds the m residual multilinears of `world` elements (index = rank)
-			// in pinned, device-visible host memory (no upload); the last log2(world) rounds run on them.
-			std::vector<B128> fin(m);
-			for (uint32_t j = 0; j < m; j++) hal.copy_d2h(ComputeMemory::as_const(cur[j]), &fin[j], 1);
-			void *h_scr = nullptr, *d_scr = nullptr;
-			uint64_t scr_elems = 0;
-			check(bn_host_scratch(ctx, &h_scr, &d_scr, &scr_elems));
-			if ((uint64_t)m * world > scr_elems) throw Error(Error::InputValidation, "residual instance does not fit the pinned scratch");
-			bn_f128 *res = (bn_f128 *)h_scr;
-			for (uint32_t j0 = 0; j0 < m; j0 += 3) {
-				const uint32_t nj = (m - j0) < 3 ? (m - j0) : 3;
-				uint64_t mine[6];
-				for (uint32_t j = 0; j < nj; j++) {
-					mine[2 * j] = fin[j0 + j].raw().lo;
-					mine[2 * j + 1] = fin[j0 + j].raw().hi;
-				}
-				std::vector<uint64_t> all((size_t)2 * nj * world);
-				if (bnh_shm_allgather(shm, mine, 2 * nj, all.data())) throw Error(Error::DeviceError, g_err);
-				for (int w = 0; w < world; w++)
-					for (uint32_t j = 0; j < nj; j++) res[(size_t)(j0 + j) * world + w] = bn_f128{all[(size_t)w * 2 * nj + 2 * j], all[(size_t)w * 2 * nj + 2 * j + 1]};
-			}
-			std::atomic_thread_fence(std::memory_order_seq_cst);
-			for (uint32_t j = 0; j < m; j++) cur[j] = FSliceMut{(char *)d_scr + (size_t)j * world * sizeof(bn_f128), (size_t)world};
-			pre_fold = true; // the pinned inputs are read-only: fold into device scratch
-			do_rounds(log_world, false, challenges + n_vars, round_coeffs_out + 3 * n_vars);
+		if (residual_rounds && log_world > 0) {
+			bn_f128 *out = round_coeffs_out + 3 * n_vars;
+			for (const auto &rc : prover.run_residual(bc, from_raw(challenges + n_vars, log_world))) out = to_raw(rc, out);
 		}
-		for (uint32_t j = 0; j < m; j++) {
-			B128 v;
-			hal.copy_d2h(ComputeMemory::as_const(cur[j]), &v, 1);
-			final_evals_out[j] = v.raw();
-		}
+		to_raw(prover.finish(), final_evals_out);
 		return 0;
 	});
+	// every route has always left the host-tail permission cleared on every exit; the peer exchange clears its own
+	if (!peer) (void)bn_host_tail_allow_peer(ctx, 0);
+	return rc;
 }
 
 static thread_local int g_mlecheck_mode = -1;

@@ -4,6 +4,7 @@
 //   ops::eq_ind_partial_eval       crates/compute/src/ops.rs:26-50
 //   calculate_round_evals          crates/core/src/protocols/sumcheck/v3/bivariate_product.rs:303-408
 //   (with eq_ind)                  crates/core/src/protocols/sumcheck/v3/bivariate_mlecheck.rs:391-520
+//   (result left on the device)    calculate_round_evals_to_device, for the sharded prover of sharded_sumcheck.hpp
 //   round coeffs from evals        v3/bivariate_product.rs:410-424
 //   BivariateRoundCore             what the three provers below share: the sum / coefficient state, the fold of the
 //                                  multilinears, the copy-out of the final evaluations
@@ -69,10 +70,11 @@ inline FSliceMut eq_ind_partial_eval(ComputeLayer &hal, DeviceBumpAllocator &dev
 }
 } // namespace ops
 
-// calculate_round_evals: returns {y_1, y_inf}.  eq_ind (optional) is appended as the last
-// composition variable, as the MLE-check prover does.
-inline std::vector<B128> calculate_round_evals(ComputeLayer &hal, size_t n_vars, B128 batch_coeff, const std::vector<FSlice> &multilins,
-                                               const std::vector<ExprEval> &prod_evaluators, const FSlice *eq_ind = nullptr)
+// One round evaluation: the memory maps and the kernel (sum at 1, extrapolation, sum at infinity) of calculate_round_evals.
+// {y_1, y_inf} come back through the host's mailbox (d_out null: accumulate_kernels) or stay on the device in d_out[0..1]
+// (accumulate_kernels_to_device; nothing is returned).
+inline std::vector<B128> launch_round_evals(ComputeLayer &hal, size_t n_vars, B128 batch_coeff, const std::vector<FSlice> &multilins,
+                                            const std::vector<ExprEval> &prod_evaluators, const FSlice *eq_ind, void *d_out)
 {
 	const size_t split_n_vars = n_vars - 1;
 	std::vector<KernelMemMap> kernel_mappings;
@@ -86,36 +88,51 @@ inline std::vector<B128> calculate_round_evals(ComputeLayer &hal, size_t n_vars,
 	const std::vector<B128> batch_coeffs = powers(batch_coeff, prod_evaluators.size());
 	const size_t m = multilins.size();
 
+	const auto kernel = [&](KernelExecutor &local_exec, size_t log_chunks, std::vector<KernelBuffer> &buffers) {
+		const size_t log_chunk_size = split_n_vars - log_chunks;
+		// composite evaluations at ONE
+		KernelValue acc_1 = local_exec.decl_value(B128::ZERO());
+		{
+			std::vector<KSlice> rows;
+			for (size_t i = 0; i < m; i++) rows.push_back(buffers[i * 3 + 1].to_ref());
+			if (eq_ind) rows.push_back(buffers.back().to_ref());
+			SlicesBatch<KSlice> eval_1s(rows, (size_t)1 << log_chunk_size);
+			for (size_t c = 0; c < prod_evaluators.size(); c++)
+				local_exec.sum_composition_evals(eval_1s, prod_evaluators[c], batch_coeffs[c], acc_1);
+		}
+		// extrapolate to the point at infinity: evals_inf = evals_0 + evals_1
+		for (size_t i = 0; i < m; i++)
+			local_exec.add(log_chunk_size, buffers[3 * i].to_ref(), buffers[3 * i + 1].to_ref(), buffers[3 * i + 2].as_mut());
+		KernelValue acc_inf = local_exec.decl_value(B128::ZERO());
+		{
+			std::vector<KSlice> rows;
+			for (size_t i = 0; i < m; i++) rows.push_back(buffers[i * 3 + 2].to_ref());
+			if (eq_ind) rows.push_back(buffers.back().to_ref());
+			SlicesBatch<KSlice> eval_infs(rows, (size_t)1 << log_chunk_size);
+			for (size_t c = 0; c < prod_evaluators.size(); c++)
+				local_exec.sum_composition_evals(eval_infs, prod_evaluators[c], batch_coeffs[c], acc_inf);
+		}
+		return std::vector<KernelValue>{acc_1, acc_inf};
+	};
 	return hal.execute([&](ComputeLayerExecutor &exec) {
-		return exec.accumulate_kernels(
-		    [&](KernelExecutor &local_exec, size_t log_chunks, std::vector<KernelBuffer> &buffers) {
-			    const size_t log_chunk_size = split_n_vars - log_chunks;
-			    // composite evaluations at ONE
-			    KernelValue acc_1 = local_exec.decl_value(B128::ZERO());
-			    {
-				    std::vector<KSlice> rows;
-				    for (size_t i = 0; i < m; i++) rows.push_back(buffers[i * 3 + 1].to_ref());
-				    if (eq_ind) rows.push_back(buffers.back().to_ref());
-				    SlicesBatch<KSlice> eval_1s(rows, (size_t)1 << log_chunk_size);
-				    for (size_t c = 0; c < prod_evaluators.size(); c++)
-					    local_exec.sum_composition_evals(eval_1s, prod_evaluators[c], batch_coeffs[c], acc_1);
-			    }
-			    // extrapolate to the point at infinity: evals_inf = evals_0 + evals_1
-			    for (size_t i = 0; i < m; i++)
-				    local_exec.add(log_chunk_size, buffers[3 * i].to_ref(), buffers[3 * i + 1].to_ref(), buffers[3 * i + 2].as_mut());
-			    KernelValue acc_inf = local_exec.decl_value(B128::ZERO());
-			    {
-				    std::vector<KSlice> rows;
-				    for (size_t i = 0; i < m; i++) rows.push_back(buffers[i * 3 + 2].to_ref());
-				    if (eq_ind) rows.push_back(buffers.back().to_ref());
-				    SlicesBatch<KSlice> eval_infs(rows, (size_t)1 << log_chunk_size);
-				    for (size_t c = 0; c < prod_evaluators.size(); c++)
-					    local_exec.sum_composition_evals(eval_infs, prod_evaluators[c], batch_coeffs[c], acc_inf);
-			    }
-			    return std::vector<KernelValue>{acc_1, acc_inf};
-		    },
-		    kernel_mappings);
+		if (!d_out) return exec.accumulate_kernels(kernel, kernel_mappings);
+		exec.accumulate_kernels_to_device(kernel, kernel_mappings, d_out);
+		return std::vector<B128>{};
 	});
+}
+
+// calculate_round_evals: returns {y_1, y_inf}.  eq_ind (optional) is appended as the last
+// composition variable, as the MLE-check prover does.
+inline std::vector<B128> calculate_round_evals(ComputeLayer &hal, size_t n_vars, B128 batch_coeff, const std::vector<FSlice> &multilins,
+                                               const std::vector<ExprEval> &prod_evaluators, const FSlice *eq_ind = nullptr)
+{
+	return launch_round_evals(hal, n_vars, batch_coeff, multilins, prod_evaluators, eq_ind, nullptr);
+}
+// the same round with {y_1, y_inf} left on the device in d_out[0..1], stream-ordered and unread (sharded_sumcheck.hpp)
+inline void calculate_round_evals_to_device(ComputeLayer &hal, size_t n_vars, B128 batch_coeff, const std::vector<FSlice> &multilins,
+                                            const std::vector<ExprEval> &prod_evaluators, void *d_out)
+{
+	launch_round_evals(hal, n_vars, batch_coeff, multilins, prod_evaluators, nullptr, d_out);
 }
 
 // RoundCoeffs c0, c1, c2 from (sum, y_1, y_inf) (v3/bivariate_product.rs:410-424)
@@ -249,6 +266,16 @@ protected:
 			return std::vector<B128>{};
 		});
 		n_vars_remaining_ -= 1;
+	}
+
+	// Between two rounds: go on over other arrays of 2^n_vars elements each, read-only until their first fold; the batched sum
+	// carries over (the sharded prover's residual instance)
+	void reseat(size_t n_vars, const std::vector<FSlice> &multilins)
+	{
+		if (state_ == Coeffs) throw SumcheckError("ExpectedFold");
+		multilins_.clear();
+		for (const auto &ml : multilins) multilins_.push_back(Multilin{true, ComputeMemory::to_mut(ml)});
+		n_vars_remaining_ = n_vars;
 	}
 
 	// the single element every multilinear has come down to
